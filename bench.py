@@ -20,17 +20,27 @@ N > 1 (one process per GPU, RCCL backend): either under a launcher (`python -m t
 every rank evaluates its contiguous ceil(N/G)-row shard of the ONE rig the config names (the reference's
 equal-chunk rule incl. cyclic padding, abstract_function_blocks.py:281-288; `pycamset_amd.sharding.padded_shard`),
 all ranks hold the same parameter string, and the timed region contains no collective: the path partitions by
-observation.  `value` = rows of the whole rig x steps / max-over-ranks time.  Two more step times are
-measured outside that region and reported under "multi_gpu": step + RCCL all-gather of the residual / Jacobian
+observation.  `value` = rows of the whole rig x steps / max-over-ranks time.  With --full, two more step times
+are measured outside that region and reported under "multi_gpu": step + RCCL all-gather of the residual / Jacobian
 blocks (what a host-side consumer of J needs; xGMI-link-bound) and normal-equations build + ONE all-reduce of the
 packed [J^T J, J^T r, cost] (what a device-side LM step needs).  `--scaling weak` gives every rank an independent
 rig of the same shape instead (seed + 1000 r).
 
-Kernel time for the roofline figure: after the wall-clock region, >= 20 extra launches carry HIP start/stop
+A plain run does what the headline needs: set-up, device warm-up (with the write-rate fill, whose figure only --full
+reports), W warm-up steps, the K timed steps, the outputs (--dump-outputs DIR) and the line.  Everything else runs
+only with --full: the roofline (below), the multi-GPU collective probes, the normal-equations probe, the device LM
+solve of configs 2 / 3 and the CPU baseline.
+
+Kernel time for the roofline figure (--full): after the wall-clock region, >= 20 extra launches carry HIP start/stop
 events (hipExtLaunchKernelGGL on the launch stream); mean / median / min are reported, the mean is what
 `roofline.achieved` uses.  The timed region itself runs without events, so they cannot perturb `value`.
 
-Rank 0 prints ONE JSON line (schema: task contract + "roofline" + "cpu_baseline").
+--dump-outputs DIR: what the last timed step computed, written before anything else touches the output buffers:
+residual.npy (N, 2) and jacobian.npy (2 N, P) in the step's float type, for a fixed seeded sample of detections when
+the whole is larger than DUMP_BYTES (detection_index.npy holds the sample).  Inputs are seeded: two builds given the
+same arguments can be compared array for array.
+
+Rank 0 prints ONE JSON line (schema: task contract; with --full also "roofline" + "cpu_baseline").
 """
 from __future__ import annotations
 
@@ -55,6 +65,8 @@ HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s me
 CONFIG_CHAIN = {1: "template", 2: "template", 3: "template", 4: "self", 5: "template"}
 CONFIG_DTYPE = {1: "f64", 2: "f64", 3: "f64", 4: "f64", 5: "f32"}
 KERNEL_SAMPLES = 24     # event-timed launches after the wall-clock region (>= 20)
+DUMP_BYTES = 48 << 20   # --dump-outputs: residual + Jacobian rows written per rank (the whole dump stays below 64 MB)
+DUMP_SEED = 0
 
 
 def chain_slabs(rig, chain):
@@ -252,6 +264,29 @@ def pmc_traffic(workload_key: str):
     return None, None
 
 
+def dump_outputs(out_dir, resid, jac, suffix: str = "") -> dict:
+    """--dump-outputs: what a caller of the step receives, residual (N, 2) and Jacobian (2 N, P), as .npy in the step's own
+    float type.  Above DUMP_BYTES, a fixed seeded sample of detections (sorted; both Jacobian rows of each), whose indices go
+    to detection_index.npy (float64: exact below 2**53).  -> {name: shape}"""
+    import torch
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    n, P = resid.shape[0], jac.shape[1]
+    per_det = (2 + 2 * P) * resid.element_size() + 8
+    if n * per_det <= DUMP_BYTES:
+        idx = np.arange(n)
+        r, j = resid, jac
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_BYTES // per_det, replace=False))
+        r = resid.index_select(0, torch.from_numpy(idx).to(resid.device))
+        j = jac.view(n, 2, P).index_select(0, torch.from_numpy(idx).to(jac.device)).reshape(-1, P)
+    arrays = {"residual": r.cpu().numpy(), "jacobian": j.cpu().numpy(), "detection_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}{suffix}.npy", a)
+    return {f"{name}{suffix}": list(a.shape) for name, a in arrays.items()}
+
+
 def self_launch(n_ranks: int, argv, script=None, python=None, extra_env=None) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILDREN
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py argv`),
@@ -271,19 +306,25 @@ def self_launch(n_ranks: int, argv, script=None, python=None, extra_env=None) ->
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(script or Path(__file__).resolve()), *argv]
     print("[bench] self-launch: " + " ".join(cmd), file=sys.stderr, flush=True)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, env=env)
+    decoder = json.JSONDecoder()
     for raw in proc.stdout:
         txt = raw.rstrip("\n")
-        # rank 0's JSON object, also when another rank's (or a library's) unterminated output shares its line: the ranks write to ONE pipe
-        is_line = False
+        # rank 0's JSON object, also when another rank's (or a library's) output shares its line: the ranks write to ONE pipe,
+        # and an unbuffered child writes the object and its newline separately, so other text may come before or after it
+        is_line, end = False, 0
         at = txt.find('{"')
         if at >= 0:
             try:
-                is_line = isinstance(json.loads(txt[at:]), dict)
+                obj, end = decoder.raw_decode(txt, at)
+                is_line = isinstance(obj, dict)
             except ValueError:
                 pass
-        if is_line and at > 0:
-            print(txt[:at], file=sys.stderr, flush=True)
-            txt = txt[at:]
+        if is_line:
+            if at > 0:
+                print(txt[:at], file=sys.stderr, flush=True)
+            if txt[end:].strip():
+                print(txt[end:], file=sys.stderr, flush=True)
+            txt = txt[at:end]
         print(txt, file=sys.stdout if is_line else sys.stderr, flush=True)
     return proc.wait()
 
@@ -321,7 +362,16 @@ def main():
     ap.add_argument("--host-path", action="store_true",
                     help="also time the host-buffer boundary (pcs_eval: H2D params + kernels + D2H of residual and Jacobian); "
                          "reported under 'host_boundary', never in 'value'")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: roofline (event-timed kernels, write-rate fill figure, PMC traffic), multi-GPU "
+                         "collective probes, normal-equations probe, device LM solve, CPU baseline.  Off: set up, warm up, time "
+                         "the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (residual, Jacobian rows; a fixed seeded "
+                         f"sample of detections when the whole exceeds {DUMP_BYTES >> 20} MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -385,7 +435,7 @@ def main():
     # equal block sizes for the all-gather (strong: already equal; weak: pad to the largest rank)
     per = int(reduce_scalar(float(N), dist.ReduceOp.MAX)) if world > 1 else N
     n_total = prob["n_total"] if prob["n_total"] is not None else int(reduce_scalar(float(prob["n_real"]), dist.ReduceOp.SUM))
-    want_gather = world > 1 and (args.collective == "allgather" or not args.no_allgather_probe)
+    want_gather = world > 1 and (args.collective == "allgather" or (args.full and not args.no_allgather_probe))
     if want_gather:
         send_r = d_r if per == N else torch.zeros((per, 2), dtype=tdt, device=dev)
         send_j = d_j if per == N else torch.zeros((2 * per, P), dtype=tdt, device=dev)
@@ -408,9 +458,11 @@ def main():
 
         streamer = JacobianHostStreamer(eng, N, device=local_rank, first_device_buffer=d_j)
 
+    last_host = [None]   # --stream-to-host: the host buffer that receives the Jacobian of the latest step
+
     def step():
         if streamer is not None:
-            streamer.step(d_p.data_ptr(), d_r.data_ptr())
+            last_host[0] = streamer.step(d_p.data_ptr(), d_r.data_ptr())
             return
         eng.eval_device_resident(d_p.data_ptr(), d_r.data_ptr(), d_j.data_ptr(), stream)
         if use_gather_in_step:
@@ -464,7 +516,8 @@ def main():
             torch.cuda.synchronize(dev)
 
     # the part's sustained write rate TODAY, in the fused kernel's store shape (non-temporal 16-byte stores, whole chunks per wave),
-    # back to back like the steps: boxes of this pool differ by 20 % in it (4.5-5.6 TB/s), and it is the bound of this path
+    # back to back like the steps: boxes of this pool differ by 20 % in it (4.5-5.6 TB/s), and it is the bound of this path.
+    # It runs in a plain run too (the timed region has always followed these 50 fills); the figure is reported with --full.
     nt_fill_GBps = None
     try:
         from pycamset_amd import _capi
@@ -486,22 +539,33 @@ def main():
     sec_per_step = timed(step, args.steps, bracket=True)
     elapsed = sec_per_step * args.steps
 
+    # ---- what the last timed step computed, before anything else writes the output buffers --------------------------
+    dumped = None
+    if args.dump_outputs:
+        jac = streamer.wait(last_host[0]) if streamer is not None else d_j
+        dumped = dump_outputs(args.dump_outputs, d_r, jac, f"_rank{rank}" if world > 1 else "")
+        if streamer is not None:
+            streamer.release(last_host[0])
+
     # ---- kernel durations: >= 20 extra launches with start/stop events, outside the wall-clock region ------------
-    eng.set_option("timing_every", 1)
-    eng.set_option("event_ring", KERNEL_SAMPLES)
-    for _ in range(2 * KERNEL_SAMPLES):   # the first batch only switches the queue to timed dispatches (its launches run 5-10 % long); the ring keeps the second
-        eng.eval_device_resident(d_p.data_ptr(), d_r.data_ptr(), d_j.data_ptr(), stream)
-    torch.cuda.synchronize(dev)
-    prep_s, eval_s = eng.kernel_ms_samples(KERNEL_SAMPLES)
-    eng.set_option("timing_every", 0)
-    iso_ms, prep_ms = float(np.mean(eval_s)), float(np.mean(prep_s))
-    # The kernel's average duration OVER THE TIMED REGION: the GPU time between two events that bracket the K steps on the launch
-    # stream, per step, minus slab_prep's own duration where a step has that second launch.  It contains the ~1-3 us between
-    # consecutive launches — an upper bound of the kernel's duration, and the figure that agrees with `rocprofv3 --stats` of
-    # this command.  The launches that carry their own start / stop events (`kernel_ms_isolated*`, after the region) follow a
-    # timed dispatch's ~12 us gap, find the memory system drained and run 4-9 % faster: reported, not used for `frac`.
-    in_region = region_gpu_ms[0] is not None and streamer is None and not use_gather_in_step
-    eval_ms = max(region_gpu_ms[0] - prep_ms, 0.0) if in_region else iso_ms
+    prep_ms = eval_ms = iso_ms = eval_s = None
+    in_region = False
+    if args.full:
+        eng.set_option("timing_every", 1)
+        eng.set_option("event_ring", KERNEL_SAMPLES)
+        for _ in range(2 * KERNEL_SAMPLES):   # the first batch only switches the queue to timed dispatches (its launches run 5-10 % long); the ring keeps the second
+            eng.eval_device_resident(d_p.data_ptr(), d_r.data_ptr(), d_j.data_ptr(), stream)
+        torch.cuda.synchronize(dev)
+        prep_s, eval_s = eng.kernel_ms_samples(KERNEL_SAMPLES)
+        eng.set_option("timing_every", 0)
+        iso_ms, prep_ms = float(np.mean(eval_s)), float(np.mean(prep_s))
+        # The kernel's average duration OVER THE TIMED REGION: the GPU time between two events that bracket the K steps on the launch
+        # stream, per step, minus slab_prep's own duration where a step has that second launch.  It contains the ~1-3 us between
+        # consecutive launches — an upper bound of the kernel's duration, and the figure that agrees with `rocprofv3 --stats` of
+        # this command.  The launches that carry their own start / stop events (`kernel_ms_isolated*`, after the region) follow a
+        # timed dispatch's ~12 us gap, find the memory system drained and run 4-9 % faster: reported, not used for `frac`.
+        in_region = region_gpu_ms[0] is not None and streamer is None and not use_gather_in_step
+        eval_ms = max(region_gpu_ms[0] - prep_ms, 0.0) if in_region else iso_ms
 
     # ---- multi-GPU extras, outside the timed region --------------------------------------------------------------
     multi = None
@@ -532,7 +596,7 @@ def main():
     normal_info = None
     from pycamset_amd.device_solver import blocked_fits
 
-    if not args.no_normal_probe and blocked_fits(eng):
+    if args.full and not args.no_normal_probe and blocked_fits(eng):
         try:
             npar = eng.n_params
             lay = eng.normal_layout()
@@ -594,9 +658,7 @@ def main():
 
     if rank == 0:
         bpd = BYTES_PER_DET[(chain, dtype)]
-        achieved = N * bpd / (eval_ms * 1e-3) / 1e9
         name = rig.name.split("/")[0]
-        traffic, traffic_source = pmc_traffic(f"{name}/{chain}/{dtype}") if (world == 1 and args.scale == 1.0 and args.emulate_world <= 1) else (None, None)
         in_bytes = 20 if dtype == "f32" else 28
         shard_txt = (f"{n_total} detections" if world == 1 else
                      f"{n_total} detections sharded into contiguous blocks of {per} per GPU" if args.scaling == "strong" else
@@ -616,9 +678,10 @@ def main():
             "data": "synthetic",
             "config": {
                 "workload": f"{name} (BASELINE config {args.config}): {rig.n_cams} cams x {rig.n_imgs} poses x {rig.n_keys} keys, "
-                            f"{shard_txt}, chain {chain}, "
-                            + ("ONE launch per step (fused residual/Jacobian kernel whose waves prepare their slabs)" if prep_ms == 0.0
-                               else "slab_prep + fused residual/Jacobian kernel per step"),
+                            f"{shard_txt}, chain {chain}"
+                            + ("" if prep_ms is None else  # known from the event-timed launches of --full
+                               ", ONE launch per step (fused residual/Jacobian kernel whose waves prepare their slabs)" if prep_ms == 0.0
+                               else ", slab_prep + fused residual/Jacobian kernel per step"),
                 "detections_total": n_total,
                 "detections_per_gpu": N,
                 "rows_per_step": 2.0 * n_total,
@@ -629,7 +692,11 @@ def main():
                 "parallelism": f"obs-shard x{world}",
                 **({"emulated_world": args.emulate_world} if args.emulate_world > 1 and world == 1 else {}),
             },
-            "roofline": {
+        }
+        if args.full:
+            achieved = N * bpd / (eval_ms * 1e-3) / 1e9
+            traffic, traffic_source = pmc_traffic(f"{name}/{chain}/{dtype}") if (world == 1 and args.scale == 1.0 and args.emulate_world <= 1) else (None, None)
+            line["roofline"] = {
                 "bound": "hbm",
                 "achieved": achieved,
                 "peak": HBM_PEAK_GBPS,
@@ -663,13 +730,14 @@ def main():
                 # output's size): the ceiling the write stream of the step is held against
                 "nt_fill_GBps_this_run": nt_fill_GBps,
                 "frac_of_nt_fill_this_run": (N * (bpd - in_bytes) / (eval_ms * 1e-3) / 1e9 / nt_fill_GBps) if nt_fill_GBps else None,
-            },
-        }
+            }
         if args.stream_to_host:
             jb = d_j.numel() * d_j.element_size()
             line["host_stream"] = {"bytes_per_step_per_gpu": jb, "d2h_GBps_per_gpu": jb * args.steps / elapsed / 1e9,
                                    "note": "PCIe-bound: the Jacobian of every step is copied to page-locked host memory "
                                            "(double buffered, overlapped with the next kernel)"}
+        if dumped:
+            line["outputs"] = {"dir": str(args.dump_outputs), "arrays": dumped}
         if multi:
             line["multi_gpu"] = multi
         if normal_info:
@@ -683,13 +751,13 @@ def main():
             line["host_boundary"] = {"ms_per_call": hs * 1e3, "rows_per_s": 2.0 * N / hs,
                                      "d2h_GBps": (2 * N * (P + 1)) * 8 / hs / 1e9,
                                      "note": "Engine.eval: pageable NumPy outputs, PCIe D2H of the dense Jacobian dominates"}
-        if world == 1 and args.scale == 1.0 and args.emulate_world <= 1 and (args.lm_compare or (args.config in (2, 3) and not args.no_normal_probe)):
+        if world == 1 and args.scale == 1.0 and args.emulate_world <= 1 and (args.lm_compare or (args.full and args.config in (2, 3) and not args.no_normal_probe)):
             try:  # a probe: its failure must not cost the bench line
                 cfgs = (2, 3) if args.lm_compare else (args.config,)
                 line["lm_end_to_end"] = {f"config_{c}": lm_end_to_end(c, with_scipy=args.lm_compare, scipy_nfev=8 if c == 2 else 4) for c in cfgs}
             except Exception as exc:  # noqa: BLE001
                 line["lm_end_to_end"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(rig, chain, ps, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:

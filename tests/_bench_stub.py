@@ -17,5 +17,10 @@ if "--fail-rank" in sys.argv and rank == int(sys.argv[sys.argv.index("--fail-ran
     dist.destroy_process_group()
     sys.exit(3)
 if rank == 0:
-    print(json.dumps({"metric": "stub", "n_gpus": world, "sum": float(t.item()), "argv": sys.argv[1:]}), flush=True)
+    line = json.dumps({"metric": "stub", "n_gpus": world, "sum": float(t.item()), "argv": sys.argv[1:]})
+    if "--glued" in sys.argv:   # other ranks' output on both sides of the object, as when unbuffered ranks share the pipe
+        sys.stdout.write(f"noise before {line}noise after\n")
+        sys.stdout.flush()
+    else:
+        print(line, flush=True)
 dist.destroy_process_group()

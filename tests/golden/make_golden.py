@@ -585,16 +585,36 @@ def round4_vectors(mods):
         print(tag, "P", res["block_param_inds"].shape[1], "nnz", res["data_all"].shape, "max |resid|", float(np.max(np.abs(res["resid"]))))
 
 
+PATCH_CASES = [("template", 0), ("self", 0), ("free", 0), ("template", 6), ("self", 6)]
+
+
+def patch_vectors(mods):
+    """What the UNPATCHED reference handlers return on the problems of tests/test_reference_patch.py: 3 cams x 4 images,
+    (6, 9) multi-dimensional keys, camera 1 fully fixed, fixed_pose 0; max_ims = 6 > 4 images makes the pose slab longer
+    than the string the detections index (afb:363) and, in the self chain, mis-offsets the point block (quirk ii)."""
+    rig = synthetic.make_rig("patch", 3, 4, synthetic.ccube_points(4, 40.0), seed=5, visibility=0.7)   # 6 x 9 keys
+    fixed = {"cam_1": {"int": rig.intr[1].copy(), "ext": rig.extr[1].copy()}}
+    for chain, max_ims in PATCH_CASES:
+        res = handler_case(mods, rig, chain, keydims=(6, 9), fixed=fixed, max_ims=max_ims)
+        np.savez_compressed(HERE / f"patch_{chain}_ims{max_ims}.npz", **res)
+        print("patch", chain, max_ims, "J shape", res["shape"], "nnz", res["data"].shape)
+
+
 def main():
     import argparse
 
     import _refload
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["round1", "round2", "round3", "round4", "round5"], default=None, help="regenerate one group of fixtures only")
+    ap.add_argument("--only", choices=["round1", "round2", "round3", "round4", "round5", "patch"], default=None,
+                    help="regenerate one group of fixtures only")
     args = ap.parse_args()
     with _refload.reference_modules() as mods:
         ch, fb, th, sbh, fph, TargetDetection = mods.ch, mods.fb, mods.th, mods.sbh, mods.fph, mods.TargetDetection
+        if args.only in (None, "patch"):
+            patch_vectors(mods)
+        if args.only == "patch":
+            return
         if args.only in (None, "round5"):
             round5_vectors(mods)
         if args.only == "round5":

@@ -1,33 +1,25 @@
-"""The INTEGRATION.md "two-line patch", applied to the reference's REAL handlers (build container only).
+"""The INTEGRATION.md "two-line patch": a handler's ``self.op_fun`` replaced by the adapter of ``pycamset_amd.function_blocks``.
 
-The reference's ``TemplateBundleHandler`` / ``SelfBundleHandler`` / ``FreePointBundleHandler`` are imported from a
-temporary copy of /root/reference (tests/golden/_refload.py), their ``self.op_fun`` (template_handler.py:152,
-standard_bundle_handler.py:182, free_point_handler.py:143) is replaced by the adapter of
-``pycamset_amd.function_blocks`` and the reference's own ``make_loss_fun`` / ``make_loss_jac`` (th:157-193) are driven:
+The handler is ``pycamset_amd.handlers``' restatement of the reference's ``TemplateBundleHandler`` / ``SelfBundleHandler`` /
+``FreePointBundleHandler``, rebuilt from the inputs stored beside the reference's own outputs (tests/golden/patch_*.npz,
+made by tests/golden/make_golden.py from the UNPATCHED reference handlers: ``op_fun`` at template_handler.py:152,
+standard_bundle_handler.py:182, free_point_handler.py:143; ``make_loss_fun`` / ``make_loss_jac`` at th:157-193).  Then:
 
-  1. with the real engine: every attribute the reference touches exists on the adapter and the only failure in this
+  1. with the real engine: every attribute the handler touches exists on the adapter and the only failure in a
      GPU-less container is ``PcsError(PCS_ERR_NODEVICE)`` out of ``pcs_create`` (there is no CPU fallback to hide it);
   2. with a test-only stand-in for ``Engine`` (arithmetic by the CPU oracle — test infrastructure, never the product):
-     the closures the REFERENCE builds around the adapter return what the unpatched reference returns.
-
-Skipped where /root/reference does not exist (the GPU box).
+     the closures built around the adapter return what the unpatched reference returned.
 """
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
+from scipy.sparse import csr_array
 
-sys.path.insert(0, str(Path(__file__).resolve().parent / "golden"))
-import _refload  # noqa: E402
-
-from oracle import ba_oracle as orc  # noqa: E402
-from pycamset_amd import _capi, synthetic  # noqa: E402
-from pycamset_amd import function_blocks as hip_fb  # noqa: E402
-from tests.test_host_logic import DuckCamset, DuckTargetND  # noqa: E402
-from tests.test_oracle_golden import assert_close  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not _refload.available(), reason="needs /root/reference (build container only)")
+from oracle import ba_oracle as orc
+from pycamset_amd import _capi
+from pycamset_amd import function_blocks as hip_fb
+from pycamset_amd.detections import TargetDetection
+from tests.test_host_logic import HANDLERS, DuckCamset, DuckTargetND
+from tests.test_oracle_golden import assert_close
 
 
 def hip_chain(chain):
@@ -78,35 +70,32 @@ class OracleEngine:
         return orc.block_param_inds(self.chain, self.det, self.counts)
 
 
-def _problem(mods, chain, rig, keydims, max_ims=0):
-    from tests.golden.make_golden import to_multidim_keys  # the fixture generator's own helper
-    names = [f"cam_{i}" for i in range(rig.n_cams)]
-    det = mods.TargetDetection(cam_names=names, data=to_multidim_keys(rig.detections, keydims), max_ims=max_ims)
-    fixed = {"cam_1": {"int": rig.intr[1].copy(), "ext": rig.extr[1].copy()}}
-    mods.th.DEFAULT_OPTIONS.update({"fixed_pose": 0})
-    cls = {"template": mods.th.TemplateBundleHandler, "self": mods.sbh.SelfBundleHandler, "free": mods.fph.FreePointBundleHandler}[chain]
-    h = cls(DuckCamset(rig.n_cams), DuckTargetND(rig.points, keydims), det, fixed_params=fixed, options={"verbosity": 0})
+def _problem(golden_dir, chain, max_ims=0):
+    """-> (handler, x, fixture): the handler of the fixture's problem, with the reference's layout rule (max index + 1,
+    afb:793-795) like the reference handler the fixture was made with, and the fixture's free vector."""
+    g = np.load(golden_dir / f"patch_{chain}_ims{max_ims}.npz")
+    n_cams = int(g["n_cams"])
+    names = [f"cam_{i}" for i in range(n_cams)]
+    fixed = {}
+    for c in range(n_cams):
+        if not g["intr_unfixed"][c]:
+            fixed.setdefault(names[c], {})["int"] = g["intr_slab"][c].copy()
+        if not g["extr_unfixed"][c]:
+            fixed.setdefault(names[c], {})["ext"] = g["extr_slab"][c].copy()
+    det = TargetDetection(names, g["detections"], max_ims=max_ims)
+    target = DuckTargetND(g["points"], tuple(int(k) for k in g["keydims"]))
+    h = HANDLERS[chain](DuckCamset(n_cams), target, det, fixed_params=fixed, options={"verbosity": 0, "fixed_pose": 0},
+                        counts="reference")
     bp = h.bundlePrimitive
-    poses = np.zeros((det.max_ims, 6))
-    poses[: rig.n_imgs] = rig.poses
-    parts = [rig.intr[bp.intr_unfixed].ravel(), rig.extr[bp.extr_unfixed].ravel()]
-    if chain != "free":
-        parts.append(poses[bp.poses_unfixed].ravel())
-    if chain != "template":
-        parts.append(rig.points.ravel()[bp.bdpt_unfixed])
-    return h, np.concatenate(parts)
-
-
-@pytest.fixture(scope="module")
-def mods():
-    with _refload.reference_modules() as m:
-        yield m
+    masks = ["intr_unfixed", "extr_unfixed"] + (["poses_unfixed"] if chain != "free" else []) + (["bdpt_unfixed"] if chain != "template" else [])
+    for m in masks:   # the free vector of the fixture means the same parameters here
+        assert np.array_equal(getattr(bp, m), g[m]), m
+    return h, g["x"].copy(), g
 
 
 @pytest.mark.parametrize("chain", ["template", "self", "free"])
-def test_patched_reference_handler_reaches_pcs_create(mods, chain):
-    rig = synthetic.make_rig("patch", 3, 4, synthetic.ccube_points(4, 40.0), seed=5, visibility=0.7)   # 6 x 9 keys
-    h, x = _problem(mods, chain, rig, (6, 9))
+def test_patched_reference_handler_reaches_pcs_create(golden_dir, chain):
+    h, x, _ = _problem(golden_dir, chain)
     h.op_fun = hip_chain(chain)                      # <- the patch
     assert h.can_make_jac() is True                  # th:154-155
     if _capi.lib().pcs_device_count() > 0:
@@ -118,22 +107,18 @@ def test_patched_reference_handler_reaches_pcs_create(mods, chain):
 
 
 @pytest.mark.parametrize("chain,max_ims", [("template", 0), ("self", 0), ("free", 0), ("template", 6), ("self", 6)])
-def test_patched_reference_handler_returns_what_the_reference_returns(mods, chain, max_ims, monkeypatch):
+def test_patched_reference_handler_returns_what_the_reference_returns(golden_dir, chain, max_ims, monkeypatch):
     """max_ims = 6 > 4 images: the handler's pose slab (and mask) is longer than the string the detections index —
     the reference reads only the leading entries (afb:363) and, in the self chain, mis-offsets the point block
     (quirk ii); the patched handler must do exactly the same."""
-    rig = synthetic.make_rig("patch", 3, 4, synthetic.ccube_points(4, 40.0), seed=5, visibility=0.7)
-    h_ref, x = _problem(mods, chain, rig, (6, 9), max_ims)
-    r_ref = np.array(h_ref.make_loss_fun(3)(x.copy()))
-    J_ref = h_ref.make_loss_jac(3)(x.copy())
-    h, x2 = _problem(mods, chain, rig, (6, 9), max_ims)
-    assert np.array_equal(x, x2)
+    h, x, g = _problem(golden_dir, chain, max_ims)
+    r_ref, J_ref = g["resid"], csr_array((g["data"], g["indices"], g["indptr"]), shape=tuple(g["shape"]))
     monkeypatch.setattr(hip_fb, "Engine", OracleEngine)      # test-only: no GPU in the build container
     h.op_fun = hip_chain(chain)                               # <- the patch
     r = h.make_loss_fun(3)(x.copy())
     J = h.make_loss_jac(3)(x.copy())
     assert r.shape == r_ref.shape and J.shape == J_ref.shape
     assert np.array_equal(J.indices, J_ref.indices) and np.array_equal(J.indptr, J_ref.indptr)
-    assert_close(r, r_ref, rtol=1e-11, rows=1e3 * np.repeat(np.max(np.abs(rig.detections[:, 3:]), axis=1), 2))
+    assert_close(r, r_ref, rtol=1e-11, rows=1e3 * np.repeat(np.max(np.abs(g["detections"][:, -2:]), axis=1), 2))
     dense_rows = np.repeat(np.max(np.abs(J_ref).toarray(), axis=1), np.diff(J_ref.indptr))
     assert_close(J.data, J_ref.data, rows=dense_rows)

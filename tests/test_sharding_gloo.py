@@ -261,6 +261,19 @@ def test_bench_launches_its_own_ranks(capfd):
     assert "noise from rank 0" in err and "noise from rank 2" in err
 
 
+def test_bench_self_launch_relays_a_line_shared_with_other_output(capfd):
+    """An unbuffered rank writes its object and the newline separately, so another rank's text can land on either side of
+    rank 0's object in the shared pipe: the object alone reaches stdout, the text around it goes to stderr."""
+    import json
+
+    rc, out, err = _capture_self_launch(capfd, 2, ["--glued"])
+    assert rc == 0, err
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1, (out, err[-3000:])
+    assert json.loads(lines[0])["sum"] == 3.0
+    assert "noise before" in err and "noise after" in err
+
+
 def test_bench_self_launch_reports_a_failed_rank(capfd):
     rc, out, err = _capture_self_launch(capfd, 2, ["--fail-rank", "1"])
     assert rc != 0

@@ -4,11 +4,11 @@ O=$R/gpurun_out/r02/final
 mkdir -p $O
 cd $R
 say() { echo "[r02_collect] $*"; }
-say "bench config 3 (default run)"; timeout -k 10 300 python bench.py > $O/bench_N1.json 2> $O/bench_N1.err < /dev/null
-say "bench config 4"; timeout -k 10 300 python bench.py --config 4 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_N1_config4_self.json 2> $O/bench_c4.err < /dev/null
-say "bench config 5 f32"; timeout -k 10 400 python bench.py --config 5 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_N1_config5_f32.json 2> $O/bench_c5.err < /dev/null
-say "bench config 5 mixed"; timeout -k 10 400 python bench.py --config 5 --dtype mixed --steps 20 --warmup 3 --no-cpu-baseline --no-normal-probe > $O/bench_N1_config5_mixed.json 2> $O/bench_c5m.err < /dev/null
-say "bench config 2"; timeout -k 10 200 python bench.py --config 2 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_N1_config2_ring8.json 2> $O/bench_c2.err < /dev/null
+say "bench config 3 (default run)"; timeout -k 10 300 python bench.py --full > $O/bench_N1.json 2> $O/bench_N1.err < /dev/null
+say "bench config 4"; timeout -k 10 300 python bench.py --full --config 4 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_N1_config4_self.json 2> $O/bench_c4.err < /dev/null
+say "bench config 5 f32"; timeout -k 10 400 python bench.py --full --config 5 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_N1_config5_f32.json 2> $O/bench_c5.err < /dev/null
+say "bench config 5 mixed"; timeout -k 10 400 python bench.py --full --config 5 --dtype mixed --steps 20 --warmup 3 --no-cpu-baseline --no-normal-probe > $O/bench_N1_config5_mixed.json 2> $O/bench_c5m.err < /dev/null
+say "bench config 2"; timeout -k 10 200 python bench.py --full --config 2 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_N1_config2_ring8.json 2> $O/bench_c2.err < /dev/null
 say "scaling projection"; bash tools/scaling_projection.sh > $O/scaling_projection_one_gpu.log 2>&1 < /dev/null
 say "sweeps"
 for args in "--config 3" "--config 4 --chain self" "--config 4 --chain free" "--config 3 --dtype f32" "--config 3 --dtype mixed" "--config 3 --shuffle" "--config 3 --mode resid --variants 4" "--config 2"; do

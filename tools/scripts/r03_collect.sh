@@ -8,12 +8,12 @@ PARTS="${@:-bench scaling stats pmc normal lm gloo}"
 say() { echo "[r03_collect] $*"; }
 has() { case " $PARTS " in *" $1 "*) return 0;; *) return 1;; esac; }
 if has bench; then
-say "bench config 3 (default run)"; timeout -k 10 300 python bench.py > $O/bench_N1.json 2> $O/bench_N1.err < /dev/null
-say "bench config 2"; timeout -k 10 200 python bench.py --config 2 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_N1_config2_ring8.json 2> $O/bench_c2.err < /dev/null
-say "bench config 4"; timeout -k 10 300 python bench.py --config 4 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_N1_config4_self.json 2> $O/bench_c4.err < /dev/null
-say "bench config 5 f32"; timeout -k 10 400 python bench.py --config 5 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_N1_config5_f32.json 2> $O/bench_c5.err < /dev/null
-say "bench config 5 mixed"; timeout -k 10 400 python bench.py --config 5 --dtype mixed --steps 20 --warmup 3 --no-cpu-baseline --no-normal-probe > $O/bench_N1_config5_mixed.json 2> $O/bench_c5m.err < /dev/null
-say "bench config 5 f32, Jacobian streamed to host"; timeout -k 10 400 python bench.py --config 5 --steps 10 --warmup 2 --no-cpu-baseline --no-normal-probe --stream-to-host > $O/bench_N1_config5_f32_stream_to_host.json 2> $O/bench_c5s.err < /dev/null
+say "bench config 3 (default run)"; timeout -k 10 300 python bench.py --full > $O/bench_N1.json 2> $O/bench_N1.err < /dev/null
+say "bench config 2"; timeout -k 10 200 python bench.py --full --config 2 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_N1_config2_ring8.json 2> $O/bench_c2.err < /dev/null
+say "bench config 4"; timeout -k 10 300 python bench.py --full --config 4 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_N1_config4_self.json 2> $O/bench_c4.err < /dev/null
+say "bench config 5 f32"; timeout -k 10 400 python bench.py --full --config 5 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_N1_config5_f32.json 2> $O/bench_c5.err < /dev/null
+say "bench config 5 mixed"; timeout -k 10 400 python bench.py --full --config 5 --dtype mixed --steps 20 --warmup 3 --no-cpu-baseline --no-normal-probe > $O/bench_N1_config5_mixed.json 2> $O/bench_c5m.err < /dev/null
+say "bench config 5 f32, Jacobian streamed to host"; timeout -k 10 400 python bench.py --full --config 5 --steps 10 --warmup 2 --no-cpu-baseline --no-normal-probe --stream-to-host > $O/bench_N1_config5_f32_stream_to_host.json 2> $O/bench_c5s.err < /dev/null
 fi
 if has scaling; then
 say "scaling projection"; bash tools/scaling_projection.sh > $O/scaling_projection_one_gpu.log 2>&1 < /dev/null
@@ -75,7 +75,7 @@ fi
 if has gloo; then
 say "gloo rehearsal of bench.py --gpus N on one GPU (ranks share the card; the box admits at most 6 GPU processes INCLUDING the launcher: a 6-rank rehearsal was killed by its process guard)"
 for n in 2 4; do
-  PCS_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29510 + n)) bench.py --gpus $n --steps 50 --warmup 5 > $O/bench_N${n}_gloo_rehearsal_one_gpu.json 2> $O/bench_N${n}_gloo.err < /dev/null
+  PCS_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29510 + n)) bench.py --full --gpus $n --steps 50 --warmup 5 > $O/bench_N${n}_gloo_rehearsal_one_gpu.json 2> $O/bench_N${n}_gloo.err < /dev/null
 done
 fi
 say "done"; ls $O
