@@ -444,6 +444,22 @@ int pcs_kernel_ms_samples(pcs_engine *h, int64_t capacity, float *slab_prep_ms, 
  * or whole passes are skipped and the results are wrong while it is non-zero); see DESIGN.md.
  * Unknown keys -> PCS_ERR_ARG. */
 int pcs_set_option(pcs_engine *h, const char *key, int64_t value);
+/* Robust loss of the engine's normal equations, with the semantics of scipy.optimize.least_squares(loss=, f_scale=): applied to each
+ * scalar residual f (the u and the v of a detection separately), z = (f / f_scale)^2, rho0 = f_scale^2 rho(z), rho1 = rho'(z),
+ * rho2 = rho''(z) / f_scale^2, linearised as scipy's scale_for_robust_loss_function:  s = sqrt(max(rho1 + 2 rho2 f^2, EPS)),
+ * row of J -> s J, f -> rho1 f / s.  A build then returns H = J~^T J~, g = J~^T r~ = J^T (rho1 f) and the cost word sum rho0
+ * (= sum f^2 for the linear loss; the LM result's cost is half of it, scipy's OptimizeResult.cost).
+ *   kind: PCS_LOSS_LINEAR (the default), PCS_LOSS_HUBER, PCS_LOSS_SOFT_L1, PCS_LOSS_CAUCHY, PCS_LOSS_ARCTAN.
+ *   PCS_ERR_ARG for a NULL handle, an unknown kind, or an f_scale that is not finite and > 0 (the setting is then unchanged).
+ * Affects every normal-equation build of the engine: pcs_normal_equations*, pcs_normal_blocks_device, pcs_lm_trial* and, through
+ * those, the device-steered and sharded LM loops; both contraction orders (option "deterministic" keeps its same-bits guarantee).
+ * Does NOT affect pcs_eval* and the compact paths (the drop-in closures keep returning the raw residuals and J), pcs_matfree (its
+ * products use the raw J), nor generated chains (pcs_genchain_*).
+ * The linear loss takes the builds' plain path: the same bits as an engine on which pcs_set_loss was never called. */
+enum { PCS_LOSS_LINEAR = 0, PCS_LOSS_HUBER = 1, PCS_LOSS_SOFT_L1 = 2, PCS_LOSS_CAUCHY = 3, PCS_LOSS_ARCTAN = 4 };
+int pcs_set_loss(pcs_engine *h, int kind, double f_scale);
+/* The current setting (kind and f_scale may be NULL); PCS_ERR_ARG for a NULL handle. */
+int pcs_get_loss(pcs_engine *h, int *kind, double *f_scale);
 /*
  * Batched n-view triangulation.
  * Replaces: nb_triangulate_full (compiled_helpers.py:609-643) = per point nb_undistort (ch:409-431) +

@@ -18,6 +18,8 @@ PCS_OK, PCS_ERR_ARG, PCS_ERR_HIP, PCS_ERR_STATE, PCS_ERR_NODEVICE, PCS_ERR_RANGE
 CHAIN_IDS = {"template": 0, "self": 1, "free": 2}
 CHAIN_P = {"template": 21, "self": 24, "free": 18}
 DTYPE_IDS = {"f64": 0, "f32": 1, "mixed": 2}   # mixed: FP64 arithmetic, FP32 residual / Jacobian bytes
+# robust losses of the normal equations (include/pcs_hip.h PCS_LOSS_*): scipy.optimize.least_squares's names
+LOSS_IDS = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3, "arctan": 4}
 
 # every symbol include/pcs_hip.h declares: name -> (restype, argtypes)
 _P = c_void_p
@@ -124,6 +126,8 @@ SYMBOLS = {
     "pcs_host_free": (c_int, [_P]),
     "pcs_membench": (c_int, [c_int, c_int, c_int64, c_int, c_int, POINTER(c_float)]),
     "pcs_set_option": (c_int, [_P, c_char_p, c_int64]),
+    "pcs_set_loss": (c_int, [_P, c_int, c_double]),
+    "pcs_get_loss": (c_int, [_P, POINTER(c_int), POINTER(c_double)]),
     "pcs_device_buffers": (c_int, [_P, POINTER(_P), POINTER(_P)]),
 }
 

@@ -85,6 +85,58 @@ __device__ __forceinline__ double2v load_uv(const DetTable &t, const int64_t i) 
     return m;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Robust losses of scipy.optimize.least_squares, applied to each scalar residual f (pcs_set_loss).  With z = (f / f_scale)^2:
+//     rho0 = f_scale^2 rho(z)     rho1 = rho'(z)     rho2 = rho''(z) / f_scale^2          (least_squares.py, construct_loss_function)
+// and the linearisation of _lsq/common.py scale_for_robust_loss_function:
+//     s = sqrt(max(rho1 + 2 rho2 f^2, EPS))        row of J -> s J          f -> rho1 f / s
+// (2 rho2 f^2 = 2 z rho''(z): f_scale drops out of s).  FP64 throughout.  A NaN residual gives NaN s, rf and rho0, as in numpy (the
+// clamp is written as `x < EPS ? EPS : x`, which keeps a NaN).  `kind` is wave-uniform wherever the kernels call this.
+constexpr int LOSS_LINEAR = 0, LOSS_HUBER = 1, LOSS_SOFT_L1 = 2, LOSS_CAUCHY = 3, LOSS_ARCTAN = 4;
+#ifndef __HIPCC_RTC__   // generated chains take no robust loss (yet): their hiprtc builds need none of this
+// rho(z) of the two losses with a transcendental rho (cauchy: log1p, arctan: atan) — rho0 only, the weights are rational.  Out of line:
+// inlined into the normal-equations kernel next to the other losses' code, the two of them raised its register allocation for EVERY
+// launch, the linear loss included (free chain, shared pass: 120 -> 180 VGPRs, four waves per SIMD -> two); called, the callee
+// works in the caller-saved registers and the kernel keeps its occupancy and zero scratch.
+__device__ __attribute__((noinline)) double robust_rho_transcendental(const int kind, const double z) { return kind == LOSS_CAUCHY ? log1p(z) : atan(z); }
+// returns s; rho0 and the scaled residual rf through the references.  DEFER_TRANSCENDENTAL: for cauchy / arctan, rho0 receives z instead
+// (the caller evaluates f_scale^2 robust_rho_transcendental(kind, z) itself; ba_normal.hpp robust_scale_row)
+template <bool DEFER_TRANSCENDENTAL = false>
+__device__ __forceinline__ double robust_rho(const int kind, const double f, const double inv_f_scale, const double f_scale_sq, double &rho0,
+                                             double &rf) {
+    const double q = f * inv_f_scale, z = q * q;
+    double rho, rho1, rho2;   // rho(z), rho'(z), rho''(z)
+    if (kind == LOSS_HUBER) {
+        const bool in = z <= 1.0;
+        const double sq = sqrt(z);
+        rho = in ? z : 2.0 * sq - 1.0;
+        rho1 = in ? 1.0 : 1.0 / sq;
+        rho2 = in ? 0.0 : -0.5 * rho1 / z;
+    } else if (kind == LOSS_SOFT_L1) {
+        const double t = 1.0 + z, st = sqrt(t);
+        rho = 2.0 * (st - 1.0);
+        rho1 = 1.0 / st;
+        rho2 = -0.5 * rho1 / t;
+    } else if (kind == LOSS_CAUCHY) {
+        rho = DEFER_TRANSCENDENTAL ? z : robust_rho_transcendental(kind, z);
+        rho1 = 1.0 / (1.0 + z);
+        rho2 = -rho1 * rho1;
+    } else if (kind == LOSS_ARCTAN) {
+        rho = DEFER_TRANSCENDENTAL ? z : robust_rho_transcendental(kind, z);
+        rho1 = 1.0 / (1.0 + z * z);
+        rho2 = -2.0 * z * rho1 * rho1;
+    } else {
+        rho = z; rho1 = 1.0; rho2 = 0.0;
+    }
+    constexpr double EPS = 2.220446049250313e-16;   // float64 machine epsilon, as scipy's EPS
+    const double js = rho1 + 2.0 * z * rho2;
+    const double s = sqrt(js < EPS ? EPS : js);
+    rho0 = DEFER_TRANSCENDENTAL && (kind == LOSS_CAUCHY || kind == LOSS_ARCTAN) ? rho : f_scale_sq * rho;
+    rf = rho1 * f / s;
+    return s;
+}
+#endif
+
 // broadcast lane `src`'s value to the whole wave through scalar registers (v_readlane_b32)
 __device__ __forceinline__ double readlane_scalar(double v, int src) {
     const uint64_t b = __builtin_bit_cast(uint64_t, v);

@@ -83,6 +83,14 @@ struct NormalArgs {
     // of lane l at (m * 4 + r) * 64 + l — and an ordered second pass sums the slots.  NULL = atomics.
     double *part;
     const int32_t *seg_base;
+    // Robust loss (pcs_set_loss; robust_rho in ba_device.hpp), a runtime switch that is uniform over the launch: 0 = linear, the kernels
+    // take their plain path.  Otherwise every pass scales each detection's two rows of J (and, where the pass has the column, its residual)
+    // before they enter the LDS image, so that H = J~^T J~ and g = J~^T r~.  The Gram's (r, r) entry then sums r~^2, not the cost: the shared
+    // pass adds sum rho0 instead — one atomic per wave, or (deterministic mode) one store per wave into wave_cost[workgroup], summed in
+    // order by normal_reduce_final_kernel.
+    int32_t loss;
+    double inv_f_scale, f_scale_sq;
+    double *wave_cost;
     int32_t debug;  // profiling switches (results are wrong while set): 2 no flush atomics, 8 no MFMA phase, 16 no evaluation,
                     // 32 run boundaries ignored, 64 no LDS image writes, 128 flush = clear only; host side: 256 / 512 / 1024 skip the shared /
                     // (cam, key) / (image, key) pass
@@ -182,6 +190,33 @@ __host__ __device__ __forceinline__ int entry_descriptor(const int m, const int 
     return oR | (oC << 4) | (eRow << 8) | (eCol << 13) | (eLd << 18) | (ePtr << 23) | (keep ? 1 << 27 : 0) | (pose ? 1 << 28 : 0);
 }
 
+// Robust loss (ba_normal_mfma_kernel): scale one lane's two rows of the LDS image by their weights and replace its residual by r~;
+// returns the lane's (rho0_u, rho0_v) — for cauchy / arctan (z_u, z_v) instead: their rho is log1p / atan, which the kernel calls itself
+// (robust_rho_transcendental), so that this function stays a LEAF.  Out of line because of registers: the runtime switch must not
+// raise the kernel's allocation for the linear loss.  Inlined, the loss code ran next to live state of the tile loop (179 -> 188 VGPRs,
+// chains T / S, shared pass; the (cam, key) pass 165 -> 171, three waves per SIMD -> two; the 32-row image spilled 144 B); a call that
+// makes further calls keeps a register across them on the stack (16 B of scratch).  As a leaf call it works in the caller-saved
+// registers: +1 to +7 VGPRs against the parent, the same waves per SIMD and zero scratch in every instantiation (profiles/r06).
+template <int CHAIN, int PASS, int KS>
+__device__ __attribute__((noinline)) double2v robust_scale_row(const int kind, const double r0, const double r1, const double inv_f_scale,
+                                                               const double f_scale_sq, unsigned char *dst) {
+    double q0, q1, f0, f1;
+    const double s0 = robust_rho<true>(kind, r0, inv_f_scale, f_scale_sq, q0, f0);
+    const double s1 = robust_rho<true>(kind, r1, inv_f_scale, f_scale_sq, q1, f1);
+#pragma unroll
+    for (int s = 0; s < normal_slots(CHAIN, PASS); ++s) {
+        double *q = reinterpret_cast<double *>(dst + s * KS);
+        if (slot_col<CHAIN, PASS>(s) == NORMAL_R) {
+            q[0] = f0;
+            q[1] = f1;
+        } else {
+            q[0] *= s0;
+            q[1] *= s1;
+        }
+    }
+    return double2v{q0, q1};
+}
+
 using d4v = __attribute__((ext_vector_type(4))) double;
 
 // Two waves per SIMD: the 22.9 KB image (ROWS = 64) allows 7 one-wave workgroups per CU anyway; the half-tile form (ROWS = 32,
@@ -235,6 +270,15 @@ __global__ __launch_bounds__(64, 2) void ba_normal_mfma_kernel(const NormalArgs 
     for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) ent[m][r] = entry_descriptor<CHAIN, PASS>(m, lane, r, tg);
+    const bool robust = a.loss != LOSS_LINEAR;   // uniform over the launch
+    if (PASS == PASS_SHARED && robust) {   // the (r, r) entry sums r~^2: not the cost, which comes from rho_acc below
+#pragma unroll
+        for (int m = 0; m < NM; ++m)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (((ent[m][r] >> 23) & 7) == 4) ent[m][r] &= ~(1 << 27);
+    }
+    double rho_acc = 0.0;   // robust loss: this lane's share of sum rho0 (shared pass)
     // lanes 0-4: the five output pointers (A, B, C, g, cost)
     const int64_t out_shift = (a.sel && *a.sel) ? 8 * a.alt : 0;   // bytes: which of the two packed states receives this build
     const uint64_t out_ptr = (lane == 1 ? (uint64_t)a.HB : lane == 2 ? (uint64_t)a.HC : lane == 3 ? (uint64_t)a.g : lane == 4 ? (uint64_t)a.cost : (uint64_t)a.H) + (uint64_t)out_shift;
@@ -417,6 +461,17 @@ __global__ __launch_bounds__(64, 2) void ba_normal_mfma_kernel(const NormalArgs 
                         q[0] = 0.0;
                         q[1] = 0.0;
                     }
+                } else if (robust) {
+                    // Robust loss: the lane's two rows are scaled by their weights and its residual replaced by r~, in the image, after J
+                    // has gone there (scaling J in registers kept all of it live across the loss code).  Every pass re-evaluates the
+                    // detection: the same weights.
+                    const double2v q = robust_scale_row<CHAIN, PASS, KS>(a.loss, r0, r1, a.inv_f_scale, a.f_scale_sq, dst);
+                    if (PASS == PASS_SHARED) {
+                        if (a.loss == LOSS_CAUCHY || a.loss == LOSS_ARCTAN)
+                            rho_acc += a.f_scale_sq * robust_rho_transcendental(a.loss, q.x) + a.f_scale_sq * robust_rho_transcendental(a.loss, q.y);
+                        else
+                            rho_acc += q.x + q.y;
+                    }
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -527,6 +582,13 @@ __global__ __launch_bounds__(64, 2) void ba_normal_mfma_kernel(const NormalArgs 
         }
     }
     flush(true);
+    if (PASS == PASS_SHARED && robust) {   // sum rho0: one add per wave (atomic), or its own slot (deterministic mode)
+        const double c = wave_sum(rho_acc);
+        if (lane == 0) {
+            if (a.part) a.wave_cost[blockIdx.x] = c;
+            else if (c != 0.0 && !(a.debug & 2)) unsafeAtomicAdd(a.cost + out_shift / 8, c);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -584,13 +646,26 @@ __global__ __launch_bounds__(64, 3) void ba_normal_imgkey_kernel(const NormalArg
     };
     const int64_t tile0 = (int64_t)blockIdx.x * a.tiles_per_wave;
     const int64_t tile1 = min(tile0 + (int64_t)a.tiles_per_wave, a.n_tiles);
+    // robust loss: the row weights of the detection come from its own residual, so the measurement is read as well (requested with the
+    // index words; the pass's sorted table carries it when a loss is set) and the projection eval_detection forms anyway is finished
+    const bool robust = a.loss != LOSS_LINEAR;   // uniform over the launch
     DetWords nxt_w{};
-    if (tile0 < tile1) nxt_w = load_words(a.tab, det_index(tile0));
+    double2v nxt_m{};
+    if (tile0 < tile1) {
+        const int64_t ic = det_index(tile0);
+        nxt_w = load_words(a.tab, ic);
+        if (robust) nxt_m = load_uv(a.tab, ic);
+    }
     for (int64_t tile = tile0; tile < tile1; ++tile) {
         const bool valid = tile * 64 + lane < a.n;
         int c, im, k;
         decode_words(a.tab, nxt_w, c, im, k);
-        if (tile + 1 < tile1) nxt_w = load_words(a.tab, det_index(tile + 1));
+        const double2v m = nxt_m;
+        if (tile + 1 < tile1) {
+            const int64_t icn = det_index(tile + 1);
+            nxt_w = load_words(a.tab, icn);
+            if (robust) nxt_m = load_uv(a.tab, icn);
+        }
         asm volatile("" ::: "memory");
         // S = A_x R_e = the pose-translation columns of the detection's block (everything else eval_detection forms is dead code here)
         T Su[3], Sv[3];
@@ -610,8 +685,16 @@ __global__ __launch_bounds__(64, 3) void ba_normal_imgkey_kernel(const NormalArg
             else eval_detection<CHAIN, T, true>(csp, pose_slab + im * POSE_STRIDE, X0, X1, X2, u, v, J);
 #pragma unroll
             for (int j = 0; j < 3; ++j) { Su[j] = J[18 + j]; Sv[j] = J[P + 18 + j]; }
+            if (robust) {
+                double q0, q1, f0, f1;
+                const double s0 = robust_rho(a.loss, u - m.x, a.inv_f_scale, a.f_scale_sq, q0, f0);
+                const double s1 = robust_rho(a.loss, v - m.y, a.inv_f_scale, a.f_scale_sq, q1, f1);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) { Su[j] *= s0; Sv[j] *= s1; }
+            }
         }
         asm volatile("" ::"v"(nxt_w.w0), "v"(nxt_w.w1), "v"(nxt_w.w2));   // consume the prefetch before any atomic is issued (ba_normal_mfma_kernel)
+        if (robust) asm volatile("" ::"v"(nxt_m.x), "v"(nxt_m.y));
 
         // runs of this tile: lane 0 always starts one
         const int pi = __shfl_up(im, 1), pk = __shfl_up(k, 1);

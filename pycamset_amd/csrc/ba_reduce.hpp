@@ -72,6 +72,7 @@ struct ReduceArgs {
     const int32_t *ent_ptr;    // n_ent + 1: the logical runs of entity e (image / key) are ent_runs[ent_ptr[e] ..), in camera order
     const int32_t *ent_runs;
     int32_t n_lr, n_grp, n_cams, n_ent;
+    int32_t n_waves;           // workgroups of the shared pass: with a robust loss the cost is the sum of their wave_cost words (NormalArgs)
 };
 
 // Step 2 of the header comment.  One workgroup per group, one WAVE per logical run (round 5, second version: the first walked the
@@ -194,10 +195,15 @@ __global__ __launch_bounds__(256) void normal_reduce_final_kernel(const NormalAr
     if (HAS_CAM && (int)blockIdx.x == ra.n_cams) {        // the cost: every group's share, in a fixed tree
         __shared__ double red[256];
         double s = 0.0;
-        for (int g = tid; g < ra.n_grp; g += 8 * 256) {
+        // linear loss: the groups' (r, r) entries; robust loss: sum rho0, one word per wave of the shared pass (the (r, r) entries sum r~^2)
+        const bool robust = a.loss != LOSS_LINEAR;
+        const double *src = robust ? a.wave_cost : ra.G + 255;
+        const int64_t stride = robust ? 1 : RED_G;
+        const int cnt = robust ? ra.n_waves : ra.n_grp;
+        for (int g = tid; g < cnt; g += 8 * 256) {
             double v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = g + 256 * u < ra.n_grp ? ra.G[(int64_t)(g + 256 * u) * RED_G + 255] : 0.0;
+            for (int u = 0; u < 8; ++u) v[u] = g + 256 * u < cnt ? src[(int64_t)(g + 256 * u) * stride] : 0.0;
 #pragma unroll
             for (int u = 0; u < 8; ++u) s += v[u];
         }

@@ -13,6 +13,7 @@
 #include <atomic>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -160,6 +161,9 @@ struct pcs_engine {
     // geometry fix (csrc/ba_reduce.hpp) instead of with f64 atomics in arrival order: two runs — and the ranks of a sharded loop — compute
     // the same bits
     int deterministic = 0;
+    // pcs_set_loss: robust loss of every normal-equation build (ba_device.hpp robust_rho; 0 = linear) and its f_scale
+    int loss = 0;
+    double f_scale = 1.0;
     int fused_trial = 1;   // option: pcs_lm_trial_build uses schur_prep_kernel / schur_finish_kernel (csrc/ba_lm_fused.hpp); 0 = the separate launches (A/B)
     // host copies of the visiting orders (shared pass of a scattered table, (cam, key) pass): the deterministic mode's tables are built from them
     std::vector<int32_t> h_order, h_order_ck;
@@ -171,8 +175,8 @@ struct pcs_engine {
         int32_t n_seg = 0, n_lr = 0, n_grp = 0, n_ent = 0, n_waves = 0;
         int32_t *d_idx = nullptr;      // one allocation: seg_base | lr_ptr | lr_segs | lr_ka | lr_kb | grp_ptr | cam_ptr | ent_ptr | ent_runs
         int64_t off[9] = {};
-        double *d_work = nullptr;      // one allocation: part | Q | G
-        int64_t work_off[3] = {};
+        double *d_work = nullptr;      // one allocation: part | Q | G | wave_cost (n_waves: the robust loss's cost, shared pass)
+        int64_t work_off[4] = {};
     } det[2];
 };
 
@@ -242,7 +246,7 @@ static void free_det_tables(pcs_engine *h) {
 
 extern "C" {
 
-int pcs_version(void) { return 100; }
+int pcs_version(void) { return 101; }
 const char *pcs_last_error(void) { return g_err.c_str(); }
 
 // ---- batched triangulation: a handle that owns the camera table, the observation buffers and the
@@ -949,6 +953,24 @@ int pcs_set_option(pcs_engine *h, const char *key, int64_t value) {
     return PCS_OK;
 }
 
+static_assert(PCS_LOSS_LINEAR == LOSS_LINEAR && PCS_LOSS_HUBER == LOSS_HUBER && PCS_LOSS_SOFT_L1 == LOSS_SOFT_L1 && PCS_LOSS_CAUCHY == LOSS_CAUCHY &&
+              PCS_LOSS_ARCTAN == LOSS_ARCTAN, "loss kinds of the C ABI and of ba_device.hpp");
+int pcs_set_loss(pcs_engine *h, int kind, double f_scale) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_set_loss: bad arguments");
+    if (kind < PCS_LOSS_LINEAR || kind > PCS_LOSS_ARCTAN) return fail(PCS_ERR_ARG, "pcs_set_loss: kind %d not in [0, 4] (linear, huber, soft_l1, cauchy, arctan)", kind);
+    if (!std::isfinite(f_scale) || !(f_scale > 0.0)) return fail(PCS_ERR_ARG, "pcs_set_loss: f_scale must be finite and > 0 (got %g)", f_scale);
+    h->loss = kind;
+    h->f_scale = f_scale;
+    return PCS_OK;
+}
+
+int pcs_get_loss(pcs_engine *h, int *kind, double *f_scale) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_get_loss: bad arguments");
+    if (kind) *kind = h->loss;
+    if (f_scale) *f_scale = h->f_scale;
+    return PCS_OK;
+}
+
 }  // extern "C"
 
 // ---- launch plumbing ---------------------------------------------------------------------------
@@ -1206,6 +1228,24 @@ static int build_point_orders(pcs_engine *h) {
     return PCS_OK;
 }
 
+// The (image, key) pass reads no measurements under the linear loss, so build_point_orders gathers none for it; a robust loss weighs
+// the pass's rows by their residuals, and the first build with one gathers the measurements into that order as well (kept with the table).
+// The gather is queued on the BUILD's stream `s`, in front of the pass that reads it; later work on any other stream is ordered behind
+// the build's `done` event (enqueue_normal's mark_done, order_after_done of the next enqueue) like every other output of the build.
+static int ensure_imgkey_uv(pcs_engine *h, hipStream_t s) {
+    void **t = h->d_sorted[PASS_IMGKEY];
+    if (t[4] || !h->d_order_ik || h->n <= 0) return PCS_OK;
+    using u2 = __attribute__((ext_vector_type(2))) uint32_t;
+    using u4 = __attribute__((ext_vector_type(4))) uint32_t;
+    hipError_t e = h->msize == 4 ? gather_rows<u2>(h->d_order_ik, h->d_uv, &t[4], h->n, s) : gather_rows<u4>(h->d_order_ik, h->d_uv, &t[4], h->n, s);
+    if (e != hipSuccess) {
+        if (t[4]) (void)hipFree(t[4]);
+        t[4] = nullptr;
+        return fail(PCS_ERR_HIP, "robust loss: gathering the measurements of the (image, key) pass failed: %s", hipGetErrorString(e));
+    }
+    return PCS_OK;
+}
+
 // ---- deterministic mode: the static tables of the ordered second pass (csrc/ba_reduce.hpp) ---------------------------------------------
 // For MFMA pass `pass` (0 shared, 1 (cam, key)) walked with `tpw` tiles per wave: segments = maximal stretches of detections inside one
 // run and one wave; logical runs = the segments of one key pair (one stretch in a sorted table; several when a pair re-appears);
@@ -1304,7 +1344,8 @@ static int ensure_det_tables(pcs_engine *h, int pass, int64_t tpw) {
     D.work_off[0] = 0;
     D.work_off[1] = n_seg * nm * 256;
     D.work_off[2] = D.work_off[1] + n_lr * RED_Q;
-    HIPCHK(hipMalloc(&D.d_work, sizeof(double) * (size_t)(D.work_off[2] + n_grp * RED_G + 2)));
+    D.work_off[3] = D.work_off[2] + n_grp * RED_G + 2;
+    HIPCHK(hipMalloc(&D.d_work, sizeof(double) * (size_t)(D.work_off[3] + n_waves)));
     D.n = n; D.tpw = tpw;
     D.n_seg = (int32_t)n_seg; D.n_lr = (int32_t)n_lr; D.n_grp = (int32_t)n_grp; D.n_ent = (int32_t)n_ent; D.n_waves = (int32_t)n_waves;
     return PCS_OK;
@@ -1407,6 +1448,7 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
     a.extr_off = h->extr_off; a.pose_off = h->pose_off; a.point_off = h->point_off;
     a.n_params = h->n_params;
     a.debug = h->normal_debug;
+    a.loss = h->loss; a.inv_f_scale = 1.0 / h->f_scale; a.f_scale_sq = h->f_scale * h->f_scale;
     a.stop = d_stop;
     a.sel = d_sel; a.alt = alt_out;
     // every wave walks a contiguous range of tiles, so its register accumulators survive across tiles.  One-wave
@@ -1434,6 +1476,10 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
         if (pass != PASS_SHARED && !a.order) return fail(PCS_ERR_STATE, "normal equations: key-sorted visiting order missing");
         a.tab = det_table(h);
         if (a.order && h->sort_tables) {   // the pass's own copy of the table, already in visiting order
+            if (pass == PASS_IMGKEY && h->loss) {   // a robust loss weighs the (image, key) pass's rows by their residuals: it needs the measurements too
+                const int rc = ensure_imgkey_uv(h, s);
+                if (rc) return rc;
+            }
             void *const *t = h->d_sorted[pass];
             if ((t[0] || t[1]) && (t[4] || pass == PASS_IMGKEY)) {   // index words AND measurements, or neither
                 a.tab.packed = static_cast<const uint32_t *>(t[0]);
@@ -1443,7 +1489,7 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
             }
         }
         hipError_t e;
-        a.part = nullptr; a.seg_base = nullptr;
+        a.part = nullptr; a.seg_base = nullptr; a.wave_cost = nullptr;
         if (pass == PASS_IMGKEY && h->deterministic) {
             // this pass keeps its atomics: a run is at most n_cams long, so with n_cams <= 64 no address gets more than two contributions
             // (csrc/ba_reduce.hpp) — beyond that the order of three could show in the last bit
@@ -1467,13 +1513,14 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
                 if ((int64_t)grid.x != D.n_waves) return fail(PCS_ERR_STATE, "deterministic mode: launch geometry and segment table disagree");
                 a.part = D.d_work + D.work_off[0];
                 a.seg_base = D.d_idx + D.off[0];
+                a.wave_cost = D.d_work + D.work_off[3];
                 e = launch_normal(h->chain, pass, h->normal_rows, a, grid, s);
                 if (e == hipSuccess) {
                     ReduceArgs ra{};
                     ra.part = a.part; ra.Q = D.d_work + D.work_off[1]; ra.G = D.d_work + D.work_off[2];
                     ra.lr_ptr = D.d_idx + D.off[1]; ra.lr_segs = D.d_idx + D.off[2]; ra.lr_ka = D.d_idx + D.off[3]; ra.lr_kb = D.d_idx + D.off[4];
                     ra.grp_ptr = D.d_idx + D.off[5]; ra.cam_ptr = D.d_idx + D.off[6]; ra.ent_ptr = D.d_idx + D.off[7]; ra.ent_runs = D.d_idx + D.off[8];
-                    ra.n_lr = D.n_lr; ra.n_grp = D.n_grp; ra.n_cams = (int32_t)h->n_cams; ra.n_ent = D.n_ent;
+                    ra.n_lr = D.n_lr; ra.n_grp = D.n_grp; ra.n_cams = (int32_t)h->n_cams; ra.n_ent = D.n_ent; ra.n_waves = D.n_waves;
                     e = launch_reduce(h->chain, pass, a, ra, s);
                 }
             } else {

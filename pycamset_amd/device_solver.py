@@ -34,6 +34,9 @@ import time
 
 import numpy as np
 
+from ._capi import LOSS_IDS
+from .engine import Engine
+
 
 class JacobianOperator:
     """J(x) restricted to the free parameters, at the engine's current linearisation point.
@@ -597,7 +600,7 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
 @dataclass
 class DeviceLMResult:
     x: np.ndarray
-    cost: float                 # 0.5 * sum r^2, like scipy's OptimizeResult.cost
+    cost: float                 # 0.5 * sum rho0 (0.5 * sum r^2 for the linear loss), like scipy's OptimizeResult.cost
     grad: np.ndarray
     optimality: float
     nit: int
@@ -664,7 +667,7 @@ class _CholeskyStep:
 
 def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float = 1e-8, gtol: float = 1e-8,
              cg_tol: float = 1e-3, cg_max_iter: int = 200, lam0: float | None = None, lam_grow0: float | None = None, reduce_fn=None, verbose: int = 0,
-             operator=None, linear_solver: str = "auto") -> DeviceLMResult:
+             operator=None, linear_solver: str = "auto", loss: str = "linear", f_scale: float = 1.0) -> DeviceLMResult:
     """Levenberg-Marquardt (Marquardt scaling D = diag(J^T J)) for a pycamset_amd handler.  The damped
     normal equations are solved by Jacobi-PCG on matrix-free J^T J products (``linear_solver='pcg'``) or
     by a Cholesky factorisation of the block-reduced J^T J (``'cholesky'``).  Every quantity that depends
@@ -680,9 +683,25 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
     0.75 by 1/3, above 0.25 by 1, below by 2; every rejected trial multiplies it by 4 (host and device rule alike; at most
     REJECTION_LIMIT = 12 in a row), a rejection BEFORE the first accepted step by ``lam_grow0`` (default LAM_GROW0 = 1e3).  1e-6 (round
     4) is one evaluation faster from a near start and up to twice as slow from a far one: a nearly undamped step from 70 px away
-    overshoots into a region where five to eight trials are rejected in a row.  ``max_iter <= 0`` evaluates the start and returns it."""
+    overshoots into a region where five to eight trials are rejected in a row.  ``max_iter <= 0`` evaluates the start and returns it.
+
+    ``loss`` / ``f_scale``: scipy ``least_squares``'s robust losses ('linear', 'huber', 'soft_l1', 'cauchy', 'arctan'), applied to each
+    scalar residual with scipy's linearisation (include/pcs_hip.h pcs_set_loss): the result's ``cost`` is scipy's ``0.5 * sum rho0`` and
+    ``grad`` is J^T (rho1 f).  The engine's loss is set for the solve and restored afterwards.  Hand-fused chains with the blocked step
+    only: a robust loss with ``linear_solver='pcg'``, with a caller's ``operator`` or with a generated chain raises NotImplementedError."""
+    if loss not in LOSS_IDS:
+        raise ValueError(f"unknown loss {loss!r}: expected one of {sorted(LOSS_IDS)}")
+    f_scale = float(f_scale)
+    if not (np.isfinite(f_scale) and f_scale > 0.0):
+        raise ValueError(f"f_scale must be finite and > 0, got {f_scale}")
     if linear_solver not in ("auto", "pcg", "cholesky"):
         raise ValueError("linear_solver must be 'auto', 'pcg' or 'cholesky'")
+    robust = loss != "linear"
+    if robust and linear_solver == "pcg":
+        raise NotImplementedError(f"loss={loss!r}: the matrix-free products of linear_solver='pcg' use the raw Jacobian; "
+                                  "a robust loss needs the blocked normal equations (linear_solver='cholesky' or 'auto')")
+    if robust and operator is not None:
+        raise NotImplementedError(f"loss={loss!r} with a caller-supplied operator: the operator's products know nothing of the loss")
     op_fun = handler.op_fun
     lam0_exact, lam0_pcg = (LAM0_EXACT, 1e-3) if lam0 is None else (float(lam0), float(lam0))
     grow0 = LAM_GROW0 if lam_grow0 is None else float(lam_grow0)
@@ -690,14 +709,22 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
         dd = handler._flat_detections()
         eng = op_fun._engine_for(dd)
         op_fun._bind_template(eng, handler._template_arg())
+        if robust and not isinstance(eng, Engine):
+            raise NotImplementedError(f"loss={loss!r}: generated chains (ChainProblem) build their normal equations without a robust loss")
         if linear_solver == "auto":   # blocked J^T J while its regions fit comfortably; beyond that matrix-free CG
             linear_solver = "cholesky" if blocked_fits(eng) else "pcg"
+        if robust and linear_solver == "pcg":
+            raise NotImplementedError(f"loss={loss!r}: this system is too large for the blocked normal equations (linear_solver='auto' chose "
+                                      "'pcg', whose matrix-free products use the raw Jacobian)")
         if linear_solver == "cholesky":
             # the solver's device workspace (two packed states, V, S, a stream) lives with the engine: a second solve on the same
             # table and mask — the usual case: a calibration re-run with other start values or tolerances — allocates nothing
             mask = np.asarray(handler._jac_mask(), dtype=bool)
             # (... and layout: a generated chain changes it with set_option("dense_normal", ...) — buffers sized for the other form would be overrun)
-            key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())))
+            # (... and the loss: nothing in the state depends on it — the engine's loss is set per solve below — but a state is never
+            # carried from one loss to another.  The cache holds ONE state: a miss drops the previous one, so a sweep over f_scale
+            # re-allocates per value instead of accumulating workspaces)
+            key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())), loss, f_scale)
             cache = eng.__dict__.setdefault("_blocked_solvers", {})
             ne = cache.get(key)
             if ne is None:
@@ -707,7 +734,14 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
                 ne = cache[key] = BlockedNormalEquations(eng, mask, reduce_fn=reduce_fn)
             ne.spd_algorithm = "auto"
             ps0 = op_fun.build_param_list(*handler.get_bundle_adjustment_inputs(np.array(x0, dtype=np.float64)))
-            return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
+            if not isinstance(eng, Engine):   # generated chains: linear only (checked above)
+                return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
+            saved_loss = eng.loss()
+            eng.set_loss(loss, f_scale)
+            try:
+                return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
+            finally:
+                eng.set_loss(*saved_loss)
         operator = JacobianOperator(eng, handler._jac_mask(), reduce_fn=reduce_fn)
     elif linear_solver == "auto":
         linear_solver = "cholesky" if hasattr(operator, "build") else "pcg"

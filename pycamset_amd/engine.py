@@ -162,6 +162,21 @@ class Engine:
         check(lib().pcs_set_option(self._h, key.encode(), int(value)))
         self.__dict__.setdefault("_options", {})[key] = int(value)
 
+    def set_loss(self, kind: str, f_scale: float = 1.0):
+        """Robust loss of every normal-equation build of this engine (``normal_equations*``, ``normal_blocks_device``, ``lm_trial*``),
+        with scipy.optimize.least_squares's names and semantics: ``kind`` in 'linear' (the default), 'huber', 'soft_l1', 'cauchy',
+        'arctan', applied to each scalar residual; ``f_scale`` finite and > 0.  ``eval*`` and the matrix-free products keep the raw
+        residuals and J (include/pcs_hip.h pcs_set_loss)."""
+        if kind not in _capi.LOSS_IDS:
+            raise ValueError(f"unknown loss {kind!r}: expected one of {sorted(_capi.LOSS_IDS)}")
+        check(lib().pcs_set_loss(self._h, _capi.LOSS_IDS[kind], float(f_scale)))
+
+    def loss(self) -> tuple[str, float]:
+        """The current (kind, f_scale) of ``set_loss``."""
+        k, fs = ctypes.c_int(0), c_double(0.0)
+        check(lib().pcs_get_loss(self._h, byref(k), byref(fs)))
+        return {v: n for n, v in _capi.LOSS_IDS.items()}[k.value], fs.value
+
     def option(self, key: str, default: int) -> int:
         """The value last given to ``set_option(key, ...)`` through this object, else ``default`` (the library's own default)."""
         return self.__dict__.get("_options", {}).get(key, default)

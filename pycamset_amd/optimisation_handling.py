@@ -37,9 +37,12 @@ def make_optimisation_function(param_handler, threads: int = 1):
 
 def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy", linear_solver: str = "auto"):
     """Solve the handler's problem; returns (result, parameter slabs at the solution) — oh:52-117.
-    ``solver='device'`` runs device_solver.lm_solve with ``linear_solver`` in {'auto', 'cholesky', 'pcg'}."""
+    ``solver='device'`` runs device_solver.lm_solve with ``linear_solver`` in {'auto', 'cholesky', 'pcg'}.
+    Optional ``problem_opts['loss']`` / ``['f_scale']`` (scipy's names, default 'linear' / 1.0 — the reference's call carries the
+    commented ``# loss = "cauchy"``, oh:96) go to whichever solver runs."""
     loss_fn, jac_fn, x0 = make_optimisation_function(param_handler, threads)
     opts = param_handler.problem_opts
+    loss, f_scale = opts.get("loss", "linear"), opts.get("f_scale", 1.0)
     start_error = mean_reprojection_error(loss_fn(x0))
     log.info("%d parameters, %d residuals, start error %.2f px", len(x0), 2 * param_handler._flat_detections().shape[0], start_error)
     if not np.isfinite(start_error) or start_error > 150:  # the reference's sanity threshold (oh:80-83)
@@ -48,11 +51,11 @@ def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy"
     if solver == "device":
         from .device_solver import lm_solve
 
-        result = lm_solve(param_handler, x0, max_iter=opts["max_nfev"], linear_solver=linear_solver)
+        result = lm_solve(param_handler, x0, max_iter=opts["max_nfev"], linear_solver=linear_solver, loss=loss, f_scale=f_scale)
         end_error = mean_reprojection_error(loss_fn(result.x))
     else:
         result = least_squares(loss_fn, x0, jac=jac_fn if jac_fn is not None else "2-point", x_scale="jac",
-                               max_nfev=opts["max_nfev"], verbose=opts["verbosity"])
+                               max_nfev=opts["max_nfev"], verbose=opts["verbosity"], loss=loss, f_scale=f_scale)
         end_error = mean_reprojection_error(result.fun)
     log.info("solved in %.2f s, final error %.2f px", time.perf_counter() - tic, end_error)
     if end_error > 5:  # oh:105-107

@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--config", type=int, default=3)
     ap.add_argument("--chain", default="template")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--loss", default="",
+                    help="comma-separated robust losses: after the phases, the whole solve alternates between 'linear' and each of them "
+                         "(three rounds; lm_solve(loss=...), f_scale 1) — run under rocprofv3 --kernel-trace for the per-trial kernels")
     a = ap.parse_args()
     rig = synthetic.config_rig(a.config)
     cs = _Camset(rig.n_cams)
@@ -139,12 +142,16 @@ def main():
 
     print(f"  loop sections (host wall us): solve + trial string {wall(lambda: ne.solve(0, lam, ps, ps_new)):.0f}, build {wall(lambda: ne.build(ps_new, 1)):.0f}, "
           f"decision + read-back {wall(decide):.0f}")
-    for it in (30,):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = lm_solve(h, x0.copy(), max_iter=it)
-        dt = time.perf_counter() - t0
-        print(f"  lm_solve: {dt * 1e3:.2f} ms for {res.nfev} evaluations ({dt / res.nfev * 1e3:.3f} ms each), cost {res.cost:.6e}, {res.message}")
+    losses = ["linear"] + [x for x in a.loss.split(",") if x]
+    for rnd in range(3 if a.loss else 1):
+        for loss in losses:
+            lm_solve(h, x0.copy(), max_iter=2, loss=loss)   # the solver state of this loss (the cache holds one)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = lm_solve(h, x0.copy(), max_iter=30, loss=loss)
+            dt = time.perf_counter() - t0
+            print(f"  lm_solve loss {loss}: {dt * 1e3:.2f} ms for {res.nfev} evaluations ({dt / res.nfev * 1e3:.3f} ms each), cost {res.cost:.6e}, "
+                  f"{res.message}")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,8 @@
 #!/usr/bin/env python3
-"""Time the block-reduced normal-equations kernel (H = J^T J, g, cost) and the dense solve that follows it."""
+"""Time the block-reduced normal-equations kernel (H = J^T J, g, cost) and the dense solve that follows it.
+
+--loss=huber,cauchy,...  A/B of robust losses (Engine.set_loss) against the linear loss instead: the losses alternate with
+'linear' in rounds of ten builds each on the same engine, default geometry; prints the median kernel time of every round."""
 import sys, time
 from pathlib import Path
 import numpy as np
@@ -11,7 +14,7 @@ from pycamset_amd.engine import Engine
 configs = [(3, "template", False), (3, "template", True), (4, "self", False), (4, "free", False)]
 if "--only-default" in sys.argv:
     configs = [c for c in configs if not c[2]]
-if any(not a.startswith("--") for a in sys.argv[1:]):
+if any(not a.startswith("--") for a in sys.argv[1:]):  # chain names
     configs = [c for c in configs if c[1] in sys.argv[1:]]
 for cfg, chain, shuffle in configs:
     rig = synthetic.config_rig(cfg)
@@ -29,6 +32,22 @@ for cfg, chain, shuffle in configs:
     gd = torch.empty(n, dtype=torch.float64, device="cuda")
     cd = torch.empty(1, dtype=torch.float64, device="cuda")
     print(f"# {rig.name} chain {chain} N={det.shape[0]} n_params={n} shuffled={shuffle}  H = {n*n*8/1e6:.1f} MB")
+    loss_arg = [a for a in sys.argv[1:] if a.startswith("--loss=")]
+    if loss_arg:
+        losses = [x for x in loss_arg[0].split("=", 1)[1].split(",") if x]
+        for rnd in range(3):
+            for loss in ["linear"] + losses:
+                e.set_loss(loss, 1.0)
+                for _ in range(2):
+                    e.normal_equations_device(ps, Hd.data_ptr(), gd.data_ptr(), cd.data_ptr())
+                e.synchronize()
+                ks = []
+                for _ in range(10):
+                    e.normal_equations_device(ps, Hd.data_ptr(), gd.data_ptr(), cd.data_ptr()); e.synchronize(); ks.append(e.last_kernel_ms()[1])
+                print(f"round {rnd} loss {loss:8s}: kernels {np.median(ks)*1e3:8.1f} us")
+        e.set_loss("linear", 1.0)
+        e.close()
+        continue
     if "--phases" in sys.argv:   # option normal_debug: 2 = skip the flush atomics (results are wrong)
         for dbg in (2, 0):
             e.set_option("normal_debug", dbg)
