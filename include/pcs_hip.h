@@ -311,6 +311,25 @@ int pcs_dense_spd_solve(int device, int64_t n, double *d_S, int64_t ld, const do
 int pcs_dense_spd_solve_opts(int device, int64_t n, double *d_S, int64_t ld, const double *d_rhs, double *d_x, double *d_work, int32_t *d_status, void *stream,
                              int algorithm, int64_t timeout_us);
 
+/* Parameter covariance from the factor the solve above leaves in S (csrc/ba_covariance.hpp; version 102).  All pointers are device
+ * memory, queued on `stream` (NULL = the default stream); bad sizes or NULL pointers return PCS_ERR_ARG without touching the GPU.
+ *   pcs_cov_trsm        X <- L^-1 X in place, L = the LOWER triangle of d_L (n x n, row stride ldl; nothing above the diagonal is
+ *                       read), X = d_X (n x n_rhs, row stride ldx: V's layout).  flags PCS_COV_TRSM_IDENTITY: X is not read and
+ *                       becomes L^-1 (n_rhs = n), its zero upper part written too.  n <= 32 768.
+ *   pcs_cov_block_gram  for every block b < n_blocks: the w x w Gram matrix G_b = X[r0:, c : c + w]' X[r0:, c : c + w] of the
+ *                       n_rows x n_cols matrix d_X (row stride ldx), c = d_col[b], w = d_width[b] (1 .. 16), r0 = d_row0[b] (NULL: 0),
+ *                       written row-major to d_out + b * out_stride (d_out holds (n_blocks - 1) * out_stride + w^2 doubles); a block
+ *                       whose columns or rows leave X is written as NaN.  Finish options: with d_linvt (n_ent x tb x tb, L_e^-T as
+ *                       pcs_schur_prepare leaves it) block b is entity c / tb and becomes L_e^-T (I + G_b) L_e^-1 (w must be tb and
+ *                       c a multiple of tb); the result is multiplied by scale (times *d_scale when d_scale is not NULL); with
+ *                       d_fixed the rows and columns of parameters d_fixed[fixed_off + column] != 0 are set to exactly 0.  The
+ *                       result is symmetric; every sum is taken in a fixed order (no atomics): two calls return the same bits. */
+#define PCS_COV_TRSM_IDENTITY 1
+int pcs_cov_trsm(int device, int64_t n, const double *d_L, int64_t ldl, double *d_X, int64_t n_rhs, int64_t ldx, int flags, void *stream);
+int pcs_cov_block_gram(int device, const double *d_X, int64_t ldx, int64_t n_rows, int64_t n_cols, const int32_t *d_col, const int32_t *d_width,
+                       const int32_t *d_row0, int64_t n_blocks, double *d_out, int64_t out_stride, const double *d_linvt, int64_t tb,
+                       const uint8_t *d_fixed, int64_t fixed_off, const double *d_scale, double scale, void *stream);
+
 /* Which entry of H / g / cost every accumulator register of the normal-equations kernel stands for (host function, no
  * GPU needed): out[m][lane][r][2], m < 2 MFMAs, lane < 64, r < 4 registers = the two local column ids (index into
  * a J row, 30 = the residual column) of D_m[(lane >> 4) + 4 r][lane & 15], or -1, -1 where the register is not owned.

@@ -34,6 +34,7 @@ class LmBuffers(ctypes.Structure):
 
 LM_FIXED_TRIAL_BUFFER, LM_VOTES = 1, 2   # include/pcs_hip.h PCS_LM_*
 LM_STATS = 12                            # doubles in a trial's read-back (and in the control block)
+COV_TRSM_IDENTITY = 1                    # include/pcs_hip.h PCS_COV_TRSM_IDENTITY
 
 
 SYMBOLS = {
@@ -77,6 +78,8 @@ SYMBOLS = {
     "pcs_dense_spd_solve": (c_int, [c_int, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
     "pcs_dense_spd_solve_algo": (c_int, [c_int, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int]),
     "pcs_dense_spd_solve_opts": (c_int, [c_int, c_int64, _P, c_int64, _P, _P, _P, _P, _P, c_int, c_int64]),
+    "pcs_cov_trsm": (c_int, [c_int, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int, _P]),
+    "pcs_cov_block_gram": (c_int, [c_int, _P, c_int64, c_int64, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_double, _P]),
     "pcs_normal_descriptors": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
     "pcs_genchain_create": (c_int, [POINTER(_P), c_char_p, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int32), c_int, POINTER(c_int64), c_int64, c_int64,
                                     c_int64, c_int64, c_int64, c_int64, c_int, c_int]),

@@ -32,6 +32,7 @@
 #include "ba_lm_fused.hpp"
 #include "ba_dense_chol.hpp"
 #include "ba_chol_persist.hpp"
+#include "ba_covariance.hpp"
 #include "ba_triangulate.hpp"
 
 // ---------------------------------------------------------------------------------------------
@@ -246,7 +247,7 @@ static void free_det_tables(pcs_engine *h) {
 
 extern "C" {
 
-int pcs_version(void) { return 101; }
+int pcs_version(void) { return 102; }
 const char *pcs_last_error(void) { return g_err.c_str(); }
 
 // ---- batched triangulation: a handle that owns the camera table, the observation buffers and the
@@ -2169,6 +2170,37 @@ int pcs_schur_vtx(int device, int64_t n_lead, int64_t n_trail, const double *d_V
     if (n_trail == 0) return PCS_OK;
     HIPCHK(hipSetDevice(device));
     launch_schur_vtx(d_V, d_x, d_w, (int)n_lead, (int)n_trail, (int)ldv, nullptr, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return PCS_OK;
+}
+
+int pcs_cov_trsm(int device, int64_t n, const double *d_L, int64_t ldl, double *d_X, int64_t n_rhs, int64_t ldx, int flags, void *stream) {
+    const bool identity = (flags & PCS_COV_TRSM_IDENTITY) != 0;
+    if (n <= 0 || n > (1 << 15) || n_rhs <= 0 || n_rhs > (1ll << 30) || ldl < n || ldx < n_rhs || !d_L || !d_X || (flags & ~PCS_COV_TRSM_IDENTITY) ||
+        (identity && n_rhs != n) || n * ldx > (1ll << 40))
+        return fail(PCS_ERR_ARG, "pcs_cov_trsm: bad arguments");
+    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_cov_trsm: device %d not available", device);
+    HIPCHK(hipSetDevice(device));
+    const CovTrsmArgs a{d_L, d_X, ldl, ldx, (int32_t)n, (int32_t)n_rhs, identity ? 1 : 0};
+    hipLaunchKernelGGL(cov_trsm_kernel, dim3((unsigned)((n_rhs + COV_NB - 1) / COV_NB)), dim3(256), 0, (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
+    return PCS_OK;
+}
+
+int pcs_cov_block_gram(int device, const double *d_X, int64_t ldx, int64_t n_rows, int64_t n_cols, const int32_t *d_col, const int32_t *d_width,
+                       const int32_t *d_row0, int64_t n_blocks, double *d_out, int64_t out_stride, const double *d_linvt, int64_t tb,
+                       const uint8_t *d_fixed, int64_t fixed_off, const double *d_scale, double scale, void *stream) {
+    if (n_rows <= 0 || n_rows > (1ll << 30) || n_cols <= 0 || n_cols > (1ll << 30) || ldx < n_cols || !d_X || !d_col || !d_width || n_blocks < 0 ||
+        n_blocks > (1ll << 31) - 1 || (n_blocks && !d_out) || out_stride < 1 || (d_linvt && (tb < 1 || tb > COV_NB)) || fixed_off < 0 || !(scale == scale))
+        return fail(PCS_ERR_ARG, "pcs_cov_block_gram: bad arguments");
+    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_cov_block_gram: device %d not available", device);
+    if (n_blocks == 0) return PCS_OK;
+    HIPCHK(hipSetDevice(device));
+    CovGramArgs a{};
+    a.X = d_X; a.ldx = ldx; a.n_rows = (int32_t)n_rows; a.n_cols = (int32_t)n_cols; a.n_blocks = (int32_t)n_blocks;
+    a.col = d_col; a.width = d_width; a.row0 = d_row0; a.out = d_out; a.out_stride = out_stride;
+    a.linvt = d_linvt; a.tb = (int32_t)tb; a.fixed = d_fixed; a.fixed_off = fixed_off; a.scale_dev = d_scale; a.scale = scale;
+    hipLaunchKernelGGL(cov_gram_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, a);
     HIPCHK(hipGetLastError());
     return PCS_OK;
 }

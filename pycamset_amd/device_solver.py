@@ -665,6 +665,19 @@ class _CholeskyStep:
         return delta.cpu().numpy(), 1, pred
 
 
+def _blocked_solver(eng, mask, reduce_fn, loss, f_scale) -> BlockedNormalEquations:
+    """The engine's cached solver state for this mask, collective, layout and loss (one state per engine: a miss drops the previous one)."""
+    key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())), loss, f_scale)
+    cache = eng.__dict__.setdefault("_blocked_solvers", {})
+    ne = cache.get(key)
+    if ne is None:
+        for old in cache.values():   # a speculative trial of the solver state being dropped may still be draining: its buffers go back to the allocator after that
+            old.stream.synchronize()
+        cache.clear()
+        ne = cache[key] = BlockedNormalEquations(eng, mask, reduce_fn=reduce_fn)
+    return ne
+
+
 def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float = 1e-8, gtol: float = 1e-8,
              cg_tol: float = 1e-3, cg_max_iter: int = 200, lam0: float | None = None, lam_grow0: float | None = None, reduce_fn=None, verbose: int = 0,
              operator=None, linear_solver: str = "auto", loss: str = "linear", f_scale: float = 1.0) -> DeviceLMResult:
@@ -724,14 +737,7 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
             # (... and the loss: nothing in the state depends on it — the engine's loss is set per solve below — but a state is never
             # carried from one loss to another.  The cache holds ONE state: a miss drops the previous one, so a sweep over f_scale
             # re-allocates per value instead of accumulating workspaces)
-            key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())), loss, f_scale)
-            cache = eng.__dict__.setdefault("_blocked_solvers", {})
-            ne = cache.get(key)
-            if ne is None:
-                for old in cache.values():   # a speculative trial of the solver state being dropped may still be draining: its buffers go back to the allocator after that
-                    old.stream.synchronize()
-                cache.clear()
-                ne = cache[key] = BlockedNormalEquations(eng, mask, reduce_fn=reduce_fn)
+            ne = _blocked_solver(eng, mask, reduce_fn, loss, f_scale)
             ne.spd_algorithm = "auto"
             ps0 = op_fun.build_param_list(*handler.get_bundle_adjustment_inputs(np.array(x0, dtype=np.float64)))
             if not isinstance(eng, Engine):   # generated chains: linear only (checked above)
@@ -799,3 +805,204 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
             break
     return DeviceLMResult(x=x, cost=0.5 * st["sumsq"], grad=st["g"], optimality=float(np.max(np.abs(st["g"]))), nit=it, nfev=nfev,
                           n_jtjv=n_lin, status=status, message=message, history=history)
+
+
+@dataclass
+class ParameterCovariance:
+    std: np.ndarray          # (n_free,) standard errors, in the order of x
+    blocks: list             # one array per slab of handler.get_bundle_adjustment_inputs(x): (rows, w, w); 0 at fixed entries
+    sigma2: float            # the residual variance used (1.0 with absolute_sigma)
+    dof: int                 # 2N - n_free
+    cost: float              # 0.5 sum r^2 at x
+    min_pivot: float = 0.0   # smallest L_ii^2 / H_ii over the free parameters (the rank test against rcond)
+
+
+def _slab_layout(slabs):
+    """(offset, rows, width) of every slab in the parameter string (the slabs' concatenation, build_param_list's order)."""
+    out, off = [], 0
+    for s in slabs:
+        s = np.asarray(s)
+        rows = s.shape[0] if s.ndim else 1
+        w = s.size // rows if rows else 0
+        out.append((off, rows, w))
+        off += s.size
+    return out, off
+
+
+def _covariance_plan(ne: BlockedNormalEquations, layout):
+    """Device descriptors of the block Gram launches: leading slabs read column blocks of L^-1 (rows from the block's first column
+    on: L^-1 is lower triangular), the trailing group is one tb x tb block per entity of Z = L^-1 V, finished with L_e^-T."""
+    torch = ne.torch
+    plan = []
+    for off, rows, w in layout:
+        if rows == 0 or w == 0:
+            plan.append(("empty", off, rows, w, None))
+        elif off + rows * w <= ne.n_lead:
+            if w > 16:
+                raise NotImplementedError(f"slab rows of {w} parameters: the block Gram kernel takes at most 16 columns")
+            cols = (off + w * np.arange(rows)).astype(np.int32)
+            d = torch.from_numpy(np.stack([cols, np.full(rows, w, np.int32), cols])).to(ne.dev)
+            plan.append(("lead", off, rows, w, d))
+        elif off >= ne.n_params - ne.n_trail:
+            o = off - (ne.n_params - ne.n_trail) + w * np.arange(rows)
+            if np.any(o % ne.tb + w > ne.tb):
+                raise NotImplementedError(f"slab rows of {w} parameters straddle the trailing entities of {ne.tb}")
+            plan.append(("trail", off, rows, w, (o // ne.tb, o % ne.tb)))
+        else:
+            raise NotImplementedError("a slab straddles the leading and the trailing parameters")
+    trail = None
+    if ne.n_trail:
+        cols = (ne.tb * np.arange(ne.n_ent)).astype(np.int32)
+        trail = torch.from_numpy(np.stack([cols, np.full(ne.n_ent, ne.tb, np.int32)])).to(ne.dev)
+    return plan, trail
+
+
+def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: float = 1e-10, reduce_fn=None) -> ParameterCovariance:
+    """Marginal covariance blocks and standard errors of the parameters at ``x`` (the free vector, scipy's ``result.x`` order), from
+    the blocked normal equations on the device: H = J'J with the linear loss and no damping, fixed parameters
+    as identity rows and columns; sigma^2 = sum r^2 / (2N - n_free), or 1 with ``absolute_sigma`` (scipy curve_fit's meaning);
+    the leading blocks are sigma^2 S^-1 (S = A - V V' = L L', column blocks of L^-1), the trailing ones
+    sigma^2 L_e^-T (I + Z_e' Z_e) L_e^-1 with Z = L^-1 V formed in place of V.  Only the blocks come back to the host.
+
+    Raises np.linalg.LinAlgError when H is singular or nearly so (a non-positive pivot, a trailing block that is not positive
+    definite, or min L_ii^2 / H_ii below ``rcond``): a free gauge or an unobserved parameter.  ValueError for a wrong ``len(x)``
+    or 2N - n_free <= 0, NotImplementedError for sharded systems (``reduce_fn``)."""
+    if reduce_fn is not None:
+        raise NotImplementedError("parameter_covariance of a sharded system (reduce_fn) is not supported: run it on one rank with all detections")
+    rcond = float(rcond)
+    if not (np.isfinite(rcond) and rcond >= 0.0):
+        raise ValueError(f"rcond must be finite and >= 0, got {rcond}")
+    x = np.asarray(x, dtype=np.float64).ravel()
+    mask = np.asarray(handler._jac_mask(), dtype=bool)
+    n_free = int(mask.sum())
+    if x.shape[0] != n_free:
+        raise ValueError(f"x has {x.shape[0]} entries, the handler has {n_free} free parameters")
+    dd = handler._flat_detections()
+    dof = 2 * int(dd.shape[0]) - n_free
+    if dof <= 0:
+        raise ValueError(f"no degrees of freedom left: 2N = {2 * int(dd.shape[0])} residuals for {n_free} free parameters")
+    slabs = handler.get_bundle_adjustment_inputs(x)
+    layout, n_str = _slab_layout(slabs)
+    if n_str != mask.shape[0]:
+        raise ValueError(f"the slabs hold {n_str} parameters, the mask {mask.shape[0]}")
+
+    op_fun = handler.op_fun
+    eng = op_fun._engine_for(dd)
+    op_fun._bind_template(eng, handler._template_arg())
+    if not blocked_fits(eng):
+        raise NotImplementedError("this system is too large for the blocked normal equations (device_solver.blocked_fits)")
+    ne = _blocked_solver(eng, mask, None, "linear", 1.0)
+    ne.stream.synchronize()   # a speculative trial of the last solve may still be draining on this state
+    torch = ne.torch
+    from .engine import cov_block_gram, cov_trsm, dense_spd_solve, schur_syrk
+
+    plan_key = tuple(layout)
+    if getattr(ne, "_cov_plan", (None,))[0] != plan_key:
+        ne._cov_plan = (plan_key,) + _covariance_plan(ne, layout)
+    _, plan, trail_desc = ne._cov_plan
+    robust = isinstance(eng, Engine)
+    saved_loss = eng.loss() if robust else None
+    nl, nt, dev = ne.n_lead, ne.n_trail, eng.device
+    try:
+        if robust:
+            eng.set_loss("linear", 1.0)
+        with torch.cuda.device(ne.dev), torch.cuda.stream(ne.stream):
+            stream = ne.stream.cuda_stream
+            ps = torch.from_numpy(np.ascontiguousarray(op_fun.build_param_list(*slabs), dtype=np.float64)).to(ne.dev)
+            ne.build(ps, 0)
+            lam = torch.zeros(1, dtype=torch.float64, device=ne.dev)
+            det = bool(eng.option("deterministic", 0))
+            for algorithm in ("auto", "launches"):
+                ne.status.zero_()
+                eng.schur_prepare(ne.packed[0].data_ptr(), ne.fixed.data_ptr(), lam.data_ptr(), ne.linvt.data_ptr(), ne.u.data_ptr(), ne.V.data_ptr(),
+                                  ne.S.data_ptr(), ne.rhs.data_ptr(), ne.dvec.data_ptr(), ne.gm.data_ptr(), ne.status.data_ptr(), stream)
+                if nt:
+                    schur_syrk(dev, nl, nt, ne.V.data_ptr(), ne.V.shape[1], ne.S.data_ptr(), nl, ne.u.data_ptr(), ne.rhs.data_ptr(), stream,
+                               work=ne.syrk_work.data_ptr() if det else None, work_len=ne.syrk_work_len)
+                dense_spd_solve(dev, nl, ne.S.data_ptr(), nl, ne.rhs.data_ptr(), ne.xl.data_ptr(), ne.chol_work.data_ptr(), ne.status.data_ptr(), stream,
+                                algorithm=algorithm, timeout_us=eng.option("spd_timeout_us", None))
+                status = int(ne.status.item())
+                if not status & 4:   # bit 2: the one-launch solve gave up waiting; S is rebuilt and factored launch by launch
+                    break
+            if status & 4:
+                raise RuntimeError("the dense factorisation did not complete")
+            names = _param_names(layout)
+            # rank test: L_ii^2 / H_ii over the free parameters (leading: the factor of S; trailing: 1 / diag(L_e^-T)), reduced here;
+            # a failed factorisation leaves NaN behind its first non-positive pivot: counted as 0
+            piv = torch.empty(ne.n_params, dtype=torch.float64, device=ne.dev)
+            piv[:nl] = torch.diagonal(ne.S) ** 2
+            if nt:
+                piv[nl:] = 1.0 / torch.diagonal(ne.linvt[: ne.n_ent * ne.tb * ne.tb].view(ne.n_ent, ne.tb, ne.tb), dim1=1, dim2=2).reshape(-1) ** 2
+            ratio = torch.where(ne.fixed.bool(), torch.full_like(piv, float("inf")), piv / ne.dvec)
+            ratio = torch.where(torch.isnan(ratio), torch.zeros_like(ratio), ratio)
+            k = int(torch.argmin(ratio).item())
+            min_pivot = float(ratio[k].item()) if n_free else float("inf")
+            hint = "a free gauge (fix a reference camera or pose) or an unobserved parameter"
+            if status & 1:
+                raise np.linalg.LinAlgError(f"H is singular: a trailing block (one pose or point) is not positive definite — {hint}")
+            if status & 2:
+                raise np.linalg.LinAlgError(f"H is singular: a non-positive pivot in the reduced system (min L_ii^2 / H_ii = {min_pivot:.3e}) — {hint}")
+            if min_pivot < rcond:
+                raise np.linalg.LinAlgError(f"H is rank deficient at parameter {k} ({names(k)}): L_ii^2 / H_ii = {min_pivot:.3e} < rcond = {rcond:.1e} — {hint}")
+            # L^-1 (zeros above the diagonal skipped) and Z = L^-1 V in place of V
+            linv = torch.empty((nl, nl), dtype=torch.float64, device=ne.dev)
+            cov_trsm(dev, nl, ne.S.data_ptr(), nl, linv.data_ptr(), nl, nl, identity=True, stream=stream)
+            if nt:
+                cov_trsm(dev, nl, ne.S.data_ptr(), nl, ne.V.data_ptr(), nt, ne.V.shape[1], stream=stream)
+            d_cost = 0 if absolute_sigma else ne.packed[0].data_ptr() + 8 * (ne.n_packed - 1)
+            scale = 1.0 if absolute_sigma else 1.0 / dof
+            outs = []
+            for kind, off, rows, w, d in plan:
+                if kind != "lead":
+                    outs.append(None)
+                    continue
+                o = torch.empty(rows * w * w, dtype=torch.float64, device=ne.dev)
+                cov_block_gram(dev, linv.data_ptr(), nl, nl, nl, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), rows, o.data_ptr(), w * w,
+                               d_fixed=ne.fixed.data_ptr(), fixed_off=0, d_scale=d_cost or None, scale=scale, stream=stream)
+                outs.append(o)
+            ent = None
+            if nt:
+                ent = torch.empty(ne.n_ent * ne.tb * ne.tb, dtype=torch.float64, device=ne.dev)
+                cov_block_gram(dev, ne.V.data_ptr(), ne.V.shape[1], nl, nt, trail_desc[0].data_ptr(), trail_desc[1].data_ptr(), None, ne.n_ent,
+                               ent.data_ptr(), ne.tb * ne.tb, d_linvt=ne.linvt.data_ptr(), tb=ne.tb, d_fixed=ne.fixed.data_ptr(), fixed_off=nl,
+                               d_scale=d_cost or None, scale=scale, stream=stream)
+            parts = [o for o in outs if o is not None] + ([ent] if ent is not None else [])
+            host = torch.cat(parts + [ne.cost(0).reshape(1)]).cpu().numpy() if parts else ne.cost(0).reshape(1).cpu().numpy()
+    finally:
+        ne.status.zero_()
+        ne.stream.synchronize()
+        if robust:
+            eng.set_loss(*saved_loss)
+    sumsq = float(host[-1])
+    at = 0
+    chunks = []
+    for o in outs:
+        if o is not None:
+            chunks.append(host[at: at + o.numel()])
+            at += o.numel()
+    ent_h = host[at: at + ne.n_ent * ne.tb * ne.tb].reshape(ne.n_ent, ne.tb, ne.tb) if nt else None
+    blocks, diag = [], np.zeros(ne.n_params)
+    it = iter(chunks)
+    for kind, off, rows, w, d in plan:
+        if kind == "lead":
+            b = next(it).reshape(rows, w, w)
+        elif kind == "trail":
+            e, o = d
+            idx = o[:, None] + np.arange(w)[None, :]
+            b = ent_h[e[:, None, None], idx[:, :, None], idx[:, None, :]]
+        else:
+            b = np.zeros((rows, w, w))
+        blocks.append(b)
+        if rows and w:
+            diag[off: off + rows * w] = np.diagonal(b, axis1=1, axis2=2).reshape(-1)
+    sigma2 = 1.0 if absolute_sigma else sumsq / dof
+    return ParameterCovariance(std=np.sqrt(diag[mask]), blocks=blocks, sigma2=sigma2, dof=dof, cost=0.5 * sumsq, min_pivot=min_pivot)
+
+
+def _param_names(layout):
+    def name(k):
+        for i, (off, rows, w) in enumerate(layout):
+            if off <= k < off + rows * w:
+                return f"slab {i}, row {(k - off) // w}, column {(k - off) % w}"
+        return "?"
+    return name

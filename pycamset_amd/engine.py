@@ -445,6 +445,25 @@ def schur_vtx(device: int, n_lead: int, n_trail: int, d_V: int, ldv: int, d_x: i
     check(lib().pcs_schur_vtx(int(device), int(n_lead), int(n_trail), c_void_p(d_V), int(ldv), c_void_p(d_x), c_void_p(d_w), s))
 
 
+def cov_trsm(device: int, n: int, d_L: int, ldl: int, d_X: int, n_rhs: int, ldx: int, identity: bool = False, stream: int | None = None):
+    """X <- L^-1 X in place on the device, L = the lower triangle of d_L (csrc/ba_covariance.hpp; raw float64 device addresses).
+    ``identity``: X is not read and becomes L^-1 (n_rhs = n)."""
+    s = c_void_p(0) if stream is None else _stream_arg(stream)
+    check(lib().pcs_cov_trsm(int(device), int(n), c_void_p(d_L), int(ldl), c_void_p(d_X), int(n_rhs), int(ldx), _capi.COV_TRSM_IDENTITY if identity else 0, s))
+
+
+def cov_block_gram(device: int, d_X: int, ldx: int, n_rows: int, n_cols: int, d_col: int, d_width: int, d_row0: int | None, n_blocks: int, d_out: int,
+                   out_stride: int, d_linvt: int | None = None, tb: int = 0, d_fixed: int | None = None, fixed_off: int = 0, d_scale: int | None = None,
+                   scale: float = 1.0, stream: int | None = None):
+    """Block b: X[r0_b:, c_b : c_b + w_b]' X[r0_b:, c_b : c_b + w_b] -> d_out + b * out_stride (csrc/ba_covariance.hpp; int32 descriptor
+    arrays on the device).  Finish options: the sandwich L_e^-T (I + G) L_e^-1 with ``d_linvt``, the factor ``scale`` (times the device
+    scalar ``d_scale``), exact zeros at the parameters ``d_fixed[fixed_off + column]`` marks."""
+    s = c_void_p(0) if stream is None else _stream_arg(stream)
+    check(lib().pcs_cov_block_gram(int(device), c_void_p(d_X), int(ldx), int(n_rows), int(n_cols), c_void_p(d_col), c_void_p(d_width), c_void_p(d_row0 or 0),
+                                   int(n_blocks), c_void_p(d_out), int(out_stride), c_void_p(d_linvt or 0), int(tb), c_void_p(d_fixed or 0), int(fixed_off),
+                                   c_void_p(d_scale or 0), float(scale), s))
+
+
 def dense_spd_work_len(n: int) -> int:
     return int(lib().pcs_dense_spd_work_len(int(n)))
 
