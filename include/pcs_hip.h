@@ -363,6 +363,17 @@ int pcs_normal_descriptors(int chain, int pass, int trail_group, int32_t *out);
  * (`data[:n][good_mask]`, afb:644-651, never exists as a dense array): keep[i] bit j = local column j of detection i is free,
  * row_off[i] = offset of its u row in the data array.
  */
+/*
+ * The device Jacobian check of ONE user block (abstract_function_block.test_self, the reference's test_self of afb:750-775):
+ * pycamset_amd/chain_compiler.py compiles the block's device bodies with csrc/ba_blockcheck.hpp into code_object_path.  points:
+ * m rows of [params(np), inp(nin, or the 3 template coordinates when templated)].  Per point: fun_out (nout), jac_out
+ * (nout x (np + nin), compute_jac's layout) and fd_out (same layout: fourth-order central differences of fun with step
+ * eps^(1/5) max(1, |x_j|); template coordinates are not differentiated).  Synchronous, host buffers; PCS_ERR_ARG when the code
+ * object was built for another shape.  Since pcs_version() 103.
+ */
+int pcs_blockcheck(const char *code_object_path, int device, int np, int nin, int nout, int templated, const double *points, int64_t m,
+                   double *fun_out, double *jac_out, double *fd_out);
+
 typedef struct pcs_genchain pcs_genchain;
 int pcs_genchain_create(pcs_genchain **out, const char *code_object_path, int row_len, int uses_template, int n_groups, const int64_t *group_off,
                      const int32_t *group_count, int n_user, const int64_t *user_off, int64_t intr_off, int64_t point_off, int64_t n_params, int64_t n_cams,

@@ -84,6 +84,7 @@ SYMBOLS = {
     "pcs_genchain_create": (c_int, [POINTER(_P), c_char_p, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int32), c_int, POINTER(c_int64), c_int64, c_int64,
                                     c_int64, c_int64, c_int64, c_int64, c_int, c_int]),
     "pcs_genchain_destroy": (c_int, [_P]),
+    "pcs_blockcheck": (c_int, [c_char_p, c_int, c_int, c_int, c_int, c_int, POINTER(c_double), c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "pcs_genchain_row_len": (c_int, [_P]),
     "pcs_genchain_set_detections_table": (c_int, [_P, POINTER(c_double), c_int64]),
     "pcs_genchain_set_template": (c_int, [_P, POINTER(c_double)]),

@@ -36,6 +36,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import check, lib
+from .block_translate import PYBODY_HEADER, has_python_bodies, translate_block
 
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
@@ -66,6 +67,7 @@ class BlockInfo:
     device_jac: str = ""
     cpp_name: str = ""
     templated: bool = False    # user SOURCE with ``template = True``: its ``inp`` is the detection's template point (afb:138, afb:374-375)
+    translated: bool = False   # user block whose bodies were translated from Python (block_translate.py)
 
 
 @dataclass
@@ -118,9 +120,13 @@ class ChainSpec:
         rigid_id = user_id = 0
         for pos, b in enumerate(function_blocks):
             name = type(b).__name__
+            # device strings win; then the shipped blocks by name; then a user block's Python bodies, translated (block_translate.py)
             is_user = bool(getattr(b, "device_fun", None)) and bool(getattr(b, "device_jac", None))
+            python_bodies = not is_user and name not in BUILTIN_KINDS and has_python_bodies(b)
+            is_user = is_user or python_bodies
             if not is_user and name not in BUILTIN_KINDS:
-                raise bad(f"block {name} is neither one of the five shipped blocks nor a device_function_block (it has no device_fun / device_jac)")
+                raise bad(f"block {name} is neither one of the five shipped blocks nor a device_function_block (it has no device_fun / device_jac)"
+                          " nor a block with Python compute_fun / compute_jac bodies")
             kind = "user" if is_user else BUILTIN_KINDS[name]
             key = id(b.params)                      # the reference tells groups apart by object identity (afb:160-163)
             gkind = {"projection": "intr", "rigid": "rigid", "template_points": "rigid", "free_point": "point", "user": "user"}[kind]
@@ -143,7 +149,12 @@ class ChainSpec:
             if kind == "user":
                 if npar < 1 or info.nout < 1 or info.nin < 0:
                     raise bad(f"user block {name}: n_params >= 1, num_out >= 1, num_inp >= 0 expected")
-                info.uidx, info.device_fun, info.device_jac = user_id, str(b.device_fun), str(b.device_jac)
+                if python_bodies:
+                    info.device_fun, info.device_jac = translate_block(b)
+                    info.translated = True
+                else:
+                    info.device_fun, info.device_jac = str(b.device_fun), str(b.device_jac)
+                info.uidx = user_id
                 info.cpp_name = f"{''.join(ch if ch.isalnum() else '_' for ch in name)}_{user_id}"
                 info.templated = bool(getattr(b, "template", False))
                 if info.templated and (pos != len(names) - 1 or info.nin != 0):
@@ -187,6 +198,23 @@ class ChainSpec:
                     intr_off=intr[0] if intr else 0, point_off=point[0] if point else 0, user_off=[starts[b.group] for b in self.user_blocks])
 
 
+def user_struct_lines(b: BlockInfo) -> list:
+    """`struct user::<name>` with the block's two device bodies (shared by the chain's unit and the block check's, blockcheck_source)."""
+    return ["namespace user {",
+            f"struct {b.cpp_name} {{   // user block {b.uidx}: {b.name}",
+            f"    static constexpr int NP = {b.n_params}, NIN = {b.nin}, NOUT = {b.nout};",
+            "    // out[NOUT]",
+            "    __device__ static __forceinline__ void fun(const double *params, const double *inp, double *out) {",
+            b.device_fun,
+            "    }",
+            "    // out[NOUT x (NP + NIN)], row-major, parameter columns first (compute_jac's layout, afb:738-748)",
+            "    __device__ static __forceinline__ void jac(const double *params, const double *inp, double *out) {",
+            b.device_jac,
+            "    }",
+            "};",
+            "}  // namespace user"]
+
+
 def emit_source(spec: ChainSpec) -> str:
     """The translation unit of one chain: the user blocks' device bodies, `struct Chain` with the straight-line evaluation of one
     detection (forward right to left, chain rule left to right — what the reference writes into template_functions/*.py,
@@ -194,20 +222,10 @@ def emit_source(spec: ChainSpec) -> str:
     B, P = spec.blocks, spec.P
     nb = len(B)
     out = [f"// generated by pycamset_amd/chain_compiler.py for: {' + '.join(spec.names)}", '#include "ba_generic.hpp"']
+    if any(b.translated for b in spec.user_blocks):
+        out.append(f'#include "{PYBODY_HEADER}"')
     for b in spec.user_blocks:
-        out += ["namespace user {",
-                f"struct {b.cpp_name} {{   // user block {b.uidx}: {b.name}",
-                f"    static constexpr int NP = {b.n_params}, NIN = {b.nin}, NOUT = {b.nout};",
-                "    // out[NOUT]",
-                "    __device__ static __forceinline__ void fun(const double *params, const double *inp, double *out) {",
-                b.device_fun,
-                "    }",
-                "    // out[NOUT x (NP + NIN)], row-major, parameter columns first (compute_jac's layout, afb:738-748)",
-                "    __device__ static __forceinline__ void jac(const double *params, const double *inp, double *out) {",
-                b.device_jac,
-                "    }",
-                "};",
-                "}  // namespace user"]
+        out += user_struct_lines(b)
     fwd, rule = [], []
     col = 0
     cols = []
@@ -282,8 +300,13 @@ def _header_digest() -> str:
     return h.hexdigest()
 
 
+def _cache_key(text: str) -> str:
+    extra = (CSRC / PYBODY_HEADER).read_text() if f'#include "{PYBODY_HEADER}"' in text else ""
+    return hashlib.sha256((text + _header_digest() + extra + FP_CONTRACT).encode()).hexdigest()[:20]
+
+
 def code_object_path(spec: ChainSpec) -> Path:
-    key = hashlib.sha256((emit_source(spec) + _header_digest() + FP_CONTRACT).encode()).hexdigest()[:20]
+    key = _cache_key(emit_source(spec))
     return CACHE / f"chain_{'_'.join(''.join(ch for ch in n if ch.isalnum())[:4] for n in spec.names)}_{key}.hsaco"
 
 
@@ -345,13 +368,51 @@ def compile_chain(spec: ChainSpec, verbose: bool = False) -> Path:
     """gfx950 code object of the chain unless an up-to-date one is cached.  Compiler: hiprtc (runtime compilation: works on a box
     without hipcc — a runtime-only ROCm install — and without a GPU), hipcc --genco when hiprtc is missing or refuses the unit;
     ``PCS_CHAIN_COMPILER=hipcc|hiprtc`` forces one."""
-    out = code_object_path(spec)
+    return _compile_unit(emit_source(spec), code_object_path(spec), f"the chain {' + '.join(spec.names)}", verbose)
+
+
+def user_block_info(block) -> BlockInfo:
+    """A lone user block as the code generator sees it: device strings first, else its Python bodies translated."""
+    name = type(block).__name__
+    if bool(getattr(block, "device_fun", None)) and bool(getattr(block, "device_jac", None)):
+        fun, jac, translated = str(block.device_fun), str(block.device_jac), False
+    elif name not in BUILTIN_KINDS and has_python_bodies(block):
+        (fun, jac), translated = translate_block(block), True
+    else:
+        raise NotImplementedError(f"block {name} is not a user block: it has neither device_fun / device_jac nor Python compute_fun / compute_jac bodies"
+                                  + (" (the shipped blocks are covered by the golden tests)" if name in BUILTIN_KINDS else ""))
+    npar, nin, nout = int(block.params.n_params), int(block.num_inp), int(block.num_out)
+    if npar < 1 or nout < 1 or nin < 0:
+        raise NotImplementedError(f"user block {name}: n_params >= 1, num_out >= 1, num_inp >= 0 expected")
+    return BlockInfo(name=name, kind="user", link=int(block.params.link_type), n_params=npar, nin=nin, nout=nout, group=0, uidx=0,
+                     device_fun=fun, device_jac=jac, cpp_name=f"{''.join(ch if ch.isalnum() else '_' for ch in name)}_0",
+                     templated=bool(getattr(block, "template", False)) and nin == 0, translated=translated)
+
+
+def blockcheck_source(b: BlockInfo) -> str:
+    """The translation unit of one block's device Jacobian check (csrc/ba_blockcheck.hpp, pcs_blockcheck)."""
+    out = [f"// generated by pycamset_amd/chain_compiler.py: the Jacobian check of user block {b.name}", '#include "ba_blockcheck.hpp"']
+    if b.translated:
+        out.append(f'#include "{PYBODY_HEADER}"')
+    out += user_struct_lines(b)
+    out += [f"PCS_BLOCKCHECK_ENTRY_POINTS(user::{b.cpp_name}, {'true' if b.templated else 'false'})", ""]
+    return "\n".join(out)
+
+
+def compile_blockcheck(b: BlockInfo, verbose: bool = False) -> Path:
+    """gfx950 code object of one block's Jacobian check, compiled and cached like a chain."""
+    text = blockcheck_source(b)
+    key = hashlib.sha256((text + (CSRC / "ba_blockcheck.hpp").read_text() + _cache_key(text)).encode()).hexdigest()[:20]
+    out = CACHE / f"blockcheck_{''.join(ch for ch in b.name if ch.isalnum())[:12]}_{key}.hsaco"
+    return _compile_unit(text, out, f"the block check of {b.name}", verbose)
+
+
+def _compile_unit(text: str, out: Path, what: str, verbose: bool = False) -> Path:
     if out.exists():
         return out
     CACHE.mkdir(exist_ok=True)
     unique = f"{os.getpid()}.{uuid.uuid4().hex[:8]}"
     src = out.with_name(f".{out.stem}.{unique}.hip")      # private to this process until the object is published
-    text = emit_source(spec)
     src.write_text(text)
     try:
         which = os.environ.get("PCS_CHAIN_COMPILER", "auto")
@@ -364,7 +425,7 @@ def compile_chain(spec: ChainSpec, verbose: bool = False) -> Path:
                     print(f"hiprtc: {out}", flush=True)
                 return out
             if which == "hiprtc":
-                raise RuntimeError(f"hiprtc failed compiling the chain {' + '.join(spec.names)}:\n{log}")
+                raise RuntimeError(f"hiprtc failed compiling {what}:\n{log}")
         tmp = out.with_name(f".{out.name}.{unique}.tmp")
         cmd = [os.environ.get("HIPCC", "hipcc"), "--genco", "--offload-arch=gfx950", "-O3", "-std=c++17", FP_CONTRACT, f"-I{CSRC}", str(src), "-o", str(tmp)]
         if verbose:
@@ -372,9 +433,9 @@ def compile_chain(spec: ChainSpec, verbose: bool = False) -> Path:
         try:
             proc = subprocess.run(cmd, capture_output=True, text=True)
         except FileNotFoundError as e:
-            raise RuntimeError(f"no compiler for the chain {' + '.join(spec.names)}: hiprtc said `{log}`, and hipcc is not installed ({e})") from None
+            raise RuntimeError(f"no compiler for {what}: hiprtc said `{log}`, and hipcc is not installed ({e})") from None
         if proc.returncode != 0 or not tmp.exists():
-            raise RuntimeError(f"hipcc failed compiling the chain {' + '.join(spec.names)}:\n{proc.stderr[-2000:]}")
+            raise RuntimeError(f"hipcc failed compiling {what}:\n{proc.stderr[-2000:]}")
         _publish(out, tmp=tmp)
         src.replace(out.with_suffix(".hip"))
         return out

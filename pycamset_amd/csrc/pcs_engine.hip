@@ -247,7 +247,7 @@ static void free_det_tables(pcs_engine *h) {
 
 extern "C" {
 
-int pcs_version(void) { return 102; }
+int pcs_version(void) { return 103; }
 const char *pcs_last_error(void) { return g_err.c_str(); }
 
 // ---- batched triangulation: a handle that owns the camera table, the observation buffers and the

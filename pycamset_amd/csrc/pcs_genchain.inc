@@ -9,6 +9,7 @@
 #include "ba_generic.hpp"
 #include "ba_blockrow.hpp"
 #include "ba_blockgram.hpp"
+#include "ba_blockcheck.hpp"
 
 struct pcs_genchain {
     int device = 0;
@@ -786,6 +787,64 @@ int pcs_genchain_last_kernel_ms(pcs_genchain *h, float *slab_prep_ms, float *eva
     if (slab_prep_ms) *slab_prep_ms = a;
     if (eval_ms) *eval_ms = b;
     return PCS_OK;
+}
+
+// The device Jacobian check of one user block (csrc/ba_blockcheck.hpp; abstract_function_block.test_self).  Synchronous; host buffers in
+// and out; its own stream and buffers.  The code object states the shape it was built for (pcs_blockcheck_shape) and must agree.
+int pcs_blockcheck(const char *code_object_path, int device, int np, int nin, int nout, int templated, const double *points, int64_t m,
+                   double *fun_out, double *jac_out, double *fd_out) {
+    if (!code_object_path || np < 1 || nin < 0 || nout < 1 || m < 1 || !points || !fun_out || !jac_out || !fd_out || (templated && nin != 0) ||
+        np + nin > 64 || nout > 64 || m > ((int64_t)1 << 26))
+        return fail(PCS_ERR_ARG, "pcs_blockcheck: bad arguments");
+    const int ndev = pcs_device_count();
+    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "pcs_blockcheck: no HIP device visible (the block check has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "pcs_blockcheck: device %d out of range [0,%d)", device, ndev);
+    HIPCHK(hipSetDevice(device));
+    const int nrow = np + (templated ? 3 : nin), nc = np + nin;
+    hipModule_t mod = nullptr;
+    hipStream_t s = nullptr;
+    double *d_pts = nullptr, *d_out = nullptr;
+    auto done = [&](int code) {
+        if (s) (void)hipStreamSynchronize(s);
+        for (double *b : {d_pts, d_out})
+            if (b) (void)hipFree(b);
+        if (s) (void)hipStreamDestroy(s);
+        if (mod) (void)hipModuleUnload(mod);
+        return code;
+    };
+#define CHECK_CHK(expr)                                                                                   \
+    do {                                                                                                  \
+        hipError_t _e = (expr);                                                                           \
+        if (_e != hipSuccess) return done(fail(PCS_ERR_HIP, "%s failed: %s (pcs_blockcheck)", #expr, hipGetErrorString(_e))); \
+    } while (0)
+    CHECK_CHK(hipModuleLoad(&mod, code_object_path));
+    hipDeviceptr_t d_shape = nullptr;
+    size_t shape_bytes = 0;
+    CHECK_CHK(hipModuleGetGlobal(&d_shape, &shape_bytes, mod, "pcs_blockcheck_shape"));
+    int shape[4] = {};
+    if (shape_bytes != sizeof(shape)) return done(fail(PCS_ERR_ARG, "pcs_blockcheck: the code object is not a block check"));
+    CHECK_CHK(hipMemcpyDtoH(shape, d_shape, sizeof(shape)));
+    if (shape[0] != np || shape[1] != nin || shape[2] != nout || shape[3] != (templated ? 1 : 0))
+        return done(fail(PCS_ERR_ARG, "pcs_blockcheck: the code object checks a block of shape (np %d, nin %d, nout %d, templated %d), not (%d, %d, %d, %d)",
+                         shape[0], shape[1], shape[2], shape[3], np, nin, nout, templated ? 1 : 0));
+    hipFunction_t f = nullptr;
+    CHECK_CHK(hipModuleGetFunction(&f, mod, "pcs_blockcheck"));
+    CHECK_CHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    const size_t n_pts = (size_t)m * nrow, n_fun = (size_t)m * nout, n_jac = (size_t)m * nout * nc;
+    CHECK_CHK(hipMalloc(&d_pts, sizeof(double) * n_pts));
+    CHECK_CHK(hipMalloc(&d_out, sizeof(double) * (n_fun + 2 * n_jac)));
+    CHECK_CHK(hipMemcpyAsync(d_pts, points, sizeof(double) * n_pts, hipMemcpyHostToDevice, s));
+    CHECK_CHK(hipMemsetAsync(d_out, 0, sizeof(double) * (n_fun + 2 * n_jac), s));
+    BlockcheckArgs a{d_pts, m, d_out, d_out + n_fun, d_out + n_fun + n_jac};
+    void *params[] = {&a};
+    const int64_t threads = m * (nc + 1);
+    CHECK_CHK(hipModuleLaunchKernel(f, (uint32_t)((threads + 255) / 256), 1, 1, 256, 1, 1, 0, s, params, nullptr));
+    CHECK_CHK(hipMemcpyAsync(fun_out, d_out, sizeof(double) * n_fun, hipMemcpyDeviceToHost, s));
+    CHECK_CHK(hipMemcpyAsync(jac_out, d_out + n_fun, sizeof(double) * n_jac, hipMemcpyDeviceToHost, s));
+    CHECK_CHK(hipMemcpyAsync(fd_out, d_out + n_fun + n_jac, sizeof(double) * n_jac, hipMemcpyDeviceToHost, s));
+    CHECK_CHK(hipStreamSynchronize(s));
+#undef CHECK_CHK
+    return done(PCS_OK);
 }
 
 }  // extern "C"

@@ -18,8 +18,9 @@ chains the reference's handlers build run on hand-fused kernels (csrc/ba_kernels
 composition of the shipped blocks AND of user blocks (``device_function_block`` below: the reference's extension point,
 afb:689-775, with the two bodies given as device code) is compiled on first use into a fused kernel of its own
 (pycamset_amd/chain_compiler.py -> csrc/ba_generic.hpp, hipcc --genco) — the counterpart of the reference's code generator
-(afb:424-463, afb:492-652, mm:147-263).  A block that is neither shipped nor a device_function_block raises, loudly: there
-is no interpreter fallback.
+(afb:424-463, afb:492-652, mm:147-263).  A user block written like the reference's, with Python ``compute_fun`` /
+``compute_jac`` bodies, is translated into the same device code (pycamset_amd/block_translate.py); a block that is neither
+shipped, nor a device_function_block, nor translatable raises, loudly: there is no interpreter fallback.
 """
 from __future__ import annotations
 
@@ -65,6 +66,18 @@ class abstract_function_block:  # afb:689-748
         if isinstance(other, optimisation_function):
             return optimisation_function(other.function_blocks + [self])
         raise ValueError(f"could not combine function block with {other}")
+
+    def test_self(self, params=None, inp=None, *, n_points: int = 1024, rtol: float = 1e-6, atol: float = 1e-9, seed: int = 0, device: int = 0) -> dict:
+        """Check this user block's Jacobian against finite differences of its forward body, on the GPU (afb:750-775).
+
+        The points are the reference's all-ones point and ``n_points`` seeded points near it, or the caller's ``params`` (M, NP) /
+        ``inp`` (M, num_inp; a templated source: the (M, 3) template points).  Raises ``AssertionError`` naming the worst
+        (output row, column, point) when ``|jac - fd| > atol * rowscale + rtol * |fd|`` anywhere or when anything is non-finite;
+        for a block with Python bodies also when the translated device bodies disagree with the Python ones.  Returns a report
+        with the largest error per column.  Shipped blocks raise ``NotImplementedError`` (the golden tests cover them)."""
+        from .block_check import check_block
+
+        return check_block(self, params, inp, n_points=n_points, rtol=rtol, atol=atol, seed=seed, device=device)
 
 
 class device_function_block(abstract_function_block):

@@ -4,7 +4,10 @@ equations from the block rows, csrc/ba_blockgram.hpp + pcs_genchain_lm_trial) ag
 default (products of csrc/ba_blockrow.hpp, the host between every two) and — on small rigs — scipy's trf on the same closures
 (optimisation_handling.py:88-98).  The chain is `projection + extrinsic3D + rigidTform3d + board_flex`: the user-written templated
 source of tests/helpers.py (a board that bends, one flex model per image) on the rigs of BASELINE's configs.
-    python tools/genchain_lm.py --config 1 2 3 [--chain division] [--dense] [--trace]"""
+    python tools/genchain_lm.py --config 1 2 3 [--chain division] [--dense] [--trace] [--python-bodies]
+
+``--python-bodies`` runs the same user blocks written with Python bodies (tests/python_blocks.py, translated to device code by
+pycamset_amd/block_translate.py) instead of their hand-written device-string twins (tests/helpers.py): the A/B of the translator."""
 import argparse
 import sys
 import time
@@ -18,17 +21,18 @@ sys.path.insert(0, str(ROOT / "tests"))
 import torch
 
 import helpers as H
+import python_blocks as PB
 from pycamset_amd import function_blocks as fb
 from pycamset_amd import handlers, synthetic
 from pycamset_amd.device_solver import lm_solve
 
 
-def problem(number: int, which: str):
+def problem(number: int, which: str, python_bodies: bool = False):
     """`flex`: projection + extrinsic3D + rigidTform3d + board_flex (a user-written templated source, five parameters per image: the
     DENSE form of the normal equations); `division`: division_projection + extrinsic3D + template_points (a user-written lens model in
     place of the shipped projection; the chain ends in one rigid transform per image: the BLOCKED form, Schur step)."""
     rig = synthetic.config_rig(number)
-    ub = H.user_blocks(fb)
+    ub = PB.python_blocks() if python_bodies else H.user_blocks(fb)
     rng = np.random.default_rng(6)
     fix_ext = np.ones((rig.n_cams, 6), dtype=bool)
     fix_ext[0] = False
@@ -86,9 +90,10 @@ def main():
     ap.add_argument("--two-launch", action="store_true", help="slab preparation as a launch of its own in front of the evaluation")
     ap.add_argument("--deterministic", action="store_true", help="the ordered contraction and step (the same bits on every run)")
     ap.add_argument("--dense", action="store_true", help="the dense form of the normal equations also where the chain has the blocked one")
+    ap.add_argument("--python-bodies", action="store_true", help="the user blocks with Python bodies (translated) instead of device strings")
     a = ap.parse_args()
     for number in a.config:
-        rig, op, prob = problem(number, a.chain)
+        rig, op, prob = problem(number, a.chain, a.python_bodies)
         eng = op._engine_for(prob._flat_detections())
         if a.dense:
             eng.set_option("dense_normal", 1)
@@ -126,6 +131,16 @@ def main():
             e1.record()
             e1.synchronize()
         print(f"  build (evaluation + zeroing + contraction):    {e0.elapsed_time(e1) * 100:8.1f} us", flush=True)
+        d_r, d_j = eng.device_buffers()
+        with torch.cuda.stream(st):   # the evaluation step alone: residual + dense block rows into the handle's buffers
+            for _ in range(3):
+                eng.eval_device(ps_dev.data_ptr(), d_r, d_j, st.cuda_stream)
+            e0.record()
+            for _ in range(20):
+                eng.eval_device(ps_dev.data_ptr(), d_r, d_j, st.cuda_stream)
+            e1.record()
+            e1.synchronize()
+        print(f"  evaluation step (residual + block rows):       {e0.elapsed_time(e1) * 50:8.1f} us", flush=True)
         if a.phases:   # where the contraction's time goes: the same build without the flush / without the matrix products (results are garbage)
             for dbg, what in ((1, "no flush"), (2, "no contraction"), (3, "loads only")):
                 eng.set_option("gram_debug", dbg)
