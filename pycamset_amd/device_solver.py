@@ -294,6 +294,35 @@ class BlockedNormalEquations:
                                self.delta.data_ptr(), ps.data_ptr(), self.fixed.data_ptr(), self.status.data_ptr(), lam.data_ptr(), stats.data_ptr(),
                                stream)
 
+    def lm_buffers(self, ps, lam, ctrl, flags, stats, stats_host=None, result_host=None, mode=None):
+        """include/pcs_hip.h pcs_lm_buffers of one trial on this state — what the device-steered loop hands pcs_lm_trial*.  ``ps``: the
+        two parameter strings; ``lam``, ``ctrl`` (12 doubles), ``flags`` (4 int32), ``stats`` (12 doubles): device tensors;
+        ``stats_host`` / ``result_host``: page-locked tensors or None.  ``mode`` (PCS_LM_* bits) defaults to the loop's: a fixed trial
+        buffer where a collective is queued on it (sharded) or the build reads its string from a fixed address (generated chains),
+        votes when sharded."""
+        from ._capi import LM_FIXED_TRIAL_BUFFER, LM_VOTES, LmBuffers
+        from .engine import SPD_ALGORITHMS
+
+        if mode is None:
+            sharded = self.reduce_fn is not None
+            mode = (LM_FIXED_TRIAL_BUFFER | LM_VOTES) if sharded else LM_FIXED_TRIAL_BUFFER if getattr(self.eng, "lm_fixed_trial_buffer", False) else 0
+        b = LmBuffers()
+        b.packed[0], b.packed[1] = self.packed[0].data_ptr(), self.packed[1].data_ptr()
+        b.ps[0], b.ps[1] = ps[0].data_ptr(), ps[1].data_ptr()
+        b.flags, b.fixed, b.lam = flags.data_ptr(), self.fixed.data_ptr(), lam.data_ptr()
+        b.linvt, b.u, b.V, b.S, b.rhs, b.dvec, b.gm = (t.data_ptr() for t in (self.linvt, self.u, self.V, self.S, self.rhs, self.dvec, self.gm))
+        b.status, b.xlead, b.w, b.spd_work = self.status.data_ptr(), self.xl.data_ptr(), self.w.data_ptr(), self.chol_work.data_ptr()
+        b.delta, b.ctrl = self.delta.data_ptr(), ctrl.data_ptr()
+        b.stats = stats.data_ptr()
+        if stats_host is not None:
+            b.stats_host = stats_host.data_ptr()
+        b.spd_algorithm = SPD_ALGORITHMS[self.spd_algorithm]
+        b.mode = mode
+        if result_host is not None:
+            b.free_idx, b.n_free, b.result_host = self.free_idx.data_ptr(), int(self.free_idx.numel()), result_host.data_ptr()
+        b.syrk_work, b.syrk_work_len = self.syrk_work.data_ptr(), self.syrk_work_len
+        return b
+
     def predicted_reduction(self, lam):
         """(0.5 (lam d'D d - g'd), step is valid) of the last ``solve`` as device tensors (tests; the loop uses ``decide``)."""
         torch = self.torch
@@ -364,8 +393,7 @@ def _lm_loop_device(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, ft
     over packed[0] (PCS_LM_FIXED_TRIAL_BUFFER); the ranks decide on identical all-reduced blocks with order-deterministic kernels
     (`_lm_solve_blocked` switches the engine's deterministic mode on for a sharded loop), so every rank walks the same path without a consensus
     collective, and a dense solve that gives up on ONE rank voids the trial on all of them (PCS_LM_VOTES)."""
-    from ._capi import LM_FIXED_TRIAL_BUFFER, LM_STATS, LM_VOTES, LmBuffers
-    from .engine import SPD_ALGORITHMS
+    from ._capi import LM_STATS
 
     torch = ne.torch
     dev = ne.dev
@@ -401,20 +429,7 @@ def _lm_loop_device(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, ft
         history = []                       # the first entry — the starting cost — comes with the first trial's read-back (no sync of its own)
 
         def buffers(k):
-            b = LmBuffers()
-            b.packed[0], b.packed[1] = ne.packed[0].data_ptr(), ne.packed[1].data_ptr()
-            b.ps[0], b.ps[1] = ps[0].data_ptr(), ps[1].data_ptr()
-            b.flags, b.fixed, b.lam = flags.data_ptr(), ne.fixed.data_ptr(), lam.data_ptr()
-            b.linvt, b.u, b.V, b.S, b.rhs, b.dvec, b.gm = (t.data_ptr() for t in (ne.linvt, ne.u, ne.V, ne.S, ne.rhs, ne.dvec, ne.gm))
-            b.status, b.xlead, b.w, b.spd_work = ne.status.data_ptr(), ne.xl.data_ptr(), ne.w.data_ptr(), ne.chol_work.data_ptr()
-            b.delta, b.ctrl = ne.delta.data_ptr(), ctrl.data_ptr()
-            b.stats, b.stats_host = stats_dev.data_ptr(), stats_host[k % ring].data_ptr()
-            b.spd_algorithm = SPD_ALGORITHMS[ne.spd_algorithm]
-            # a fixed trial buffer: where a collective is queued on it (sharded) or the build reads its string from a fixed address (generated chains)
-            b.mode = (LM_FIXED_TRIAL_BUFFER | LM_VOTES) if sharded else LM_FIXED_TRIAL_BUFFER if getattr(eng, "lm_fixed_trial_buffer", False) else 0
-            b.free_idx, b.n_free, b.result_host = ne.free_idx.data_ptr(), n_free, result_host.data_ptr()
-            b.syrk_work, b.syrk_work_len = ne.syrk_work.data_ptr(), ne.syrk_work_len
-            return b
+            return ne.lm_buffers(ps, lam, ctrl, flags, stats_dev, stats_host[k % ring], result_host)
 
         # The read-back of trial k lands in page-locked memory the device writes directly (lm_decide_kernel; all twelve words are -1 for
         # a launch that found the stop flag raised).  The host waits for THOSE words instead of an event — an event record between two
@@ -446,6 +461,7 @@ def _lm_loop_device(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, ft
             return v.copy()
 
         code, nfev, n_lin, it = 0, 1, 0, 0
+        trials = []                        # every decided trial's read-back, void ones included
         limit = REJECTION_LIMIT * max_iter + 16          # every accepted step is preceded by fewer than REJECTION_LIMIT rejections
         queued = read = 0
         if max_iter > 0:
@@ -463,6 +479,7 @@ def _lm_loop_device(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, ft
                 if read >= queued:
                     break
                 continue
+            trials.append(st)
             n_lin += 1
             nfev += 1
             if not history:
@@ -500,7 +517,8 @@ def _lm_loop_device(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, ft
         if not history:
             history.append(cost)
     return DeviceLMResult(x=x, cost=cost, grad=g, optimality=float(np.max(np.abs(g))) if g.size else 0.0, nit=it, nfev=nfev,
-                          n_jtjv=n_lin, status=STOP_STATUS.get(code, 0), message=STOP_MESSAGES.get(code, f"stopped ({code})"), history=history)
+                          n_jtjv=n_lin, status=STOP_STATUS.get(code, 0), message=STOP_MESSAGES.get(code, f"stopped ({code})"), history=history,
+                          trials=trials)
 
 
 def _gain_ratio(ne: BlockedNormalEquations, stats) -> float:
@@ -535,6 +553,7 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
         status, message = 0, "maximum number of iterations reached"
         it = 0
         any_accepted = False
+        trials = []
         for it in range(1, max_iter + 1):
             accepted = False
             stop = False
@@ -555,30 +574,42 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
                 verdict.record()
                 verdict.synchronize()
                 stats = stats_host.numpy().copy()
+                # the trial's record in the device-steered loop's layout: pcs_lm_decide leaves [8] .. [10] to the loop, and [11] is
+                # completed below where this loop's own rules change lambda
+                trials.append(stats)
+                stats[9], stats[10] = len(trials), cur
                 if stats[0] < 0:   # the one-launch dense solve gave up waiting on SOME rank (status bit 2): nothing of this trial is valid —
+                    stats[8] = 9
                     ne.spd_algorithm = "launches"   # every rank repeats it with the launch-per-column form (the decision left the damping alone)
                     nfev -= 1
                     n_lin -= 1
                     continue
+                stats[8] = 0
                 retry += 1
                 gmax = float(stats[1])
                 if verbose:
                     print(f"  it {it}: lam {stats[7]:.2e} cost {0.5 * stats[6]:.6e} -> {0.5 * stats[5]:.6e} accepted {bool(stats[0])}")
                 if gmax <= gtol:   # the state BEFORE this step was already stationary: the step is dropped
                     status, message, stop = 1, "gtol reached", True
+                    stats[0], stats[8], stats[11] = 0, 1, stats[7]
                     break
                 if stats[0] > 0:
                     accepted = any_accepted = True
                     # pcs_lm_decide applied the classic 1/3; a gain ratio above LAM_FAST[0] earns LAM_FAST[1] (the device-steered loop's rule)
                     if _gain_ratio(ne, stats) > LAM_FAST[0]:
-                        lam.fill_(max(float(stats[7]) * LAM_FAST[1], 1e-12))
+                        stats[11] = max(float(stats[7]) * LAM_FAST[1], 1e-12)
+                        lam.fill_(stats[11])
                     ps, ps_new = ps_new, ps
                     cur, new = new, cur
+                    stats[10] = cur
                     history.append(0.5 * float(stats[5]))
                     rel_drop, step_norm, x_norm = float(stats[2]), float(stats[3]), float(stats[4])
                     break
                 if not any_accepted and lam_grow0 > 1.0:   # a rejection before the first accepted step: the device rule multiplied by 4
                     lam.mul_(lam_grow0 / 4.0)
+                    stats[11] *= lam_grow0 / 4.0
+                if retry == REJECTION_LIMIT:
+                    stats[8] = 2
             if stop:
                 break
             if not accepted:
@@ -586,15 +617,19 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
                 break
             if rel_drop <= ftol:
                 status, message = 3, "ftol reached"
+                trials[-1][8] = 3
                 break
             if step_norm <= xtol * (xtol + x_norm):
                 status, message = 4, "xtol reached"
+                trials[-1][8] = 4
                 break
+            if it == max_iter:
+                trials[-1][8] = 5
         g = ne.gradient(cur, lam)
         x = ps[ne.free_idx].cpu().numpy()
         cost = 0.5 * float(ne.cost(cur).item())
     return DeviceLMResult(x=x, cost=cost, grad=g, optimality=float(np.max(np.abs(g))) if g.size else 0.0, nit=it, nfev=nfev,
-                          n_jtjv=n_lin, status=status, message=message, history=history)
+                          n_jtjv=n_lin, status=status, message=message, history=history, trials=trials)
 
 
 @dataclass
@@ -609,6 +644,10 @@ class DeviceLMResult:
     status: int
     message: str
     history: list = field(default_factory=list)
+    # one float64 array per decided trial (void ones included), in the read-back layout of include/pcs_hip.h (pcs_lm_trial stats):
+    # accepted (1 / 0, -1 void), max |g|, relative cost drop, |step|, |x|, new and old sum r^2, lambda used, stop code after the trial,
+    # trial number, current state after it, lambda for the next trial.  The PCG / host loop puts NaN where it has no such number.
+    trials: list = field(default_factory=list)
 
 
 class _PcgStep:
@@ -763,48 +802,67 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
     status, message = 0, "maximum number of iterations reached"
     it = 0
     any_accepted = False
+    trials = []
+
+    def record(accepted, gmax, sumsq_new, step_norm, x_norm, lam_used, lam_next):
+        rel = 0.5 * (st["sumsq"] - sumsq_new) / (0.5 * st["sumsq"])
+        trials.append(np.array([1.0 if accepted else 0.0, gmax, rel, step_norm, x_norm, sumsq_new, st["sumsq"], lam_used, 0.0, len(trials) + 1.0,
+                                np.nan, lam_next]))
+
     for it in range(1, max_iter + 1):
-        if float(np.max(np.abs(st["g"]))) <= gtol:
+        gmax = float(np.max(np.abs(st["g"])))
+        if gmax <= gtol:
             status, message = 1, "gtol reached"
             break
         accepted = False
+        x_norm = float(np.linalg.norm(x))
         for retry in range(REJECTION_LIMIT):  # damping retries
             if retry:
                 step.restore(st)
             delta, k, pred = step.solve(st, lam)
             n_lin += k
+            # a rejection before the first accepted step multiplies lambda by lam_grow0 (when that is > 1), every other one by 4
+            grow = grow0 if not any_accepted and grow0 > 1.0 else 4.0
             if delta is None:   # damped matrix not positive definite: more damping
-                lam *= 4.0 if any_accepted else max(grow0, 4.0)
+                record(False, gmax, np.nan, np.nan, x_norm, lam, lam * grow)
+                lam *= grow
                 continue
             x_new = x + delta
             st_new = step.evaluate(param_str(x_new))
             nfev += 1
             actual = 0.5 * (st["sumsq"] - st_new["sumsq"])
             rho = actual / pred if pred > 0 else -1.0
+            step_norm = float(np.linalg.norm(delta))
             if verbose:
                 print(f"  it {it}: lam {lam:.2e} lin {k} cost {0.5 * st['sumsq']:.6e} -> {0.5 * st_new['sumsq']:.6e} rho {rho:.3f}")
             if np.isfinite(st_new["sumsq"]) and actual > 0:
                 accepted = any_accepted = True
-                step_norm, x_norm = float(np.linalg.norm(delta)), float(np.linalg.norm(x))
                 rel_drop = actual / (0.5 * st["sumsq"])
-                x, st = x_new, st_new
                 fast = linear_solver != "pcg" and rho > LAM_FAST[0]    # exact steps only: less damping costs an inexact (CG) step iterations
-                lam = max(lam * (LAM_FAST[1] if fast else 1.0 / 3.0 if rho > 0.75 else 1.0 if rho > 0.25 else 2.0), 1e-12)
+                lam_next = max(lam * (LAM_FAST[1] if fast else 1.0 / 3.0 if rho > 0.75 else 1.0 if rho > 0.25 else 2.0), 1e-12)
+                record(True, gmax, st_new["sumsq"], step_norm, x_norm, lam, lam_next)
+                x, st, lam = x_new, st_new, lam_next
                 history.append(0.5 * st["sumsq"])
                 break
-            lam *= 4.0 if any_accepted else max(grow0, 4.0)
+            record(False, gmax, st_new["sumsq"], step_norm, x_norm, lam, lam * grow)
+            lam *= grow
         if not accepted:
             step.restore(st)
             status, message = 2, "no further decrease (damping exhausted)"
+            trials[-1][8] = 2
             break
         if rel_drop <= ftol:
             status, message = 3, "ftol reached"
+            trials[-1][8] = 3
             break
         if step_norm <= xtol * (xtol + x_norm):
             status, message = 4, "xtol reached"
+            trials[-1][8] = 4
             break
+        if it == max_iter:
+            trials[-1][8] = 5
     return DeviceLMResult(x=x, cost=0.5 * st["sumsq"], grad=st["g"], optimality=float(np.max(np.abs(st["g"]))), nit=it, nfev=nfev,
-                          n_jtjv=n_lin, status=status, message=message, history=history)
+                          n_jtjv=n_lin, status=status, message=message, history=history, trials=trials)
 
 
 @dataclass
