@@ -533,6 +533,37 @@ int pcs_tri_last_kernel_ms(pcs_triangulator *t, float *kernel_ms);
 int pcs_triangulate(int device, int64_t n_obs, const int32_t *cam, const double *uv, int64_t n_pts, const int64_t *start_inds,
                     int64_t n_cams, const double *proj, const double *intrinsics, const double *dists, double *pts,
                     float *kernel_ms);
+/* Reprojection-error refinement of the triangulation (csrc/ba_tri_refine.hpp).  Since pcs_version() 104.
+ * For point j with views v = (camera c_v, measurement uv_v): minimise sum_v || uv_v - pi_{c_v}(X) ||^2 over X, pi_c = the reference's
+ * Camera.project_points(distort=True) (cameras/camera.py:242-272): h = P_c [X; 1], pixel (h0 / h2, h1 / h2), then the Brown-Conrady
+ * distortion nb_distort_prealloc (camera.py:32-56) with fx = K00, fy = K11, (cx, cy) = K[0:2, 2] and the table's [k0, k1, p0, p1, k2].
+ * Per point Levenberg-Marquardt on the 3 x 3 system (H + lam diag(H)) d = g, H = J'J, g = J'r, starting from the DLT point of the last
+ * pcs_tri_run on the same cameras and observations (read on the device where that run wrote it: the handle's output or the caller's
+ * d_pts, which must still hold it).  A trial is accepted when its cost is lower and every view has depth h2 > 0, so a returned point
+ * never costs more than its start.  Stops: max_iter trials, relative cost decrease <= ftol, step <= xtol (xtol + |X|), max |g| <= gtol.
+ *   pcs_tri_refine   queue the refinement on `stream` (NULL = the handle's stream), ordered after the run like the runs among themselves.
+ *                    Outputs (device buffers of the caller, or NULL = handle-owned): d_pts (n_pts, 3) refined points; d_rms (n_pts, 2)
+ *                    RMS reprojection error sqrt(sum_v |r_v|^2 / n_v) at the returned point and at the DLT point; d_info (n_pts, 3)
+ *                    int32 {trials used, status PCS_TRI_REFINE_*, views}; with flags PCS_TRI_REFINE_RESIDUALS, d_resid (n_obs, 2)
+ *                    residuals uv - pi(X) at the returned points in the handle's observation order.  PCS_ERR_ARG: NULL handle,
+ *                    max_iter < 0, a negative or non-finite tolerance, unknown flags; PCS_ERR_STATE: no run since the cameras or
+ *                    observations were last set.
+ *   pcs_tri_refined  copy the handle-owned outputs of the last refinement to the host (any pointer may be NULL; blocking).
+ *                    PCS_ERR_STATE when there was no refinement since the last run or a requested output went to a caller buffer.
+ *   pcs_tri_last_refine_ms  device time of the last refinement kernel.
+ * Defaults of the Python front end (pycamset_amd.compiled_helpers.REFINE_DEFAULTS): max_iter 10, ftol 1e-10, xtol 1e-10, gtol 0. */
+#define PCS_TRI_REFINE_RESIDUALS 1
+enum {
+    PCS_TRI_REFINE_NOT_REFINED = 0,   /* non-finite DLT start or a start behind a camera: the DLT point is returned unchanged */
+    PCS_TRI_REFINE_CONVERGED = 1,     /* ftol, xtol or gtol */
+    PCS_TRI_REFINE_MAX_ITER = 2,      /* max_iter trials used */
+    PCS_TRI_REFINE_NO_DECREASE = 3    /* the damping grew past 1e10 without a lower cost, or the damped system lost definiteness */
+};
+enum { PCS_TRI_OUT_POINTS = 1, PCS_TRI_OUT_RMS = 2, PCS_TRI_OUT_INFO = 4, PCS_TRI_OUT_RESIDUALS = 8 };
+int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, double gtol, int flags, double *d_pts, double *d_rms,
+                   int32_t *d_info, double *d_resid, void *stream);
+int pcs_tri_refined(pcs_triangulator *t, double *pts, double *rms, int32_t *info, double *resid);
+int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms);
 
 /* Page-locked host memory for outputs: pcs_eval / pcs_eval_compact copy device -> host at PCIe rate
  * into such buffers (a pageable destination is several times slower).  Replaces nothing in the

@@ -35,6 +35,9 @@ class LmBuffers(ctypes.Structure):
 LM_FIXED_TRIAL_BUFFER, LM_VOTES = 1, 2   # include/pcs_hip.h PCS_LM_*
 LM_STATS = 12                            # doubles in a trial's read-back (and in the control block)
 COV_TRSM_IDENTITY = 1                    # include/pcs_hip.h PCS_COV_TRSM_IDENTITY
+TRI_REFINE_RESIDUALS = 1                 # include/pcs_hip.h PCS_TRI_REFINE_RESIDUALS
+# include/pcs_hip.h PCS_TRI_REFINE_*: per-point status of the triangulation refinement
+TRI_NOT_REFINED, TRI_CONVERGED, TRI_MAX_ITER, TRI_NO_DECREASE = 0, 1, 2, 3
 
 
 SYMBOLS = {
@@ -126,6 +129,9 @@ SYMBOLS = {
     "pcs_tri_points": (c_int, [_P, POINTER(c_double)]),
     "pcs_tri_synchronize": (c_int, [_P, _P]),
     "pcs_tri_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_tri_refine": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, _P, _P, _P, _P, _P]),
+    "pcs_tri_refined": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
+    "pcs_tri_last_refine_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_host_alloc": (c_int, [POINTER(_P), c_int64]),
     "pcs_host_free": (c_int, [_P]),
     "pcs_membench": (c_int, [c_int, c_int, c_int64, c_int, c_int, POINTER(c_float)]),

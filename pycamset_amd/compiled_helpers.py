@@ -11,6 +11,8 @@ The reference calls them with the detection table on every call (template_handle
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 
 from .engine import Engine
@@ -50,6 +52,47 @@ def bundle_adj_parrallel_solver(dct, im_points, projection_matrixes, intrinsics,
 
 last_triangulate_kernel_ms = None
 
+# Defaults of the triangulation refinement (include/pcs_hip.h pcs_tri_refine).  max_iter counts LM trials (one pass over a point's
+# views each; a DLT start converges in 2-4).  ftol / xtol stop at a relative cost decrease / a step relative to |X| of 1e-10: far below
+# the noise of any measurement, and a step that small moves the point by less than its own rounding after one more GN step.
+# gtol (max |J'r| <= gtol) is off: J'r carries pixel^2 per world unit, so no absolute threshold suits every rig.
+REFINE_DEFAULTS = {"max_iter": 10, "ftol": 1e-10, "xtol": 1e-10, "gtol": 0.0}
+# per-point status of the refinement (include/pcs_hip.h PCS_TRI_REFINE_*)
+TRI_NOT_REFINED, TRI_CONVERGED, TRI_MAX_ITER, TRI_NO_DECREASE = 0, 1, 2, 3
+
+
+def check_refine_options(max_iter, ftol, xtol, gtol):
+    """Validate the refinement options on the host (ValueError) before anything is queued."""
+    if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or not 0 <= int(max_iter) < 2 ** 31:
+        raise ValueError(f"max_iter must be an integer >= 0, got {max_iter!r}")
+    out = [int(max_iter)]
+    for name, v in (("ftol", ftol), ("xtol", xtol), ("gtol", gtol)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}") from None
+        if not (np.isfinite(f) and f >= 0.0):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+        out.append(f)
+    return tuple(out)
+
+
+@dataclass
+class TriangulationResult:
+    """Refined triangulation (``refine_triangulation``, ``multi_cam_triangulate(return_result=True)``, ``Triangulator.refined``).
+
+    points, points_dlt: (n, 3) refined and DLT points; rms, rms_dlt: (n,) RMS reprojection error sqrt(sum_v |r_v|^2 / n_v) in pixels at
+    them (rms <= rms_dlt); n_views, iterations (LM trials), status (TRI_*): (n,) int32; residuals: (n_obs, 2) uv - pi(points) in the
+    observation order, or None."""
+    points: np.ndarray
+    points_dlt: np.ndarray
+    rms: np.ndarray
+    rms_dlt: np.ndarray
+    n_views: np.ndarray
+    iterations: np.ndarray
+    status: np.ndarray
+    residuals: np.ndarray | None = None
+
 
 class Triangulator:
     """Owner of one ``pcs_triangulator`` handle (include/pcs_hip.h): the camera table, device copies of the
@@ -67,6 +110,7 @@ class Triangulator:
         _capi.check(_capi.lib().pcs_tri_create(ctypes.byref(self._h), int(device), int(n_cams)))
         self.n_cams, self.device, self.n_pts = int(n_cams), int(device), 0
         self._cam_key = None
+        self._n_obs = 0
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -101,6 +145,7 @@ class Triangulator:
             self._h, cam.shape[0], cam.ctypes.data_as(ct.POINTER(ct.c_int32)), uv.ctypes.data_as(ct.POINTER(ct.c_double)),
             start.shape[0] - 1, start.ctypes.data_as(ct.POINTER(ct.c_int64))))
         self.n_pts = start.shape[0] - 1
+        self._n_obs = cam.shape[0]
 
     def set_observations_device(self, n_obs: int, d_cam: int, d_uv: int, n_pts: int, d_start: int):
         """Raw device addresses (e.g. ``tensor.data_ptr()``) of int32 cam, float64 uv, int64 start_inds: used in place."""
@@ -108,6 +153,7 @@ class Triangulator:
         self._capi.check(self._capi.lib().pcs_tri_set_observations_device(self._h, int(n_obs), ct.c_void_p(d_cam), ct.c_void_p(d_uv),
                                                                           int(n_pts), ct.c_void_p(d_start)))
         self.n_pts = int(n_pts)
+        self._n_obs = int(n_obs)
 
     def group_table_device(self, n: int, d_cam: int, d_feat: int, d_uv: int, n_features: int, stream: int | None = None):
         """The grouping of ``multi_cam_triangulate`` (cameras/camera_set.py:371-378) on the device: raw device addresses of int32
@@ -121,6 +167,7 @@ class Triangulator:
                                                                ct.byref(n_pts), ct.byref(n_kept), ct.byref(grouped), _stream_arg(stream)))
         if grouped.value:
             self.n_pts = int(n_pts.value)
+            self._n_obs = int(n_kept.value)
         return int(n_pts.value), int(n_kept.value), bool(grouped.value)
 
     def run(self, d_pts: int | None = None, stream: int | None = None):
@@ -144,8 +191,49 @@ class Triangulator:
         self._capi.check(self._capi.lib().pcs_tri_last_kernel_ms(self._h, self._ct.byref(ms)))
         return float(ms.value)
 
+    def refine(self, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
+               gtol: float = REFINE_DEFAULTS["gtol"], residuals: bool = False, d_pts: int | None = None, d_rms: int | None = None,
+               d_info: int | None = None, d_resid: int | None = None, stream: int | None = None):
+        """Queue the reprojection-error refinement of the last ``run``'s points (asynchronous, like ``run``; include/pcs_hip.h
+        pcs_tri_refine).  Device addresses: ``d_pts`` (n_pts, 3) float64, ``d_rms`` (n_pts, 2) float64 [rms, rms at the DLT point],
+        ``d_info`` (n_pts, 3) int32 [trials, status, views], ``d_resid`` (n_obs, 2) float64 (with ``residuals``); None = handle-owned
+        (fetch them with ``refined()``)."""
+        from .engine import _stream_arg
+        max_iter, ftol, xtol, gtol = check_refine_options(max_iter, ftol, xtol, gtol)
+        vp = self._ct.c_void_p
+        self._capi.check(self._capi.lib().pcs_tri_refine(self._h, max_iter, ftol, xtol, gtol, self._capi.TRI_REFINE_RESIDUALS if residuals else 0,
+                                                         vp(d_pts or 0), vp(d_rms or 0), vp(d_info or 0), vp(d_resid or 0), _stream_arg(stream)))
+        self._refined_residuals = bool(residuals) and not d_resid
+
+    def refined(self, points_dlt: np.ndarray | None = None) -> "TriangulationResult":
+        """Wait for the last ``refine`` and return its handle-owned outputs.  ``points_dlt``: the start points, when the run wrote
+        them to a caller buffer (otherwise they are fetched from the handle)."""
+        ct, n = self._ct, max(self.n_pts, 0)
+        dp = ct.POINTER(ct.c_double)
+        pts, rms, info = np.empty((n, 3)), np.empty((n, 2)), np.empty((n, 3), dtype=np.int32)
+        resid = np.empty((self._n_obs, 2)) if getattr(self, "_refined_residuals", False) else None
+        self._capi.check(self._capi.lib().pcs_tri_refined(self._h, pts.ctypes.data_as(dp), rms.ctypes.data_as(dp), info.ctypes.data_as(ct.POINTER(ct.c_int32)),
+                                                          resid.ctypes.data_as(dp) if resid is not None else None))
+        start = self.points() if points_dlt is None else np.asarray(points_dlt, dtype=np.float64).reshape(n, 3)
+        return TriangulationResult(points=pts, points_dlt=start, rms=rms[:, 0].copy(), rms_dlt=rms[:, 1].copy(), n_views=info[:, 2].copy(),
+                                   iterations=info[:, 0].copy(), status=info[:, 1].copy(), residuals=resid)
+
+    def last_refine_ms(self) -> float:
+        ms = self._ct.c_float(0.0)
+        self._capi.check(self._capi.lib().pcs_tri_last_refine_ms(self._h, self._ct.byref(ms)))
+        return float(ms.value)
+
 
 _tri_cache: dict = {}
+
+
+def _triangulator(device: int, n_cams: int) -> Triangulator:
+    key = (int(device), int(n_cams))
+    tri = _tri_cache.get(key)
+    if tri is None:
+        _tri_cache.clear()
+        tri = _tri_cache[key] = Triangulator(n_cams, device)
+    return tri
 
 
 def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0) -> np.ndarray:
@@ -158,11 +246,7 @@ def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0) -> 
     start = np.asarray(start_inds, dtype=np.int64)
     if start.shape[0] <= 1:
         return np.empty((0, 3))
-    key = (int(device), int(P.shape[0]))
-    tri = _tri_cache.get(key)
-    if tri is None:
-        _tri_cache.clear()
-        tri = _tri_cache[key] = Triangulator(P.shape[0], device)
+    tri = _triangulator(device, P.shape[0])
     tri.set_cameras(P, intr, dist)
     tri.set_observations(data[:, 0].astype(np.int32), data[:, -2:], start)
     tri.run()
@@ -171,32 +255,98 @@ def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0) -> 
     return pts
 
 
-def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: int = 0) -> np.ndarray:
+def _empty_result(return_residuals: bool) -> TriangulationResult:
+    z, i = np.empty((0, 3)), np.empty(0, dtype=np.int32)
+    return TriangulationResult(points=z, points_dlt=z.copy(), rms=np.empty(0), rms_dlt=np.empty(0), n_views=i, iterations=i.copy(), status=i.copy(),
+                               residuals=np.empty((0, 2)) if return_residuals else None)
+
+
+def refine_triangulation(data, proj, start_inds, intr, dist, *, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"],
+                         xtol: float = REFINE_DEFAULTS["xtol"], gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False,
+                         device: int = 0) -> TriangulationResult:
+    """``nb_triangulate_full`` followed by the per-point refinement of the reprojection error in the measured (distorted) pixels
+    (include/pcs_hip.h pcs_tri_refine): DLT and refinement are queued back to back on the device, one synchronisation at the end.
+    ``data`` rows = [cam, ..., u, v] sorted by point, ``start_inds`` (n_pts + 1).  Returns a ``TriangulationResult``; with
+    ``return_residuals`` its ``residuals`` are (n_obs, 2) in the rows' order."""
+    global last_triangulate_kernel_ms
+    opts = check_refine_options(max_iter, ftol, xtol, gtol)
+    data = np.asarray(data, dtype=np.float64)
+    P = np.asarray(proj, dtype=np.float64)
+    start = np.asarray(start_inds, dtype=np.int64)
+    if data.ndim != 2 or data.shape[1] < 3 or start.ndim != 1 or start.shape[0] < 1:
+        raise ValueError("expected data (n_obs, >= 3) and start_inds (n_pts + 1,)")
+    if start.shape[0] <= 1:
+        return _empty_result(return_residuals)
+    tri = _triangulator(device, P.shape[0])
+    tri.set_cameras(P, intr, dist)
+    tri.set_observations(data[:, 0].astype(np.int32), data[:, -2:], start)
+    tri.run()
+    tri.refine(*opts, residuals=return_residuals)
+    res = tri.refined()
+    last_triangulate_kernel_ms = tri.last_kernel_ms()
+    return res
+
+
+def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: int = 0, *, refine: bool = False, return_result: bool = False,
+                          max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
+                          gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False):
     """``CameraSet.multi_cam_triangulate`` for a detection table (cameras/camera_set.py:343-402, the array branch): ``data`` rows =
     [cam, image, key..., u, v] as ``TargetDetection.get_data`` returns them; the features seen by more than one camera are
     triangulated, in order of first appearance.  Grouping (``np.unique`` twice in the reference: 0.37 s for 1e6 rows) AND
     triangulation run on the device; a table whose features are not stored consecutively takes the host grouping
-    (``group_reconstructable``: the reference's semantics for any table).  ``distort=False`` zeroes the distortion (camera_set.py:384-385)."""
-    global last_triangulate_kernel_ms
-    import torch
+    (``group_reconstructable``: the reference's semantics for any table).  ``distort=False`` zeroes the distortion (camera_set.py:384-385).
 
+    ``refine=True``: the DLT points are refined to the minimum of the reprojection error (``refine_triangulation``; options max_iter,
+    ftol, xtol, gtol), grouping, DLT and refinement queued back to back, one synchronisation at the end.  ``return_result=True``
+    returns the ``TriangulationResult`` (points, RMS errors, status, with ``return_residuals`` the residuals in the order of the kept
+    rows) instead of the points; without ``refine`` it carries the DLT points and their RMS (a refinement with max_iter = 0).  The
+    default returns the DLT points, as before."""
+    global last_triangulate_kernel_ms
+    with_result = refine or return_result
+    if with_result:
+        opts = check_refine_options(max_iter if refine else 0, ftol, xtol, gtol)
     table = np.asarray(data, dtype=np.float64)
     P = np.asarray(proj, dtype=np.float64)
     D = np.zeros_like(np.asarray(dist, dtype=np.float64)) if not distort else np.asarray(dist, dtype=np.float64)
+
+    def out(res: TriangulationResult):
+        return res if return_result else res.points
+
+    empty = (lambda: out(_empty_result(return_residuals))) if with_result else (lambda: np.empty((0, 3)))
     if table.shape[0] == 0:
-        return np.empty((0, 3))
+        return empty()
+    tri, n_pts = _group_on_device(table, P, intr, D, device)
+    if tri is None:                                                         # host grouping
+        rec, start = group_reconstructable(table)
+        if not with_result:
+            return nb_triangulate_full(rec, P, start, intr, D, device=device)
+        return out(refine_triangulation(rec, P, start, intr, D, max_iter=opts[0], ftol=opts[1], xtol=opts[2], gtol=opts[3],
+                                        return_residuals=return_residuals, device=device))
+    if n_pts == 0:
+        return empty()
+    tri.run()
+    if not with_result:
+        pts = tri.points()
+        last_triangulate_kernel_ms = tri.last_kernel_ms()
+        return pts
+    tri.refine(*opts, residuals=return_residuals)
+    res = tri.refined()
+    last_triangulate_kernel_ms = tri.last_kernel_ms()
+    return out(res)
+
+
+def _group_on_device(table: np.ndarray, P: np.ndarray, intr, D: np.ndarray, device: int):
+    """The grouping of ``multi_cam_triangulate`` on the device for a non-empty table: (the cached Triangulator holding the kept rows,
+    n_pts), or (None, 0) when the table needs the host grouping."""
+    import torch
+
     ids = table[:, 1:-2].astype(np.int64)                                   # (image, key...) columns
     dims = ids.max(axis=0) + 1
     n_features = int(np.prod(dims))
     if n_features >= 2 ** 31 or ids.min() < 0:
-        rec, start = group_reconstructable(table)
-        return nb_triangulate_full(rec, P, start, intr, D, device=device)
+        return None, 0
     feat = np.ravel_multi_index(ids.T, dims).astype(np.int32)               # a dense id per feature: no sort needed
-    key = (int(device), int(P.shape[0]))
-    tri = _tri_cache.get(key)
-    if tri is None:
-        _tri_cache.clear()
-        tri = _tri_cache[key] = Triangulator(P.shape[0], device)
+    tri = _triangulator(device, P.shape[0])
     tri.set_cameras(P, intr, D)
     dev = torch.device("cuda", device)
     d_cam = torch.from_numpy(table[:, 0].astype(np.int32)).to(dev)
@@ -204,15 +354,7 @@ def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: 
     d_uv = torch.from_numpy(np.ascontiguousarray(table[:, -2:])).to(dev)
     torch.cuda.synchronize(dev)                                             # the uploads ran on torch's stream, the grouping runs on the handle's
     n_pts, _, grouped = tri.group_table_device(table.shape[0], d_cam.data_ptr(), d_feat.data_ptr(), d_uv.data_ptr(), n_features)
-    if not grouped:
-        rec, start = group_reconstructable(table)
-        return nb_triangulate_full(rec, P, start, intr, D, device=device)
-    if n_pts == 0:
-        return np.empty((0, 3))
-    tri.run()
-    pts = tri.points()
-    last_triangulate_kernel_ms = tri.last_kernel_ms()
-    return pts
+    return (tri, n_pts) if grouped else (None, 0)
 
 
 def group_reconstructable(data: np.ndarray):

@@ -34,6 +34,7 @@
 #include "ba_chol_persist.hpp"
 #include "ba_covariance.hpp"
 #include "ba_triangulate.hpp"
+#include "ba_tri_refine.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -247,7 +248,7 @@ static void free_det_tables(pcs_engine *h) {
 
 extern "C" {
 
-int pcs_version(void) { return 103; }
+int pcs_version(void) { return 104; }
 const char *pcs_last_error(void) { return g_err.c_str(); }
 
 // ---- batched triangulation: a handle that owns the camera table, the observation buffers and the
@@ -285,6 +286,15 @@ struct pcs_triangulator {
     hipStream_t done_stream = nullptr;
     bool have_done = false;
     bool out_owned = false;   // the last run wrote the handle-owned output (pcs_tri_points has something to return)
+    // the refinement (pcs_tri_refine): it starts from the points of the last run on the current cameras and observations
+    bool run_valid = false;          // a run since the cameras / observations were last set
+    const double *run_pts = nullptr; // where that run wrote its points (handle-owned or the caller's buffer)
+    double *d_rpts = nullptr, *d_rrms = nullptr, *d_rres = nullptr; int32_t *d_rinfo = nullptr;   // handle-owned refinement outputs
+    int64_t rpts_capacity = 0, rrms_capacity = 0, rres_capacity = 0, rinfo_capacity = 0;
+    int refine_owned = 0;            // PCS_TRI_OUT_* bits: which outputs of the last refinement are handle-owned
+    bool refine_valid = false;       // a refinement since the last run (pcs_tri_refined has something to return)
+    hipEvent_t r0 = nullptr, r1 = nullptr;
+    bool refine_timed = false;
 };
 
 static hipError_t tri_wait_done_host(pcs_triangulator *t) { return t->have_done ? hipEventSynchronize(t->done) : hipSuccess; }
@@ -318,6 +328,8 @@ int pcs_tri_create(pcs_triangulator **out, int device, int64_t n_cams) {
     hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&t->e0);
     if (e == hipSuccess) e = hipEventCreate(&t->e1);
+    if (e == hipSuccess) e = hipEventCreate(&t->r0);
+    if (e == hipSuccess) e = hipEventCreate(&t->r1);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMalloc(&t->d_tab, sizeof(double) * n_cams * TRI_CAM_STRIDE);
     if (e != hipSuccess) {
@@ -335,10 +347,13 @@ int pcs_tri_destroy(pcs_triangulator *t) {
     if (t->stream) (void)hipStreamSynchronize(t->stream);
     (void)tri_wait_done_host(t);   // a run on a caller stream may still read the tables
     for (void *b : {(void *)t->d_tab, (void *)t->d_cam, (void *)t->d_uv, (void *)t->d_start, t->d_scr, t->d_scl, (void *)t->d_pts, (void *)t->d_order, (void *)t->d_hist,
-                    (void *)t->d_count, (void *)t->d_block_sums, (void *)t->d_totals})
+                    (void *)t->d_count, (void *)t->d_block_sums, (void *)t->d_totals, (void *)t->d_rpts, (void *)t->d_rrms, (void *)t->d_rres,
+                    (void *)t->d_rinfo})
         if (b) (void)hipFree(b);
     if (t->e0) (void)hipEventDestroy(t->e0);
     if (t->e1) (void)hipEventDestroy(t->e1);
+    if (t->r0) (void)hipEventDestroy(t->r0);
+    if (t->r1) (void)hipEventDestroy(t->r1);
     if (t->done) (void)hipEventDestroy(t->done);
     if (t->stream) (void)hipStreamDestroy(t->stream);
     delete t;
@@ -360,6 +375,7 @@ int pcs_tri_set_cameras(pcs_triangulator *t, const double *proj, const double *i
     HIPCHK(hipStreamSynchronize(t->stream));
     HIPCHK(hipMemcpy(t->d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
     t->have_cams = true;
+    t->run_valid = t->refine_valid = false;   // a refinement must start from points of these cameras
     return PCS_OK;
 }
 
@@ -390,6 +406,7 @@ int pcs_tri_set_observations(pcs_triangulator *t, int64_t n_obs, const int32_t *
     t->n_obs = n_obs; t->n_pts = n_pts;
     t->order_valid = false;
     t->out_owned = false;   // results of an earlier problem are not this problem's
+    t->run_valid = t->refine_valid = false;
     return PCS_OK;
 }
 
@@ -399,6 +416,7 @@ int pcs_tri_set_observations_device(pcs_triangulator *t, int64_t n_obs, const in
     t->n_obs = n_obs; t->n_pts = n_pts;
     t->order_valid = false;
     t->out_owned = false;
+    t->run_valid = t->refine_valid = false;
     return PCS_OK;
 }
 
@@ -418,6 +436,7 @@ int pcs_tri_group_device(pcs_triangulator *t, int64_t n, const int32_t *d_cam, c
     HIPCHK(tri_wait_done_host(t));   // a run queued on ANY stream may still read the observation copies this call overwrites
     HIPCHK(hipStreamSynchronize(t->stream));
     t->n_pts = -1;
+    t->run_valid = t->refine_valid = false;
     if (n == 0) {
         int rc0 = tri_grow((void **)&t->d_start, &t->pts_capacity, 1, sizeof(int64_t));
         if (rc0) return rc0;
@@ -471,7 +490,12 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
     if (!t) return fail(PCS_ERR_ARG, "pcs_tri_run: bad arguments");
     if (!t->have_cams) return fail(PCS_ERR_STATE, "pcs_tri_run: cameras not set");
     if (t->n_pts < 0) return fail(PCS_ERR_STATE, "pcs_tri_run: observations not set");
-    if (t->n_pts == 0) return PCS_OK;
+    t->refine_valid = false;
+    if (t->n_pts == 0) {
+        t->run_valid = true;
+        t->run_pts = d_pts;
+        return PCS_OK;
+    }
     HIPCHK(hipSetDevice(t->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->stream;
     const bool need_order = t->variant != 0 && t->sort_points && !t->order_valid && t->n_pts < (1ll << 31);
@@ -531,9 +555,95 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
     HIPCHK(hipGetLastError());
     t->timed = true;
     t->out_owned = owned;
+    t->run_valid = true;
+    t->run_pts = d_pts;
     t->have_done = true;
     t->done_stream = s;   // compared only, never used as a handle again
     HIPCHK(hipEventRecord(t->done, s));
+    return PCS_OK;
+}
+
+// The refinement of the last run's points (csrc/ba_tri_refine.hpp): per-point LM on the reprojection error in the measured pixels.
+static_assert(TRI_REFINE_NOT_REFINED == PCS_TRI_REFINE_NOT_REFINED && TRI_REFINE_CONVERGED == PCS_TRI_REFINE_CONVERGED &&
+              TRI_REFINE_MAX_ITER == PCS_TRI_REFINE_MAX_ITER && TRI_REFINE_NO_DECREASE == PCS_TRI_REFINE_NO_DECREASE, "status codes of pcs_hip.h");
+int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, double gtol, int flags, double *d_pts, double *d_rms,
+                   int32_t *d_info, double *d_resid, void *stream) {
+    if (max_iter < 0 || !(ftol >= 0.0 && ftol < INFINITY) || !(xtol >= 0.0 && xtol < INFINITY) || !(gtol >= 0.0 && gtol < INFINITY) ||
+        (flags & ~PCS_TRI_REFINE_RESIDUALS))
+        return fail(PCS_ERR_ARG, "pcs_tri_refine: bad options (max_iter >= 0, finite tolerances >= 0, flags PCS_TRI_REFINE_RESIDUALS)");
+    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_refine: NULL handle");
+    if (!t->have_cams || t->n_pts < 0 || !t->run_valid)
+        return fail(PCS_ERR_STATE, "pcs_tri_refine: no run on the current cameras and observations (pcs_tri_run first)");
+    const bool want_resid = flags & PCS_TRI_REFINE_RESIDUALS;
+    const int owned = (d_pts ? 0 : PCS_TRI_OUT_POINTS) | (d_rms ? 0 : PCS_TRI_OUT_RMS) | (d_info ? 0 : PCS_TRI_OUT_INFO) |
+                      (want_resid && !d_resid ? PCS_TRI_OUT_RESIDUALS : 0);
+    if (t->n_pts == 0) {
+        t->refine_owned = owned;
+        t->refine_valid = true;
+        return PCS_OK;
+    }
+    HIPCHK(hipSetDevice(t->device));
+    hipStream_t s = stream ? (hipStream_t)stream : t->stream;
+    const bool grows = ((owned & PCS_TRI_OUT_POINTS) && t->n_pts > t->rpts_capacity) || ((owned & PCS_TRI_OUT_RMS) && t->n_pts > t->rrms_capacity) ||
+                       ((owned & PCS_TRI_OUT_INFO) && t->n_pts > t->rinfo_capacity) || ((owned & PCS_TRI_OUT_RESIDUALS) && t->n_obs > t->rres_capacity);
+    if (t->have_done) {   // the run (or an earlier refinement) first: this reads its points and shares the outputs
+        if (grows || s == hipStreamLegacy || t->done_stream == hipStreamLegacy) HIPCHK(hipEventSynchronize(t->done));
+        else if (s != t->done_stream) HIPCHK(hipStreamWaitEvent(s, t->done, 0));
+    }
+    int rc;
+    if (owned & PCS_TRI_OUT_POINTS) {
+        if ((rc = tri_grow((void **)&t->d_rpts, &t->rpts_capacity, t->n_pts, 3 * sizeof(double)))) return rc;
+        d_pts = t->d_rpts;
+    }
+    if (owned & PCS_TRI_OUT_RMS) {
+        if ((rc = tri_grow((void **)&t->d_rrms, &t->rrms_capacity, t->n_pts, 2 * sizeof(double)))) return rc;
+        d_rms = t->d_rrms;
+    }
+    if (owned & PCS_TRI_OUT_INFO) {
+        if ((rc = tri_grow((void **)&t->d_rinfo, &t->rinfo_capacity, t->n_pts, 3 * sizeof(int32_t)))) return rc;
+        d_info = t->d_rinfo;
+    }
+    if (owned & PCS_TRI_OUT_RESIDUALS) {
+        if ((rc = tri_grow((void **)&t->d_rres, &t->rres_capacity, std::max<int64_t>(1, t->n_obs), 2 * sizeof(double)))) return rc;
+        d_resid = t->d_rres;
+    }
+    constexpr int G = 4, V = 6;   // the DLT kernel's default geometry (profiles/r09: resources and time)
+    const dim3 grid((unsigned)((t->n_pts * G + 255) / 256));
+    hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->r0, t->r1, 0, t->cur_cam, (const double2 *)t->cur_uv,
+                          t->cur_start, (const double *)t->d_tab, t->run_pts, t->n_pts, (const int32_t *)(t->order_valid ? t->d_order : nullptr),
+                          max_iter, ftol, xtol, gtol, d_pts, d_rms, d_info, want_resid ? d_resid : nullptr);
+    HIPCHK(hipGetLastError());
+    t->refine_timed = true;
+    t->refine_owned = owned;
+    t->refine_valid = true;
+    t->have_done = true;
+    t->done_stream = s;
+    HIPCHK(hipEventRecord(t->done, s));
+    return PCS_OK;
+}
+
+int pcs_tri_refined(pcs_triangulator *t, double *pts, double *rms, int32_t *info, double *resid) {
+    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_refined: NULL handle");
+    if (!t->refine_valid) return fail(PCS_ERR_STATE, "pcs_tri_refined: no refinement since the last run (pcs_tri_refine first)");
+    const int want = (pts ? PCS_TRI_OUT_POINTS : 0) | (rms ? PCS_TRI_OUT_RMS : 0) | (info ? PCS_TRI_OUT_INFO : 0) | (resid ? PCS_TRI_OUT_RESIDUALS : 0);
+    if (want & ~t->refine_owned)
+        return fail(PCS_ERR_STATE, "pcs_tri_refined: the last refinement wrote some of these outputs to caller buffers (or computed no residuals)");
+    if (t->n_pts == 0) return PCS_OK;
+    HIPCHK(hipSetDevice(t->device));
+    HIPCHK(tri_wait_done_host(t));   // the refinement may have been queued on a caller stream
+    if (pts) HIPCHK(hipMemcpyAsync(pts, t->d_rpts, sizeof(double) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
+    if (rms) HIPCHK(hipMemcpyAsync(rms, t->d_rrms, sizeof(double) * 2 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
+    if (info) HIPCHK(hipMemcpyAsync(info, t->d_rinfo, sizeof(int32_t) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
+    if (resid && t->n_obs) HIPCHK(hipMemcpyAsync(resid, t->d_rres, sizeof(double) * 2 * t->n_obs, hipMemcpyDeviceToHost, t->stream));
+    HIPCHK(hipStreamSynchronize(t->stream));
+    return PCS_OK;
+}
+
+int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms) {
+    if (!t || !kernel_ms) return fail(PCS_ERR_ARG, "pcs_tri_last_refine_ms: bad arguments");
+    if (!t->refine_timed) return fail(PCS_ERR_STATE, "pcs_tri_last_refine_ms: no refinement has run yet");
+    HIPCHK(hipEventSynchronize(t->r1));
+    HIPCHK(hipEventElapsedTime(kernel_ms, t->r0, t->r1));
     return PCS_OK;
 }
 
