@@ -293,7 +293,7 @@ int pcs_schur_syrk_ordered(int device, int64_t n_lead, int64_t n_trail, const do
  *                       right-hand side rides along as one more block row, the backward substitution is a chain of 32-word hand-offs
  *                       between the owners of the diagonal tiles.  n <= 1 984 on a 256-CU part (8 tiles per workgroup);
  *   PCS_SPD_LAUNCHES    one launch per block column + substitution launches (csrc/ba_dense_chol.hpp): any n <= 32 768;
- *   PCS_SPD_AUTO        the first where it fits (environment PCS_CHOL_LAUNCHES=1: always the second).
+ *   PCS_SPD_AUTO        the first where it fits.
  * All pointers are device memory; d_work holds pcs_dense_spd_work_len(n) doubles; *d_status |= 2 when a pivot is not positive,
  * |= 4 when the one-launch form gave up waiting (another process holds the compute units: the results are not valid — solve
  * again with PCS_SPD_LAUNCHES); queued on `stream` (NULL = the default stream). */

@@ -1,6 +1,6 @@
 """In-tree build of the HIP extension: ``python -m pycamset_amd.build``.
 
-One translation unit, gfx950 only; hipcc cross-compiles without a GPU.  The result,
+One translation unit (csrc/pcs_engine.hip and the pcs_*.inc files it includes), gfx950 only; hipcc cross-compiles without a GPU.  The result,
 ``pycamset_amd/libpcs_hip.so``, is git-ignored but travels with gpurun snapshots.
 """
 from __future__ import annotations
@@ -12,8 +12,8 @@ from pathlib import Path
 
 PKG = Path(__file__).resolve().parent
 SRC = PKG / "csrc" / "pcs_engine.hip"
-DEPS = [SRC, PKG / "csrc" / "ba_device.hpp", PKG / "csrc" / "ba_rtc_prelude.hpp", PKG / "csrc" / "ba_kernels.hpp", PKG / "csrc" / "ba_matfree.hpp", PKG / "csrc" / "ba_normal.hpp", PKG / "csrc" / "ba_schur.hpp", PKG / "csrc" / "ba_dense_chol.hpp", PKG / "csrc" / "ba_chol_persist.hpp", PKG / "csrc" / "ba_covariance.hpp", PKG / "csrc" / "ba_generic.hpp", PKG / "csrc" / "ba_blockrow.hpp", PKG / "csrc" / "ba_blockgram.hpp", PKG / "csrc" / "ba_blockcheck.hpp", PKG / "csrc" / "pcs_genchain.inc",
-        PKG / "csrc" / "ba_triangulate.hpp", PKG / "csrc" / "ba_tri_refine.hpp", PKG.parent / "include" / "pcs_hip.h"]
+# everything the translation unit can include: every file directly under csrc/ and the public header
+DEPS = sorted(f for f in (PKG / "csrc").iterdir() if f.is_file()) + [PKG.parent / "include" / "pcs_hip.h"]
 OUT = PKG / "libpcs_hip.so"
 
 

@@ -6,7 +6,8 @@
 // block-reduced normal equations, runs on the FP64 matrix cores (ba_normal.hpp).  See DESIGN.md.
 //
 // Kernels: ba_kernels.hpp (evaluation, compaction, legacy cost), ba_matfree.hpp (J products without J),
-// ba_normal.hpp (J^T J / J^T r), ba_triangulate.hpp; device maths: ba_device.hpp.  This file: launch plumbing + the C ABI.
+// ba_normal.hpp (J^T J / J^T r), ba_triangulate.hpp; device maths: ba_device.hpp.  This file: the pcs_engine handle + its part of the C ABI; one translation unit with
+// pcs_common.inc (errors, device queries), pcs_triangulator.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -41,23 +42,9 @@
 // ---------------------------------------------------------------------------------------------
 using namespace pcs;
 
-static thread_local std::string g_err;
-
-static int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t _e = (expr);                                                                   \
-        if (_e != hipSuccess) return fail(PCS_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+#include "pcs_common.inc"
+#include "pcs_triangulator.inc"
+#include "pcs_solver.inc"
 
 struct pcs_engine {
     int chain = 0, dtype = 0, device = 0, P = 0;
@@ -247,526 +234,6 @@ static void free_det_tables(pcs_engine *h) {
 }
 
 extern "C" {
-
-int pcs_version(void) { return 104; }
-const char *pcs_last_error(void) { return g_err.c_str(); }
-
-// ---- batched triangulation: a handle that owns the camera table, the observation buffers and the
-// kernel's scratch, so that repeated calls (CameraSet.multi_cam_triangulate per frame set, cameras/camera_set.py:343-402)
-// pay neither allocations nor — with device-resident inputs — copies.
-struct pcs_triangulator {
-    int device = 0;
-    int64_t n_cams = 0;
-    bool have_cams = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool timed = false;
-    double *d_tab = nullptr;
-    // handle-owned copies of host inputs (grown on demand)
-    int32_t *d_cam = nullptr; double *d_uv = nullptr; int64_t *d_start = nullptr;
-    int64_t obs_capacity = 0, uv_capacity = 0, pts_capacity = 0;
-    // scratch + default output
-    void *d_scr = nullptr, *d_scl = nullptr; double *d_pts = nullptr;
-    int64_t scr_capacity = 0, scl_capacity = 0, out_capacity = 0;
-    // current problem (device pointers: handle-owned or the caller's)
-    const int32_t *cur_cam = nullptr; const double *cur_uv = nullptr; const int64_t *cur_start = nullptr;
-    int64_t n_obs = 0, n_pts = -1;
-    // the grouping in front of the triangulation (pcs_tri_group_device): per-feature counts, block sums of the scan, totals
-    int32_t *d_count = nullptr; uint64_t *d_block_sums = nullptr; int64_t *d_totals = nullptr;
-    int64_t count_capacity = 0, block_capacity = 0;
-    int32_t *d_order = nullptr, *d_hist = nullptr;   // points by view count (built by the first run of a set of observations)
-    int64_t order_capacity = 0;
-    bool order_valid = false, sort_points = true;
-    int variant = 1; // 1: views in registers + divide-free rotations (round 4; 3: eight instead of six register views per lane); 0: round 3's kernel (PCS_TRI_VARIANT=0)
-    int lanes = 4;   // lanes per point: 1, 2, 4, 8 or 16 (profiles/r01/tri_legacy_bench.log: 4 is fastest at 2-22 views)
-    // Ordering across streams, as in pcs_engine: `done` is recorded after every run; whatever touches the camera table, the
-    // handle-owned observation copies, the scratch or the output next first waits for it — on the host where the host
-    // writes or reads, with hipStreamWaitEvent where a run moves to another stream (scratch and output are shared).
-    hipEvent_t done = nullptr;
-    hipStream_t done_stream = nullptr;
-    bool have_done = false;
-    bool out_owned = false;   // the last run wrote the handle-owned output (pcs_tri_points has something to return)
-    // the refinement (pcs_tri_refine): it starts from the points of the last run on the current cameras and observations
-    bool run_valid = false;          // a run since the cameras / observations were last set
-    const double *run_pts = nullptr; // where that run wrote its points (handle-owned or the caller's buffer)
-    double *d_rpts = nullptr, *d_rrms = nullptr, *d_rres = nullptr; int32_t *d_rinfo = nullptr;   // handle-owned refinement outputs
-    int64_t rpts_capacity = 0, rrms_capacity = 0, rres_capacity = 0, rinfo_capacity = 0;
-    int refine_owned = 0;            // PCS_TRI_OUT_* bits: which outputs of the last refinement are handle-owned
-    bool refine_valid = false;       // a refinement since the last run (pcs_tri_refined has something to return)
-    hipEvent_t r0 = nullptr, r1 = nullptr;
-    bool refine_timed = false;
-};
-
-static hipError_t tri_wait_done_host(pcs_triangulator *t) { return t->have_done ? hipEventSynchronize(t->done) : hipSuccess; }
-
-static int tri_grow(void **buf, int64_t *cap, int64_t need, size_t elem) {
-    if (need <= *cap) return PCS_OK;
-    if (*buf) HIPCHK(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    HIPCHK(hipMalloc(buf, elem * (size_t)need));
-    *cap = need;
-    return PCS_OK;
-}
-
-int pcs_tri_create(pcs_triangulator **out, int device, int64_t n_cams) {
-    if (!out || n_cams <= 0) return fail(PCS_ERR_ARG, "pcs_tri_create: bad arguments");
-    *out = nullptr;
-    const int ndev = pcs_device_count();
-    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "pcs_tri_create: no HIP device visible (no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "pcs_tri_create: device out of range");
-    HIPCHK(hipSetDevice(device));
-    pcs_triangulator *t = new pcs_triangulator();
-    t->device = device;
-    t->n_cams = n_cams;
-    const char *lanes_env = getenv("PCS_TRI_LANES");   // A/B switch
-    const int lanes = lanes_env ? atoi(lanes_env) : 4;
-    t->lanes = (lanes == 1 || lanes == 2 || lanes == 8 || lanes == 16) ? lanes : 4;
-    const char *var_env = getenv("PCS_TRI_VARIANT");
-    t->variant = var_env ? atoi(var_env) : 1;
-    t->sort_points = getenv("PCS_TRI_NO_SORT") == nullptr;   // A/B switch
-    hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&t->e0);
-    if (e == hipSuccess) e = hipEventCreate(&t->e1);
-    if (e == hipSuccess) e = hipEventCreate(&t->r0);
-    if (e == hipSuccess) e = hipEventCreate(&t->r1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc(&t->d_tab, sizeof(double) * n_cams * TRI_CAM_STRIDE);
-    if (e != hipSuccess) {
-        const int rc = fail(PCS_ERR_HIP, "pcs_tri_create: %s", hipGetErrorString(e));
-        pcs_tri_destroy(t);
-        return rc;
-    }
-    *out = t;
-    return PCS_OK;
-}
-
-int pcs_tri_destroy(pcs_triangulator *t) {
-    if (!t) return PCS_OK;
-    (void)hipSetDevice(t->device);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    (void)tri_wait_done_host(t);   // a run on a caller stream may still read the tables
-    for (void *b : {(void *)t->d_tab, (void *)t->d_cam, (void *)t->d_uv, (void *)t->d_start, t->d_scr, t->d_scl, (void *)t->d_pts, (void *)t->d_order, (void *)t->d_hist,
-                    (void *)t->d_count, (void *)t->d_block_sums, (void *)t->d_totals, (void *)t->d_rpts, (void *)t->d_rrms, (void *)t->d_rres,
-                    (void *)t->d_rinfo})
-        if (b) (void)hipFree(b);
-    if (t->e0) (void)hipEventDestroy(t->e0);
-    if (t->e1) (void)hipEventDestroy(t->e1);
-    if (t->r0) (void)hipEventDestroy(t->r0);
-    if (t->r1) (void)hipEventDestroy(t->r1);
-    if (t->done) (void)hipEventDestroy(t->done);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
-    delete t;
-    return PCS_OK;
-}
-
-int pcs_tri_set_cameras(pcs_triangulator *t, const double *proj, const double *intrinsics, const double *dists) {
-    if (!t || !proj || !intrinsics || !dists) return fail(PCS_ERR_ARG, "pcs_tri_set_cameras: bad arguments");
-    std::vector<double> tab((size_t)t->n_cams * TRI_CAM_STRIDE, 0.0);
-    for (int64_t c = 0; c < t->n_cams; ++c) {
-        double *r = tab.data() + c * TRI_CAM_STRIDE;
-        for (int k = 0; k < 12; ++k) r[k] = proj[12 * c + k];
-        const double *K = intrinsics + 9 * c;
-        r[22] = K[0]; r[23] = K[2]; r[24] = K[4]; r[25] = K[5];
-        for (int k = 0; k < 5; ++k) r[26 + k] = dists[5 * c + k];
-    }
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // a run queued on ANY stream may still read the table
-    HIPCHK(hipStreamSynchronize(t->stream));
-    HIPCHK(hipMemcpy(t->d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    t->have_cams = true;
-    t->run_valid = t->refine_valid = false;   // a refinement must start from points of these cameras
-    return PCS_OK;
-}
-
-int pcs_tri_set_observations(pcs_triangulator *t, int64_t n_obs, const int32_t *cam, const double *uv, int64_t n_pts, const int64_t *start_inds) {
-    if (!t || n_obs < 0 || n_pts < 0 || !start_inds || (n_obs > 0 && (!cam || !uv))) return fail(PCS_ERR_ARG, "pcs_tri_set_observations: bad arguments");
-    if (start_inds[0] != 0 || start_inds[n_pts] != n_obs) return fail(PCS_ERR_ARG, "pcs_tri_set_observations: start_inds must run from 0 to n_obs");
-    for (int64_t j = 0; j < n_pts; ++j)
-        if (start_inds[j + 1] < start_inds[j]) return fail(PCS_ERR_ARG, "pcs_tri_set_observations: start_inds must be non-decreasing");
-    for (int64_t r = 0; r < n_obs; ++r)
-        if (cam[r] < 0 || cam[r] >= t->n_cams) return fail(PCS_ERR_RANGE, "observation %lld has camera %d outside [0,%lld)", (long long)r, cam[r], (long long)t->n_cams);
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // a run queued on ANY stream may still read the observation copies
-    HIPCHK(hipStreamSynchronize(t->stream));
-    t->n_pts = -1;
-    int rc = tri_grow((void **)&t->d_cam, &t->obs_capacity, std::max<int64_t>(1, n_obs), sizeof(int32_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_uv, &t->uv_capacity, std::max<int64_t>(1, n_obs), 2 * sizeof(double));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_start, &t->pts_capacity, n_pts + 1, sizeof(int64_t));
-    if (rc) return rc;
-    if (n_obs) {
-        HIPCHK(hipMemcpyAsync(t->d_cam, cam, sizeof(int32_t) * n_obs, hipMemcpyHostToDevice, t->stream));
-        HIPCHK(hipMemcpyAsync(t->d_uv, uv, sizeof(double) * 2 * n_obs, hipMemcpyHostToDevice, t->stream));
-    }
-    HIPCHK(hipMemcpyAsync(t->d_start, start_inds, sizeof(int64_t) * (n_pts + 1), hipMemcpyHostToDevice, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));   // the caller may reuse its host arrays
-    t->cur_cam = t->d_cam; t->cur_uv = t->d_uv; t->cur_start = t->d_start;
-    t->n_obs = n_obs; t->n_pts = n_pts;
-    t->order_valid = false;
-    t->out_owned = false;   // results of an earlier problem are not this problem's
-    t->run_valid = t->refine_valid = false;
-    return PCS_OK;
-}
-
-int pcs_tri_set_observations_device(pcs_triangulator *t, int64_t n_obs, const int32_t *d_cam, const double *d_uv, int64_t n_pts, const int64_t *d_start_inds) {
-    if (!t || n_obs < 0 || n_pts < 0 || !d_start_inds || (n_obs > 0 && (!d_cam || !d_uv))) return fail(PCS_ERR_ARG, "pcs_tri_set_observations_device: bad arguments");
-    t->cur_cam = d_cam; t->cur_uv = d_uv; t->cur_start = d_start_inds;   // caller-owned, not range-checked (stay on the device)
-    t->n_obs = n_obs; t->n_pts = n_pts;
-    t->order_valid = false;
-    t->out_owned = false;
-    t->run_valid = t->refine_valid = false;
-    return PCS_OK;
-}
-
-// The grouping CameraSet.multi_cam_triangulate does in front of nb_triangulate_full (cameras/camera_set.py:371-378), on the device
-// (csrc/ba_triangulate.hpp, "the grouping in front of the triangulation"): from n table rows (camera, dense feature id, measurement;
-// caller-owned device arrays, the table grouped by feature) to the handle's current observations — the rows of features seen by at
-// least two cameras, in table order, and their start indices.  One host synchronisation (the counts).  *grouped = 0: the table is
-// NOT grouped by feature (a feature's rows are not consecutive): nothing was set, the caller groups on the host.
-int pcs_tri_group_device(pcs_triangulator *t, int64_t n, const int32_t *d_cam, const int32_t *d_feat, const double *d_uv, int64_t n_features,
-                         int64_t *n_pts, int64_t *n_kept, int32_t *grouped, void *stream) {
-    if (!t || n < 0 || n > INT32_MAX || n_features <= 0 || n_features > INT32_MAX || !n_pts || !n_kept || !grouped || (n > 0 && (!d_cam || !d_feat || !d_uv)))
-        return fail(PCS_ERR_ARG, "pcs_tri_group_device: bad arguments");
-    *n_pts = *n_kept = 0;
-    *grouped = 1;
-    HIPCHK(hipSetDevice(t->device));
-    hipStream_t s = stream ? (hipStream_t)stream : t->stream;
-    HIPCHK(tri_wait_done_host(t));   // a run queued on ANY stream may still read the observation copies this call overwrites
-    HIPCHK(hipStreamSynchronize(t->stream));
-    t->n_pts = -1;
-    t->run_valid = t->refine_valid = false;
-    if (n == 0) {
-        int rc0 = tri_grow((void **)&t->d_start, &t->pts_capacity, 1, sizeof(int64_t));
-        if (rc0) return rc0;
-        HIPCHK(hipMemsetAsync(t->d_start, 0, sizeof(int64_t), s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->cur_cam = t->d_cam; t->cur_uv = t->d_uv; t->cur_start = t->d_start;
-        t->n_obs = 0; t->n_pts = 0; t->order_valid = false; t->out_owned = false;
-        return PCS_OK;
-    }
-    const int64_t n_blocks = (n + TRI_GROUP_BLOCK - 1) / TRI_GROUP_BLOCK;
-    int rc = tri_grow((void **)&t->d_cam, &t->obs_capacity, n, sizeof(int32_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_uv, &t->uv_capacity, n, 2 * sizeof(double));
-    if (rc) return rc;
-    // one entry per kept run + 1.  A GROUPED table has at most n / 2 kept runs, but whether it is grouped is only known afterwards: in a table
-    // whose features interleave every row can be the head of a kept run (writes up to start[n]; sized for n / 2 + 2 until this was found
-    // by a fault in the full test suite — alone, the overrun stayed inside the allocation)
-    rc = tri_grow((void **)&t->d_start, &t->pts_capacity, n + 2, sizeof(int64_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_count, &t->count_capacity, n_features, sizeof(int32_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_block_sums, &t->block_capacity, n_blocks, sizeof(uint64_t));
-    if (rc) return rc;
-    if (!t->d_totals) HIPCHK(hipMalloc(&t->d_totals, sizeof(int64_t) * 4));
-    HIPCHK(hipMemsetAsync(t->d_count, 0, sizeof(int32_t) * n_features, s));
-    HIPCHK(hipMemsetAsync(t->d_totals, 0, sizeof(int64_t) * 4, s));
-    TriGroupArgs a{d_cam, d_feat, reinterpret_cast<const double2 *>(d_uv), t->d_count, t->d_block_sums, t->d_totals, t->d_cam,
-                   reinterpret_cast<double2 *>(t->d_uv), t->d_start, n, n_features, (int32_t)n_blocks};
-    hipLaunchKernelGGL(tri_group_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(tri_group_blocksum_kernel, dim3((unsigned)n_blocks), dim3(TRI_GROUP_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(tri_group_scan_sums_kernel, dim3(1), dim3(TRI_GROUP_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(tri_group_scatter_kernel, dim3((unsigned)n_blocks), dim3(TRI_GROUP_BLOCK), 0, s, a);
-    HIPCHK(hipGetLastError());
-    int64_t totals[4];
-    HIPCHK(hipMemcpyAsync(totals, t->d_totals, sizeof totals, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (totals[2] != totals[3]) {   // more runs than features: some feature's rows are not consecutive
-        *grouped = 0;
-        return PCS_OK;
-    }
-    *n_kept = totals[0];
-    *n_pts = totals[1];
-    t->cur_cam = t->d_cam; t->cur_uv = t->d_uv; t->cur_start = t->d_start;
-    t->n_obs = totals[0]; t->n_pts = totals[1];
-    t->order_valid = false;
-    t->out_owned = false;
-    return PCS_OK;
-}
-
-int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
-    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_run: bad arguments");
-    if (!t->have_cams) return fail(PCS_ERR_STATE, "pcs_tri_run: cameras not set");
-    if (t->n_pts < 0) return fail(PCS_ERR_STATE, "pcs_tri_run: observations not set");
-    t->refine_valid = false;
-    if (t->n_pts == 0) {
-        t->run_valid = true;
-        t->run_pts = d_pts;
-        return PCS_OK;
-    }
-    HIPCHK(hipSetDevice(t->device));
-    hipStream_t s = stream ? (hipStream_t)stream : t->stream;
-    const bool need_order = t->variant != 0 && t->sort_points && !t->order_valid && t->n_pts < (1ll << 31);
-    const bool grows = t->n_obs > t->scr_capacity || t->n_obs > t->scl_capacity || (!d_pts && t->n_pts > t->out_capacity) || (need_order && t->n_pts > t->order_capacity);
-    if (t->have_done) {   // scratch and output are shared between runs: the previous one finishes first
-        if (grows || s == hipStreamLegacy || t->done_stream == hipStreamLegacy) HIPCHK(hipEventSynchronize(t->done));   // frees need the host to wait
-        else if (s != t->done_stream) HIPCHK(hipStreamWaitEvent(s, t->done, 0));
-    }
-    int rc = tri_grow(&t->d_scr, &t->scr_capacity, std::max<int64_t>(1, t->n_obs), 4 * sizeof(double));   // Householder row r_i per observation
-    if (rc) return rc;
-    rc = tri_grow(&t->d_scl, &t->scl_capacity, std::max<int64_t>(1, t->n_obs), 2 * sizeof(double));   // (1 / E_i, lambda_i)
-    if (rc) return rc;
-    const bool owned = !d_pts;
-    if (owned) {
-        rc = tri_grow((void **)&t->d_pts, &t->out_capacity, t->n_pts, 3 * sizeof(double));
-        if (rc) return rc;
-        d_pts = t->d_pts;
-    }
-    const int lanes = t->lanes;
-    const dim3 grid((unsigned)((t->n_pts * lanes + 255) / 256));
-    if (need_order) {
-        // the visiting order of this set of observations, on the run's own stream (the caller's start_inds may have been produced there)
-        rc = tri_grow((void **)&t->d_order, &t->order_capacity, t->n_pts, sizeof(int32_t));
-        if (rc) return rc;
-        if (!t->d_hist) HIPCHK(hipMalloc(&t->d_hist, sizeof(int32_t) * 512));
-        HIPCHK(hipMemsetAsync(t->d_hist, 0, sizeof(int32_t) * 512, s));
-        const dim3 pg((unsigned)((t->n_pts + 255) / 256));
-        hipLaunchKernelGGL(tri_order_count_kernel, pg, dim3(256), 0, s, t->cur_start, t->n_pts, t->d_hist);
-        hipLaunchKernelGGL(tri_order_scan_kernel, dim3(1), dim3(256), 0, s, t->d_hist);
-        hipLaunchKernelGGL(tri_order_scatter_kernel, pg, dim3(256), 0, s, t->cur_start, t->n_pts, t->d_hist, t->d_order);
-        HIPCHK(hipGetLastError());
-        t->order_valid = true;
-    }
-#define PCS_TRI_LAUNCH(G_)                                                                                                     \
-    hipExtLaunchKernelGGL(triangulate_kernel<G_>, grid, dim3(256), 0, s, t->e0, t->e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
-                          t->cur_start, (const double *)t->d_tab, (double4 *)t->d_scr, (double2 *)t->d_scl, d_pts, t->n_pts)
-#define PCS_TRI_LAUNCH_REG(G_, V_)                                                                                                     \
-    hipExtLaunchKernelGGL((triangulate_reg_kernel<G_, V_>), grid, dim3(256), 0, s, t->e0, t->e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
-                          t->cur_start, (const double *)t->d_tab, (double4 *)t->d_scr, (double2 *)t->d_scl, d_pts, t->n_pts, (const int32_t *)(t->order_valid ? t->d_order : nullptr))
-    if (t->variant == 0) {   // round 3's form (views in the global scratch, IEEE divides): kept for A/B (PCS_TRI_VARIANT=0)
-        if (lanes == 1) PCS_TRI_LAUNCH(1);
-        else if (lanes == 2) PCS_TRI_LAUNCH(2);
-        else if (lanes == 8) PCS_TRI_LAUNCH(8);
-        else if (lanes == 16) PCS_TRI_LAUNCH(16);
-        else PCS_TRI_LAUNCH(4);
-    } else {                 // views in registers (6 or 8 per lane; further ones in the scratch), divide-free rotations
-        if (lanes == 1) PCS_TRI_LAUNCH_REG(1, 8);
-        else if (lanes == 2) PCS_TRI_LAUNCH_REG(2, 8);
-        else if (lanes == 8) PCS_TRI_LAUNCH_REG(8, 8);
-        else if (lanes == 16) PCS_TRI_LAUNCH_REG(16, 8);
-        else if (t->variant == 3) PCS_TRI_LAUNCH_REG(4, 8);
-        else PCS_TRI_LAUNCH_REG(4, 6);   // 24 views in registers at 156 VGPRs (three waves per SIMD): 47 us against 52 us for (4, 8); (4, 3) — four waves
-                                         // per SIMD, 12 register views, the rest through the scratch records — 53 us, (4, 4) 49 us (profiles/r05/tri_bench_r05.log)
-    }
-#undef PCS_TRI_LAUNCH_REG
-#undef PCS_TRI_LAUNCH
-    HIPCHK(hipGetLastError());
-    t->timed = true;
-    t->out_owned = owned;
-    t->run_valid = true;
-    t->run_pts = d_pts;
-    t->have_done = true;
-    t->done_stream = s;   // compared only, never used as a handle again
-    HIPCHK(hipEventRecord(t->done, s));
-    return PCS_OK;
-}
-
-// The refinement of the last run's points (csrc/ba_tri_refine.hpp): per-point LM on the reprojection error in the measured pixels.
-static_assert(TRI_REFINE_NOT_REFINED == PCS_TRI_REFINE_NOT_REFINED && TRI_REFINE_CONVERGED == PCS_TRI_REFINE_CONVERGED &&
-              TRI_REFINE_MAX_ITER == PCS_TRI_REFINE_MAX_ITER && TRI_REFINE_NO_DECREASE == PCS_TRI_REFINE_NO_DECREASE, "status codes of pcs_hip.h");
-int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, double gtol, int flags, double *d_pts, double *d_rms,
-                   int32_t *d_info, double *d_resid, void *stream) {
-    if (max_iter < 0 || !(ftol >= 0.0 && ftol < INFINITY) || !(xtol >= 0.0 && xtol < INFINITY) || !(gtol >= 0.0 && gtol < INFINITY) ||
-        (flags & ~PCS_TRI_REFINE_RESIDUALS))
-        return fail(PCS_ERR_ARG, "pcs_tri_refine: bad options (max_iter >= 0, finite tolerances >= 0, flags PCS_TRI_REFINE_RESIDUALS)");
-    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_refine: NULL handle");
-    if (!t->have_cams || t->n_pts < 0 || !t->run_valid)
-        return fail(PCS_ERR_STATE, "pcs_tri_refine: no run on the current cameras and observations (pcs_tri_run first)");
-    const bool want_resid = flags & PCS_TRI_REFINE_RESIDUALS;
-    const int owned = (d_pts ? 0 : PCS_TRI_OUT_POINTS) | (d_rms ? 0 : PCS_TRI_OUT_RMS) | (d_info ? 0 : PCS_TRI_OUT_INFO) |
-                      (want_resid && !d_resid ? PCS_TRI_OUT_RESIDUALS : 0);
-    if (t->n_pts == 0) {
-        t->refine_owned = owned;
-        t->refine_valid = true;
-        return PCS_OK;
-    }
-    HIPCHK(hipSetDevice(t->device));
-    hipStream_t s = stream ? (hipStream_t)stream : t->stream;
-    const bool grows = ((owned & PCS_TRI_OUT_POINTS) && t->n_pts > t->rpts_capacity) || ((owned & PCS_TRI_OUT_RMS) && t->n_pts > t->rrms_capacity) ||
-                       ((owned & PCS_TRI_OUT_INFO) && t->n_pts > t->rinfo_capacity) || ((owned & PCS_TRI_OUT_RESIDUALS) && t->n_obs > t->rres_capacity);
-    if (t->have_done) {   // the run (or an earlier refinement) first: this reads its points and shares the outputs
-        if (grows || s == hipStreamLegacy || t->done_stream == hipStreamLegacy) HIPCHK(hipEventSynchronize(t->done));
-        else if (s != t->done_stream) HIPCHK(hipStreamWaitEvent(s, t->done, 0));
-    }
-    int rc;
-    if (owned & PCS_TRI_OUT_POINTS) {
-        if ((rc = tri_grow((void **)&t->d_rpts, &t->rpts_capacity, t->n_pts, 3 * sizeof(double)))) return rc;
-        d_pts = t->d_rpts;
-    }
-    if (owned & PCS_TRI_OUT_RMS) {
-        if ((rc = tri_grow((void **)&t->d_rrms, &t->rrms_capacity, t->n_pts, 2 * sizeof(double)))) return rc;
-        d_rms = t->d_rrms;
-    }
-    if (owned & PCS_TRI_OUT_INFO) {
-        if ((rc = tri_grow((void **)&t->d_rinfo, &t->rinfo_capacity, t->n_pts, 3 * sizeof(int32_t)))) return rc;
-        d_info = t->d_rinfo;
-    }
-    if (owned & PCS_TRI_OUT_RESIDUALS) {
-        if ((rc = tri_grow((void **)&t->d_rres, &t->rres_capacity, std::max<int64_t>(1, t->n_obs), 2 * sizeof(double)))) return rc;
-        d_resid = t->d_rres;
-    }
-    constexpr int G = 4, V = 6;   // the DLT kernel's default geometry (profiles/r09: resources and time)
-    const dim3 grid((unsigned)((t->n_pts * G + 255) / 256));
-    hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->r0, t->r1, 0, t->cur_cam, (const double2 *)t->cur_uv,
-                          t->cur_start, (const double *)t->d_tab, t->run_pts, t->n_pts, (const int32_t *)(t->order_valid ? t->d_order : nullptr),
-                          max_iter, ftol, xtol, gtol, d_pts, d_rms, d_info, want_resid ? d_resid : nullptr);
-    HIPCHK(hipGetLastError());
-    t->refine_timed = true;
-    t->refine_owned = owned;
-    t->refine_valid = true;
-    t->have_done = true;
-    t->done_stream = s;
-    HIPCHK(hipEventRecord(t->done, s));
-    return PCS_OK;
-}
-
-int pcs_tri_refined(pcs_triangulator *t, double *pts, double *rms, int32_t *info, double *resid) {
-    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_refined: NULL handle");
-    if (!t->refine_valid) return fail(PCS_ERR_STATE, "pcs_tri_refined: no refinement since the last run (pcs_tri_refine first)");
-    const int want = (pts ? PCS_TRI_OUT_POINTS : 0) | (rms ? PCS_TRI_OUT_RMS : 0) | (info ? PCS_TRI_OUT_INFO : 0) | (resid ? PCS_TRI_OUT_RESIDUALS : 0);
-    if (want & ~t->refine_owned)
-        return fail(PCS_ERR_STATE, "pcs_tri_refined: the last refinement wrote some of these outputs to caller buffers (or computed no residuals)");
-    if (t->n_pts == 0) return PCS_OK;
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // the refinement may have been queued on a caller stream
-    if (pts) HIPCHK(hipMemcpyAsync(pts, t->d_rpts, sizeof(double) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    if (rms) HIPCHK(hipMemcpyAsync(rms, t->d_rrms, sizeof(double) * 2 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    if (info) HIPCHK(hipMemcpyAsync(info, t->d_rinfo, sizeof(int32_t) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    if (resid && t->n_obs) HIPCHK(hipMemcpyAsync(resid, t->d_rres, sizeof(double) * 2 * t->n_obs, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    return PCS_OK;
-}
-
-int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms) {
-    if (!t || !kernel_ms) return fail(PCS_ERR_ARG, "pcs_tri_last_refine_ms: bad arguments");
-    if (!t->refine_timed) return fail(PCS_ERR_STATE, "pcs_tri_last_refine_ms: no refinement has run yet");
-    HIPCHK(hipEventSynchronize(t->r1));
-    HIPCHK(hipEventElapsedTime(kernel_ms, t->r0, t->r1));
-    return PCS_OK;
-}
-
-int pcs_tri_points(pcs_triangulator *t, double *pts) {
-    if (!t || !pts) return fail(PCS_ERR_ARG, "pcs_tri_points: bad arguments");
-    if (t->n_pts < 0 || (t->n_pts > 0 && (!t->out_owned || !t->d_pts || t->out_capacity < t->n_pts)))
-        return fail(PCS_ERR_STATE, "pcs_tri_points: the last run left no handle-owned result (run with d_pts = NULL first)");
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // the run may have been queued on a caller stream
-    if (t->n_pts) HIPCHK(hipMemcpyAsync(pts, t->d_pts, sizeof(double) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    return PCS_OK;
-}
-
-int pcs_tri_synchronize(pcs_triangulator *t, void *stream) {
-    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_synchronize: bad arguments");
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(hipStreamSynchronize(stream ? (hipStream_t)stream : t->stream));
-    return PCS_OK;
-}
-
-int pcs_tri_last_kernel_ms(pcs_triangulator *t, float *kernel_ms) {
-    if (!t || !kernel_ms) return fail(PCS_ERR_ARG, "pcs_tri_last_kernel_ms: bad arguments");
-    if (!t->timed) return fail(PCS_ERR_STATE, "pcs_tri_last_kernel_ms: nothing has run yet");
-    HIPCHK(hipEventSynchronize(t->e1));
-    HIPCHK(hipEventElapsedTime(kernel_ms, t->e0, t->e1));
-    return PCS_OK;
-}
-
-// stateless convenience form: one temporary handle per call (allocations + copies every time — use the handle API
-// for repeated calls)
-int pcs_triangulate(int device, int64_t n_obs, const int32_t *cam, const double *uv, int64_t n_pts, const int64_t *start_inds,
-                    int64_t n_cams, const double *proj, const double *intrinsics, const double *dists, double *pts,
-                    float *kernel_ms) {
-    if (n_obs < 0 || n_pts < 0 || n_cams <= 0 || !start_inds || !proj || !intrinsics || !dists || (n_pts > 0 && !pts) ||
-        (n_obs > 0 && (!cam || !uv)))
-        return fail(PCS_ERR_ARG, "pcs_triangulate: bad arguments");
-    if (n_pts == 0) return PCS_OK;
-    pcs_triangulator *t = nullptr;
-    int rc = pcs_tri_create(&t, device, n_cams);
-    if (rc) return rc;
-    rc = pcs_tri_set_cameras(t, proj, intrinsics, dists);
-    if (!rc) rc = pcs_tri_set_observations(t, n_obs, cam, uv, n_pts, start_inds);
-    if (!rc) rc = pcs_tri_run(t, nullptr, nullptr);
-    if (!rc) rc = pcs_tri_points(t, pts);
-    if (!rc && kernel_ms) rc = pcs_tri_last_kernel_ms(t, kernel_ms);
-    const std::string keep = g_err;   // pcs_tri_destroy must not clobber the message
-    pcs_tri_destroy(t);
-    g_err = keep;
-    return rc;
-}
-
-int pcs_host_alloc(void **out, int64_t bytes) {
-    if (!out || bytes <= 0) return fail(PCS_ERR_ARG, "pcs_host_alloc: bad arguments");
-    *out = nullptr;
-    HIPCHK(hipHostMalloc(out, (size_t)bytes, hipHostMallocDefault));
-    return PCS_OK;
-}
-
-int pcs_host_free(void *p) {
-    if (p) HIPCHK(hipHostFree(p));
-    return PCS_OK;
-}
-
-int pcs_membench(int device, int kind, int64_t bytes, int iters, int blocks_per_cu, float *mean_ms) {
-    if (kind < 0 || kind > 8 || bytes < 4096 || iters < 1 || !mean_ms) return fail(PCS_ERR_ARG, "pcs_membench: bad arguments");
-    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_membench: device %d not available", device);
-    HIPCHK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    void *src = nullptr, *dst = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (src) (void)hipFree(src);
-        if (dst) (void)hipFree(dst);
-    };
-#define MBCHK(expr)                                                                                              \
-    do {                                                                                                         \
-        hipError_t _e = (expr);                                                                                  \
-        if (_e != hipSuccess) { const int _rc = fail(PCS_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); cleanup(); return _rc; } \
-    } while (0)
-    MBCHK(hipMalloc(&dst, bytes));
-    if (kind == 2 || kind == 3) {
-        MBCHK(hipMalloc(&src, bytes));
-        MBCHK(hipMemset(src, 1, bytes));
-    }
-    MBCHK(hipEventCreate(&e0));
-    MBCHK(hipEventCreate(&e1));
-    const int64_t n16 = bytes / 16;
-    const dim3 grid((unsigned)std::min<int64_t>((n16 + 255) / 256, (int64_t)prop.multiProcessorCount * std::max(1, blocks_per_cu)));
-    auto launch = [&]() {
-        switch (kind) {
-            case 0: hipLaunchKernelGGL(membench_kernel<0>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            case 1: hipLaunchKernelGGL(membench_kernel<1>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            case 2: hipLaunchKernelGGL(membench_kernel<2>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            case 3: hipLaunchKernelGGL(membench_kernel<3>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            case 4: hipLaunchKernelGGL(membench_kernel<4>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            case 5: hipLaunchKernelGGL(membench_kernel<5>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            case 6: hipLaunchKernelGGL(membench_kernel<6>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            case 7: hipLaunchKernelGGL(membench_kernel<7>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-            default: hipLaunchKernelGGL(membench_kernel<8>, grid, dim3(256), 0, nullptr, (const double2 *)src, (double2 *)dst, n16); break;
-        }
-    };
-    for (int i = 0; i < 3; ++i) launch();
-    MBCHK(hipEventRecord(e0, nullptr));
-    for (int i = 0; i < iters; ++i) launch();
-    MBCHK(hipEventRecord(e1, nullptr));
-    MBCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    MBCHK(hipEventElapsedTime(&ms, e0, e1));
-#undef MBCHK
-    *mean_ms = ms / iters;
-    cleanup();
-    return PCS_OK;
-}
-
-int pcs_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
 
 int pcs_create(pcs_engine **out, int chain, int dtype, int64_t n_cams, int64_t n_imgs, int64_t n_keys, int device) {
     if (!out) return fail(PCS_ERR_ARG, "pcs_create: out is NULL");
@@ -1277,30 +744,6 @@ static hipError_t gather_rows(const int32_t *order, const void *src, void **dst,
 
 // (cam, key)- and (image, key)-sorted visiting orders for the point passes of the normal equations: built on the host
 // at the first normal-equations call of a self / free engine (two stable sorts, ~0.1 s at 1e6 detections)
-static int build_point_orders(pcs_engine *h);
-// all or nothing: a build that fails half-way (an allocation, a gather launch) leaves no sorted copy behind, so that the
-// next call starts again instead of pairing sorted index words with unsorted measurements
-static int ensure_point_orders(pcs_engine *h) {
-    if (h->point_orders_tried) return PCS_OK;
-    const int rc = build_point_orders(h);
-    if (rc == PCS_OK) {
-        h->point_orders_tried = true;
-        return PCS_OK;
-    }
-    const std::string keep = g_err;
-    (void)hipStreamSynchronize(h->stream);
-    for (int32_t **o : {&h->d_order_ck, &h->d_order_ik}) {
-        if (*o) (void)hipFree(*o);
-        *o = nullptr;
-    }
-    for (auto &t : h->d_sorted)
-        for (void *&b : t) {
-            if (b) (void)hipFree(b);
-            b = nullptr;
-        }
-    g_err = keep;
-    return rc;
-}
 static int build_point_orders(pcs_engine *h) {
     const int64_t n = h->n;
     if (n <= 0) return PCS_OK;
@@ -1337,6 +780,30 @@ static int build_point_orders(pcs_engine *h) {
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return PCS_OK;
+}
+
+// all or nothing: a build that fails half-way (an allocation, a gather launch) leaves no sorted copy behind, so that the
+// next call starts again instead of pairing sorted index words with unsorted measurements
+static int ensure_point_orders(pcs_engine *h) {
+    if (h->point_orders_tried) return PCS_OK;
+    const int rc = build_point_orders(h);
+    if (rc == PCS_OK) {
+        h->point_orders_tried = true;
+        return PCS_OK;
+    }
+    const std::string keep = g_err;
+    (void)hipStreamSynchronize(h->stream);
+    for (int32_t **o : {&h->d_order_ck, &h->d_order_ik}) {
+        if (*o) (void)hipFree(*o);
+        *o = nullptr;
+    }
+    for (auto &t : h->d_sorted)
+        for (void *&b : t) {
+            if (b) (void)hipFree(b);
+            b = nullptr;
+        }
+    g_err = keep;
+    return rc;
 }
 
 // The (image, key) pass reads no measurements under the linear loss, so build_point_orders gathers none for it; a robust loss weighs
@@ -1481,14 +948,6 @@ static hipError_t launch_reduce(int chain, int pass, const NormalArgs &a, const 
     return chain == CHAIN_SELF ? launch_reduce_p<CHAIN_SELF, PASS_CAMKEY>(a, ra, s) : launch_reduce_p<CHAIN_FREE, PASS_CAMKEY>(a, ra, s);
 }
 
-// The blocked layout of J^T J (NormalArgs, ba_normal.hpp): where the parameter string splits into leading part and trailing group.
-struct BlockLayout {
-    int64_t n_lead, n_trail, n_ent, trail_off;
-    int tb, tg;
-    int64_t a_len() const { return n_lead * n_lead; }
-    int64_t b_len() const { return n_lead * n_trail; }
-    int64_t c_len() const { return n_ent * tb * tb; }
-};
 static BlockLayout block_layout(const pcs_engine *h) {
     BlockLayout L{};
     if (h->chain == PCS_CHAIN_TEMPLATE) { L.tg = 2; L.tb = 6; L.trail_off = h->pose_off; L.n_ent = h->n_imgs; }
@@ -1500,10 +959,10 @@ static BlockLayout block_layout(const pcs_engine *h) {
 
 // slab_prep + the normal-equations passes on `s`; d_prm holds the parameter string; outputs are zeroed here.
 // blocked: d_H points at the packed [A | B | C] (contiguous), see pcs_normal_blocks_device.
-// d_sel (LM loop with two states, ba_schur.hpp SchurArgs::sel): when *d_sel != 0 the string is read alt_prm doubles and the outputs are written
-// alt_out doubles further on.
-static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, double *d_g, double *d_cost, hipStream_t s, bool blocked = false, const int32_t *d_stop = nullptr,
-                          const int32_t *d_sel = nullptr, int64_t alt_prm = 0, int64_t alt_out = 0, bool skip_prologue = false) {
+// What a build inside an LM trial adds: the stop flag; sel (LM loop with two states, ba_schur.hpp SchurArgs::sel): when *sel != 0 the string is read
+// alt_prm doubles and the outputs are written alt_out doubles further on; skip_prologue: the launch in front has prepared the slabs and zeroed the outputs.
+struct NormalTrial { const int32_t *stop = nullptr, *sel = nullptr; int64_t alt_prm = 0, alt_out = 0; bool skip_prologue = false; };
+static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, double *d_g, double *d_cost, hipStream_t s, bool blocked = false, const NormalTrial &t = {}) {
     if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     if (h->n > INT32_MAX) return fail(PCS_ERR_ARG, "normal equations: tables beyond 2^31 rows are not supported (visiting orders are int32)");
     if (h->chain == PCS_CHAIN_TEMPLATE && !h->have_template) return fail(PCS_ERR_STATE, "template points not set");
@@ -1520,8 +979,8 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
     HIPCHK(hipSetDevice(h->device));
     int rc0 = ensure_point_orders(h);
     if (rc0) return rc0;
-    if ((d_stop || d_sel) && (reinterpret_cast<uintptr_t>(d_H) % 16 || alt_out % 2)) return fail(PCS_ERR_ARG, "normal equations behind a stop flag / state selector need 16-byte aligned buffers");
-    if (skip_prologue) {   // the caller's previous kernel has prepared the slabs and zeroed the outputs (schur_finish_kernel, csrc/ba_lm_fused.hpp)
+    if ((t.stop || t.sel) && (reinterpret_cast<uintptr_t>(d_H) % 16 || t.alt_out % 2)) return fail(PCS_ERR_ARG, "normal equations behind a stop flag / state selector need 16-byte aligned buffers");
+    if (t.skip_prologue) {   // the caller's previous kernel has prepared the slabs and zeroed the outputs (schur_finish_kernel, csrc/ba_lm_fused.hpp)
         HIPCHK(order_after_done(h, s));
         h->linearized = true;
     } else if (reinterpret_cast<uintptr_t>(d_H) % 16 == 0) {   // slab_prep and the zeroing of the outputs in one launch
@@ -1530,15 +989,15 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
         int64_t threads = slab_prep_threads(h->n_cams, h->n_imgs, has_pose);
         if (copy_points) threads = std::max<int64_t>(threads, std::min<int64_t>(3 * h->n_keys, 1 << 16));
         const int prep_blocks = (int)((threads + 63) / 64);
-        const int64_t n_h = blocked ? L.a_len() + L.b_len() + L.c_len() : h->n_params * h->n_params;
+        const int64_t n_h = blocked ? L.h_len() : h->n_params * h->n_params;
         const int zero_blocks = (int)std::min<int64_t>((n_h / 2 + 63) / 64 + 1, (int64_t)h->n_cu * 32);
         hipLaunchKernelGGL(normal_prologue_kernel, dim3((unsigned)(prep_blocks + zero_blocks)), dim3(64), 0, s, d_prm, (double *)h->d_cam_slab,
                            (double *)h->d_pose_slab, (double *)h->d_points, (int)h->n_cams, (int)h->n_imgs, (int)h->n_keys, h->extr_off,
-                           h->pose_off, h->point_off, has_pose, copy_points, prep_blocks, d_H, n_h, d_g, h->n_params, d_cost, d_stop, d_sel, alt_prm, alt_out);
+                           h->pose_off, h->point_off, has_pose, copy_points, prep_blocks, d_H, n_h, d_g, h->n_params, d_cost, t.stop, t.sel, t.alt_prm, t.alt_out);
         HIPCHK(hipGetLastError());
         h->linearized = true;
     } else {
-        HIPCHK(hipMemsetAsync(d_H, 0, sizeof(double) * (blocked ? L.a_len() + L.b_len() + L.c_len() : h->n_params * h->n_params), s));
+        HIPCHK(hipMemsetAsync(d_H, 0, sizeof(double) * (blocked ? L.h_len() : h->n_params * h->n_params), s));
         HIPCHK(hipMemsetAsync(d_g, 0, sizeof(double) * h->n_params, s));
         HIPCHK(hipMemsetAsync(d_cost, 0, sizeof(double), s));
         int rc = launch_slab_prep(h, d_prm, s);
@@ -1560,8 +1019,8 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
     a.n_params = h->n_params;
     a.debug = h->normal_debug;
     a.loss = h->loss; a.inv_f_scale = 1.0 / h->f_scale; a.f_scale_sq = h->f_scale * h->f_scale;
-    a.stop = d_stop;
-    a.sel = d_sel; a.alt = alt_out;
+    a.stop = t.stop;
+    a.sel = t.sel; a.alt = t.alt_out;
     // every wave walks a contiguous range of tiles, so its register accumulators survive across tiles.  One-wave
     // workgroups; the LDS image (22.9 KB for 22 columns x 64 rows) allows 7 per CU, and exactly one resident round of
     // waves is fastest (92 us against 105 us with two rounds on rig-32, profiles/r02/sweeps.md).
@@ -2071,10 +1530,7 @@ int pcs_normal_equations_device(pcs_engine *h, const double *param_str, double *
 
 int pcs_normal_layout(const pcs_engine *h, int64_t *out5) {
     if (!h || !out5) return fail(PCS_ERR_ARG, "pcs_normal_layout: bad arguments");
-    const BlockLayout L = block_layout(h);
-    out5[0] = L.n_lead; out5[1] = L.n_trail; out5[2] = L.tb;
-    out5[3] = L.a_len() + L.b_len() + L.c_len() + h->n_params + 1;
-    out5[4] = h->n_params;
+    layout_out5(block_layout(h), h->n_params, out5);
     return PCS_OK;
 }
 
@@ -2082,514 +1538,54 @@ int pcs_normal_blocks_device(pcs_engine *h, const double *d_param_str, double *d
     if (!h || !d_param_str || !d_packed) return fail(PCS_ERR_ARG, "pcs_normal_blocks_device: bad arguments");
     if (reinterpret_cast<uintptr_t>(d_packed) % 16) return fail(PCS_ERR_ARG, "pcs_normal_blocks_device: the packed buffer must be 16-byte aligned");
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    const BlockLayout L = block_layout(h);
-    double *d_g = d_packed + L.a_len() + L.b_len() + L.c_len();
+    double *d_g = d_packed + block_layout(h).h_len();
     return enqueue_normal(h, d_param_str, d_packed, d_g, d_g + h->n_params, s, true);
 }
 
-static int enqueue_schur_prepare(const BlockLayout &L, double *d_packed, const uint8_t *d_fixed, const double *d_lambda, double *d_linvt, double *d_u,
-                                 double *d_V, double *d_S, double *d_rhs, double *d_dvec, double *d_gm, int32_t *d_status, hipStream_t s, const int32_t *d_stop,
-                                 double *d_fill = nullptr, int64_t fill_n = 0, const int32_t *d_sel = nullptr, int64_t alt = 0) {
-    SchurArgs a{};
-    a.sel = d_sel; a.alt = alt;
-    a.fill = reinterpret_cast<uint64_t *>(d_fill); a.fill_n = d_fill ? fill_n : 0;
-    a.A = d_packed; a.B = d_packed + L.a_len(); a.C = a.B + L.b_len(); a.g = a.C + L.c_len();
-    a.fixed = d_fixed; a.lambda = d_lambda;
-    a.linvt = d_linvt; a.u = d_u; a.V = d_V; a.S = d_S; a.rhs = d_rhs; a.dvec = d_dvec; a.gm = d_gm; a.status = d_status;
-    a.n_lead = L.n_lead; a.n_trail = L.n_trail; a.n_ent = L.n_ent; a.trail_off = L.trail_off;
-    a.stop = d_stop;
-    auto blocks = [](int64_t n) { return dim3((unsigned)((n + 255) / 256)); };
-    // trailing blocks and the leading block are independent: one launch (schur_trail_lead_kernel); V needs the trailing factors
-    const int64_t nbt = (L.n_lead + 31) / 32, trail_blocks = (L.n_ent + 255) / 256;
-    a.trail_blocks = (int32_t)trail_blocks;
-    if (trail_blocks + nbt * nbt > 0) {
-        const dim3 grid((unsigned)(trail_blocks + nbt * nbt));
-        if (L.tb == 6) hipLaunchKernelGGL(schur_trail_lead_kernel<6>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(schur_trail_lead_kernel<3>, grid, dim3(256), 0, s, a);
-        HIPCHK(hipGetLastError());
-    }
-    if (L.n_ent > 0 && L.n_lead > 0) {
-        if (L.tb == 6) hipLaunchKernelGGL(schur_v_kernel<6>, blocks(L.n_lead * L.n_ent), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(schur_v_kernel<3>, blocks(L.n_lead * L.n_ent), dim3(256), 0, s, a);
-        HIPCHK(hipGetLastError());
-    }
-    return PCS_OK;
-}
-static int enqueue_schur_prepare(pcs_engine *h, double *d_packed, const uint8_t *d_fixed, const double *d_lambda, double *d_linvt, double *d_u,
-                                 double *d_V, double *d_S, double *d_rhs, double *d_dvec, double *d_gm, int32_t *d_status, hipStream_t s, const int32_t *d_stop,
-                                 double *d_fill = nullptr, int64_t fill_n = 0, const int32_t *d_sel = nullptr, int64_t alt = 0) {
-    return enqueue_schur_prepare(block_layout(h), d_packed, d_fixed, d_lambda, d_linvt, d_u, d_V, d_S, d_rhs, d_dvec, d_gm, d_status, s, d_stop, d_fill, fill_n, d_sel, alt);
-}
-
+// The pieces of a trial for a loop the host steers (pcs_solver.inc: schur_prepare_piece, schur_finish_piece, lm_decide_piece).
 int pcs_schur_prepare(pcs_engine *h, double *d_packed, const uint8_t *d_fixed, const double *d_lambda, double *d_linvt, double *d_u,
                       double *d_V, double *d_S, double *d_rhs, double *d_dvec, double *d_gm, int32_t *d_status, void *stream) {
-    if (!h || !d_packed || !d_fixed || !d_lambda || !d_linvt || !d_u || !d_V || !d_S || !d_rhs || !d_dvec || !d_gm || !d_status)
-        return fail(PCS_ERR_ARG, "pcs_schur_prepare: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    return enqueue_schur_prepare(h, d_packed, d_fixed, d_lambda, d_linvt, d_u, d_V, d_S, d_rhs, d_dvec, d_gm, d_status, stream ? (hipStream_t)stream : h->stream, nullptr);
-}
-
-int pcs_lm_decide(pcs_engine *h, const double *d_cost_old, const double *d_cost_new, const double *d_dvec, const double *d_gm, const double *d_delta,
-                  const double *d_ps, const uint8_t *d_fixed, int32_t *d_status, double *d_lambda, double *d_stats, void *stream) {
-    if (!h || !d_cost_old || !d_cost_new || !d_dvec || !d_gm || !d_delta || !d_ps || !d_fixed || !d_status || !d_lambda || !d_stats)
-        return fail(PCS_ERR_ARG, "pcs_lm_decide: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    LmDecideArgs a{};
-    a.tail[0] = d_cost_old; a.tail[1] = d_cost_new; a.ps2[0] = a.ps2[1] = d_ps;
-    a.dvec = d_dvec; a.gm = d_gm; a.delta = d_delta; a.fixed = d_fixed; a.status = d_status; a.lambda = d_lambda; a.stats = d_stats; a.n_params = h->n_params;
-    hipLaunchKernelGGL(lm_decide_kernel, dim3(1), dim3(1024), 0, s, a);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-
-static int enqueue_schur_finish(const BlockLayout &L, const double *d_linvt, const double *d_u, const double *d_w, const double *d_xlead, const uint8_t *d_fixed,
-                                double *d_delta, const double *d_ps_in, double *d_ps_out, hipStream_t s, const int32_t *d_stop, const int32_t *d_sel = nullptr,
-                                double *d_vote = nullptr, int64_t vote_alt = 0, const int32_t *d_status = nullptr, double *d_zero = nullptr, int64_t zero_n = 0,
-                                int n_cu = 256) {
-    SchurBackArgs a{};
-    a.zero = d_zero; a.zero_n = d_zero ? zero_n : 0;
-    a.sel = d_sel; a.vote = d_vote; a.vote_alt = vote_alt; a.status = d_status;
-    a.linvt = d_linvt; a.u = d_u; a.w = d_w; a.xl = d_xlead; a.fixed = d_fixed; a.delta = d_delta;
-    a.ps_in = d_ps_in; a.ps_out = d_ps_out;
-    a.n_lead = L.n_lead; a.n_ent = L.n_ent; a.trail_off = L.trail_off;
-    a.stop = d_stop;
-    const int64_t n = std::max(L.n_lead, L.n_ent);
-    // with a buffer to zero on the way: enough workgroups for that as well (8 doubles per thread and pass, at most four workgroups per CU)
-    const int64_t zero_blocks = a.zero ? std::min<int64_t>((a.zero_n / 8 + 255) / 256, (int64_t)n_cu * 4) : 0;
-    const dim3 grid((unsigned)std::max<int64_t>((n + 255) / 256, zero_blocks));
-    if (L.tb == 6) hipLaunchKernelGGL(schur_back_kernel<6>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(schur_back_kernel<3>, grid, dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-static int enqueue_schur_finish(pcs_engine *h, const double *d_linvt, const double *d_u, const double *d_w, const double *d_xlead, const uint8_t *d_fixed,
-                                double *d_delta, const double *d_ps_in, double *d_ps_out, hipStream_t s, const int32_t *d_stop, const int32_t *d_sel = nullptr,
-                                double *d_vote = nullptr, int64_t vote_alt = 0, const int32_t *d_status = nullptr) {
-    return enqueue_schur_finish(block_layout(h), d_linvt, d_u, d_w, d_xlead, d_fixed, d_delta, d_ps_in, d_ps_out, s, d_stop, d_sel, d_vote, vote_alt, d_status);
+    if (!h) return fail(PCS_ERR_ARG, "pcs_schur_prepare: bad arguments");
+    return schur_prepare_piece("pcs_schur_prepare", h->device, block_layout(h), stream ? (hipStream_t)stream : h->stream, d_packed, d_fixed, d_lambda, d_linvt, d_u, d_V, d_S, d_rhs, d_dvec, d_gm, d_status);
 }
 
 int pcs_schur_finish(pcs_engine *h, const double *d_linvt, const double *d_u, const double *d_w, const double *d_xlead, const uint8_t *d_fixed,
                      double *d_delta, const double *d_ps_in, double *d_ps_out, void *stream) {
-    if (!h || !d_linvt || !d_u || !d_w || !d_xlead || !d_fixed || !d_delta || ((d_ps_in == nullptr) != (d_ps_out == nullptr)))
-        return fail(PCS_ERR_ARG, "pcs_schur_finish: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    return enqueue_schur_finish(h, d_linvt, d_u, d_w, d_xlead, d_fixed, d_delta, d_ps_in, d_ps_out, stream ? (hipStream_t)stream : h->stream, nullptr);
+    if (!h) return fail(PCS_ERR_ARG, "pcs_schur_finish: bad arguments");
+    return schur_finish_piece("pcs_schur_finish", h->device, block_layout(h), stream ? (hipStream_t)stream : h->stream, d_linvt, d_u, d_w, d_xlead, d_fixed, d_delta, d_ps_in, d_ps_out);
 }
 
-int64_t pcs_dense_spd_work_len(int64_t n) {   // launch-per-column form: inverses + diagonal tiles + y; one-launch form: flags + x + y
-    if (n <= 0) return -1;
-    const int64_t nb = (n + 31) / 32;
-    return std::max<int64_t>(2 * nb * 32 * 32 + nb * 32, cp_work_doubles(nb));
+int pcs_lm_decide(pcs_engine *h, const double *d_cost_old, const double *d_cost_new, const double *d_dvec, const double *d_gm, const double *d_delta,
+                  const double *d_ps, const uint8_t *d_fixed, int32_t *d_status, double *d_lambda, double *d_stats, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_lm_decide: bad arguments");
+    return lm_decide_piece("pcs_lm_decide", h->device, h->n_params, stream ? (hipStream_t)stream : h->stream, d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed, d_status, d_lambda, d_stats);
 }
 
-static int device_cu_count(int device);
-// launch geometry of S -= V V' (csrc/ba_schur.hpp): tile width, tiles of the lower triangle, K split.  `ordered` = the partial sums of a
-// split go through a workspace and are subtracted in order (deterministic mode) instead of meeting in atomics.
-struct SyrkGeometry { bool big; int64_t tw, tiles, ksplit, kchunk; };
-static SyrkGeometry syrk_geometry(int64_t n_lead, int64_t n_trail, bool ordered) {
-    // 64 x 64 tiles once 32 x 32 ones alone would fill the chip twice over (their operand traffic, not the matrix cores, is the bound then:
-    // rig-32-self 175 us -> ~100 us); PCS_SYRK_TILE=32 / 64 forces one form (A/B)
-    static const int forced = getenv("PCS_SYRK_TILE") ? atoi(getenv("PCS_SYRK_TILE")) : 0;
-    const int64_t nb32 = (n_lead + 31) / 32;
-    SyrkGeometry g{};
-    g.big = forced == 64 || (forced != 32 && nb32 * (nb32 + 1) / 2 >= 1024);
-    g.tw = g.big ? 64 : 32;
-    const int64_t nb = (n_lead + g.tw - 1) / g.tw;
-    g.tiles = nb * (nb + 1) / 2;
-    // split K until ~512 workgroups exist (rig-32: 120 tiles x 5; the 2e4-point free chain: 21 tiles x 25 of 60 000 columns)
-    int64_t ksplit = std::min<int64_t>((512 + g.tiles - 1) / g.tiles, (n_trail + 127) / 128);
-    ksplit = std::max<int64_t>(1, ksplit);
-    int64_t kchunk = ((n_trail + ksplit - 1) / ksplit + 63) / 64 * 64;
-    ksplit = (n_trail + kchunk - 1) / kchunk;
-    if (g.big) {
-        // 64 x 64 tiles run two workgroups per CU: split K so that the workgroups fill whole rounds of the resident ones — the cost of a
-        // split = rounds x (columns per workgroup + ~64 columns' worth of ramp and atomics); rig-32-self: 378 tiles x 4 = 2.95 rounds.
-        // Ordered mode: every split also writes and re-reads a 32 KB partial tile (rig-32-self: 50 MB per solve for four splits) —
-        // priced as 48 more columns per split.  (Priced at 192 the model left rig-32-self unsplit: 378 workgroups of 1 458 columns on
-        // 512 slots took 172.7 us against 133.4 us for the four-way split with atomics, profiles/r05/lm_trace_rig32_self_form11.log.)
-        int dev = 0;
-        const int cus = hipGetDevice(&dev) == hipSuccess && device_cu_count(dev) > 0 ? device_cu_count(dev) : 256;
-        const int64_t slots = 2 * (int64_t)cus;
-        int64_t best = INT64_MAX;
-        for (int64_t ks = 1; ks <= std::max<int64_t>(1, n_trail / 128); ++ks) {
-            const int64_t kc = ((n_trail + ks - 1) / ks + 63) / 64 * 64, real = (n_trail + kc - 1) / kc;
-            const int64_t cost = (g.tiles * real + slots - 1) / slots * (kc + 64 + ((ordered && real > 1) ? 48 : 0));
-            if (cost < best) { best = cost; ksplit = real; kchunk = kc; }
-        }
-    }
-    g.ksplit = ksplit; g.kchunk = kchunk;
-    return g;
-}
-// doubles of the ordered mode's workspace (0: the product is not split, nothing is needed)
-static int64_t syrk_work_doubles(int64_t n_lead, int64_t n_trail) {
-    const SyrkGeometry g = syrk_geometry(n_lead, n_trail, true);
-    return g.ksplit > 1 ? g.ksplit * (g.tiles * g.tw * g.tw + n_lead) : 0;
-}
-
-static int enqueue_schur_syrk(int64_t n_lead, int64_t n_trail, const double *d_V, int64_t ldv, double *d_S, int64_t lds, const double *d_u, double *d_rhs,
-                              hipStream_t s, const int32_t *d_stop, double *d_ws = nullptr, int64_t ws_doubles = 0) {
-    const bool ordered = d_ws != nullptr;
-    const SyrkGeometry g = syrk_geometry(n_lead, n_trail, ordered);
-    if (ordered && g.ksplit > 1 && ws_doubles < g.ksplit * (g.tiles * g.tw * g.tw + n_lead))
-        return fail(PCS_ERR_ARG, "pcs_schur_syrk: the ordered mode needs a workspace of %lld doubles (pcs_schur_syrk_work_len), got %lld",
-                    (long long)(g.ksplit * (g.tiles * g.tw * g.tw + n_lead)), (long long)ws_doubles);
-    SchurSyrkArgs a{d_V, d_S, d_u, d_rhs, (int32_t)n_lead, (int32_t)n_trail, (int32_t)ldv, (int32_t)lds, (int32_t)g.ksplit, (int32_t)g.kchunk, d_stop};
-    a.ws = (ordered && g.ksplit > 1) ? d_ws : nullptr;
-    a.ws_rhs = a.ws ? d_ws + g.ksplit * g.tiles * g.tw * g.tw : nullptr;
-    a.tiles = (int32_t)g.tiles;
-    if (g.big) hipLaunchKernelGGL(schur_syrk64_kernel, dim3((unsigned)(g.tiles * g.ksplit)), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(schur_syrk_kernel, dim3((unsigned)(g.tiles * g.ksplit)), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-    if (a.ws) {
-        if (g.big) hipLaunchKernelGGL(schur_syrk_reduce_kernel<64>, dim3((unsigned)(g.tiles * 16)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(schur_syrk_reduce_kernel<32>, dim3((unsigned)(g.tiles * 4)), dim3(256), 0, s, a);
-        HIPCHK(hipGetLastError());
-    }
-    return PCS_OK;
-}
-
-int64_t pcs_schur_syrk_work_len(int64_t n_lead, int64_t n_trail) {
-    if (n_lead <= 0 || n_trail < 0) return -1;
-    return syrk_work_doubles(n_lead, n_trail);
-}
-
-int pcs_schur_syrk_ordered(int device, int64_t n_lead, int64_t n_trail, const double *d_V, int64_t ldv, double *d_S, int64_t lds, const double *d_u,
-                           double *d_rhs, double *d_work, int64_t work_doubles, void *stream) {
-    if (n_lead <= 0 || n_lead > (1 << 15) || n_trail < 0 || n_trail > (1ll << 30) || ldv < n_trail || lds < n_lead || !d_S || (n_trail && !d_V) || (d_u && !d_rhs) || !d_work)
-        return fail(PCS_ERR_ARG, "pcs_schur_syrk_ordered: bad arguments");
-    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_schur_syrk_ordered: device %d not available", device);
-    if (n_trail == 0) return PCS_OK;
-    HIPCHK(hipSetDevice(device));
-    return enqueue_schur_syrk(n_lead, n_trail, d_V, ldv, d_S, lds, d_u, d_rhs, (hipStream_t)stream, nullptr, d_work, work_doubles);
-}
-
-int pcs_schur_syrk(int device, int64_t n_lead, int64_t n_trail, const double *d_V, int64_t ldv, double *d_S, int64_t lds, const double *d_u,
-                   double *d_rhs, void *stream) {
-    if (n_lead <= 0 || n_lead > (1 << 15) || n_trail < 0 || n_trail > (1ll << 30) || ldv < n_trail || lds < n_lead || !d_S || (n_trail && !d_V) || (d_u && !d_rhs))
-        return fail(PCS_ERR_ARG, "pcs_schur_syrk: bad arguments");
-    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_schur_syrk: device %d not available", device);
-    if (n_trail == 0) return PCS_OK;
-    HIPCHK(hipSetDevice(device));
-    return enqueue_schur_syrk(n_lead, n_trail, d_V, ldv, d_S, lds, d_u, d_rhs, (hipStream_t)stream, nullptr);
-}
-
-int pcs_schur_vtx(int device, int64_t n_lead, int64_t n_trail, const double *d_V, int64_t ldv, const double *d_x, double *d_w, void *stream) {
-    if (n_lead <= 0 || n_trail < 0 || n_trail > (1ll << 30) || ldv < n_trail || (n_trail && (!d_V || !d_x || !d_w))) return fail(PCS_ERR_ARG, "pcs_schur_vtx: bad arguments");
-    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_schur_vtx: device %d not available", device);
-    if (n_trail == 0) return PCS_OK;
-    HIPCHK(hipSetDevice(device));
-    launch_schur_vtx(d_V, d_x, d_w, (int)n_lead, (int)n_trail, (int)ldv, nullptr, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-
-int pcs_cov_trsm(int device, int64_t n, const double *d_L, int64_t ldl, double *d_X, int64_t n_rhs, int64_t ldx, int flags, void *stream) {
-    const bool identity = (flags & PCS_COV_TRSM_IDENTITY) != 0;
-    if (n <= 0 || n > (1 << 15) || n_rhs <= 0 || n_rhs > (1ll << 30) || ldl < n || ldx < n_rhs || !d_L || !d_X || (flags & ~PCS_COV_TRSM_IDENTITY) ||
-        (identity && n_rhs != n) || n * ldx > (1ll << 40))
-        return fail(PCS_ERR_ARG, "pcs_cov_trsm: bad arguments");
-    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_cov_trsm: device %d not available", device);
-    HIPCHK(hipSetDevice(device));
-    const CovTrsmArgs a{d_L, d_X, ldl, ldx, (int32_t)n, (int32_t)n_rhs, identity ? 1 : 0};
-    hipLaunchKernelGGL(cov_trsm_kernel, dim3((unsigned)((n_rhs + COV_NB - 1) / COV_NB)), dim3(256), 0, (hipStream_t)stream, a);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-
-int pcs_cov_block_gram(int device, const double *d_X, int64_t ldx, int64_t n_rows, int64_t n_cols, const int32_t *d_col, const int32_t *d_width,
-                       const int32_t *d_row0, int64_t n_blocks, double *d_out, int64_t out_stride, const double *d_linvt, int64_t tb,
-                       const uint8_t *d_fixed, int64_t fixed_off, const double *d_scale, double scale, void *stream) {
-    if (n_rows <= 0 || n_rows > (1ll << 30) || n_cols <= 0 || n_cols > (1ll << 30) || ldx < n_cols || !d_X || !d_col || !d_width || n_blocks < 0 ||
-        n_blocks > (1ll << 31) - 1 || (n_blocks && !d_out) || out_stride < 1 || (d_linvt && (tb < 1 || tb > COV_NB)) || fixed_off < 0 || !(scale == scale))
-        return fail(PCS_ERR_ARG, "pcs_cov_block_gram: bad arguments");
-    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_cov_block_gram: device %d not available", device);
-    if (n_blocks == 0) return PCS_OK;
-    HIPCHK(hipSetDevice(device));
-    CovGramArgs a{};
-    a.X = d_X; a.ldx = ldx; a.n_rows = (int32_t)n_rows; a.n_cols = (int32_t)n_cols; a.n_blocks = (int32_t)n_blocks;
-    a.col = d_col; a.width = d_width; a.row0 = d_row0; a.out = d_out; a.out_stride = out_stride;
-    a.linvt = d_linvt; a.tb = (int32_t)tb; a.fixed = d_fixed; a.fixed_off = fixed_off; a.scale_dev = d_scale; a.scale = scale;
-    hipLaunchKernelGGL(cov_gram_kernel, dim3((unsigned)n_blocks), dim3(256), 0, (hipStream_t)stream, a);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-
-static int device_cu_count(int device) {
-    static std::atomic<int> cached[64];
-    if (device < 0 || device >= 64) return 0;
-    int v = cached[device].load();
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) v = 0;
-        cached[device].store(v);
-    }
-    return v;
-}
-
-int pcs_dense_spd_solve(int device, int64_t n, double *d_S, int64_t ld, const double *d_rhs, double *d_x, double *d_work, int32_t *d_status, void *stream) {
-    return pcs_dense_spd_solve_algo(device, n, d_S, ld, d_rhs, d_x, d_work, d_status, stream, PCS_SPD_AUTO);
-}
-
-static int enqueue_dense_spd(int device, int64_t n, double *d_S, int64_t ld, const double *d_rhs, double *d_x, double *d_work, int32_t *d_status, void *stream,
-                             int algorithm, const int32_t *d_stop, bool prefilled = false, int64_t timeout_us = 250000);
-
-// does a solve of size n with this algorithm request take the ONE persistent launch (csrc/ba_chol_persist.hpp)?  Wherever its tiles fit
-// the chip's LDS: n <= 1 984 on 256 CUs.  (Round 5 also tried ONE workgroup with the whole matrix in its LDS for n <= 160 — nothing to hand
-// over —: 110 us at n = 120 against the persistent kernel's 47: fourteen workgroups load, update and factor their tiles side by side, one
-// workgroup does it all in sequence.  Dropped.)
-static bool dense_spd_is_one_launch(int device, int64_t n, int algorithm) {
-    static const bool env_launches = getenv("PCS_CHOL_LAUNCHES") != nullptr;   // A/B switch for whole runs
-    return n > 0 && cp_fits(n, device_cu_count(device)) && (algorithm == PCS_SPD_ONE_LAUNCH || (algorithm == PCS_SPD_AUTO && !env_launches));
-}
-
-int pcs_dense_spd_solve_algo(int device, int64_t n, double *d_S, int64_t ld, const double *d_rhs, double *d_x, double *d_work, int32_t *d_status, void *stream,
-                             int algorithm) {
-    return enqueue_dense_spd(device, n, d_S, ld, d_rhs, d_x, d_work, d_status, stream, algorithm, nullptr);
-}
-
-int pcs_dense_spd_solve_opts(int device, int64_t n, double *d_S, int64_t ld, const double *d_rhs, double *d_x, double *d_work, int32_t *d_status, void *stream,
-                             int algorithm, int64_t timeout_us) {
-    if (timeout_us < 1 || timeout_us > 60000000) return fail(PCS_ERR_ARG, "pcs_dense_spd_solve_opts: timeout_us must be in [1, 60000000]");
-    return enqueue_dense_spd(device, n, d_S, ld, d_rhs, d_x, d_work, d_status, stream, algorithm, nullptr, false, timeout_us);
-}
-
-static int enqueue_dense_spd(int device, int64_t n, double *d_S, int64_t ld, const double *d_rhs, double *d_x, double *d_work, int32_t *d_status, void *stream,
-                             int algorithm, const int32_t *d_stop, bool prefilled, int64_t timeout_us) {
-    constexpr int NB = 32;
-    if (n <= 0 || n > (1 << 15) || ld < n || !d_S || !d_rhs || !d_x || !d_work || !d_status) return fail(PCS_ERR_ARG, "pcs_dense_spd_solve: bad arguments");
-    if (algorithm != PCS_SPD_AUTO && algorithm != PCS_SPD_LAUNCHES && algorithm != PCS_SPD_ONE_LAUNCH) return fail(PCS_ERR_ARG, "pcs_dense_spd_solve: unknown algorithm %d", algorithm);
-    if (device < 0 || device >= pcs_device_count()) return fail(PCS_ERR_NODEVICE, "pcs_dense_spd_solve: device %d not available", device);
-    HIPCHK(hipSetDevice(device));
-    if (algorithm == PCS_SPD_ONE_LAUNCH && !cp_fits(n, device_cu_count(device)))
-        return fail(PCS_ERR_ARG, "pcs_dense_spd_solve: n = %lld does not fit the one-launch form on %d compute units", (long long)n, device_cu_count(device));
-    if (dense_spd_is_one_launch(device, n, algorithm)) {
-        HIPCHK(cp_launch(n, d_S, ld, d_rhs, d_x, d_work, d_status, device_cu_count(device), (hipStream_t)stream, 1.0e-6 * (double)timeout_us, nullptr, d_stop, prefilled));
-        return PCS_OK;
-    }
-    hipStream_t s = (hipStream_t)stream;   // NULL = the default stream
-    const int nblk = (int)((n + NB - 1) / NB);
-    double *d_ldiag = d_work + (int64_t)nblk * NB * NB;
-    double *d_y = d_ldiag + (int64_t)nblk * NB * NB;
-    CholArgs a{d_S, d_work, d_ldiag, d_status, (int32_t)n, (int32_t)ld, 0, d_rhs, d_y, d_stop};
-    a.k = 0;
-    hipLaunchKernelGGL(chol_panel_kernel<NB>, dim3((unsigned)nblk), dim3(256), 0, s, a);
-    for (int k = 0; k + 1 < nblk; ++k) {   // trailing update with column k + panel step of column k + 1, one launch
-        a.k = k;
-        const int m = nblk - k - 1;
-        hipLaunchKernelGGL(chol_step_kernel<NB>, dim3((unsigned)(m * (m + 1) / 2)), dim3(256), 0, s, a);
-    }
-    HIPCHK(hipGetLastError());
-    // backward sweep L' x = y: pieces of at most 16 blocks in one workgroup each, lower-right first; between two pieces a GEMV over
-    // many workgroups takes the solved rows out of the rest of y (csrc/ba_dense_chol.hpp)
-    struct Rec {
-        static void run(hipStream_t s, const CholSolveArgs &base, int kb0, int kb1) {
-            constexpr int NBk = 32;
-            if (kb1 - kb0 <= 16) {
-                CholSolveArgs b = base;
-                b.kb0 = kb0; b.kb1 = kb1;
-                const size_t lds = sizeof(double) * ((size_t)(kb1 - kb0) * NBk + NBk);
-                hipLaunchKernelGGL(chol_solve_kernel<NBk>, dim3(1), dim3(512), lds, s, b);
-                return;
-            }
-            const int mid = kb0 + (kb1 - kb0 + 1) / 2;
-            run(s, base, mid, kb1);
-            const int r0 = mid * NBk, r1 = std::min<int>(kb1 * NBk, base.n), c0 = kb0 * NBk, c1 = mid * NBk;
-            hipLaunchKernelGGL(chol_gemv_t_kernel, dim3((unsigned)((c1 - c0 + 63) / 64)), dim3(1024), 0, s, (const double *)base.L, (int)base.ld, (const double *)base.x, base.y,
-                               r0, r1, c0, c1, base.stop);
-            run(s, base, kb0, mid);
-        }
-    };
-    CholSolveArgs b{d_S, d_work, d_ldiag, d_y, d_x, (int32_t)n, (int32_t)ld, 0, nblk, d_stop};
-    Rec::run(s, b, 0, nblk);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-
-// The fused forms of the trial's small kernels (csrc/ba_lm_fused.hpp).
-static int enqueue_schur_prep_fused(const BlockLayout &L, const pcs_lm_buffers *b, hipStream_t s, const int32_t *d_stop, const int32_t *d_sel, int64_t alt,
-                                    double *d_fill, int64_t fill_n) {
-    SchurArgs a{};
-    a.sel = d_sel; a.alt = alt;
-    a.fill = reinterpret_cast<uint64_t *>(d_fill); a.fill_n = d_fill ? fill_n : 0;
-    a.A = b->packed[0]; a.B = a.A + L.a_len(); a.C = a.B + L.b_len(); a.g = a.C + L.c_len();
-    a.fixed = b->fixed; a.lambda = b->lambda;
-    a.linvt = b->linvt; a.u = b->u; a.V = b->V; a.S = b->S; a.rhs = b->rhs; a.dvec = b->dvec; a.gm = b->gm; a.status = b->status;
-    a.n_lead = L.n_lead; a.n_trail = L.n_trail; a.n_ent = L.n_ent; a.trail_off = L.trail_off;
-    a.stop = d_stop;
-    const int epb = prep_epb(L.tb);
-    const int64_t ent_chunks = (L.n_ent + epb - 1) / epb, row_chunks = std::max<int64_t>(1, (L.n_lead + PREP_RPB - 1) / PREP_RPB);
-    const int64_t nbt = (L.n_lead + 31) / 32;
-    a.ent_chunks = (int32_t)ent_chunks;
-    a.trail_blocks = (int32_t)(ent_chunks * row_chunks);
-    const int64_t grid = ent_chunks * row_chunks + nbt * nbt;
-    if (grid <= 0) return PCS_OK;
-    if (grid > INT32_MAX) return fail(PCS_ERR_ARG, "pcs_lm_trial_build: the system is too large for one launch of the Schur preparation");
-    if (L.tb == 6) hipLaunchKernelGGL(schur_prep_kernel<6>, dim3((unsigned)grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(schur_prep_kernel<3>, dim3((unsigned)grid), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-
-// what schur_finish_kernel prepares for the build that follows it, beyond the step itself: the hand-fused engines' slabs and point copy
-// (a generated chain has its own preparation: all of it empty)
-struct FinishSlabs {
-    double *cam_slab = nullptr, *pose_slab = nullptr, *points = nullptr;
-    int64_t n_cams = 0, n_imgs = 0, n_keys = 0, extr_off = 0, pose_off = 0, point_off = 0;
-    bool has_pose = false, copy_points = false;
-};
-static int enqueue_schur_finish_fused(const BlockLayout &L, int64_t n_params, int n_cu, const FinishSlabs &fs, const pcs_lm_buffers *b, hipStream_t s, const int32_t *d_stop,
-                                      const int32_t *d_sel, int64_t alt_pk, int64_t n_packed) {
-    SchurFinishArgs a{};
-    a.V = b->V; a.xl = b->xlead; a.n_lead = (int32_t)L.n_lead; a.n_trail = (int32_t)L.n_trail; a.ldv = (int32_t)std::max<int64_t>(1, L.n_trail);
-    a.linvt = b->linvt; a.u = b->u; a.fixed = b->fixed; a.delta = b->delta; a.ps_in = b->ps[0]; a.ps_out = b->ps[1];
-    a.n_ent = L.n_ent; a.trail_off = L.trail_off;
-    a.stop = d_stop; a.sel = d_sel;
-    a.vote = (b->mode & PCS_LM_VOTES) ? b->packed[1] + n_packed : nullptr; a.vote_alt = -alt_pk; a.status = b->status;
-    a.cam_slab = fs.cam_slab; a.pose_slab = fs.pose_slab; a.points = fs.points;
-    a.n_cams = (int32_t)fs.n_cams; a.n_imgs = (int32_t)fs.n_imgs; a.n_keys = (int32_t)fs.n_keys;
-    a.has_pose = fs.has_pose; a.copy_points = fs.copy_points;
-    a.extr_off = fs.extr_off; a.pose_off = fs.pose_off; a.point_off = fs.point_off;
-    a.Hm = b->packed[1]; a.n_h = L.a_len() + L.b_len() + L.c_len(); a.g = a.Hm + a.n_h; a.n_g = n_params; a.cost = a.g + n_params; a.alt_out = -alt_pk;
-    const int ecb = finish_ecb(L.tb);
-    const int64_t w_blocks = (L.n_ent + ecb - 1) / ecb;
-    const bool lead_poses = a.has_pose && fs.pose_off < L.trail_off;
-    const int64_t lead_threads = std::max<int64_t>(L.n_lead, fs.n_cams * CAM_STRIDE + (lead_poses ? fs.n_imgs * POSE_STRIDE : 0));
-    const int64_t lead_blocks = std::max<int64_t>(1, (lead_threads + 1023) / 1024);
-    const int64_t zero_blocks = std::min<int64_t>((a.n_h / 2 + 1023) / 1024 + 1, (int64_t)n_cu * 4);
-    a.w_blocks = (int32_t)w_blocks; a.lead_blocks = (int32_t)lead_blocks;
-    const int64_t grid = w_blocks + lead_blocks + zero_blocks;
-    if (grid > INT32_MAX) return fail(PCS_ERR_ARG, "pcs_lm_trial_build: the system is too large for one launch of the step's completion");
-    if (L.tb == 6) hipLaunchKernelGGL(schur_finish_kernel<6>, dim3((unsigned)grid), dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL(schur_finish_kernel<3>, dim3((unsigned)grid), dim3(1024), 0, s, a);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
-}
-static int enqueue_schur_finish_fused(pcs_engine *h, const pcs_lm_buffers *b, hipStream_t s, const int32_t *d_stop, const int32_t *d_sel, int64_t alt_pk,
-                                      int64_t n_packed) {
-    FinishSlabs fs;
-    fs.cam_slab = (double *)h->d_cam_slab; fs.pose_slab = (double *)h->d_pose_slab; fs.points = (double *)h->d_points;
-    fs.n_cams = h->n_cams; fs.n_imgs = h->n_imgs; fs.n_keys = h->n_keys;
-    fs.has_pose = h->chain != PCS_CHAIN_FREE; fs.copy_points = h->chain != PCS_CHAIN_TEMPLATE;
-    fs.extr_off = h->extr_off; fs.pose_off = h->pose_off; fs.point_off = h->point_off;
-    return enqueue_schur_finish_fused(block_layout(h), h->n_params, h->n_cu, fs, b, s, d_stop, d_sel, alt_pk, n_packed);
-}
-
-// One whole Levenberg-Marquardt trial in two halves (round 5; pcs_lm_trial = both): BUILD = the damped Schur step from the current state at
-// *lambda (+ the trial parameter string) and the normal equations at the trial string into the other state's packed buffer; FINISH = the
-// decision INCLUDING the loop's termination rules, the state flip of an accepted trial and the read-back of the twelve numbers the host
-// follows the loop with.  A sharded loop puts its all-reduce of the trial state between the two, on the same stream.  Every kernel starts
-// with PCS_STOP_GUARD on flags[0], so the host may queue trial t + 1 before it has read the verdict of trial t.
-static int lm_check(const void *h, const pcs_lm_buffers *b, const char *who) {
-    if (!h || !b || !b->packed[0] || !b->packed[1] || !b->ps[0] || !b->ps[1] || !b->flags || !b->fixed || !b->lambda || !b->linvt || !b->u || !b->V || !b->S || !b->rhs ||
-        !b->dvec || !b->gm || !b->status || !b->xlead || !b->w || !b->spd_work || !b->delta || !b->ctrl || !b->stats)
-        return fail(PCS_ERR_ARG, "%s: bad arguments", who);
-    if (reinterpret_cast<uintptr_t>(b->packed[0]) % 16 || reinterpret_cast<uintptr_t>(b->packed[1]) % 16) return fail(PCS_ERR_ARG, "%s: the packed buffers must be 16-byte aligned", who);
-    if (b->mode & ~(PCS_LM_FIXED_TRIAL_BUFFER | PCS_LM_VOTES)) return fail(PCS_ERR_ARG, "%s: unknown mode bits", who);
-    return PCS_OK;
-}
-
+// One Levenberg-Marquardt trial in two halves (pcs_solver.inc: enqueue_lm_trial_build, enqueue_lm_finish).
 int pcs_lm_trial_build(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
-    int rc = lm_check(h, b, "pcs_lm_trial_build");
+    const int rc = lm_check(h, b, "pcs_lm_trial_build");
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    const BlockLayout L = block_layout(h);
-    const int32_t *stop = b->flags, *sel = b->flags + 2;
-    const int64_t alt_pk = b->packed[1] - b->packed[0], alt_ps = b->ps[1] - b->ps[0];   // doubles from state 0 to state 1
-    // the one-launch Cholesky wants its hand-over workspace at the fill value: schur_trail_lead_kernel sets it on the way (one launch fewer)
-    const bool prefill = L.n_lead > 0 && dense_spd_is_one_launch(h->device, L.n_lead, b->spd_algorithm);
-    // fused: the two launches in front of the matrix products as one, the three behind the dense solve as one (csrc/ba_lm_fused.hpp); they
-    // need every trailing entity to have leading rows to ride on and the normal equations' prologue to be theirs to replace
-    const bool fused = h->fused_trial && L.n_lead > 0 && L.n_ent > 0 && h->n > 0;
-    if (fused) rc = enqueue_schur_prep_fused(L, b, s, stop, sel, alt_pk, prefill ? b->spd_work : nullptr, prefill ? cp_work_doubles((L.n_lead + 31) / 32) : 0);
-    else rc = enqueue_schur_prepare(h, b->packed[0], b->fixed, b->lambda, b->linvt, b->u, b->V, b->S, b->rhs, b->dvec, b->gm, b->status, s, stop,
-                                    prefill ? b->spd_work : nullptr, prefill ? cp_work_doubles((L.n_lead + 31) / 32) : 0, sel, alt_pk);
-    if (rc) return rc;
-    const int64_t ldv = std::max<int64_t>(1, L.n_trail);
-    if (L.n_trail > 0 && L.n_lead > 0) {
-        if (h->deterministic && !b->syrk_work && syrk_work_doubles(L.n_lead, L.n_trail) > 0)
-            return fail(PCS_ERR_ARG, "pcs_lm_trial_build: deterministic mode needs pcs_lm_buffers.syrk_work (pcs_schur_syrk_work_len doubles)");
-        rc = enqueue_schur_syrk(L.n_lead, L.n_trail, b->V, ldv, b->S, L.n_lead, b->u, b->rhs, s, stop, h->deterministic ? b->syrk_work : nullptr, b->syrk_work_len);
-        if (rc) return rc;
-    }
-    const int64_t n_packed = L.a_len() + L.b_len() + L.c_len() + h->n_params + 1;
-    const double *w = b->u;
-    if (L.n_lead > 0) {
-        rc = enqueue_dense_spd(h->device, L.n_lead, b->S, L.n_lead, b->rhs, b->xlead, b->spd_work, b->status, s, b->spd_algorithm, stop, prefill, h->spd_timeout_us);
-        if (rc) return rc;
-        if (L.n_trail > 0 && !fused) {
-            launch_schur_vtx(b->V, b->xlead, b->w, (int)L.n_lead, (int)L.n_trail, (int)ldv, stop, s);
-            HIPCHK(hipGetLastError());
-            w = b->w;
-        }
-    }
-    double *g_new = b->packed[1] + L.a_len() + L.b_len() + L.c_len();
-    if (fused) {
-        // w = V' x_l, the back substitution, the step, the trial string, this rank's vote, the slabs at the trial string and the zeroed trial state
-        rc = enqueue_schur_finish_fused(h, b, s, stop, sel, alt_pk, n_packed);
-        if (rc) return rc;
-        return enqueue_normal(h, b->ps[1], b->packed[1], g_new, g_new + h->n_params, s, true, stop, sel, -alt_ps, -alt_pk, true);
-    }
-    // the step, the trial string (ps[1] while state 0 is current) and this rank's vote behind the TRIAL state's packed buffer
-    rc = enqueue_schur_finish(h, b->linvt, b->u, w, b->xlead, b->fixed, b->delta, b->ps[0], b->ps[1], s, stop, sel,
-                              (b->mode & PCS_LM_VOTES) ? b->packed[1] + n_packed : nullptr, -alt_pk, b->status);
-    if (rc) return rc;
-    if (h->n == 0) {
-        // a rank whose observation shard is empty (ceil(N / world) rows per rank can leave the last ranks without any) contributes zeros
-        // to the all-reduce of the trial state; the vote word behind it stays
-        if (!(b->mode & PCS_LM_FIXED_TRIAL_BUFFER)) return fail(PCS_ERR_STATE, "no detections set");
-        HIPCHK(hipMemsetAsync(b->packed[1], 0, sizeof(double) * (size_t)n_packed, s));
-        return PCS_OK;
-    }
-    return enqueue_normal(h, b->ps[1], b->packed[1], g_new, g_new + h->n_params, s, true, stop, sel, -alt_ps, -alt_pk);
-}
-
-// The second half of a trial for a state of n_packed doubles ([blocks | g | cost]; pcs_engine and pcs_genchain alike).
-static int enqueue_lm_finish(int n_cu, int64_t n_params, int64_t n_packed, const pcs_lm_buffers *b, hipStream_t s) {
-    const bool fixed_buffer = (b->mode & PCS_LM_FIXED_TRIAL_BUFFER) != 0;
-    LmDecideArgs a{};
-    a.tail[0] = b->packed[0] + n_packed - 1; a.tail[1] = b->packed[1] + n_packed - 1;
-    a.ps2[0] = b->ps[0]; a.ps2[1] = b->ps[1];
-    a.sel = b->flags + 2;
-    a.dvec = b->dvec; a.gm = b->gm; a.delta = b->delta; a.fixed = b->fixed; a.status = b->status; a.lambda = b->lambda; a.stats = b->stats;
-    a.n_params = n_params;
-    a.ctrl = b->ctrl; a.stop_flag = b->flags; a.accept_flag = b->flags + 1;
-    a.use_votes = (b->mode & PCS_LM_VOTES) ? 1 : 0;
-    a.keep_sel = fixed_buffer ? 1 : 0;
-    if (b->result_host && b->free_idx && b->n_free > 0) {   // the final state straight into the host's mapped buffer when this trial ends the loop
-        double *result_mapped = nullptr;
-        if (hipHostGetDevicePointer(reinterpret_cast<void **>(&result_mapped), b->result_host, 0) == hipSuccess && result_mapped) {
-            a.free_idx = b->free_idx; a.n_free = b->n_free; a.result = result_mapped;
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    // the read-back: lm_decide_kernel writes the twelve numbers straight into the page-locked buffer when the device can address it (no
-    // copy launch); a buffer that is not mapped gets an asynchronous copy
-    double *stats_mapped = nullptr;
-    if (b->stats_host && hipHostGetDevicePointer(reinterpret_cast<void **>(&stats_mapped), b->stats_host, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        stats_mapped = nullptr;
-    }
-    a.stats_host = stats_mapped;
-    hipLaunchKernelGGL(lm_decide_kernel, dim3(1), dim3(1024), 0, s, a);
-    HIPCHK(hipGetLastError());
-    if (b->stats_host && !stats_mapped) HIPCHK(hipMemcpyAsync(b->stats_host, b->stats, sizeof(double) * LM_STATS, hipMemcpyDeviceToHost, s));
-    if (fixed_buffer) {   // the trial state sits in a fixed buffer (the one a sharded loop's all-reduce was queued on) — an accepted one is copied over the current state
-        const int copy_blocks = (int)std::min<int64_t>((n_packed / 2 + 255) / 256 + 1, (int64_t)n_cu * 8);
-        hipLaunchKernelGGL(lm_accept_kernel, dim3((unsigned)copy_blocks), dim3(256), 0, s, (const int32_t *)(b->flags + 1), (const double *)b->packed[1], b->packed[0], n_packed,
-                           (const double *)b->ps[1], b->ps[0], n_params);
-        HIPCHK(hipGetLastError());
-    }
-    return PCS_OK;
+    LmTrialDesc d;
+    d.who = "pcs_lm_trial_build"; d.device = h->device; d.n_cu = h->n_cu; d.n_params = h->n_params; d.L = block_layout(h);
+    d.deterministic = h->deterministic != 0; d.spd_timeout_us = h->spd_timeout_us;
+    d.fused = h->fused_trial && d.L.n_lead > 0 && d.L.n_ent > 0 && h->n > 0;
+    d.selector = true;
+    d.empty_zero_state = h->n == 0;
+    d.slabs = FinishSlabs{(double *)h->d_cam_slab, (double *)h->d_pose_slab, (double *)h->d_points, h->n_cams, h->n_imgs, h->n_keys, h->extr_off, h->pose_off, h->point_off,
+                          h->chain != PCS_CHAIN_FREE, h->chain != PCS_CHAIN_TEMPLATE};
+    return enqueue_lm_trial_build(d, b, stream ? (hipStream_t)stream : h->stream, [&](hipStream_t s, bool fused) {
+        const int64_t alt_pk = b->packed[1] - b->packed[0], alt_ps = b->ps[1] - b->ps[0];   // doubles from state 0 to state 1
+        double *g_new = b->packed[1] + d.L.h_len();
+        return enqueue_normal(h, b->ps[1], b->packed[1], g_new, g_new + h->n_params, s, true, NormalTrial{b->flags, b->flags + 2, -alt_ps, -alt_pk, fused});
+    });
 }
 
 int pcs_lm_trial_finish(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
-    int rc = lm_check(h, b, "pcs_lm_trial_finish");
+    const int rc = lm_check(h, b, "pcs_lm_trial_finish");
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    const BlockLayout L = block_layout(h);
-    return enqueue_lm_finish(h->n_cu, h->n_params, L.a_len() + L.b_len() + L.c_len() + h->n_params + 1, b, stream ? (hipStream_t)stream : h->stream);
+    return enqueue_lm_finish(h->n_cu, h->n_params, block_layout(h).packed_len(h->n_params), b, stream ? (hipStream_t)stream : h->stream);
 }
 
 int pcs_lm_trial(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {

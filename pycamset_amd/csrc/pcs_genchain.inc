@@ -1,4 +1,4 @@
-// pcs_genchain.inc — host side of generated chains (included by pcs_engine.hip; uses its fail() / HIPCHK).
+// pcs_genchain.inc — host side of generated chains (included last by pcs_engine.hip; uses pcs_common.inc and pcs_solver.inc).
 //
 // A pcs_genchain owns a code object that pycamset_amd/chain_compiler.py compiled for ONE composition of the reference's function
 // blocks (csrc/ba_generic.hpp), the detection table, one Rodrigues slab per rigid parameter group and output scratch.  It is the
@@ -460,10 +460,7 @@ static BlockLayout genchain_layout(const pcs_genchain *h) {
 
 int pcs_genchain_normal_layout(const pcs_genchain *h, int64_t *out5) {
     if (!h || !out5) return fail(PCS_ERR_ARG, "pcs_genchain_normal_layout: bad arguments");
-    const BlockLayout L = genchain_layout(h);
-    out5[0] = L.n_lead; out5[1] = L.n_trail; out5[2] = L.tb;
-    out5[3] = L.a_len() + L.b_len() + L.c_len() + h->n_params + 1;
-    out5[4] = h->n_params;
+    layout_out5(genchain_layout(h), h->n_params, out5);
     return PCS_OK;
 }
 
@@ -605,7 +602,7 @@ static int genchain_enqueue_normal(pcs_genchain *h, const double *d_param_str, d
     const BlockLayout L = genchain_layout(h);
     const int64_t lim = (int64_t)1 << 32;
     if (L.a_len() >= lim || L.b_len() >= lim || L.c_len() >= lim) return fail(PCS_ERR_ARG, "normal equations of the chain: a region beyond 32 GiB");
-    const int64_t n_h = L.a_len() + L.b_len() + L.c_len();
+    const int64_t n_h = L.h_len();
     if (!zeroed) HIPCHK(hipMemsetAsync(d_packed, 0, sizeof(double) * (size_t)(n_h + np + 1), s));
     BlockGramArgs a{};
     a.tab.packed = h->d_packed; a.tab.cam = h->d_cam; a.tab.img = h->d_img; a.tab.key = h->d_key; a.tab.uv = h->d_uv;
@@ -674,87 +671,48 @@ int pcs_genchain_normal_blocks_device(pcs_genchain *h, const double *d_param_str
 }
 
 // One Levenberg-Marquardt trial of a generated chain in two halves, like pcs_lm_trial_build / pcs_lm_trial_finish (same buffers, same
-// decision kernel, same read-back).  The generated evaluation kernel reads its parameter string from a fixed address, so the trial is
-// always built at ps[1] into packed[1] and an accepted one is copied over state 0: mode must hold PCS_LM_FIXED_TRIAL_BUFFER.
+// shared build — pcs_solver.inc enqueue_lm_trial_build —, same decision kernel, same read-back).  The generated evaluation kernel reads its
+// parameter string from a fixed address, so the trial is always built at ps[1] into packed[1] and an accepted one is copied over state 0:
+// mode must hold PCS_LM_FIXED_TRIAL_BUFFER.
 int pcs_genchain_lm_trial_build(pcs_genchain *h, const pcs_lm_buffers *b, void *stream) {
-    int rc = lm_check(h, b, "pcs_genchain_lm_trial_build");
+    const int rc = lm_check(h, b, "pcs_genchain_lm_trial_build");
     if (rc) return rc;
     if (!(b->mode & PCS_LM_FIXED_TRIAL_BUFFER)) return fail(PCS_ERR_ARG, "pcs_genchain_lm_trial_build: a generated chain builds its trial into packed[1] (mode PCS_LM_FIXED_TRIAL_BUFFER)");
     HIPCHK(hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    const BlockLayout L = genchain_layout(h);
-    const int32_t *stop = b->flags;
-    const int64_t n_packed = L.a_len() + L.b_len() + L.c_len() + h->n_params + 1;
-    const bool prefill = dense_spd_is_one_launch(h->device, L.n_lead, b->spd_algorithm);
-    // with trailing entities: their factors, V = B L^-T and the leading tiles in ONE launch (schur_prep_kernel, csrc/ba_lm_fused.hpp)
-    if (L.n_ent > 0 && L.n_lead > 0)
-        rc = enqueue_schur_prep_fused(L, b, s, stop, nullptr, 0, prefill ? b->spd_work : nullptr, prefill ? cp_work_doubles((L.n_lead + 31) / 32) : 0);
-    else
-        rc = enqueue_schur_prepare(L, b->packed[0], b->fixed, b->lambda, b->linvt, b->u, b->V, b->S, b->rhs, b->dvec, b->gm, b->status, s, stop,
-                                   prefill ? b->spd_work : nullptr, prefill ? cp_work_doubles((L.n_lead + 31) / 32) : 0);
-    if (rc) return rc;
-    const int64_t ldv = std::max<int64_t>(1, L.n_trail);
-    if (L.n_trail > 0) {
-        if (h->deterministic && !b->syrk_work && syrk_work_doubles(L.n_lead, L.n_trail) > 0)
-            return fail(PCS_ERR_ARG, "pcs_genchain_lm_trial_build: deterministic mode needs pcs_lm_buffers.syrk_work (pcs_schur_syrk_work_len doubles)");
-        rc = enqueue_schur_syrk(L.n_lead, L.n_trail, b->V, ldv, b->S, L.n_lead, b->u, b->rhs, s, stop, h->deterministic ? b->syrk_work : nullptr, b->syrk_work_len);
-        if (rc) return rc;
-    }
-    rc = enqueue_dense_spd(h->device, L.n_lead, b->S, L.n_lead, b->rhs, b->xlead, b->spd_work, b->status, s, b->spd_algorithm, stop, prefill, h->spd_timeout_us);
-    if (rc) return rc;
-    if (L.n_ent > 0 && L.n_lead > 0) {
-        // w = V' x_l, the back substitution, the step, the trial string, the vote and the zeroed trial state in ONE launch (schur_finish_kernel,
-        // csrc/ba_lm_fused.hpp — without the slab preparation it does for the hand-fused engines)
-        rc = enqueue_schur_finish_fused(L, h->n_params, h->n_cu, FinishSlabs{}, b, s, stop, nullptr, 0, n_packed);
-    } else {
-        // the step, the trial string — and the trial state zeroed on the way (the contraction sums into it)
-        rc = enqueue_schur_finish(L, b->linvt, b->u, b->u, b->xlead, b->fixed, b->delta, b->ps[0], b->ps[1], s, stop, nullptr,
-                                  (b->mode & PCS_LM_VOTES) ? b->packed[1] + n_packed : nullptr, 0, b->status, b->packed[1], n_packed, h->n_cu);
-    }
-    if (rc) return rc;
-    return genchain_enqueue_normal(h, b->ps[1], b->packed[1], s, stop, true);
+    LmTrialDesc d;
+    d.who = "pcs_genchain_lm_trial_build"; d.device = h->device; d.n_cu = h->n_cu; d.n_params = h->n_params; d.L = genchain_layout(h);
+    d.deterministic = h->deterministic; d.spd_timeout_us = h->spd_timeout_us;
+    d.fused = d.L.n_ent > 0 && d.L.n_lead > 0;   // with trailing entities always (without the slab preparation the completion does for the engines)
+    d.finish_zeroes = true;   // (selector and empty_zero_state stay off: one state, and an empty table is refused by genchain_enqueue_normal with "no detections set")
+    return enqueue_lm_trial_build(d, b, stream ? (hipStream_t)stream : h->stream,
+                                  [&](hipStream_t s, bool) { return genchain_enqueue_normal(h, b->ps[1], b->packed[1], s, b->flags, true); });
 }
 
-// The pieces of a trial as calls of their own, for a loop the HOST steers (a sharded solve whose collective goes through the host, and
-// tests): pcs_schur_prepare / pcs_schur_finish / pcs_lm_decide for the handle's layout.  The caller runs pcs_schur_syrk,
-// pcs_dense_spd_solve and pcs_schur_vtx (which take sizes, not handles) in between.
+// The pieces of a trial as calls of their own (pcs_solver.inc: schur_prepare_piece, schur_finish_piece, lm_decide_piece) for the handle's layout.
 int pcs_genchain_schur_prepare(pcs_genchain *h, double *d_packed, const uint8_t *d_fixed, const double *d_lambda, double *d_linvt, double *d_u,
                                double *d_V, double *d_S, double *d_rhs, double *d_dvec, double *d_gm, int32_t *d_status, void *stream) {
-    if (!h || !d_packed || !d_fixed || !d_lambda || !d_linvt || !d_u || !d_V || !d_S || !d_rhs || !d_dvec || !d_gm || !d_status)
-        return fail(PCS_ERR_ARG, "pcs_genchain_schur_prepare: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    return enqueue_schur_prepare(genchain_layout(h), d_packed, d_fixed, d_lambda, d_linvt, d_u, d_V, d_S, d_rhs, d_dvec, d_gm, d_status,
-                                 stream ? (hipStream_t)stream : h->stream, nullptr);
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_schur_prepare: bad arguments");
+    return schur_prepare_piece("pcs_genchain_schur_prepare", h->device, genchain_layout(h), stream ? (hipStream_t)stream : h->stream, d_packed, d_fixed, d_lambda, d_linvt, d_u, d_V, d_S, d_rhs, d_dvec, d_gm, d_status);
 }
 
 int pcs_genchain_schur_finish(pcs_genchain *h, const double *d_linvt, const double *d_u, const double *d_w, const double *d_xlead, const uint8_t *d_fixed,
                               double *d_delta, const double *d_ps_in, double *d_ps_out, void *stream) {
-    if (!h || !d_linvt || !d_u || !d_w || !d_xlead || !d_fixed || !d_delta || ((d_ps_in == nullptr) != (d_ps_out == nullptr)))
-        return fail(PCS_ERR_ARG, "pcs_genchain_schur_finish: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    return enqueue_schur_finish(genchain_layout(h), d_linvt, d_u, d_w, d_xlead, d_fixed, d_delta, d_ps_in, d_ps_out, stream ? (hipStream_t)stream : h->stream, nullptr);
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_schur_finish: bad arguments");
+    return schur_finish_piece("pcs_genchain_schur_finish", h->device, genchain_layout(h), stream ? (hipStream_t)stream : h->stream, d_linvt, d_u, d_w, d_xlead, d_fixed, d_delta, d_ps_in, d_ps_out);
 }
 
 int pcs_genchain_lm_decide(pcs_genchain *h, const double *d_cost_old, const double *d_cost_new, const double *d_dvec, const double *d_gm, const double *d_delta,
                            const double *d_ps, const uint8_t *d_fixed, int32_t *d_status, double *d_lambda, double *d_stats, void *stream) {
-    if (!h || !d_cost_old || !d_cost_new || !d_dvec || !d_gm || !d_delta || !d_ps || !d_fixed || !d_status || !d_lambda || !d_stats)
-        return fail(PCS_ERR_ARG, "pcs_genchain_lm_decide: bad arguments");
-    HIPCHK(hipSetDevice(h->device));
-    LmDecideArgs a{};
-    a.tail[0] = d_cost_old; a.tail[1] = d_cost_new; a.ps2[0] = a.ps2[1] = d_ps;
-    a.dvec = d_dvec; a.gm = d_gm; a.delta = d_delta; a.fixed = d_fixed; a.status = d_status; a.lambda = d_lambda; a.stats = d_stats; a.n_params = h->n_params;
-    hipLaunchKernelGGL(lm_decide_kernel, dim3(1), dim3(1024), 0, stream ? (hipStream_t)stream : h->stream, a);
-    HIPCHK(hipGetLastError());
-    return PCS_OK;
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_lm_decide: bad arguments");
+    return lm_decide_piece("pcs_genchain_lm_decide", h->device, h->n_params, stream ? (hipStream_t)stream : h->stream, d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed, d_status, d_lambda, d_stats);
 }
 
 int pcs_genchain_lm_trial_finish(pcs_genchain *h, const pcs_lm_buffers *b, void *stream) {
-    int rc = lm_check(h, b, "pcs_genchain_lm_trial_finish");
+    const int rc = lm_check(h, b, "pcs_genchain_lm_trial_finish");
     if (rc) return rc;
     if (!(b->mode & PCS_LM_FIXED_TRIAL_BUFFER)) return fail(PCS_ERR_ARG, "pcs_genchain_lm_trial_finish: mode must hold PCS_LM_FIXED_TRIAL_BUFFER");
     HIPCHK(hipSetDevice(h->device));
-    const BlockLayout L = genchain_layout(h);
-    return enqueue_lm_finish(h->n_cu, h->n_params, L.a_len() + L.b_len() + L.c_len() + h->n_params + 1, b, stream ? (hipStream_t)stream : h->stream);
+    return enqueue_lm_finish(h->n_cu, h->n_params, genchain_layout(h).packed_len(h->n_params), b, stream ? (hipStream_t)stream : h->stream);
 }
 
 int pcs_genchain_lm_trial(pcs_genchain *h, const pcs_lm_buffers *b, void *stream) {

@@ -4,7 +4,8 @@ A: lm_decide_kernel (pcs_lm_trial_finish) on hand-filled inputs, one row per bra
 B: real solves driven one trial at a time (pcs_lm_trial + a synchronisation): the step against the device's own system (backward
    error) and the oracle's normal equations, the costs and stats against the reference, the decision against ``decide``, the
    hand-off from trial to trial.
-C: the real loops (device-steered with speculation, host-steered) reproduce the stepwise drive.
+C: the real loops (device-steered with speculation, host-steered) reproduce the stepwise drive; the fused and the separate launches of a trial
+   (engine option "fused_trial") give the same bits.
 D: every stop code on a real problem."""
 import numpy as np
 import pytest
@@ -554,6 +555,34 @@ def test_loops_reproduce_the_stepwise_drive(name):
             rho = 0.5 * (rc["stats"][6] - rc["stats"][5]) / R.predicted_reduction(rc["lam"], rc["dvec"], rc["gm"], rc["delta"])
             assert R.near_a_threshold(rho, rc["ctrl"]), (k, hs[k], want[k])
     assert host.message == res.message and host.nit == res.nit and host.nfev == res.nfev
+
+
+@pytest.mark.parametrize("name", ["ring8-template-far20", "ring8-self-gauge"])
+def test_fused_and_separate_trial_launches_give_the_same_bits(name):
+    """DESIGN section 4 and INTEGRATION.md: ``set_option("fused_trial", 0)`` runs the small kernels of a trial as separate launches and
+    returns the same bits.  In deterministic mode (the default mode's atomics reorder the last bits from run to run) every read-back of
+    every trial and the solution are compared exactly: no tolerance."""
+    from pycamset_amd.device_solver import lm_solve
+    build, _, _, lam0, _, _ = FIXTURES[name]
+    _, h, x0 = build()
+    eng = h.op_fun._engine_for(h._flat_detections())
+    eng.set_option("deterministic", 1)
+    res = {}
+    try:
+        for fused in (1, 0):
+            eng.set_option("fused_trial", fused)
+            res[fused] = lm_solve(h, x0.copy(), max_iter=30, lam0=lam0, linear_solver="cholesky")
+    finally:
+        eng.set_option("fused_trial", 1)
+        eng.set_option("deterministic", 0)
+
+    def bits(v):
+        return np.ascontiguousarray(v, dtype=np.float64).view(np.uint64)
+
+    assert len(res[1].trials) == len(res[0].trials) > 0
+    for k, (fused, separate) in enumerate(zip(res[1].trials, res[0].trials)):
+        assert np.array_equal(bits(fused), bits(separate)), (name, k, fused, separate)
+    assert np.array_equal(bits(res[1].x), bits(res[0].x)), name
 
 
 # =================================================================================== D: every stop code on a real problem
