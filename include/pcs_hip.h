@@ -565,6 +565,57 @@ int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, 
 int pcs_tri_refined(pcs_triangulator *t, double *pts, double *rms, int32_t *info, double *resid);
 int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batched target-pose estimation, PnP (csrc/ba_pnp.hpp).  Since pcs_version() 105.
+ * Replaces: AbstractTarget.target_pose_in_cam_image (calibration_targets/abstract_target.py:345-405: at least 6 points,
+ *           cv2.solvePnPGeneric, the solution of lowest error), called per camera and image by estimate_camera_relative_poses
+ *           (optimisation/template_handler.py:484-491) in front of calc_initial_params (template_handler.py:302-346).
+ * A view is the set of detections of one (camera, image) pair.  Per view: the measurements are undistorted (five fixed-point steps) for
+ * a linear start that needs no prior (planar views, lambda_min / lambda_mid of the template points' scatter < 1e-3: homography;
+ * others: 3 x 4 DLT), then a 6-parameter Levenberg-Marquardt minimises sum || uv - pi(R X + t) ||^2 in the measured pixels with the full
+ * Brown-Conrady model; planar views are also refined from the second pose of the planar ambiguity and the lower cost is kept (the
+ * reference's argmin over solvePnPGeneric's solutions).  Pose convention: X_cam = R(r) X_target + t, r a Rodrigues vector, |r| <= pi.
+ * Damping, accept rule and stops are those of pcs_tri_refine (the step is compared with the Frobenius size of [R | t]).
+ *   pcs_pnp_create            n_cams cameras, a template of n_keys points
+ *   pcs_pnp_set_cameras       intr (n_cams, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2], the engine's intrinsics slab
+ *                             (template_handler.py:321-329 builds the same rows from the camera set)
+ *   pcs_pnp_set_template      points (n_keys, 3): target.point_data flattened (template_handler.py:511)
+ *   pcs_pnp_set_observations  host arrays, copied: key (n_obs) int32, uv (n_obs, 2), sorted by view; view j owns rows
+ *                             [start_inds[j], start_inds[j+1]) and belongs to camera view_cam[j]; keys and cameras are range-checked
+ *                             -> PCS_ERR_RANGE (abstract_target.py:360-375 gathers the same per image)
+ *   pcs_pnp_run               queue the kernels on `stream` (NULL = the handle's stream).  A view with fewer than min_points
+ *                             observations (the reference: 6, abstract_target.py:377), a non-finite start or a start behind the camera
+ *                             is not estimated: NaN pose, status 0.  Outputs (device buffers of the caller, or NULL = handle-owned):
+ *                             d_pose (n_views, 6); d_pose_init (n_views, 6) the linear start; d_pose_alt (n_views, 6) the second planar
+ *                             start (NaN for 3-D views); d_rms (n_views, 2) RMS reprojection error at the returned pose and at the
+ *                             start, pixels; d_info (n_views, 3) int32 {trials used, status PCS_PNP_*, observations}; with flags
+ *                             PCS_PNP_RESIDUALS, d_resid (n_obs, 2) residuals at the returned pose in observation order.
+ *                             PCS_ERR_ARG: NULL handle, max_iter < 0, a negative or non-finite tolerance, min_points < 1, unknown flags.
+ *   pcs_pnp_results           copy handle-owned outputs of the last run to the host (any pointer may be NULL; blocking)
+ *                             (replaces the Mat_ac array of template_handler.py:485-491)
+ *   pcs_pnp_last_kernel_ms    device time of the last run: ordering of the views, start and LM kernels.  PCS_ERR_STATE when the
+ *                             last run had no views and so queued nothing.
+ */
+typedef struct pcs_pose_estimator pcs_pose_estimator;
+#define PCS_PNP_RESIDUALS 1
+enum {
+    PCS_PNP_NOT_ESTIMATED = 0,   /* too few observations, a non-finite start or a start behind the camera: the pose is NaN */
+    PCS_PNP_CONVERGED = 1,       /* ftol, xtol or gtol */
+    PCS_PNP_MAX_ITER = 2,        /* max_iter trials used */
+    PCS_PNP_NO_DECREASE = 3      /* the damping grew past 1e10 without a lower cost, or the damped system lost definiteness */
+};
+enum { PCS_PNP_OUT_POSE = 1, PCS_PNP_OUT_POSE_INIT = 2, PCS_PNP_OUT_POSE_ALT = 4, PCS_PNP_OUT_RMS = 8, PCS_PNP_OUT_INFO = 16, PCS_PNP_OUT_RESIDUALS = 32 };
+int pcs_pnp_create(pcs_pose_estimator **out, int device, int64_t n_cams, int64_t n_keys);
+int pcs_pnp_destroy(pcs_pose_estimator *p);
+int pcs_pnp_set_cameras(pcs_pose_estimator *p, const double *intr);
+int pcs_pnp_set_template(pcs_pose_estimator *p, const double *points);
+int pcs_pnp_set_observations(pcs_pose_estimator *p, int64_t n_obs, const int32_t *key, const double *uv, int64_t n_views, const int64_t *start_inds,
+                             const int32_t *view_cam);
+int pcs_pnp_run(pcs_pose_estimator *p, int max_iter, double ftol, double xtol, double gtol, int min_points, int flags, double *d_pose,
+                double *d_pose_init, double *d_pose_alt, double *d_rms, int32_t *d_info, double *d_resid, void *stream);
+int pcs_pnp_results(pcs_pose_estimator *p, double *pose, double *pose_init, double *pose_alt, double *rms, int32_t *info, double *resid);
+int pcs_pnp_last_kernel_ms(pcs_pose_estimator *p, float *kernel_ms);
+
 /* Page-locked host memory for outputs: pcs_eval / pcs_eval_compact copy device -> host at PCIe rate
  * into such buffers (a pageable destination is several times slower).  Replaces nothing in the
  * reference (NumPy owns every array there, afb:561); SURVEY 8 f1 "zero-copy hand-off". */

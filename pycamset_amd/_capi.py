@@ -38,6 +38,9 @@ COV_TRSM_IDENTITY = 1                    # include/pcs_hip.h PCS_COV_TRSM_IDENTI
 TRI_REFINE_RESIDUALS = 1                 # include/pcs_hip.h PCS_TRI_REFINE_RESIDUALS
 # include/pcs_hip.h PCS_TRI_REFINE_*: per-point status of the triangulation refinement
 TRI_NOT_REFINED, TRI_CONVERGED, TRI_MAX_ITER, TRI_NO_DECREASE = 0, 1, 2, 3
+PNP_RESIDUALS = 1                        # include/pcs_hip.h PCS_PNP_RESIDUALS
+# include/pcs_hip.h PCS_PNP_*: per-view status of the pose estimation
+PNP_NOT_ESTIMATED, PNP_CONVERGED, PNP_MAX_ITER, PNP_NO_DECREASE = 0, 1, 2, 3
 
 
 SYMBOLS = {
@@ -132,6 +135,14 @@ SYMBOLS = {
     "pcs_tri_refine": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, _P, _P, _P, _P, _P]),
     "pcs_tri_refined": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
     "pcs_tri_last_refine_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_pnp_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
+    "pcs_pnp_destroy": (c_int, [_P]),
+    "pcs_pnp_set_cameras": (c_int, [_P, POINTER(c_double)]),
+    "pcs_pnp_set_template": (c_int, [_P, POINTER(c_double)]),
+    "pcs_pnp_set_observations": (c_int, [_P, c_int64, POINTER(c_int32), POINTER(c_double), c_int64, POINTER(c_int64), POINTER(c_int32)]),
+    "pcs_pnp_run": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "pcs_pnp_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
+    "pcs_pnp_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_host_alloc": (c_int, [POINTER(_P), c_int64]),
     "pcs_host_free": (c_int, [_P]),
     "pcs_membench": (c_int, [c_int, c_int, c_int64, c_int, c_int, POINTER(c_float)]),

@@ -6,6 +6,9 @@ pyCamSet/optimisation/compiled_helpers.py, evaluated by the HIP engine:
     bundle_adjustment_costfn(dct, im_points, projection_matrixes, intrinsics, dists) -> (2N,)   ch:518-549
     bundle_adj_parrallel_solver(dct (T, L, 5), ...) -> (T, 2L)                                  ch:493-516
 
+Row f5, ``estimate_view_poses``: the per-view target pose the reference gets from cv2.solvePnPGeneric
+(calibration_targets/abstract_target.py:345-405) in front of ``calc_initial_params``.
+
 The reference calls them with the detection table on every call (template_handler.py:537-543,
 :586-592); the table is uploaded once and cached by content.
 """
@@ -378,3 +381,194 @@ def group_reconstructable(data: np.ndarray):
     starts = np.zeros(sizes.shape[0] + 1, dtype=np.int64)
     np.cumsum(sizes, out=starts[1:])
     return kept, starts
+
+
+# ---- batched target-pose estimation (row f5: the PnP in front of calc_initial_params) -------------------------------------------------
+# per-view status of the pose estimation (include/pcs_hip.h PCS_PNP_*)
+PNP_NOT_ESTIMATED, PNP_CONVERGED, PNP_MAX_ITER, PNP_NO_DECREASE = 0, 1, 2, 3
+last_pnp_kernel_ms = None
+
+
+@dataclass
+class ViewPoses:
+    """Target poses per (camera, image) view (``estimate_view_poses``): ``poses`` (C, I, 6) = [rotvec, t] with
+    X_cam = R(rotvec) X_target + t, |rotvec| <= pi; ``poses_init`` the linear start, ``poses_alt`` the second start of a planar view (NaN
+    for 3-D views); ``rms`` / ``rms_init`` (C, I) RMS reprojection error in pixels at the pose / at the start (rms <= rms_init);
+    ``status`` (PNP_*), ``iterations`` (LM trials), ``n_points`` (C, I) int32; ``residuals`` (N, 2) uv - projection in the table's row
+    order, or None.  Views without detections or with fewer than ``min_points``: NaN, status 0 (the reference's mode="nan")."""
+    poses: np.ndarray
+    poses_init: np.ndarray
+    poses_alt: np.ndarray
+    rms: np.ndarray
+    rms_init: np.ndarray
+    status: np.ndarray
+    iterations: np.ndarray
+    n_points: np.ndarray
+    residuals: np.ndarray | None = None
+
+
+class PoseEstimator:
+    """Owner of one ``pcs_pose_estimator`` handle (include/pcs_hip.h): camera table, template, observation copies and outputs stay on
+    the device across calls."""
+
+    def __init__(self, n_cams: int, n_keys: int, device: int = 0):
+        import ctypes
+
+        from . import _capi
+
+        self._capi, self._ct = _capi, ctypes
+        self._h = ctypes.c_void_p()
+        _capi.check(_capi.lib().pcs_pnp_create(ctypes.byref(self._h), int(device), int(n_cams), int(n_keys)))
+        self.n_cams, self.n_keys, self.device = int(n_cams), int(n_keys), int(device)
+        self.n_views, self.n_obs = 0, 0
+        self._residuals = False
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            self._capi.lib().pcs_pnp_destroy(self._h)
+            self._h = self._ct.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_cameras(self, intr):
+        K = np.ascontiguousarray(intr, dtype=np.float64)
+        if K.shape != (self.n_cams, 9):
+            raise ValueError(f"expected intr ({self.n_cams}, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2]")
+        self._capi.check(self._capi.lib().pcs_pnp_set_cameras(self._h, K.ctypes.data_as(self._ct.POINTER(self._ct.c_double))))
+
+    def set_template(self, points):
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        if pts.shape[0] != self.n_keys:
+            raise ValueError(f"expected {self.n_keys} template points")
+        self._capi.check(self._capi.lib().pcs_pnp_set_template(self._h, pts.ctypes.data_as(self._ct.POINTER(self._ct.c_double))))
+
+    def set_observations(self, key, uv, start_inds, view_cam):
+        """Host arrays sorted by view: key (n_obs,) int, uv (n_obs, 2), start_inds (n_views + 1,), view_cam (n_views,) int."""
+        ct = self._ct
+        key = np.ascontiguousarray(key, dtype=np.int32)
+        uv = np.ascontiguousarray(uv, dtype=np.float64)
+        start = np.ascontiguousarray(start_inds, dtype=np.int64)
+        vcam = np.ascontiguousarray(view_cam, dtype=np.int32)
+        if start.ndim != 1 or start.shape[0] < 1 or vcam.shape != (start.shape[0] - 1,) or uv.shape != (key.shape[0], 2):
+            raise ValueError("expected key (n_obs,), uv (n_obs, 2), start_inds (n_views + 1,), view_cam (n_views,)")
+        self._capi.check(self._capi.lib().pcs_pnp_set_observations(
+            self._h, key.shape[0], key.ctypes.data_as(ct.POINTER(ct.c_int32)), uv.ctypes.data_as(ct.POINTER(ct.c_double)), start.shape[0] - 1,
+            start.ctypes.data_as(ct.POINTER(ct.c_int64)), vcam.ctypes.data_as(ct.POINTER(ct.c_int32))))
+        self.n_views, self.n_obs = start.shape[0] - 1, key.shape[0]
+
+    def run(self, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
+            gtol: float = REFINE_DEFAULTS["gtol"], min_points: int = 6, residuals: bool = False, stream: int | None = None):
+        """Queue the start and LM kernels (asynchronous; handle-owned outputs, fetched with ``results()``)."""
+        from .engine import _stream_arg
+        max_iter, ftol, xtol, gtol = check_refine_options(max_iter, ftol, xtol, gtol)
+        min_points = check_min_points(min_points)
+        self._capi.check(self._capi.lib().pcs_pnp_run(self._h, max_iter, ftol, xtol, gtol, min_points, self._capi.PNP_RESIDUALS if residuals else 0,
+                                                      None, None, None, None, None, None, _stream_arg(stream)))
+        self._residuals = bool(residuals)
+
+    def results(self):
+        """Wait for the last ``run``: (pose (n_views, 6), pose_init, pose_alt, rms (n_views, 2), info (n_views, 3) int32, residuals or None)."""
+        ct, n = self._ct, self.n_views
+        dp = ct.POINTER(ct.c_double)
+        pose, init, alt, rms, info = np.empty((n, 6)), np.empty((n, 6)), np.empty((n, 6)), np.empty((n, 2)), np.empty((n, 3), dtype=np.int32)
+        resid = np.empty((self.n_obs, 2)) if self._residuals else None
+        self._capi.check(self._capi.lib().pcs_pnp_results(self._h, pose.ctypes.data_as(dp), init.ctypes.data_as(dp), alt.ctypes.data_as(dp),
+                                                          rms.ctypes.data_as(dp), info.ctypes.data_as(ct.POINTER(ct.c_int32)),
+                                                          resid.ctypes.data_as(dp) if resid is not None else None))
+        return pose, init, alt, rms, info, resid
+
+    def last_kernel_ms(self) -> float:
+        ms = self._ct.c_float(0.0)
+        self._capi.check(self._capi.lib().pcs_pnp_last_kernel_ms(self._h, self._ct.byref(ms)))
+        return float(ms.value)
+
+
+def check_min_points(min_points) -> int:
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) < 2 ** 31:
+        raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
+    return int(min_points)
+
+
+def group_by_view(dct, n_imgs: int):
+    """The host grouping of ``estimate_view_poses``: one stable sort on (cam * n_imgs + im, key), skipped when the table is already
+    ordered.  The key takes part so that a view's observations reach the device in one order whatever the order of the table: the
+    same table shuffled gives the same bits.  -> (order or None, view ids (n_views,), start (n_views + 1,))."""
+    d = np.asarray(dct, dtype=np.float64)
+    vid = d[:, 0].astype(np.int64) * int(n_imgs) + d[:, 1].astype(np.int64)
+    key = d[:, 2].astype(np.int64)
+    span = int(key.max()) + 1 if key.shape[0] else 1
+    rank = vid * span + key if key.shape[0] and key.min() >= 0 else vid   # keys out of range are refused by the handle later
+    order = None
+    if rank.shape[0] > 1 and np.any(rank[1:] < rank[:-1]):
+        order = np.argsort(rank, kind="stable")
+        vid = vid[order]
+    head = np.ones(vid.shape[0], dtype=bool)
+    head[1:] = vid[1:] != vid[:-1]
+    first = np.nonzero(head)[0]
+    return order, vid[first], np.concatenate([first, [vid.shape[0]]]).astype(np.int64)
+
+
+_pnp_cache: dict = {}
+
+
+def _pose_estimator(device: int, n_cams: int, n_keys: int) -> PoseEstimator:
+    key = (int(device), int(n_cams), int(n_keys))
+    est = _pnp_cache.get(key)
+    if est is None:
+        _pnp_cache.clear()
+        est = _pnp_cache[key] = PoseEstimator(n_cams, n_keys, device)
+    return est
+
+
+def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_points: int = 6, max_iter: int = REFINE_DEFAULTS["max_iter"],
+                        ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"], gtol: float = REFINE_DEFAULTS["gtol"],
+                        return_residuals: bool = False, device: int = 0) -> ViewPoses:
+    """The pose of the known target in every (camera, image) view, on the device (include/pcs_hip.h pcs_pnp_run): what the reference's
+    ``target_pose_in_cam_image`` (calibration_targets/abstract_target.py:345-405, cv2.solvePnPGeneric and the solution of lowest error)
+    gives ``estimate_camera_relative_poses`` (optimisation/template_handler.py:484-491) per camera and image.
+
+    ``dct``: the flattened (N, 5) table [cam, im, key, u, v] in any order; ``points``: the template (K, 3) (or ``target.point_data``);
+    ``intr``: (C, 9) rows [fx, cx, fy, cy, k0, k1, p0, p1, k2]; ``n_imgs``: images of the result (default: largest image index + 1)."""
+    global last_pnp_kernel_ms
+    opts = check_refine_options(max_iter, ftol, xtol, gtol)
+    min_points = check_min_points(min_points)
+    d = np.asarray(dct, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    K = np.asarray(intr, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 5 or K.ndim != 2 or K.shape[1] != 9:
+        raise ValueError("expected dct (N, 5) = [cam, im, key, u, v] and intr (C, 9)")
+    C = K.shape[0]
+    if n_imgs is None:
+        n_imgs = int(d[:, 1].max()) + 1 if d.shape[0] else 0
+    I = int(n_imgs)
+    if d.shape[0] and (d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 1].min() < 0 or d[:, 1].max() >= I):
+        raise ValueError("camera or image index of the table outside the intrinsics / n_imgs")
+    out = ViewPoses(poses=np.full((C, I, 6), np.nan), poses_init=np.full((C, I, 6), np.nan), poses_alt=np.full((C, I, 6), np.nan),
+                    rms=np.full((C, I), np.nan), rms_init=np.full((C, I), np.nan), status=np.zeros((C, I), dtype=np.int32),
+                    iterations=np.zeros((C, I), dtype=np.int32), n_points=np.zeros((C, I), dtype=np.int32),
+                    residuals=np.empty((d.shape[0], 2)) if return_residuals else None)
+    if d.shape[0] == 0:
+        return out
+    order, ids, start = group_by_view(d, I)
+    ds = d if order is None else d[order]
+    est = _pose_estimator(device, C, pts.shape[0])
+    est.set_cameras(K)
+    est.set_template(pts)
+    est.set_observations(ds[:, 2].astype(np.int32), ds[:, 3:5], start, (ids // I).astype(np.int32))
+    est.run(*opts, min_points=min_points, residuals=return_residuals)
+    pose, init, alt, rms, info, resid = est.results()
+    last_pnp_kernel_ms = est.last_kernel_ms()
+    c, i = ids // I, ids % I
+    out.poses[c, i], out.poses_init[c, i], out.poses_alt[c, i] = pose, init, alt
+    out.rms[c, i], out.rms_init[c, i] = rms[:, 0], rms[:, 1]
+    out.iterations[c, i], out.status[c, i], out.n_points[c, i] = info[:, 0], info[:, 1], info[:, 2]
+    if return_residuals:
+        if order is None:
+            out.residuals = resid
+        else:
+            out.residuals[order] = resid
+    return out

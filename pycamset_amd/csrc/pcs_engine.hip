@@ -36,6 +36,7 @@
 #include "ba_covariance.hpp"
 #include "ba_triangulate.hpp"
 #include "ba_tri_refine.hpp"
+#include "ba_pnp.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -44,6 +45,7 @@ using namespace pcs;
 
 #include "pcs_common.inc"
 #include "pcs_triangulator.inc"
+#include "pcs_pnp.inc"
 #include "pcs_solver.inc"
 
 struct pcs_engine {

@@ -16,9 +16,9 @@ so ``scipy.optimize.least_squares(loss_fn, x0, jac=jac_fn, x_scale='jac', ...)``
 parameter groups exist, so here ONE table (``_CHAIN_GROUPS``) drives one primitive and one handler core.
 
 ``camset`` only needs ``get_names()`` / ``get_n_cams()`` and ``target`` only needs ``point_data`` — the
-attributes the reference touches on this path (th:116-129, th:160-163).  Initial-pose estimation (OpenCV
-PnP, th:302-346), outlier prompts and CameraSet reconstruction are outside the path: initial parameters
-are supplied with ``set_initial_params``.
+attributes the reference touches on this path (th:116-129, th:160-163).  ``calc_initial_params`` (th:302-346) computes a
+start vector from the detections with the device's batched PnP (``pose_seeding``); outlier prompts and CameraSet
+reconstruction are outside the path.  ``get_initial_params`` returns what ``set_initial_params`` was given.
 
 Differences from the reference, on purpose:
   * The engine lays the parameter string out from the SLAB sizes (n_cams, max_ims, number of target
@@ -275,8 +275,43 @@ class TemplateBundleHandler:  # th:80-240
         if self.initial_params is not None:
             return self.initial_params
         raise NotImplementedError(
-            "calc_initial_params needs OpenCV PnP (template_handler.py:302-346), which is outside the "
-            "accelerated path: supply a start vector with set_initial_params()")
+            "no start vector has been set: compute one from the detections with calc_initial_params() (template_handler.py:302-346, "
+            "device PnP) and hand it to set_initial_params(), or supply your own")
+
+    def calc_initial_params(self, intr=None) -> np.ndarray:  # th:302-346
+        """A start vector from the detections: per-view target poses on the device (``compiled_helpers.estimate_view_poses``), the view
+        graph of ``pose_seeding.estimate_camera_relative_poses`` (th:468-601), then the free entries in slab order — unfixed intrinsics,
+        extrinsics and poses (plus, for the self and free chains, the free point scalars of the template).  ``intr``: (C, 9) rows
+        [fx, cx, fy, cy, k0, k1, p0, p1, k2]; default: ``camset[idc].intrinsic`` / ``.distortion_coefs`` (th:321-329).  Sets
+        ``missing_poses``; returns the vector without storing it.  The interactive outlier prompt (th:242-279) is not mirrored."""
+        from .pose_seeding import estimate_camera_relative_poses
+
+        bp = self.bundlePrimitive
+        n_cams = bp.intr.shape[0]
+        if intr is None:
+            try:
+                intr = np.stack([np.concatenate((np.asarray(self.camset[idc].intrinsic)[[0, 0, 1, 1], [0, 2, 1, 2]].squeeze(),
+                                                 np.asarray(self.camset[idc].distortion_coefs).squeeze()), axis=0) for idc in range(n_cams)])
+            except (TypeError, AttributeError, KeyError, IndexError):
+                raise ValueError("calc_initial_params: the camset holds no intrinsics (camset[idc].intrinsic / .distortion_coefs): "
+                                 "pass intr (C, 9)") from None
+        intr = np.array(intr, dtype=np.float64)
+        if intr.shape != (n_cams, 9):
+            raise ValueError(f"intr must be ({n_cams}, 9), got {intr.shape}")
+        for idc, name in enumerate(self.cam_names):   # a fixed camera's intrinsics are the fixed ones
+            if "int" in self.fixed_params.get(name, {}):
+                intr[idc] = self.fixed_params[name]["int"]
+        n_imgs = bp.poses.shape[0] if "pose" in bp.groups else self.detection.max_ims
+        extr, poses, self.initial_per_im_error, missing = estimate_camera_relative_poses(
+            self._flat_detections(), self.point_data.reshape((-1, 3)), intr, n_cams, n_imgs,
+            ref_cam=self.problem_opts.get("ref_cam", 0), ref_pose=self.problem_opts.get("ref_pose", 0))
+        self.missing_poses = missing
+        parts = [intr[bp.intr_unfixed].ravel(), extr[bp.extr_unfixed].ravel()]
+        if "pose" in bp.groups:
+            parts.append(poses[bp.poses_unfixed].ravel())
+        if "bdpt" in bp.groups:
+            parts.append(self.flat_point_data[bp.bdpt_unfixed])
+        return np.concatenate(parts)
 
     def get_detection_data(self, flatten=False) -> np.ndarray:  # th:387-406
         detection = self.detection

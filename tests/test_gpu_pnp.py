@@ -1,0 +1,161 @@
+"""The batched target-pose estimation on the GPU (include/pcs_hip.h pcs_pnp_run, csrc/ba_pnp.hpp) against its NumPy restatement
+(tests/pnp_reference.py, itself pinned to scipy.optimize.least_squares and to noise-free truth in tests/test_pnp_reference.py).
+
+Tolerances.  The restatement's LM is started from the device's own ``poses_init`` / ``poses_alt``, so both take the same trials; they
+differ by the rounding of the kernel's reciprocals and of the summation order.  1e-9 (radians; translation relative to the viewing
+distance) is the figure of tests/test_gpu_tri_refine.py for the same LM policy; ``rms_init`` is the NumPy RMS at ``poses_init`` to
+1e-12 relative plus 1e-12 px (a residual is the difference of two pixel coordinates near 1e3, each known to ~1e-13 px)."""
+import numpy as np
+import pytest
+
+from pycamset_amd import handlers, synthetic
+from pycamset_amd import compiled_helpers as hip_ch
+from pycamset_amd.detections import TargetDetection
+from tests import pnp_reference as ref
+from tests.test_pnp_reference import CUBE, DuckCamset, DuckTarget, PLANE, assert_recovers_truth, pose_error, truth_rig
+
+pytestmark = pytest.mark.gpu
+
+G, V = 16, 4   # lanes per view and observations held in registers per lane (csrc/pcs_pnp.inc PNP_G, PNP_V)
+
+
+def views_of(det, n_imgs):
+    ds, ids, start = ref.group_views(det, n_imgs)
+    return [(int(v) // n_imgs, int(v) % n_imgs, ds[start[k]:start[k + 1]]) for k, v in enumerate(ids)]
+
+
+def assert_matches_restatement(res, det, points, intr, n_imgs, **opts):
+    for c, i, rows in views_of(det, n_imgs):
+        keys, uv = rows[:, 2].astype(int), rows[:, 3:5]
+        assert res.n_points[c, i] == len(keys)
+        if len(keys) < 6:
+            assert res.status[c, i] == hip_ch.PNP_NOT_ESTIMATED and np.all(np.isnan(res.poses[c, i]))
+            continue
+        start, _, _ = ref.linear_start(keys, uv, intr[c], points)
+        for a, b in zip(res.poses_init[c, i], start):   # the same start was taken
+            assert abs(a - b) <= 1e-6 * max(1.0, abs(b)), (c, i, res.poses_init[c, i], start)
+        r = ref.solve_view(keys, uv, intr[c], points, start=res.poses_init[c, i], alt=res.poses_alt[c, i], **opts)
+        assert res.status[c, i] in (hip_ch.PNP_CONVERGED, hip_ch.PNP_MAX_ITER, hip_ch.PNP_NO_DECREASE)
+        assert 1 <= res.iterations[c, i] <= opts.get("max_iter", 10)
+        assert res.rms[c, i] <= res.rms_init[c, i]
+        r_np = ref.rms(res.poses_init[c, i], points[keys], uv, intr[c])
+        assert abs(res.rms_init[c, i] - r_np) <= 1e-12 * r_np + 1e-12, (c, i, res.rms_init[c, i], r_np)
+        ang, dt = pose_error(res.poses[c, i], r["pose"])
+        print(f"view ({c}, {i}) n = {len(keys)}: angle {ang:.2e} rad, translation {dt:.2e}, trials {res.iterations[c, i]} / {r['iterations']}")
+        assert ang <= 1e-9 and dt <= 1e-9, (c, i, ang, dt)
+
+
+@pytest.mark.parametrize("kind,vis", [("cube", 1.0), ("planar", 1.0), ("face", 1.0), ("cube", 0.5)])
+def test_parity_with_the_restatement(kind, vis):
+    """Noisy rigs (0.3 px).  At visibility 0.5 the views of a wave differ in size (about 40 to 56 observations: some lanes hold
+    three register observations, some four)."""
+    rig, det = truth_rig(kind, noise_px=0.3, seed=21, visibility=vis)
+    res = hip_ch.estimate_view_poses(det, rig.points, rig.intr_true, n_imgs=3)
+    assert res.poses.shape == (3, 3, 6) and res.residuals is None
+    assert np.all(np.isfinite(res.poses_alt).all(axis=-1) == (kind != "cube"))
+    assert_matches_restatement(res, det, rig.points, rig.intr_true, 3)
+
+
+def test_isotropic_target_takes_the_3d_start():
+    """The 8 corners of a cube with dyadic coordinates: the scatter of every view is exactly 2^-9 I in any summation order, so its
+    three eigenvalues are equal.  Such a view is 3-D (no second start), recovers the truth without noise and follows the
+    restatement with noise."""
+    rig, det = truth_rig("corners")
+    res = hip_ch.estimate_view_poses(det, rig.points, rig.intr_true, n_imgs=3)
+    assert np.all(np.isfinite(res.poses_init)) and np.all(np.isnan(res.poses_alt))
+    assert_recovers_truth(res, rig)
+    rig, det = truth_rig("corners", noise_px=0.3, seed=21)
+    res = hip_ch.estimate_view_poses(det, rig.points, rig.intr_true, n_imgs=3)
+    assert np.all(np.isnan(res.poses_alt))
+    assert_matches_restatement(res, det, rig.points, rig.intr_true, 3)
+
+
+def test_noise_free_truth_in_one_launch_of_mixed_views():
+    """Cube, planar and single-face views side by side in one launch (the template holds the cube's points followed by the board's):
+    the start takes divergent paths inside a wave, and every view recovers the truth like the restatement does."""
+    cube, det_c = truth_rig("cube")
+    plane, det_p = truth_rig("planar")
+    face, det_f = truth_rig("face")
+    pts = np.concatenate([CUBE, PLANE])
+    det_p, det_f = det_p.copy(), det_f.copy()
+    det_p[:, 2] += CUBE.shape[0]
+    det_p[:, 1] += 3
+    det_f[:, 1] += 6
+    assert np.array_equal(cube.intr_true, plane.intr_true) and np.array_equal(cube.extr_true, face.extr_true)   # same seed: same cameras, same poses
+    res = hip_ch.estimate_view_poses(np.concatenate([det_c, det_p, det_f]), pts, cube.intr_true, n_imgs=9)
+    for k, rig in enumerate((cube, plane, face)):
+        sub = ref.ViewPosesRef()
+        sub.poses, sub.rms, sub.status, sub.n_points = (getattr(res, n)[:, 3 * k:3 * k + 3] for n in ("poses", "rms", "status", "n_points"))
+        assert_recovers_truth(sub, rig)
+
+
+def test_shapes_at_which_the_kernel_can_go_wrong():
+    """Views of 5 (refused), exactly 6, below G, G and G * V + 1 observations, 17 views (four whole waves of four groups and one wave
+    with one live and three dead groups), no views, max_iter = 0, a NaN measurement, a shuffled table."""
+    rig = synthetic.make_rig("pnp-shapes", 1, 17, CUBE, seed=33, noise_px=0.3)
+    det = rig.detections
+    rng = np.random.default_rng(5)
+    sizes = {0: 5, 1: 6, 2: G - 3, 3: G, 4: G * V + 1}
+    keep = np.ones(det.shape[0], dtype=bool)
+    for im, n in sizes.items():
+        rows = np.nonzero(det[:, 1] == im)[0]
+        keep[rng.permutation(rows)[n:]] = False
+    det = det[keep]
+    intr = rig.intr_true
+    base = hip_ch.estimate_view_poses(det, rig.points, intr, n_imgs=17, return_residuals=True)
+    assert [int(base.n_points[0, im]) for im in sizes] == list(sizes.values())
+    assert base.status[0, 0] == hip_ch.PNP_NOT_ESTIMATED and np.all(np.isnan(base.poses[0, 0])) and np.isnan(base.rms[0, 0]) and base.iterations[0, 0] == 0
+    assert np.all(base.status[0, 1:] != hip_ch.PNP_NOT_ESTIMATED) and np.all(np.isfinite(base.poses[0, 1:]))
+    assert_matches_restatement(base, det, rig.points, intr, 17)
+    # residuals at the returned poses, in the table's order
+    for c, i, rows in views_of(det, 17):
+        sel = det[:, 1] == i
+        if i == 0:
+            assert np.all(np.isnan(base.residuals[sel]))
+        else:
+            r_np = ref.residuals(base.poses[c, i], rig.points[rows[:, 2].astype(int)], rows[:, 3:5], intr[c])
+            assert np.allclose(base.residuals[sel], r_np, rtol=0, atol=1e-9)
+    # no views
+    e = hip_ch.estimate_view_poses(det[:0], rig.points, intr, n_imgs=17)
+    assert np.all(np.isnan(e.poses)) and np.all(e.status == 0) and np.all(e.n_points == 0)
+    # min_points is the caller's: with 5 the five-point view is tried as well (an underdetermined DLT: whatever it gives, the others keep their bits)
+    five = hip_ch.estimate_view_poses(det, rig.points, intr, n_imgs=17, min_points=5)
+    assert five.n_points[0, 0] == 5 and np.array_equal(five.poses[0, 1:], base.poses[0, 1:])
+    # max_iter = 0: the start's bits, MAX_ITER
+    z = hip_ch.estimate_view_poses(det, rig.points, intr, n_imgs=17, max_iter=0)
+    assert np.array_equal(z.poses[0, 1:], z.poses_init[0, 1:]) and np.array_equal(z.poses_init, base.poses_init, equal_nan=True)
+    assert np.all(z.status[0, 1:] == hip_ch.PNP_MAX_ITER) and np.all(z.iterations == 0) and np.array_equal(z.rms[0, 1:], z.rms_init[0, 1:])
+    # a NaN measurement changes only its own view
+    bad = det.copy()
+    bad[np.nonzero(det[:, 1] == 7)[0][2], 4] = np.nan
+    b = hip_ch.estimate_view_poses(bad, rig.points, intr, n_imgs=17)
+    assert b.status[0, 7] == hip_ch.PNP_NOT_ESTIMATED and np.all(np.isnan(b.poses[0, 7]))
+    others = np.arange(17) != 7
+    assert np.array_equal(b.poses[0, others], base.poses[0, others], equal_nan=True) and np.array_equal(b.rms[0, others], base.rms[0, others], equal_nan=True)
+    # a shuffled table gives the same bits
+    perm = rng.permutation(det.shape[0])
+    s = hip_ch.estimate_view_poses(det[perm], rig.points, intr, n_imgs=17, return_residuals=True)
+    assert np.array_equal(s.poses, base.poses, equal_nan=True) and np.array_equal(s.rms, base.rms, equal_nan=True)
+    assert np.array_equal(s.iterations, base.iterations) and np.array_equal(s.residuals, base.residuals[perm], equal_nan=True)
+
+
+def test_from_detections_to_a_finished_calibration():
+    """Config 1 geometry at small scale (3 cameras, 6 images, the cube target at visibility 0.2), 0.3 px noise, intrinsics jiggled as
+    ``rig.intr``: calc_initial_params -> set_initial_params -> device_solver.lm_solve ends with the cost of the solve started from the
+    rig's jiggled truth, to the solve's ftol.  No start vector comes from outside."""
+    from pycamset_amd import device_solver
+
+    rig = synthetic.config_rig(1, n_imgs=6)
+    td = TargetDetection([f"cam_{i}" for i in range(rig.n_cams)], rig.detections)
+
+    def solve(x0_of):
+        h = handlers.TemplateBundleHandler(DuckCamset(rig.n_cams), DuckTarget(rig.points), td)
+        x0 = x0_of(h)
+        h.set_initial_params(x0)
+        return device_solver.lm_solve(h, h.get_initial_params()), x0
+
+    seeded, x0 = solve(lambda h: h.calc_initial_params(rig.intr))
+    truth, _ = solve(lambda h: np.concatenate([rig.intr.ravel(), rig.extr.ravel(), rig.poses[1:].ravel()]))
+    assert x0.shape == (9 * 3 + 6 * 3 + 6 * 5,) and np.all(np.isfinite(x0))
+    print(f"cost from the seeded start {seeded.cost:.12e}, from the jiggled truth {truth.cost:.12e}")
+    assert abs(seeded.cost - truth.cost) <= 1e-8 * truth.cost
