@@ -14,11 +14,13 @@ The reference calls them with the detection table on every call (template_handle
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
 
-from .engine import Engine
+from . import _capi
+from .engine import Engine, _stream_arg
 
 _cache: dict = {}
 
@@ -97,27 +99,31 @@ class TriangulationResult:
     residuals: np.ndarray | None = None
 
 
-class Triangulator:
-    """Owner of one ``pcs_triangulator`` handle (include/pcs_hip.h): the camera table, device copies of the
-    observations, the kernel's scratch and the output live on the device across calls, so repeated
-    triangulations with the same cameras (``CameraSet.multi_cam_triangulate`` per set of frames,
-    cameras/camera_set.py:343-402) allocate nothing and — with device-resident inputs — copy nothing."""
+def _cached_handle(cache: dict, key, factory):
+    """One handle at a time per cache: a new key replaces the old handle."""
+    h = cache.get(key)
+    if h is None:
+        cache.clear()
+        h = cache[key] = factory()
+    return h
 
-    def __init__(self, n_cams: int, device: int = 0):
-        import ctypes
 
-        from . import _capi
+class _Handle:
+    """What the owners of a batched C-ABI handle share: creation and destruction through the named entry points, the call-and-check,
+    the ``last_*_ms`` getters and the ctypes pointer casts."""
+    _create = _destroy = ""
 
+    def __init__(self, device: int, *sizes: int):
         self._capi, self._ct = _capi, ctypes
         self._h = ctypes.c_void_p()
-        _capi.check(_capi.lib().pcs_tri_create(ctypes.byref(self._h), int(device), int(n_cams)))
-        self.n_cams, self.device, self.n_pts = int(n_cams), int(device), 0
-        self._cam_key = None
-        self._n_obs = 0
+        self._call(self._create, ctypes.byref(self._h), int(device), *(int(n) for n in sizes))
+
+    def _call(self, name: str, *args):
+        self._capi.check(getattr(self._capi.lib(), name)(*args))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
-            self._capi.lib().pcs_tri_destroy(self._h)
+            getattr(self._capi.lib(), self._destroy)(self._h)
             self._h = self._ct.c_void_p()
 
     def __del__(self):
@@ -125,6 +131,32 @@ class Triangulator:
             self.close()
         except Exception:
             pass
+
+    def _ms(self, getter: str) -> float:
+        ms = self._ct.c_float(0.0)
+        self._call(getter, self._h, self._ct.byref(ms))
+        return float(ms.value)
+
+    def _ptr(self, a):
+        return None if a is None else a.ctypes.data_as(self._ct.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+
+    def _addr(self, d):
+        return self._ct.c_void_p(d or 0)
+
+
+class Triangulator(_Handle):
+    """Owner of one ``pcs_triangulator`` handle (include/pcs_hip.h): the camera table, device copies of the
+    observations, the kernel's scratch and the output live on the device across calls, so repeated
+    triangulations with the same cameras (``CameraSet.multi_cam_triangulate`` per set of frames,
+    cameras/camera_set.py:343-402) allocate nothing and — with device-resident inputs — copy nothing."""
+
+    _create, _destroy = "pcs_tri_create", "pcs_tri_destroy"
+
+    def __init__(self, n_cams: int, device: int = 0):
+        super().__init__(device, n_cams)
+        self.n_cams, self.device, self.n_pts = int(n_cams), int(device), 0
+        self._cam_key = None
+        self._n_obs = 0
 
     def set_cameras(self, proj, intr, dist):
         P = np.ascontiguousarray(proj, dtype=np.float64)
@@ -134,8 +166,7 @@ class Triangulator:
             raise ValueError("expected proj (C,3,4), intr (C,3,3), dist (C,5)")
         key = hash(P.tobytes() + K.tobytes() + D.tobytes())
         if key != self._cam_key:   # the same cameras across calls: nothing to upload
-            dp = self._ct.POINTER(self._ct.c_double)
-            self._capi.check(self._capi.lib().pcs_tri_set_cameras(self._h, P.ctypes.data_as(dp), K.ctypes.data_as(dp), D.ctypes.data_as(dp)))
+            self._call("pcs_tri_set_cameras", self._h, self._ptr(P), self._ptr(K), self._ptr(D))
             self._cam_key = key
 
     def set_observations(self, cam, uv, start_inds):
@@ -143,18 +174,13 @@ class Triangulator:
         cam = np.ascontiguousarray(cam, dtype=np.int32)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         start = np.ascontiguousarray(start_inds, dtype=np.int64)
-        ct = self._ct
-        self._capi.check(self._capi.lib().pcs_tri_set_observations(
-            self._h, cam.shape[0], cam.ctypes.data_as(ct.POINTER(ct.c_int32)), uv.ctypes.data_as(ct.POINTER(ct.c_double)),
-            start.shape[0] - 1, start.ctypes.data_as(ct.POINTER(ct.c_int64))))
+        self._call("pcs_tri_set_observations", self._h, cam.shape[0], self._ptr(cam), self._ptr(uv), start.shape[0] - 1, self._ptr(start))
         self.n_pts = start.shape[0] - 1
         self._n_obs = cam.shape[0]
 
     def set_observations_device(self, n_obs: int, d_cam: int, d_uv: int, n_pts: int, d_start: int):
         """Raw device addresses (e.g. ``tensor.data_ptr()``) of int32 cam, float64 uv, int64 start_inds: used in place."""
-        ct = self._ct
-        self._capi.check(self._capi.lib().pcs_tri_set_observations_device(self._h, int(n_obs), ct.c_void_p(d_cam), ct.c_void_p(d_uv),
-                                                                          int(n_pts), ct.c_void_p(d_start)))
+        self._call("pcs_tri_set_observations_device", self._h, int(n_obs), self._addr(d_cam), self._addr(d_uv), int(n_pts), self._addr(d_start))
         self.n_pts = int(n_pts)
         self._n_obs = int(n_obs)
 
@@ -163,11 +189,10 @@ class Triangulator:
         camera indices, int32 dense feature ids (< ``n_features``) and float64 measurements of ``n`` table rows grouped by feature.
         -> (n_pts, n_kept, grouped); with ``grouped`` the handle's current observations are the rows of the features seen by at least
         two cameras (``run`` next); not grouped: nothing was set (group on the host: ``group_reconstructable``)."""
-        from .engine import _stream_arg
         ct = self._ct
         n_pts, n_kept, grouped = ct.c_int64(), ct.c_int64(), ct.c_int32()
-        self._capi.check(self._capi.lib().pcs_tri_group_device(self._h, int(n), ct.c_void_p(d_cam), ct.c_void_p(d_feat), ct.c_void_p(d_uv), int(n_features),
-                                                               ct.byref(n_pts), ct.byref(n_kept), ct.byref(grouped), _stream_arg(stream)))
+        self._call("pcs_tri_group_device", self._h, int(n), self._addr(d_cam), self._addr(d_feat), self._addr(d_uv), int(n_features),
+                   ct.byref(n_pts), ct.byref(n_kept), ct.byref(grouped), _stream_arg(stream))
         if grouped.value:
             self.n_pts = int(n_pts.value)
             self._n_obs = int(n_kept.value)
@@ -176,23 +201,19 @@ class Triangulator:
     def run(self, d_pts: int | None = None, stream: int | None = None):
         """Queue the kernel (asynchronous).  ``d_pts`` = device address of an (n_pts, 3) float64 buffer, or None for the
         handle-owned output (fetch it with ``points()``)."""
-        from .engine import _stream_arg
-        self._capi.check(self._capi.lib().pcs_tri_run(self._h, self._ct.c_void_p(d_pts or 0), _stream_arg(stream)))
+        self._call("pcs_tri_run", self._h, self._addr(d_pts), _stream_arg(stream))
 
     def synchronize(self, stream: int | None = None):
-        from .engine import _stream_arg
-        self._capi.check(self._capi.lib().pcs_tri_synchronize(self._h, _stream_arg(stream)))
+        self._call("pcs_tri_synchronize", self._h, _stream_arg(stream))
 
     def points(self) -> np.ndarray:
         pts = np.empty((max(self.n_pts, 0), 3))
         if self.n_pts > 0:
-            self._capi.check(self._capi.lib().pcs_tri_points(self._h, pts.ctypes.data_as(self._ct.POINTER(self._ct.c_double))))
+            self._call("pcs_tri_points", self._h, self._ptr(pts))
         return pts
 
     def last_kernel_ms(self) -> float:
-        ms = self._ct.c_float(0.0)
-        self._capi.check(self._capi.lib().pcs_tri_last_kernel_ms(self._h, self._ct.byref(ms)))
-        return float(ms.value)
+        return self._ms("pcs_tri_last_kernel_ms")
 
     def refine(self, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
                gtol: float = REFINE_DEFAULTS["gtol"], residuals: bool = False, d_pts: int | None = None, d_rms: int | None = None,
@@ -201,42 +222,31 @@ class Triangulator:
         pcs_tri_refine).  Device addresses: ``d_pts`` (n_pts, 3) float64, ``d_rms`` (n_pts, 2) float64 [rms, rms at the DLT point],
         ``d_info`` (n_pts, 3) int32 [trials, status, views], ``d_resid`` (n_obs, 2) float64 (with ``residuals``); None = handle-owned
         (fetch them with ``refined()``)."""
-        from .engine import _stream_arg
         max_iter, ftol, xtol, gtol = check_refine_options(max_iter, ftol, xtol, gtol)
-        vp = self._ct.c_void_p
-        self._capi.check(self._capi.lib().pcs_tri_refine(self._h, max_iter, ftol, xtol, gtol, self._capi.TRI_REFINE_RESIDUALS if residuals else 0,
-                                                         vp(d_pts or 0), vp(d_rms or 0), vp(d_info or 0), vp(d_resid or 0), _stream_arg(stream)))
+        self._call("pcs_tri_refine", self._h, max_iter, ftol, xtol, gtol, self._capi.TRI_REFINE_RESIDUALS if residuals else 0,
+                   self._addr(d_pts), self._addr(d_rms), self._addr(d_info), self._addr(d_resid), _stream_arg(stream))
         self._refined_residuals = bool(residuals) and not d_resid
 
     def refined(self, points_dlt: np.ndarray | None = None) -> "TriangulationResult":
         """Wait for the last ``refine`` and return its handle-owned outputs.  ``points_dlt``: the start points, when the run wrote
         them to a caller buffer (otherwise they are fetched from the handle)."""
-        ct, n = self._ct, max(self.n_pts, 0)
-        dp = ct.POINTER(ct.c_double)
+        n = max(self.n_pts, 0)
         pts, rms, info = np.empty((n, 3)), np.empty((n, 2)), np.empty((n, 3), dtype=np.int32)
         resid = np.empty((self._n_obs, 2)) if getattr(self, "_refined_residuals", False) else None
-        self._capi.check(self._capi.lib().pcs_tri_refined(self._h, pts.ctypes.data_as(dp), rms.ctypes.data_as(dp), info.ctypes.data_as(ct.POINTER(ct.c_int32)),
-                                                          resid.ctypes.data_as(dp) if resid is not None else None))
+        self._call("pcs_tri_refined", self._h, self._ptr(pts), self._ptr(rms), self._ptr(info), self._ptr(resid))
         start = self.points() if points_dlt is None else np.asarray(points_dlt, dtype=np.float64).reshape(n, 3)
         return TriangulationResult(points=pts, points_dlt=start, rms=rms[:, 0].copy(), rms_dlt=rms[:, 1].copy(), n_views=info[:, 2].copy(),
                                    iterations=info[:, 0].copy(), status=info[:, 1].copy(), residuals=resid)
 
     def last_refine_ms(self) -> float:
-        ms = self._ct.c_float(0.0)
-        self._capi.check(self._capi.lib().pcs_tri_last_refine_ms(self._h, self._ct.byref(ms)))
-        return float(ms.value)
+        return self._ms("pcs_tri_last_refine_ms")
 
 
 _tri_cache: dict = {}
 
 
 def _triangulator(device: int, n_cams: int) -> Triangulator:
-    key = (int(device), int(n_cams))
-    tri = _tri_cache.get(key)
-    if tri is None:
-        _tri_cache.clear()
-        tri = _tri_cache[key] = Triangulator(n_cams, device)
-    return tri
+    return _cached_handle(_tri_cache, (int(device), int(n_cams)), lambda: Triangulator(n_cams, device))
 
 
 def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0) -> np.ndarray:
@@ -407,84 +417,60 @@ class ViewPoses:
     residuals: np.ndarray | None = None
 
 
-class PoseEstimator:
+class PoseEstimator(_Handle):
     """Owner of one ``pcs_pose_estimator`` handle (include/pcs_hip.h): camera table, template, observation copies and outputs stay on
     the device across calls."""
 
+    _create, _destroy = "pcs_pnp_create", "pcs_pnp_destroy"
+
     def __init__(self, n_cams: int, n_keys: int, device: int = 0):
-        import ctypes
-
-        from . import _capi
-
-        self._capi, self._ct = _capi, ctypes
-        self._h = ctypes.c_void_p()
-        _capi.check(_capi.lib().pcs_pnp_create(ctypes.byref(self._h), int(device), int(n_cams), int(n_keys)))
+        super().__init__(device, n_cams, n_keys)
         self.n_cams, self.n_keys, self.device = int(n_cams), int(n_keys), int(device)
         self.n_views, self.n_obs = 0, 0
         self._residuals = False
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._capi.lib().pcs_pnp_destroy(self._h)
-            self._h = self._ct.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_cameras(self, intr):
         K = np.ascontiguousarray(intr, dtype=np.float64)
         if K.shape != (self.n_cams, 9):
             raise ValueError(f"expected intr ({self.n_cams}, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2]")
-        self._capi.check(self._capi.lib().pcs_pnp_set_cameras(self._h, K.ctypes.data_as(self._ct.POINTER(self._ct.c_double))))
+        self._call("pcs_pnp_set_cameras", self._h, self._ptr(K))
 
     def set_template(self, points):
         pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
         if pts.shape[0] != self.n_keys:
             raise ValueError(f"expected {self.n_keys} template points")
-        self._capi.check(self._capi.lib().pcs_pnp_set_template(self._h, pts.ctypes.data_as(self._ct.POINTER(self._ct.c_double))))
+        self._call("pcs_pnp_set_template", self._h, self._ptr(pts))
 
     def set_observations(self, key, uv, start_inds, view_cam):
         """Host arrays sorted by view: key (n_obs,) int, uv (n_obs, 2), start_inds (n_views + 1,), view_cam (n_views,) int."""
-        ct = self._ct
         key = np.ascontiguousarray(key, dtype=np.int32)
         uv = np.ascontiguousarray(uv, dtype=np.float64)
         start = np.ascontiguousarray(start_inds, dtype=np.int64)
         vcam = np.ascontiguousarray(view_cam, dtype=np.int32)
         if start.ndim != 1 or start.shape[0] < 1 or vcam.shape != (start.shape[0] - 1,) or uv.shape != (key.shape[0], 2):
             raise ValueError("expected key (n_obs,), uv (n_obs, 2), start_inds (n_views + 1,), view_cam (n_views,)")
-        self._capi.check(self._capi.lib().pcs_pnp_set_observations(
-            self._h, key.shape[0], key.ctypes.data_as(ct.POINTER(ct.c_int32)), uv.ctypes.data_as(ct.POINTER(ct.c_double)), start.shape[0] - 1,
-            start.ctypes.data_as(ct.POINTER(ct.c_int64)), vcam.ctypes.data_as(ct.POINTER(ct.c_int32))))
+        self._call("pcs_pnp_set_observations", self._h, key.shape[0], self._ptr(key), self._ptr(uv), start.shape[0] - 1, self._ptr(start), self._ptr(vcam))
         self.n_views, self.n_obs = start.shape[0] - 1, key.shape[0]
 
     def run(self, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
             gtol: float = REFINE_DEFAULTS["gtol"], min_points: int = 6, residuals: bool = False, stream: int | None = None):
         """Queue the start and LM kernels (asynchronous; handle-owned outputs, fetched with ``results()``)."""
-        from .engine import _stream_arg
         max_iter, ftol, xtol, gtol = check_refine_options(max_iter, ftol, xtol, gtol)
         min_points = check_min_points(min_points)
-        self._capi.check(self._capi.lib().pcs_pnp_run(self._h, max_iter, ftol, xtol, gtol, min_points, self._capi.PNP_RESIDUALS if residuals else 0,
-                                                      None, None, None, None, None, None, _stream_arg(stream)))
+        self._call("pcs_pnp_run", self._h, max_iter, ftol, xtol, gtol, min_points, self._capi.PNP_RESIDUALS if residuals else 0,
+                   None, None, None, None, None, None, _stream_arg(stream))
         self._residuals = bool(residuals)
 
     def results(self):
         """Wait for the last ``run``: (pose (n_views, 6), pose_init, pose_alt, rms (n_views, 2), info (n_views, 3) int32, residuals or None)."""
-        ct, n = self._ct, self.n_views
-        dp = ct.POINTER(ct.c_double)
+        n = self.n_views
         pose, init, alt, rms, info = np.empty((n, 6)), np.empty((n, 6)), np.empty((n, 6)), np.empty((n, 2)), np.empty((n, 3), dtype=np.int32)
         resid = np.empty((self.n_obs, 2)) if self._residuals else None
-        self._capi.check(self._capi.lib().pcs_pnp_results(self._h, pose.ctypes.data_as(dp), init.ctypes.data_as(dp), alt.ctypes.data_as(dp),
-                                                          rms.ctypes.data_as(dp), info.ctypes.data_as(ct.POINTER(ct.c_int32)),
-                                                          resid.ctypes.data_as(dp) if resid is not None else None))
+        self._call("pcs_pnp_results", self._h, self._ptr(pose), self._ptr(init), self._ptr(alt), self._ptr(rms), self._ptr(info), self._ptr(resid))
         return pose, init, alt, rms, info, resid
 
     def last_kernel_ms(self) -> float:
-        ms = self._ct.c_float(0.0)
-        self._capi.check(self._capi.lib().pcs_pnp_last_kernel_ms(self._h, self._ct.byref(ms)))
-        return float(ms.value)
+        return self._ms("pcs_pnp_last_kernel_ms")
 
 
 def check_min_points(min_points) -> int:
@@ -516,12 +502,7 @@ _pnp_cache: dict = {}
 
 
 def _pose_estimator(device: int, n_cams: int, n_keys: int) -> PoseEstimator:
-    key = (int(device), int(n_cams), int(n_keys))
-    est = _pnp_cache.get(key)
-    if est is None:
-        _pnp_cache.clear()
-        est = _pnp_cache[key] = PoseEstimator(n_cams, n_keys, device)
-    return est
+    return _cached_handle(_pnp_cache, (int(device), int(n_cams), int(n_keys)), lambda: PoseEstimator(n_cams, n_keys, device))
 
 
 def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_points: int = 6, max_iter: int = REFINE_DEFAULTS["max_iter"],

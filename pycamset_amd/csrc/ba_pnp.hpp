@@ -3,10 +3,8 @@
 // The first step of the reference's calc_initial_params: AbstractTarget.target_pose_in_cam_image (calibration_targets/abstract_target.py:345-405)
 // hands a view's detections of the known target and the camera's intrinsics to cv2.solvePnPGeneric and keeps the solution of lowest
 // error; estimate_camera_relative_poses (optimisation/template_handler.py:468-601) does so for every camera and image.  Here every view is
-// one group of G lanes, as triangulate_refine_kernel (ba_tri_refine.hpp) gives every point one: lane g owns observations g, g + G, ...,
-// group sums are xor-butterfly shuffles (every lane of a group holds identical bits and takes identical branches), the small dense
-// solves run redundantly in every lane.  No atomics; a view's result does not depend on its wave neighbours.  Two kernels, so that the
-// registers of the 11 x 11 start do not set the occupancy of the LM passes:
+// one group of G lanes; what such a group guarantees is in DESIGN.md, "Batched handles".  Two kernels, so that the registers of the
+// 11 x 11 start do not set the occupancy of the LM passes:
 //
 // pnp_start_kernel — the linear start, no prior needed (after OpenCV's iterative PnP):
 //   (a) measurements to normalised image coordinates with the triangulation's five fixed-point steps (undistort5_fast);
@@ -25,10 +23,9 @@
 // pnp_lm_kernel — (c) Levenberg-Marquardt on the MEASURED pixels, full Brown-Conrady model, from the start and (planar views, when
 //   at least one trial is allowed) from the second pose; the lower final cost is kept — the reference's argmin over solvePnPGeneric's
 //   solutions.  Parameters (d omega, d t) of R <- exp([d omega]x) R, t <- t + d t: d X_cam = -[R X]x d omega + d t.  One pass per trial
-//   accumulates 21 + 6 + 2 sums (H = J'J, g = J'r, cost, points with depth <= 0 or non-finite).  Damping, accept and stop rules are
-//   those of triangulate_refine_kernel (lambda0 1e-4, x10 on reject, x0.1 on accept, limits 1e10 / 1e-15; accept only a lower cost with
-//   every point in front; ftol, xtol — the step against the Frobenius size of [R | t] — and gtol).  The first V observations of a
-//   lane (measurement, key, template point) stay in registers, further ones are re-read in every pass (L2-resident).
+//   accumulates 21 + 6 + 2 sums (H = J'J, g = J'r, cost, points with depth <= 0 or non-finite).  Damping, accept and stop rules:
+//   DESIGN.md; xtol measures the step against the Frobenius size of [R | t].  The first V observations of a lane (measurement, key,
+//   template point) stay in registers, further ones are re-read in every pass (L2-resident).
 //   A pose that no accepted trial moved is returned with the bits of its start.
 #pragma once
 #include <hip/hip_runtime.h>

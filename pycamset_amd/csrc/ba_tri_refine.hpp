@@ -11,11 +11,9 @@
 // Layout as in triangulate_reg_kernel: G lanes per point, lane g owns views g, g + G, ...; the measurement and camera index of its
 // first V views stay in registers, further views are re-read from global memory (L2-resident) in every pass; camera rows come from
 // the 256-B table (L1-resident).  One pass per LM trial evaluates r and the 2 x 3 Jacobian at the candidate point and accumulates
-// 11 sums (6 of H = J'J, 3 of g = J'r, the cost, the number of views with depth h2 <= 0 or a non-finite value).  The group sums are
-// xor-butterfly shuffles: IEEE addition is commutative, so every lane of a group holds identical sums and takes identical
-// accept / stop branches, and the damped 3 x 3 system is solved redundantly in every lane (LDL', positive-definiteness checked).
-// An accepted trial's H and g are already summed: a trial costs one pass.  No atomics; a point's result does not depend on its wave
-// neighbours (converged groups are frozen; absent views add nothing).
+// 11 sums (6 of H = J'J, 3 of g = J'r, the cost, the number of views with depth h2 <= 0 or a non-finite value); the damped 3 x 3
+// system is an LDL' solve with positive-definiteness checked.  An accepted trial's H and g are already summed: a trial costs one pass.
+// What a group of lanes guarantees, and the damping, accept and stop rules shared with pnp_lm_kernel: DESIGN.md, "Batched handles".
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -7,19 +7,21 @@
 //
 // Kernels: ba_kernels.hpp (evaluation, compaction, legacy cost), ba_matfree.hpp (J products without J),
 // ba_normal.hpp (J^T J / J^T r), ba_triangulate.hpp; device maths: ba_device.hpp.  This file: the pcs_engine handle + its part of the C ABI; one translation unit with
-// pcs_common.inc (errors, device queries), pcs_triangulator.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
+// pcs_common.inc (errors, device queries), pcs_handle.inc (what the batched handles share), pcs_triangulator.inc, pcs_pnp.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <atomic>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -44,6 +46,7 @@
 using namespace pcs;
 
 #include "pcs_common.inc"
+#include "pcs_handle.inc"
 #include "pcs_triangulator.inc"
 #include "pcs_pnp.inc"
 #include "pcs_solver.inc"
@@ -176,6 +179,7 @@ struct pcs_engine {
 // queued on the engine's own stream or on the default stream (handles that outlive every call) mark_done only notes the
 // stream; the record happens when somebody needs to wait — it then covers everything queued on that stream so far, a
 // superset.  Work on any other caller stream is recorded at once: that stream may be destroyed before the next call.
+// (The batched handles record after every run: RunFence in pcs_handle.inc.)
 static hipError_t flush_done(pcs_engine *h) {
     if (!h->done_pending) return hipSuccess;
     h->done_pending = false;

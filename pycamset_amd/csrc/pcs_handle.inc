@@ -1,0 +1,196 @@
+// pcs_handle.inc — what the batched handles (pcs_triangulator.inc, pcs_pnp.inc) share; included after pcs_common.inc.  Plain structs and
+// free functions; what they guarantee is in DESIGN.md, "Batched handles".
+
+// One growable device buffer: a pointer and its capacity in elements.
+struct DevBuf {
+    void *p = nullptr;
+    int64_t cap = 0;
+    template <class T> T *as() const { return static_cast<T *>(p); }
+    bool grows(int64_t need) const { return need > cap; }
+    hipError_t alloc(int64_t need, size_t elem_bytes) {   // an EMPTY buffer only; it stays empty on failure (create: the caller words the error)
+        const hipError_t e = hipMalloc(&p, elem_bytes * (size_t)need);
+        if (e == hipSuccess) cap = need;
+        return e;
+    }
+    int grow(int64_t need, size_t elem_bytes) {   // free, then malloc: the contents are not kept
+        if (!grows(need)) return PCS_OK;
+        if (p) HIPCHK(hipFree(p));
+        p = nullptr, cap = 0;
+        HIPCHK(alloc(need, elem_bytes));
+        return PCS_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr, cap = 0;
+    }
+};
+
+// Ordering of a handle's runs across streams: `done` is recorded after every run; whatever touches what a run reads or writes next
+// waits for it first.  (pcs_engine.hip's flush_done / mark_done are the lazily recording variant of this for the engine.)
+struct RunFence {
+    hipEvent_t done = nullptr;
+    hipStream_t done_stream = nullptr;   // compared only, never used as a handle again
+    bool have_done = false;
+    hipError_t create() { return hipEventCreateWithFlags(&done, hipEventDisableTiming); }
+    void destroy() {
+        if (done) (void)hipEventDestroy(done);
+        done = nullptr, have_done = false;
+    }
+    hipError_t wait_host() const { return have_done ? hipEventSynchronize(done) : hipSuccess; }
+    // Scratch and outputs are shared between runs, so the previous run finishes first.  A call that grows a buffer frees one, and a free
+    // needs the host to wait; hipStreamWaitEvent on the legacy stream is avoided, so there the host waits as well.  Another stream waits
+    // for the event; the same stream is ordered already.
+    hipError_t before_run(hipStream_t s, bool grows) const {
+        if (!have_done) return hipSuccess;
+        if (grows || s == hipStreamLegacy || done_stream == hipStreamLegacy) return hipEventSynchronize(done);
+        return s != done_stream ? hipStreamWaitEvent(s, done, 0) : hipSuccess;
+    }
+    hipError_t after_run(hipStream_t s) {
+        have_done = true, done_stream = s;
+        return hipEventRecord(done, s);
+    }
+};
+
+// Device time of the last run: two events and whether they were ever recorded.
+struct KernelTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    bool timed = false;
+    hipError_t create() {
+        const hipError_t e = hipEventCreate(&e0);
+        return e == hipSuccess ? hipEventCreate(&e1) : e;
+    }
+    void destroy() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        e0 = e1 = nullptr;
+    }
+};
+
+static int timer_ms(const char *who, KernelTimer *t, float *kernel_ms, const char *nothing_yet) {
+    if (!t || !kernel_ms) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (!t->timed) return fail(PCS_ERR_STATE, "%s: %s", who, nothing_yet);
+    HIPCHK(hipEventSynchronize(t->e1));
+    HIPCHK(hipEventElapsedTime(kernel_ms, t->e0, t->e1));
+    return PCS_OK;
+}
+
+// The device, the handle's own stream and the fence of its runs.
+struct HandleCore {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    RunFence fence;
+    hipError_t create(int dev) {
+        device = dev;
+        const hipError_t e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+        return e == hipSuccess ? fence.create() : e;
+    }
+    // a run queued on ANY stream may still read what the caller is about to overwrite, free or fetch
+    hipError_t quiesce() const {
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = fence.wait_host();
+        if (e == hipSuccess && stream) e = hipStreamSynchronize(stream);
+        return e;
+    }
+    hipStream_t stream_or(void *caller) const { return caller ? (hipStream_t)caller : stream; }
+    void destroy(std::initializer_list<DevBuf *> bufs, std::initializer_list<KernelTimer *> timers) {
+        (void)quiesce();
+        for (DevBuf *b : bufs) b->release();
+        for (KernelTimer *t : timers) t->destroy();
+        fence.destroy();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+static int open_device(const char *who, int device) {
+    const int ndev = pcs_device_count();
+    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "%s: no HIP device visible (no CPU fallback)", who);
+    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "%s: device out of range", who);
+    HIPCHK(hipSetDevice(device));
+    return PCS_OK;
+}
+
+// `rest_ok` / `rest`: the caller's own options and their wording, so that one message names every constraint
+static int check_lm_options(const char *who, int max_iter, double ftol, double xtol, double gtol, bool rest_ok, const char *rest) {
+    if (!rest_ok || max_iter < 0 || !(ftol >= 0.0 && ftol < INFINITY) || !(xtol >= 0.0 && xtol < INFINITY) || !(gtol >= 0.0 && gtol < INFINITY))
+        return fail(PCS_ERR_ARG, "%s: bad options (max_iter >= 0, finite tolerances >= 0, %s)", who, rest);
+    return PCS_OK;
+}
+
+// Host arrays copied into handle-owned buffers (set_observations): every allocation first, then the copies on the handle's stream, then
+// a wait, so that the caller may reuse its arrays.  A buffer is never empty: at least one element is allocated.
+struct HostArray {
+    DevBuf &buf;
+    const void *src;
+    int64_t count;
+    size_t elem_bytes;
+};
+
+static int upload_host_arrays(const HandleCore &c, const HostArray *a, int n) {
+    for (int i = 0; i < n; ++i)
+        if (const int rc = a[i].buf.grow(std::max<int64_t>(1, a[i].count), a[i].elem_bytes)) return rc;
+    for (int i = 0; i < n; ++i)
+        if (a[i].count) HIPCHK(hipMemcpyAsync(a[i].buf.p, a[i].src, a[i].elem_bytes * (size_t)a[i].count, hipMemcpyHostToDevice, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream));
+    return PCS_OK;
+}
+
+// One output of a run: it goes to the caller's device buffer or, when the caller passed none, to a handle-owned one (PCS_*_OUT_* bit
+// set in `owned`).  Fetching uses the same slot with `ptr` the caller's HOST array.
+struct OutSlot {
+    int bit;
+    DevBuf &buf;
+    void *ptr;       // run: in, the caller's device buffer or NULL; after grow_owned_slots, where the run writes.  fetch: the host array or NULL
+    int64_t count;   // elements the run writes / the fetch copies (at least one is allocated)
+    size_t elem_bytes;
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+};
+
+static int owned_slots(const OutSlot *sl, int n, bool *grows) {
+    int owned = 0;
+    for (int i = 0; i < n; ++i)
+        if (!sl[i].ptr) {
+            owned |= sl[i].bit;
+            *grows = *grows || sl[i].buf.grows(sl[i].count);   // the one element of an empty output replaces nothing: no wait for it
+        }
+    return owned;
+}
+
+// after the fence, before the first enqueue: nothing is queued by a call that fails in an allocation
+static int grow_owned_slots(OutSlot *sl, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!sl[i].ptr) {
+            if (const int rc = sl[i].buf.grow(std::max<int64_t>(1, sl[i].count), sl[i].elem_bytes)) return rc;
+            sl[i].ptr = sl[i].buf.p;
+        }
+    return PCS_OK;
+}
+
+// The handle-owned outputs of the last run to the host arrays of the slots that have one; refused when the run wrote one of them
+// elsewhere.  `ran`: false for an empty problem, which has nothing to copy.
+static int fetch_slots(const HandleCore &c, const OutSlot *sl, int n, int owned, bool ran, const char *who, const char *refusal) {
+    int want = 0;
+    for (int i = 0; i < n; ++i) want |= sl[i].ptr ? sl[i].bit : 0;
+    if (want & ~owned) return fail(PCS_ERR_STATE, "%s: %s", who, refusal);
+    if (!ran) return PCS_OK;
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(c.fence.wait_host());   // the run may have been queued on a caller stream
+    for (int i = 0; i < n; ++i)
+        if (sl[i].ptr && sl[i].count)
+            HIPCHK(hipMemcpyAsync(sl[i].ptr, sl[i].buf.p, sl[i].elem_bytes * (size_t)sl[i].count, hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipStreamSynchronize(c.stream));
+    return PCS_OK;
+}
+
+// The visiting order of n groups given by their start indices: groups of like size side by side, so that a wave does not mix small and
+// large ones (counts above 255 share a bucket).  d_hist: 512 int32; queued on the run's own stream (the start indices may have been
+// produced there).
+constexpr int64_t GROUP_ORDER_HIST = 512;
+static int enqueue_group_order(const int64_t *d_start, int64_t n, int32_t *d_hist, int32_t *d_order, hipStream_t s) {
+    HIPCHK(hipMemsetAsync(d_hist, 0, sizeof(int32_t) * GROUP_ORDER_HIST, s));
+    const dim3 pg((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(tri_order_count_kernel, pg, dim3(256), 0, s, d_start, n, d_hist);
+    hipLaunchKernelGGL(tri_order_scan_kernel, dim3(1), dim3(256), 0, s, d_hist);
+    hipLaunchKernelGGL(tri_order_scatter_kernel, pg, dim3(256), 0, s, d_start, n, d_hist, d_order);
+    HIPCHK(hipGetLastError());
+    return PCS_OK;
+}

@@ -1,72 +1,39 @@
 // pcs_triangulator.inc — host side of the batched triangulation (included by pcs_engine.hip; kernels: ba_triangulate.hpp, ba_tri_refine.hpp).
+// Fence, buffers and output slots are those of pcs_handle.inc (DESIGN.md, "Batched handles").
 extern "C" {
 // ---- batched triangulation (SURVEY f4): a handle that owns the camera table, the observation buffers and the
 // kernel's scratch, so that repeated calls (CameraSet.multi_cam_triangulate per frame set, cameras/camera_set.py:343-402)
 // pay neither allocations nor — with device-resident inputs — copies.
 struct pcs_triangulator {
-    int device = 0;
+    HandleCore core;
+    KernelTimer timer, refine_timer;
     int64_t n_cams = 0;
     bool have_cams = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool timed = false;
-    double *d_tab = nullptr;
-    // handle-owned copies of host inputs (grown on demand)
-    int32_t *d_cam = nullptr; double *d_uv = nullptr; int64_t *d_start = nullptr;
-    int64_t obs_capacity = 0, uv_capacity = 0, pts_capacity = 0;
-    // scratch + default output
-    void *d_scr = nullptr, *d_scl = nullptr; double *d_pts = nullptr;
-    int64_t scr_capacity = 0, scl_capacity = 0, out_capacity = 0;
+    DevBuf tab;                // camera table
+    DevBuf cam, uv, start;     // handle-owned copies of host inputs (grown on demand)
+    DevBuf scr, scl, pts;      // scratch (Householder row r_i; (1 / E_i, lambda_i) per observation) + default output
     // current problem (device pointers: handle-owned or the caller's)
     const int32_t *cur_cam = nullptr; const double *cur_uv = nullptr; const int64_t *cur_start = nullptr;
     int64_t n_obs = 0, n_pts = -1;
-    // the grouping in front of the triangulation (pcs_tri_group_device): per-feature counts, block sums of the scan, totals
-    int32_t *d_count = nullptr; uint64_t *d_block_sums = nullptr; int64_t *d_totals = nullptr;
-    int64_t count_capacity = 0, block_capacity = 0;
-    int32_t *d_order = nullptr, *d_hist = nullptr;   // points by view count (built by the first run of a set of observations)
-    int64_t order_capacity = 0;
+    DevBuf count, block_sums, totals;   // the grouping in front of the triangulation (pcs_tri_group_device): per-feature counts, block sums of the scan, totals
+    DevBuf order, hist;                 // points by view count (enqueue_group_order), built by the first run of a set of observations
     bool order_valid = false, sort_points = true;
     int variant = 1; // 1: views in registers + divide-free rotations (round 4; 3: eight instead of six register views per lane); 0: round 3's kernel (PCS_TRI_VARIANT=0)
     int lanes = 4;   // lanes per point: 1, 2, 4, 8 or 16 (profiles/r01/tri_legacy_bench.log: 4 is fastest at 2-22 views)
-    // Ordering across streams, as in pcs_engine: `done` is recorded after every run; whatever touches the camera table, the
-    // handle-owned observation copies, the scratch or the output next first waits for it — on the host where the host
-    // writes or reads, with hipStreamWaitEvent where a run moves to another stream (scratch and output are shared).
-    hipEvent_t done = nullptr;
-    hipStream_t done_stream = nullptr;
-    bool have_done = false;
     bool out_owned = false;   // the last run wrote the handle-owned output (pcs_tri_points has something to return)
     // the refinement (pcs_tri_refine): it starts from the points of the last run on the current cameras and observations
     bool run_valid = false;          // a run since the cameras / observations were last set
     const double *run_pts = nullptr; // where that run wrote its points (handle-owned or the caller's buffer)
-    double *d_rpts = nullptr, *d_rrms = nullptr, *d_rres = nullptr; int32_t *d_rinfo = nullptr;   // handle-owned refinement outputs
-    int64_t rpts_capacity = 0, rrms_capacity = 0, rres_capacity = 0, rinfo_capacity = 0;
+    DevBuf rpts, rrms, rres, rinfo;  // handle-owned refinement outputs
     int refine_owned = 0;            // PCS_TRI_OUT_* bits: which outputs of the last refinement are handle-owned
     bool refine_valid = false;       // a refinement since the last run (pcs_tri_refined has something to return)
-    hipEvent_t r0 = nullptr, r1 = nullptr;
-    bool refine_timed = false;
 };
-
-static hipError_t tri_wait_done_host(pcs_triangulator *t) { return t->have_done ? hipEventSynchronize(t->done) : hipSuccess; }
-
-static int tri_grow(void **buf, int64_t *cap, int64_t need, size_t elem) {
-    if (need <= *cap) return PCS_OK;
-    if (*buf) HIPCHK(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    HIPCHK(hipMalloc(buf, elem * (size_t)need));
-    *cap = need;
-    return PCS_OK;
-}
 
 int pcs_tri_create(pcs_triangulator **out, int device, int64_t n_cams) {
     if (!out || n_cams <= 0) return fail(PCS_ERR_ARG, "pcs_tri_create: bad arguments");
     *out = nullptr;
-    const int ndev = pcs_device_count();
-    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "pcs_tri_create: no HIP device visible (no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "pcs_tri_create: device out of range");
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = open_device("pcs_tri_create", device)) return rc;
     pcs_triangulator *t = new pcs_triangulator();
-    t->device = device;
     t->n_cams = n_cams;
     const char *lanes_env = getenv("PCS_TRI_LANES");   // A/B switch
     const int lanes = lanes_env ? atoi(lanes_env) : 4;
@@ -74,13 +41,12 @@ int pcs_tri_create(pcs_triangulator **out, int device, int64_t n_cams) {
     const char *var_env = getenv("PCS_TRI_VARIANT");
     t->variant = var_env ? atoi(var_env) : 1;
     t->sort_points = getenv("PCS_TRI_NO_SORT") == nullptr;   // A/B switch
-    hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&t->e0);
-    if (e == hipSuccess) e = hipEventCreate(&t->e1);
-    if (e == hipSuccess) e = hipEventCreate(&t->r0);
-    if (e == hipSuccess) e = hipEventCreate(&t->r1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&t->done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc(&t->d_tab, sizeof(double) * n_cams * TRI_CAM_STRIDE);
+    hipError_t e = t->core.create(device);
+    if (e == hipSuccess) e = t->timer.create();
+    if (e == hipSuccess) e = t->refine_timer.create();
+    if (e == hipSuccess) e = t->tab.alloc(n_cams * TRI_CAM_STRIDE, sizeof(double));
+    if (e == hipSuccess) e = t->hist.alloc(GROUP_ORDER_HIST, sizeof(int32_t));
+    if (e == hipSuccess) e = t->totals.alloc(4, sizeof(int64_t));
     if (e != hipSuccess) {
         const int rc = fail(PCS_ERR_HIP, "pcs_tri_create: %s", hipGetErrorString(e));
         pcs_tri_destroy(t);
@@ -92,21 +58,24 @@ int pcs_tri_create(pcs_triangulator **out, int device, int64_t n_cams) {
 
 int pcs_tri_destroy(pcs_triangulator *t) {
     if (!t) return PCS_OK;
-    (void)hipSetDevice(t->device);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    (void)tri_wait_done_host(t);   // a run on a caller stream may still read the tables
-    for (void *b : {(void *)t->d_tab, (void *)t->d_cam, (void *)t->d_uv, (void *)t->d_start, t->d_scr, t->d_scl, (void *)t->d_pts, (void *)t->d_order, (void *)t->d_hist,
-                    (void *)t->d_count, (void *)t->d_block_sums, (void *)t->d_totals, (void *)t->d_rpts, (void *)t->d_rrms, (void *)t->d_rres,
-                    (void *)t->d_rinfo})
-        if (b) (void)hipFree(b);
-    if (t->e0) (void)hipEventDestroy(t->e0);
-    if (t->e1) (void)hipEventDestroy(t->e1);
-    if (t->r0) (void)hipEventDestroy(t->r0);
-    if (t->r1) (void)hipEventDestroy(t->r1);
-    if (t->done) (void)hipEventDestroy(t->done);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
+    t->core.destroy({&t->tab, &t->cam, &t->uv, &t->start, &t->scr, &t->scl, &t->pts, &t->count, &t->block_sums, &t->totals, &t->order, &t->hist, &t->rpts,
+                     &t->rrms, &t->rres, &t->rinfo},
+                    {&t->timer, &t->refine_timer});
     delete t;
     return PCS_OK;
+}
+
+// a new set of observations (handle-owned copies or the caller's device arrays): results of an earlier problem are not this problem's,
+// and a refinement must start from points of these observations
+static void tri_new_problem(pcs_triangulator *t, const int32_t *d_cam, const double *d_uv, const int64_t *d_start, int64_t n_obs, int64_t n_pts) {
+    t->cur_cam = d_cam; t->cur_uv = d_uv; t->cur_start = d_start;
+    t->n_obs = n_obs; t->n_pts = n_pts;
+    t->order_valid = false;
+    t->out_owned = false;
+    t->run_valid = t->refine_valid = false;
+}
+static void tri_own_problem(pcs_triangulator *t, int64_t n_obs, int64_t n_pts) {
+    tri_new_problem(t, t->cam.as<int32_t>(), t->uv.as<double>(), t->start.as<int64_t>(), n_obs, n_pts);
 }
 
 int pcs_tri_set_cameras(pcs_triangulator *t, const double *proj, const double *intrinsics, const double *dists) {
@@ -119,10 +88,8 @@ int pcs_tri_set_cameras(pcs_triangulator *t, const double *proj, const double *i
         r[22] = K[0]; r[23] = K[2]; r[24] = K[4]; r[25] = K[5];
         for (int k = 0; k < 5; ++k) r[26 + k] = dists[5 * c + k];
     }
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // a run queued on ANY stream may still read the table
-    HIPCHK(hipStreamSynchronize(t->stream));
-    HIPCHK(hipMemcpy(t->d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    HIPCHK(t->core.quiesce());
+    HIPCHK(hipMemcpy(t->tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
     t->have_cams = true;
     t->run_valid = t->refine_valid = false;   // a refinement must start from points of these cameras
     return PCS_OK;
@@ -135,37 +102,17 @@ int pcs_tri_set_observations(pcs_triangulator *t, int64_t n_obs, const int32_t *
         if (start_inds[j + 1] < start_inds[j]) return fail(PCS_ERR_ARG, "pcs_tri_set_observations: start_inds must be non-decreasing");
     for (int64_t r = 0; r < n_obs; ++r)
         if (cam[r] < 0 || cam[r] >= t->n_cams) return fail(PCS_ERR_RANGE, "observation %lld has camera %d outside [0,%lld)", (long long)r, cam[r], (long long)t->n_cams);
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // a run queued on ANY stream may still read the observation copies
-    HIPCHK(hipStreamSynchronize(t->stream));
+    HIPCHK(t->core.quiesce());
     t->n_pts = -1;
-    int rc = tri_grow((void **)&t->d_cam, &t->obs_capacity, std::max<int64_t>(1, n_obs), sizeof(int32_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_uv, &t->uv_capacity, std::max<int64_t>(1, n_obs), 2 * sizeof(double));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_start, &t->pts_capacity, n_pts + 1, sizeof(int64_t));
-    if (rc) return rc;
-    if (n_obs) {
-        HIPCHK(hipMemcpyAsync(t->d_cam, cam, sizeof(int32_t) * n_obs, hipMemcpyHostToDevice, t->stream));
-        HIPCHK(hipMemcpyAsync(t->d_uv, uv, sizeof(double) * 2 * n_obs, hipMemcpyHostToDevice, t->stream));
-    }
-    HIPCHK(hipMemcpyAsync(t->d_start, start_inds, sizeof(int64_t) * (n_pts + 1), hipMemcpyHostToDevice, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));   // the caller may reuse its host arrays
-    t->cur_cam = t->d_cam; t->cur_uv = t->d_uv; t->cur_start = t->d_start;
-    t->n_obs = n_obs; t->n_pts = n_pts;
-    t->order_valid = false;
-    t->out_owned = false;   // results of an earlier problem are not this problem's
-    t->run_valid = t->refine_valid = false;
+    const HostArray arrays[] = {{t->cam, cam, n_obs, sizeof(int32_t)}, {t->uv, uv, n_obs, 2 * sizeof(double)}, {t->start, start_inds, n_pts + 1, sizeof(int64_t)}};
+    if (const int rc = upload_host_arrays(t->core, arrays, 3)) return rc;
+    tri_own_problem(t, n_obs, n_pts);
     return PCS_OK;
 }
 
 int pcs_tri_set_observations_device(pcs_triangulator *t, int64_t n_obs, const int32_t *d_cam, const double *d_uv, int64_t n_pts, const int64_t *d_start_inds) {
     if (!t || n_obs < 0 || n_pts < 0 || !d_start_inds || (n_obs > 0 && (!d_cam || !d_uv))) return fail(PCS_ERR_ARG, "pcs_tri_set_observations_device: bad arguments");
-    t->cur_cam = d_cam; t->cur_uv = d_uv; t->cur_start = d_start_inds;   // caller-owned, not range-checked (stay on the device)
-    t->n_obs = n_obs; t->n_pts = n_pts;
-    t->order_valid = false;
-    t->out_owned = false;
-    t->run_valid = t->refine_valid = false;
+    tri_new_problem(t, d_cam, d_uv, d_start_inds, n_obs, n_pts);   // caller-owned, not range-checked (stay on the device)
     return PCS_OK;
 }
 
@@ -180,47 +127,38 @@ int pcs_tri_group_device(pcs_triangulator *t, int64_t n, const int32_t *d_cam, c
         return fail(PCS_ERR_ARG, "pcs_tri_group_device: bad arguments");
     *n_pts = *n_kept = 0;
     *grouped = 1;
-    HIPCHK(hipSetDevice(t->device));
-    hipStream_t s = stream ? (hipStream_t)stream : t->stream;
-    HIPCHK(tri_wait_done_host(t));   // a run queued on ANY stream may still read the observation copies this call overwrites
-    HIPCHK(hipStreamSynchronize(t->stream));
+    hipStream_t s = t->core.stream_or(stream);
+    HIPCHK(t->core.quiesce());   // a run queued on ANY stream may still read the observation copies this call overwrites
     t->n_pts = -1;
     t->run_valid = t->refine_valid = false;
+    int rc;
     if (n == 0) {
-        int rc0 = tri_grow((void **)&t->d_start, &t->pts_capacity, 1, sizeof(int64_t));
-        if (rc0) return rc0;
-        HIPCHK(hipMemsetAsync(t->d_start, 0, sizeof(int64_t), s));
+        if ((rc = t->start.grow(1, sizeof(int64_t)))) return rc;
+        HIPCHK(hipMemsetAsync(t->start.p, 0, sizeof(int64_t), s));
         HIPCHK(hipStreamSynchronize(s));
-        t->cur_cam = t->d_cam; t->cur_uv = t->d_uv; t->cur_start = t->d_start;
-        t->n_obs = 0; t->n_pts = 0; t->order_valid = false; t->out_owned = false;
+        tri_own_problem(t, 0, 0);
         return PCS_OK;
     }
     const int64_t n_blocks = (n + TRI_GROUP_BLOCK - 1) / TRI_GROUP_BLOCK;
-    int rc = tri_grow((void **)&t->d_cam, &t->obs_capacity, n, sizeof(int32_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_uv, &t->uv_capacity, n, 2 * sizeof(double));
-    if (rc) return rc;
+    if ((rc = t->cam.grow(n, sizeof(int32_t)))) return rc;
+    if ((rc = t->uv.grow(n, 2 * sizeof(double)))) return rc;
     // one entry per kept run + 1.  A GROUPED table has at most n / 2 kept runs, but whether it is grouped is only known afterwards: in a table
     // whose features interleave every row can be the head of a kept run (writes up to start[n]; sized for n / 2 + 2 until this was found
     // by a fault in the full test suite — alone, the overrun stayed inside the allocation)
-    rc = tri_grow((void **)&t->d_start, &t->pts_capacity, n + 2, sizeof(int64_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_count, &t->count_capacity, n_features, sizeof(int32_t));
-    if (rc) return rc;
-    rc = tri_grow((void **)&t->d_block_sums, &t->block_capacity, n_blocks, sizeof(uint64_t));
-    if (rc) return rc;
-    if (!t->d_totals) HIPCHK(hipMalloc(&t->d_totals, sizeof(int64_t) * 4));
-    HIPCHK(hipMemsetAsync(t->d_count, 0, sizeof(int32_t) * n_features, s));
-    HIPCHK(hipMemsetAsync(t->d_totals, 0, sizeof(int64_t) * 4, s));
-    TriGroupArgs a{d_cam, d_feat, reinterpret_cast<const double2 *>(d_uv), t->d_count, t->d_block_sums, t->d_totals, t->d_cam,
-                   reinterpret_cast<double2 *>(t->d_uv), t->d_start, n, n_features, (int32_t)n_blocks};
+    if ((rc = t->start.grow(n + 2, sizeof(int64_t)))) return rc;
+    if ((rc = t->count.grow(n_features, sizeof(int32_t)))) return rc;
+    if ((rc = t->block_sums.grow(n_blocks, sizeof(uint64_t)))) return rc;
+    HIPCHK(hipMemsetAsync(t->count.p, 0, sizeof(int32_t) * n_features, s));
+    HIPCHK(hipMemsetAsync(t->totals.p, 0, sizeof(int64_t) * 4, s));
+    TriGroupArgs a{d_cam, d_feat, reinterpret_cast<const double2 *>(d_uv), t->count.as<int32_t>(), t->block_sums.as<uint64_t>(), t->totals.as<int64_t>(),
+                   t->cam.as<int32_t>(), t->uv.as<double2>(), t->start.as<int64_t>(), n, n_features, (int32_t)n_blocks};
     hipLaunchKernelGGL(tri_group_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(tri_group_blocksum_kernel, dim3((unsigned)n_blocks), dim3(TRI_GROUP_BLOCK), 0, s, a);
     hipLaunchKernelGGL(tri_group_scan_sums_kernel, dim3(1), dim3(TRI_GROUP_BLOCK), 0, s, a);
     hipLaunchKernelGGL(tri_group_scatter_kernel, dim3((unsigned)n_blocks), dim3(TRI_GROUP_BLOCK), 0, s, a);
     HIPCHK(hipGetLastError());
     int64_t totals[4];
-    HIPCHK(hipMemcpyAsync(totals, t->d_totals, sizeof totals, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(totals, t->totals.p, sizeof totals, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (totals[2] != totals[3]) {   // more runs than features: some feature's rows are not consecutive
         *grouped = 0;
@@ -228,10 +166,7 @@ int pcs_tri_group_device(pcs_triangulator *t, int64_t n, const int32_t *d_cam, c
     }
     *n_kept = totals[0];
     *n_pts = totals[1];
-    t->cur_cam = t->d_cam; t->cur_uv = t->d_uv; t->cur_start = t->d_start;
-    t->n_obs = totals[0]; t->n_pts = totals[1];
-    t->order_valid = false;
-    t->out_owned = false;
+    tri_own_problem(t, totals[0], totals[1]);
     return PCS_OK;
 }
 
@@ -245,45 +180,33 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
         t->run_pts = d_pts;
         return PCS_OK;
     }
-    HIPCHK(hipSetDevice(t->device));
-    hipStream_t s = stream ? (hipStream_t)stream : t->stream;
+    HIPCHK(hipSetDevice(t->core.device));
+    hipStream_t s = t->core.stream_or(stream);
     const bool need_order = t->variant != 0 && t->sort_points && !t->order_valid && t->n_pts < (1ll << 31);
-    const bool grows = t->n_obs > t->scr_capacity || t->n_obs > t->scl_capacity || (!d_pts && t->n_pts > t->out_capacity) || (need_order && t->n_pts > t->order_capacity);
-    if (t->have_done) {   // scratch and output are shared between runs: the previous one finishes first
-        if (grows || s == hipStreamLegacy || t->done_stream == hipStreamLegacy) HIPCHK(hipEventSynchronize(t->done));   // frees need the host to wait
-        else if (s != t->done_stream) HIPCHK(hipStreamWaitEvent(s, t->done, 0));
-    }
-    int rc = tri_grow(&t->d_scr, &t->scr_capacity, std::max<int64_t>(1, t->n_obs), 4 * sizeof(double));   // Householder row r_i per observation
+    const int64_t obs_alloc = std::max<int64_t>(1, t->n_obs);
+    OutSlot out{1, t->pts, d_pts, t->n_pts, 3 * sizeof(double)};
+    bool grows = t->scr.grows(t->n_obs) || t->scl.grows(t->n_obs) || (need_order && t->order.grows(t->n_pts));
+    const bool owned = owned_slots(&out, 1, &grows);
+    HIPCHK(t->core.fence.before_run(s, grows));   // scratch and output are shared between runs
+    int rc = t->scr.grow(obs_alloc, 4 * sizeof(double));
+    if (!rc) rc = t->scl.grow(obs_alloc, 2 * sizeof(double));
+    if (!rc) rc = grow_owned_slots(&out, 1);
+    if (!rc && need_order) rc = t->order.grow(t->n_pts, sizeof(int32_t));
     if (rc) return rc;
-    rc = tri_grow(&t->d_scl, &t->scl_capacity, std::max<int64_t>(1, t->n_obs), 2 * sizeof(double));   // (1 / E_i, lambda_i)
-    if (rc) return rc;
-    const bool owned = !d_pts;
-    if (owned) {
-        rc = tri_grow((void **)&t->d_pts, &t->out_capacity, t->n_pts, 3 * sizeof(double));
-        if (rc) return rc;
-        d_pts = t->d_pts;
-    }
+    d_pts = out.as<double>();
     const int lanes = t->lanes;
     const dim3 grid((unsigned)((t->n_pts * lanes + 255) / 256));
     if (need_order) {
-        // the visiting order of this set of observations, on the run's own stream (the caller's start_inds may have been produced there)
-        rc = tri_grow((void **)&t->d_order, &t->order_capacity, t->n_pts, sizeof(int32_t));
-        if (rc) return rc;
-        if (!t->d_hist) HIPCHK(hipMalloc(&t->d_hist, sizeof(int32_t) * 512));
-        HIPCHK(hipMemsetAsync(t->d_hist, 0, sizeof(int32_t) * 512, s));
-        const dim3 pg((unsigned)((t->n_pts + 255) / 256));
-        hipLaunchKernelGGL(tri_order_count_kernel, pg, dim3(256), 0, s, t->cur_start, t->n_pts, t->d_hist);
-        hipLaunchKernelGGL(tri_order_scan_kernel, dim3(1), dim3(256), 0, s, t->d_hist);
-        hipLaunchKernelGGL(tri_order_scatter_kernel, pg, dim3(256), 0, s, t->cur_start, t->n_pts, t->d_hist, t->d_order);
-        HIPCHK(hipGetLastError());
+        if ((rc = enqueue_group_order(t->cur_start, t->n_pts, t->hist.as<int32_t>(), t->order.as<int32_t>(), s))) return rc;
         t->order_valid = true;
     }
-#define PCS_TRI_LAUNCH(G_)                                                                                                     \
-    hipExtLaunchKernelGGL(triangulate_kernel<G_>, grid, dim3(256), 0, s, t->e0, t->e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
-                          t->cur_start, (const double *)t->d_tab, (double4 *)t->d_scr, (double2 *)t->d_scl, d_pts, t->n_pts)
-#define PCS_TRI_LAUNCH_REG(G_, V_)                                                                                                     \
-    hipExtLaunchKernelGGL((triangulate_reg_kernel<G_, V_>), grid, dim3(256), 0, s, t->e0, t->e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
-                          t->cur_start, (const double *)t->d_tab, (double4 *)t->d_scr, (double2 *)t->d_scl, d_pts, t->n_pts, (const int32_t *)(t->order_valid ? t->d_order : nullptr))
+#define PCS_TRI_LAUNCH(G_)                                                                                                                   \
+    hipExtLaunchKernelGGL(triangulate_kernel<G_>, grid, dim3(256), 0, s, t->timer.e0, t->timer.e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
+                          t->cur_start, t->tab.as<const double>(), t->scr.as<double4>(), t->scl.as<double2>(), d_pts, t->n_pts)
+#define PCS_TRI_LAUNCH_REG(G_, V_)                                                                                                                   \
+    hipExtLaunchKernelGGL((triangulate_reg_kernel<G_, V_>), grid, dim3(256), 0, s, t->timer.e0, t->timer.e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
+                          t->cur_start, t->tab.as<const double>(), t->scr.as<double4>(), t->scl.as<double2>(), d_pts, t->n_pts,                          \
+                          t->order_valid ? t->order.as<const int32_t>() : nullptr)
     if (t->variant == 0) {   // round 3's form (views in the global scratch, IEEE divides): kept for A/B (PCS_TRI_VARIANT=0)
         if (lanes == 1) PCS_TRI_LAUNCH(1);
         else if (lanes == 2) PCS_TRI_LAUNCH(2);
@@ -302,124 +225,90 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
 #undef PCS_TRI_LAUNCH_REG
 #undef PCS_TRI_LAUNCH
     HIPCHK(hipGetLastError());
-    t->timed = true;
+    t->timer.timed = true;
     t->out_owned = owned;
     t->run_valid = true;
     t->run_pts = d_pts;
-    t->have_done = true;
-    t->done_stream = s;   // compared only, never used as a handle again
-    HIPCHK(hipEventRecord(t->done, s));
+    HIPCHK(t->core.fence.after_run(s));
     return PCS_OK;
 }
 
 // The refinement of the last run's points (csrc/ba_tri_refine.hpp): per-point LM on the reprojection error in the measured pixels.
 static_assert(TRI_REFINE_NOT_REFINED == PCS_TRI_REFINE_NOT_REFINED && TRI_REFINE_CONVERGED == PCS_TRI_REFINE_CONVERGED &&
               TRI_REFINE_MAX_ITER == PCS_TRI_REFINE_MAX_ITER && TRI_REFINE_NO_DECREASE == PCS_TRI_REFINE_NO_DECREASE, "status codes of pcs_hip.h");
+
+// the outputs in the order of the PCS_TRI_OUT_* bits; the residuals last, so that a refinement without them takes the first three
+enum { TRI_SLOT_POINTS, TRI_SLOT_RMS, TRI_SLOT_INFO, TRI_SLOT_RESID, TRI_SLOTS };
+static std::array<OutSlot, TRI_SLOTS> tri_out_slots(pcs_triangulator *t, void *o_pts, void *o_rms, void *o_info, void *o_resid) {
+    const int64_t n = t->n_pts;
+    return {{{PCS_TRI_OUT_POINTS, t->rpts, o_pts, n, 3 * sizeof(double)}, {PCS_TRI_OUT_RMS, t->rrms, o_rms, n, 2 * sizeof(double)},
+             {PCS_TRI_OUT_INFO, t->rinfo, o_info, n, 3 * sizeof(int32_t)}, {PCS_TRI_OUT_RESIDUALS, t->rres, o_resid, t->n_obs, 2 * sizeof(double)}}};
+}
+
 int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, double gtol, int flags, double *d_pts, double *d_rms,
                    int32_t *d_info, double *d_resid, void *stream) {
-    if (max_iter < 0 || !(ftol >= 0.0 && ftol < INFINITY) || !(xtol >= 0.0 && xtol < INFINITY) || !(gtol >= 0.0 && gtol < INFINITY) ||
-        (flags & ~PCS_TRI_REFINE_RESIDUALS))
-        return fail(PCS_ERR_ARG, "pcs_tri_refine: bad options (max_iter >= 0, finite tolerances >= 0, flags PCS_TRI_REFINE_RESIDUALS)");
+    const bool rest_ok = !(flags & ~PCS_TRI_REFINE_RESIDUALS);
+    if (const int rc = check_lm_options("pcs_tri_refine", max_iter, ftol, xtol, gtol, rest_ok, "flags PCS_TRI_REFINE_RESIDUALS")) return rc;
     if (!t) return fail(PCS_ERR_ARG, "pcs_tri_refine: NULL handle");
     if (!t->have_cams || t->n_pts < 0 || !t->run_valid)
         return fail(PCS_ERR_STATE, "pcs_tri_refine: no run on the current cameras and observations (pcs_tri_run first)");
     const bool want_resid = flags & PCS_TRI_REFINE_RESIDUALS;
-    const int owned = (d_pts ? 0 : PCS_TRI_OUT_POINTS) | (d_rms ? 0 : PCS_TRI_OUT_RMS) | (d_info ? 0 : PCS_TRI_OUT_INFO) |
-                      (want_resid && !d_resid ? PCS_TRI_OUT_RESIDUALS : 0);
+    auto out = tri_out_slots(t, d_pts, d_rms, d_info, d_resid);
+    const int n_out = want_resid ? TRI_SLOTS : TRI_SLOTS - 1;
+    bool grows = false;
+    const int owned = owned_slots(out.data(), n_out, &grows);
     if (t->n_pts == 0) {
         t->refine_owned = owned;
         t->refine_valid = true;
         return PCS_OK;
     }
-    HIPCHK(hipSetDevice(t->device));
-    hipStream_t s = stream ? (hipStream_t)stream : t->stream;
-    const bool grows = ((owned & PCS_TRI_OUT_POINTS) && t->n_pts > t->rpts_capacity) || ((owned & PCS_TRI_OUT_RMS) && t->n_pts > t->rrms_capacity) ||
-                       ((owned & PCS_TRI_OUT_INFO) && t->n_pts > t->rinfo_capacity) || ((owned & PCS_TRI_OUT_RESIDUALS) && t->n_obs > t->rres_capacity);
-    if (t->have_done) {   // the run (or an earlier refinement) first: this reads its points and shares the outputs
-        if (grows || s == hipStreamLegacy || t->done_stream == hipStreamLegacy) HIPCHK(hipEventSynchronize(t->done));
-        else if (s != t->done_stream) HIPCHK(hipStreamWaitEvent(s, t->done, 0));
-    }
-    int rc;
-    if (owned & PCS_TRI_OUT_POINTS) {
-        if ((rc = tri_grow((void **)&t->d_rpts, &t->rpts_capacity, t->n_pts, 3 * sizeof(double)))) return rc;
-        d_pts = t->d_rpts;
-    }
-    if (owned & PCS_TRI_OUT_RMS) {
-        if ((rc = tri_grow((void **)&t->d_rrms, &t->rrms_capacity, t->n_pts, 2 * sizeof(double)))) return rc;
-        d_rms = t->d_rrms;
-    }
-    if (owned & PCS_TRI_OUT_INFO) {
-        if ((rc = tri_grow((void **)&t->d_rinfo, &t->rinfo_capacity, t->n_pts, 3 * sizeof(int32_t)))) return rc;
-        d_info = t->d_rinfo;
-    }
-    if (owned & PCS_TRI_OUT_RESIDUALS) {
-        if ((rc = tri_grow((void **)&t->d_rres, &t->rres_capacity, std::max<int64_t>(1, t->n_obs), 2 * sizeof(double)))) return rc;
-        d_resid = t->d_rres;
-    }
+    HIPCHK(hipSetDevice(t->core.device));
+    hipStream_t s = t->core.stream_or(stream);
+    HIPCHK(t->core.fence.before_run(s, grows));   // the run (or an earlier refinement) first: this reads its points and shares the outputs
+    if (const int rc = grow_owned_slots(out.data(), n_out)) return rc;
     constexpr int G = 4, V = 6;   // the DLT kernel's default geometry (profiles/r09: resources and time)
     const dim3 grid((unsigned)((t->n_pts * G + 255) / 256));
-    hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->r0, t->r1, 0, t->cur_cam, (const double2 *)t->cur_uv,
-                          t->cur_start, (const double *)t->d_tab, t->run_pts, t->n_pts, (const int32_t *)(t->order_valid ? t->d_order : nullptr),
-                          max_iter, ftol, xtol, gtol, d_pts, d_rms, d_info, want_resid ? d_resid : nullptr);
+    hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->refine_timer.e0, t->refine_timer.e1, 0, t->cur_cam,
+                          (const double2 *)t->cur_uv, t->cur_start, t->tab.as<const double>(), t->run_pts, t->n_pts,
+                          t->order_valid ? t->order.as<const int32_t>() : nullptr, max_iter, ftol, xtol, gtol, out[TRI_SLOT_POINTS].as<double>(),
+                          out[TRI_SLOT_RMS].as<double>(), out[TRI_SLOT_INFO].as<int32_t>(), want_resid ? out[TRI_SLOT_RESID].as<double>() : nullptr);
     HIPCHK(hipGetLastError());
-    t->refine_timed = true;
+    t->refine_timer.timed = true;
     t->refine_owned = owned;
     t->refine_valid = true;
-    t->have_done = true;
-    t->done_stream = s;
-    HIPCHK(hipEventRecord(t->done, s));
+    HIPCHK(t->core.fence.after_run(s));
     return PCS_OK;
 }
 
 int pcs_tri_refined(pcs_triangulator *t, double *pts, double *rms, int32_t *info, double *resid) {
     if (!t) return fail(PCS_ERR_ARG, "pcs_tri_refined: NULL handle");
     if (!t->refine_valid) return fail(PCS_ERR_STATE, "pcs_tri_refined: no refinement since the last run (pcs_tri_refine first)");
-    const int want = (pts ? PCS_TRI_OUT_POINTS : 0) | (rms ? PCS_TRI_OUT_RMS : 0) | (info ? PCS_TRI_OUT_INFO : 0) | (resid ? PCS_TRI_OUT_RESIDUALS : 0);
-    if (want & ~t->refine_owned)
-        return fail(PCS_ERR_STATE, "pcs_tri_refined: the last refinement wrote some of these outputs to caller buffers (or computed no residuals)");
-    if (t->n_pts == 0) return PCS_OK;
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // the refinement may have been queued on a caller stream
-    if (pts) HIPCHK(hipMemcpyAsync(pts, t->d_rpts, sizeof(double) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    if (rms) HIPCHK(hipMemcpyAsync(rms, t->d_rrms, sizeof(double) * 2 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    if (info) HIPCHK(hipMemcpyAsync(info, t->d_rinfo, sizeof(int32_t) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    if (resid && t->n_obs) HIPCHK(hipMemcpyAsync(resid, t->d_rres, sizeof(double) * 2 * t->n_obs, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    return PCS_OK;
+    const auto out = tri_out_slots(t, pts, rms, info, resid);
+    return fetch_slots(t->core, out.data(), TRI_SLOTS, t->refine_owned, t->n_pts != 0, "pcs_tri_refined",
+                       "the last refinement wrote some of these outputs to caller buffers (or computed no residuals)");
 }
 
 int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms) {
-    if (!t || !kernel_ms) return fail(PCS_ERR_ARG, "pcs_tri_last_refine_ms: bad arguments");
-    if (!t->refine_timed) return fail(PCS_ERR_STATE, "pcs_tri_last_refine_ms: no refinement has run yet");
-    HIPCHK(hipEventSynchronize(t->r1));
-    HIPCHK(hipEventElapsedTime(kernel_ms, t->r0, t->r1));
-    return PCS_OK;
+    return timer_ms("pcs_tri_last_refine_ms", t ? &t->refine_timer : nullptr, kernel_ms, "no refinement has run yet");
 }
 
 int pcs_tri_points(pcs_triangulator *t, double *pts) {
     if (!t || !pts) return fail(PCS_ERR_ARG, "pcs_tri_points: bad arguments");
-    if (t->n_pts < 0 || (t->n_pts > 0 && (!t->out_owned || !t->d_pts || t->out_capacity < t->n_pts)))
+    if (t->n_pts < 0 || (t->n_pts > 0 && (!t->out_owned || !t->pts.p || t->pts.cap < t->n_pts)))
         return fail(PCS_ERR_STATE, "pcs_tri_points: the last run left no handle-owned result (run with d_pts = NULL first)");
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(tri_wait_done_host(t));   // the run may have been queued on a caller stream
-    if (t->n_pts) HIPCHK(hipMemcpyAsync(pts, t->d_pts, sizeof(double) * 3 * t->n_pts, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    return PCS_OK;
+    const OutSlot out{1, t->pts, pts, t->n_pts, 3 * sizeof(double)};
+    return fetch_slots(t->core, &out, 1, 1, true, "pcs_tri_points", "");
 }
 
 int pcs_tri_synchronize(pcs_triangulator *t, void *stream) {
     if (!t) return fail(PCS_ERR_ARG, "pcs_tri_synchronize: bad arguments");
-    HIPCHK(hipSetDevice(t->device));
-    HIPCHK(hipStreamSynchronize(stream ? (hipStream_t)stream : t->stream));
+    HIPCHK(hipSetDevice(t->core.device));
+    HIPCHK(hipStreamSynchronize(t->core.stream_or(stream)));
     return PCS_OK;
 }
 
 int pcs_tri_last_kernel_ms(pcs_triangulator *t, float *kernel_ms) {
-    if (!t || !kernel_ms) return fail(PCS_ERR_ARG, "pcs_tri_last_kernel_ms: bad arguments");
-    if (!t->timed) return fail(PCS_ERR_STATE, "pcs_tri_last_kernel_ms: nothing has run yet");
-    HIPCHK(hipEventSynchronize(t->e1));
-    HIPCHK(hipEventElapsedTime(kernel_ms, t->e0, t->e1));
-    return PCS_OK;
+    return timer_ms("pcs_tri_last_kernel_ms", t ? &t->timer : nullptr, kernel_ms, "nothing has run yet");
 }
 
 // stateless convenience form: one temporary handle per call (allocations + copies every time — use the handle API

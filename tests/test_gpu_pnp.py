@@ -139,6 +139,62 @@ def test_shapes_at_which_the_kernel_can_go_wrong():
     assert np.array_equal(s.iterations, base.iterations) and np.array_equal(s.residuals, base.residuals[perm], equal_nan=True)
 
 
+def stream_table():
+    """2 cameras x 3 images of a planar 9 x 9 board: a view of 81 observations (more than G * V: the loop beyond the registers runs),
+    one of 12 (fewer than G) and one of 4 (fewer than min_points, refused)."""
+    rig = synthetic.make_rig("pnp-streams", 2, 3, synthetic.charuco_points(10), seed=41, noise_px=0.3)
+    det = rig.detections
+    keep = np.ones(det.shape[0], dtype=bool)
+    for (c, i), n in {(0, 1): 12, (1, 2): 4}.items():
+        keep[np.nonzero((det[:, 0] == c) & (det[:, 1] == i))[0][n:]] = False
+    return rig, det[keep]
+
+
+def test_pose_estimator_orders_runs_across_streams():
+    """The fence of the handle (csrc/pcs_handle.inc RunFence), driven by hand.  Run A on a caller stream; without a synchronisation new
+    observations (the setter waits for that run) and run B on the handle's own stream.  Run A holds the first half of the views, not
+    the whole table, so that run C (the whole table on the caller stream) really grows the buffers and waits on the host before it
+    frees.  Then two runs back to back on different streams with nothing between them: the full refinement on the caller stream and,
+    behind it, the much shorter run of no trial (max_iter = 0) on the handle's stream into the same outputs; only the event keeps the
+    long run from finishing last and overwriting the short one.  Every result equals the front end's bit for bit."""
+    import torch
+    rig, det = stream_table()
+    want = hip_ch.estimate_view_poses(det, rig.points, rig.intr_true, n_imgs=3)
+    want0 = hip_ch.estimate_view_poses(det, rig.points, rig.intr_true, n_imgs=3, max_iter=0)
+    order, ids, start = hip_ch.group_by_view(det, 3)
+    ds = det if order is None else det[order]
+    n = np.diff(start)
+    assert len(ids) == 6 and n.max() > G * V and np.any((n >= 6) & (n < G)) and n.min() < 6
+    c, i = ids // 3, ids % 3
+    assert want.status[c, i].tolist().count(hip_ch.PNP_NOT_ESTIMATED) == 1
+    assert not np.array_equal(want.poses[c, i], want0.poses[c, i], equal_nan=True)
+
+    def assert_rows(got, w, rows):
+        oracle = (w.poses[c, i], w.poses_init[c, i], w.poses_alt[c, i], np.stack([w.rms[c, i], w.rms_init[c, i]], axis=1),
+                  np.stack([w.iterations[c, i], w.status[c, i], w.n_points[c, i]], axis=1))
+        for a, b in zip(got[:5], oracle):
+            assert np.array_equal(a, b[:rows], equal_nan=a.dtype.kind == "f")
+
+    key, uv, vcam = ds[:, 2].astype(np.int32), ds[:, 3:5], c.astype(np.int32)
+    est = hip_ch.PoseEstimator(2, rig.points.shape[0])
+    est.set_cameras(rig.intr_true)
+    est.set_template(rig.points)
+    half = len(ids) // 2
+    est.set_observations(key[: start[half]], uv[: start[half]], start[: half + 1], vcam[:half])   # small buffers first: run C grows them
+    side = torch.cuda.Stream()
+    est.run(stream=side.cuda_stream)                                                              # run A: the caller's stream
+    est.set_observations(key[: start[half]], uv[: start[half]], start[: half + 1], vcam[:half])   # no synchronisation by the caller
+    est.run()                                                                                     # run B: the handle's own stream
+    assert_rows(est.results(), want, half)
+    est.set_observations(key, uv, start, vcam)                                                    # the whole table: every buffer grows
+    est.run(stream=side.cuda_stream)                                                              # run C
+    assert_rows(est.results(), want, len(ids))
+    est.run(stream=side.cuda_stream)                                                              # back to back: the long run ...
+    est.run(max_iter=0)                                                                           # ... and the short one behind it
+    assert_rows(est.results(), want0, len(ids))
+    est.close()
+
+
 def test_from_detections_to_a_finished_calibration():
     """Config 1 geometry at small scale (3 cameras, 6 images, the cube target at visibility 0.2), 0.3 px noise, intrinsics jiggled as
     ``rig.intr``: calc_initial_params -> set_initial_params -> device_solver.lm_solve ends with the cost of the solve started from the
