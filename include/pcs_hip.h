@@ -616,6 +616,67 @@ int pcs_pnp_run(pcs_pose_estimator *p, int max_iter, double ftol, double xtol, d
 int pcs_pnp_results(pcs_pose_estimator *p, double *pose, double *pose_init, double *pose_alt, double *rms, int32_t *info, double *resid);
 int pcs_pnp_last_kernel_ms(pcs_pose_estimator *p, float *kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Camera intrinsics from planar target views (csrc/ba_intrinsics.hpp).  Since pcs_version() 106.
+ * Replaces: AbstractTarget.initial_calibration (calibration_targets/abstract_target.py:263-343: per camera every (image, board) group
+ *           with more than 12 detections goes to cv2.calibrateCamera), the rough intrinsics calc_initial_params starts from
+ *           (optimisation/template_handler.py:321-329 reads them from the camera set).  The closed form of that call: Zhang's method
+ *           with zero skew ("full") and OpenCV's initCameraMatrix2D, principal point at the image centre ("focal"); no distortion.
+ * A group is the set of detections of one (camera, image, board) triple.  Per group a homography pixels <- plane frame (h33 = 1, 8 x 8
+ * normal equations, Hartley-normalised pixels; the plane frame is the PnP start's: centroid c, in-plane axes e1, e2 of the template
+ * points' scatter, metres); per camera the constraints h1' B h2 = 0, h1' B h1 = h2' B h2 of its groups on B = K^-T K^-1.
+ *   pcs_intr_create            n_cams cameras, a template of n_keys points
+ *   pcs_intr_set_template      points (n_keys, 3): target.point_data flattened (abstract_target.py:307 gathers the same per board from point_local)
+ *   pcs_intr_set_observations  host arrays, copied: key (n_obs) int32, uv (n_obs, 2), sorted by group; group j owns rows
+ *                              [start_inds[j], start_inds[j+1]) and belongs to camera group_cam[j]; the groups are sorted by camera;
+ *                              keys and cameras are range-checked -> PCS_ERR_RANGE (abstract_target.py:297-310 gathers the same)
+ *   pcs_intr_run               queue the two kernels on `stream` (NULL = the handle's stream).  model: PCS_INTR_MODEL_*; AUTO is FOCAL
+ *                              when res is given (what OpenCV does) and FULL otherwise.  min_points >= 4 (the reference: 13, "more
+ *                              than 12", abstract_target.py:306).  res: host (n_cams, 2) = (h, w) per camera, or NULL: the normalising
+ *                              centre ((w - 1) / 2, (h - 1) / 2) and scale (w + h) / 2; without it the count-weighted mean of the
+ *                              groups' pixel centroids and spreads.  A group with too few observations, a non-planar template, a
+ *                              non-finite measurement or a failed fit contributes nothing (its status says why).  The full model falls
+ *                              back to the focal one (status PCS_INTR_FOCAL_FALLBACK) when B is not definite, the camera has fewer
+ *                              than two used groups, V'V has more than one vanishing eigenvalue, or the result is not finite.
+ *                              Outputs (device buffers of the caller, or NULL = handle-owned): d_intr (n_cams, 9) =
+ *                              [fx, cx, fy, cy, 0, 0, 0, 0, 0] (NaN when not estimated); d_cam_info (n_cams, 2) int32 {status
+ *                              PCS_INTR_*, groups used}; d_eig_ratio (n_cams) smallest / second smallest eigenvalue of V'V (near 1:
+ *                              the views do not constrain the model); d_homographies (n_groups, 9) row-major; d_frames (n_groups, 9)
+ *                              = [c, e1, e2]; d_group_info (n_groups, 2) int32 {status PCS_INTR_GROUP_*, observations};
+ *                              d_pixel_stats (n_groups, 3) = pixel centroid and mean distance from it.
+ *                              PCS_ERR_ARG: NULL handle, unknown model, min_points < 4, a non-finite or non-positive res.
+ *   pcs_intr_results           copy handle-owned outputs of the last run to the host (any pointer may be NULL; blocking)
+ *                              (replaces the camera matrix cv2.calibrateCamera returns, abstract_target.py:313-333)
+ *   pcs_intr_last_kernel_ms    device time of the last run: both kernels.
+ */
+typedef struct pcs_intrinsics_estimator pcs_intrinsics_estimator;
+enum { PCS_INTR_MODEL_AUTO = 0, PCS_INTR_MODEL_FULL = 1, PCS_INTR_MODEL_FOCAL = 2 };
+enum {
+    PCS_INTR_NOT_ESTIMATED = 0,    /* no usable group, or the focal system is singular or gave a non-positive 1 / f^2: the row is NaN */
+    PCS_INTR_FULL = 1,             /* fx, cx, fy, cy from B */
+    PCS_INTR_FOCAL = 2,            /* the focal model was asked for: fx, fy, the principal point at the normalising centre */
+    PCS_INTR_FOCAL_FALLBACK = 3    /* the full model was asked for and could not be used */
+};
+enum {
+    PCS_INTR_GROUP_TOO_FEW = 0,     /* fewer than min_points observations */
+    PCS_INTR_GROUP_USED = 1,
+    PCS_INTR_GROUP_NOT_PLANAR = 2,  /* lambda_min >= 1e-3 lambda_mid of the template points' scatter (the PnP start's rule) */
+    PCS_INTR_GROUP_NOT_FINITE = 3,  /* a non-finite measurement, or all measurements in one pixel */
+    PCS_INTR_GROUP_FIT_FAILED = 4   /* the homography's normal equations lost definiteness */
+};
+enum { PCS_INTR_OUT_INTR = 1, PCS_INTR_OUT_CAM_INFO = 2, PCS_INTR_OUT_EIG_RATIO = 4, PCS_INTR_OUT_HOMOGRAPHIES = 8, PCS_INTR_OUT_FRAMES = 16,
+       PCS_INTR_OUT_GROUP_INFO = 32, PCS_INTR_OUT_PIXEL_STATS = 64 };
+int pcs_intr_create(pcs_intrinsics_estimator **out, int device, int64_t n_cams, int64_t n_keys);
+int pcs_intr_destroy(pcs_intrinsics_estimator *p);
+int pcs_intr_set_template(pcs_intrinsics_estimator *p, const double *points);
+int pcs_intr_set_observations(pcs_intrinsics_estimator *p, int64_t n_obs, const int32_t *key, const double *uv, int64_t n_groups, const int64_t *start_inds,
+                              const int32_t *group_cam);
+int pcs_intr_run(pcs_intrinsics_estimator *p, int model, int min_points, const double *res, double *d_intr, int32_t *d_cam_info, double *d_eig_ratio,
+                 double *d_homographies, double *d_frames, int32_t *d_group_info, double *d_pixel_stats, void *stream);
+int pcs_intr_results(pcs_intrinsics_estimator *p, double *intr, int32_t *cam_info, double *eig_ratio, double *homographies, double *frames,
+                     int32_t *group_info, double *pixel_stats);
+int pcs_intr_last_kernel_ms(pcs_intrinsics_estimator *p, float *kernel_ms);
+
 /* Page-locked host memory for outputs: pcs_eval / pcs_eval_compact copy device -> host at PCIe rate
  * into such buffers (a pageable destination is several times slower).  Replaces nothing in the
  * reference (NumPy owns every array there, afb:561); SURVEY 8 f1 "zero-copy hand-off". */

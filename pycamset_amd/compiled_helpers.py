@@ -8,6 +8,8 @@ pyCamSet/optimisation/compiled_helpers.py, evaluated by the HIP engine:
 
 Row f5, ``estimate_view_poses``: the per-view target pose the reference gets from cv2.solvePnPGeneric
 (calibration_targets/abstract_target.py:345-405) in front of ``calc_initial_params``.
+Row f6, ``estimate_intrinsics``: the per-camera intrinsics the reference gets from cv2.calibrateCamera
+(``AbstractTarget.initial_calibration``, abstract_target.py:263-343), from planar views in closed form, optionally refined.
 
 The reference calls them with the detection table on every call (template_handler.py:537-543,
 :586-592); the table is uploaded once and cached by content.
@@ -553,3 +555,221 @@ def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_poi
         else:
             out.residuals[order] = resid
     return out
+
+
+# ---- intrinsics from planar views (row f6: the rough intrinsics calc_initial_params starts from) -------------------------------------
+# per-camera and per-group status of the estimate (include/pcs_hip.h PCS_INTR_*, PCS_INTR_GROUP_*)
+from ._capi import (INTR_FOCAL, INTR_FOCAL_FALLBACK, INTR_FULL, INTR_GROUP_FIT_FAILED, INTR_GROUP_NOT_FINITE,  # noqa: E402,F401
+                    INTR_GROUP_NOT_PLANAR, INTR_GROUP_TOO_FEW, INTR_GROUP_USED, INTR_NOT_ESTIMATED)
+last_intrinsics_kernel_ms = None
+
+
+@dataclass
+class IntrinsicsEstimate:
+    """Intrinsics per camera from planar target views (``estimate_intrinsics``).  ``intr`` (C, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2]
+    (the closed form has zero distortion; NaN rows where ``status`` is INTR_NOT_ESTIMATED); ``status`` (INTR_*), ``n_groups`` (groups
+    used) (C,) int32; ``eig_ratio`` (C,) smallest / second smallest eigenvalue of the constraint matrix (near 1: the views do not
+    constrain the model).  Per (camera, image, board) group: ``homographies`` (G, 3, 3) pixels <- metric plane frame, ``plane_frames``
+    (G, 9) = [centroid, e1, e2] of that frame in template coordinates, ``group_status`` (INTR_GROUP_*), ``group_counts``,
+    ``group_index`` (G, 3) = [cam, im, board].  With ``refine=True``: ``intr_init`` the closed form, ``intr`` the refined rows,
+    ``rms_init`` / ``rms`` (C,) RMS reprojection error in pixels before and after, ``lm`` the ``DeviceLMResult``."""
+    intr: np.ndarray
+    status: np.ndarray
+    n_groups: np.ndarray
+    eig_ratio: np.ndarray
+    homographies: np.ndarray
+    plane_frames: np.ndarray
+    group_status: np.ndarray
+    group_counts: np.ndarray
+    group_index: np.ndarray
+    intr_init: np.ndarray | None = None
+    rms_init: np.ndarray | None = None
+    rms: np.ndarray | None = None
+    lm: object | None = None
+
+
+class IntrinsicsEstimator(_Handle):
+    """Owner of one ``pcs_intrinsics_estimator`` handle (include/pcs_hip.h): template, observation copies and outputs stay on the
+    device across calls."""
+
+    _create, _destroy = "pcs_intr_create", "pcs_intr_destroy"
+
+    def __init__(self, n_cams: int, n_keys: int, device: int = 0):
+        super().__init__(device, n_cams, n_keys)
+        self.n_cams, self.n_keys, self.device = int(n_cams), int(n_keys), int(device)
+        self.n_groups = 0
+
+    def set_template(self, points):
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        if pts.shape[0] != self.n_keys:
+            raise ValueError(f"expected {self.n_keys} template points")
+        self._call("pcs_intr_set_template", self._h, self._ptr(pts))
+
+    def set_observations(self, key, uv, start_inds, group_cam):
+        """Host arrays sorted by group, the groups sorted by camera: key (n_obs,) int, uv (n_obs, 2), start_inds (n_groups + 1,),
+        group_cam (n_groups,) int."""
+        key = np.ascontiguousarray(key, dtype=np.int32)
+        uv = np.ascontiguousarray(uv, dtype=np.float64)
+        start = np.ascontiguousarray(start_inds, dtype=np.int64)
+        gcam = np.ascontiguousarray(group_cam, dtype=np.int32)
+        if start.ndim != 1 or start.shape[0] < 1 or gcam.shape != (start.shape[0] - 1,) or uv.shape != (key.shape[0], 2):
+            raise ValueError("expected key (n_obs,), uv (n_obs, 2), start_inds (n_groups + 1,), group_cam (n_groups,)")
+        self._call("pcs_intr_set_observations", self._h, key.shape[0], self._ptr(key), self._ptr(uv), start.shape[0] - 1, self._ptr(start), self._ptr(gcam))
+        self.n_groups = start.shape[0] - 1
+
+    def run(self, model: str = "auto", min_points: int = 13, res=None, stream: int | None = None):
+        """Queue the two kernels (asynchronous; handle-owned outputs, fetched with ``results()``).  ``res``: (n_cams, 2) = (h, w) or None."""
+        model_id, min_points = check_intrinsics_options(model, min_points)
+        r = None if res is None else check_res(res, self.n_cams)
+        self._call("pcs_intr_run", self._h, model_id, min_points, self._ptr(r), None, None, None, None, None, None, None, _stream_arg(stream))
+
+    def results(self):
+        """Wait for the last ``run``: (intr (n_cams, 9), cam_info (n_cams, 2) int32 [status, groups used], eig_ratio (n_cams,),
+        homographies (n_groups, 9), frames (n_groups, 9), group_info (n_groups, 2) int32 [status, observations], pixel_stats (n_groups, 3))."""
+        c, n = self.n_cams, self.n_groups
+        out = (np.empty((c, 9)), np.empty((c, 2), dtype=np.int32), np.empty(c), np.empty((n, 9)), np.empty((n, 9)), np.empty((n, 2), dtype=np.int32),
+               np.empty((n, 3)))
+        self._call("pcs_intr_results", self._h, *(self._ptr(a) for a in out))
+        return out
+
+    def last_kernel_ms(self) -> float:
+        return self._ms("pcs_intr_last_kernel_ms")
+
+
+def check_intrinsics_options(model, min_points):
+    """-> (model id, min_points); ValueError before anything is queued.  A homography needs four points."""
+    if model not in _capi.INTR_MODEL_IDS:
+        raise ValueError(f"model must be one of {sorted(_capi.INTR_MODEL_IDS)}, got {model!r}")
+    if check_min_points(min_points) < 4:
+        raise ValueError(f"min_points must be at least 4 (a homography has eight unknowns), got {min_points!r}")
+    return _capi.INTR_MODEL_IDS[model], int(min_points)
+
+
+def check_res(res, n_cams: int) -> np.ndarray:
+    """``res`` = (h, w) or (n_cams, 2) -> contiguous (n_cams, 2) float64; ValueError unless finite and positive."""
+    r = np.asarray(res, dtype=np.float64)
+    if r.shape not in ((2,), (n_cams, 2)):
+        raise ValueError(f"res must be (h, w) or ({n_cams}, 2), got shape {r.shape}")
+    r = np.ascontiguousarray(np.broadcast_to(r, (n_cams, 2)))
+    if not (np.all(np.isfinite(r)) and np.all(r > 0)):
+        raise ValueError("res must be finite and positive")
+    return r
+
+
+def group_by_board(dct, n_imgs: int, board_of_key, n_boards: int):
+    """The host grouping of ``estimate_intrinsics``: one stable sort on (cam, im, board, key), as ``group_by_view`` does it (the same
+    table shuffled reaches the device in the same order).  -> (order or None, group ids (cam * n_imgs + im) * n_boards + board, start)."""
+    d = np.asarray(dct, dtype=np.float64)
+    key = d[:, 2].astype(np.int64)
+    gid = (d[:, 0].astype(np.int64) * int(n_imgs) + d[:, 1].astype(np.int64)) * int(n_boards) + np.asarray(board_of_key, dtype=np.int64)[key]
+    rank = gid * (int(key.max()) + 1 if key.shape[0] else 1) + key
+    order = None
+    if rank.shape[0] > 1 and np.any(rank[1:] < rank[:-1]):
+        order = np.argsort(rank, kind="stable")
+        gid = gid[order]
+    head = np.ones(gid.shape[0], dtype=bool)
+    head[1:] = gid[1:] != gid[:-1]
+    first = np.nonzero(head)[0]
+    return order, gid[first], np.concatenate([first, [gid.shape[0]]]).astype(np.int64)
+
+
+_intr_cache: dict = {}
+
+
+def _intrinsics_estimator(device: int, n_cams: int, n_keys: int) -> IntrinsicsEstimator:
+    return _cached_handle(_intr_cache, (int(device), int(n_cams), int(n_keys)), lambda: IntrinsicsEstimator(n_cams, n_keys, device))
+
+
+def estimate_intrinsics(dct, points, *, n_cams: int | None = None, n_imgs: int | None = None, board_of_key=None, res=None, model: str = "auto",
+                        min_points: int = 13, refine: bool = False, device: int = 0, **lm_opts) -> IntrinsicsEstimate:
+    """Camera intrinsics from the detections of a target made of planar boards, on the device (include/pcs_hip.h pcs_intr_run): what the
+    reference's ``AbstractTarget.initial_calibration`` (calibration_targets/abstract_target.py:263-343) gets from cv2.calibrateCamera,
+    as Zhang's closed form with zero skew (``model="full"``) or OpenCV's initCameraMatrix2D form (``"focal"``: the principal point
+    at the image centre).  ``"auto"`` takes the focal model when ``res`` is given, as OpenCV does, and the full model otherwise.
+
+    ``dct``: the flattened (N, 5) table [cam, im, key, u, v] in any order; ``points``: the template (K, 3); ``board_of_key`` (K,) int:
+    the planar board of every key (default: one board; for a Ccube the face); ``res``: (h, w) or (C, 2); a group is used when it has at
+    least ``min_points`` observations (the reference: more than 12).
+
+    ``refine=True`` runs the device LM (``device_solver.lm_solve``, options ``lm_opts``) on projection + extrinsic3D + template
+    points with every extrinsic fixed at identity, one free pose per (camera, image) view (started by ``estimate_view_poses`` at the
+    closed form) and all nine intrinsics of every estimated camera free.  Cameras and views without an estimate stay out of it."""
+    global last_intrinsics_kernel_ms
+    check_intrinsics_options(model, min_points)
+    if lm_opts and not refine:
+        raise ValueError(f"options {sorted(lm_opts)} belong to the refinement: pass refine=True")
+    d = np.asarray(dct, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    if d.ndim != 2 or d.shape[1] != 5:
+        raise ValueError("expected dct (N, 5) = [cam, im, key, u, v]")
+    K = pts.shape[0]
+    bok = np.zeros(K, dtype=np.int64) if board_of_key is None else np.asarray(board_of_key)
+    if bok.shape != (K,) or bok.dtype.kind not in "iu" or (K and bok.min() < 0):
+        raise ValueError(f"board_of_key must be ({K},) non-negative integers")
+    n_boards = int(bok.max()) + 1 if K else 1
+    C = (int(d[:, 0].max()) + 1 if d.shape[0] else 0) if n_cams is None else int(n_cams)
+    I = (int(d[:, 1].max()) + 1 if d.shape[0] else 0) if n_imgs is None else int(n_imgs)
+    if d.shape[0] and (d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 1].min() < 0 or d[:, 1].max() >= I or d[:, 2].min() < 0 or d[:, 2].max() >= K):
+        raise ValueError("camera, image or key index of the table outside n_cams / n_imgs / the template")
+    r = None if res is None else check_res(res, C)
+    if d.shape[0] == 0 or C == 0:
+        z = np.zeros(C, dtype=np.int32)
+        out = IntrinsicsEstimate(intr=np.full((C, 9), np.nan), status=z, n_groups=z.copy(), eig_ratio=np.full(C, np.nan), homographies=np.empty((0, 3, 3)),
+                                 plane_frames=np.empty((0, 9)), group_status=np.empty(0, dtype=np.int32), group_counts=np.empty(0, dtype=np.int32),
+                                 group_index=np.empty((0, 3), dtype=np.int64))
+    else:
+        order, gid, start = group_by_board(d, I, bok, n_boards)
+        ds = d if order is None else d[order]
+        index = np.stack([gid // (I * n_boards), (gid // n_boards) % I, gid % n_boards], axis=1)
+        est = _intrinsics_estimator(device, C, K)
+        est.set_template(pts)
+        est.set_observations(ds[:, 2].astype(np.int32), ds[:, 3:5], start, index[:, 0].astype(np.int32))
+        est.run(model, min_points, r)
+        intr, cinfo, eig, H, frames, ginfo, _ = est.results()
+        last_intrinsics_kernel_ms = est.last_kernel_ms()
+        out = IntrinsicsEstimate(intr=intr, status=cinfo[:, 0].copy(), n_groups=cinfo[:, 1].copy(), eig_ratio=eig, homographies=H.reshape(-1, 3, 3),
+                                 plane_frames=frames, group_status=ginfo[:, 0].copy(), group_counts=ginfo[:, 1].copy(), group_index=index)
+    if refine:
+        _refine_intrinsics(out, d, pts, I, device, lm_opts)
+    return out
+
+
+def _refine_intrinsics(est: IntrinsicsEstimate, d: np.ndarray, pts: np.ndarray, n_imgs: int, device: int, lm_opts: dict) -> None:
+    """The refinement of ``estimate_intrinsics``: fills ``intr_init``, ``intr``, ``rms_init``, ``rms`` and ``lm`` in place."""
+    from . import function_blocks as fb
+    from .device_solver import lm_solve
+    from .handlers import ChainProblem
+
+    C, I = est.intr.shape[0], int(n_imgs)
+    est.intr_init = est.intr.copy()
+    est.rms_init, est.rms = np.full(C, np.nan), np.full(C, np.nan)
+    have = est.status != INTR_NOT_ESTIMATED
+    if not have.any():
+        return
+    cam, im = d[:, 0].astype(np.int64), d[:, 1].astype(np.int64)
+    start = np.where(have[:, None], est.intr, np.array([1.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0]))   # rows of cameras that stay out: never read
+    vp = estimate_view_poses(d[have[cam]], pts, start, n_imgs=I, device=device)
+    seen = vp.status != PNP_NOT_ESTIMATED                                   # (C, I) views with a pose
+    rows = have[cam] & seen[cam, im]
+    if not rows.any():
+        return
+    det = np.ascontiguousarray(np.column_stack([cam[rows], cam[rows] * I + im[rows], d[rows, 2], d[rows, 3:5]]))
+    poses = np.where(seen[:, :, None], vp.poses, 0.0).reshape(C * I, 6)
+    free_cam = np.zeros(C, dtype=bool)
+    free_cam[np.unique(cam[rows])] = True
+    unfixed = [np.repeat(free_cam[:, None], 9, axis=1), np.zeros((C, 6), dtype=bool), np.repeat(seen.reshape(-1, 1), 6, axis=1)]
+    op = fb.optimisation_function([fb.projection(), fb.extrinsic3D(), fb.template_points()], device=device, counts=(C, C * I, pts.shape[0]))
+    prob = ChainProblem(op, det, [start, np.zeros((C, 6)), poses], template=pts, unfixed=unfixed)
+    loss = prob.make_loss_fun()
+    n_rows = np.bincount(det[:, 0].astype(np.int64), minlength=C)
+
+    def rms_per_camera(x):
+        r2 = np.sum(np.asarray(loss(x)).reshape(-1, 2) ** 2, axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(free_cam, np.sqrt(np.bincount(det[:, 0].astype(np.int64), weights=r2, minlength=C) / n_rows), np.nan)
+
+    est.rms_init = rms_per_camera(prob.x0)
+    est.lm = lm_solve(prob, prob.x0, **lm_opts)
+    refined = prob.get_bundle_adjustment_inputs(est.lm.x)[0]
+    est.intr = np.where(free_cam[:, None], refined, est.intr_init)
+    est.rms = rms_per_camera(est.lm.x)

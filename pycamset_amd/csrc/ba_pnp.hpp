@@ -16,7 +16,7 @@
 //         with the target's centre kept in place: R2 = (2 v v' - I) R (2 e3 e3' - I), t2 = t' - R2 c;
 //       otherwise: q = (X - c) / s, 3 x 4 DLT with p34 = 1 by the 11 x 11 normal equations; R = nearest rotation of the left block M
 //         (det M > 0 required), t' = (s / mean singular value of M) p4, t = t' - R c.
-//       Both fits are one routine (pnp_fit<D>, D = 2 or 3): unknowns [row 0 (D + 1) | row 1 (D + 1) | row 2 (D)], normal matrix
+//       Both fits are one routine (pnp_fit<D>, D = 2 or 3; the measurement's image point comes from a functor, here PnpCameraMap): unknowns [row 0 (D + 1) | row 1 (D + 1) | row 2 (D)], normal matrix
 //       [[A 0 B1] [0 A B2] [B1' B2' C]].  Fixing the last element to 1 is sound because t_z > 0 for a target in front of the camera.
 //       Nearest rotation: M (M'M)^(-1/2) from the Jacobi eigenvectors of M'M.  The result does not depend on the choice of the in-plane
 //       eigenvectors (a square grid has lambda_1 = lambda_2): the fit and every later step are covariant under it.
@@ -86,10 +86,9 @@ __device__ __forceinline__ void pnp_rotvec(const double (&R)[9], double (&r)[3])
     r[0] = k * x; r[1] = k * y; r[2] = k * z;
 }
 
-// one Jacobi rotation of the symmetric A (full storage) in the (P, Q) plane; V accumulates the eigenvectors in its columns
-template <int P, int Q>
-__device__ __forceinline__ void pnp_jacobi_rotate(double (&A)[3][3], double (&V)[3][3]) {
-    constexpr int Rr = 3 - P - Q;
+// one Jacobi rotation of the symmetric N x N matrix A (full storage) in the (P, Q) plane; V accumulates the eigenvectors in its columns
+template <int N, int P, int Q>
+__device__ __forceinline__ void pnp_jacobi_rotate(double (&A)[N][N], double (&V)[N][N]) {
     const double apq = A[P][Q];
     if (apq == 0.0 || !isfinite(apq)) return;
     const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
@@ -99,29 +98,41 @@ __device__ __forceinline__ void pnp_jacobi_rotate(double (&A)[3][3], double (&V)
     A[P][P] -= t * apq;
     A[Q][Q] += t * apq;
     A[P][Q] = A[Q][P] = 0.0;
-    const double arp = A[Rr][P], arq = A[Rr][Q];
-    A[Rr][P] = A[P][Rr] = c * arp - s * arq;
-    A[Rr][Q] = A[Q][Rr] = s * arp + c * arq;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int r = 0; r < N; ++r) {
+        if (r == P || r == Q) continue;
+        const double arp = A[r][P], arq = A[r][Q];
+        A[r][P] = A[P][r] = c * arp - s * arq;
+        A[r][Q] = A[Q][r] = s * arp + c * arq;
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
         const double vp = V[k][P], vq = V[k][Q];
         V[k][P] = c * vp - s * vq;
         V[k][Q] = s * vp + c * vq;
     }
 }
 
-// eigenvalues (the diagonal of A on return, unsorted) and eigenvectors (columns of V) of a symmetric 3 x 3: eight cyclic sweeps
-__device__ __forceinline__ void pnp_jacobi3(double (&A)[3][3], double (&V)[3][3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 8; ++sweep) {
-        pnp_jacobi_rotate<0, 1>(A, V);
-        pnp_jacobi_rotate<0, 2>(A, V);
-        pnp_jacobi_rotate<1, 2>(A, V);
-    }
+// one cyclic sweep: the pairs (0, 1), (0, 2), ..., (N - 2, N - 1), every index a compile-time constant (the matrices stay in registers)
+template <int N, int P = 0, int Q = 1>
+__device__ __forceinline__ void pnp_jacobi_sweep(double (&A)[N][N], double (&V)[N][N]) {
+    pnp_jacobi_rotate<N, P, Q>(A, V);
+    if constexpr (Q + 1 < N) pnp_jacobi_sweep<N, P, Q + 1>(A, V);
+    else if constexpr (P + 2 < N) pnp_jacobi_sweep<N, P + 1, P + 2>(A, V);
 }
+
+// eigenvalues (the diagonal of A on return, unsorted) and eigenvectors (columns of V) of a symmetric N x N by cyclic Jacobi sweeps
+template <int N>
+__device__ __forceinline__ void pnp_jacobi(double (&A)[N][N], double (&V)[N][N], const int sweeps) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < sweeps; ++sweep) pnp_jacobi_sweep<N>(A, V);
+}
+
+// the symmetric 3 x 3 case: eight sweeps
+__device__ __forceinline__ void pnp_jacobi3(double (&A)[3][3], double (&V)[3][3]) { pnp_jacobi<3>(A, V, 8); }
 
 // nearest rotation of M (row-major): the polar factor M (M'M)^(-1/2); sig = mean singular value
 __device__ __forceinline__ void pnp_nearest_rotation(const double (&M)[9], double (&R)[9], double &sig) {
@@ -185,11 +196,25 @@ __device__ __forceinline__ bool pnp_ldl(double (&A)[N * (N + 1) / 2], const doub
     return ok;
 }
 
-// Least squares of the projective map with its last element 1 from q = F (X - c) inv_s (D coordinates) to the normalised image:
-// the group's normal equations (every lane identical bits) and their solution h (3 D + 2).
-template <int D, int G>
+// measurement -> normalised image point of the PnP start: the camera table's five fixed-point undistortion steps, then the pinhole inverse
+struct PnpCameraMap {
+    const double *ct;
+    double cx, cy, ifx, ify;
+    __device__ __forceinline__ explicit PnpCameraMap(const double *__restrict__ t) : ct(t), cx(t[23]), cy(t[25]), ifx(tri_rcp(t[22])), ify(tri_rcp(t[24])) {}
+    __device__ __forceinline__ void operator()(const double2 m, double &x, double &y) const {
+        double uo, vo;
+        undistort5_fast(m.x, m.y, ct, uo, vo);
+        x = (uo - cx) * ifx;
+        y = (vo - cy) * ify;
+    }
+};
+
+// Least squares of the projective map with its last element 1 from q = F (X - c) inv_s (D coordinates) to the image point that
+// `to_image` makes of a measurement (PnpCameraMap; ba_intrinsics.hpp: Hartley-normalised pixels): the group's normal equations (every
+// lane identical bits) and their solution h (3 D + 2).
+template <int D, int G, class Map>
 __device__ __forceinline__ bool pnp_fit(const int32_t *__restrict__ key, const double2 *__restrict__ uv, const int64_t s0, const int64_t s1, const int g,
-                                        const double *__restrict__ ct, const double *__restrict__ pts, const double (&c)[3], const double (&F)[D][3],
+                                        const Map &to_image, const double *__restrict__ pts, const double (&c)[3], const double (&F)[D][3],
                                         const double inv_s, double (&h)[3 * D + 2]) {
     constexpr int M = D + 1, N = 3 * D + 2;
     double A[N * (N + 1) / 2], b[N];
@@ -197,8 +222,6 @@ __device__ __forceinline__ bool pnp_fit(const int32_t *__restrict__ key, const d
     for (int k = 0; k < N * (N + 1) / 2; ++k) A[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < N; ++k) b[k] = 0.0;
-    const double fx = ct[22], cx = ct[23], fy = ct[24], cy = ct[25];
-    const double ifx = tri_rcp(fx), ify = tri_rcp(fy);
     for (int64_t o = s0 + g; o < s1; o += G) {
         const double2 m = uv[o];
         const double *X = pts + 3 * (int64_t)key[o];
@@ -207,9 +230,9 @@ __device__ __forceinline__ bool pnp_fit(const int32_t *__restrict__ key, const d
 #pragma unroll
         for (int k = 0; k < D; ++k) qt[k] = q[k] = (F[k][0] * d0 + F[k][1] * d1 + F[k][2] * d2) * inv_s;
         qt[D] = 1.0;
-        double uo, vo;
-        undistort5_fast(m.x, m.y, ct, uo, vo);
-        const double x = (uo - cx) * ifx, y = (vo - cy) * ify, w = x * x + y * y;
+        double x, y;
+        to_image(m, x, y);
+        const double w = x * x + y * y;
 #pragma unroll
         for (int i = 0; i < M; ++i) {
 #pragma unroll
@@ -248,30 +271,15 @@ __device__ __forceinline__ bool pnp_fit(const int32_t *__restrict__ key, const d
     return pnp_ldl<N>(A, b, h);
 }
 
-__device__ __forceinline__ void pnp_write_nan(double *__restrict__ p) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) p[k] = __builtin_nan("");
-}
-
+// Centroid c (two passes: centroid, then scatter) of a group's template points, the frame of their scatter (e3: the eigenvector of the
+// smallest eigenvalue, the normal of a planar target; e1: of the largest; e2 = e3 x e1), the smallest and the middle eigenvalue and
+// the scale s = sqrt(tr S / n).  The view is planar when l_min < PNP_PLANAR_RATIO l_mid.  Every lane of the group gets identical bits.
+// (The eigenvector matrix stays local to this routine: selected through a reference it would be indexed dynamically, in scratch.)
 template <int G>
-__global__ __launch_bounds__(256) void pnp_start_kernel(const int32_t *__restrict__ key, const double2 *__restrict__ uv, const int64_t *__restrict__ start,
-                                                        const int32_t *__restrict__ view_cam, const double *__restrict__ cam_tab,
-                                                        const double *__restrict__ pts, const int64_t n_views, const int32_t *__restrict__ order,
-                                                        const int min_points, double *__restrict__ pose_init, double *__restrict__ pose_alt) {
-    const int64_t gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const int g = threadIdx.x & (G - 1);
-    if (gid >= n_views) return;   // whole groups leave together; the shuffles below stay inside a group
-    const int64_t j = order ? order[gid] : gid;
-    const int64_t s0 = start[j], s1 = start[j + 1];
-    const int64_t n = s1 - s0;
-    double *po = pose_init + 6 * j, *pa = pose_alt + 6 * j;
-    if (n <= 0 || n < min_points) {
-        if (g == 0) { pnp_write_nan(po); pnp_write_nan(pa); }
-        return;
-    }
-    const double *ct = cam_tab + (int64_t)view_cam[j] * TRI_CAM_STRIDE;
-    // centroid, then scatter
-    double c[3] = {0.0, 0.0, 0.0};
+__device__ __forceinline__ void pnp_template_frame(const int32_t *__restrict__ key, const double *__restrict__ pts, const int64_t s0, const int64_t s1,
+                                                   const int g, const int64_t n, double (&c)[3], double (&e1)[3], double (&e2)[3], double (&e3)[3],
+                                                   double &l_min, double &l_mid, double &s) {
+    c[0] = c[1] = c[2] = 0.0;
     for (int64_t o = s0 + g; o < s1; o += G) {
         const double *X = pts + 3 * (int64_t)key[o];
         c[0] += X[0]; c[1] += X[1]; c[2] += X[2];
@@ -297,24 +305,50 @@ __global__ __launch_bounds__(256) void pnp_start_kernel(const int32_t *__restric
     const int o_a = i_min == 0 ? 1 : 0, o_b = i_min == 2 ? 1 : 2;
     const double l_a = o_a == 0 ? l0 : l1, l_b = o_b == 1 ? l1 : l2;
     const int i_max = l_a >= l_b ? o_a : o_b;
-    const double s = sqrt((l0 + l1 + l2) * inv_n);
-    const double l_min = i_min == 0 ? l0 : (i_min == 1 ? l1 : l2), l_mid = l_a >= l_b ? l_b : l_a;
+    s = sqrt((l0 + l1 + l2) * inv_n);
+    l_min = i_min == 0 ? l0 : (i_min == 1 ? l1 : l2);
+    l_mid = l_a >= l_b ? l_b : l_a;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        e3[k] = i_min == 0 ? E[k][0] : (i_min == 1 ? E[k][1] : E[k][2]);
+        e1[k] = i_max == 0 ? E[k][0] : (i_max == 1 ? E[k][1] : E[k][2]);
+    }
+    e2[0] = e3[1] * e1[2] - e3[2] * e1[1]; e2[1] = e3[2] * e1[0] - e3[0] * e1[2]; e2[2] = e3[0] * e1[1] - e3[1] * e1[0];
+}
+
+__device__ __forceinline__ void pnp_write_nan(double *__restrict__ p) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) p[k] = __builtin_nan("");
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void pnp_start_kernel(const int32_t *__restrict__ key, const double2 *__restrict__ uv, const int64_t *__restrict__ start,
+                                                        const int32_t *__restrict__ view_cam, const double *__restrict__ cam_tab,
+                                                        const double *__restrict__ pts, const int64_t n_views, const int32_t *__restrict__ order,
+                                                        const int min_points, double *__restrict__ pose_init, double *__restrict__ pose_alt) {
+    const int64_t gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
+    const int g = threadIdx.x & (G - 1);
+    if (gid >= n_views) return;   // whole groups leave together; the shuffles below stay inside a group
+    const int64_t j = order ? order[gid] : gid;
+    const int64_t s0 = start[j], s1 = start[j + 1];
+    const int64_t n = s1 - s0;
+    double *po = pose_init + 6 * j, *pa = pose_alt + 6 * j;
+    if (n <= 0 || n < min_points) {
+        if (g == 0) { pnp_write_nan(po); pnp_write_nan(pa); }
+        return;
+    }
+    const double *ct = cam_tab + (int64_t)view_cam[j] * TRI_CAM_STRIDE;
+    double c[3], e1[3], e2[3], e3[3], l_min, l_mid, s;
+    pnp_template_frame<G>(key, pts, s0, s1, g, n, c, e1, e2, e3, l_min, l_mid, s);
     bool ok = true;
     double pose[6], alt[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) pose[k] = alt[k] = __builtin_nan("");
     const double inv_s = 1.0 / s;
     if (ok && l_min < PNP_PLANAR_RATIO * l_mid) {   // planar
-        double e1[3], e3[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            e3[k] = i_min == 0 ? E[k][0] : (i_min == 1 ? E[k][1] : E[k][2]);
-            e1[k] = i_max == 0 ? E[k][0] : (i_max == 1 ? E[k][1] : E[k][2]);
-        }
-        const double e2[3] = {e3[1] * e1[2] - e3[2] * e1[1], e3[2] * e1[0] - e3[0] * e1[2], e3[0] * e1[1] - e3[1] * e1[0]};
         const double F[2][3] = {{e1[0], e1[1], e1[2]}, {e2[0], e2[1], e2[2]}};
         double h[8];
-        ok = pnp_fit<2, G>(key, uv, s0, s1, g, ct, pts, c, F, inv_s, h);
+        ok = pnp_fit<2, G>(key, uv, s0, s1, g, PnpCameraMap(ct), pts, c, F, inv_s, h);
         if (ok) {
             const double c1[3] = {h[0], h[3], h[6]}, c2[3] = {h[1], h[4], h[7]}, c3[3] = {h[2], h[5], 1.0};
             const double nrm = sqrt(0.5 * (c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2] + c2[0] * c2[0] + c2[1] * c2[1] + c2[2] * c2[2]));
@@ -358,7 +392,7 @@ __global__ __launch_bounds__(256) void pnp_start_kernel(const int32_t *__restric
     } else if (ok) {   // a 3-D view
         const double F[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
         double p[11];
-        ok = pnp_fit<3, G>(key, uv, s0, s1, g, ct, pts, c, F, inv_s, p);
+        ok = pnp_fit<3, G>(key, uv, s0, s1, g, PnpCameraMap(ct), pts, c, F, inv_s, p);
         const double M[9] = {p[0], p[1], p[2], p[4], p[5], p[6], p[8], p[9], p[10]};
         const double det = M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]);
         ok = ok && det > 0.0;

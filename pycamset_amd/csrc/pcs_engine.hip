@@ -7,7 +7,7 @@
 //
 // Kernels: ba_kernels.hpp (evaluation, compaction, legacy cost), ba_matfree.hpp (J products without J),
 // ba_normal.hpp (J^T J / J^T r), ba_triangulate.hpp; device maths: ba_device.hpp.  This file: the pcs_engine handle + its part of the C ABI; one translation unit with
-// pcs_common.inc (errors, device queries), pcs_handle.inc (what the batched handles share), pcs_triangulator.inc, pcs_pnp.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
+// pcs_common.inc (errors, device queries), pcs_handle.inc (what the batched handles share), pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -39,6 +39,7 @@
 #include "ba_triangulate.hpp"
 #include "ba_tri_refine.hpp"
 #include "ba_pnp.hpp"
+#include "ba_intrinsics.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -49,6 +50,7 @@ using namespace pcs;
 #include "pcs_handle.inc"
 #include "pcs_triangulator.inc"
 #include "pcs_pnp.inc"
+#include "pcs_intrinsics.inc"
 #include "pcs_solver.inc"
 
 struct pcs_engine {

@@ -17,7 +17,8 @@ parameter groups exist, so here ONE table (``_CHAIN_GROUPS``) drives one primiti
 
 ``camset`` only needs ``get_names()`` / ``get_n_cams()`` and ``target`` only needs ``point_data`` — the
 attributes the reference touches on this path (th:116-129, th:160-163).  ``calc_initial_params`` (th:302-346) computes a
-start vector from the detections with the device's batched PnP (``pose_seeding``); outlier prompts and CameraSet
+start vector from the detections with the device's batched PnP (``pose_seeding``) and, where the camset holds no intrinsics, with
+the device's intrinsics estimate (``compiled_helpers.estimate_intrinsics``); outlier prompts and CameraSet
 reconstruction are outside the path.  ``get_initial_params`` returns what ``set_initial_params`` was given.
 
 Differences from the reference, on purpose:
@@ -189,6 +190,7 @@ class TemplateBundleHandler:  # th:80-240
         self.param_len = None
         self.jac_mask = None
         self.missing_poses = missing_poses
+        self.initial_intrinsics = None   # the IntrinsicsEstimate of calc_initial_params, where it had to make one
 
         n_poses = detection.max_ims
         n_cams = camset.get_n_cams()
@@ -282,8 +284,10 @@ class TemplateBundleHandler:  # th:80-240
         """A start vector from the detections: per-view target poses on the device (``compiled_helpers.estimate_view_poses``), the view
         graph of ``pose_seeding.estimate_camera_relative_poses`` (th:468-601), then the free entries in slab order — unfixed intrinsics,
         extrinsics and poses (plus, for the self and free chains, the free point scalars of the template).  ``intr``: (C, 9) rows
-        [fx, cx, fy, cy, k0, k1, p0, p1, k2]; default: ``camset[idc].intrinsic`` / ``.distortion_coefs`` (th:321-329).  Sets
-        ``missing_poses``; returns the vector without storing it.  The interactive outlier prompt (th:242-279) is not mirrored."""
+        [fx, cx, fy, cy, k0, k1, p0, p1, k2]; default: ``camset[idc].intrinsic`` / ``.distortion_coefs`` (th:321-329) and, where the
+        camset holds none, the device's estimate from the planar views of the detections (``compiled_helpers.estimate_intrinsics`` with
+        ``refine=True`` and ``camset[idc].res`` where present — the reference's ``initial_calibration``, abstract_target.py:263-343),
+        kept on ``initial_intrinsics``.  Sets ``missing_poses``; returns the vector without storing it.  The interactive outlier prompt (th:242-279) is not mirrored."""
         from .pose_seeding import estimate_camera_relative_poses
 
         bp = self.bundlePrimitive
@@ -293,8 +297,7 @@ class TemplateBundleHandler:  # th:80-240
                 intr = np.stack([np.concatenate((np.asarray(self.camset[idc].intrinsic)[[0, 0, 1, 1], [0, 2, 1, 2]].squeeze(),
                                                  np.asarray(self.camset[idc].distortion_coefs).squeeze()), axis=0) for idc in range(n_cams)])
             except (TypeError, AttributeError, KeyError, IndexError):
-                raise ValueError("calc_initial_params: the camset holds no intrinsics (camset[idc].intrinsic / .distortion_coefs): "
-                                 "pass intr (C, 9)") from None
+                intr = self._estimate_initial_intrinsics(n_cams)
         intr = np.array(intr, dtype=np.float64)
         if intr.shape != (n_cams, 9):
             raise ValueError(f"intr must be ({n_cams}, 9), got {intr.shape}")
@@ -312,6 +315,36 @@ class TemplateBundleHandler:  # th:80-240
         if "bdpt" in bp.groups:
             parts.append(self.flat_point_data[bp.bdpt_unfixed])
         return np.concatenate(parts)
+
+    def _estimate_initial_intrinsics(self, n_cams: int) -> np.ndarray:
+        """(C, 9) from the detections alone.  A key's board is its index along the FIRST key axis of ``target.point_data`` — the face of a
+        Ccube, whether its points are laid out (faces, n, 3) or (faces, rows, cols, 3) — and a target with one key axis, (n, 3), is
+        one board.  A free camera without an estimate raises: its rows would be NaN."""
+        from . import compiled_helpers as ch
+
+        shape = tuple(int(n) for n in self.target_point_shape[:-1])
+        n_keys = int(np.prod(shape))
+        try:
+            res = np.array([np.asarray(self.camset[idc].res, dtype=np.float64).reshape(2) for idc in range(n_cams)])
+        except (TypeError, AttributeError, KeyError, IndexError, ValueError):
+            res = None
+        n_imgs = self.bundlePrimitive.poses.shape[0] if "pose" in self.bundlePrimitive.groups else self.detection.max_ims
+        per_board = int(np.prod(shape[1:])) if len(shape) > 1 else n_keys
+        board_of_key = np.arange(n_keys) // per_board
+        no_intr = "calc_initial_params: the camset holds no intrinsics (camset[idc].intrinsic / .distortion_coefs)"
+        try:
+            est = ch.estimate_intrinsics(self._flat_detections(), self.point_data.reshape((-1, 3)), n_cams=n_cams, n_imgs=n_imgs,
+                                         board_of_key=board_of_key, res=res, refine=True, device=self.op_fun.device)
+        except ch._capi.PcsError as e:
+            if e.code != ch._capi.PCS_ERR_NODEVICE:
+                raise
+            raise ValueError(f"{no_intr} and no device is visible to estimate them: pass intr (C, 9)") from e
+        self.initial_intrinsics = est
+        lost = [name for idc, name in enumerate(self.cam_names)
+                if est.status[idc] == ch.INTR_NOT_ESTIMATED and "int" not in self.fixed_params.get(name, {})]
+        if lost:
+            raise ValueError(f"{no_intr} and the planar views of {lost} do not give an estimate: pass intr (C, 9)")
+        return np.where(np.isfinite(est.intr), est.intr, 0.0)   # rows of fixed cameras without an estimate are replaced below
 
     def get_detection_data(self, flatten=False) -> np.ndarray:  # th:387-406
         detection = self.detection
