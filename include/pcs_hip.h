@@ -677,6 +677,60 @@ int pcs_intr_results(pcs_intrinsics_estimator *p, double *intr, int32_t *cam_inf
                      int32_t *group_info, double *pixel_stats);
 int pcs_intr_last_kernel_ms(pcs_intrinsics_estimator *p, float *kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * View-graph seeding of a rig (csrc/ba_riggraph.hpp).  Since pcs_version() 107.
+ * Replaces: estimate_camera_relative_poses (optimisation/template_handler.py:468-601), which takes the target of one image that EVERY
+ *           camera sees as the world and raises where there is none (template_handler.py:454-466), and scores the per-image candidates
+ *           with one pass of the legacy cost per camera (template_handler.py:528-578).  Here the co-visibility graph only has to be
+ *           connected.  M[c, i] is the view transform target -> camera c in image i (pcs_pnp_results; NaN where not estimated); a
+ *           3 x 4 transform is 12 doubles, rows [R | t].
+ *   pcs_rig_create            n_cams cameras (<= 46340), n_imgs images, a template of n_keys points (no counterpart: a handle)
+ *   pcs_rig_destroy           frees the handle (no counterpart)
+ *   pcs_rig_set_cameras       intr (n_cams, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2] (template_handler.py:504-507: K and dists)
+ *   pcs_rig_set_template      points (n_keys, 3): target.point_data flattened (template_handler.py:511).  frame (4 doubles, or NULL)
+ *                             receives the centroid pbar and the RMS distance rho of the points from it.
+ *   pcs_rig_set_observations  host arrays, copied: as pcs_pnp_set_observations, plus view_im (n_views) the image of every view; views
+ *                             sorted by (camera, image); cameras, images and keys are range-checked -> PCS_ERR_RANGE
+ *                             (template_handler.py:537-543 hands the same table to the cost)
+ *   pcs_rig_set_view_poses    poses (n_cams, n_imgs, 6) = [rotvec, t] of M[c, i], NaN where there is none (the Mat_ac array of
+ *                             template_handler.py:484-491)
+ *   pcs_rig_run_edges         queue the edge consensus on `stream` (NULL = the handle's): per camera pair a < b (lexicographic order,
+ *                             n_cams (n_cams - 1) / 2 pairs) the candidates T_i = M[a, i] inv(M[b, i]) of the n images both see, the
+ *                             distance d(T_i, T_j)^2 = (rho^2 / 3)(6 - 2 tr(R_i' R_j)) + |(R_i - R_j) m_b + t_i - t_j|^2 with
+ *                             m_b = mean_j M[b, j] pbar, and the medoid: the candidate of smallest S_i = sum_j d(T_i, T_j), ties to the
+ *                             lowest image (replaces the single reference image of template_handler.py:493-497)
+ *   pcs_rig_edges             copy the edge outputs to the host (any pointer may be NULL; blocking): info (pairs, 2) int32 {n, medoid
+ *                             image or -1}; T (pairs, 12) camera b -> camera a (NaN for n = 0); stats (pairs, 3) = {sigma = S / (n - 1)
+ *                             (0 for n = 1, NaN for n = 0), S of the medoid, S of the runner-up (+inf for n < 2)}
+ *   pcs_rig_set_extrinsics    ext (n_cams, 12) world -> camera, composed by the caller along a tree through the pairs (the Mrt_ac of
+ *                             template_handler.py:497)
+ *   pcs_rig_run_scores        queue the scoring: W[c', i] = inv(E_c') M[c', i] for every camera and image (template_handler.py:499-502,
+ *                             without the forward fill of :528-532) and, for every view (c, i) and every candidate camera c', the sum over
+ *                             the view's detections of |project_c(E_c W[c', i] p_k) - uv| with the legacy cost's formulas
+ *                             (compiled_helpers.py:518-549) -> partial[c', view]; errors[c', i] adds the views of image i in view order
+ *                             (template_handler.py:535-560 for all cameras in one pass over the table).  NaN where W[c', i] is.
+ *   pcs_rig_results           copy the scoring outputs to the host (any pointer may be NULL; blocking): W (n_cams, n_imgs, 12),
+ *                             errors (n_cams, n_imgs), partial (n_cams, n_views) (the `errors` list of template_handler.py:518-560)
+ *   pcs_rig_last_kernel_ms    device time of the last edge run (view matrices + edge kernel), of the last preparation (W and the
+ *                             projections) and of the last scoring (score + per-image sums); any pointer may be NULL.  PCS_ERR_STATE
+ *                             when the run asked for has not happened.
+ *   PCS_ERR_STATE from a run whose inputs are not all set, and from a read-back without a run on the current inputs.
+ */
+typedef struct pcs_rig_graph pcs_rig_graph;
+int pcs_rig_create(pcs_rig_graph **out, int device, int64_t n_cams, int64_t n_imgs, int64_t n_keys);
+int pcs_rig_destroy(pcs_rig_graph *p);
+int pcs_rig_set_cameras(pcs_rig_graph *p, const double *intr);
+int pcs_rig_set_template(pcs_rig_graph *p, const double *points, double *frame);
+int pcs_rig_set_observations(pcs_rig_graph *p, int64_t n_obs, const int32_t *key, const double *uv, int64_t n_views, const int64_t *start_inds,
+                             const int32_t *view_cam, const int32_t *view_im);
+int pcs_rig_set_view_poses(pcs_rig_graph *p, const double *poses);
+int pcs_rig_run_edges(pcs_rig_graph *p, void *stream);
+int pcs_rig_edges(pcs_rig_graph *p, int32_t *info, double *T, double *stats);
+int pcs_rig_set_extrinsics(pcs_rig_graph *p, const double *ext);
+int pcs_rig_run_scores(pcs_rig_graph *p, void *stream);
+int pcs_rig_results(pcs_rig_graph *p, double *W, double *errors, double *partial);
+int pcs_rig_last_kernel_ms(pcs_rig_graph *p, float *edges_ms, float *prepare_ms, float *scores_ms);
+
 /* Page-locked host memory for outputs: pcs_eval / pcs_eval_compact copy device -> host at PCIe rate
  * into such buffers (a pageable destination is several times slower).  Replaces nothing in the
  * reference (NumPy owns every array there, afb:561); SURVEY 8 f1 "zero-copy hand-off". */

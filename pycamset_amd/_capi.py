@@ -155,6 +155,18 @@ SYMBOLS = {
     "pcs_intr_results": (c_int, [_P, POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32),
                                  POINTER(c_double)]),
     "pcs_intr_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_rig_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64, c_int64]),
+    "pcs_rig_destroy": (c_int, [_P]),
+    "pcs_rig_set_cameras": (c_int, [_P, POINTER(c_double)]),
+    "pcs_rig_set_template": (c_int, [_P, POINTER(c_double), POINTER(c_double)]),
+    "pcs_rig_set_observations": (c_int, [_P, c_int64, POINTER(c_int32), POINTER(c_double), c_int64, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
+    "pcs_rig_set_view_poses": (c_int, [_P, POINTER(c_double)]),
+    "pcs_rig_run_edges": (c_int, [_P, _P]),
+    "pcs_rig_edges": (c_int, [_P, POINTER(c_int32), POINTER(c_double), POINTER(c_double)]),
+    "pcs_rig_set_extrinsics": (c_int, [_P, POINTER(c_double)]),
+    "pcs_rig_run_scores": (c_int, [_P, _P]),
+    "pcs_rig_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+    "pcs_rig_last_kernel_ms": (c_int, [_P, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
     "pcs_host_alloc": (c_int, [POINTER(_P), c_int64]),
     "pcs_host_free": (c_int, [_P]),
     "pcs_membench": (c_int, [c_int, c_int, c_int64, c_int, c_int, POINTER(c_float)]),

@@ -773,3 +773,175 @@ def _refine_intrinsics(est: IntrinsicsEstimate, d: np.ndarray, pts: np.ndarray, 
     refined = prob.get_bundle_adjustment_inputs(est.lm.x)[0]
     est.intr = np.where(free_cam[:, None], refined, est.intr_init)
     est.rms = rms_per_camera(est.lm.x)
+
+
+# ---- view-graph seeding (row f7: extrinsics along a tree through the co-visibility graph, candidates scored in one pass) ------------
+last_rig_kernel_ms = None
+
+
+@dataclass
+class EdgeConsensus:
+    """Relative camera transforms by consensus (``rig_edge_consensus``), per pair a < b in lexicographic order: ``pairs`` (P, 2);
+    ``n`` (P,) images both cameras have a pose for; ``medoid`` (P,) the image whose candidate M[a, i] inv(M[b, i]) was chosen (-1 for
+    n = 0); ``T`` (P, 3, 4) that transform, camera b -> camera a (NaN for n = 0); ``sigma`` (P,) mean distance of the medoid from the
+    other candidates in length units (0 for n = 1, NaN for n = 0); ``score`` / ``runner_up`` (P,) the summed distances of the medoid and
+    of the second-best candidate (+inf for n < 2); ``centroid`` (3,), ``rho``: the template's centroid and RMS radius."""
+    pairs: np.ndarray
+    n: np.ndarray
+    medoid: np.ndarray
+    T: np.ndarray
+    sigma: np.ndarray
+    score: np.ndarray
+    runner_up: np.ndarray
+    centroid: np.ndarray
+    rho: float
+
+
+def camera_pairs(n_cams: int) -> np.ndarray:
+    """(P, 2): the pairs a < b in the order of the device's edge outputs; pair (a, b) is row a (2 C - a - 1) / 2 + b - a - 1."""
+    a, b = np.triu_indices(int(n_cams), k=1)
+    return np.stack([a, b], axis=1)
+
+
+class RigGraph(_Handle):
+    """Owner of one ``pcs_rig_graph`` handle (include/pcs_hip.h): cameras, template, observation copies, view poses, extrinsics and the
+    outputs of the two runs (edges, scores) stay on the device across calls."""
+
+    _create, _destroy = "pcs_rig_create", "pcs_rig_destroy"
+
+    def __init__(self, n_cams: int, n_imgs: int, n_keys: int, device: int = 0):
+        super().__init__(device, n_cams, n_imgs, n_keys)
+        self.n_cams, self.n_imgs, self.n_keys, self.device = int(n_cams), int(n_imgs), int(n_keys), int(device)
+        self.n_pairs = self.n_cams * (self.n_cams - 1) // 2
+        self.n_views = 0
+        self.centroid, self.rho = None, None
+
+    def set_cameras(self, intr):
+        K = np.ascontiguousarray(intr, dtype=np.float64)
+        if K.shape != (self.n_cams, 9):
+            raise ValueError(f"expected intr ({self.n_cams}, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2]")
+        self._call("pcs_rig_set_cameras", self._h, self._ptr(K))
+
+    def set_template(self, points):
+        """-> (centroid (3,), rho): the template's centroid and the RMS distance of its points from it."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        if pts.shape[0] != self.n_keys:
+            raise ValueError(f"expected {self.n_keys} template points")
+        frame = np.empty(4)
+        self._call("pcs_rig_set_template", self._h, self._ptr(pts), self._ptr(frame))
+        self.centroid, self.rho = frame[:3].copy(), float(frame[3])
+        return self.centroid, self.rho
+
+    def set_observations(self, key, uv, start_inds, view_cam, view_im):
+        """Host arrays sorted by view, the views sorted by (camera, image) — ``group_by_view``'s order: key (n_obs,) int, uv (n_obs, 2),
+        start_inds (n_views + 1,), view_cam, view_im (n_views,) int."""
+        key = np.ascontiguousarray(key, dtype=np.int32)
+        uv = np.ascontiguousarray(uv, dtype=np.float64)
+        start = np.ascontiguousarray(start_inds, dtype=np.int64)
+        vcam = np.ascontiguousarray(view_cam, dtype=np.int32)
+        vim = np.ascontiguousarray(view_im, dtype=np.int32)
+        if start.ndim != 1 or start.shape[0] < 1 or vcam.shape != (start.shape[0] - 1,) or vim.shape != vcam.shape or uv.shape != (key.shape[0], 2):
+            raise ValueError("expected key (n_obs,), uv (n_obs, 2), start_inds (n_views + 1,), view_cam and view_im (n_views,)")
+        self._call("pcs_rig_set_observations", self._h, key.shape[0], self._ptr(key), self._ptr(uv), start.shape[0] - 1, self._ptr(start), self._ptr(vcam),
+                   self._ptr(vim))
+        self.n_views = start.shape[0] - 1
+
+    def set_view_poses(self, poses):
+        p = np.ascontiguousarray(poses, dtype=np.float64)
+        if p.shape != (self.n_cams, self.n_imgs, 6):
+            raise ValueError(f"expected view poses ({self.n_cams}, {self.n_imgs}, 6)")
+        self._call("pcs_rig_set_view_poses", self._h, self._ptr(p))
+
+    def run_edges(self, stream: int | None = None):
+        """Queue the edge consensus (asynchronous; fetch with ``edges()``)."""
+        self._call("pcs_rig_run_edges", self._h, _stream_arg(stream))
+
+    def edges(self):
+        """Wait for the last ``run_edges``: (info (P, 2) int32 [n, medoid image], T (P, 12), stats (P, 3) [sigma, S, runner-up S])."""
+        n = self.n_pairs
+        info, T, stats = np.empty((n, 2), dtype=np.int32), np.empty((n, 12)), np.empty((n, 3))
+        self._call("pcs_rig_edges", self._h, self._ptr(info), self._ptr(T), self._ptr(stats))
+        return info, T, stats
+
+    def set_extrinsics(self, ext):
+        E = np.ascontiguousarray(np.asarray(ext, dtype=np.float64).reshape(-1, 12))
+        if E.shape != (self.n_cams, 12):
+            raise ValueError(f"expected extrinsics ({self.n_cams}, 3, 4), world -> camera")
+        self._call("pcs_rig_set_extrinsics", self._h, self._ptr(E))
+
+    def run_scores(self, stream: int | None = None):
+        """Queue preparation, scoring and the per-image sums (asynchronous; fetch with ``results()``)."""
+        self._call("pcs_rig_run_scores", self._h, _stream_arg(stream))
+
+    def results(self, partial: bool = False):
+        """Wait for the last ``run_scores``: (W (C, I, 3, 4), errors (C, I)[, partial (C, n_views)])."""
+        W, err = np.empty((self.n_cams, self.n_imgs, 3, 4)), np.empty((self.n_cams, self.n_imgs))
+        part = np.empty((self.n_cams, self.n_views)) if partial else None
+        self._call("pcs_rig_results", self._h, self._ptr(W), self._ptr(err), self._ptr(part))
+        return (W, err, part) if partial else (W, err)
+
+    def last_edges_ms(self) -> float:
+        ms = self._ct.c_float(0.0)
+        self._call("pcs_rig_last_kernel_ms", self._h, self._ct.byref(ms), None, None)
+        return float(ms.value)
+
+    def last_scores_ms(self):
+        """-> (preparation, scoring) device times of the last ``run_scores``."""
+        a, b = self._ct.c_float(0.0), self._ct.c_float(0.0)
+        self._call("pcs_rig_last_kernel_ms", self._h, None, self._ct.byref(a), self._ct.byref(b))
+        return float(a.value), float(b.value)
+
+
+_rig_cache: dict = {}
+
+
+def _rig_graph(device: int, n_cams: int, n_imgs: int, n_keys: int) -> RigGraph:
+    return _cached_handle(_rig_cache, (int(device), int(n_cams), int(n_imgs), int(n_keys)), lambda: RigGraph(n_cams, n_imgs, n_keys, device))
+
+
+def rig_edge_consensus(view_poses, points, device: int = 0) -> EdgeConsensus:
+    """Per camera pair the medoid of the relative transforms M[a, i] inv(M[b, i]) over the images both cameras have a pose for, on the
+    device (include/pcs_hip.h pcs_rig_run_edges).  ``view_poses`` (C, I, 6) as ``estimate_view_poses`` returns them (NaN = no pose);
+    ``points`` the template (K, 3)."""
+    global last_rig_kernel_ms
+    vp = np.asarray(view_poses, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    if vp.ndim != 3 or vp.shape[2] != 6 or vp.shape[0] < 1 or vp.shape[1] < 1:
+        raise ValueError("expected view poses (C, I, 6)")
+    C, I = vp.shape[:2]
+    g = _rig_graph(device, C, I, pts.shape[0])
+    centroid, rho = g.set_template(pts)
+    g.set_view_poses(vp)
+    g.run_edges()
+    info, T, stats = g.edges()
+    last_rig_kernel_ms = g.last_edges_ms()
+    return EdgeConsensus(pairs=camera_pairs(C), n=info[:, 0].copy(), medoid=info[:, 1].copy(), T=T.reshape(-1, 3, 4), sigma=stats[:, 0].copy(),
+                         score=stats[:, 1].copy(), runner_up=stats[:, 2].copy(), centroid=centroid, rho=rho)
+
+
+def rig_candidate_scores(dct, points, intr, view_poses, ext, n_imgs: int, device: int = 0):
+    """Every camera's estimate of every image's target pose, W[c', i] = inv(E_c') M[c', i], and its summed reprojection error over ALL
+    detections of the image, errors[c', i], in one pass over the table on the device (include/pcs_hip.h pcs_rig_run_scores).
+    ``dct`` (N, 5) in any order; ``ext`` (C, 3, 4) world -> camera.  -> (W (C, I, 3, 4), errors (C, I)), NaN where camera c' has no pose
+    for image i."""
+    global last_rig_kernel_ms
+    d = np.asarray(dct, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    vp = np.asarray(view_poses, dtype=np.float64)
+    C, I = vp.shape[0], int(n_imgs)
+    if d.ndim != 2 or d.shape[1] != 5 or vp.shape != (C, I, 6):
+        raise ValueError("expected dct (N, 5) = [cam, im, key, u, v] and view poses (C, n_imgs, 6)")
+    if d.shape[0] and (d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 1].min() < 0 or d[:, 1].max() >= I):
+        raise ValueError("camera or image index of the table outside the view poses")
+    order, ids, start = group_by_view(d, I)
+    ds = d if order is None else d[order]
+    g = _rig_graph(device, C, I, pts.shape[0])
+    g.set_cameras(intr)
+    g.set_template(pts)
+    g.set_observations(ds[:, 2].astype(np.int32), ds[:, 3:5], start, (ids // I).astype(np.int32), (ids % I).astype(np.int32))
+    g.set_view_poses(vp)
+    g.set_extrinsics(ext)
+    g.run_scores()
+    W, errors = g.results()
+    last_rig_kernel_ms = sum(g.last_scores_ms())
+    return W, errors

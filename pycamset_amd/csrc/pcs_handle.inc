@@ -1,4 +1,4 @@
-// pcs_handle.inc — what the batched handles (pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc) share; included after pcs_common.inc.  Plain structs and
+// pcs_handle.inc — what the batched handles (pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc, pcs_rig.inc) share; included after pcs_common.inc.  Plain structs and
 // free functions; what they guarantee is in DESIGN.md, "Batched handles".
 
 // One growable device buffer: a pointer and its capacity in elements.

@@ -280,15 +280,22 @@ class TemplateBundleHandler:  # th:80-240
             "no start vector has been set: compute one from the detections with calc_initial_params() (template_handler.py:302-346, "
             "device PnP) and hand it to set_initial_params(), or supply your own")
 
-    def calc_initial_params(self, intr=None) -> np.ndarray:  # th:302-346
+    def calc_initial_params(self, intr=None, *, seeding: str = "reference") -> np.ndarray:  # th:302-346
         """A start vector from the detections: per-view target poses on the device (``compiled_helpers.estimate_view_poses``), the view
         graph of ``pose_seeding.estimate_camera_relative_poses`` (th:468-601), then the free entries in slab order — unfixed intrinsics,
         extrinsics and poses (plus, for the self and free chains, the free point scalars of the template).  ``intr``: (C, 9) rows
         [fx, cx, fy, cy, k0, k1, p0, p1, k2]; default: ``camset[idc].intrinsic`` / ``.distortion_coefs`` (th:321-329) and, where the
         camset holds none, the device's estimate from the planar views of the detections (``compiled_helpers.estimate_intrinsics`` with
         ``refine=True`` and ``camset[idc].res`` where present — the reference's ``initial_calibration``, abstract_target.py:263-343),
-        kept on ``initial_intrinsics``.  Sets ``missing_poses``; returns the vector without storing it.  The interactive outlier prompt (th:242-279) is not mirrored."""
-        from .pose_seeding import estimate_camera_relative_poses
+        kept on ``initial_intrinsics``.  Sets ``missing_poses``; returns the vector without storing it.  The interactive outlier prompt (th:242-279) is not mirrored.
+
+        ``seeding``: ``"reference"`` (default) is the reference's view graph, which needs an image that every camera sees and raises
+        ValueError without one; ``"graph"`` is ``pose_seeding.estimate_camera_relative_poses_graph``, which needs only a connected
+        co-visibility graph; ``"auto"`` takes the reference's and falls back to the graph on exactly that error."""
+        from .pose_seeding import estimate_camera_relative_poses, estimate_camera_relative_poses_graph
+
+        if seeding not in ("reference", "graph", "auto"):
+            raise ValueError(f"seeding must be 'reference', 'graph' or 'auto', got {seeding!r}")
 
         bp = self.bundlePrimitive
         n_cams = bp.intr.shape[0]
@@ -305,9 +312,18 @@ class TemplateBundleHandler:  # th:80-240
             if "int" in self.fixed_params.get(name, {}):
                 intr[idc] = self.fixed_params[name]["int"]
         n_imgs = bp.poses.shape[0] if "pose" in bp.groups else self.detection.max_ims
-        extr, poses, self.initial_per_im_error, missing = estimate_camera_relative_poses(
-            self._flat_detections(), self.point_data.reshape((-1, 3)), intr, n_cams, n_imgs,
-            ref_cam=self.problem_opts.get("ref_cam", 0), ref_pose=self.problem_opts.get("ref_pose", 0))
+        args = (self._flat_detections(), self.point_data.reshape((-1, 3)), intr, n_cams, n_imgs)
+        refs = {"ref_cam": self.problem_opts.get("ref_cam", 0), "ref_pose": self.problem_opts.get("ref_pose", 0)}
+        if seeding == "graph":
+            seeded = estimate_camera_relative_poses_graph(*args, **refs)
+        else:
+            try:
+                seeded = estimate_camera_relative_poses(*args, **refs)
+            except ValueError as e:
+                if seeding != "auto" or "Couldn't find an initial pose" not in str(e):
+                    raise
+                seeded = estimate_camera_relative_poses_graph(*args, **refs)
+        extr, poses, self.initial_per_im_error, missing = seeded
         self.missing_poses = missing
         parts = [intr[bp.intr_unfixed].ravel(), extr[bp.extr_unfixed].ravel()]
         if "pose" in bp.groups:

@@ -11,6 +11,8 @@ One deviation on purpose: the reference appends the final per-image costs to the
 2 I values; this returns the I final ones."""
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 from scipy.spatial.transform import Rotation
 
@@ -111,3 +113,167 @@ def estimate_camera_relative_poses(dct, points, intr, n_cams: int, n_imgs: int, 
     per_im_error = per_image_cost(Mat_rt)                                    # th:585-595
     Mat_rt[ref_pose] = np.eye(4)                                             # th:600
     return pose_from_4x4(Mrt_ac), pose_from_4x4(Mat_rt), per_im_error, missing
+
+
+# ---- seeding over the co-visibility graph: no image has to be seen by every camera --------------------------------------------------
+def rigid_inverse(M: np.ndarray) -> np.ndarray:
+    """(..., 4, 4) rigid transforms -> their inverses [R' | -R' t]."""
+    out = np.zeros_like(M)
+    Rt = np.swapaxes(M[..., :3, :3], -1, -2)
+    out[..., :3, :3] = Rt
+    out[..., :3, 3] = -np.einsum("...ab,...b->...a", Rt, M[..., :3, 3])
+    out[..., 3, 3] = 1.0
+    return out
+
+
+def to_4x4(T: np.ndarray) -> np.ndarray:
+    """(..., 3, 4) -> (..., 4, 4) with the row [0, 0, 0, 1] (NaN transforms stay NaN in their first three rows)."""
+    out = np.zeros(T.shape[:-2] + (4, 4))
+    out[..., :3, :] = T
+    out[..., 3, 3] = 1.0
+    return out
+
+
+def relative_gap(best: np.ndarray, runner_up: np.ndarray) -> np.ndarray:
+    """(runner-up - best) / runner-up: how clearly an argmin was decided; inf where there is no runner-up, 0 where both vanish."""
+    best, runner_up = np.asarray(best, dtype=np.float64), np.asarray(runner_up, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        gap = np.where(runner_up > 0, (runner_up - best) / runner_up, 0.0)
+    return np.where(np.isfinite(runner_up), gap, np.inf)
+
+
+def shortest_path_tree(n_cams: int, pairs: np.ndarray, cost: np.ndarray, ref_cam: int):
+    """Dijkstra from ``ref_cam`` over the undirected edges ``pairs`` (P, 2) of finite ``cost`` (P,) -> (parents (C,), -1 for ``ref_cam``
+    and for unreachable cameras; the reached cameras in the order they were settled).  Among equally distant cameras the lower index is
+    settled first, among equally good parents the lower index is kept."""
+    w = np.full((n_cams, n_cams), np.inf)
+    ok = np.isfinite(cost)
+    w[pairs[ok, 0], pairs[ok, 1]] = w[pairs[ok, 1], pairs[ok, 0]] = cost[ok]
+    dist = np.full(n_cams, np.inf)
+    dist[ref_cam] = 0.0
+    parents = np.full(n_cams, -1, dtype=np.int64)
+    done = np.zeros(n_cams, dtype=bool)
+    settled = []
+    for _ in range(n_cams):
+        u = int(np.argmin(np.where(done, np.inf, dist)))   # the first of equal minima: the lowest index
+        if done[u] or not np.isfinite(dist[u]):
+            break
+        done[u] = True
+        settled.append(u)
+        nd = dist[u] + w[u]
+        better = ~done & ((nd < dist) | ((nd == dist) & np.isfinite(nd) & (u < parents)))
+        dist[better], parents[better] = nd[better], u
+    return parents, settled
+
+
+@dataclass
+class RigGraphInfo:
+    """Diagnostics of ``estimate_camera_relative_poses_graph``: per camera pair a < b (``pairs`` (P, 2), lexicographic) the number of
+    shared images ``n``, the ``medoid`` image, the spread ``sigma`` and the relative ``gap`` between the medoid's score and the
+    runner-up's, the transform ``T`` (P, 3, 4) and the tree cost ``edge_cost`` = sigma + rho / n; the tree's ``parents`` (C,) (-1 for
+    ``ref_cam``); per image ``best_cam`` (-1: missing) and ``error_gap``, the relative gap between the lowest and the second lowest
+    candidate error; the full ``errors`` (C, I) matrix (NaN: camera c has no estimate of image i); ``dependent`` (C, I): image i is
+    the medoid image of the edge from camera c to its parent, where c's estimate repeats the parent's and is no candidate; ``rho``."""
+    pairs: np.ndarray
+    n: np.ndarray
+    medoid: np.ndarray
+    sigma: np.ndarray
+    gap: np.ndarray
+    T: np.ndarray
+    edge_cost: np.ndarray
+    parents: np.ndarray
+    best_cam: np.ndarray
+    error_gap: np.ndarray
+    errors: np.ndarray
+    dependent: np.ndarray
+    rho: float
+
+
+def estimate_camera_relative_poses_graph(dct, points, intr, n_cams: int, n_imgs: int, ref_cam: int = 0, ref_pose: int = 0, *, view_pose_fn=None,
+                                         edge_fn=None, score_fn=None, return_graph: bool = False):
+    """-> (extr (C, 6), poses (I, 6), per_im_error (I,), missing (I,) bool) like ``estimate_camera_relative_poses``, for any rig whose
+    co-visibility graph is connected: no image has to be seen by every camera.
+
+    1. Per camera pair the relative transform is the medoid of M[a, i] inv(M[b, i]) over the images i both cameras have a pose for
+       (``edge_fn(view_poses, points)`` -> an object with the fields of ``compiled_helpers.EdgeConsensus``; default: the device's).
+    2. The extrinsics are composed along the shortest-path tree from ``ref_cam`` with edge cost sigma + rho / n (``shortest_path_tree``):
+       E_ref_cam = I, E_c = T[c, parent] E_parent.  Cameras the tree does not reach raise ValueError naming them.
+    3. Every camera's estimate W[c', i] = inv(E_c') M[c', i] of every image's target pose is scored over all detections of the image
+       (``score_fn(dct, points, intr, view_poses, ext (C, 3, 4), n_imgs)`` -> (W (C, I, 3, 4), errors (C, I)); default: the device's); the
+       image takes the candidate of lowest finite error, ties to the lowest camera.  Camera c is no candidate for the medoid image of the
+       edge to its parent: E_c is made from that very view, so its estimate there repeats the parent's and their errors tie up to
+       rounding by construction.  An image without a finite candidate is ``missing``
+       and takes the pose of the previous non-missing image (of the first one, when none precedes it).
+    4. The world becomes the target of ``ref_pose`` (of the first non-missing image, when that one is missing): that pose is exactly 0.
+
+    ``per_im_error`` is NaN for missing images.  ``return_graph=True`` appends a ``RigGraphInfo``."""
+    from . import compiled_helpers as ch
+
+    view_pose_fn = ch.estimate_view_poses if view_pose_fn is None else view_pose_fn
+    edge_fn = ch.rig_edge_consensus if edge_fn is None else edge_fn
+    score_fn = ch.rig_candidate_scores if score_fn is None else score_fn
+    dct = np.ascontiguousarray(dct, dtype=np.float64)
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    intr = np.asarray(intr, dtype=np.float64)
+    C, I = int(n_cams), int(n_imgs)
+    if intr.shape != (C, 9):
+        raise ValueError(f"expected intr ({C}, 9)")
+    if not 0 <= int(ref_cam) < C or not 0 <= int(ref_pose) < I:
+        raise ValueError(f"ref_cam must be in [0, {C}) and ref_pose in [0, {I})")
+    view_poses = np.asarray(view_pose_fn(dct, points, intr, n_imgs=I).poses, dtype=np.float64)
+    if view_poses.shape != (C, I, 6):
+        raise ValueError(f"view_pose_fn must return poses ({C}, {I}, 6)")
+    # 1. edges
+    edges = edge_fn(view_poses, points)
+    pairs, n = np.asarray(edges.pairs, dtype=np.int64).reshape(-1, 2), np.asarray(edges.n, dtype=np.int64)
+    sigma, T = np.asarray(edges.sigma, dtype=np.float64), to_4x4(np.asarray(edges.T, dtype=np.float64).reshape(-1, 3, 4))
+    usable = (n > 0) & (np.asarray(edges.medoid) >= 0) & np.isfinite(sigma)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        edge_cost = np.where(usable, sigma + float(edges.rho) / np.maximum(n, 1), np.inf)
+    # 2. tree
+    parents, settled = shortest_path_tree(C, pairs, edge_cost, int(ref_cam))
+    lost = sorted(set(range(C)) - set(settled))
+    if lost:
+        raise ValueError(f"Couldn't find an initial pose for all cameras: cameras {lost} share no estimated image with the cameras connected to camera {int(ref_cam)}.")
+    E = np.zeros((C, 4, 4))
+    E[int(ref_cam)] = np.eye(4)
+    medoid = np.asarray(edges.medoid, dtype=np.int64)
+    # E_c is made of camera c's and its parent's views of the edge's medoid image, so W[c, medoid] IS W[parent, medoid] up to rounding:
+    # there camera c is no candidate of its own (its error ties with the parent's by construction, and rounding would pick)
+    dependent = np.zeros((C, I), dtype=bool)
+    for c in settled[1:]:
+        p = int(parents[c])
+        a, b = min(c, p), max(c, p)
+        T_ab = T[a * (2 * C - a - 1) // 2 + b - a - 1]                        # camera b -> camera a
+        E[c] = (T_ab if c == a else rigid_inverse(T_ab)) @ E[p]
+        dependent[c, medoid[a * (2 * C - a - 1) // 2 + b - a - 1]] = True
+    # 3. candidates
+    W, errors = score_fn(dct, points, intr, view_poses, E[:, :3, :], I)
+    W, errors = to_4x4(np.asarray(W, dtype=np.float64).reshape(C, I, 3, 4)), np.asarray(errors, dtype=np.float64).reshape(C, I)
+    finite = np.isfinite(errors) & ~dependent
+    ranked = np.sort(np.where(finite, errors, np.inf), axis=0)
+    missing = ~finite.any(axis=0)
+    if missing.all():
+        raise ValueError("No image has an estimated target pose.")
+    best_cam = np.where(missing, -1, np.argmin(np.where(finite, errors, np.inf), axis=0))
+    per_im_error = np.where(missing, np.nan, ranked[0])
+    error_gap = relative_gap(ranked[0], ranked[1]) if C > 1 else np.full(I, np.inf)
+    pose = W[np.maximum(best_cam, 0), np.arange(I)]
+    first = int(np.argmin(missing))
+    for i in range(I):
+        if missing[i]:
+            pose[i] = pose[i - 1] if i > first else pose[first]
+    # 4. the world is the target of the reference pose
+    ref = int(ref_pose) if not missing[int(ref_pose)] else first
+    P_ref = pose[ref].copy()
+    pose = rigid_inverse(P_ref) @ pose
+    E = E @ P_ref
+    poses6 = pose_from_4x4(pose)
+    poses6[ref] = 0.0
+    out = (pose_from_4x4(E), poses6, per_im_error, missing)
+    if not return_graph:
+        return out
+    info = RigGraphInfo(pairs=pairs, n=n, medoid=medoid, sigma=sigma, dependent=dependent,
+                        gap=relative_gap(edges.score, edges.runner_up), T=T[:, :3, :], edge_cost=edge_cost, parents=parents, best_cam=best_cam,
+                        error_gap=error_gap, errors=errors, rho=float(edges.rho))
+    return out + (info,)
