@@ -731,6 +731,59 @@ int pcs_rig_run_scores(pcs_rig_graph *p, void *stream);
 int pcs_rig_results(pcs_rig_graph *p, double *W, double *errors, double *partial);
 int pcs_rig_last_kernel_ms(pcs_rig_graph *p, float *edges_ms, float *prepare_ms, float *scores_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-group reprojection statistics of a residual vector on the device (csrc/ba_groupstats.hpp).  Since pcs_version() 108.
+ * Replaces: what a user does after the solve, on the host, from a read-back residual: the mean of optimisation_handling.py:66-70
+ *           (mean_reprojection_error), the per-image error and its MAD test (optimisation/template_handler.py:242-279 with
+ *           utils/general_utils.py:108-133), and the per-view RMS that cv2.calibrateCameraExtended returns as perViewErrors.
+ * Per detection e = sqrt(ru^2 + rv^2); a detection whose e is not finite is counted in n_nonfinite and takes no part in anything else.
+ * Groupings (PCS_STATS_BY_*): camera (n_cams groups), image (n_imgs), key (n_keys), view = (camera, image) (n_cams * n_imgs, group
+ * c * n_imgs + i) and PCS_STATS_OVERALL, one group over all rows.  A group may be empty.  Inside a group the rows are taken in ascending
+ * table order, whatever the order of the table; sums go through fixed trees and there are no floating-point atomics: two runs give the
+ * same bits.  Median and MAD (median of |e - median|) are exact: the middle order statistic, or (a + b) * 0.5 of the two middle ones.
+ *   pcs_stats_create             n_cams, n_imgs, n_keys: the group counts (no counterpart: a handle)
+ *   pcs_stats_destroy            frees the handle (no counterpart)
+ *   pcs_stats_set_groups         host arrays cam, img, key (n) int32, the id columns of the detection table, in table order (the columns
+ *                                template_handler.py:537-543 hands to the per-image cost); an id outside [0, count) -> PCS_ERR_RANGE.
+ *                                Builds the group index on the device (a stable radix sort of the rows by group); it is kept until
+ *                                the next call.  A refused table leaves the handle without groups.  Blocking.
+ *   pcs_stats_set_groups_device  the same from device arrays; the range check runs on the device (PCS_ERR_RANGE names the lowest bad
+ *                                row, and the handle then has no groups).  Blocking.
+ *   pcs_stats_run                queue the kernels on `stream` (NULL = the handle's stream).  d_resid: 2 n doubles [u0, v0, u1, v1, ...]
+ *                                on the device: pcs_device_buffers / pcs_genchain_device_buffers of a PCS_F64 engine, or the caller's
+ *                                own (what optimisation_handling.py:66-70 reshapes to (-1, 2) on the host).  flags:
+ *                                PCS_STATS_NO_ORDER_STATISTICS leaves median and mad NaN and skips the selection.  Outputs (device
+ *                                buffers of the caller, or NULL = handle-owned), G = n_cams + n_imgs + n_keys + n_cams * n_imgs + 1
+ *                                groups in the order camera, image, key, view, overall: d_errors (n) = e; d_counts (3, G) int32 =
+ *                                count of finite rows, n_nonfinite, argmax (the table row of the largest finite e, the lowest row of
+ *                                equal ones, -1 for a group without finite rows); d_values (7, G) = sum_e, sum_e2, sum_ru, sum_rv,
+ *                                max_e, median, mad (max_e, median and mad are NaN for a group without finite rows).
+ *                                PCS_ERR_STATE: no groups set.
+ *   pcs_stats_results            copy one grouping's handle-owned outputs of the last run to the host (any pointer may be NULL;
+ *                                blocking); every array has the grouping's number of groups.  sum_e / count is the mean error (the
+ *                                overall one: optimisation_handling.py:66-70), sqrt(sum_e2 / count) the RMS (per view: OpenCV's
+ *                                perViewErrors), sum_ru / count and sum_rv / count the bias; median and mad are what
+ *                                utils/general_utils.py:108-133 computes on the host.  PCS_ERR_STATE: no run on the current groups,
+ *                                or the run wrote the asked outputs to caller buffers.
+ *   pcs_stats_errors             copy the handle-owned e (n) of the last run to the host (blocking) (the per-detection norm of
+ *                                optimisation_handling.py:66-70)
+ *   pcs_stats_last_kernel_ms     device time of the last index build, of the last error kernel and of the last statistics (gather +
+ *                                statistics kernel); any pointer may be NULL.  PCS_ERR_STATE when the part asked for has not run.
+ */
+typedef struct pcs_residual_stats pcs_residual_stats;
+enum { PCS_STATS_BY_CAMERA = 0, PCS_STATS_BY_IMAGE = 1, PCS_STATS_BY_KEY = 2, PCS_STATS_BY_VIEW = 3, PCS_STATS_OVERALL = 4 };
+#define PCS_STATS_NO_ORDER_STATISTICS 1
+enum { PCS_STATS_OUT_ERRORS = 1, PCS_STATS_OUT_COUNTS = 2, PCS_STATS_OUT_VALUES = 4 };
+int pcs_stats_create(pcs_residual_stats **out, int device, int64_t n_cams, int64_t n_imgs, int64_t n_keys);
+int pcs_stats_destroy(pcs_residual_stats *p);
+int pcs_stats_set_groups(pcs_residual_stats *p, int64_t n, const int32_t *cam, const int32_t *img, const int32_t *key);
+int pcs_stats_set_groups_device(pcs_residual_stats *p, int64_t n, const int32_t *d_cam, const int32_t *d_img, const int32_t *d_key);
+int pcs_stats_run(pcs_residual_stats *p, const double *d_resid, int flags, double *d_errors, int32_t *d_counts, double *d_values, void *stream);
+int pcs_stats_results(pcs_residual_stats *p, int grouping, int32_t *count, int32_t *n_nonfinite, int32_t *argmax, double *sum_e, double *sum_e2,
+                      double *sum_ru, double *sum_rv, double *max_e, double *median, double *mad);
+int pcs_stats_errors(pcs_residual_stats *p, double *errors);
+int pcs_stats_last_kernel_ms(pcs_residual_stats *p, float *index_ms, float *error_ms, float *stats_ms);
+
 /* Page-locked host memory for outputs: pcs_eval / pcs_eval_compact copy device -> host at PCIe rate
  * into such buffers (a pageable destination is several times slower).  Replaces nothing in the
  * reference (NumPy owns every array there, afb:561); SURVEY 8 f1 "zero-copy hand-off". */

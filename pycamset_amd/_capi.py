@@ -45,6 +45,9 @@ PNP_NOT_ESTIMATED, PNP_CONVERGED, PNP_MAX_ITER, PNP_NO_DECREASE = 0, 1, 2, 3
 INTR_MODEL_IDS = {"auto": 0, "full": 1, "focal": 2}
 INTR_NOT_ESTIMATED, INTR_FULL, INTR_FOCAL, INTR_FOCAL_FALLBACK = 0, 1, 2, 3
 INTR_GROUP_TOO_FEW, INTR_GROUP_USED, INTR_GROUP_NOT_PLANAR, INTR_GROUP_NOT_FINITE, INTR_GROUP_FIT_FAILED = 0, 1, 2, 3, 4
+# include/pcs_hip.h PCS_STATS_*: the groupings of the residual statistics, in the order of the device's outputs, and the run flag
+STATS_GROUPINGS = {"camera": 0, "image": 1, "key": 2, "view": 3, "overall": 4}
+STATS_NO_ORDER_STATISTICS = 1
 
 
 SYMBOLS = {
@@ -167,6 +170,15 @@ SYMBOLS = {
     "pcs_rig_run_scores": (c_int, [_P, _P]),
     "pcs_rig_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "pcs_rig_last_kernel_ms": (c_int, [_P, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+    "pcs_stats_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64, c_int64]),
+    "pcs_stats_destroy": (c_int, [_P]),
+    "pcs_stats_set_groups": (c_int, [_P, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "pcs_stats_set_groups_device": (c_int, [_P, c_int64, _P, _P, _P]),
+    "pcs_stats_run": (c_int, [_P, _P, c_int, _P, _P, _P, _P]),
+    "pcs_stats_results": (c_int, [_P, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_double), POINTER(c_double), POINTER(c_double),
+                                  POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
+    "pcs_stats_errors": (c_int, [_P, POINTER(c_double)]),
+    "pcs_stats_last_kernel_ms": (c_int, [_P, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
     "pcs_host_alloc": (c_int, [POINTER(_P), c_int64]),
     "pcs_host_free": (c_int, [_P]),
     "pcs_membench": (c_int, [c_int, c_int, c_int64, c_int, c_int, POINTER(c_float)]),

@@ -41,6 +41,7 @@
 #include "ba_pnp.hpp"
 #include "ba_intrinsics.hpp"
 #include "ba_riggraph.hpp"
+#include "ba_groupstats.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -53,6 +54,7 @@ using namespace pcs;
 #include "pcs_pnp.inc"
 #include "pcs_intrinsics.inc"
 #include "pcs_rig.inc"
+#include "pcs_stats.inc"
 #include "pcs_solver.inc"
 
 struct pcs_engine {

@@ -18,8 +18,8 @@ parameter groups exist, so here ONE table (``_CHAIN_GROUPS``) drives one primiti
 ``camset`` only needs ``get_names()`` / ``get_n_cams()`` and ``target`` only needs ``point_data`` — the
 attributes the reference touches on this path (th:116-129, th:160-163).  ``calc_initial_params`` (th:302-346) computes a
 start vector from the detections with the device's batched PnP (``pose_seeding``) and, where the camset holds no intrinsics, with
-the device's intrinsics estimate (``compiled_helpers.estimate_intrinsics``); outlier prompts and CameraSet
-reconstruction are outside the path.  ``get_initial_params`` returns what ``set_initial_params`` was given.
+the device's intrinsics estimate (``compiled_helpers.estimate_intrinsics``); the outlier prompt's decision is the option
+``"outliers"`` (``find_and_exclude_transform_outliers``); CameraSet reconstruction is outside the path.  ``get_initial_params`` returns what ``set_initial_params`` was given.
 
 Differences from the reference, on purpose:
   * The engine lays the parameter string out from the SLAB sizes (n_cams, max_ims, number of target
@@ -34,6 +34,7 @@ Differences from the reference, on purpose:
 """
 from __future__ import annotations
 
+import logging
 from copy import deepcopy
 
 import numpy as np
@@ -41,6 +42,8 @@ from scipy.sparse import csr_array
 
 from . import function_blocks as fb
 from .detections import TargetDetection  # noqa: F401  (re-exported: the handlers' input type)
+
+log = logging.getLogger(__name__)
 
 DEFAULT_OPTIONS = {  # th:24-31
     "verbosity": 2,
@@ -287,7 +290,8 @@ class TemplateBundleHandler:  # th:80-240
         [fx, cx, fy, cy, k0, k1, p0, p1, k2]; default: ``camset[idc].intrinsic`` / ``.distortion_coefs`` (th:321-329) and, where the
         camset holds none, the device's estimate from the planar views of the detections (``compiled_helpers.estimate_intrinsics`` with
         ``refine=True`` and ``camset[idc].res`` where present — the reference's ``initial_calibration``, abstract_target.py:263-343),
-        kept on ``initial_intrinsics``.  Sets ``missing_poses``; returns the vector without storing it.  The interactive outlier prompt (th:242-279) is not mirrored.
+        kept on ``initial_intrinsics``.  Sets ``missing_poses`` and runs ``find_and_exclude_transform_outliers`` on the per-image error of the
+        seeding (th:319), which excludes images only under ``options["outliers"] == "y"``; returns the vector without storing it.
 
         ``seeding``: ``"reference"`` (default) is the reference's view graph, which needs an image that every camera sees and raises
         ValueError without one; ``"graph"`` is ``pose_seeding.estimate_camera_relative_poses_graph``, which needs only a connected
@@ -325,12 +329,42 @@ class TemplateBundleHandler:  # th:80-240
                 seeded = estimate_camera_relative_poses_graph(*args, **refs)
         extr, poses, self.initial_per_im_error, missing = seeded
         self.missing_poses = missing
+        self.find_and_exclude_transform_outliers(self.initial_per_im_error)   # th:319
         parts = [intr[bp.intr_unfixed].ravel(), extr[bp.extr_unfixed].ravel()]
         if "pose" in bp.groups:
             parts.append(poses[bp.poses_unfixed].ravel())
         if "bdpt" in bp.groups:
             parts.append(self.flat_point_data[bp.bdpt_unfixed])
         return np.concatenate(parts)
+
+    def find_and_exclude_transform_outliers(self, per_im_error):  # th:242-279
+        """The MAD test (``diagnostics.mad_outliers``, threshold 20) on the per-image error over the images that are not missing yet,
+        for at most 10 rounds; a round without outliers ends the loop.  The reference asks at a prompt whether to exclude what it found
+        (th:268-270); here ``options["outliers"]`` holds the answer: ``"y"`` marks the images found as missing poses and tests the rest
+        again, ``"n"`` logs them and stops, and ``"ask"`` (the default: there is nobody to ask) does what ``"n"`` does.  Returns the
+        images found in all rounds (excluded only under ``"y"``)."""
+        from . import diagnostics
+
+        if self.missing_poses is None:
+            raise ValueError("missing poses should be initialised before calling this function")
+        answer = self.problem_opts.get("outliers", "ask")
+        per_im_error = np.asarray(per_im_error, dtype=np.float64)
+        found_all = []
+        for round_no in range(10):
+            not_missing = np.where(~np.asarray(self.missing_poses, dtype=bool))[0]
+            found = diagnostics.mad_outliers(per_im_error[not_missing], out_thresh=20)
+            if found is None:
+                log.info("no outlier images in round %d", round_no)
+                break
+            images = not_missing[found]
+            found_all.extend(int(i) for i in images)
+            log.critical("outlier images %s in round %d: these may prevent the calibration from converging", images.tolist(), round_no)
+            if answer != "y":
+                log.critical('not excluded (options["outliers"] is %r; "y" excludes them)', answer)
+                break
+            self.missing_poses = np.array(self.missing_poses, dtype=bool)
+            self.missing_poses[images] = True
+        return np.array(found_all, dtype=np.int64)
 
     def _estimate_initial_intrinsics(self, n_cams: int) -> np.ndarray:
         """(C, 9) from the detections alone.  A key's board is its index along the FIRST key axis of ``target.point_data`` — the face of a
