@@ -507,6 +507,10 @@ int pcs_get_loss(pcs_engine *h, int *kind, double *f_scale);
  *                                    buffer (n_pts,3) of the caller, or NULL = handle-owned output
  *   pcs_tri_points                   copy the handle-owned output to the host (blocking; PCS_ERR_STATE when the last run
  *                                    wrote to a caller buffer instead)
+ * Fewer than two views: start_inds may repeat a value (a point without views, also at the end of the table, where its start equals
+ * n_obs) or advance by one.  Such a point is not determined; pcs_tri_run writes three NaNs for it, whichever kernel runs, reads no
+ * observation outside [0, n_obs) for it, and the points around it keep the bits they have without it.  pcs_tri_refine leaves it at
+ * PCS_TRI_REFINE_NOT_REFINED with NaN points, NaN RMS values and its view count.
  * Runs on different streams are ordered by the handle (scratch and output are shared): an event recorded after every run
  * is waited for by the next run, by pcs_tri_points and by the setters, whatever stream the run was queued on.
  * pcs_triangulate is the stateless convenience form (temporary handle: allocations and copies on every call).
@@ -527,6 +531,13 @@ int pcs_tri_set_observations_device(pcs_triangulator *t, int64_t n_obs, const in
 int pcs_tri_group_device(pcs_triangulator *t, int64_t n, const int32_t *d_cam, const int32_t *d_feat, const double *d_uv, int64_t n_features,
                          int64_t *n_pts, int64_t *n_kept, int32_t *grouped, void *stream);
 int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream);
+/* What pcs_tri_run launches for this handle (read-only; since pcs_version() 109): out[0] lanes per point (1, 2, 4, 8 or 16), out[1]
+ * views per lane kept in registers (0 for the kernel that keeps every view in the global scratch), out[2] 1 for the register kernel and
+ * 0 for the scratch kernel, out[3] 1 when the points are visited in order of their view count and 0 for table order.  The geometry is
+ * fixed at pcs_tri_create from the environment switches PCS_TRI_LANES (1, 2, 4, 8, 16; anything else: 4), PCS_TRI_VARIANT (0: scratch
+ * kernel; 3: eight register views at four lanes; anything else: the default) and PCS_TRI_NO_SORT (set: table order); the default is
+ * {4, 6, 1, 1}.  The switches exist for A/B timing and tests: every geometry computes the same points to rounding. */
+int pcs_tri_launch_config(pcs_triangulator *t, int32_t out[4]);
 int pcs_tri_points(pcs_triangulator *t, double *pts);
 int pcs_tri_synchronize(pcs_triangulator *t, void *stream);
 int pcs_tri_last_kernel_ms(pcs_triangulator *t, float *kernel_ms);
@@ -554,7 +565,7 @@ int pcs_triangulate(int device, int64_t n_obs, const int32_t *cam, const double 
  * Defaults of the Python front end (pycamset_amd.compiled_helpers.REFINE_DEFAULTS): max_iter 10, ftol 1e-10, xtol 1e-10, gtol 0. */
 #define PCS_TRI_REFINE_RESIDUALS 1
 enum {
-    PCS_TRI_REFINE_NOT_REFINED = 0,   /* non-finite DLT start or a start behind a camera: the DLT point is returned unchanged */
+    PCS_TRI_REFINE_NOT_REFINED = 0,   /* non-finite DLT start (a point with fewer than two views included) or a start behind a camera: the DLT point is returned unchanged */
     PCS_TRI_REFINE_CONVERGED = 1,     /* ftol, xtol or gtol */
     PCS_TRI_REFINE_MAX_ITER = 2,      /* max_iter trials used */
     PCS_TRI_REFINE_NO_DECREASE = 3    /* the damping grew past 1e10 without a lower cost, or the damped system lost definiteness */

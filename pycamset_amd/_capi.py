@@ -136,6 +136,7 @@ SYMBOLS = {
     "pcs_tri_set_observations_device": (c_int, [_P, c_int64, _P, _P, c_int64, _P]),
     "pcs_tri_group_device": (c_int, [_P, c_int64, _P, _P, _P, c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_int32), _P]),
     "pcs_tri_run": (c_int, [_P, _P, _P]),
+    "pcs_tri_launch_config": (c_int, [_P, POINTER(c_int32)]),
     "pcs_tri_points": (c_int, [_P, POINTER(c_double)]),
     "pcs_tri_synchronize": (c_int, [_P, _P]),
     "pcs_tri_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),

@@ -205,6 +205,13 @@ class Triangulator(_Handle):
         handle-owned output (fetch it with ``points()``)."""
         self._call("pcs_tri_run", self._h, self._addr(d_pts), _stream_arg(stream))
 
+    def launch_config(self) -> tuple:
+        """What ``run`` launches for this handle (include/pcs_hip.h pcs_tri_launch_config): (lanes per point, register views per lane —
+        0 for the scratch kernel —, 1 for the register kernel, 1 for points visited in order of their view count)."""
+        out = (self._ct.c_int32 * 4)()
+        self._call("pcs_tri_launch_config", self._h, out)
+        return tuple(int(v) for v in out)
+
     def synchronize(self, stream: int | None = None):
         self._call("pcs_tri_synchronize", self._h, _stream_arg(stream))
 

@@ -22,7 +22,7 @@
 namespace pcs {
 
 // status codes (include/pcs_hip.h PCS_TRI_REFINE_*)
-constexpr int TRI_REFINE_NOT_REFINED = 0;   // non-finite DLT start or a start behind a camera: the DLT point is returned unchanged
+constexpr int TRI_REFINE_NOT_REFINED = 0;   // non-finite DLT start (fewer than two views included) or a start behind a camera: the DLT point is returned unchanged
 constexpr int TRI_REFINE_CONVERGED = 1;     // ftol, xtol or gtol
 constexpr int TRI_REFINE_MAX_ITER = 2;      // max_iter trials used
 constexpr int TRI_REFINE_NO_DECREASE = 3;   // the damping grew past its limit, or the damped system lost definiteness
@@ -209,6 +209,8 @@ __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *
         }
     }
     if (!live) return;
+    // A point with fewer than two views comes with a NaN start (triangulate_kernel) and is not refined.  Its RMS is NaN as well: one
+    // view gives a NaN cost, no view gives 0 / 0.  Its loads above are guarded by q < s1, so a point without views reads no observation.
     const double n_v = (double)(s1 - s0);
     if (g == 0) {
         pts_out[3 * j + 0] = X[0];

@@ -106,6 +106,9 @@ __global__ __launch_bounds__(256) void triangulate_kernel(const int32_t *__restr
     const bool live = gid < n_pts;  // whole groups are live or dead; dead groups still take part in the shuffles
     const int64_t j = live ? gid : n_pts - 1;
     const int64_t s0 = start[j], s1 = live ? start[j + 1] : s0;
+    // fewer than two views determine no point (one view: a rank-2 factor whose last pivots are rounding residue): three NaNs are
+    // written, and the group does not keep its wave in the iteration
+    const bool solve = live && s1 - s0 >= 2;
     double R[4][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     for (int64_t q = s0 + g; q < s1; q += G) {  // pass 1: undistort, Householder rows, fold the C rows into R
         const double *ct = cam_tab + (int64_t)cam[q] * TRI_CAM_STRIDE;
@@ -187,12 +190,12 @@ __global__ __launch_bounds__(256) void triangulate_kernel(const int32_t *__restr
             X0 = n0; X1 = n1; X2 = n2;
             done = it > 0 && !(change > 1e-14 * size);  // also leaves on NaN
         }
-        if (__all(done || !live)) break;  // the shuffles are wave-wide: leave together
+        if (__all(done || !solve)) break;  // the shuffles are wave-wide: leave together
     }
     if (live && g == 0) {
-        pts[3 * j + 0] = X0;
-        pts[3 * j + 1] = X1;
-        pts[3 * j + 2] = X2;
+        pts[3 * j + 0] = solve ? X0 : NAN;
+        pts[3 * j + 1] = solve ? X1 : NAN;
+        pts[3 * j + 2] = solve ? X2 : NAN;
     }
 }
 
@@ -294,7 +297,13 @@ __global__ __launch_bounds__(256) void triangulate_reg_kernel(const int32_t *__r
     const bool live = gid < n_pts;  // whole groups are live or dead; dead groups still take part in the shuffles
     const int64_t jv = live ? gid : n_pts - 1;
     const int64_t j = order ? order[jv] : jv;   // points of equal view counts side by side (tri_order_*_kernel)
-    const int64_t s0 = start[j], s1 = live ? start[j + 1] : s0;
+    // A group without views — a dead group, or a point whose start_inds repeat — takes the empty range at observation 0: a point
+    // without views at the end of the table starts at n_obs, one past the arrays, and an absent view below reads the range's first
+    // observation.  (A wave reads one only when one of its lanes has a view, so the arrays are not empty then.)
+    const int64_t a0 = start[j], a1 = start[j + 1];
+    const bool any = live && a1 > a0;
+    const int64_t s0 = any ? a0 : 0, s1 = any ? a1 : 0;
+    const bool solve = s1 - s0 >= 2;   // fewer than two views: three NaNs (triangulate_kernel)
     // the wave's largest number of register views per lane: the unrolled loops stop there (uniform)
     int nv = (int)((s1 - s0 - g + G - 1) / G);
     nv = nv < 0 ? 0 : (nv > V ? V : nv);
@@ -311,7 +320,7 @@ __global__ __launch_bounds__(256) void triangulate_reg_kernel(const int32_t *__r
         if (v >= nv_w) continue;
         const int64_t q = s0 + g + (int64_t)v * G;
         const bool have = q < s1;
-        const int64_t qc = have ? q : s0;   // some readable observation for absent views (dead groups: the last point's first)
+        const int64_t qc = have ? q : s0;   // some readable observation for absent views (a group without views: observation 0)
         const double *ct = cam_tab + (int64_t)cam[qc] * TRI_CAM_STRIDE;
         const double2 m = uv[qc];
         double uu, vv, inv_alpha, r[4], c0[4], c1[4];
@@ -422,12 +431,12 @@ __global__ __launch_bounds__(256) void triangulate_reg_kernel(const int32_t *__r
             X0 = n0; X1 = n1; X2 = n2;
             done = it > 0 && !(change > 1e-14 * size);  // also leaves on NaN
         }
-        if (__all(done || !live)) break;  // the shuffles are wave-wide: leave together
+        if (__all(done || !solve)) break;  // the shuffles are wave-wide: leave together
     }
     if (live && g == 0) {
-        pts[3 * j + 0] = X0;
-        pts[3 * j + 1] = X1;
-        pts[3 * j + 2] = X2;
+        pts[3 * j + 0] = solve ? X0 : NAN;
+        pts[3 * j + 1] = solve ? X1 : NAN;
+        pts[3 * j + 2] = solve ? X2 : NAN;
     }
 }
 

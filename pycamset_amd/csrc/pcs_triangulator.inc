@@ -56,6 +56,26 @@ int pcs_tri_create(pcs_triangulator **out, int device, int64_t n_cams) {
     return PCS_OK;
 }
 
+// what pcs_tri_run launches for this handle — the one place that turns the switches read at creation into a kernel geometry
+struct TriLaunch {
+    int lanes, reg_views;   // G; V (0: the scratch kernel)
+    bool sorted;            // the points are visited in order of their view count
+};
+static TriLaunch tri_launch(const pcs_triangulator *t) {
+    if (t->variant == 0) return {t->lanes, 0, false};
+    return {t->lanes, t->lanes == 4 && t->variant != 3 ? 6 : 8, t->sort_points};
+}
+
+int pcs_tri_launch_config(pcs_triangulator *t, int32_t out[4]) {
+    if (!t || !out) return fail(PCS_ERR_ARG, "pcs_tri_launch_config: bad arguments");
+    const TriLaunch l = tri_launch(t);
+    out[0] = l.lanes;
+    out[1] = l.reg_views;
+    out[2] = l.reg_views != 0;
+    out[3] = l.sorted;
+    return PCS_OK;
+}
+
 int pcs_tri_destroy(pcs_triangulator *t) {
     if (!t) return PCS_OK;
     t->core.destroy({&t->tab, &t->cam, &t->uv, &t->start, &t->scr, &t->scl, &t->pts, &t->count, &t->block_sums, &t->totals, &t->order, &t->hist, &t->rpts,
@@ -182,7 +202,8 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
     }
     HIPCHK(hipSetDevice(t->core.device));
     hipStream_t s = t->core.stream_or(stream);
-    const bool need_order = t->variant != 0 && t->sort_points && !t->order_valid && t->n_pts < (1ll << 31);
+    const TriLaunch launch = tri_launch(t);
+    const bool need_order = launch.sorted && !t->order_valid && t->n_pts < (1ll << 31);
     const int64_t obs_alloc = std::max<int64_t>(1, t->n_obs);
     OutSlot out{1, t->pts, d_pts, t->n_pts, 3 * sizeof(double)};
     bool grows = t->scr.grows(t->n_obs) || t->scl.grows(t->n_obs) || (need_order && t->order.grows(t->n_pts));
@@ -194,7 +215,7 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
     if (!rc && need_order) rc = t->order.grow(t->n_pts, sizeof(int32_t));
     if (rc) return rc;
     d_pts = out.as<double>();
-    const int lanes = t->lanes;
+    const int lanes = launch.lanes;
     const dim3 grid((unsigned)((t->n_pts * lanes + 255) / 256));
     if (need_order) {
         if ((rc = enqueue_group_order(t->cur_start, t->n_pts, t->hist.as<int32_t>(), t->order.as<int32_t>(), s))) return rc;
@@ -207,7 +228,7 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
     hipExtLaunchKernelGGL((triangulate_reg_kernel<G_, V_>), grid, dim3(256), 0, s, t->timer.e0, t->timer.e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
                           t->cur_start, t->tab.as<const double>(), t->scr.as<double4>(), t->scl.as<double2>(), d_pts, t->n_pts,                          \
                           t->order_valid ? t->order.as<const int32_t>() : nullptr)
-    if (t->variant == 0) {   // round 3's form (views in the global scratch, IEEE divides): kept for A/B (PCS_TRI_VARIANT=0)
+    if (launch.reg_views == 0) {   // round 3's form (views in the global scratch, IEEE divides): kept for A/B (PCS_TRI_VARIANT=0)
         if (lanes == 1) PCS_TRI_LAUNCH(1);
         else if (lanes == 2) PCS_TRI_LAUNCH(2);
         else if (lanes == 8) PCS_TRI_LAUNCH(8);
@@ -218,7 +239,7 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
         else if (lanes == 2) PCS_TRI_LAUNCH_REG(2, 8);
         else if (lanes == 8) PCS_TRI_LAUNCH_REG(8, 8);
         else if (lanes == 16) PCS_TRI_LAUNCH_REG(16, 8);
-        else if (t->variant == 3) PCS_TRI_LAUNCH_REG(4, 8);
+        else if (launch.reg_views == 8) PCS_TRI_LAUNCH_REG(4, 8);
         else PCS_TRI_LAUNCH_REG(4, 6);   // 24 views in registers at 156 VGPRs (three waves per SIMD): 47 us against 52 us for (4, 8); (4, 3) — four waves
                                          // per SIMD, 12 register views, the rest through the scratch records — 53 us, (4, 4) 49 us (profiles/r05/tri_bench_r05.log)
     }
