@@ -7,7 +7,7 @@
 //
 // Kernels: ba_kernels.hpp (evaluation, compaction, legacy cost), ba_matfree.hpp (J products without J),
 // ba_normal.hpp (J^T J / J^T r), ba_triangulate.hpp, ba_pnp.hpp, ba_intrinsics.hpp, ba_riggraph.hpp; device maths: ba_device.hpp.  This file: the pcs_engine handle + its part of the C ABI; one translation unit with
-// pcs_common.inc (errors, device queries), pcs_handle.inc (what the batched handles share), pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc, pcs_rig.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
+// pcs_common.inc (errors, device queries), pcs_handle.inc (what every handle shares), pcs_dettable.inc (the detection table of both engine kinds), pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc, pcs_rig.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -50,6 +50,7 @@ using namespace pcs;
 
 #include "pcs_common.inc"
 #include "pcs_handle.inc"
+#include "pcs_dettable.inc"
 #include "pcs_triangulator.inc"
 #include "pcs_pnp.inc"
 #include "pcs_intrinsics.inc"
@@ -59,7 +60,7 @@ using namespace pcs;
 
 struct pcs_engine {
     int chain = 0, dtype = 0, device = 0, P = 0;
-    int64_t n_cams = 0, n_imgs = 0, n_keys = 0, n_params = 0, n = 0;
+    int64_t n_cams = 0, n_imgs = 0, n_keys = 0, n_params = 0;
     int64_t extr_off = 0, pose_off = 0, point_off = 0;
     size_t msize = 8;   // bytes of a measurement scalar on the device (4 for PCS_F32); slabs and arithmetic are always FP64
     size_t osize = 8;   // bytes of the residual / Jacobian type written out (4 for PCS_F32 and PCS_MIXED)
@@ -88,12 +89,10 @@ struct pcs_engine {
     bool lazy_done = true;       // option "lazy_done_event" (A/B switch)
     bool lazy_any_stream = false;   // "lazy_done_event" = 2: also on caller streams (the caller keeps the stream alive until it resets the option)
     // static inputs
-    int32_t *d_cam = nullptr, *d_img = nullptr, *d_key = nullptr;  // split index arrays (only when the packed word does not fit)
-    uint32_t *d_packed = nullptr;      // cam | image | key bit fields, one word per detection (DetTable, ba_device.hpp)
-    int key_bits = 0, img_bits = 0;
+    DetStore det;                      // the detection table (pcs_dettable.inc); det.n = number of detections
     bool pack_indices = true;          // option "pack_indices" (A/B switch; takes effect at the next upload)
-    int32_t *d_order = nullptr;  // (cam, image)-sorted visiting order of a scattered table (normal equations), or NULL
-    int32_t *d_order_ck = nullptr, *d_order_ik = nullptr;  // (cam, key) / (image, key) orders for the point passes
+    DevBuf d_order;              // (cam, image)-sorted visiting order of a scattered table (normal equations), or empty
+    DevBuf d_order_ck, d_order_ik;   // (cam, key) / (image, key) orders for the point passes
     // the detection table copied out in the visiting orders (index words; measurements except for the (image, key) pass): the
     // passes then stream their inputs instead of gathering 4 + 16 scattered bytes per detection through the order
     void *d_sorted[3][5] = {};   // per pass (shared — only for a scattered table —, (cam, key), (image, key)): packed, cam, img, key, uv
@@ -101,32 +100,24 @@ struct pcs_engine {
     bool point_orders_tried = false;
     int normal_rows = 64;        // detections per LDS image of the normal-equations kernel (64 or 32)
     int waves_per_wg = 0;        // fused kernel: waves per workgroup (0 = automatic: fewer for small tables)
-    void *d_uv = nullptr;
-    std::vector<int32_t> h_cam, h_img, h_key;
     bool have_template = false;
     // per-step
-    double *d_param = nullptr;
+    DevBuf d_param;
     double *h_param = nullptr;  // pinned staging
-    void *d_cam_slab = nullptr, *d_pose_slab = nullptr, *d_points = nullptr;
-    void *d_sink = nullptr;  // 64 B: where tail lanes put their residual
+    DevBuf d_cam_slab, d_pose_slab, d_points;
+    DevBuf d_sink;  // 64 B: where tail lanes put their residual
     // scratch outputs for the host-buffer entry points
-    void *d_resid = nullptr, *d_jac = nullptr;
-    int64_t jac_capacity = 0, resid_capacity = 0;
+    DevBuf d_resid, d_jac;
     // compaction
-    uint32_t *d_keep = nullptr;
-    int64_t *d_row_off = nullptr;
+    DevBuf d_keep, d_row_off;   // uint32 masks, int64 offsets
     int64_t nnz = -1;
-    void *d_data = nullptr;
-    int64_t data_capacity = 0;
+    DevBuf d_data;
     // matrix-free operators (f2)
-    double *d_vin = nullptr, *d_vout = nullptr, *d_cost = nullptr;
-    int64_t vin_capacity = 0, vout_capacity = 0;
+    DevBuf d_vin, d_vout, d_cost;
     // normal equations (f2): scratch of the host-buffer entry point
-    double *d_H = nullptr;
-    int64_t H_capacity = 0;
+    DevBuf d_H;
     // legacy cost (f3)
-    void *d_im_points = nullptr, *d_cam_tab = nullptr;
-    int64_t im_points_capacity = 0;
+    DevBuf d_im_points, d_cam_tab;
     bool linearized = false;
     int normal_debug = 0;
     int normal_imgkey_wgs_per_cu = 0;   // 0 = default (48)
@@ -177,7 +168,7 @@ struct pcs_engine {
         int64_t off[9] = {};
         double *d_work = nullptr;      // one allocation: part | Q | G | wave_cost (n_waves: the robust loss's cost, shared pass)
         int64_t work_off[4] = {};
-    } det[2];
+    } det_pass[2];
 };
 
 // `done` is recorded LAZILY where that is safe (round 3): an event record is a packet of its own between two launches, and a
@@ -238,11 +229,31 @@ static int ring_read(pcs_engine *h, int64_t i, float *prep_ms, float *eval_ms) {
 static int64_t padded_points(int64_t n_keys) { return (n_keys * 3 + 3) & ~(int64_t)3; }
 
 static void free_det_tables(pcs_engine *h) {
-    for (auto &d : h->det) {
+    for (auto &d : h->det_pass) {
         if (d.d_idx) (void)hipFree(d.d_idx);
         if (d.d_work) (void)hipFree(d.d_work);
         d = pcs_engine::DetPass{};
     }
+}
+
+static void free_sorted_tables(pcs_engine *h) {
+    for (auto &t : h->d_sorted)
+        for (void *&b : t) {
+            if (b) (void)hipFree(b);
+            b = nullptr;
+        }
+}
+
+// everything a new detection table replaces (a smaller table gives its memory back); the caller has waited for the work that reads it
+static void release_table(pcs_engine *h) {
+    h->det.release();
+    for (DevBuf *b : {&h->d_order, &h->d_order_ck, &h->d_order_ik, &h->d_resid, &h->d_jac, &h->d_keep, &h->d_row_off, &h->d_data}) b->release();
+    free_sorted_tables(h);
+    free_det_tables(h);
+    h->point_orders_tried = false;
+    h->nnz = -1;
+    h->h_order.clear();
+    h->h_order_ck.clear();
 }
 
 extern "C" {
@@ -256,10 +267,7 @@ int pcs_create(pcs_engine **out, int chain, int dtype, int64_t n_cams, int64_t n
         return fail(PCS_ERR_ARG, "pcs_create: counts must be positive (cams %lld imgs %lld keys %lld)", (long long)n_cams,
                     (long long)n_imgs, (long long)n_keys);
     if (n_cams > (1 << 24) || n_imgs > (1 << 24) || n_keys > (1 << 26)) return fail(PCS_ERR_ARG, "pcs_create: counts too large");
-    int ndev = pcs_device_count();
-    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "pcs_create: no HIP device visible (this engine has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "pcs_create: device %d out of range [0,%d)", device, ndev);
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = open_device("pcs_create", device, "this engine has no CPU fallback", true)) return rc;
     pcs_engine *h = new pcs_engine();
     h->chain = chain;
     h->dtype = dtype;
@@ -276,34 +284,37 @@ int pcs_create(pcs_engine **out, int chain, int dtype, int64_t n_cams, int64_t n
     h->n_params = chain == PCS_CHAIN_TEMPLATE ? 15 * n_cams + 6 * n_imgs
                   : chain == PCS_CHAIN_SELF   ? 15 * n_cams + 6 * n_imgs + 3 * n_keys
                                               : 15 * n_cams + 3 * n_keys;
-#define CREATE_CHK(expr)                                                                           \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            int _rc = fail(PCS_ERR_HIP, "%s failed: %s (pcs_create)", #expr, hipGetErrorString(_e)); \
-            pcs_destroy(h); /* releases whatever was allocated so far */                           \
-            return _rc;                                                                            \
-        }                                                                                          \
-    } while (0)
-    hipDeviceProp_t prop;
-    CREATE_CHK(hipGetDeviceProperties(&prop, device));
-    h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    h->lds_limit = prop.maxSharedMemoryPerMultiProcessor > 0 ? prop.maxSharedMemoryPerMultiProcessor
-                   : prop.sharedMemPerBlock > 0            ? prop.sharedMemPerBlock
-                                                           : 64 * 1024;
-    CREATE_CHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->ev.assign(4, nullptr);
     h->ev_has_prep.assign(1, 0);
-    for (auto &e : h->ev) CREATE_CHK(hipEventCreate(&e));
-    CREATE_CHK(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-    CREATE_CHK(hipMalloc(&h->d_param, sizeof(double) * h->n_params));
-    CREATE_CHK(hipHostMalloc(reinterpret_cast<void **>(&h->h_param), sizeof(double) * h->n_params, hipHostMallocDefault));
-    CREATE_CHK(hipMalloc(&h->d_cam_slab, sizeof(double) * n_cams * CAM_STRIDE));
-    CREATE_CHK(hipMalloc(&h->d_pose_slab, sizeof(double) * std::max<int64_t>(1, h->n_imgs) * POSE_STRIDE));
-    CREATE_CHK(hipMalloc(&h->d_points, sizeof(double) * padded_points(n_keys)));
-    CREATE_CHK(hipMemset(h->d_points, 0, sizeof(double) * padded_points(n_keys)));
-    CREATE_CHK(hipMalloc(&h->d_sink, 64));
-#undef CREATE_CHK
+    // the steps of the set-up in order; the first that fails is named in the error and ends it
+    hipError_t e = hipSuccess;
+    const char *failed = nullptr;
+    auto step = [&](const char *what, hipError_t r) {
+        if (r != hipSuccess) e = r, failed = what;
+        return r == hipSuccess;
+    };
+    hipDeviceProp_t prop;
+    bool ok = step("hipGetDeviceProperties", hipGetDeviceProperties(&prop, device));
+    if (ok) {
+        h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        h->lds_limit = prop.maxSharedMemoryPerMultiProcessor > 0 ? prop.maxSharedMemoryPerMultiProcessor
+                       : prop.sharedMemPerBlock > 0            ? prop.sharedMemPerBlock
+                                                               : 64 * 1024;
+        ok = step("hipStreamCreateWithFlags", hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    }
+    for (auto &ev : h->ev) ok = ok && step("hipEventCreate", hipEventCreate(&ev));
+    ok = ok && step("hipEventCreateWithFlags(done)", hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+    ok = ok && step("hipHostMalloc(h_param)", hipHostMalloc(reinterpret_cast<void **>(&h->h_param), sizeof(double) * h->n_params, hipHostMallocDefault));
+    struct { const char *what; DevBuf &b; int64_t n; } fixed[] = {{"hipMalloc(d_param)", h->d_param, h->n_params}, {"hipMalloc(d_cam_slab)", h->d_cam_slab, n_cams * CAM_STRIDE},
+                                                                  {"hipMalloc(d_pose_slab)", h->d_pose_slab, std::max<int64_t>(1, h->n_imgs) * POSE_STRIDE},
+                                                                  {"hipMalloc(d_points)", h->d_points, padded_points(n_keys)}, {"hipMalloc(d_sink)", h->d_sink, 8}};
+    for (auto &f : fixed) ok = ok && step(f.what, f.b.alloc(f.n, sizeof(double)));
+    ok = ok && step("hipMemset(d_points)", hipMemset(h->d_points.p, 0, sizeof(double) * padded_points(n_keys)));
+    if (!ok) {
+        const int rc = fail(PCS_ERR_HIP, "%s failed: %s (pcs_create)", failed, hipGetErrorString(e));
+        pcs_destroy(h);   // releases whatever was allocated so far
+        return rc;
+    }
     *out = h;
     return PCS_OK;
 }
@@ -312,14 +323,9 @@ int pcs_destroy(pcs_engine *h) {
     if (!h) return PCS_OK;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    void *bufs[] = {h->d_cam, h->d_img, h->d_key, h->d_packed, h->d_order, h->d_order_ck, h->d_order_ik, h->d_uv, h->d_param, h->d_cam_slab, h->d_pose_slab, h->d_points,
-                    h->d_resid, h->d_jac, h->d_keep, h->d_row_off, h->d_data, h->d_vin, h->d_vout, h->d_cost, h->d_im_points, h->d_cam_tab, h->d_sink, h->d_H};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    for (auto &t : h->d_sorted)
-        for (void *b : t)
-            if (b) (void)hipFree(b);
-    free_det_tables(h);
+    release_table(h);   // what belongs to the detection table; then the buffers that outlive a table
+    for (DevBuf *b : {&h->d_param, &h->d_cam_slab, &h->d_pose_slab, &h->d_points, &h->d_sink, &h->d_vin, &h->d_vout, &h->d_cost, &h->d_H, &h->d_im_points, &h->d_cam_tab})
+        b->release();
     if (h->h_param) (void)hipHostFree(h->h_param);
     for (auto &e : h->ev)
         if (e) (void)hipEventDestroy(e);
@@ -331,29 +337,24 @@ int pcs_destroy(pcs_engine *h) {
 
 int64_t pcs_n_params(const pcs_engine *h) { return h ? h->n_params : -1; }
 int pcs_row_len(const pcs_engine *h) { return h ? h->P : -1; }
-int64_t pcs_n_detections(const pcs_engine *h) { return h ? h->n : -1; }
+int64_t pcs_n_detections(const pcs_engine *h) { return h ? h->det.n : -1; }
 
-static int upload_detections(pcs_engine *h, std::vector<int32_t> &cam, std::vector<int32_t> &img, std::vector<int32_t> &key,
-                             const double *uv, int64_t n) {
-    // range check: an out-of-range index would be an out-of-bounds slab read on the device.  The
-    // engine's own tables are only replaced once the new ones are known to be good.
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t c = cam[i], im = img[i], k = key[i];
-        if (c < 0 || c >= h->n_cams || k < 0 || k >= h->n_keys || (h->chain != PCS_CHAIN_FREE && (im < 0 || im >= h->n_imgs)))
-            return fail(PCS_ERR_RANGE, "detection %lld = (cam %d, im %d, key %d) outside (%lld, %lld, %lld)", (long long)i, c, im, k,
-                        (long long)h->n_cams, (long long)h->n_imgs, (long long)h->n_keys);
-    }
-    h->h_cam.swap(cam); h->h_img.swap(img); h->h_key.swap(key);
-    h->n = 0;  // stays 0 (= "no detections set") if an allocation or copy below fails
+static DetCounts det_counts(const pcs_engine *h) { return DetCounts{h->n_cams, h->n_imgs, h->n_keys, h->chain == PCS_CHAIN_FREE}; }
+
+static int upload_detections(pcs_engine *h, DetColumns &c, const double *uv) {
+    // the engine's own tables are only replaced once the new ones are known to be good
+    const DetCounts counts = det_counts(h);
+    if (const int rc = det_check_range(c, counts)) return rc;
+    const int64_t n = (int64_t)c.cam.size();
+    double locality = 1.0, segments = 1.0;
     {   // slab-read locality of the table, per 64-detection tile (drives the automatic variant choice)
         int64_t tiles = 0, good = 0, runs = 0;
-        const bool has_img = h->chain != PCS_CHAIN_FREE;
         for (int64_t t0 = 0; t0 < n; t0 += TILE, ++tiles) {
             const int64_t t1 = std::min<int64_t>(t0 + TILE, n);
             int64_t p0 = -1, p1 = -1, prev = -1;
             bool ok = true;
             for (int64_t i = t0; i < t1; ++i) {
-                const int64_t pr = ((int64_t)h->h_cam[i] << 32) | (has_img ? (uint32_t)h->h_img[i] : 0u);
+                const int64_t pr = ((int64_t)c.cam[i] << 32) | (counts.no_img ? 0u : (uint32_t)c.img[i]);
                 runs += pr != prev;   // an upper bound of the distinct pairs of the tile; exact for run-ordered tables
                 prev = pr;
                 if (pr == p0 || pr == p1) continue;
@@ -361,95 +362,42 @@ static int upload_detections(pcs_engine *h, std::vector<int32_t> &cam, std::vect
             }
             good += ok;
         }
-        h->tile_locality = tiles ? (double)good / (double)tiles : 1.0;
-        h->tile_segments = tiles ? (double)runs / (double)tiles : 1.0;
+        if (tiles) locality = (double)good / (double)tiles, segments = (double)runs / (double)tiles;
     }
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(wait_done_host(h));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->point_orders_tried = false;
-    for (void **b : {(void **)&h->d_cam, (void **)&h->d_img, (void **)&h->d_key, (void **)&h->d_packed, (void **)&h->d_order, (void **)&h->d_order_ck,
-                     (void **)&h->d_order_ik, &h->d_uv, &h->d_resid, &h->d_jac,
-                     (void **)&h->d_keep, (void **)&h->d_row_off, &h->d_data}) {
-        if (*b) HIPCHK(hipFree(*b));
-        *b = nullptr;
-    }
-    for (auto &t : h->d_sorted)
-        for (void *&b : t) {
-            if (b) HIPCHK(hipFree(b));
-            b = nullptr;
-        }
-    h->jac_capacity = h->resid_capacity = h->data_capacity = 0;
-    h->nnz = -1;
-    free_det_tables(h);
-    h->h_order.clear();
-    h->h_order_ck.clear();
-    if (n == 0) return PCS_OK;
-    // index word: cam | image | key bit fields when they fit 32 bits (12 -> 4 bytes per detection), else three arrays
-    auto bits_for = [](int64_t count) { int b = 0; while (((int64_t)1 << b) < count) ++b; return b; };
-    h->key_bits = bits_for(h->n_keys);
-    h->img_bits = h->chain == PCS_CHAIN_FREE ? 0 : bits_for(h->n_imgs);   // the free chain has no image column (its values are not range-checked)
-    if (h->pack_indices && h->key_bits + h->img_bits + bits_for(h->n_cams) <= 32 && h->key_bits + h->img_bits <= 31) {
-        std::vector<uint32_t> w(n);
-        for (int64_t i = 0; i < n; ++i)
-            w[i] = ((uint32_t)h->h_cam[i] << (h->key_bits + h->img_bits)) | ((h->img_bits ? (uint32_t)h->h_img[i] : 0u) << h->key_bits) | (uint32_t)h->h_key[i];
-        HIPCHK(hipMalloc(&h->d_packed, sizeof(uint32_t) * n));
-        HIPCHK(hipMemcpy(h->d_packed, w.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(hipMalloc(&h->d_cam, sizeof(int32_t) * n));
-        HIPCHK(hipMalloc(&h->d_img, sizeof(int32_t) * n));
-        HIPCHK(hipMalloc(&h->d_key, sizeof(int32_t) * n));
-        HIPCHK(hipMemcpy(h->d_cam, h->h_cam.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_img, h->h_img.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_key, h->h_key.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMalloc(&h->d_uv, h->msize * 2 * n));
-    if (h->msize == 8) {
-        HIPCHK(hipMemcpy(h->d_uv, uv, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> f(2 * n);
-        for (int64_t i = 0; i < 2 * n; ++i) f[i] = (float)uv[i];
-        HIPCHK(hipMemcpy(h->d_uv, f.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    }
-    if (h->tile_locality < 0.5 && n <= INT32_MAX) {
+    release_table(h);   // det.n stays 0 (= "no detections set") if an allocation or copy below fails
+    h->tile_locality = locality;
+    h->tile_segments = segments;
+    if (n > 0 && locality < 0.5 && n <= INT32_MAX) {
         // scattered table: a (cam, image)-sorted visiting order for the kernels whose result does not depend on
         // the row order (ba_normal_kernel keeps its accumulators per (cam, image) run)
         std::vector<int32_t> order(n);
         for (int64_t i = 0; i < n; ++i) order[i] = (int32_t)i;
-        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-            return h->h_cam[x] != h->h_cam[y] ? h->h_cam[x] < h->h_cam[y] : h->h_img[x] < h->h_img[y];
-        });
-        HIPCHK(hipMalloc(&h->d_order, sizeof(int32_t) * n));
-        HIPCHK(hipMemcpy(h->d_order, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return c.cam[x] != c.cam[y] ? c.cam[x] < c.cam[y] : c.img[x] < c.img[y]; });
+        if (const int rc = h->d_order.grow(n, sizeof(int32_t))) return rc;
+        HIPCHK(hipMemcpy(h->d_order.p, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
         h->h_order.swap(order);
     }
-    h->n = n;
-    return PCS_OK;
+    return h->det.upload(c, uv, counts, h->pack_indices, h->msize == 4);
 }
 
 int pcs_set_detections_table(pcs_engine *h, const double *det5, int64_t n) {
     if (!h || (!det5 && n > 0) || n < 0) return fail(PCS_ERR_ARG, "pcs_set_detections_table: bad arguments");
-    std::vector<int32_t> cam(n), img(n), key(n);
-    std::vector<double> uv(2 * n);
-    for (int64_t i = 0; i < n; ++i) {
-        for (int j = 0; j < 3; ++j)  // NaN / huge values have no int32 image: refuse instead of casting
-            if (!(det5[5 * i + j] > -1.0 && det5[5 * i + j] < 2147483648.0))
-                return fail(PCS_ERR_RANGE, "detection %lld: index column %d = %g is not an index", (long long)i, j, det5[5 * i + j]);
-        cam[i] = (int32_t)det5[5 * i + 0];  // int() cast like afb:214 / afb:375
-        img[i] = (int32_t)det5[5 * i + 1];
-        key[i] = (int32_t)det5[5 * i + 2];
-        uv[2 * i] = det5[5 * i + 3];
-        uv[2 * i + 1] = det5[5 * i + 4];
-    }
-    return upload_detections(h, cam, img, key, uv.data(), n);
+    DetColumns c;
+    std::vector<double> uv;
+    if (const int rc = det_parse(det5, n, c, uv)) return rc;
+    return upload_detections(h, c, uv.data());
 }
 
 int pcs_set_detections(pcs_engine *h, const int32_t *cam, const int32_t *img, const int32_t *key, const double *uv, int64_t n) {
     if (!h || n < 0 || (n > 0 && (!cam || !key || !uv || (!img && h->chain != PCS_CHAIN_FREE))))
         return fail(PCS_ERR_ARG, "pcs_set_detections: bad arguments");
-    std::vector<int32_t> c(cam, cam + n), k(key, key + n), im;
-    if (img) im.assign(img, img + n); else im.assign(n, 0);
-    return upload_detections(h, c, im, k, uv, n);
+    DetColumns c;
+    c.cam.assign(cam, cam + n), c.key.assign(key, key + n);
+    if (img) c.img.assign(img, img + n); else c.img.assign(n, 0);
+    return upload_detections(h, c, uv);
 }
 
 int pcs_set_template(pcs_engine *h, const double *points) {
@@ -458,7 +406,7 @@ int pcs_set_template(pcs_engine *h, const double *points) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(wait_done_host(h));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(h->d_points, points, sizeof(double) * 3 * h->n_keys, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_points.p, points, sizeof(double) * 3 * h->n_keys, hipMemcpyHostToDevice));
     h->have_template = true;
     return PCS_OK;
 }
@@ -568,16 +516,6 @@ int pcs_get_loss(pcs_engine *h, int *kind, double *f_scale) {
 // dispatch itself, without the extra barrier packets that hipEventRecord would put between kernels.
 struct EvPair { hipEvent_t start, stop; };
 
-static DetTable det_table(const pcs_engine *h) {
-    DetTable t{};
-    t.packed = h->d_packed;
-    t.cam = h->d_cam; t.img = h->d_img; t.key = h->d_key;
-    t.uv = h->d_uv;
-    t.key_bits = h->key_bits; t.img_bits = h->img_bits;
-    t.uv_f32 = h->msize == 4;
-    return t;
-}
-
 template <int CHAIN, int MODE, int VARIANT, typename TO, bool PREP = false>
 static hipError_t launch_eval_v(const EvalArgs &a, dim3 grid, int threads, size_t lds, hipStream_t s, EvPair ev) {
     auto kern = ba_eval_kernel<CHAIN, MODE, VARIANT, TO, PREP>;
@@ -678,8 +616,8 @@ static int launch_slab_prep(pcs_engine *h, const double *d_prm, hipStream_t s, h
     int64_t threads = slab_prep_threads(h->n_cams, h->n_imgs, has_pose);   // one per slab element
     if (copy_points) threads = std::max<int64_t>(threads, std::min<int64_t>(3 * h->n_keys, 1 << 16));
     const dim3 grid((unsigned)((threads + 63) / 64));
-    hipExtLaunchKernelGGL(slab_prep_kernel, grid, dim3(64), 0, s, start, stop, 0, d_prm, (double *)h->d_cam_slab,
-                          (double *)h->d_pose_slab, (double *)h->d_points, (int)h->n_cams, (int)h->n_imgs, (int)h->n_keys,
+    hipExtLaunchKernelGGL(slab_prep_kernel, grid, dim3(64), 0, s, start, stop, 0, d_prm, h->d_cam_slab.as<double>(),
+                          h->d_pose_slab.as<double>(), h->d_points.as<double>(), (int)h->n_cams, (int)h->n_imgs, (int)h->n_keys,
                           h->extr_off, h->pose_off, h->point_off, has_pose, copy_points);
     HIPCHK(hipGetLastError());
     h->linearized = true;
@@ -757,38 +695,38 @@ static hipError_t gather_rows(const int32_t *order, const void *src, void **dst,
 // (cam, key)- and (image, key)-sorted visiting orders for the point passes of the normal equations: built on the host
 // at the first normal-equations call of a self / free engine (two stable sorts, ~0.1 s at 1e6 detections)
 static int build_point_orders(pcs_engine *h) {
-    const int64_t n = h->n;
+    const int64_t n = h->det.n;
     if (n <= 0) return PCS_OK;
     if (h->chain != PCS_CHAIN_TEMPLATE) {
         std::vector<int32_t> order(n);
         for (int pass = 0; pass < (h->chain == PCS_CHAIN_SELF ? 2 : 1); ++pass) {
-            const std::vector<int32_t> &major = pass == 0 ? h->h_cam : h->h_img;
+            const std::vector<int32_t> &major = pass == 0 ? h->det.h.cam : h->det.h.img;
             for (int64_t i = 0; i < n; ++i) order[i] = (int32_t)i;
             std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-                return major[x] != major[y] ? major[x] < major[y] : h->h_key[x] < h->h_key[y];
+                return major[x] != major[y] ? major[x] < major[y] : h->det.h.key[x] < h->det.h.key[y];
             });
-            int32_t **dst = pass == 0 ? &h->d_order_ck : &h->d_order_ik;
-            HIPCHK(hipMalloc(dst, sizeof(int32_t) * n));
-            HIPCHK(hipMemcpy(*dst, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
+            DevBuf &dst = pass == 0 ? h->d_order_ck : h->d_order_ik;
+            if (const int rc = dst.grow(n, sizeof(int32_t))) return rc;
+            HIPCHK(hipMemcpy(dst.p, order.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
             if (pass == 0) h->h_order_ck = order;
         }
     }
     // the table in each visiting order: the shared pass of a scattered table, the (cam, key) pass, the (image, key) pass (which
     // reads no measurements)
-    const int32_t *orders[3] = {h->d_order, h->d_order_ck, h->d_order_ik};
+    const int32_t *orders[3] = {h->d_order.as<int32_t>(), h->d_order_ck.as<int32_t>(), h->d_order_ik.as<int32_t>()};
     using u2 = __attribute__((ext_vector_type(2))) uint32_t;
     using u4 = __attribute__((ext_vector_type(4))) uint32_t;
     for (int pass = 0; pass < 3; ++pass) {
         if (!orders[pass]) continue;
         void **t = h->d_sorted[pass];
-        if (h->d_packed) {
-            HIPCHK(gather_rows<uint32_t>(orders[pass], h->d_packed, &t[0], n, h->stream));
+        if (h->det.packed.p) {
+            HIPCHK(gather_rows<uint32_t>(orders[pass], h->det.packed.p, &t[0], n, h->stream));
         } else {
-            HIPCHK(gather_rows<uint32_t>(orders[pass], h->d_cam, &t[1], n, h->stream));
-            HIPCHK(gather_rows<uint32_t>(orders[pass], h->d_img, &t[2], n, h->stream));
-            HIPCHK(gather_rows<uint32_t>(orders[pass], h->d_key, &t[3], n, h->stream));
+            HIPCHK(gather_rows<uint32_t>(orders[pass], h->det.cam.p, &t[1], n, h->stream));
+            HIPCHK(gather_rows<uint32_t>(orders[pass], h->det.img.p, &t[2], n, h->stream));
+            HIPCHK(gather_rows<uint32_t>(orders[pass], h->det.key.p, &t[3], n, h->stream));
         }
-        if (pass != PASS_IMGKEY) HIPCHK(h->msize == 4 ? gather_rows<u2>(orders[pass], h->d_uv, &t[4], n, h->stream) : gather_rows<u4>(orders[pass], h->d_uv, &t[4], n, h->stream));
+        if (pass != PASS_IMGKEY) HIPCHK(h->msize == 4 ? gather_rows<u2>(orders[pass], h->det.uv.p, &t[4], n, h->stream) : gather_rows<u4>(orders[pass], h->det.uv.p, &t[4], n, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return PCS_OK;
@@ -805,15 +743,9 @@ static int ensure_point_orders(pcs_engine *h) {
     }
     const std::string keep = g_err;
     (void)hipStreamSynchronize(h->stream);
-    for (int32_t **o : {&h->d_order_ck, &h->d_order_ik}) {
-        if (*o) (void)hipFree(*o);
-        *o = nullptr;
-    }
-    for (auto &t : h->d_sorted)
-        for (void *&b : t) {
-            if (b) (void)hipFree(b);
-            b = nullptr;
-        }
+    h->d_order_ck.release();
+    h->d_order_ik.release();
+    free_sorted_tables(h);
     g_err = keep;
     return rc;
 }
@@ -824,10 +756,10 @@ static int ensure_point_orders(pcs_engine *h) {
 // the build's `done` event (enqueue_normal's mark_done, order_after_done of the next enqueue) like every other output of the build.
 static int ensure_imgkey_uv(pcs_engine *h, hipStream_t s) {
     void **t = h->d_sorted[PASS_IMGKEY];
-    if (t[4] || !h->d_order_ik || h->n <= 0) return PCS_OK;
+    if (t[4] || !h->d_order_ik.p || h->det.n <= 0) return PCS_OK;
     using u2 = __attribute__((ext_vector_type(2))) uint32_t;
     using u4 = __attribute__((ext_vector_type(4))) uint32_t;
-    hipError_t e = h->msize == 4 ? gather_rows<u2>(h->d_order_ik, h->d_uv, &t[4], h->n, s) : gather_rows<u4>(h->d_order_ik, h->d_uv, &t[4], h->n, s);
+    hipError_t e = h->msize == 4 ? gather_rows<u2>(h->d_order_ik.as<int32_t>(), h->det.uv.p, &t[4], h->det.n, s) : gather_rows<u4>(h->d_order_ik.as<int32_t>(), h->det.uv.p, &t[4], h->det.n, s);
     if (e != hipSuccess) {
         if (t[4]) (void)hipFree(t[4]);
         t[4] = nullptr;
@@ -841,23 +773,23 @@ static int ensure_imgkey_uv(pcs_engine *h, hipStream_t s) {
 // run and one wave; logical runs = the segments of one key pair (one stretch in a sorted table; several when a pair re-appears);
 // groups = up to RED_RUNS_PER_GROUP logical runs of one camera; per camera its groups, per entity (image / key) its runs in camera order.
 static int ensure_det_tables(pcs_engine *h, int pass, int64_t tpw) {
-    pcs_engine::DetPass &D = h->det[pass];
-    if (D.n == h->n && D.tpw == tpw && D.d_idx) return PCS_OK;
+    pcs_engine::DetPass &D = h->det_pass[pass];
+    if (D.n == h->det.n && D.tpw == tpw && D.d_idx) return PCS_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(wait_done_host(h));
     if (D.d_idx) (void)hipFree(D.d_idx);
     if (D.d_work) (void)hipFree(D.d_work);
     D = pcs_engine::DetPass{};
-    const int64_t n = h->n;
+    const int64_t n = h->det.n;
     const bool has_pose = h->chain != PCS_CHAIN_FREE;
     const std::vector<int32_t> *order = nullptr;
-    if (pass == PASS_SHARED) { if (h->d_order) order = &h->h_order; }
+    if (pass == PASS_SHARED) { if (h->d_order.p) order = &h->h_order; }
     else order = &h->h_order_ck;
     if (order && (int64_t)order->size() != n) return fail(PCS_ERR_STATE, "deterministic mode: the host copy of a visiting order is missing");
     auto key_of = [&](int64_t d, int32_t &ka, int32_t &kb) {
         const int64_t i = order ? (*order)[d] : d;
-        ka = h->h_cam[i];
-        kb = pass == PASS_SHARED ? (has_pose ? h->h_img[i] : 0) : h->h_key[i];
+        ka = h->det.h.cam[i];
+        kb = pass == PASS_SHARED ? (has_pose ? h->det.h.img[i] : 0) : h->det.h.key[i];
     };
     const int64_t per_wave = tpw * TILE;
     const int64_t n_waves = (n + per_wave - 1) / per_wave;
@@ -975,8 +907,8 @@ static BlockLayout block_layout(const pcs_engine *h) {
 // alt_prm doubles and the outputs are written alt_out doubles further on; skip_prologue: the launch in front has prepared the slabs and zeroed the outputs.
 struct NormalTrial { const int32_t *stop = nullptr, *sel = nullptr; int64_t alt_prm = 0, alt_out = 0; bool skip_prologue = false; };
 static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, double *d_g, double *d_cost, hipStream_t s, bool blocked = false, const NormalTrial &t = {}) {
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
-    if (h->n > INT32_MAX) return fail(PCS_ERR_ARG, "normal equations: tables beyond 2^31 rows are not supported (visiting orders are int32)");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n > INT32_MAX) return fail(PCS_ERR_ARG, "normal equations: tables beyond 2^31 rows are not supported (visiting orders are int32)");
     if (h->chain == PCS_CHAIN_TEMPLATE && !h->have_template) return fail(PCS_ERR_STATE, "template points not set");
     const BlockLayout L = block_layout(h);
     if (!blocked) {
@@ -1003,8 +935,8 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
         const int prep_blocks = (int)((threads + 63) / 64);
         const int64_t n_h = blocked ? L.h_len() : h->n_params * h->n_params;
         const int zero_blocks = (int)std::min<int64_t>((n_h / 2 + 63) / 64 + 1, (int64_t)h->n_cu * 32);
-        hipLaunchKernelGGL(normal_prologue_kernel, dim3((unsigned)(prep_blocks + zero_blocks)), dim3(64), 0, s, d_prm, (double *)h->d_cam_slab,
-                           (double *)h->d_pose_slab, (double *)h->d_points, (int)h->n_cams, (int)h->n_imgs, (int)h->n_keys, h->extr_off,
+        hipLaunchKernelGGL(normal_prologue_kernel, dim3((unsigned)(prep_blocks + zero_blocks)), dim3(64), 0, s, d_prm, h->d_cam_slab.as<double>(),
+                           h->d_pose_slab.as<double>(), h->d_points.as<double>(), (int)h->n_cams, (int)h->n_imgs, (int)h->n_keys, h->extr_off,
                            h->pose_off, h->point_off, has_pose, copy_points, prep_blocks, d_H, n_h, d_g, h->n_params, d_cost, t.stop, t.sel, t.alt_prm, t.alt_out);
         HIPCHK(hipGetLastError());
         h->linearized = true;
@@ -1016,8 +948,8 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
         if (rc) return rc;
     }
     NormalArgs a{};
-    a.tab = det_table(h);
-    a.cam_slab = h->d_cam_slab; a.pose_slab = h->d_pose_slab; a.points = h->d_points;
+    a.tab = h->det.table();
+    a.cam_slab = h->d_cam_slab.p; a.pose_slab = h->d_pose_slab.p; a.points = h->d_points.p;
     a.H = d_H; a.g = d_g; a.cost = d_cost;
     if (blocked) {
         a.HB = d_H + L.a_len(); a.HC = a.HB + L.b_len();
@@ -1026,7 +958,7 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
         a.HB = a.HC = d_H;
         a.ldA = (int32_t)h->n_params; a.ldB = 0; a.tb = 0; a.trail_group = -1; a.trail_off = 0;
     }
-    a.n = h->n; a.n_tiles = (h->n + TILE - 1) / TILE;
+    a.n = h->det.n; a.n_tiles = (h->det.n + TILE - 1) / TILE;
     a.extr_off = h->extr_off; a.pose_off = h->pose_off; a.point_off = h->point_off;
     a.n_params = h->n_params;
     a.debug = h->normal_debug;
@@ -1054,9 +986,9 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
     const int n_pass = h->chain == PCS_CHAIN_TEMPLATE ? 1 : h->chain == PCS_CHAIN_SELF ? 3 : 2;
     for (int pass = 0; pass < n_pass; ++pass) {
         if (h->normal_debug & (256 << pass)) continue;   // profiling: time the passes one by one
-        a.order = pass == PASS_SHARED ? h->d_order : pass == PASS_CAMKEY ? h->d_order_ck : h->d_order_ik;
+        a.order = pass == PASS_SHARED ? h->d_order.as<int32_t>() : pass == PASS_CAMKEY ? h->d_order_ck.as<int32_t>() : h->d_order_ik.as<int32_t>();
         if (pass != PASS_SHARED && !a.order) return fail(PCS_ERR_STATE, "normal equations: key-sorted visiting order missing");
-        a.tab = det_table(h);
+        a.tab = h->det.table();
         if (a.order && h->sort_tables) {   // the pass's own copy of the table, already in visiting order
             if (pass == PASS_IMGKEY && h->loss) {   // a robust loss weighs the (image, key) pass's rows by their residuals: it needs the measurements too
                 const int rc = ensure_imgkey_uv(h, s);
@@ -1091,7 +1023,7 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
             if (h->deterministic) {   // the kernel stores its finished accumulators per segment, an ordered second pass sums them (csrc/ba_reduce.hpp)
                 const int rc = ensure_det_tables(h, pass, a.tiles_per_wave);
                 if (rc) return rc;
-                const pcs_engine::DetPass &D = h->det[pass];
+                const pcs_engine::DetPass &D = h->det_pass[pass];
                 if ((int64_t)grid.x != D.n_waves) return fail(PCS_ERR_STATE, "deterministic mode: launch geometry and segment table disagree");
                 a.part = D.d_work + D.work_off[0];
                 a.seg_base = D.d_idx + D.off[0];
@@ -1122,7 +1054,7 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
 
 // Queue slab_prep + the evaluation kernel on `s`.  d_prm must already hold the parameter string.
 static int enqueue_eval(pcs_engine *h, const double *d_prm, void *d_resid, void *d_out, bool compact, hipStream_t s) {
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     if (h->chain == PCS_CHAIN_TEMPLATE && !h->have_template) return fail(PCS_ERR_STATE, "template points not set");
     const int mode = (d_resid ? MODE_RESID : 0) | (d_out ? MODE_JAC : 0);
     if (!mode) return PCS_OK;
@@ -1131,7 +1063,7 @@ static int enqueue_eval(pcs_engine *h, const double *d_prm, void *d_resid, void 
     const bool slab_lds_forced = h->variant >= 0 && (h->variant & VAR_SLAB_LDS);
     const bool prep = !compact && !slab_lds_forced && !(h->variant >= 0 && (mode & MODE_JAC) && !(h->variant & VAR_TRANSPOSE)) &&
                       (h->fuse_prep > 0 || (h->fuse_prep < 0 && h->tile_locality >= 0.5 && h->tile_segments <= 2.5 &&
-                                            ((h->osize == 8 && (mode & MODE_JAC)) || h->n <= h->fuse_prep_max_n)));
+                                            ((h->osize == 8 && (mode & MODE_JAC)) || h->det.n <= h->fuse_prep_max_n)));
     hipEvent_t no_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     const bool timed = h->timing_every > 0 && (h->eval_count++ % h->timing_every) == 0;
     hipEvent_t *ev = timed ? ring_slot(h, !prep) : no_ev;
@@ -1144,18 +1076,18 @@ static int enqueue_eval(pcs_engine *h, const double *d_prm, void *d_resid, void 
     }
     EvalArgs a{};
     a.prm = d_prm; a.extr_off = h->extr_off; a.pose_off = h->pose_off; a.point_off = h->point_off;
-    a.tab = det_table(h);
-    a.cam_slab = h->d_cam_slab; a.pose_slab = h->d_pose_slab; a.points = h->d_points;
-    a.resid = d_resid; a.jac = d_out; a.sink = h->d_sink;
+    a.tab = h->det.table();
+    a.cam_slab = h->d_cam_slab.p; a.pose_slab = h->d_pose_slab.p; a.points = h->d_points.p;
+    a.resid = d_resid; a.jac = d_out; a.sink = h->d_sink.p;
     a.xcd_remap = h->xcd_remap ? 1 : 0;
-    a.n = h->n; a.n_cams = (int32_t)h->n_cams; a.n_imgs = (int32_t)h->n_imgs; a.n_keys = (int32_t)h->n_keys;
-    a.n_tiles = (h->n + TILE - 1) / TILE;
+    a.n = h->det.n; a.n_cams = (int32_t)h->n_cams; a.n_imgs = (int32_t)h->n_imgs; a.n_keys = (int32_t)h->n_keys;
+    a.n_tiles = (h->det.n + TILE - 1) / TILE;
     if (compact) {
-        a.keep = h->d_keep; a.row_off = h->d_row_off;
+        a.keep = h->d_keep.as<uint32_t>(); a.row_off = h->d_row_off.as<int64_t>();
         if (timed) HIPCHK(hipEventRecord(ev[2], s));
         hipError_t e;
         if (h->compact_variant == 0 && h->dtype == PCS_F64) {  // per-lane stores (first version, kept for A/B)
-            const int64_t blocks = std::min<int64_t>((h->n + WG_THREADS - 1) / WG_THREADS, (int64_t)h->n_cu * 8);
+            const int64_t blocks = std::min<int64_t>((h->det.n + WG_THREADS - 1) / WG_THREADS, (int64_t)h->n_cu * 8);
             e = launch_compact_t(h->chain, mode, a, dim3((unsigned)blocks), s);
         } else {
             const int64_t wpc = h->wgs_per_cu > 0 ? h->wgs_per_cu : 16;
@@ -1235,28 +1167,19 @@ static int stage_params(pcs_engine *h, const double *param_str, hipStream_t s) {
     // the pinned staging buffer is reused: wait until the previous copy out of it has been consumed
     HIPCHK(wait_done_host(h));
     memcpy(h->h_param, param_str, sizeof(double) * h->n_params);
-    HIPCHK(hipMemcpyAsync(h->d_param, h->h_param, sizeof(double) * h->n_params, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_param.as<double>(), h->h_param, sizeof(double) * h->n_params, hipMemcpyHostToDevice, s));
     HIPCHK(mark_done(h, s));
     return PCS_OK;
 }
 
 static int ensure_scratch(pcs_engine *h, bool want_resid, bool want_jac, bool want_data) {
     HIPCHK(hipSetDevice(h->device));
-    if (want_resid && h->resid_capacity < 2 * h->n) {
-        if (h->d_resid) HIPCHK(hipFree(h->d_resid));
-        HIPCHK(hipMalloc(&h->d_resid, sizeof(double) * 2 * h->n));  // doubles: the legacy cost of a mixed engine writes f64
-        h->resid_capacity = 2 * h->n;
-    }
-    if (want_jac && h->jac_capacity < 2 * h->n * h->P) {
-        if (h->d_jac) HIPCHK(hipFree(h->d_jac));
-        HIPCHK(hipMalloc(&h->d_jac, h->osize * 2 * h->n * h->P));
-        h->jac_capacity = 2 * h->n * h->P;
-    }
-    if (want_data && h->data_capacity < std::max<int64_t>(1, h->nnz)) {
-        if (h->d_data) HIPCHK(hipFree(h->d_data));
-        HIPCHK(hipMalloc(&h->d_data, h->osize * std::max<int64_t>(1, h->nnz)));
-        h->data_capacity = std::max<int64_t>(1, h->nnz);
-    }
+    if (want_resid)   // doubles: the legacy cost of a mixed engine writes f64
+        if (const int rc = h->d_resid.grow(2 * h->det.n, sizeof(double))) return rc;
+    if (want_jac)
+        if (const int rc = h->d_jac.grow(2 * h->det.n * h->P, h->osize)) return rc;
+    if (want_data)
+        if (const int rc = h->d_data.grow(std::max<int64_t>(1, h->nnz), h->osize)) return rc;
     return PCS_OK;
 }
 
@@ -1288,38 +1211,38 @@ int pcs_eval_device(pcs_engine *h, const double *param_str, void *d_resid, void 
     HIPCHK(hipSetDevice(h->device));
     int rc = stage_params(h, param_str, s);
     if (rc) return rc;
-    return enqueue_eval(h, h->d_param, d_resid, d_jac, false, s);
+    return enqueue_eval(h, h->d_param.as<double>(), d_resid, d_jac, false, s);
 }
 
 int pcs_eval(pcs_engine *h, const double *param_str, double *resid, double *jac) {
     if (!h || !param_str) return fail(PCS_ERR_ARG, "pcs_eval: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     int rc = ensure_scratch(h, resid != nullptr, jac != nullptr, false);
     if (rc) return rc;
-    rc = pcs_eval_device(h, param_str, resid ? h->d_resid : nullptr, jac ? h->d_jac : nullptr, nullptr);
+    rc = pcs_eval_device(h, param_str, resid ? h->d_resid.p : nullptr, jac ? h->d_jac.p : nullptr, nullptr);
     if (rc) return rc;
-    if (resid && (rc = download(h, resid, h->d_resid, 2 * h->n, h->stream))) return rc;
-    if (jac && (rc = download(h, jac, h->d_jac, 2 * h->n * h->P, h->stream))) return rc;
+    if (resid && (rc = download(h, resid, h->d_resid.p, 2 * h->det.n, h->stream))) return rc;
+    if (jac && (rc = download(h, jac, h->d_jac.p, 2 * h->det.n * h->P, h->stream))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return PCS_OK;
 }
 
 int pcs_device_buffers(pcs_engine *h, void **d_resid, void **d_jac) {
     if (!h) return fail(PCS_ERR_ARG, "pcs_device_buffers: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     int rc = ensure_scratch(h, d_resid != nullptr, d_jac != nullptr, false);
     if (rc) return rc;
-    if (d_resid) *d_resid = h->d_resid;
-    if (d_jac) *d_jac = h->d_jac;
+    if (d_resid) *d_resid = h->d_resid.p;
+    if (d_jac) *d_jac = h->d_jac.p;
     return PCS_OK;
 }
 
 int pcs_block_param_inds(pcs_engine *h, int64_t *out) {
     if (!h || !out) return fail(PCS_ERR_ARG, "pcs_block_param_inds: bad arguments");
     const int P = h->P;
-    for (int64_t i = 0; i < h->n; ++i) {
+    for (int64_t i = 0; i < h->det.n; ++i) {
         int64_t *o = out + i * P;
-        const int64_t c = h->h_cam[i], im = h->h_img[i], k = h->h_key[i];
+        const int64_t c = h->det.h.cam[i], im = h->det.h.img[i], k = h->det.h.key[i];
         int j = 0;
         for (int q = 0; q < 9; ++q) o[j++] = 9 * c + q;
         for (int q = 0; q < 6; ++q) o[j++] = h->extr_off + 6 * c + q;
@@ -1334,7 +1257,7 @@ int pcs_block_param_inds(pcs_engine *h, int64_t *out) {
 // keep-mask of one detection's local columns under `unfixed`
 static inline uint32_t keep_mask(const pcs_engine *h, const uint8_t *unfixed, int64_t i) {
     if (!unfixed) return (1u << h->P) - 1u;
-    const int64_t c = h->h_cam[i], im = h->h_img[i], k = h->h_key[i];
+    const int64_t c = h->det.h.cam[i], im = h->det.h.img[i], k = h->det.h.key[i];
     uint32_t m = 0;
     int j = 0;
     for (int q = 0; q < 9; ++q, ++j) m |= (uint32_t)(unfixed[9 * c + q] != 0) << j;
@@ -1354,8 +1277,8 @@ int pcs_csr_structure(pcs_engine *h, const uint8_t *unfixed, int64_t *indices, i
     std::vector<int64_t> cols(h->P);
     int64_t pos = 0;
     if (indptr) indptr[0] = 0;
-    for (int64_t i = 0; i < h->n; ++i) {
-        const int64_t c = h->h_cam[i], im = h->h_img[i], k = h->h_key[i];
+    for (int64_t i = 0; i < h->det.n; ++i) {
+        const int64_t c = h->det.h.cam[i], im = h->det.h.img[i], k = h->det.h.key[i];
         int j = 0;
         for (int q = 0; q < 9; ++q) cols[j++] = 9 * c + q;
         for (int q = 0; q < 6; ++q) cols[j++] = h->extr_off + 6 * c + q;
@@ -1379,11 +1302,11 @@ int pcs_csr_structure(pcs_engine *h, const uint8_t *unfixed, int64_t *indices, i
 
 int pcs_set_unfixed(pcs_engine *h, const uint8_t *unfixed, int64_t *nnz_out) {
     if (!h) return fail(PCS_ERR_ARG, "pcs_set_unfixed: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
-    std::vector<uint32_t> keep(h->n);
-    std::vector<int64_t> off(h->n);
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    std::vector<uint32_t> keep(h->det.n);
+    std::vector<int64_t> off(h->det.n);
     int64_t pos = 0;
-    for (int64_t i = 0; i < h->n; ++i) {
+    for (int64_t i = 0; i < h->det.n; ++i) {
         keep[i] = keep_mask(h, unfixed, i);
         off[i] = pos;
         pos += 2 * __builtin_popcount(keep[i]);
@@ -1391,10 +1314,10 @@ int pcs_set_unfixed(pcs_engine *h, const uint8_t *unfixed, int64_t *nnz_out) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(wait_done_host(h));   // an evaluation on any stream may still read the masks
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (!h->d_keep) HIPCHK(hipMalloc(&h->d_keep, sizeof(uint32_t) * h->n));
-    if (!h->d_row_off) HIPCHK(hipMalloc(&h->d_row_off, sizeof(int64_t) * h->n));
-    HIPCHK(hipMemcpy(h->d_keep, keep.data(), sizeof(uint32_t) * h->n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_row_off, off.data(), sizeof(int64_t) * h->n, hipMemcpyHostToDevice));
+    if (const int rc = h->d_keep.grow(h->det.n, sizeof(uint32_t))) return rc;   // released with the table: allocated once per table
+    if (const int rc = h->d_row_off.grow(h->det.n, sizeof(int64_t))) return rc;
+    HIPCHK(hipMemcpy(h->d_keep.p, keep.data(), sizeof(uint32_t) * h->det.n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_row_off.p, off.data(), sizeof(int64_t) * h->det.n, hipMemcpyHostToDevice));
     h->nnz = pos;
     if (nnz_out) *nnz_out = pos;
     return PCS_OK;
@@ -1407,7 +1330,7 @@ int pcs_eval_compact_device(pcs_engine *h, const double *param_str, void *d_resi
     HIPCHK(hipSetDevice(h->device));
     int rc = stage_params(h, param_str, s);
     if (rc) return rc;
-    return enqueue_eval(h, h->d_param, d_resid, d_data, true, s);
+    return enqueue_eval(h, h->d_param.as<double>(), d_resid, d_data, true, s);
 }
 
 int pcs_eval_compact(pcs_engine *h, const double *param_str, double *resid, double *data) {
@@ -1415,10 +1338,10 @@ int pcs_eval_compact(pcs_engine *h, const double *param_str, double *resid, doub
     if (h->nnz < 0) return fail(PCS_ERR_STATE, "pcs_set_unfixed has not been called");
     int rc = ensure_scratch(h, resid != nullptr, false, data != nullptr);
     if (rc) return rc;
-    rc = pcs_eval_compact_device(h, param_str, resid ? h->d_resid : nullptr, data ? h->d_data : nullptr, nullptr);
+    rc = pcs_eval_compact_device(h, param_str, resid ? h->d_resid.p : nullptr, data ? h->d_data.p : nullptr, nullptr);
     if (rc) return rc;
-    if (resid && (rc = download(h, resid, h->d_resid, 2 * h->n, h->stream))) return rc;
-    if (data && h->nnz > 0 && (rc = download(h, data, h->d_data, h->nnz, h->stream))) return rc;
+    if (resid && (rc = download(h, resid, h->d_resid.p, 2 * h->det.n, h->stream))) return rc;
+    if (data && h->nnz > 0 && (rc = download(h, data, h->d_data.p, h->nnz, h->stream))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     return PCS_OK;
 }
@@ -1426,17 +1349,13 @@ int pcs_eval_compact(pcs_engine *h, const double *param_str, double *resid, doub
 int pcs_legacy_cost(pcs_engine *h, const double *im_points, const double *proj, const double *intrinsics, const double *dists,
                     double *errors) {
     if (!h || !im_points || !proj || !intrinsics || !dists || !errors) return fail(PCS_ERR_ARG, "pcs_legacy_cost: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     if (h->chain == PCS_CHAIN_FREE) return fail(PCS_ERR_ARG, "pcs_legacy_cost: needs an engine with images (template or self chain)");
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int64_t n_pts = h->n_imgs * h->n_keys * 3;
-    if (n_pts > h->im_points_capacity) {
-        if (h->d_im_points) HIPCHK(hipFree(h->d_im_points));
-        HIPCHK(hipMalloc(&h->d_im_points, sizeof(double) * n_pts));
-        h->im_points_capacity = n_pts;
-    }
-    if (!h->d_cam_tab) HIPCHK(hipMalloc(&h->d_cam_tab, sizeof(double) * h->n_cams * LEGACY_STRIDE));
+    if (const int rc = h->d_im_points.grow(n_pts, sizeof(double))) return rc;
+    if (const int rc = h->d_cam_tab.grow(h->n_cams * LEGACY_STRIDE, sizeof(double))) return rc;
     int rc = ensure_scratch(h, true, false, false);
     if (rc) return rc;
     std::vector<double> tab((size_t)h->n_cams * LEGACY_STRIDE, 0.0);
@@ -1448,29 +1367,29 @@ int pcs_legacy_cost(pcs_engine *h, const double *im_points, const double *proj, 
         for (int j = 0; j < 5; ++j) t[16 + j] = dists[5 * c + j];
     }
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemcpyAsync(h->d_im_points, im_points, sizeof(double) * n_pts, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(h->d_cam_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_im_points.p, im_points, sizeof(double) * n_pts, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_cam_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));   // `tab` is a local
-    const int64_t n_tiles = (h->n + 63) / 64;
+    const int64_t n_tiles = (h->det.n + 63) / 64;
     const dim3 grid((unsigned)std::min<int64_t>((n_tiles + 3) / 4, (int64_t)h->n_cu * 16));
     hipEvent_t *ev = ring_slot(h, false);
-    hipExtLaunchKernelGGL(legacy_cost_kernel, grid, dim3(256), 0, s, ev[2], ev[3], 0, det_table(h), (const double *)h->d_im_points,
-                          (const double *)h->d_cam_tab, (double *)h->d_resid, h->n, h->n_keys, h->d_sink);
+    hipExtLaunchKernelGGL(legacy_cost_kernel, grid, dim3(256), 0, s, ev[2], ev[3], 0, h->det.table(), h->d_im_points.as<const double>(),
+                          h->d_cam_tab.as<const double>(), h->d_resid.as<double>(), h->det.n, h->n_keys, h->d_sink.p);
     HIPCHK(hipGetLastError());
     ++h->ev_count;
     h->events_valid = true;
     HIPCHK(mark_done(h, s));
-    return download(h, errors, h->d_resid, 2 * h->n, s, sizeof(double));
+    return download(h, errors, h->d_resid.p, 2 * h->det.n, s, sizeof(double));
 }
 
 int pcs_linearize(pcs_engine *h, const double *param_str) {
     if (!h || !param_str) return fail(PCS_ERR_ARG, "pcs_linearize: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     if (h->chain == PCS_CHAIN_TEMPLATE && !h->have_template) return fail(PCS_ERR_STATE, "template points not set");
     HIPCHK(hipSetDevice(h->device));
     int rc = stage_params(h, param_str, h->stream);
     if (rc) return rc;
-    rc = launch_slab_prep(h, h->d_param, h->stream);
+    rc = launch_slab_prep(h, h->d_param.as<double>(), h->stream);
     if (rc) return rc;
     HIPCHK(mark_done(h, h->stream));
     return PCS_OK;
@@ -1483,27 +1402,19 @@ int pcs_matfree(pcs_engine *h, int op, const double *in, double *out, double *co
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     HIPCHK(order_after_done(h, s));  // the slabs may have been prepared on a caller stream
-    const int64_t n_in = (op == OP_JTU) ? 2 * h->n : (op == OP_JV || op == OP_JTJV) ? h->n_params : 0;
-    const int64_t n_out = (op == OP_JV) ? 2 * h->n : h->n_params;
-    if (n_in > h->vin_capacity) {
-        if (h->d_vin) HIPCHK(hipFree(h->d_vin));
-        HIPCHK(hipMalloc(&h->d_vin, sizeof(double) * n_in));
-        h->vin_capacity = n_in;
-    }
-    if (n_out > h->vout_capacity) {
-        if (h->d_vout) HIPCHK(hipFree(h->d_vout));
-        HIPCHK(hipMalloc(&h->d_vout, sizeof(double) * n_out));
-        h->vout_capacity = n_out;
-    }
-    if (!h->d_cost) HIPCHK(hipMalloc(&h->d_cost, sizeof(double)));
-    if (n_in) HIPCHK(hipMemcpyAsync(h->d_vin, in, sizeof(double) * n_in, hipMemcpyHostToDevice, s));
-    if (op != OP_JV) HIPCHK(hipMemsetAsync(h->d_vout, 0, sizeof(double) * n_out, s));
-    if (op == OP_GRAD) HIPCHK(hipMemsetAsync(h->d_cost, 0, sizeof(double), s));
+    const int64_t n_in = (op == OP_JTU) ? 2 * h->det.n : (op == OP_JV || op == OP_JTJV) ? h->n_params : 0;
+    const int64_t n_out = (op == OP_JV) ? 2 * h->det.n : h->n_params;
+    if (const int rc = h->d_vin.grow(n_in, sizeof(double))) return rc;
+    if (const int rc = h->d_vout.grow(n_out, sizeof(double))) return rc;
+    if (const int rc = h->d_cost.grow(1, sizeof(double))) return rc;
+    if (n_in) HIPCHK(hipMemcpyAsync(h->d_vin.as<double>(), in, sizeof(double) * n_in, hipMemcpyHostToDevice, s));
+    if (op != OP_JV) HIPCHK(hipMemsetAsync(h->d_vout.as<double>(), 0, sizeof(double) * n_out, s));
+    if (op == OP_GRAD) HIPCHK(hipMemsetAsync(h->d_cost.as<double>(), 0, sizeof(double), s));
     MatfreeArgs a{};
-    a.tab = det_table(h);
-    a.cam_slab = h->d_cam_slab; a.pose_slab = h->d_pose_slab; a.points = h->d_points;
-    a.vin = h->d_vin; a.vout = h->d_vout; a.cost = h->d_cost;
-    a.n = h->n; a.n_tiles = (h->n + TILE - 1) / TILE;
+    a.tab = h->det.table();
+    a.cam_slab = h->d_cam_slab.p; a.pose_slab = h->d_pose_slab.p; a.points = h->d_points.p;
+    a.vin = h->d_vin.as<double>(); a.vout = h->d_vout.as<double>(); a.cost = h->d_cost.as<double>();
+    a.n = h->det.n; a.n_tiles = (h->det.n + TILE - 1) / TILE;
     a.extr_off = h->extr_off; a.pose_off = h->pose_off; a.point_off = h->point_off;
     a.n_params = (int32_t)h->n_params;
     // workgroup-private LDS accumulators (+ one reduction panel per wave) when they fit
@@ -1525,8 +1436,8 @@ int pcs_matfree(pcs_engine *h, int op, const double *in, double *out, double *co
     ++h->ev_count;
     h->events_valid = true;
     HIPCHK(mark_done(h, s));
-    HIPCHK(hipMemcpyAsync(out, h->d_vout, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
-    if (op == OP_GRAD && cost) HIPCHK(hipMemcpyAsync(cost, h->d_cost, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, h->d_vout.as<double>(), sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+    if (op == OP_GRAD && cost) HIPCHK(hipMemcpyAsync(cost, h->d_cost.as<double>(), sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return PCS_OK;
 }
@@ -1537,7 +1448,7 @@ int pcs_normal_equations_device(pcs_engine *h, const double *param_str, double *
     HIPCHK(hipSetDevice(h->device));
     int rc = stage_params(h, param_str, s);
     if (rc) return rc;
-    return enqueue_normal(h, h->d_param, d_H, d_g, d_cost, s);
+    return enqueue_normal(h, h->d_param.as<double>(), d_H, d_g, d_cost, s);
 }
 
 int pcs_normal_layout(const pcs_engine *h, int64_t *out5) {
@@ -1581,10 +1492,10 @@ int pcs_lm_trial_build(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
     LmTrialDesc d;
     d.who = "pcs_lm_trial_build"; d.device = h->device; d.n_cu = h->n_cu; d.n_params = h->n_params; d.L = block_layout(h);
     d.deterministic = h->deterministic != 0; d.spd_timeout_us = h->spd_timeout_us;
-    d.fused = h->fused_trial && d.L.n_lead > 0 && d.L.n_ent > 0 && h->n > 0;
+    d.fused = h->fused_trial && d.L.n_lead > 0 && d.L.n_ent > 0 && h->det.n > 0;
     d.selector = true;
-    d.empty_zero_state = h->n == 0;
-    d.slabs = FinishSlabs{(double *)h->d_cam_slab, (double *)h->d_pose_slab, (double *)h->d_points, h->n_cams, h->n_imgs, h->n_keys, h->extr_off, h->pose_off, h->point_off,
+    d.empty_zero_state = h->det.n == 0;
+    d.slabs = FinishSlabs{h->d_cam_slab.as<double>(), h->d_pose_slab.as<double>(), h->d_points.as<double>(), h->n_cams, h->n_imgs, h->n_keys, h->extr_off, h->pose_off, h->point_off,
                           h->chain != PCS_CHAIN_FREE, h->chain != PCS_CHAIN_TEMPLATE};
     return enqueue_lm_trial_build(d, b, stream ? (hipStream_t)stream : h->stream, [&](hipStream_t s, bool fused) {
         const int64_t alt_pk = b->packed[1] - b->packed[0], alt_ps = b->ps[1] - b->ps[0];   // doubles from state 0 to state 1
@@ -1607,23 +1518,17 @@ int pcs_lm_trial(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
 
 int pcs_normal_equations(pcs_engine *h, const double *param_str, double *H, double *g, double *cost) {
     if (!h || !param_str || !H || !g || !cost) return fail(PCS_ERR_ARG, "pcs_normal_equations: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     if (h->n_params > PCS_NORMAL_MAX_PARAMS)  // the same limit as enqueue_normal, checked BEFORE the scratch allocation
         return fail(PCS_ERR_ARG, "pcs_normal_equations: %lld parameters make a dense J^T J of %.1f GB (limit %d parameters: 32-bit offsets); use pcs_matfree",
                     (long long)h->n_params, (double)h->n_params * (double)h->n_params * 8e-9, PCS_NORMAL_MAX_PARAMS);
     HIPCHK(hipSetDevice(h->device));
     const int64_t need = h->n_params * h->n_params + h->n_params + 1;  // H | g | cost in one scratch buffer
-    if (h->H_capacity < need) {
-        if (h->d_H) HIPCHK(hipFree(h->d_H));
-        h->d_H = nullptr;
-        h->H_capacity = 0;
-        HIPCHK(hipMalloc(&h->d_H, sizeof(double) * need));
-        h->H_capacity = need;
-    }
-    double *d_g = h->d_H + h->n_params * h->n_params, *d_cost = d_g + h->n_params;
-    int rc = pcs_normal_equations_device(h, param_str, h->d_H, d_g, d_cost, nullptr);
+    if (const int rc = h->d_H.grow(need, sizeof(double))) return rc;
+    double *d_g = h->d_H.as<double>() + h->n_params * h->n_params, *d_cost = d_g + h->n_params;
+    int rc = pcs_normal_equations_device(h, param_str, h->d_H.as<double>(), d_g, d_cost, nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(H, h->d_H, sizeof(double) * h->n_params * h->n_params, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(H, h->d_H.as<double>(), sizeof(double) * h->n_params * h->n_params, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(g, d_g, sizeof(double) * h->n_params, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(cost, d_cost, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -1,4 +1,4 @@
-// pcs_genchain.inc — host side of generated chains (included last by pcs_engine.hip; uses pcs_common.inc and pcs_solver.inc).
+// pcs_genchain.inc — host side of generated chains (included last by pcs_engine.hip; uses pcs_common.inc, pcs_handle.inc, pcs_dettable.inc and pcs_solver.inc).
 //
 // A pcs_genchain owns a code object that pycamset_amd/chain_compiler.py compiled for ONE composition of the reference's function
 // blocks (csrc/ba_generic.hpp), the detection table, one Rodrigues slab per rigid parameter group and output scratch.  It is the
@@ -16,7 +16,7 @@ struct pcs_genchain {
     int P = 0, uses_template = 0, n_groups = 0, n_user = 0;
     int dtype = PCS_F64;   // PCS_F64 | PCS_F32 (float measurements and outputs) | PCS_MIXED (double measurements, float outputs); arithmetic is FP64
     int64_t user_off[GENERIC_MAX_GROUPS] = {};
-    int64_t n_params = 0, n_cams = 0, n_imgs = 0, n_keys = 0, n = 0;
+    int64_t n_params = 0, n_cams = 0, n_imgs = 0, n_keys = 0;
     int64_t group_off[GENERIC_MAX_GROUPS] = {};
     int32_t group_count[GENERIC_MAX_GROUPS] = {};
     int64_t intr_off = 0, point_off = 0;
@@ -27,23 +27,20 @@ struct pcs_genchain {
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {};
     bool timed = false;
-    double *d_param = nullptr, *d_tmpl = nullptr, *d_slab[GENERIC_MAX_GROUPS] = {};
-    void *d_sink = nullptr;
-    uint32_t *d_packed = nullptr;
-    int32_t *d_cam = nullptr, *d_img = nullptr, *d_key = nullptr;
-    double *d_uv = nullptr;
-    int key_bits = 0, img_bits = 0;
+    DevBuf d_param, d_tmpl, d_slab[GENERIC_MAX_GROUPS];
+    DevBuf d_sink;
+    DetStore det;                   // the detection table (pcs_dettable.inc); det.n = number of detections
     bool have_template = false;
-    void *d_resid = nullptr, *d_jac = nullptr, *d_data = nullptr;
-    uint64_t *d_keep = nullptr;     // per detection: bit j set = local column j is free
-    int64_t *d_row_off = nullptr;   // per detection: offset of its u row in the CSR data array
+    DevBuf d_resid, d_jac, d_data;
+    DevBuf d_keep;      // per detection, uint64: bit j set = local column j is free
+    DevBuf d_row_off;   // per detection, int64: offset of its u row in the CSR data array
     int64_t nnz = -1;
     // products with the materialised Jacobian (pcs_genchain_linearize / pcs_genchain_matfree)
     int n_blocks = 0;
     int32_t blk_col0[BLOCKROW_MAX_BLOCKS] = {}, blk_np[BLOCKROW_MAX_BLOCKS] = {}, blk_link[BLOCKROW_MAX_BLOCKS] = {};
     int64_t blk_start[BLOCKROW_MAX_BLOCKS] = {};
     bool linearized = false;
-    double *d_vin = nullptr, *d_vout = nullptr;   // max(n_params, 2N) + 1 each
+    DevBuf d_vin, d_vout;   // max(n_params, 2N) + 1 doubles each
     // normal equations (ba_blockgram.hpp): per pass — (camera, image) = the table's order, (camera, key), (image, key) — the detections
     // in that order (passes 1, 2: an index per position) cut into segments; built on first use from the host copy of the index columns
     struct GramTables {   // one set per mode ([0] default, [1] ORDERED): switching the mode back and forth (a sharded solve does) rebuilds nothing
@@ -53,9 +50,7 @@ struct pcs_genchain {
     } gram[2];
     // ORDERED mode (option "deterministic"): four orders, the groups of consecutive segments per order, a workspace of one matrix per segment
     bool deterministic = false, gram_keys = false;
-    double *d_gram_ws = nullptr;
-    int64_t gram_ws_cap = 0;
-    std::vector<int32_t> h_cam, h_img, h_key;
+    DevBuf d_gram_ws;
     int64_t spd_timeout_us = 250000;   // option "spd_timeout_us": how long the one-launch dense solve of an LM trial waits for a hand-over
     bool timing = true;                // option "timing": 0 = no start / stop events around the evaluation launches (an LM loop switches them off)
     int gram_debug = 0;                // option "gram_debug" (measurements only): 1 = no flush, 2 = no contraction
@@ -73,15 +68,13 @@ int pcs_genchain_destroy(pcs_genchain *h) {
     if (!h) return PCS_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *b : {(void *)h->d_param, (void *)h->d_tmpl, h->d_sink, (void *)h->d_packed, (void *)h->d_cam, (void *)h->d_img, (void *)h->d_key,
-                    (void *)h->d_uv, h->d_resid, h->d_jac, h->d_data, (void *)h->d_keep, (void *)h->d_row_off, (void *)h->d_vin, (void *)h->d_vout, (void *)h->d_gram_ws})
-        if (b) (void)hipFree(b);
+    h->det.release();
+    for (DevBuf *b : {&h->d_param, &h->d_tmpl, &h->d_sink, &h->d_resid, &h->d_jac, &h->d_data, &h->d_keep, &h->d_row_off, &h->d_vin, &h->d_vout, &h->d_gram_ws}) b->release();
+    for (DevBuf &b : h->d_slab) b.release();
     for (auto &g : h->gram)
         for (int q = 0; q < 4; ++q)
             for (int32_t *b : {g.d_seg[q], g.d_order[q], g.d_grp[q][0], g.d_grp[q][1], g.d_grp[q][2], g.d_gidx[q]})
                 if (b) (void)hipFree(b);
-    for (double *b : h->d_slab)
-        if (b) (void)hipFree(b);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->module) (void)hipModuleUnload(h->module);
@@ -98,10 +91,7 @@ int pcs_genchain_create(pcs_genchain **out, const char *code_object_path, int ro
         (dtype != PCS_F64 && dtype != PCS_F32 && dtype != PCS_MIXED))
         return fail(PCS_ERR_ARG, "pcs_genchain_create: bad arguments");
     *out = nullptr;
-    const int ndev = pcs_device_count();
-    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "pcs_genchain_create: no HIP device visible (generated chains have no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "pcs_genchain_create: device %d out of range [0,%d)", device, ndev);
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = open_device("pcs_genchain_create", device, "generated chains have no CPU fallback", true)) return rc;
     pcs_genchain *h = new pcs_genchain();
     h->device = device;
     h->uses_template = uses_template ? 1 : 0; h->n_groups = n_groups; h->n_user = n_user; h->dtype = dtype;
@@ -110,38 +100,43 @@ int pcs_genchain_create(pcs_genchain **out, const char *code_object_path, int ro
     h->intr_off = intr_off; h->point_off = point_off;
     for (int g = 0; g < n_groups; ++g) { h->group_off[g] = group_off[g]; h->group_count[g] = group_count[g]; }
     for (int u = 0; u < n_user; ++u) h->user_off[u] = user_off[u];
-#define CHAIN_CHK(expr)                                                                            \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            int _rc = fail(PCS_ERR_HIP, "%s failed: %s (pcs_genchain_create)", #expr, hipGetErrorString(_e)); \
-            pcs_genchain_destroy(h);                                                                  \
-            return _rc;                                                                            \
-        }                                                                                          \
-    } while (0)
+    // the steps of the set-up in order; the first that fails is named in the error and ends it
+    hipError_t e = hipSuccess;
+    std::string failed;
+    auto step = [&](const std::string &what, hipError_t r) {
+        if (r != hipSuccess) e = r, failed = what;
+        return r == hipSuccess;
+    };
     hipDeviceProp_t prop;
-    CHAIN_CHK(hipGetDeviceProperties(&prop, device));
-    h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    CHAIN_CHK(hipModuleLoad(&h->module, code_object_path));
-    CHAIN_CHK(hipModuleGetFunction(&h->f_prep, h->module, "pcs_genchain_prep"));
+    bool ok = step("hipGetDeviceProperties", hipGetDeviceProperties(&prop, device));
+    if (ok) {
+        h->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        ok = step(std::string("hipModuleLoad(") + code_object_path + ")", hipModuleLoad(&h->module, code_object_path));
+    }
+    auto function = [&](hipFunction_t *f, const std::string &name) { ok = ok && step("hipModuleGetFunction(" + name + ")", hipModuleGetFunction(f, h->module, name.c_str())); };
+    function(&h->f_prep, "pcs_genchain_prep");
     for (int one = 0; one < 2; ++one) {
         const std::string sfx = one ? "_one" : "";
         for (int m = 1; m <= 3; ++m) {
-            CHAIN_CHK(hipModuleGetFunction(&h->f_eval[one][m], h->module, ("pcs_genchain_eval_" + std::to_string(m) + sfx).c_str()));
-            CHAIN_CHK(hipModuleGetFunction(&h->f_eval_f32[one][m], h->module, ("pcs_genchain_eval_" + std::to_string(m) + "_f32" + sfx).c_str()));
+            function(&h->f_eval[one][m], "pcs_genchain_eval_" + std::to_string(m) + sfx);
+            function(&h->f_eval_f32[one][m], "pcs_genchain_eval_" + std::to_string(m) + "_f32" + sfx);
             if (m >= 2) {
-                CHAIN_CHK(hipModuleGetFunction(&h->f_compact[one][m], h->module, ("pcs_genchain_compact_" + std::to_string(m) + sfx).c_str()));
-                CHAIN_CHK(hipModuleGetFunction(&h->f_compact_f32[one][m], h->module, ("pcs_genchain_compact_" + std::to_string(m) + "_f32" + sfx).c_str()));
+                function(&h->f_compact[one][m], "pcs_genchain_compact_" + std::to_string(m) + sfx);
+                function(&h->f_compact_f32[one][m], "pcs_genchain_compact_" + std::to_string(m) + "_f32" + sfx);
             }
         }
     }
-    CHAIN_CHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (auto &e : h->ev) CHAIN_CHK(hipEventCreate(&e));
-    CHAIN_CHK(hipMalloc(&h->d_param, sizeof(double) * n_params));
-    CHAIN_CHK(hipMalloc(&h->d_sink, 64));
-    for (int g = 0; g < n_groups; ++g) CHAIN_CHK(hipMalloc(&h->d_slab[g], sizeof(double) * std::max<int64_t>(1, group_count[g]) * POSE_STRIDE));
-    if (uses_template) CHAIN_CHK(hipMalloc(&h->d_tmpl, sizeof(double) * 3 * n_keys));
-#undef CHAIN_CHK
+    ok = ok && step("hipStreamCreateWithFlags", hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    for (auto &ev : h->ev) ok = ok && step("hipEventCreate", hipEventCreate(&ev));
+    ok = ok && step("hipMalloc(d_param)", h->d_param.alloc(n_params, sizeof(double)));
+    ok = ok && step("hipMalloc(d_sink)", h->d_sink.alloc(8, sizeof(double)));   // 64 B
+    for (int g = 0; g < n_groups; ++g) ok = ok && step("hipMalloc(d_slab)", h->d_slab[g].alloc(std::max<int64_t>(1, group_count[g]) * POSE_STRIDE, sizeof(double)));
+    if (uses_template) ok = ok && step("hipMalloc(d_tmpl)", h->d_tmpl.alloc(3 * n_keys, sizeof(double)));
+    if (!ok) {
+        const int rc = fail(PCS_ERR_HIP, "%s failed: %s (pcs_genchain_create)", failed.c_str(), hipGetErrorString(e));
+        pcs_genchain_destroy(h);
+        return rc;
+    }
     *out = h;
     return PCS_OK;
 }
@@ -150,68 +145,28 @@ int pcs_genchain_row_len(const pcs_genchain *h) { return h ? h->P : -1; }
 
 int pcs_genchain_set_detections_table(pcs_genchain *h, const double *det5, int64_t n) {
     if (!h || (!det5 && n > 0) || n < 0) return fail(PCS_ERR_ARG, "pcs_genchain_set_detections_table: bad arguments");
-    std::vector<int32_t> cam(n), img(n), key(n);
-    std::vector<double> uv(2 * n);
-    for (int64_t i = 0; i < n; ++i) {
-        for (int j = 0; j < 3; ++j)
-            if (!(det5[5 * i + j] > -1.0 && det5[5 * i + j] < 2147483648.0))
-                return fail(PCS_ERR_RANGE, "detection %lld: index column %d = %g is not an index", (long long)i, j, det5[5 * i + j]);
-        cam[i] = (int32_t)det5[5 * i + 0]; img[i] = (int32_t)det5[5 * i + 1]; key[i] = (int32_t)det5[5 * i + 2];
-        if (cam[i] >= h->n_cams || img[i] >= h->n_imgs || key[i] >= h->n_keys)
-            return fail(PCS_ERR_RANGE, "detection %lld = (cam %d, im %d, key %d) outside (%lld, %lld, %lld)", (long long)i, cam[i], img[i], key[i],
-                        (long long)h->n_cams, (long long)h->n_imgs, (long long)h->n_keys);
-        uv[2 * i] = det5[5 * i + 3]; uv[2 * i + 1] = det5[5 * i + 4];
-    }
+    const DetCounts counts{h->n_cams, h->n_imgs, h->n_keys, false};
+    DetColumns c;
+    std::vector<double> uv;
+    if (const int rc = det_parse(det5, n, c, uv, &counts)) return rc;
     // the one-launch form's condition: every detection of a tile belongs to the (camera, image) pair of the tile's first or of its last detection
     h->two_pair_tiles = true;
     for (int64_t t0 = 0; t0 < n && h->two_pair_tiles; t0 += TILE) {
         const int64_t t1 = std::min<int64_t>(n, t0 + TILE) - 1;
         for (int64_t i = t0 + 1; i < t1; ++i)
-            if ((cam[i] != cam[t0] || img[i] != img[t0]) && (cam[i] != cam[t1] || img[i] != img[t1])) { h->two_pair_tiles = false; break; }
+            if ((c.cam[i] != c.cam[t0] || c.img[i] != c.img[t0]) && (c.cam[i] != c.cam[t1] || c.img[i] != c.img[t1])) { h->two_pair_tiles = false; break; }
     }
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (void **b : {(void **)&h->d_packed, (void **)&h->d_cam, (void **)&h->d_img, (void **)&h->d_key, (void **)&h->d_uv, &h->d_resid,
-                     &h->d_jac, &h->d_data, (void **)&h->d_keep, (void **)&h->d_row_off, (void **)&h->d_vin, (void **)&h->d_vout}) {
-        if (*b) HIPCHK(hipFree(*b));
-        *b = nullptr;
-    }
-    h->n = 0;
+    h->det.release();   // det.n stays 0 (= "no detections set") if an allocation or copy below fails
+    for (DevBuf *b : {&h->d_resid, &h->d_jac, &h->d_data, &h->d_keep, &h->d_row_off, &h->d_vin, &h->d_vout}) b->release();
     h->gram[0].built = h->gram[1].built = false;   // (the tables themselves are freed and rebuilt by genchain_gram_tables)
-    h->h_cam.clear(); h->h_img.clear(); h->h_key.clear();
     h->linearized = false;
     h->nnz = -1;
     if (n == 0) return PCS_OK;
-    h->h_cam = cam; h->h_img = img; h->h_key = key;   // for the segment tables of the normal equations (built on first use)
-    auto bits_for = [](int64_t count) { int b = 0; while (((int64_t)1 << b) < count) ++b; return b; };
-    h->key_bits = bits_for(h->n_keys);
-    h->img_bits = bits_for(h->n_imgs);
-    if (h->key_bits + h->img_bits + bits_for(h->n_cams) <= 32 && h->key_bits + h->img_bits <= 31) {
-        std::vector<uint32_t> w(n);
-        for (int64_t i = 0; i < n; ++i) w[i] = ((uint32_t)cam[i] << (h->key_bits + h->img_bits)) | ((uint32_t)img[i] << h->key_bits) | (uint32_t)key[i];
-        HIPCHK(hipMalloc(&h->d_packed, sizeof(uint32_t) * n));
-        HIPCHK(hipMemcpy(h->d_packed, w.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(hipMalloc(&h->d_cam, sizeof(int32_t) * n));
-        HIPCHK(hipMalloc(&h->d_img, sizeof(int32_t) * n));
-        HIPCHK(hipMalloc(&h->d_key, sizeof(int32_t) * n));
-        HIPCHK(hipMemcpy(h->d_cam, cam.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_img, img.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_key, key.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    }
-    if (h->dtype == PCS_F32) {   // float measurements (the rounding happens here, on upload)
-        std::vector<float> uvf(2 * n);
-        for (int64_t i = 0; i < 2 * n; ++i) uvf[i] = (float)uv[i];
-        HIPCHK(hipMalloc(&h->d_uv, sizeof(float) * 2 * n));
-        HIPCHK(hipMemcpy(h->d_uv, uvf.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(hipMalloc(&h->d_uv, sizeof(double) * 2 * n));
-        HIPCHK(hipMemcpy(h->d_uv, uv.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMalloc(&h->d_resid, h->out_elem() * 2 * n));
-    HIPCHK(hipMalloc(&h->d_jac, h->out_elem() * 2 * n * h->P));
-    h->n = n;
-    return PCS_OK;
+    if (const int rc = h->d_resid.grow(2 * n, h->out_elem())) return rc;
+    if (const int rc = h->d_jac.grow(2 * n * h->P, h->out_elem())) return rc;
+    return h->det.upload(c, uv.data(), counts, true, h->dtype == PCS_F32);   // generated chains always pack when the widths allow
 }
 
 int pcs_genchain_set_template(pcs_genchain *h, const double *points) {
@@ -219,7 +174,7 @@ int pcs_genchain_set_template(pcs_genchain *h, const double *points) {
     if (!h->uses_template) return fail(PCS_ERR_ARG, "pcs_genchain_set_template: the chain's source is not template_points");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(h->d_tmpl, points, sizeof(double) * 3 * h->n_keys, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_tmpl.p, points, sizeof(double) * 3 * h->n_keys, hipMemcpyHostToDevice));
     h->have_template = true;
     return PCS_OK;
 }
@@ -228,7 +183,7 @@ int pcs_genchain_set_template(pcs_genchain *h, const double *points) {
 // compact: d_jac is the CSR data array and only the unfixed columns are written (pcs_genchain_set_unfixed).
 static int genchain_enqueue(pcs_genchain *h, const double *d_param_str, void *d_resid, void *d_jac, bool compact, void *stream) {
     if (!h || !d_param_str) return fail(PCS_ERR_ARG, "pcs_genchain_eval_device: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     if (h->uses_template && !h->have_template) return fail(PCS_ERR_STATE, "template points not set");
     if (compact && (h->nnz < 0 || !d_jac)) return fail(PCS_ERR_STATE, "pcs_genchain_set_unfixed has not been called");
     const int mode = (d_resid ? MODE_RESID : 0) | (d_jac ? MODE_JAC : 0);
@@ -236,20 +191,19 @@ static int genchain_enqueue(pcs_genchain *h, const double *d_param_str, void *d_
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = stream ? (hipStream_t)stream : h->stream;
     GenericArgs a{};
-    a.tab.packed = h->d_packed; a.tab.cam = h->d_cam; a.tab.img = h->d_img; a.tab.key = h->d_key; a.tab.uv = h->d_uv;
-    a.tab.key_bits = h->key_bits; a.tab.img_bits = h->img_bits; a.tab.uv_f32 = h->dtype == PCS_F32;
-    a.prm = d_param_str; a.tmpl = h->d_tmpl;
+    a.tab = h->det.table();
+    a.prm = d_param_str; a.tmpl = h->d_tmpl.as<double>();
     int64_t prep_threads = 0;
     for (int g = 0; g < h->n_groups; ++g) {
-        a.slab[g] = h->d_slab[g]; a.group_off[g] = h->group_off[g]; a.group_count[g] = h->group_count[g];
+        a.slab[g] = h->d_slab[g].as<double>(); a.group_off[g] = h->group_off[g]; a.group_count[g] = h->group_count[g];
         prep_threads += (int64_t)h->group_count[g] * POSE_STRIDE;
     }
     a.n_groups = h->n_groups;
     a.intr_off = h->intr_off; a.point_off = h->point_off;
     for (int u = 0; u < h->n_user; ++u) a.user_off[u] = h->user_off[u];
-    a.resid = d_resid; a.jac = d_jac; a.sink = h->d_sink;
-    a.keep = h->d_keep; a.row_off = h->d_row_off;
-    a.n = h->n; a.n_tiles = (h->n + TILE - 1) / TILE;
+    a.resid = d_resid; a.jac = d_jac; a.sink = h->d_sink.p;
+    a.keep = h->d_keep.as<uint64_t>(); a.row_off = h->d_row_off.as<int64_t>();
+    a.n = h->det.n; a.n_tiles = (h->det.n + TILE - 1) / TILE;
     const int waves = a.n_tiles >= (int64_t)h->n_cu * 32 ? WAVES_PER_WG : a.n_tiles >= (int64_t)h->n_cu * 16 ? 2 : 1;
     a.tiles_per_wg = waves;   // one tile per wave, like the hand-fused kernel with slabs through L1/L2
     void *params[] = {&a};
@@ -302,19 +256,19 @@ int pcs_genchain_eval_compact_device(pcs_genchain *h, const double *d_param_str,
 static int chain_stage(pcs_genchain *h, const double *param_str) {
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_param, param_str, sizeof(double) * h->n_params, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_param.as<double>(), param_str, sizeof(double) * h->n_params, hipMemcpyHostToDevice, h->stream));
     return PCS_OK;
 }
 
 int pcs_genchain_eval(pcs_genchain *h, const double *param_str, void *resid, void *jac) {
     if (!h || !param_str) return fail(PCS_ERR_ARG, "pcs_genchain_eval: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     int rc = chain_stage(h, param_str);
     if (rc) return rc;
-    rc = pcs_genchain_eval_device(h, h->d_param, resid ? h->d_resid : nullptr, jac ? h->d_jac : nullptr, nullptr);
+    rc = pcs_genchain_eval_device(h, h->d_param.as<double>(), resid ? h->d_resid.p : nullptr, jac ? h->d_jac.p : nullptr, nullptr);
     if (rc) return rc;
-    if (resid) HIPCHK(hipMemcpyAsync(resid, h->d_resid, h->out_elem() * 2 * h->n, hipMemcpyDeviceToHost, h->stream));
-    if (jac) HIPCHK(hipMemcpyAsync(jac, h->d_jac, h->out_elem() * 2 * h->n * h->P, hipMemcpyDeviceToHost, h->stream));
+    if (resid) HIPCHK(hipMemcpyAsync(resid, h->d_resid.p, h->out_elem() * 2 * h->det.n, hipMemcpyDeviceToHost, h->stream));
+    if (jac) HIPCHK(hipMemcpyAsync(jac, h->d_jac.p, h->out_elem() * 2 * h->det.n * h->P, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PCS_OK;
 }
@@ -323,9 +277,9 @@ int pcs_genchain_eval(pcs_genchain *h, const double *param_str, void *resid, voi
 // is free; row_off[i] = offset of its u row in the CSR data array (its v row follows: same kept columns).  nnz = total entries.
 int pcs_genchain_set_unfixed(pcs_genchain *h, const uint64_t *keep, const int64_t *row_off, int64_t nnz) {
     if (!h || nnz < 0 || !keep || !row_off) return fail(PCS_ERR_ARG, "pcs_genchain_set_unfixed: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     int64_t expect = 0;
-    for (int64_t i = 0; i < h->n; ++i) {
+    for (int64_t i = 0; i < h->det.n; ++i) {
         if (h->P < 64 && (keep[i] >> h->P)) return fail(PCS_ERR_RANGE, "pcs_genchain_set_unfixed: detection %lld keeps a column beyond the row length", (long long)i);
         if (row_off[i] != expect) return fail(PCS_ERR_RANGE, "pcs_genchain_set_unfixed: row_off[%lld] = %lld, the packed layout needs %lld", (long long)i, (long long)row_off[i], (long long)expect);
         expect += 2 * (int64_t)__builtin_popcountll(keep[i]);
@@ -333,15 +287,12 @@ int pcs_genchain_set_unfixed(pcs_genchain *h, const uint64_t *keep, const int64_
     if (expect != nnz) return fail(PCS_ERR_RANGE, "pcs_genchain_set_unfixed: nnz = %lld, the masks keep %lld entries", (long long)nnz, (long long)expect);
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (void **b : {(void **)&h->d_keep, (void **)&h->d_row_off, &h->d_data}) {
-        if (*b) HIPCHK(hipFree(*b));
-        *b = nullptr;
-    }
-    HIPCHK(hipMalloc(&h->d_keep, sizeof(uint64_t) * h->n));
-    HIPCHK(hipMalloc(&h->d_row_off, sizeof(int64_t) * h->n));
-    HIPCHK(hipMalloc(&h->d_data, h->out_elem() * std::max<int64_t>(1, nnz) + 256));   // + one line: the last pass may store whole 16-byte units
-    HIPCHK(hipMemcpy(h->d_keep, keep, sizeof(uint64_t) * h->n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_row_off, row_off, sizeof(int64_t) * h->n, hipMemcpyHostToDevice));
+    for (DevBuf *b : {&h->d_keep, &h->d_row_off, &h->d_data}) b->release();
+    if (const int rc = h->d_keep.grow(h->det.n, sizeof(uint64_t))) return rc;
+    if (const int rc = h->d_row_off.grow(h->det.n, sizeof(int64_t))) return rc;
+    if (const int rc = h->d_data.grow((int64_t)h->out_elem() * std::max<int64_t>(1, nnz) + 256, 1)) return rc;   // bytes; + one line: the last pass may store whole 16-byte units
+    HIPCHK(hipMemcpy(h->d_keep.p, keep, sizeof(uint64_t) * h->det.n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_row_off.p, row_off, sizeof(int64_t) * h->det.n, hipMemcpyHostToDevice));
     h->nnz = nnz;
     return PCS_OK;
 }
@@ -351,10 +302,10 @@ int pcs_genchain_eval_compact(pcs_genchain *h, const double *param_str, void *re
     if (h->nnz < 0) return fail(PCS_ERR_STATE, "pcs_genchain_set_unfixed has not been called");
     int rc = chain_stage(h, param_str);
     if (rc) return rc;
-    rc = genchain_enqueue(h, h->d_param, resid ? h->d_resid : nullptr, h->d_data, true, nullptr);
+    rc = genchain_enqueue(h, h->d_param.as<double>(), resid ? h->d_resid.p : nullptr, h->d_data.p, true, nullptr);
     if (rc) return rc;
-    if (h->nnz > 0) HIPCHK(hipMemcpyAsync(data, h->d_data, h->out_elem() * h->nnz, hipMemcpyDeviceToHost, h->stream));
-    if (resid) HIPCHK(hipMemcpyAsync(resid, h->d_resid, h->out_elem() * 2 * h->n, hipMemcpyDeviceToHost, h->stream));
+    if (h->nnz > 0) HIPCHK(hipMemcpyAsync(data, h->d_data.p, h->out_elem() * h->nnz, hipMemcpyDeviceToHost, h->stream));
+    if (resid) HIPCHK(hipMemcpyAsync(resid, h->d_resid.p, h->out_elem() * 2 * h->det.n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return PCS_OK;
 }
@@ -400,7 +351,7 @@ int pcs_genchain_linearize(pcs_genchain *h, const double *param_str) {
     if (h->n_blocks == 0) return fail(PCS_ERR_STATE, "pcs_genchain_set_blocks has not been called");
     int rc = chain_stage(h, param_str);
     if (rc) return rc;
-    rc = genchain_enqueue(h, h->d_param, h->d_resid, h->d_jac, false, nullptr);
+    rc = genchain_enqueue(h, h->d_param.as<double>(), h->d_resid.p, h->d_jac.p, false, nullptr);
     if (rc) return rc;
     h->linearized = true;
     return PCS_OK;
@@ -411,24 +362,23 @@ int pcs_genchain_matfree(pcs_genchain *h, int op, const double *in, double *out,
     if (!h || !out || op < 0 || op > 4 || ((op == BR_JV || op == BR_JTU || op == BR_JTJV) && !in)) return fail(PCS_ERR_ARG, "pcs_genchain_matfree: bad arguments");
     if (!h->linearized) return fail(PCS_ERR_STATE, "pcs_genchain_linearize has not been called");
     HIPCHK(hipSetDevice(h->device));
-    const int64_t n_in = op == BR_JTU ? 2 * h->n : (op == BR_JV || op == BR_JTJV) ? h->n_params : 0;
-    const int64_t n_out = op == BR_JV ? 2 * h->n : h->n_params;
-    const int64_t cap = std::max<int64_t>(h->n_params, 2 * h->n) + 1;
-    if (!h->d_vin) HIPCHK(hipMalloc(&h->d_vin, sizeof(double) * cap));
-    if (!h->d_vout) HIPCHK(hipMalloc(&h->d_vout, sizeof(double) * cap));
+    const int64_t n_in = op == BR_JTU ? 2 * h->det.n : (op == BR_JV || op == BR_JTJV) ? h->n_params : 0;
+    const int64_t n_out = op == BR_JV ? 2 * h->det.n : h->n_params;
+    const int64_t cap = std::max<int64_t>(h->n_params, 2 * h->det.n) + 1;
+    if (const int rc = h->d_vin.grow(cap, sizeof(double))) return rc;   // released with the table: allocated once per table
+    if (const int rc = h->d_vout.grow(cap, sizeof(double))) return rc;
     hipStream_t s = h->stream;
-    if (n_in) HIPCHK(hipMemcpyAsync(h->d_vin, in, sizeof(double) * n_in, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->d_vout, 0, sizeof(double) * (n_out + 1), s));
+    if (n_in) HIPCHK(hipMemcpyAsync(h->d_vin.as<double>(), in, sizeof(double) * n_in, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->d_vout.as<double>(), 0, sizeof(double) * (n_out + 1), s));
     BlockRowArgs a{};
-    a.tab.packed = h->d_packed; a.tab.cam = h->d_cam; a.tab.img = h->d_img; a.tab.key = h->d_key; a.tab.uv = h->d_uv;
-    a.tab.key_bits = h->key_bits; a.tab.img_bits = h->img_bits; a.tab.uv_f32 = 0;
-    a.J = static_cast<const double *>(h->d_jac); a.resid = static_cast<const double *>(h->d_resid);
-    a.in = h->d_vin; a.out = h->d_vout; a.cost = h->d_vout + n_out;
-    a.n = h->n; a.n_params = h->n_params; a.P = h->P; a.n_blocks = h->n_blocks;
+    a.tab = h->det.table();   // (FP64 chains only: double measurements)
+    a.J = static_cast<const double *>(h->d_jac.p); a.resid = static_cast<const double *>(h->d_resid.p);
+    a.in = h->d_vin.as<double>(); a.out = h->d_vout.as<double>(); a.cost = h->d_vout.as<double>() + n_out;
+    a.n = h->det.n; a.n_params = h->n_params; a.P = h->P; a.n_blocks = h->n_blocks;
     for (int b = 0; b < h->n_blocks; ++b) { a.blk_col0[b] = h->blk_col0[b]; a.blk_np[b] = h->blk_np[b]; a.blk_link[b] = h->blk_link[b]; a.blk_start[b] = h->blk_start[b]; }
     a.lds_acc = op != BR_JV && h->n_params * (int64_t)sizeof(double) <= 65536;
     const size_t lds = a.lds_acc ? sizeof(double) * (size_t)h->n_params : 0;
-    const int64_t wgs = std::min<int64_t>((h->n + 255) / 256, (int64_t)h->n_cu * (a.lds_acc ? 2 : 8));
+    const int64_t wgs = std::min<int64_t>((h->det.n + 255) / 256, (int64_t)h->n_cu * (a.lds_acc ? 2 : 8));
     const dim3 grid((unsigned)std::max<int64_t>(1, wgs));
     switch (op) {
         case BR_JV: hipLaunchKernelGGL(blockrow_kernel<BR_JV>, grid, dim3(256), lds, s, a); break;
@@ -438,8 +388,8 @@ int pcs_genchain_matfree(pcs_genchain *h, int op, const double *in, double *out,
         default: hipLaunchKernelGGL(blockrow_kernel<BR_GRAD>, grid, dim3(256), lds, s, a); break;
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, h->d_vout, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
-    if (cost && op == BR_GRAD) HIPCHK(hipMemcpyAsync(cost, h->d_vout + n_out, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, h->d_vout.as<double>(), sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+    if (cost && op == BR_GRAD) HIPCHK(hipMemcpyAsync(cost, h->d_vout.as<double>() + n_out, sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return PCS_OK;
 }
@@ -500,7 +450,7 @@ int pcs_genchain_set_option(pcs_genchain *h, const char *key, int64_t value) {
 static int genchain_gram_tables(pcs_genchain *h) {
     pcs_genchain::GramTables &G = h->gram[h->deterministic ? 1 : 0];
     if (G.built) return PCS_OK;
-    const int64_t n = h->n;
+    const int64_t n = h->det.n;
     if (n > INT32_MAX) return fail(PCS_ERR_ARG, "normal equations of the chain: tables beyond 2^31 rows are not supported");
     bool key_linked = false;
     for (int b = 0; b < h->n_blocks; ++b) key_linked = key_linked || h->blk_link[b] == 2;
@@ -513,7 +463,7 @@ static int genchain_gram_tables(pcs_genchain *h) {
         }
     for (int p = 0; p < 4; ++p) G.n_seg[p] = G.n_grp[p][0] = G.n_grp[p][1] = G.n_grp[p][2] = 0;
     const int64_t cap = std::min<int64_t>(GRAM_SEG, std::max<int64_t>(16, (n / 4096 + 15) / 16 * 16));
-    const std::vector<int32_t> *kind[3] = {&h->h_cam, &h->h_img, &h->h_key};
+    const std::vector<int32_t> *kind[3] = {&h->det.h.cam, &h->det.h.img, &h->det.h.key};
     // (major, minor) entity kinds per pass; -1: the pass does not exist in this mode / for this chain
     int major[4] = {-1, -1, -1, -1}, minor[4] = {-1, -1, -1, -1};
     bool sorted[4] = {false, false, false, false};
@@ -591,11 +541,11 @@ static int genchain_enqueue_normal(pcs_genchain *h, const double *d_param_str, d
     if (h->n_blocks == 0) return fail(PCS_ERR_STATE, "pcs_genchain_set_blocks has not been called");
     if (h->P + 1 > GRAM_MAX_COLS) return fail(PCS_ERR_ARG, "dense normal equations: block rows of %d columns (limit %d)", h->P, GRAM_MAX_COLS - 1);
     if (h->n_params > PCS_NORMAL_MAX_PARAMS) return fail(PCS_ERR_ARG, "dense normal equations: more than %d parameters", PCS_NORMAL_MAX_PARAMS);
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     int rc = genchain_gram_tables(h);
     if (rc) return rc;
     const pcs_genchain::GramTables &G = h->gram[h->deterministic ? 1 : 0];
-    rc = genchain_enqueue(h, d_param_str, h->d_resid, h->d_jac, false, s);
+    rc = genchain_enqueue(h, d_param_str, h->d_resid.p, h->d_jac.p, false, s);
     if (rc) return rc;
     h->linearized = true;
     const int64_t np = h->n_params;
@@ -605,9 +555,8 @@ static int genchain_enqueue_normal(pcs_genchain *h, const double *d_param_str, d
     const int64_t n_h = L.h_len();
     if (!zeroed) HIPCHK(hipMemsetAsync(d_packed, 0, sizeof(double) * (size_t)(n_h + np + 1), s));
     BlockGramArgs a{};
-    a.tab.packed = h->d_packed; a.tab.cam = h->d_cam; a.tab.img = h->d_img; a.tab.key = h->d_key; a.tab.uv = h->d_uv;
-    a.tab.key_bits = h->key_bits; a.tab.img_bits = h->img_bits; a.tab.uv_f32 = 0;
-    a.J = static_cast<const double *>(h->d_jac); a.resid = static_cast<const double *>(h->d_resid);
+    a.tab = h->det.table();   // (FP64 chains only: double measurements)
+    a.J = static_cast<const double *>(h->d_jac.p); a.resid = static_cast<const double *>(h->d_resid.p);
     a.A = d_packed; a.B = a.A + L.a_len(); a.C = a.B + L.b_len(); a.g = d_packed + n_h; a.cost = a.g + np;
     a.n_params = np; a.n_lead = L.n_lead; a.n_trail = L.n_trail; a.trail_off = L.trail_off; a.tb = L.tb;
     a.P = h->P; a.n_blocks = h->n_blocks;
@@ -627,18 +576,15 @@ static int genchain_enqueue_normal(pcs_genchain *h, const double *d_param_str, d
         int64_t most = 0;
         for (int pass = 0; pass < 4; ++pass) most = std::max(most, G.n_seg[pass]);
         const int64_t need = most * gram_blocks(nb) * 256;
-        if (need > h->gram_ws_cap) {
+        if (h->d_gram_ws.grows(need)) {
             HIPCHK(hipStreamSynchronize(s));
-            if (h->d_gram_ws) HIPCHK(hipFree(h->d_gram_ws));
-            h->d_gram_ws = nullptr; h->gram_ws_cap = 0;
-            HIPCHK(hipMalloc(&h->d_gram_ws, sizeof(double) * need));
-            h->gram_ws_cap = need;
+            if (const int rc = h->d_gram_ws.grow(need, sizeof(double))) return rc;
         }
     }
     for (int pass = 0; pass < 4; ++pass) {   // one launch per table order that has pairs of columns to sum (default mode: key-linked columns add two)
         if (G.n_seg[pass] <= 0) continue;
         a.seg = G.d_seg[pass]; a.n_seg = (int32_t)G.n_seg[pass]; a.order = G.d_order[pass]; a.pass = pass;
-        a.det = h->deterministic ? 1 : 0; a.ws = h->deterministic ? h->d_gram_ws : nullptr;
+        a.det = h->deterministic ? 1 : 0; a.ws = h->deterministic ? h->d_gram_ws.as<double>() : nullptr;
         a.grp[0] = G.d_grp[pass][0]; a.grp[1] = G.d_grp[pass][1]; a.grp[2] = G.d_grp[pass][2]; a.gidx = G.d_gidx[pass];
         a.n_grp[0] = (int32_t)G.n_grp[pass][0]; a.n_grp[1] = (int32_t)G.n_grp[pass][1]; a.n_grp[2] = (int32_t)G.n_grp[pass][2];
         hipError_t e;
@@ -722,9 +668,9 @@ int pcs_genchain_lm_trial(pcs_genchain *h, const pcs_lm_buffers *b, void *stream
 
 int pcs_genchain_device_buffers(pcs_genchain *h, void **d_resid, void **d_jac) {
     if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_device_buffers: bad arguments");
-    if (h->n <= 0) return fail(PCS_ERR_STATE, "no detections set");
-    if (d_resid) *d_resid = h->d_resid;
-    if (d_jac) *d_jac = h->d_jac;
+    if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
+    if (d_resid) *d_resid = h->d_resid.p;
+    if (d_jac) *d_jac = h->d_jac.p;
     return PCS_OK;
 }
 
@@ -754,18 +700,14 @@ int pcs_blockcheck(const char *code_object_path, int device, int np, int nin, in
     if (!code_object_path || np < 1 || nin < 0 || nout < 1 || m < 1 || !points || !fun_out || !jac_out || !fd_out || (templated && nin != 0) ||
         np + nin > 64 || nout > 64 || m > ((int64_t)1 << 26))
         return fail(PCS_ERR_ARG, "pcs_blockcheck: bad arguments");
-    const int ndev = pcs_device_count();
-    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "pcs_blockcheck: no HIP device visible (the block check has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "pcs_blockcheck: device %d out of range [0,%d)", device, ndev);
-    HIPCHK(hipSetDevice(device));
+    if (const int rc = open_device("pcs_blockcheck", device, "the block check has no CPU fallback", true)) return rc;
     const int nrow = np + (templated ? 3 : nin), nc = np + nin;
     hipModule_t mod = nullptr;
     hipStream_t s = nullptr;
-    double *d_pts = nullptr, *d_out = nullptr;
+    DevBuf pts, outb;
     auto done = [&](int code) {
         if (s) (void)hipStreamSynchronize(s);
-        for (double *b : {d_pts, d_out})
-            if (b) (void)hipFree(b);
+        pts.release(), outb.release();
         if (s) (void)hipStreamDestroy(s);
         if (mod) (void)hipModuleUnload(mod);
         return code;
@@ -789,8 +731,9 @@ int pcs_blockcheck(const char *code_object_path, int device, int np, int nin, in
     CHECK_CHK(hipModuleGetFunction(&f, mod, "pcs_blockcheck"));
     CHECK_CHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     const size_t n_pts = (size_t)m * nrow, n_fun = (size_t)m * nout, n_jac = (size_t)m * nout * nc;
-    CHECK_CHK(hipMalloc(&d_pts, sizeof(double) * n_pts));
-    CHECK_CHK(hipMalloc(&d_out, sizeof(double) * (n_fun + 2 * n_jac)));
+    CHECK_CHK(pts.alloc((int64_t)n_pts, sizeof(double)));
+    CHECK_CHK(outb.alloc((int64_t)(n_fun + 2 * n_jac), sizeof(double)));
+    double *d_pts = pts.as<double>(), *d_out = outb.as<double>();
     CHECK_CHK(hipMemcpyAsync(d_pts, points, sizeof(double) * n_pts, hipMemcpyHostToDevice, s));
     CHECK_CHK(hipMemsetAsync(d_out, 0, sizeof(double) * (n_fun + 2 * n_jac), s));
     BlockcheckArgs a{d_pts, m, d_out, d_out + n_fun, d_out + n_fun + n_jac};

@@ -1,5 +1,7 @@
-// pcs_handle.inc — what the batched handles (pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc, pcs_rig.inc) share; included after pcs_common.inc.  Plain structs and
-// free functions; what they guarantee is in DESIGN.md, "Batched handles".
+// pcs_handle.inc — what the handles share; included after pcs_common.inc.  Plain structs and free functions.  DevBuf and open_device serve
+// every handle, the two engine kinds (pcs_engine, pcs_genchain) included; the fence, the timer, the output slots and the checks of
+// set_observations serve the batched handles (pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc, pcs_rig.inc, pcs_stats.inc).  What
+// they guarantee is in DESIGN.md, "Batched handles".
 
 // One growable device buffer: a pointer and its capacity in elements.
 struct DevBuf {
@@ -101,10 +103,13 @@ struct HandleCore {
     }
 };
 
-static int open_device(const char *who, int device) {
+// The two engine kinds and the block check word both refusals at more length than the batched handles: `no_fallback` says what has no CPU
+// fallback, `show_range` puts the device and the range into the second message.
+static int open_device(const char *who, int device, const char *no_fallback = "no CPU fallback", bool show_range = false) {
     const int ndev = pcs_device_count();
-    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "%s: no HIP device visible (no CPU fallback)", who);
-    if (device < 0 || device >= ndev) return fail(PCS_ERR_ARG, "%s: device out of range", who);
+    if (ndev <= 0) return fail(PCS_ERR_NODEVICE, "%s: no HIP device visible (%s)", who, no_fallback);
+    if (device < 0 || device >= ndev)
+        return show_range ? fail(PCS_ERR_ARG, "%s: device %d out of range [0,%d)", who, device, ndev) : fail(PCS_ERR_ARG, "%s: device out of range", who);
     HIPCHK(hipSetDevice(device));
     return PCS_OK;
 }
@@ -113,6 +118,35 @@ static int open_device(const char *who, int device) {
 static int check_lm_options(const char *who, int max_iter, double ftol, double xtol, double gtol, bool rest_ok, const char *rest) {
     if (!rest_ok || max_iter < 0 || !(ftol >= 0.0 && ftol < INFINITY) || !(xtol >= 0.0 && xtol < INFINITY) || !(gtol >= 0.0 && gtol < INFINITY))
         return fail(PCS_ERR_ARG, "%s: bad options (max_iter >= 0, finite tolerances >= 0, %s)", who, rest);
+    return PCS_OK;
+}
+
+// The grouped table of a set_observations call: start_inds runs from 0 to n_obs and never decreases, and every observation's key lies
+// in [0, n_keys).  `group_ok(j)` checks the handle's own per-group columns (0, or the code of its refusal);
+// it runs in group order right behind group j's start index, so that the first bad GROUP decides the refusal, ahead of any bad key.
+template <class GroupOk>
+static int check_grouped_observations(const char *who, int64_t n_obs, const int32_t *key, int64_t n_keys, int64_t n_groups, const int64_t *start_inds,
+                                      GroupOk group_ok) {
+    if (start_inds[0] != 0 || start_inds[n_groups] != n_obs) return fail(PCS_ERR_ARG, "%s: start_inds must run from 0 to n_obs", who);
+    for (int64_t j = 0; j < n_groups; ++j) {
+        if (start_inds[j + 1] < start_inds[j]) return fail(PCS_ERR_ARG, "%s: start_inds must be non-decreasing", who);
+        if (const int rc = group_ok(j)) return rc;
+    }
+    for (int64_t r = 0; r < n_obs; ++r)
+        if (key[r] < 0 || key[r] >= n_keys) return fail(PCS_ERR_RANGE, "observation %lld has key %d outside [0,%lld)", (long long)r, key[r], (long long)n_keys);
+    return PCS_OK;
+}
+
+// a group's camera / image column
+static int check_group_entity(const char *group, int64_t j, const char *what, int32_t v, int64_t count) {
+    if (v < 0 || v >= count) return fail(PCS_ERR_RANGE, "%s %lld has %s %d outside [0,%lld)", group, (long long)j, what, v, (long long)count);
+    return PCS_OK;
+}
+
+// A host array into a buffer of fixed size (allocated at create): a run queued on any stream may still read it, so the handle is quiesced first
+static int set_fixed_array(const HandleCore &c, DevBuf &buf, const void *src, size_t bytes) {
+    HIPCHK(c.quiesce());
+    HIPCHK(hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice));
     return PCS_OK;
 }
 

@@ -48,8 +48,7 @@ int pcs_intr_destroy(pcs_intrinsics_estimator *p) {
 
 int pcs_intr_set_template(pcs_intrinsics_estimator *p, const double *points) {
     if (!p || !points) return fail(PCS_ERR_ARG, "pcs_intr_set_template: bad arguments");
-    HIPCHK(p->core.quiesce());
-    HIPCHK(hipMemcpy(p->pts.p, points, sizeof(double) * 3 * p->n_keys, hipMemcpyHostToDevice));
+    if (const int rc = set_fixed_array(p->core, p->pts, points, sizeof(double) * 3 * p->n_keys)) return rc;
     p->have_template = true;
     p->run_valid = false;
     return PCS_OK;
@@ -59,18 +58,15 @@ int pcs_intr_set_observations(pcs_intrinsics_estimator *p, int64_t n_obs, const 
                               const int32_t *group_cam) {
     if (!p || n_obs < 0 || n_groups < 0 || n_groups > INT32_MAX || !start_inds || (n_obs > 0 && (!key || !uv)) || (n_groups > 0 && !group_cam))
         return fail(PCS_ERR_ARG, "pcs_intr_set_observations: bad arguments");
-    if (start_inds[0] != 0 || start_inds[n_groups] != n_obs) return fail(PCS_ERR_ARG, "pcs_intr_set_observations: start_inds must run from 0 to n_obs");
     std::vector<int64_t> cam_start((size_t)p->n_cams + 1, 0);
-    for (int64_t j = 0; j < n_groups; ++j) {
-        if (start_inds[j + 1] < start_inds[j]) return fail(PCS_ERR_ARG, "pcs_intr_set_observations: start_inds must be non-decreasing");
-        if (group_cam[j] < 0 || group_cam[j] >= p->n_cams)
-            return fail(PCS_ERR_RANGE, "group %lld has camera %d outside [0,%lld)", (long long)j, group_cam[j], (long long)p->n_cams);
+    const int bad = check_grouped_observations("pcs_intr_set_observations", n_obs, key, p->n_keys, n_groups, start_inds, [&](int64_t j) {
+        if (const int rc = check_group_entity("group", j, "camera", group_cam[j], p->n_cams)) return rc;
         if (j > 0 && group_cam[j] < group_cam[j - 1]) return fail(PCS_ERR_ARG, "pcs_intr_set_observations: the groups must be sorted by camera");
         ++cam_start[group_cam[j] + 1];
-    }
+        return (int)PCS_OK;
+    });
+    if (bad) return bad;
     for (int64_t c = 0; c < p->n_cams; ++c) cam_start[c + 1] += cam_start[c];
-    for (int64_t r = 0; r < n_obs; ++r)
-        if (key[r] < 0 || key[r] >= p->n_keys) return fail(PCS_ERR_RANGE, "observation %lld has key %d outside [0,%lld)", (long long)r, key[r], (long long)p->n_keys);
     HIPCHK(p->core.quiesce());
     p->n_groups = -1;
     const HostArray arrays[] = {{p->key, key, n_obs, sizeof(int32_t)}, {p->uv, uv, n_obs, 2 * sizeof(double)},

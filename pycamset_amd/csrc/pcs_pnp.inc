@@ -51,8 +51,7 @@ int pcs_pnp_set_cameras(pcs_pose_estimator *p, const double *intr) {
     std::vector<double> tab((size_t)p->n_cams * TRI_CAM_STRIDE, 0.0);
     for (int64_t c = 0; c < p->n_cams; ++c)
         for (int k = 0; k < 9; ++k) tab[c * TRI_CAM_STRIDE + 22 + k] = intr[9 * c + k];   // [fx cx fy cy k0 k1 p0 p1 k2]: the slab row as it is
-    HIPCHK(p->core.quiesce());
-    HIPCHK(hipMemcpy(p->tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    if (const int rc = set_fixed_array(p->core, p->tab, tab.data(), sizeof(double) * tab.size())) return rc;
     p->have_cams = true;
     p->run_valid = false;
     return PCS_OK;
@@ -60,8 +59,7 @@ int pcs_pnp_set_cameras(pcs_pose_estimator *p, const double *intr) {
 
 int pcs_pnp_set_template(pcs_pose_estimator *p, const double *points) {
     if (!p || !points) return fail(PCS_ERR_ARG, "pcs_pnp_set_template: bad arguments");
-    HIPCHK(p->core.quiesce());
-    HIPCHK(hipMemcpy(p->pts.p, points, sizeof(double) * 3 * p->n_keys, hipMemcpyHostToDevice));
+    if (const int rc = set_fixed_array(p->core, p->pts, points, sizeof(double) * 3 * p->n_keys)) return rc;
     p->have_template = true;
     p->run_valid = false;
     return PCS_OK;
@@ -71,14 +69,9 @@ int pcs_pnp_set_observations(pcs_pose_estimator *p, int64_t n_obs, const int32_t
                              const int32_t *view_cam) {
     if (!p || n_obs < 0 || n_views < 0 || n_views > INT32_MAX || !start_inds || (n_obs > 0 && (!key || !uv)) || (n_views > 0 && !view_cam))
         return fail(PCS_ERR_ARG, "pcs_pnp_set_observations: bad arguments");
-    if (start_inds[0] != 0 || start_inds[n_views] != n_obs) return fail(PCS_ERR_ARG, "pcs_pnp_set_observations: start_inds must run from 0 to n_obs");
-    for (int64_t j = 0; j < n_views; ++j) {
-        if (start_inds[j + 1] < start_inds[j]) return fail(PCS_ERR_ARG, "pcs_pnp_set_observations: start_inds must be non-decreasing");
-        if (view_cam[j] < 0 || view_cam[j] >= p->n_cams)
-            return fail(PCS_ERR_RANGE, "view %lld has camera %d outside [0,%lld)", (long long)j, view_cam[j], (long long)p->n_cams);
-    }
-    for (int64_t r = 0; r < n_obs; ++r)
-        if (key[r] < 0 || key[r] >= p->n_keys) return fail(PCS_ERR_RANGE, "observation %lld has key %d outside [0,%lld)", (long long)r, key[r], (long long)p->n_keys);
+    if (const int rc = check_grouped_observations("pcs_pnp_set_observations", n_obs, key, p->n_keys, n_views, start_inds,
+                                                  [&](int64_t j) { return check_group_entity("view", j, "camera", view_cam[j], p->n_cams); }))
+        return rc;
     HIPCHK(p->core.quiesce());
     p->n_views = -1;
     const HostArray arrays[] = {{p->key, key, n_obs, sizeof(int32_t)}, {p->uv, uv, n_obs, 2 * sizeof(double)},

@@ -67,8 +67,7 @@ int pcs_rig_destroy(pcs_rig_graph *p) {
 
 int pcs_rig_set_cameras(pcs_rig_graph *p, const double *intr) {
     if (!p || !intr) return fail(PCS_ERR_ARG, "pcs_rig_set_cameras: bad arguments");
-    HIPCHK(p->core.quiesce());
-    HIPCHK(hipMemcpy(p->intr.p, intr, sizeof(double) * 9 * p->n_cams, hipMemcpyHostToDevice));
+    if (const int rc = set_fixed_array(p->core, p->intr, intr, sizeof(double) * 9 * p->n_cams)) return rc;
     p->have_cams = true;
     p->scores_valid = false;
     return PCS_OK;
@@ -84,8 +83,7 @@ int pcs_rig_set_template(pcs_rig_graph *p, const double *points, double *frame) 
         for (int d = 0; d < 3; ++d) s += (points[3 * k + d] - c[d]) * (points[3 * k + d] - c[d]);
     const double rho = std::sqrt(s / (double)p->n_keys);
     if (!(rho < INFINITY)) return fail(PCS_ERR_ARG, "pcs_rig_set_template: the template points must be finite");
-    HIPCHK(p->core.quiesce());
-    HIPCHK(hipMemcpy(p->pts.p, points, sizeof(double) * 3 * p->n_keys, hipMemcpyHostToDevice));
+    if (const int rc = set_fixed_array(p->core, p->pts, points, sizeof(double) * 3 * p->n_keys)) return rc;
     for (int d = 0; d < 3; ++d) p->centroid[d] = c[d];
     p->rho = rho;
     if (frame) frame[0] = c[0], frame[1] = c[1], frame[2] = c[2], frame[3] = rho;
@@ -98,18 +96,14 @@ int pcs_rig_set_observations(pcs_rig_graph *p, int64_t n_obs, const int32_t *key
                              const int32_t *view_cam, const int32_t *view_im) {
     if (!p || n_obs < 0 || n_views < 0 || n_views > INT32_MAX || !start_inds || (n_obs > 0 && (!key || !uv)) || (n_views > 0 && (!view_cam || !view_im)))
         return fail(PCS_ERR_ARG, "pcs_rig_set_observations: bad arguments");
-    if (start_inds[0] != 0 || start_inds[n_views] != n_obs) return fail(PCS_ERR_ARG, "pcs_rig_set_observations: start_inds must run from 0 to n_obs");
     std::vector<int64_t> im_start((size_t)p->n_imgs + 1, 0);
-    for (int64_t j = 0; j < n_views; ++j) {
-        if (start_inds[j + 1] < start_inds[j]) return fail(PCS_ERR_ARG, "pcs_rig_set_observations: start_inds must be non-decreasing");
-        if (view_cam[j] < 0 || view_cam[j] >= p->n_cams)
-            return fail(PCS_ERR_RANGE, "view %lld has camera %d outside [0,%lld)", (long long)j, view_cam[j], (long long)p->n_cams);
-        if (view_im[j] < 0 || view_im[j] >= p->n_imgs)
-            return fail(PCS_ERR_RANGE, "view %lld has image %d outside [0,%lld)", (long long)j, view_im[j], (long long)p->n_imgs);
+    const int bad = check_grouped_observations("pcs_rig_set_observations", n_obs, key, p->n_keys, n_views, start_inds, [&](int64_t j) {
+        if (const int rc = check_group_entity("view", j, "camera", view_cam[j], p->n_cams)) return rc;
+        if (const int rc = check_group_entity("view", j, "image", view_im[j], p->n_imgs)) return rc;
         ++im_start[view_im[j] + 1];
-    }
-    for (int64_t r = 0; r < n_obs; ++r)
-        if (key[r] < 0 || key[r] >= p->n_keys) return fail(PCS_ERR_RANGE, "observation %lld has key %d outside [0,%lld)", (long long)r, key[r], (long long)p->n_keys);
+        return (int)PCS_OK;
+    });
+    if (bad) return bad;
     for (int64_t i = 0; i < p->n_imgs; ++i) im_start[i + 1] += im_start[i];
     std::vector<int32_t> im_views((size_t)n_views);   // a counting sort by image: stable, so an image's views stay in view order
     {
@@ -132,8 +126,7 @@ int pcs_rig_set_observations(pcs_rig_graph *p, int64_t n_obs, const int32_t *key
 
 int pcs_rig_set_view_poses(pcs_rig_graph *p, const double *poses) {
     if (!p || !poses) return fail(PCS_ERR_ARG, "pcs_rig_set_view_poses: bad arguments");
-    HIPCHK(p->core.quiesce());
-    HIPCHK(hipMemcpy(p->pose.p, poses, sizeof(double) * 6 * p->n_cams * p->n_imgs, hipMemcpyHostToDevice));
+    if (const int rc = set_fixed_array(p->core, p->pose, poses, sizeof(double) * 6 * p->n_cams * p->n_imgs)) return rc;
     p->have_poses = true;
     p->mat_valid = p->edges_valid = p->scores_valid = false;
     return PCS_OK;
@@ -141,8 +134,7 @@ int pcs_rig_set_view_poses(pcs_rig_graph *p, const double *poses) {
 
 int pcs_rig_set_extrinsics(pcs_rig_graph *p, const double *ext) {
     if (!p || !ext) return fail(PCS_ERR_ARG, "pcs_rig_set_extrinsics: bad arguments");
-    HIPCHK(p->core.quiesce());
-    HIPCHK(hipMemcpy(p->ext.p, ext, sizeof(double) * 12 * p->n_cams, hipMemcpyHostToDevice));
+    if (const int rc = set_fixed_array(p->core, p->ext, ext, sizeof(double) * 12 * p->n_cams)) return rc;
     p->have_extr = true;
     p->scores_valid = false;
     return PCS_OK;
