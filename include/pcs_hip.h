@@ -628,6 +628,68 @@ int pcs_pnp_results(pcs_pose_estimator *p, double *pose, double *pose_init, doub
 int pcs_pnp_last_kernel_ms(pcs_pose_estimator *p, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
+ * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
+ *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one
+ *           independent 6-parameter least-squares problem per image over the detections of all cameras that see it; every image is
+ *           solved by its own group of lanes with its own damping, and a converged image is frozen while its neighbours continue.
+ * Unknown per image: T = (R, t), target -> world, as [rotvec, t].  Residual of a detection (camera c, key k): uv - project_c(E_c (R X_k + t))
+ * in the measured pixels, full Brown-Conrady model; update R <- exp([d omega]x) R, t <- t + d t.  Damping, accept rule, stops and status
+ * codes are those of pcs_pnp_run; a point counts as behind when it is behind ITS camera.  No floating-point atomics, every sum in a fixed
+ * order: for a given group width two runs give the same bits; the two widths differ in rounding only.
+ *   pcs_rigpose_create            n_cams cameras, a template of n_keys points (no counterpart: a handle)
+ *   pcs_rigpose_destroy           frees the handle (no counterpart)
+ *   pcs_rigpose_set_cameras       intr (n_cams, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2], held fixed (find_target.py:9-82 puts "int" and
+ *                                 "dst" of every camera into fixed_params)
+ *   pcs_rigpose_set_extrinsics    ext (n_cams, 12) world -> camera, rows [R | t] of a 3 x 4 transform, held fixed (the "ext" of
+ *                                 find_target.py:9-82); the convention of pcs_rig_set_extrinsics
+ *   pcs_rigpose_set_template      points (n_keys, 3): target.point_data flattened (find_target.py:9-82 hands the target to the handler)
+ *   pcs_rigpose_set_observations  host arrays, copied: key (n_obs) int32, cam (n_obs) int32, uv (n_obs, 2), sorted by (image, camera,
+ *                                 key); group j (one image) owns rows [start_inds[j], start_inds[j+1]).  Inside a group cam must not
+ *                                 decrease -> PCS_ERR_ARG; cameras and keys are range-checked -> PCS_ERR_RANGE; the first bad group
+ *                                 decides the refusal.  Forgets the start poses.  (find_target.py:9-82 selects the detections of the
+ *                                 time step the same way)
+ *   pcs_rigpose_set_start         poses (n_groups, 6) = [rotvec, t] of the start, after the observations (find_target.py:9-82 starts
+ *                                 from calc_initial_params)
+ *   pcs_rigpose_run               queue the kernel on `stream` (NULL = the handle's stream).  group_lanes: 16 or 64 lanes per image, 0
+ *                                 = 64 when the mean number of observations per image is at least 256, else 16.  A group with fewer
+ *                                 than min_points observations, a non-finite start or a point behind its camera at the start is not
+ *                                 estimated: NaN pose, status 0.  Outputs (device buffers of the caller, or NULL = handle-owned):
+ *                                 d_pose (n_groups, 6); d_rms (n_groups, 2) RMS reprojection error at the returned pose and at the
+ *                                 start, pixels; d_info (n_groups, 4) int32 {trials used, status PCS_RIGPOSE_*, observations, cameras
+ *                                 that contributed}; d_hess (n_groups, 21) the packed upper triangle of J'J at the returned pose by
+ *                                 rows (00 01 .. 05 11 .. 55; NaN when not estimated); with flags PCS_RIGPOSE_RESIDUALS, d_resid
+ *                                 (n_obs, 2) residuals at the returned pose in observation order.  PCS_ERR_ARG: NULL handle,
+ *                                 max_iter < 0, a negative or non-finite tolerance, min_points < 1, another group_lanes, unknown flags.
+ *                                 (replaces the optimiser call of find_target.py:9-82)
+ *   pcs_rigpose_results           copy handle-owned outputs of the last run to the host (any pointer may be NULL; blocking) (the poses
+ *                                 find_target.py:9-82 reads back from the optimised parameter vector)
+ *   pcs_rigpose_last_kernel_ms    device time of the last run: ordering of the images and the LM kernel.  PCS_ERR_STATE when the last
+ *                                 run had no images and so queued nothing (no counterpart).
+ */
+typedef struct pcs_rig_localiser pcs_rig_localiser;
+#define PCS_RIGPOSE_RESIDUALS 1
+enum {
+    PCS_RIGPOSE_NOT_ESTIMATED = 0,   /* too few observations, a non-finite start or a point behind its camera at the start: the pose is NaN */
+    PCS_RIGPOSE_CONVERGED = 1,       /* ftol, xtol or gtol */
+    PCS_RIGPOSE_MAX_ITER = 2,        /* max_iter trials used */
+    PCS_RIGPOSE_NO_DECREASE = 3      /* the damping grew past 1e10 without a lower cost, or the damped system lost definiteness */
+};
+enum { PCS_RIGPOSE_OUT_POSE = 1, PCS_RIGPOSE_OUT_RMS = 2, PCS_RIGPOSE_OUT_INFO = 4, PCS_RIGPOSE_OUT_HESSIAN = 8, PCS_RIGPOSE_OUT_RESIDUALS = 16 };
+int pcs_rigpose_create(pcs_rig_localiser **out, int device, int64_t n_cams, int64_t n_keys);
+int pcs_rigpose_destroy(pcs_rig_localiser *p);
+int pcs_rigpose_set_cameras(pcs_rig_localiser *p, const double *intr);
+int pcs_rigpose_set_extrinsics(pcs_rig_localiser *p, const double *ext);
+int pcs_rigpose_set_template(pcs_rig_localiser *p, const double *points);
+int pcs_rigpose_set_observations(pcs_rig_localiser *p, int64_t n_obs, const int32_t *key, const int32_t *cam, const double *uv, int64_t n_groups,
+                                 const int64_t *start_inds);
+int pcs_rigpose_set_start(pcs_rig_localiser *p, const double *poses);
+int pcs_rigpose_run(pcs_rig_localiser *p, int max_iter, double ftol, double xtol, double gtol, int min_points, int group_lanes, int flags,
+                    double *d_pose, double *d_rms, int32_t *d_info, double *d_hess, double *d_resid, void *stream);
+int pcs_rigpose_results(pcs_rig_localiser *p, double *pose, double *rms, int32_t *info, double *hess, double *resid);
+int pcs_rigpose_last_kernel_ms(pcs_rig_localiser *p, float *kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Camera intrinsics from planar target views (csrc/ba_intrinsics.hpp).  Since pcs_version() 106.
  * Replaces: AbstractTarget.initial_calibration (calibration_targets/abstract_target.py:263-343: per camera every (image, board) group
  *           with more than 12 detections goes to cv2.calibrateCamera), the rough intrinsics calc_initial_params starts from

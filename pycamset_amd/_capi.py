@@ -41,6 +41,9 @@ TRI_NOT_REFINED, TRI_CONVERGED, TRI_MAX_ITER, TRI_NO_DECREASE = 0, 1, 2, 3
 PNP_RESIDUALS = 1                        # include/pcs_hip.h PCS_PNP_RESIDUALS
 # include/pcs_hip.h PCS_PNP_*: per-view status of the pose estimation
 PNP_NOT_ESTIMATED, PNP_CONVERGED, PNP_MAX_ITER, PNP_NO_DECREASE = 0, 1, 2, 3
+RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
+# include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
+RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
 # include/pcs_hip.h PCS_INTR_MODEL_*, PCS_INTR_* (per camera) and PCS_INTR_GROUP_* (per (camera, image, board) group)
 INTR_MODEL_IDS = {"auto": 0, "full": 1, "focal": 2}
 INTR_NOT_ESTIMATED, INTR_FULL, INTR_FOCAL, INTR_FOCAL_FALLBACK = 0, 1, 2, 3
@@ -151,6 +154,16 @@ SYMBOLS = {
     "pcs_pnp_run": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "pcs_pnp_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
     "pcs_pnp_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
+    "pcs_rigpose_destroy": (c_int, [_P]),
+    "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),
+    "pcs_rigpose_set_extrinsics": (c_int, [_P, POINTER(c_double)]),
+    "pcs_rigpose_set_template": (c_int, [_P, POINTER(c_double)]),
+    "pcs_rigpose_set_observations": (c_int, [_P, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_rigpose_set_start": (c_int, [_P, POINTER(c_double)]),
+    "pcs_rigpose_run": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "pcs_rigpose_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]),
+    "pcs_rigpose_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_intr_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_intr_destroy": (c_int, [_P]),
     "pcs_intr_set_template": (c_int, [_P, POINTER(c_double)]),

@@ -952,3 +952,275 @@ def rig_candidate_scores(dct, points, intr, view_poses, ext, n_imgs: int, device
     W, errors = g.results()
     last_rig_kernel_ms = sum(g.last_scores_ms())
     return W, errors
+
+
+# ---- the target pose per image in a calibrated rig (row f9: optimisation/find_target.py) -----------------------------------------------
+# per-image status of the localisation (include/pcs_hip.h PCS_RIGPOSE_*: the meanings of PCS_PNP_*)
+from ._capi import RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE, RIGPOSE_NOT_ESTIMATED  # noqa: E402,F401
+last_rigpose_kernel_ms = None
+# a scaled J'J whose smallest eigenvalue is below this fraction of its largest leaves no digit of the covariance: the image is reported NaN
+COVARIANCE_RANK_TOL = 1e-12
+
+
+def unpack_hessian(packed) -> np.ndarray:
+    """(n, 21) packed upper triangles by rows (00 01 .. 05 11 .. 55) -> (n, 6, 6) symmetric."""
+    packed = np.asarray(packed, dtype=np.float64).reshape(-1, 21)
+    H = np.empty((packed.shape[0], 6, 6))
+    iu = np.triu_indices(6)
+    H[:, iu[0], iu[1]] = packed
+    H[:, iu[1], iu[0]] = packed
+    return H
+
+
+@dataclass
+class ImagePoses:
+    """Target poses per image in a rig of fixed cameras (``localise_target``): ``poses`` (I, 6) = [rotvec, t], target -> world,
+    X_cam = E_c (R(rotvec) X_target + t); ``poses_init`` the start; ``rms`` / ``rms_init`` (I,) RMS reprojection error in pixels over all
+    detections of the image at the pose / at the start (rms <= rms_init); ``status`` (RIGPOSE_*), ``iterations`` (LM trials),
+    ``n_points`` (detections), ``n_cams`` (cameras that contributed): (I,) int32; ``hessian`` (I, 6, 6) = J'J at the pose for the update
+    R <- exp([d omega]x) R, t <- t + d t; ``residuals`` (N, 2) uv - projection in the table's row order, or None.  Images without
+    detections, with fewer than ``min_points`` or without a usable start: NaN, status 0."""
+    poses: np.ndarray
+    poses_init: np.ndarray
+    rms: np.ndarray
+    rms_init: np.ndarray
+    status: np.ndarray
+    iterations: np.ndarray
+    n_points: np.ndarray
+    n_cams: np.ndarray
+    hessian: np.ndarray
+    residuals: np.ndarray | None = None
+
+    def covariance(self, absolute_sigma: bool = False) -> np.ndarray:
+        """(I, 6, 6) = sigma^2 inv(H) in the coordinates (d omega, d t) of the update, sigma^2 = sum r^2 / (2 n - 6), or 1 with
+        ``absolute_sigma`` (the meanings of ``device_solver.parameter_covariance``).  NaN for an image that was not estimated, has no
+        degree of freedom left (2 n <= 6) or a singular H (a NumPy batch inverse on the host; nothing raises)."""
+        I = self.hessian.shape[0]
+        out = np.full((I, 6, 6), np.nan)
+        n = self.n_points.astype(np.float64)
+        for i in range(I):
+            H = self.hessian[i]
+            dof = 2.0 * n[i] - 6.0
+            if not np.all(np.isfinite(H)) or (dof <= 0 and not absolute_sigma):
+                continue
+            d = np.sqrt(np.diag(H))
+            if not np.all(d > 0):
+                continue
+            lam = np.linalg.eigvalsh(H / np.outer(d, d))
+            if not lam[0] > COVARIANCE_RANK_TOL * lam[-1]:
+                continue
+            try:
+                inv = np.linalg.inv(H)
+            except np.linalg.LinAlgError:
+                continue
+            s2 = 1.0 if absolute_sigma else self.rms[i] ** 2 * n[i] / dof
+            out[i] = s2 * inv
+        return out
+
+
+class RigLocaliser(_Handle):
+    """Owner of one ``pcs_rig_localiser`` handle (include/pcs_hip.h): camera and extrinsic tables, template, observation copies, start
+    poses and outputs stay on the device across calls."""
+
+    _create, _destroy = "pcs_rigpose_create", "pcs_rigpose_destroy"
+
+    def __init__(self, n_cams: int, n_keys: int, device: int = 0):
+        super().__init__(device, n_cams, n_keys)
+        self.n_cams, self.n_keys, self.device = int(n_cams), int(n_keys), int(device)
+        self.n_groups, self.n_obs = 0, 0
+        self._residuals = False
+
+    def set_cameras(self, intr):
+        K = np.ascontiguousarray(intr, dtype=np.float64)
+        if K.shape != (self.n_cams, 9):
+            raise ValueError(f"expected intr ({self.n_cams}, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2]")
+        self._call("pcs_rigpose_set_cameras", self._h, self._ptr(K))
+
+    def set_extrinsics(self, ext):
+        E = np.ascontiguousarray(ext, dtype=np.float64)
+        if E.shape != (self.n_cams, 3, 4):
+            raise ValueError(f"expected ext ({self.n_cams}, 3, 4) world -> camera")
+        self._call("pcs_rigpose_set_extrinsics", self._h, self._ptr(E))
+
+    def set_template(self, points):
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        if pts.shape[0] != self.n_keys:
+            raise ValueError(f"expected {self.n_keys} template points")
+        self._call("pcs_rigpose_set_template", self._h, self._ptr(pts))
+
+    def set_observations(self, key, cam, uv, start_inds):
+        """Host arrays sorted by (image, camera, key): key, cam (n_obs,) int, uv (n_obs, 2), start_inds (n_groups + 1,)."""
+        key = np.ascontiguousarray(key, dtype=np.int32)
+        cam = np.ascontiguousarray(cam, dtype=np.int32)
+        uv = np.ascontiguousarray(uv, dtype=np.float64)
+        start = np.ascontiguousarray(start_inds, dtype=np.int64)
+        if start.ndim != 1 or start.shape[0] < 1 or key.ndim != 1 or cam.shape != key.shape or uv.shape != (key.shape[0], 2):
+            raise ValueError("expected key (n_obs,), cam (n_obs,), uv (n_obs, 2), start_inds (n_groups + 1,)")
+        self._call("pcs_rigpose_set_observations", self._h, key.shape[0], self._ptr(key), self._ptr(cam), self._ptr(uv), start.shape[0] - 1, self._ptr(start))
+        self.n_groups, self.n_obs = start.shape[0] - 1, key.shape[0]
+
+    def set_start(self, poses):
+        p = np.ascontiguousarray(poses, dtype=np.float64)
+        if p.shape != (self.n_groups, 6):
+            raise ValueError(f"expected start poses ({self.n_groups}, 6)")
+        self._call("pcs_rigpose_set_start", self._h, self._ptr(p))
+
+    def run(self, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
+            gtol: float = REFINE_DEFAULTS["gtol"], min_points: int = 6, group_lanes: int | None = None, residuals: bool = False,
+            stream: int | None = None):
+        """Queue the kernel (asynchronous; handle-owned outputs, fetched with ``results()``)."""
+        max_iter, ftol, xtol, gtol = check_refine_options(max_iter, ftol, xtol, gtol)
+        min_points = check_min_points(min_points)
+        lanes = check_group_lanes(group_lanes)
+        self._call("pcs_rigpose_run", self._h, max_iter, ftol, xtol, gtol, min_points, lanes, self._capi.RIGPOSE_RESIDUALS if residuals else 0,
+                   None, None, None, None, None, _stream_arg(stream))
+        self._residuals = bool(residuals)
+
+    def results(self):
+        """Wait for the last ``run``: (pose (n, 6), rms (n, 2), info (n, 4) int32, hessian (n, 21), residuals or None)."""
+        n = self.n_groups
+        pose, rms, info, hess = np.empty((n, 6)), np.empty((n, 2)), np.empty((n, 4), dtype=np.int32), np.empty((n, 21))
+        resid = np.empty((self.n_obs, 2)) if self._residuals else None
+        self._call("pcs_rigpose_results", self._h, self._ptr(pose), self._ptr(rms), self._ptr(info), self._ptr(hess), self._ptr(resid))
+        return pose, rms, info, hess, resid
+
+    def last_kernel_ms(self) -> float:
+        return self._ms("pcs_rigpose_last_kernel_ms")
+
+
+def check_group_lanes(group_lanes) -> int:
+    """None (the width rule of include/pcs_hip.h pcs_rigpose_run decides), 16 or 64 -> the C argument."""
+    if group_lanes is None:
+        return 0
+    if isinstance(group_lanes, bool) or not isinstance(group_lanes, (int, np.integer)) or int(group_lanes) not in (16, 64):
+        raise ValueError(f"group_lanes must be None, 16 or 64, got {group_lanes!r}")
+    return int(group_lanes)
+
+
+def group_by_image(dct):
+    """The host grouping of ``localise_target``: one stable sort on (im, cam, key), skipped when the table is already ordered, so that
+    an image's observations reach the device in one order whatever the order of the table.  ``dct`` holds valid camera indices.
+    -> (order or None, image ids (n_groups,), start (n_groups + 1,))."""
+    d = np.asarray(dct, dtype=np.float64)
+    im, cam, key = d[:, 1].astype(np.int64), d[:, 0].astype(np.int64), d[:, 2].astype(np.int64)
+    n = d.shape[0]
+    cspan = int(cam.max()) + 1 if n else 1
+    kspan = int(key.max()) + 1 if n else 1
+    rank = (im * cspan + cam) * kspan + key if n and key.min() >= 0 else im * cspan + cam   # keys out of range are refused by the handle later
+    order = None
+    if n > 1 and np.any(rank[1:] < rank[:-1]):
+        order = np.argsort(rank, kind="stable")
+        im = im[order]
+    head = np.ones(n, dtype=bool)
+    head[1:] = im[1:] != im[:-1]
+    first = np.nonzero(head)[0]
+    return order, im[first], np.concatenate([first, [n]]).astype(np.int64)
+
+
+_rigpose_cache: dict = {}
+
+
+def _rig_localiser(device: int, n_cams: int, n_keys: int) -> RigLocaliser:
+    return _cached_handle(_rigpose_cache, (int(device), int(n_cams), int(n_keys)), lambda: RigLocaliser(n_cams, n_keys, device))
+
+
+def rig_pose_start(dct, points, intr, ext, n_imgs: int, min_points: int = 6, device: int = 0) -> np.ndarray:
+    """A start (I, 6) for ``localise_target`` from the existing pieces: the per-view poses of ``estimate_view_poses``, every camera's
+    estimate W[c', i] = inv(E_c') M[c', i] of the image's pose and its error over ALL detections of the image
+    (``rig_candidate_scores``); the image takes the finite candidate of lowest error, ties to the lowest camera.  NaN where there is none."""
+    from .pose_seeding import pose_from_4x4, to_4x4
+
+    vp = estimate_view_poses(dct, points, intr, n_imgs=n_imgs, min_points=min_points, device=device)
+    W, errors = rig_candidate_scores(dct, points, intr, vp.poses, ext, n_imgs, device=device)
+    W, errors = np.asarray(W, dtype=np.float64).reshape(-1, n_imgs, 3, 4), np.asarray(errors, dtype=np.float64).reshape(-1, n_imgs)
+    finite = np.isfinite(errors) & np.isfinite(W.reshape(W.shape[0], n_imgs, 12)).all(axis=-1)
+    best = np.argmin(np.where(finite, errors, np.inf), axis=0)   # the first of equal minima: the lowest camera
+    start = pose_from_4x4(to_4x4(W[best, np.arange(n_imgs)]))
+    start[~finite.any(axis=0)] = np.nan
+    return start
+
+
+def check_localise_arguments(dct, points, intr, ext, n_imgs, poses_init, min_points, max_iter, ftol, xtol, gtol, group_lanes):
+    """Everything ``localise_target`` can refuse on the host (ValueError), before a device is touched."""
+    opts = check_refine_options(max_iter, ftol, xtol, gtol)
+    min_points = check_min_points(min_points)
+    lanes = check_group_lanes(group_lanes)
+    d = np.asarray(dct, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64)
+    K = np.asarray(intr, dtype=np.float64)
+    E = np.asarray(ext, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 5 or K.ndim != 2 or K.shape[1] != 9:
+        raise ValueError("expected dct (N, 5) = [cam, im, key, u, v] and intr (C, 9)")
+    if pts.size == 0 or pts.size % 3:
+        raise ValueError("expected template points (K, 3)")
+    pts = pts.reshape(-1, 3)
+    C = K.shape[0]
+    if E.shape != (C, 3, 4):
+        raise ValueError(f"expected ext ({C}, 3, 4) world -> camera, got {E.shape}")
+    if not (np.all(np.isfinite(K)) and np.all(np.isfinite(E))):
+        raise ValueError("intr and ext must be finite: every camera is held fixed")
+    if n_imgs is None:
+        n_imgs = int(d[:, 1].max()) + 1 if d.shape[0] else 0
+    if isinstance(n_imgs, bool) or not isinstance(n_imgs, (int, np.integer)) or n_imgs < 0:
+        raise ValueError(f"n_imgs must be an integer >= 0, got {n_imgs!r}")
+    I = int(n_imgs)
+    if d.shape[0]:
+        if d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 1].min() < 0 or d[:, 1].max() >= I:
+            raise ValueError("camera or image index of the table outside the intrinsics / n_imgs")
+        if d[:, 2].min() < 0 or d[:, 2].max() >= pts.shape[0]:
+            raise ValueError("key of the table outside the template")
+    if poses_init is not None:
+        poses_init = np.array(poses_init, dtype=np.float64)
+        if poses_init.shape != (I, 6):
+            raise ValueError(f"expected poses_init ({I}, 6), got {poses_init.shape}")
+    return d, pts, K, E, I, poses_init, min_points, opts, lanes
+
+
+def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_init=None, min_points: int = 6,
+                    max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
+                    gtol: float = REFINE_DEFAULTS["gtol"], group_lanes: int | None = None, return_residuals: bool = False,
+                    device: int = 0) -> ImagePoses:
+    """The pose of the known target in every image of a rig whose cameras are held fixed, on the device (include/pcs_hip.h
+    pcs_rigpose_run): what the reference's ``find_target_poses`` (optimisation/find_target.py:9-82) gets from a bundle adjustment with
+    every camera's "ext" / "int" / "dst" fixed, as one independent 6-parameter problem per image.
+
+    ``dct``: the flattened (N, 5) table [cam, im, key, u, v] in any order (the same table shuffled gives the same bits); ``points``: the
+    template (K, 3); ``intr``: (C, 9) rows [fx, cx, fy, cy, k0, k1, p0, p1, k2]; ``ext``: (C, 3, 4) world -> camera, the convention of
+    ``rig_candidate_scores``; ``n_imgs``: images of the result (default: largest image index + 1); ``poses_init``: (I, 6) starts (NaN
+    rows are not estimated), default ``rig_pose_start``; ``group_lanes``: 16 or 64 lanes per image, default by the mean number of
+    detections per image (include/pcs_hip.h)."""
+    global last_rigpose_kernel_ms
+    d, pts, K, E, I, start, min_points, opts, lanes = check_localise_arguments(dct, points, intr, ext, n_imgs, poses_init, min_points, max_iter, ftol, xtol,
+                                                                               gtol, group_lanes)
+    out = ImagePoses(poses=np.full((I, 6), np.nan), poses_init=np.full((I, 6), np.nan), rms=np.full(I, np.nan), rms_init=np.full(I, np.nan),
+                     status=np.zeros(I, dtype=np.int32), iterations=np.zeros(I, dtype=np.int32), n_points=np.zeros(I, dtype=np.int32),
+                     n_cams=np.zeros(I, dtype=np.int32), hessian=np.full((I, 6, 6), np.nan),
+                     residuals=np.empty((d.shape[0], 2)) if return_residuals else None)
+    if start is not None:
+        out.poses_init[:] = start
+    if d.shape[0] == 0:
+        return out
+    order, ids, first = group_by_image(d)
+    ds = d if order is None else d[order]
+    if start is None:
+        start = rig_pose_start(ds, pts, K, E, I, min_points=min_points, device=device)
+        out.poses_init[:] = start
+    loc = _rig_localiser(device, K.shape[0], pts.shape[0])
+    loc.set_cameras(K)
+    loc.set_extrinsics(E)
+    loc.set_template(pts)
+    loc.set_observations(ds[:, 2].astype(np.int32), ds[:, 0].astype(np.int32), ds[:, 3:5], first)
+    loc.set_start(start[ids])
+    loc.run(*opts, min_points=min_points, group_lanes=lanes or None, residuals=return_residuals)
+    pose, rms, info, hess, resid = loc.results()
+    last_rigpose_kernel_ms = loc.last_kernel_ms()
+    out.poses[ids] = pose
+    out.rms[ids], out.rms_init[ids] = rms[:, 0], rms[:, 1]
+    out.iterations[ids], out.status[ids], out.n_points[ids], out.n_cams[ids] = info[:, 0], info[:, 1], info[:, 2], info[:, 3]
+    out.hessian[ids] = unpack_hessian(hess)
+    if return_residuals:
+        if order is None:
+            out.residuals = resid
+        else:
+            out.residuals[order] = resid
+    return out

@@ -39,6 +39,7 @@
 #include "ba_triangulate.hpp"
 #include "ba_tri_refine.hpp"
 #include "ba_pnp.hpp"
+#include "ba_rigpose.hpp"
 #include "ba_intrinsics.hpp"
 #include "ba_riggraph.hpp"
 #include "ba_groupstats.hpp"
@@ -53,6 +54,7 @@ using namespace pcs;
 #include "pcs_dettable.inc"
 #include "pcs_triangulator.inc"
 #include "pcs_pnp.inc"
+#include "pcs_rigpose.inc"
 #include "pcs_intrinsics.inc"
 #include "pcs_rig.inc"
 #include "pcs_stats.inc"

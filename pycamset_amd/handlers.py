@@ -283,7 +283,7 @@ class TemplateBundleHandler:  # th:80-240
             "no start vector has been set: compute one from the detections with calc_initial_params() (template_handler.py:302-346, "
             "device PnP) and hand it to set_initial_params(), or supply your own")
 
-    def calc_initial_params(self, intr=None, *, seeding: str = "reference") -> np.ndarray:  # th:302-346
+    def calc_initial_params(self, intr=None, *, seeding: str = "reference", refine_poses: bool = False) -> np.ndarray:  # th:302-346
         """A start vector from the detections: per-view target poses on the device (``compiled_helpers.estimate_view_poses``), the view
         graph of ``pose_seeding.estimate_camera_relative_poses`` (th:468-601), then the free entries in slab order — unfixed intrinsics,
         extrinsics and poses (plus, for the self and free chains, the free point scalars of the template).  ``intr``: (C, 9) rows
@@ -295,7 +295,12 @@ class TemplateBundleHandler:  # th:80-240
 
         ``seeding``: ``"reference"`` (default) is the reference's view graph, which needs an image that every camera sees and raises
         ValueError without one; ``"graph"`` is ``pose_seeding.estimate_camera_relative_poses_graph``, which needs only a connected
-        co-visibility graph; ``"auto"`` takes the reference's and falls back to the graph on exactly that error."""
+        co-visibility graph; ``"auto"`` takes the reference's and falls back to the graph on exactly that error.
+
+        ``refine_poses``: the seeded pose of an image is ONE camera's estimate, the candidate of lowest error.  When true, every image's
+        pose is refined over the detections of all cameras with the seeded extrinsics and intrinsics held fixed
+        (``compiled_helpers.localise_target``) before the vector is assembled; an image that could not be refined keeps its seeded pose
+        and the reference image, whose pose is exactly 0 and fixed, is left alone.  Off by default."""
         from .pose_seeding import estimate_camera_relative_poses, estimate_camera_relative_poses_graph
 
         if seeding not in ("reference", "graph", "auto"):
@@ -330,12 +335,27 @@ class TemplateBundleHandler:  # th:80-240
         extr, poses, self.initial_per_im_error, missing = seeded
         self.missing_poses = missing
         self.find_and_exclude_transform_outliers(self.initial_per_im_error)   # th:319
+        if refine_poses:
+            poses = self._refine_seeded_poses(args[0], args[1], intr, extr, poses)
         parts = [intr[bp.intr_unfixed].ravel(), extr[bp.extr_unfixed].ravel()]
         if "pose" in bp.groups:
             parts.append(poses[bp.poses_unfixed].ravel())
         if "bdpt" in bp.groups:
             parts.append(self.flat_point_data[bp.bdpt_unfixed])
         return np.concatenate(parts)
+
+    def _refine_seeded_poses(self, dct, points, intr, extr, poses) -> np.ndarray:
+        """``calc_initial_params(refine_poses=True)``: the seeded image poses refined per image with every camera fixed at its seeded
+        extrinsics.  The accept rule only ever lowers an image's cost, so no image gets worse."""
+        from . import compiled_helpers as ch
+        from .pose_seeding import pose_to_4x4
+
+        poses = np.array(poses, dtype=np.float64)
+        res = ch.localise_target(dct, points, intr, pose_to_4x4(extr)[:, :3, :], n_imgs=poses.shape[0], poses_init=poses,
+                                 device=self.op_fun.device)
+        take = (res.status != ch.RIGPOSE_NOT_ESTIMATED) & np.all(np.isfinite(res.poses), axis=1) & ~np.all(poses == 0.0, axis=1)
+        poses[take] = res.poses[take]
+        return poses
 
     def find_and_exclude_transform_outliers(self, per_im_error):  # th:242-279
         """The MAD test (``diagnostics.mad_outliers``, threshold 20) on the per-image error over the images that are not missing yet,

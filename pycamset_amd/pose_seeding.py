@@ -277,3 +277,51 @@ def estimate_camera_relative_poses_graph(dct, points, intr, n_cams: int, n_imgs:
                         gap=relative_gap(edges.score, edges.runner_up), T=T[:, :3, :], edge_cost=edge_cost, parents=parents, best_cam=best_cam,
                         error_gap=error_gap, errors=errors, rho=float(edges.rho))
     return out + (info,)
+
+
+# ---- resection: the extrinsics of every camera with the target poses held fixed ----------------------------------------------------
+@dataclass
+class CameraResection:
+    """What ``resect_cameras`` returns, per camera: ``poses`` (C, 6) = [rotvec, t] world -> camera (NaN where not estimated), ``rms`` /
+    ``rms_init`` (C,) RMS reprojection error in pixels, ``status`` (PNP_*), ``iterations``, ``n_points`` (C,) int32; ``images`` (I,)
+    bool: the images that took part (a finite pose)."""
+    poses: np.ndarray
+    rms: np.ndarray
+    rms_init: np.ndarray
+    status: np.ndarray
+    iterations: np.ndarray
+    n_points: np.ndarray
+    images: np.ndarray
+
+
+def resect_cameras(dct, points, intr, image_poses, *, view_pose_fn=None, **opts) -> CameraResection:
+    """The mirror problem of ``compiled_helpers.localise_target``: the extrinsics of every camera with the target poses of the images
+    held fixed — a camera added to a calibrated rig.  No kernel of its own: the world points T_i X_k of all images form one "template"
+    of I * K points with key' = i * K + k, every camera is one view of it, and the batched PnP
+    (``view_pose_fn(dct', points', intr, n_imgs=1, **opts)``, default ``compiled_helpers.estimate_view_poses``) does the rest.
+    ``image_poses`` (I, 6) = [rotvec, t], target -> world; images with a NaN pose are dropped from the table first."""
+    from . import compiled_helpers as ch
+
+    view_pose_fn = ch.estimate_view_poses if view_pose_fn is None else view_pose_fn
+    d = np.asarray(dct, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    K = np.asarray(intr, dtype=np.float64)
+    P = np.asarray(image_poses, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 5 or K.ndim != 2 or K.shape[1] != 9 or P.ndim != 2 or P.shape[1] != 6:
+        raise ValueError("expected dct (N, 5) = [cam, im, key, u, v], intr (C, 9) and image poses (I, 6)")
+    C, I, nk = K.shape[0], P.shape[0], pts.shape[0]
+    if d.shape[0] and (d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 1].min() < 0 or d[:, 1].max() >= I or d[:, 2].min() < 0 or d[:, 2].max() >= nk):
+        raise ValueError("camera, image or key index of the table outside the intrinsics / image poses / template")
+    known = np.all(np.isfinite(P), axis=1)
+    T = pose_to_4x4(np.where(known[:, None], P, 0.0))
+    world = (np.einsum("iab,kb->ika", T[:, :3, :3], pts) + T[:, None, :3, 3]).reshape(I * nk, 3)   # unknown images: never referenced
+    rows = d[known[d[:, 1].astype(np.int64)]]
+    table = np.empty((rows.shape[0], 5))
+    table[:, 0], table[:, 1] = rows[:, 0], 0.0
+    table[:, 2] = rows[:, 1].astype(np.int64) * nk + rows[:, 2].astype(np.int64)
+    table[:, 3:] = rows[:, 3:]
+    vp = view_pose_fn(table, world, K, n_imgs=1, **opts)
+    col = lambda name, fill, dtype: (np.asarray(getattr(vp, name))[:, 0] if hasattr(vp, name) else np.full(C, fill)).astype(dtype)   # noqa: E731
+    return CameraResection(poses=np.asarray(vp.poses, dtype=np.float64).reshape(C, 6), rms=col("rms", np.nan, np.float64),
+                           rms_init=col("rms_init", np.nan, np.float64), status=col("status", 0, np.int32),
+                           iterations=col("iterations", 0, np.int32), n_points=col("n_points", 0, np.int32), images=known)
