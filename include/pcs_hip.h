@@ -396,6 +396,18 @@ int pcs_genchain_eval_compact_device(pcs_genchain *h, const double *d_param_str,
  * of pcs_matfree.  pcs_genchain_set_blocks (once, after create) tells which global column a local column stands for: block b
  * covers local columns [col0_b, col0_b + np_b), its parameters of entity e (link_b: 0 camera, 1 image, 2 key) start at start_b + np_b e. */
 int pcs_genchain_set_blocks(pcs_genchain *h, int n_blocks, const int32_t *col0, const int32_t *n_params, const int32_t *link, const int64_t *start);
+/* SHARED parameter groups (since pcs_version() 111): a chain compiled with groups that are indexed through a table — one lens for
+ * several cameras, image i with the pose of position i mod n, one transform per face of a target, one global parameter set
+ * (pycamset_amd.function_blocks.param_type's mod_function / key_type.SINGLE) — takes the tables here: per block of the chain
+ * (n_blocks, link as for pcs_genchain_set_blocks) tables[b] = NULL for a block indexed by its entity, else table_len[b] group
+ * indices, one per camera / image / key, each in [0, n_mapped[b]); the block's group then holds n_mapped[b] parameter sets and a
+ * rigid group must have been created with group_count = n_mapped[b].  Call it once, after create and BEFORE pcs_genchain_set_blocks
+ * (whose range check then counts groups) and before the first evaluation.  Nothing is launched.  PCS_ERR_ARG: a table_len that
+ * is not the entity count of the link, a call after pcs_genchain_set_blocks or after an evaluation; PCS_ERR_RANGE: a table value
+ * outside [0, n_mapped[b]).  The ordered sums (option "deterministic") are refused for such a handle; a shared group is never the
+ * trailing group of the blocked normal equations. */
+int pcs_genchain_set_group_maps(pcs_genchain *h, int n_blocks, const int32_t *link, const int32_t *const *tables, const int64_t *table_len,
+                                const int32_t *n_mapped);
 int pcs_genchain_linearize(pcs_genchain *h, const double *param_str);
 int pcs_genchain_matfree(pcs_genchain *h, int op, const double *in, double *out, double *cost);
 /* The exact Levenberg-Marquardt step for ANY generated chain (round 5; csrc/ba_blockgram.hpp).  Replaces what scipy's trf does with the

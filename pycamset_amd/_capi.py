@@ -111,6 +111,7 @@ SYMBOLS = {
     "pcs_genchain_eval_compact": (c_int, [_P, POINTER(c_double), _P, _P]),
     "pcs_genchain_eval_compact_device": (c_int, [_P, _P, _P, _P, _P]),
     "pcs_genchain_set_blocks": (c_int, [_P, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int64)]),
+    "pcs_genchain_set_group_maps": (c_int, [_P, c_int, POINTER(c_int32), POINTER(c_void_p), POINTER(c_int64), POINTER(c_int32)]),
     "pcs_genchain_linearize": (c_int, [_P, POINTER(c_double)]),
     "pcs_genchain_matfree": (c_int, [_P, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double)]),
     "pcs_genchain_normal_layout": (c_int, [_P, POINTER(c_int64)]),

@@ -21,6 +21,13 @@ family raises.
 Parameter layout = the reference's ``make_param_struct`` (afb:777-820): unique parameter objects in block order — two
 blocks of the same class share their class-level ``params`` object (afb:160-163) and therefore ONE group; each group
 takes ``n_params x count(link type)`` consecutive columns of the parameter string.
+
+SHARED parameters (``param_type(..., mod_function=)``, ``key_type.SINGLE``; the reference declares both and builds neither,
+afb:42-61, afb:803): a group may be indexed THROUGH A TABLE entity -> group index.  The table is host data, evaluated once per
+engine (``param_type.group_table``) and uploaded (``pcs_genchain_set_group_maps``); the group then takes ``n_params x (largest
+group index + 1)`` columns.  The generated code only knows WHETHER a group goes through a table (``c.intr_m()`` instead of
+``c.intr()``, ...): a chain without tables compiles to the code it compiled to before, and the tables are not part of the code
+object's hash.  ``SINGLE`` is a camera-linked group whose table is all zeros, so nothing downstream knows a fourth link type.
 """
 from __future__ import annotations
 
@@ -42,6 +49,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 CACHE = PKG / "_chains"
 LINK_CAM, LINK_IMG, LINK_KEY = 0, 1, 2          # afb:42-46 key_type
+LINK_SINGLE = 3                                 # key_type.SINGLE: compiled as a camera-linked group with an all-zero table
 SRC_TEMPLATE, SRC_FREE = 0, 1
 MAX_GROUPS = 8
 
@@ -66,6 +74,7 @@ class BlockInfo:
     device_fun: str = ""
     device_jac: str = ""
     cpp_name: str = ""
+    mapped: bool = False       # its parameter group is indexed through a table entity -> group index (param_type.mod_function / SINGLE)
     templated: bool = False    # user SOURCE with ``template = True``: its ``inp`` is the detection's template point (afb:138, afb:374-375)
     translated: bool = False   # user block whose bodies were translated from Python (block_translate.py)
 
@@ -74,8 +83,29 @@ class BlockInfo:
 class ChainSpec:
     """What the code generator and the host side need to know about a composition."""
     blocks: list
-    # parameter groups in string order: dict(kind in {'intr', 'rigid', 'point', 'user'}, link, n_params, slab)
+    # parameter groups in string order: dict(kind in {'intr', 'rigid', 'point', 'user'}, link, n_params, slab, mapped, name)
     groups: list = field(default_factory=list)
+    params: list = field(default_factory=list)   # the groups' param_type objects: the tables of mapped groups are evaluated from them (group_tables)
+    _tables: dict = field(default_factory=dict, repr=False, compare=False)   # (group, entity count) -> its evaluated table
+
+    @property
+    def has_maps(self) -> bool:
+        return any(g["mapped"] for g in self.groups)
+
+    def group_tables(self, n_cams: int, n_imgs: int, n_keys: int) -> list:
+        """Per group the int32 table entity -> group index for these entity counts, None for a group indexed by the entity itself."""
+        count = {LINK_CAM: n_cams, LINK_IMG: n_imgs, LINK_KEY: n_keys}
+        out = []
+        for i, (g, par) in enumerate(zip(self.groups, self.params)):
+            if not g["mapped"]:
+                out.append(None)
+                continue
+            n = int(count[g["link"]])
+            if (i, n) not in self._tables:      # a mod_function is evaluated ONCE per spec and entity count (from_blocks fills this in when it has the counts)
+                t = par.group_table(n, g["name"])
+                self._tables[(i, n)] = np.arange(n, dtype=np.int32) if t is None else t   # (a spec made without counts cannot know that a callable is the identity)
+            out.append(self._tables[(i, n)])
+        return out
 
     @property
     def names(self) -> tuple:
@@ -103,7 +133,10 @@ class ChainSpec:
         return [b for b in self.blocks if b.kind == "user"]
 
     @classmethod
-    def from_blocks(cls, function_blocks) -> "ChainSpec":
+    def from_blocks(cls, function_blocks, counts=None) -> "ChainSpec":
+        """``counts`` = (n_cams, n_imgs, n_keys): with them a ``mod_function`` is evaluated here, and a table that maps every entity to
+        itself is dropped — that chain IS the un-mapped chain.  Without them (validation, pre-building code objects) every group that
+        declares a ``mod_function`` counts as mapped."""
         names = tuple(type(b).__name__ for b in function_blocks)
 
         def bad(why):
@@ -116,7 +149,7 @@ class ChainSpec:
             raise bad("a chain needs at least two blocks")
         if len(names) > MAX_BLOCKS:
             raise bad("too many blocks")
-        groups, seen, blocks = [], {}, []
+        groups, params, seen, blocks, tables = [], [], {}, [], {}
         rigid_id = user_id = 0
         for pos, b in enumerate(function_blocks):
             name = type(b).__name__
@@ -131,21 +164,43 @@ class ChainSpec:
             key = id(b.params)                      # the reference tells groups apart by object identity (afb:160-163)
             gkind = {"projection": "intr", "rigid": "rigid", "template_points": "rigid", "free_point": "point", "user": "user"}[kind]
             link, npar = int(b.params.link_type), int(b.params.n_params)
-            if link not in (LINK_CAM, LINK_IMG, LINK_KEY):
-                raise bad(f"block {name}: parameters must be per camera, per image or per key")
+            if link not in (LINK_CAM, LINK_IMG, LINK_KEY, LINK_SINGLE):
+                raise bad(f"block {name}: parameters must be per camera, per image, per key or SINGLE")
+            mod = getattr(b.params, "mod_function", None)
+            if link == LINK_SINGLE:
+                if mod is not None:
+                    raise bad(f"block {name}: key_type.SINGLE together with a mod_function")
+                link, mapped = LINK_CAM, True      # every camera -> group 0
+            elif mod is None:
+                mapped = False
+            elif counts is not None:
+                if key in seen:                      # a group's table is evaluated once, by its first block
+                    mapped = groups[seen[key]]["mapped"]
+                else:
+                    try:
+                        found = b.params.group_table(counts[link], name)
+                    except ValueError as e:
+                        raise bad(str(e)) from None
+                    mapped = found is not None
+                    if mapped:
+                        tables[(len(groups), int(counts[link]))] = found
+            else:
+                mapped = True
             if key not in seen:
-                g = dict(kind=gkind, link=link, n_params=npar, slab=None)
+                g = dict(kind=gkind, link=link, n_params=npar, slab=None, mapped=mapped, name=name)
                 if gkind == "rigid":
                     if link not in (LINK_CAM, LINK_IMG) or npar != 6:
-                        raise bad(f"block {name} does not carry a 6-parameter per-camera / per-image transform")
+                        raise bad(f"block {name} does not carry a 6-parameter per-camera / per-image transform (a transform per group of KEYS — the "
+                                  "faces of a target — is a user block: PER_KEY, 6 parameters, template = True; examples/shared_parameters.py)")
                     g["slab"] = rigid_id
                     rigid_id += 1
                 seen[key] = len(groups)
                 groups.append(g)
+                params.append(b.params)
             g = groups[seen[key]]
             if g["kind"] != gkind:
                 raise bad(f"block {name} shares its parameter object with a block of another kind")
-            info = BlockInfo(name=name, kind=kind, link=link, n_params=npar, nin=int(b.num_inp), nout=int(b.num_out), group=seen[key], slab=g["slab"])
+            info = BlockInfo(name=name, kind=kind, link=link, n_params=npar, nin=int(b.num_inp), nout=int(b.num_out), group=seen[key], slab=g["slab"], mapped=g["mapped"])
             if kind == "user":
                 if npar < 1 or info.nout < 1 or info.nin < 0:
                     raise bad(f"user block {name}: n_params >= 1, num_out >= 1, num_inp >= 0 expected")
@@ -182,20 +237,24 @@ class ChainSpec:
                 raise bad(f"`{b.name}` needs a block on either side")
             if i + 1 < len(blocks) and b.nin != blocks[i + 1].nout:
                 raise bad(f"block {i} ({b.name}) takes {b.nin} inputs but block {i + 1} ({blocks[i + 1].name}) produces {blocks[i + 1].nout}")
-        return cls(blocks=blocks, groups=groups)
+        return cls(blocks=blocks, groups=groups, params=params, _tables=tables)
 
     # -- the reference's parameter-string layout for given entity counts (afb:793-818) --------------------
     def layout(self, n_cams: int, n_imgs: int, n_keys: int) -> dict:
+        """A mapped group takes ``n_params x (largest group index + 1)`` columns: the reference's rule with its TODO filled in (afb:803)."""
         count = {LINK_CAM: n_cams, LINK_IMG: n_imgs, LINK_KEY: n_keys}
-        off, starts = 0, []
-        for g in self.groups:
+        tables = self.group_tables(n_cams, n_imgs, n_keys)
+        off, starts, gcount = 0, [], []
+        for g, t in zip(self.groups, tables):
             starts.append(off)
-            off += g["n_params"] * count[g["link"]]
-        rigid = [(starts[i], count[g["link"]]) for i, g in enumerate(self.groups) if g["kind"] == "rigid"]
+            gcount.append(int(count[g["link"]]) if t is None else (int(t.max()) + 1 if t.shape[0] else 1))
+            off += g["n_params"] * gcount[-1]
+        rigid = [(starts[i], gcount[i]) for i, g in enumerate(self.groups) if g["kind"] == "rigid"]
         intr = [starts[i] for i, g in enumerate(self.groups) if g["kind"] == "intr"]
         point = [starts[i] for i, g in enumerate(self.groups) if g["kind"] == "point"]
         return dict(n_params=off, starts=starts, rigid_off=[r[0] for r in rigid], rigid_count=[r[1] for r in rigid],
-                    intr_off=intr[0] if intr else 0, point_off=point[0] if point else 0, user_off=[starts[b.group] for b in self.user_blocks])
+                    intr_off=intr[0] if intr else 0, point_off=point[0] if point else 0, user_off=[starts[b.group] for b in self.user_blocks],
+                    tables=tables, group_count=gcount)
 
 
 def user_struct_lines(b: BlockInfo) -> list:
@@ -237,20 +296,20 @@ def emit_source(spec: ChainSpec) -> str:
         b = B[i]
         x_in = f"x{i + 1}"
         if b.kind == "free_point":
-            fwd.append(f"double x{i}[3]; {{ const double *pp = c.point(); x{i}[0] = pp[0]; x{i}[1] = pp[1]; x{i}[2] = pp[2]; }}")
+            fwd.append(f"double x{i}[3]; {{ const double *pp = c.point{'_m' if b.mapped else ''}(); x{i}[0] = pp[0]; x{i}[1] = pp[1]; x{i}[2] = pp[2]; }}")
         elif b.kind == "template_points":
             fwd.append(f"double x{i}[3], E{i}[9]; {{ const double *tp = c.tpoint(); const double X[3] = {{tp[0], tp[1], tp[2]}}; "
-                       f"pcs::rigid_fwd<JAC>(c.slab({b.slab}, {_LINK_CPP[b.link]}), X, x{i}, E{i}); }}")
+                       f"pcs::rigid_fwd<JAC>(c.slab{'_m' if b.mapped else ''}({b.slab}, {_LINK_CPP[b.link]}), X, x{i}, E{i}); }}")
         elif b.kind == "rigid":
-            fwd.append(f"double x{i}[3], E{i}[9]; pcs::rigid_fwd<JAC>(c.slab({b.slab}, {_LINK_CPP[b.link]}), {x_in}, x{i}, E{i});")
+            fwd.append(f"double x{i}[3], E{i}[9]; pcs::rigid_fwd<JAC>(c.slab{'_m' if b.mapped else ''}({b.slab}, {_LINK_CPP[b.link]}), {x_in}, x{i}, E{i});")
         elif b.kind == "user":
             inp = x_in if b.nin > 0 else "nullptr"
             if b.templated:   # a templated source: inp = template[key] (three doubles), like `inp[:3] = t_data[int(datum[2])]` (afb:374-375)
                 fwd.append(f"double xt{i}[3]; {{ const double *tp = c.tpoint(); xt{i}[0] = tp[0]; xt{i}[1] = tp[1]; xt{i}[2] = tp[2]; }}")
                 inp = f"xt{i}"
-            fwd.append(f"double x{i}[{b.nout}]; const double *p{i} = c.user({b.uidx}, {_LINK_CPP[b.link]}, {b.n_params}); user::{b.cpp_name}::fun(p{i}, {inp}, x{i});")
+            fwd.append(f"double x{i}[{b.nout}]; const double *p{i} = c.user{'_m' if b.mapped else ''}({b.uidx}, {_LINK_CPP[b.link]}, {b.n_params}); user::{b.cpp_name}::fun(p{i}, {inp}, x{i});")
         elif b.kind == "projection":
-            fwd.append(f"double Ap[18], Ax[2][3]; pcs::project_generic<JAC>(c.intr(), {x_in}[0], {x_in}[1], {x_in}[2], u, v, Ap, Ax);")
+            fwd.append(f"double Ap[18], Ax[2][3]; pcs::project_generic<JAC>(c.intr{'_m' if b.mapped else ''}(), {x_in}[0], {x_in}[1], {x_in}[2], u, v, Ap, Ax);")
     if B[0].kind == "user":
         fwd.append("u = x0[0]; v = x0[1];")
     # chain rule, first block to source: S{i} = d(u, v) / d(input of block i)
@@ -267,7 +326,7 @@ def emit_source(spec: ChainSpec) -> str:
             rule.append(f"double Jb{i}[{b.nout * (b.n_params + b.nin)}]; user::{b.cpp_name}::jac(p{i}, {inp}, Jb{i});")
             rule.append(f"double S{i}[2][{nin}]; pcs::chain_user<P, {cols[i]}, {b.n_params}, {b.nin}, {b.nout}>({prev}, Jb{i}, J, S{i});")
         elif b.kind == "rigid":
-            rule.append(f"double S{i}[2][3]; pcs::chain_rigid<P, {cols[i]}>({prev}, E{i}, c.slab({b.slab}, {_LINK_CPP[b.link]}), J, S{i});")
+            rule.append(f"double S{i}[2][3]; pcs::chain_rigid<P, {cols[i]}>({prev}, E{i}, c.slab{'_m' if b.mapped else ''}({b.slab}, {_LINK_CPP[b.link]}), J, S{i});")
         elif b.kind == "template_points":
             rule.append(f"pcs::chain_template<P, {cols[i]}>({prev}, E{i}, J);")
         elif b.kind == "free_point":
@@ -275,10 +334,16 @@ def emit_source(spec: ChainSpec) -> str:
         prev = f"S{i}"
     slab_links = [g["link"] for g in spec.groups if g["kind"] == "rigid"]
     link_cases = " ".join(f"g == {i} ? {_LINK_CPP[l]} :" for i, l in enumerate(slab_links))
+    # which groups the code indexes through a table (GenericArgs::intr_map / point_map / slab_map / user_map): bit 0 the intrinsics, bit 1 the
+    # points, bit 8 + g rigid group g, bit 16 + u user block u — the host refuses to launch without the tables the code reads
+    mapped = sum(1 << (8 + i) for i, g in enumerate(g for g in spec.groups if g["kind"] == "rigid") if g["mapped"])
+    mapped |= sum(1 << (16 + b.uidx) for b in spec.user_blocks if b.mapped)
+    mapped |= sum({"projection": 1, "free_point": 2}.get(b.kind, 0) for b in B if b.mapped)
     out += ["struct Chain {",
             f"    static constexpr int P = {P};",
             f"    static constexpr int N_SLABS = {len(slab_links)};   // Rodrigues slabs (one per rigid parameter group) and whose transform each holds",
             f"    __device__ static constexpr int slab_link(const int g) {{ return {link_cases} pcs::LINK_CAM; }}",
+            f"    static constexpr unsigned MAPPED = 0x{mapped:x}u;   // parameter groups indexed through a table entity -> group (shared parameters)",
             "    template <bool JAC, typename Ctx>",
             "    __device__ static __forceinline__ void eval(const Ctx &c, double &u, double &v, double (&J)[2 * P]) {"]
     out += ["        " + ln for ln in fwd]
@@ -452,7 +517,10 @@ def block_param_inds(spec: ChainSpec, lay: dict, det_idx: np.ndarray) -> np.ndar
     cols = []
     for g in spec.group_of_block:     # blocks that share a parameter group repeat its columns (the reference gathers per block)
         grp = spec.groups[g]
-        cols.append(lay["starts"][g] + grp["n_params"] * idx[grp["link"]][:, None] + np.arange(grp["n_params"])[None, :])
+        ent = idx[grp["link"]]
+        if lay["tables"][g] is not None:      # a shared group: the entity's group index
+            ent = lay["tables"][g].astype(np.int64)[ent]
+        cols.append(lay["starts"][g] + grp["n_params"] * ent[:, None] + np.arange(grp["n_params"])[None, :])
     return np.ascontiguousarray(np.concatenate(cols, axis=1), dtype=np.int64)
 
 
@@ -486,9 +554,9 @@ class ChainEngine:
         if dtype not in ("f64", "f32", "mixed"):
             raise ValueError("dtype must be 'f64', 'f32' or 'mixed'")
         self.dtype = dtype
-        self.spec = ChainSpec.from_blocks(function_blocks)
-        self.chain = " + ".join(self.spec.names)
         self.n_cams, self.n_imgs, self.n_keys, self.device = int(n_cams), int(n_imgs), int(n_keys), int(device)
+        self.spec = ChainSpec.from_blocks(function_blocks, counts=(self.n_cams, self.n_imgs, self.n_keys))
+        self.chain = " + ".join(self.spec.names)
         self.P = self.spec.P
         self.lay = self.spec.layout(self.n_cams, self.n_imgs, self.n_keys)
         self.n_params = self.lay["n_params"]
@@ -501,8 +569,15 @@ class ChainEngine:
         check(lib().pcs_genchain_create(byref(self._h), str(path).encode(), self.P, int(self.spec.uses_template), ng, off, cnt, nu, uoff,
                                         self.lay["intr_off"], self.lay["point_off"], self.n_params, self.n_cams, self.n_imgs, self.n_keys,
                                         {"f64": 0, "f32": 1, "mixed": 2}[self.dtype], self.device))
-        # which global column a local column stands for (pcs_genchain_matfree)
         nb = len(self.spec.blocks)
+        if self.spec.has_maps:   # the tables entity -> group index of shared groups, per block; before set_blocks, which then counts GROUPS
+            tabs = [self.lay["tables"][b.group] for b in self.spec.blocks]
+            self._tables = [None if t is None else np.ascontiguousarray(t, dtype=np.int32) for t in tabs]
+            ptrs = (c_void_p * nb)(*[None if t is None else t.ctypes.data for t in self._tables])
+            check(lib().pcs_genchain_set_group_maps(self._h, nb, (c_int32 * nb)(*[b.link for b in self.spec.blocks]), ptrs,
+                                                    (c_int64 * nb)(*[0 if t is None else t.shape[0] for t in self._tables]),
+                                                    (c_int32 * nb)(*[self.lay["group_count"][b.group] for b in self.spec.blocks])))
+        # which global column a local column stands for (pcs_genchain_matfree)
         col0 = np.concatenate([[0], np.cumsum([b.n_params for b in self.spec.blocks])[:-1]]).astype(np.int32)
         check(lib().pcs_genchain_set_blocks(self._h, nb, (c_int32 * nb)(*col0), (c_int32 * nb)(*[b.n_params for b in self.spec.blocks]),
                                             (c_int32 * nb)(*[b.link for b in self.spec.blocks]), (c_int64 * nb)(*[self.lay["starts"][b.group] for b in self.spec.blocks])))
@@ -622,8 +697,9 @@ class ChainEngine:
     DENSE_OPTIONS = ("spd_timeout_us", "timing", "gram_debug", "dense_normal")
 
     def deterministic_supported(self) -> bool:
-        """The ordered sums write every destination from ONE pair of local columns: no two blocks may share a parameter group."""
-        return len(set(self.spec.group_of_block)) == len(self.spec.blocks)
+        """The ordered sums write every destination from ONE pair of local columns and ONE workgroup: no two blocks may share a
+        parameter group, and no group may be indexed through a table (several entities then share a destination)."""
+        return len(set(self.spec.group_of_block)) == len(self.spec.blocks) and not self.spec.has_maps
 
     def dense_lm_supported(self) -> bool:
         """Does the contraction of csrc/ba_blockgram.hpp take this chain?  FP64 block rows of at most 63 columns, n_params <= 65 535."""
@@ -681,6 +757,9 @@ class ChainEngine:
         maps to "timing"; "lazy_done_event" has nothing to switch here."""
         value = int(value)
         if key == "deterministic":
+            if value and self.spec.has_maps:
+                raise NotImplementedError("deterministic mode: parameter groups shared through a mod_function / key_type.SINGLE are not supported in the ordered sums "
+                                          "(several cameras, images or keys write one destination; csrc/ba_blockgram.hpp)")
             if value and not self.deterministic_supported():
                 raise NotImplementedError("deterministic mode: blocks that share a parameter group are not supported in the ordered sums (csrc/ba_blockgram.hpp)")
             check(lib().pcs_genchain_set_option(self._h, b"deterministic", value))

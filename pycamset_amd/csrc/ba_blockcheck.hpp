@@ -19,6 +19,8 @@
 #include "ba_rtc_prelude.hpp"
 #endif
 
+#include "ba_device.hpp"   // what a user body may call in a chain, it may call here: pcs::rot_terms / pcs::rot_element (Rodrigues rotation and its derivative)
+
 namespace pcs {
 
 struct BlockcheckArgs {

@@ -61,6 +61,12 @@ struct BlockGramArgs {
     int32_t P, n_seg, n_blocks;
     int32_t blk_col0[BLOCKROW_MAX_BLOCKS], blk_np[BLOCKROW_MAX_BLOCKS], blk_link[BLOCKROW_MAX_BLOCKS];   // link: 0 camera, 1 image, 2 key
     int64_t blk_start[BLOCKROW_MAX_BLOCKS];
+    // Shared parameter groups (pcs_genchain_set_group_maps): the block's table entity -> group index, NULL = the entity itself.  The
+    // destination of a local column is col_base + col_mul * map[entity]; which PASS sums a pair of columns and which waves of a workgroup
+    // combine before the flush still follow the BASE entity (a mapped camera column is constant over a (camera, image) run, a mapped key
+    // column over a (., key) run): two entities of one group meet in the atomics.  Default mode only — the ordered mode writes every
+    // destination from one workgroup and is refused for such chains.  A mapped group is never the trailing group of the blocked form.
+    const int32_t *blk_map[BLOCKROW_MAX_BLOCKS];
     const int32_t *stop;    // optional LM stop word (ba_schur.hpp PCS_STOP_GUARD)
     int32_t debug;          // measurements only (option "gram_debug"): 1 = no flush, 2 = no contraction
     // ORDERED mode (option "deterministic"): the contraction stores every segment's matrix, raw, to ws[segment][entry] instead of
@@ -134,14 +140,16 @@ __global__ __launch_bounds__(64 * gram_waves(NB)) void blockrow_gram_kernel(cons
     __shared__ int64_t col_base[GRAM_MAX_COLS];
     __shared__ int32_t col_mul[GRAM_MAX_COLS], col_link[GRAM_MAX_COLS];
     __shared__ int32_t seg_id[3][WAVES];   // camera, image, key of the waves' segments (-1: varies / no segment)
+    __shared__ const int32_t *col_map[GRAM_MAX_COLS];   // the column's table entity -> group index (shared parameters), or NULL
     extern __shared__ double gram_lds[];   // WAVES x NE
     if (threadIdx.x < GRAM_MAX_COLS) {
         const int p = threadIdx.x;
         int64_t base = 0;
         int32_t mul = 0, link = -1;
+        const int32_t *map = nullptr;
         for (int b = 0; b < a.n_blocks; ++b)
-            if (p >= a.blk_col0[b] && p < a.blk_col0[b] + a.blk_np[b]) { base = a.blk_start[b] + (p - a.blk_col0[b]); mul = a.blk_np[b]; link = a.blk_link[b]; }
-        col_base[p] = base; col_mul[p] = mul; col_link[p] = link;
+            if (p >= a.blk_col0[b] && p < a.blk_col0[b] + a.blk_np[b]) { base = a.blk_start[b] + (p - a.blk_col0[b]); mul = a.blk_np[b]; link = a.blk_link[b]; map = a.blk_map[b]; }
+        col_base[p] = base; col_mul[p] = mul; col_link[p] = link; col_map[p] = map;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s_id = blockIdx.x * WAVES + wave;
@@ -277,12 +285,14 @@ __global__ __launch_bounds__(64 * gram_waves(NB)) void blockrow_gram_kernel(cons
             unsafeAtomicAdd(a.cost, sum);
             continue;
         }
-        const int64_t gp = col_base[p] + (int64_t)col_mul[p] * ip;
+        const int32_t *mp = col_map[p];
+        const int64_t gp = col_base[p] + (int64_t)col_mul[p] * (mp ? mp[ip] : ip);
         if (c == P) {
             unsafeAtomicAdd(a.g + gp, sum);
             continue;
         }
-        gram_add(a, gp, col_base[c] + (int64_t)col_mul[c] * ic, p == c, sum);
+        const int32_t *mc = col_map[c];
+        gram_add(a, gp, col_base[c] + (int64_t)col_mul[c] * (mc ? mc[ic] : ic), p == c, sum);
     }
 }
 

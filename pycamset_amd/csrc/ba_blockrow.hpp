@@ -5,7 +5,8 @@
 // writes its dense block rows (ba_generic.hpp); what a Levenberg-Marquardt solver needs from them (optimisation_handling.py:88-98
 // hands J to scipy: column norms, J^T f, lsmr mat-vecs) is generic over the chain once J exists: row i's column p belongs to
 // block b(p) and sits at global column  start_b + np_b * index_b(detection) + (p - col0_b)  — the reference's
-// get_block_param_inds (afb:192-233) evaluated on the fly from the detection's (camera, image, key).  One lane per detection,
+// get_block_param_inds (afb:192-233) evaluated on the fly from the detection's (camera, image, key) — through the block's table
+// entity -> group index where its parameters are shared (blk_map: the input gather of J v and the output column of every scatter).  One lane per detection,
 // J read once per product (2 P doubles per detection: 432 B at P = 27), sums through a workgroup-private accumulator of the whole
 // parameter string in LDS (ds_add_f64) while it fits 64 KB, one global f64 atomic per touched entry per workgroup after that; larger
 // strings use global atomics directly.  J never crosses PCIe and, sharded, ranks all-reduce parameter-sized vectors only.
@@ -32,7 +33,14 @@ struct BlockRowArgs {
     int32_t P, n_blocks, lds_acc;
     int32_t blk_col0[BLOCKROW_MAX_BLOCKS], blk_np[BLOCKROW_MAX_BLOCKS], blk_link[BLOCKROW_MAX_BLOCKS];   // link: 0 camera, 1 image, 2 key
     int64_t blk_start[BLOCKROW_MAX_BLOCKS];
+    const int32_t *blk_map[BLOCKROW_MAX_BLOCKS];   // shared parameter groups: the block's table entity -> group index (NULL: the entity itself)
 };
+
+// the index of block b's parameter set for a detection of camera c, image im, key k
+__device__ __forceinline__ int blockrow_index(const int32_t link, const int32_t *map, const int c, const int im, const int k) {
+    const int idx = link == 0 ? c : link == 1 ? im : k;
+    return map ? map[idx] : idx;
+}
 
 template <int OP>
 __global__ __launch_bounds__(256) void blockrow_kernel(const BlockRowArgs a) {
@@ -57,7 +65,7 @@ __global__ __launch_bounds__(256) void blockrow_kernel(const BlockRowArgs a) {
         double wu = 0.0, wv = 0.0;
         if constexpr (OP == BR_JV || OP == BR_JTJV) {
             for (int b = 0; b < a.n_blocks; ++b) {
-                const int idx = a.blk_link[b] == 0 ? c : a.blk_link[b] == 1 ? im : k;
+                const int idx = blockrow_index(a.blk_link[b], a.blk_map[b], c, im, k);
                 const double *vin = a.in + a.blk_start[b] + (int64_t)a.blk_np[b] * idx;
                 for (int q = 0; q < a.blk_np[b]; ++q) {
                     const int p = a.blk_col0[b] + q;
@@ -78,7 +86,7 @@ __global__ __launch_bounds__(256) void blockrow_kernel(const BlockRowArgs a) {
         }
         if constexpr (SCATTER) {
             for (int b = 0; b < a.n_blocks; ++b) {
-                const int idx = a.blk_link[b] == 0 ? c : a.blk_link[b] == 1 ? im : k;
+                const int idx = blockrow_index(a.blk_link[b], a.blk_map[b], c, im, k);
                 const int64_t col = a.blk_start[b] + (int64_t)a.blk_np[b] * idx;
                 for (int q = 0; q < a.blk_np[b]; ++q) {
                     const int p = a.blk_col0[b] + q;

@@ -54,6 +54,13 @@ struct GenericArgs {
     // compaction at the store (pcs_genchain_eval_compact): per detection the kept local columns and the offset of its u row in `jac` (= data)
     const uint64_t *keep;
     const int64_t *row_off;
+    // SHARED parameter groups (param_type's mod_function / key_type.SINGLE; pcs_genchain_set_group_maps): a table entity -> group index per
+    // group that the generated code indexes through one (c.slab_m / intr_m / point_m / user_m; Spec::MAPPED says which), NULL for every other
+    // group.  Which groups go through a table is fixed when the chain is compiled; the tables are run-time data.  group_count and the
+    // slabs of a mapped rigid group count GROUPS, not entities.
+    const int32_t *slab_map[GENERIC_MAX_GROUPS];
+    const int32_t *intr_map, *point_map;
+    const int32_t *user_map[GENERIC_MAX_GROUPS];
 };
 
 // element `slot` of the slab (R | t | dR/dr | pad) of one 6-parameter transform (same element functions as slab_prep_kernel)
@@ -96,7 +103,8 @@ struct LaneSlabs {
         for (int r = 0; r < ROUNDS; ++r) {
             const int e = 64 * r + lane;
             const int g = e < NEL ? e / POSE_STRIDE : 0;   // lanes past the end recompute an element of group 0 (never read)
-            const int idx = Spec::slab_link(g) == LINK_CAM ? c0 : im0;
+            int idx = Spec::slab_link(g) == LINK_CAM ? c0 : im0;
+            if ((Spec::MAPPED >> (8 + g)) & 1u) idx = a.slab_map[g][idx];   // (wave-uniform like c0 and im0)
             el[r] = generic_slab_element(a.prm + a.group_off[g] + 6 * (int64_t)idx, e < NEL ? e - g * POSE_STRIDE : 0);
         }
     }
@@ -254,8 +262,17 @@ struct ChainCtx {
     }
     __device__ __forceinline__ IntrRow intr() const { return IntrRow{a.prm + a.intr_off + 9 * (int64_t)c}; }
     __device__ __forceinline__ const double *point() const { return a.prm + a.point_off + 3 * (int64_t)k; }
-    __device__ __forceinline__ const double *tpoint() const { return a.tmpl + 3 * (int64_t)k; }
+    __device__ __forceinline__ const double *tpoint() const { return a.tmpl + 3 * (int64_t)k; }   // the template is indexed by the key itself, always
     __device__ __forceinline__ const double *user(const int u, const int link, const int np) const { return a.prm + a.user_off[u] + (int64_t)np * index_of(link); }
+    // the same through the group's table (shared parameters)
+    __device__ __forceinline__ IntrRow intr_m() const { return IntrRow{a.prm + a.intr_off + 9 * (int64_t)a.intr_map[c]}; }
+    __device__ __forceinline__ const double *point_m() const { return a.prm + a.point_off + 3 * (int64_t)a.point_map[k]; }
+    __device__ __forceinline__ const double *user_m(const int u, const int link, const int np) const { return a.prm + a.user_off[u] + (int64_t)np * a.user_map[u][index_of(link)]; }
+    __device__ __forceinline__ auto slab_m(const int g, const int link) const {   // UNIFORM: the index is wave-uniform, so is its group
+        const double *p = a.slab[g] + (int64_t)a.slab_map[g][index_of(link)] * POSE_STRIDE;
+        if constexpr (UNIFORM) return ScalarSlab(p);
+        else return p;
+    }
 };
 
 // the same for the one-launch form: the slabs of this detection's (camera, image) pair are held across the wave's lanes
@@ -272,8 +289,13 @@ struct ChainCtxLanes {
     }
     __device__ __forceinline__ IntrRow intr() const { return IntrRow{a.prm + a.intr_off + 9 * (int64_t)c}; }
     __device__ __forceinline__ const double *point() const { return a.prm + a.point_off + 3 * (int64_t)k; }
-    __device__ __forceinline__ const double *tpoint() const { return a.tmpl + 3 * (int64_t)k; }
+    __device__ __forceinline__ const double *tpoint() const { return a.tmpl + 3 * (int64_t)k; }   // the template is indexed by the key itself, always
     __device__ __forceinline__ const double *user(const int u, const int link, const int np) const { return a.prm + a.user_off[u] + (int64_t)np * index_of(link); }
+    // the same through the group's table (shared parameters)
+    __device__ __forceinline__ IntrRow intr_m() const { return IntrRow{a.prm + a.intr_off + 9 * (int64_t)a.intr_map[c]}; }
+    __device__ __forceinline__ const double *point_m() const { return a.prm + a.point_off + 3 * (int64_t)a.point_map[k]; }
+    __device__ __forceinline__ const double *user_m(const int u, const int link, const int np) const { return a.prm + a.user_off[u] + (int64_t)np * a.user_map[u][index_of(link)]; }
+    __device__ __forceinline__ auto slab_m(const int g, const int link) const { return slab(g, link); }   // LaneSlabs::prepare went through the table
 };
 
 // one detection of a tile through the generated chain.  ONE (the one-launch step, no slab-preparation launch ran; the host picks it
@@ -431,6 +453,7 @@ __device__ __forceinline__ void generic_compact_body(const GenericArgs &a) {
 // What chain_compiler.py appends after the ChainSpec struct it emits: the entry points of the code object — every kernel in the
 // two-launch form (behind pcs_genchain_prep) and in the one-launch form (`_one`).
 #define PCS_GENCHAIN_ENTRY_POINTS(Spec)                                                                                              \
+    extern "C" __device__ const unsigned pcs_genchain_mapped[1] = {Spec::MAPPED};                                                     \
     extern "C" __global__ void pcs_genchain_prep(const pcs::GenericArgs a) { pcs::generic_slab_prep_body(a); }                        \
     extern "C" __global__ __launch_bounds__(256) void pcs_genchain_eval_1(const pcs::GenericArgs a) { pcs::generic_eval_body<Spec, 1, double, false>(a); } \
     extern "C" __global__ __launch_bounds__(256) void pcs_genchain_eval_2(const pcs::GenericArgs a) { pcs::generic_eval_body<Spec, 2, double, false>(a); } \

@@ -39,6 +39,19 @@ struct pcs_genchain {
     int n_blocks = 0;
     int32_t blk_col0[BLOCKROW_MAX_BLOCKS] = {}, blk_np[BLOCKROW_MAX_BLOCKS] = {}, blk_link[BLOCKROW_MAX_BLOCKS] = {};
     int64_t blk_start[BLOCKROW_MAX_BLOCKS] = {};
+    // shared parameter groups (pcs_genchain_set_group_maps): per block the table entity -> group index on the device (empty: the entity
+    // itself) and how many groups it addresses; map_* are the same tables by the role the generated kernel reads them in
+    int n_map_blocks = 0;
+    bool any_map = false, evaluated = false;
+    unsigned mapped_mask = 0;   // the code object's pcs_genchain_mapped: which groups its kernels index through a table
+    DevBuf d_blk_map[BLOCKROW_MAX_BLOCKS];
+    int32_t map_link[BLOCKROW_MAX_BLOCKS] = {}, map_groups[BLOCKROW_MAX_BLOCKS] = {};
+    const int32_t *slab_map[GENERIC_MAX_GROUPS] = {}, *intr_map = nullptr, *point_map = nullptr, *user_map[GENERIC_MAX_GROUPS] = {};
+    const int32_t *blk_map(int b) const { return b < n_map_blocks ? static_cast<const int32_t *>(d_blk_map[b].p) : nullptr; }
+    int64_t blk_count(int b) const {   // parameter sets of block b: groups of a shared block, entities otherwise
+        if (blk_map(b)) return map_groups[b];
+        return blk_link[b] == 0 ? n_cams : blk_link[b] == 1 ? n_imgs : n_keys;
+    }
     bool linearized = false;
     DevBuf d_vin, d_vout;   // max(n_params, 2N) + 1 doubles each
     // normal equations (ba_blockgram.hpp): per pass — (camera, image) = the table's order, (camera, key), (image, key) — the detections
@@ -71,6 +84,7 @@ int pcs_genchain_destroy(pcs_genchain *h) {
     h->det.release();
     for (DevBuf *b : {&h->d_param, &h->d_tmpl, &h->d_sink, &h->d_resid, &h->d_jac, &h->d_data, &h->d_keep, &h->d_row_off, &h->d_vin, &h->d_vout, &h->d_gram_ws}) b->release();
     for (DevBuf &b : h->d_slab) b.release();
+    for (DevBuf &b : h->d_blk_map) b.release();
     for (auto &g : h->gram)
         for (int q = 0; q < 4; ++q)
             for (int32_t *b : {g.d_seg[q], g.d_order[q], g.d_grp[q][0], g.d_grp[q][1], g.d_grp[q][2], g.d_gidx[q]})
@@ -125,6 +139,13 @@ int pcs_genchain_create(pcs_genchain **out, const char *code_object_path, int ro
                 function(&h->f_compact_f32[one][m], "pcs_genchain_compact_" + std::to_string(m) + "_f32" + sfx);
             }
         }
+    }
+    if (ok) {   // which parameter groups the code indexes through a table (shared parameters): pcs_genchain_set_group_maps must supply them
+        hipDeviceptr_t d_mask = nullptr;
+        size_t mask_bytes = 0;
+        ok = step("hipModuleGetGlobal(pcs_genchain_mapped)", hipModuleGetGlobal(&d_mask, &mask_bytes, h->module, "pcs_genchain_mapped"));
+        ok = ok && step("the size of pcs_genchain_mapped", mask_bytes == sizeof(unsigned) ? hipSuccess : hipErrorInvalidValue);
+        ok = ok && step("hipMemcpyDtoH(pcs_genchain_mapped)", hipMemcpyDtoH(&h->mapped_mask, d_mask, sizeof(unsigned)));
     }
     ok = ok && step("hipStreamCreateWithFlags", hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     for (auto &ev : h->ev) ok = ok && step("hipEventCreate", hipEventCreate(&ev));
@@ -186,6 +207,13 @@ static int genchain_enqueue(pcs_genchain *h, const double *d_param_str, void *d_
     if (h->det.n <= 0) return fail(PCS_ERR_STATE, "no detections set");
     if (h->uses_template && !h->have_template) return fail(PCS_ERR_STATE, "template points not set");
     if (compact && (h->nnz < 0 || !d_jac)) return fail(PCS_ERR_STATE, "pcs_genchain_set_unfixed has not been called");
+    if (h->any_map && h->n_blocks == 0) return fail(PCS_ERR_STATE, "pcs_genchain_set_group_maps was called: pcs_genchain_set_blocks must follow before the first evaluation");
+    if (h->mapped_mask) {   // the kernels read these tables unconditionally
+        bool have = (!(h->mapped_mask & 1u) || h->intr_map) && (!(h->mapped_mask & 2u) || h->point_map);
+        for (int g = 0; g < GENERIC_MAX_GROUPS; ++g)
+            have = have && (!((h->mapped_mask >> (8 + g)) & 1u) || h->slab_map[g]) && (!((h->mapped_mask >> (16 + g)) & 1u) || h->user_map[g]);
+        if (!have) return fail(PCS_ERR_STATE, "the chain was compiled with shared parameter groups: pcs_genchain_set_group_maps and pcs_genchain_set_blocks must supply their tables first");
+    }
     const int mode = (d_resid ? MODE_RESID : 0) | (d_jac ? MODE_JAC : 0);
     if (!mode) return PCS_OK;
     HIPCHK(hipSetDevice(h->device));
@@ -200,7 +228,10 @@ static int genchain_enqueue(pcs_genchain *h, const double *d_param_str, void *d_
     }
     a.n_groups = h->n_groups;
     a.intr_off = h->intr_off; a.point_off = h->point_off;
-    for (int u = 0; u < h->n_user; ++u) a.user_off[u] = h->user_off[u];
+    for (int u = 0; u < h->n_user; ++u) { a.user_off[u] = h->user_off[u]; a.user_map[u] = h->user_map[u]; }
+    for (int g = 0; g < h->n_groups; ++g) a.slab_map[g] = h->slab_map[g];
+    a.intr_map = h->intr_map; a.point_map = h->point_map;
+    h->evaluated = true;
     a.resid = d_resid; a.jac = d_jac; a.sink = h->d_sink.p;
     a.keep = h->d_keep.as<uint64_t>(); a.row_off = h->d_row_off.as<int64_t>();
     a.n = h->det.n; a.n_tiles = (h->det.n + TILE - 1) / TILE;
@@ -310,22 +341,90 @@ int pcs_genchain_eval_compact(pcs_genchain *h, const double *param_str, void *re
     return PCS_OK;
 }
 
+// Shared parameter groups (param_type's mod_function / key_type.SINGLE; the reference declares them, afb:42-61, and leaves them a TODO,
+// afb:803): per block a table entity -> group index, NULL for a block indexed by the entity itself.  Called once, after create and BEFORE
+// pcs_genchain_set_blocks (which then counts a shared block's parameter sets in groups) and before the first evaluation; nothing is
+// launched.  table_len[b] must be the entity count of link[b] given at create, every value lie in [0, n_mapped[b]).
+int pcs_genchain_set_group_maps(pcs_genchain *h, int n_blocks, const int32_t *link, const int32_t *const *tables, const int64_t *table_len, const int32_t *n_mapped) {
+    if (!h || n_blocks < 1 || n_blocks > BLOCKROW_MAX_BLOCKS || !link || !tables || !table_len || !n_mapped) return fail(PCS_ERR_ARG, "pcs_genchain_set_group_maps: bad arguments");
+    if (h->evaluated) return fail(PCS_ERR_ARG, "pcs_genchain_set_group_maps: the chain has been evaluated; the tables are set once, before the first evaluation");
+    if (h->n_blocks != 0 || h->any_map) return fail(PCS_ERR_ARG, "pcs_genchain_set_group_maps: call it once, before pcs_genchain_set_blocks");
+    bool any = false;
+    for (int b = 0; b < n_blocks; ++b) {
+        if (!tables[b]) continue;
+        any = true;
+        const int64_t count = link[b] == 0 ? h->n_cams : link[b] == 1 ? h->n_imgs : link[b] == 2 ? h->n_keys : -1;
+        if (count < 0) return fail(PCS_ERR_ARG, "pcs_genchain_set_group_maps: block %d has link %d (0 camera, 1 image, 2 key)", b, link[b]);
+        if (table_len[b] != count) return fail(PCS_ERR_ARG, "pcs_genchain_set_group_maps: the table of block %d has %lld entries, the chain has %lld entities of its link", b, (long long)table_len[b], (long long)count);
+        if (n_mapped[b] < 1) return fail(PCS_ERR_RANGE, "pcs_genchain_set_group_maps: block %d maps to %d groups", b, n_mapped[b]);
+        for (int64_t i = 0; i < count; ++i)
+            if (tables[b][i] < 0 || tables[b][i] >= n_mapped[b])
+                return fail(PCS_ERR_RANGE, "pcs_genchain_set_group_maps: table of block %d, entity %lld -> group %d outside [0, %d)", b, (long long)i, tables[b][i], n_mapped[b]);
+    }
+    if (!any) return PCS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    for (int b = 0; b < n_blocks; ++b) {
+        if (!tables[b]) continue;
+        hipError_t e = h->d_blk_map[b].alloc(table_len[b], sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemcpy(h->d_blk_map[b].p, tables[b], sizeof(int32_t) * table_len[b], hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            for (DevBuf &m : h->d_blk_map) m.release();
+            return fail(PCS_ERR_HIP, "pcs_genchain_set_group_maps: uploading the table of block %d failed: %s", b, hipGetErrorString(e));
+        }
+        h->map_link[b] = link[b]; h->map_groups[b] = n_mapped[b];
+    }
+    h->n_map_blocks = n_blocks; h->any_map = true;
+    return PCS_OK;
+}
+
 // Which global column every local column of a block row stands for (the reference's get_block_param_inds, afb:192-233, as a rule):
 // block b covers local columns [col0_b, col0_b + np_b), its parameters of entity e (camera / image / key by link_b) start at
 // start_b + np_b e.  Needed by pcs_genchain_matfree only.
 int pcs_genchain_set_blocks(pcs_genchain *h, int n_blocks, const int32_t *col0, const int32_t *n_params, const int32_t *link, const int64_t *start) {
     if (!h || n_blocks < 1 || n_blocks > BLOCKROW_MAX_BLOCKS || !col0 || !n_params || !link || !start) return fail(PCS_ERR_ARG, "pcs_genchain_set_blocks: bad arguments");
+    if (h->any_map && n_blocks != h->n_map_blocks)
+        return fail(PCS_ERR_ARG, "pcs_genchain_set_blocks: %d blocks, pcs_genchain_set_group_maps described %d", n_blocks, h->n_map_blocks);
     int64_t cols = 0;
     for (int b = 0; b < n_blocks; ++b) {
-        const int64_t count = link[b] == 0 ? h->n_cams : link[b] == 1 ? h->n_imgs : link[b] == 2 ? h->n_keys : -1;
+        int64_t count = link[b] == 0 ? h->n_cams : link[b] == 1 ? h->n_imgs : link[b] == 2 ? h->n_keys : -1;
+        if (h->blk_map(b)) {   // a shared block: its group holds one parameter set per GROUP
+            if (link[b] != h->map_link[b]) return fail(PCS_ERR_ARG, "pcs_genchain_set_blocks: block %d has link %d, its table was given for link %d", b, link[b], h->map_link[b]);
+            count = h->map_groups[b];
+        }
         if (count < 0 || col0[b] != cols || n_params[b] < 1 || start[b] < 0 || start[b] + n_params[b] * count > h->n_params)
             return fail(PCS_ERR_RANGE, "pcs_genchain_set_blocks: block %d does not fit the parameter string", b);
         cols += n_params[b];
     }
     if (cols != h->P) return fail(PCS_ERR_RANGE, "pcs_genchain_set_blocks: the blocks cover %lld columns, the row has %d", (long long)cols, h->P);
+    for (int b = 0; b < n_blocks; ++b)   // blocks of ONE group (the same first column) go through the same table, or through none
+        for (int c = b + 1; c < n_blocks; ++c)
+            if (start[b] == start[c] && (h->blk_map(b) != nullptr) != (h->blk_map(c) != nullptr))
+                return fail(PCS_ERR_ARG, "pcs_genchain_set_blocks: blocks %d and %d share a parameter group, but only one of them has a table (pcs_genchain_set_group_maps)", b, c);
+            else if (start[b] == start[c] && h->blk_map(b) && h->map_groups[b] != h->map_groups[c])
+                return fail(PCS_ERR_ARG, "pcs_genchain_set_blocks: blocks %d and %d share a parameter group, their tables address %d and %d groups", b, c, h->map_groups[b], h->map_groups[c]);
     h->n_blocks = n_blocks;
     h->gram[0].built = h->gram[1].built = false;
     for (int b = 0; b < n_blocks; ++b) { h->blk_col0[b] = col0[b]; h->blk_np[b] = n_params[b]; h->blk_link[b] = link[b]; h->blk_start[b] = start[b]; }
+    // the tables by the role the generated kernel reads them in: a block's group is the rigid group, the intrinsics, the points or the
+    // user block whose first column it starts at (a role the chain does not have is never read)
+    for (int g = 0; g < GENERIC_MAX_GROUPS; ++g) h->slab_map[g] = h->user_map[g] = nullptr;
+    h->intr_map = h->point_map = nullptr;
+    for (int b = 0; b < n_blocks; ++b) {
+        const int32_t *map = h->blk_map(b);
+        if (!map) continue;
+        for (int g = 0; g < h->n_groups; ++g)
+            if (h->group_off[g] == start[b]) {
+                if (h->group_count[g] != h->map_groups[b]) {
+                    h->n_blocks = 0;
+                    return fail(PCS_ERR_RANGE, "pcs_genchain_set_blocks: block %d maps to %d groups, its rigid group was created with %d", b, h->map_groups[b], h->group_count[g]);
+                }
+                h->slab_map[g] = map;
+            }
+        for (int u = 0; u < h->n_user; ++u)
+            if (h->user_off[u] == start[b]) h->user_map[u] = map;
+        if (h->intr_off == start[b]) h->intr_map = map;
+        if (h->point_off == start[b]) h->point_map = map;
+    }
     // Schur structure: the group that ENDS the parameter string, when it is one rigid transform per image (6) or one point per key (3) —
     // the entity kinds the step kernels of ba_schur.hpp factor in registers — and something leads it.  A detection has one image and one
     // key, so two such entities never share a row: C is block diagonal.  Every other chain keeps the dense form.
@@ -337,8 +436,11 @@ int pcs_genchain_set_blocks(pcs_genchain *h, int n_blocks, const int32_t *col0, 
     const bool kind = (n_params[last] == 6 && link[last] == 1) || (n_params[last] == 3 && link[last] == 2);
     bool alone = true;   // no other group overlaps it
     for (int b = 0; b < n_blocks; ++b)
-        if (start[b] != start[last] && start[b] + (int64_t)n_params[b] * (link[b] == 0 ? h->n_cams : link[b] == 1 ? h->n_imgs : h->n_keys) > start[last]) alone = false;
-    if (kind && alone && start[last] > 0 && start[last] + n_params[last] * count == h->n_params) {
+        if (start[b] != start[last] && start[b] + (int64_t)n_params[b] * h->blk_count(b) > start[last]) alone = false;
+    bool shared = false;   // a shared group is never the trailing group: its entities would not own their block of C
+    for (int b = 0; b < n_blocks; ++b)
+        if (start[b] == start[last] && h->blk_map(b)) shared = true;
+    if (kind && alone && !shared && start[last] > 0 && start[last] + n_params[last] * count == h->n_params) {
         h->trail_off = start[last]; h->tb = n_params[last]; h->n_ent = count;
     }
     return PCS_OK;
@@ -375,7 +477,7 @@ int pcs_genchain_matfree(pcs_genchain *h, int op, const double *in, double *out,
     a.J = static_cast<const double *>(h->d_jac.p); a.resid = static_cast<const double *>(h->d_resid.p);
     a.in = h->d_vin.as<double>(); a.out = h->d_vout.as<double>(); a.cost = h->d_vout.as<double>() + n_out;
     a.n = h->det.n; a.n_params = h->n_params; a.P = h->P; a.n_blocks = h->n_blocks;
-    for (int b = 0; b < h->n_blocks; ++b) { a.blk_col0[b] = h->blk_col0[b]; a.blk_np[b] = h->blk_np[b]; a.blk_link[b] = h->blk_link[b]; a.blk_start[b] = h->blk_start[b]; }
+    for (int b = 0; b < h->n_blocks; ++b) { a.blk_col0[b] = h->blk_col0[b]; a.blk_np[b] = h->blk_np[b]; a.blk_link[b] = h->blk_link[b]; a.blk_start[b] = h->blk_start[b]; a.blk_map[b] = h->blk_map(b); }
     a.lds_acc = op != BR_JV && h->n_params * (int64_t)sizeof(double) <= 65536;
     const size_t lds = a.lds_acc ? sizeof(double) * (size_t)h->n_params : 0;
     const int64_t wgs = std::min<int64_t>((h->det.n + 255) / 256, (int64_t)h->n_cu * (a.lds_acc ? 2 : 8));
@@ -426,6 +528,7 @@ int pcs_genchain_set_option(pcs_genchain *h, const char *key, int64_t value) {
     } else if (!strcmp(key, "dense_normal")) {
         h->dense_normal = value != 0;
     } else if (!strcmp(key, "deterministic")) {
+        if (value && h->any_map) return fail(PCS_ERR_ARG, "deterministic mode: shared parameter groups (pcs_genchain_set_group_maps) are not supported in the ordered sums");
         if (value) {   // every destination must belong to ONE pair of local columns (blockrow_gram_reduce_kernel writes it with a plain add)
             for (int b = 0; b < h->n_blocks; ++b)
                 for (int c = b + 1; c < h->n_blocks; ++c)
@@ -560,7 +663,7 @@ static int genchain_enqueue_normal(pcs_genchain *h, const double *d_param_str, d
     a.A = d_packed; a.B = a.A + L.a_len(); a.C = a.B + L.b_len(); a.g = d_packed + n_h; a.cost = a.g + np;
     a.n_params = np; a.n_lead = L.n_lead; a.n_trail = L.n_trail; a.trail_off = L.trail_off; a.tb = L.tb;
     a.P = h->P; a.n_blocks = h->n_blocks;
-    for (int b = 0; b < h->n_blocks; ++b) { a.blk_col0[b] = h->blk_col0[b]; a.blk_np[b] = h->blk_np[b]; a.blk_link[b] = h->blk_link[b]; a.blk_start[b] = h->blk_start[b]; }
+    for (int b = 0; b < h->n_blocks; ++b) { a.blk_col0[b] = h->blk_col0[b]; a.blk_np[b] = h->blk_np[b]; a.blk_link[b] = h->blk_link[b]; a.blk_start[b] = h->blk_start[b]; a.blk_map[b] = h->blk_map(b); }
     a.stop = d_stop; a.debug = h->gram_debug;
     const int nb = (h->P + 1 + 15) / 16;
     auto launch = [&](auto kernel, int nbc) -> hipError_t {

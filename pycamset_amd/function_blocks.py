@@ -39,11 +39,62 @@ class key_type(IntEnum):  # afb:42-46
 
 
 class param_type:  # afb:50-70
+    """A parameter group: ``n_params`` parameters per camera / image / key (``link_type``), or ONE set for every detection
+    (``key_type.SINGLE``).  ``mod_function`` SHARES parameters between entities — the reference's "functional lookup: think about
+    the rotating calibration" (afb:48-61), which its ``make_param_struct`` leaves as a TODO (afb:803): it maps the entity index
+    to a group index, and the group then holds ``n_params x (largest group index + 1)`` columns of the parameter string.  Either
+    a callable ``int -> int`` (plain Python, or a numba-jitted function: its ``.py_func`` is called) or an integer array used as
+    the table directly.  The table is evaluated on the host, once per engine (``group_table``); no code is translated.
+
+        p = projection(); p.params = param_type(key_type.SINGLE, 9)                        # one lens for every camera
+        t = template_points(); t.params = param_type(key_type.PER_IMG, 6, lambda i: i % 12)  # a turntable with 12 positions
+    """
+
     def __init__(self, link_type: key_type, n_params: int, mod_function=None) -> None:
         self.link_type = link_type
         self.n_params = n_params
         self.sparse_param = False
         self.mod_function = mod_function
+        if mod_function is not None:
+            if int(link_type) == int(key_type.SINGLE):
+                raise ValueError("param_type: key_type.SINGLE has one parameter set for every detection; a mod_function has nothing to map")
+            if not callable(getattr(mod_function, "py_func", mod_function)):
+                t = np.asarray(mod_function)
+                if t.ndim != 1 or t.dtype.kind not in "iu":
+                    raise ValueError("param_type: mod_function must be a callable int -> int or a one-dimensional integer array")
+
+    def group_table(self, count: int, block: str = "?") -> np.ndarray | None:
+        """The int32 table entity -> group for ``count`` entities, or None when the group is indexed by the entity itself (no
+        ``mod_function``, or one that maps every entity to itself).  ``SINGLE`` is the table of zeros.  ``block`` names the block
+        in the refusals: negative or non-integer values, a table shorter than ``count``."""
+        count = int(count)
+        if int(self.link_type) == int(key_type.SINGLE):
+            if self.mod_function is not None:
+                raise ValueError(f"block {block}: key_type.SINGLE together with a mod_function")
+            return np.zeros(count, dtype=np.int32)
+        if self.mod_function is None:
+            return None
+        fun = getattr(self.mod_function, "py_func", self.mod_function)
+        if callable(fun):
+            vals = [fun(i) for i in range(count)]
+        else:
+            vals = np.asarray(self.mod_function)
+            if vals.ndim != 1:
+                raise ValueError(f"block {block}: the mod_function table must be one-dimensional")
+            if vals.shape[0] < count:
+                raise ValueError(f"block {block}: the mod_function table has {vals.shape[0]} entries, the chain indexes {count} entities")
+            vals = vals[:count]
+        arr = np.asarray(vals)
+        if arr.shape != (count,):
+            raise ValueError(f"block {block}: mod_function must return one integer per entity")
+        if arr.dtype.kind == "b" or arr.dtype.kind not in "iuf" or (arr.dtype.kind == "f" and not np.all(arr == np.floor(arr))):
+            raise ValueError(f"block {block}: mod_function returned non-integer group indices")
+        if count and (arr.min() < 0 or arr.max() > np.iinfo(np.int32).max):
+            raise ValueError(f"block {block}: mod_function returned a negative group index" if arr.min() < 0 else f"block {block}: group index beyond int32")
+        table = arr.astype(np.int32)
+        if np.array_equal(table, np.arange(count, dtype=np.int32)):
+            return None          # every entity its own group: the un-mapped chain in every respect
+        return table
 
 
 class abstract_function_block:  # afb:689-748
@@ -105,6 +156,30 @@ class device_function_block(abstract_function_block):
     same rule S <- S . d out / d inp.  A first block must have ``num_out = 2`` (the pixel), neighbours must agree
     (``num_inp`` of a block = ``num_out`` of the next), the last block is a source.  As in the reference, blocks that share
     one ``param_type`` OBJECT share one parameter group (afb:160-163).
+
+    SHARED parameters: ``param_type(link, n, mod_function)`` maps the entity index to a group index (a callable or an integer
+    table), ``key_type.SINGLE`` is one set for everything; ``params`` then points at the parameters of the detection's GROUP.
+    A target made of rigid boards — the reference's Ccube has six faces — gets one small transform per FACE between the rigid
+    template and ``free_point`` (36 unknowns instead of 3 per corner) as a templated source whose key-linked group is shared
+    per face (examples/shared_parameters.py runs it on ``synthetic.ccube_points``, face of key = k // points_per_face)::
+
+        class face_transform(device_function_block):        # out = R(params[0:3]) inp + params[3:6], one set per face
+            template = True
+            num_inp, num_out, array_memory = 0, 3, 0
+            params = param_type(key_type.PER_KEY, 6, lambda k: k // 81)
+            device_fun = "const pcs::RotTerms t = pcs::rot_terms(params[0], params[1], params[2]);" \
+                         " for (int r = 0; r < 3; ++r) out[r] = pcs::rot_element(t, 3 * r) * inp[0] + pcs::rot_element(t, 3 * r + 1) * inp[1]" \
+                         " + pcs::rot_element(t, 3 * r + 2) * inp[2] + params[3 + r];"
+            device_jac = "const pcs::RotTerms t = pcs::rot_terms(params[0], params[1], params[2]);" \
+                         " for (int r = 0; r < 3; ++r) for (int a = 0; a < 3; ++a) {" \
+                         "   out[6 * r + a] = pcs::rot_element(t, 9 + 9 * a + 3 * r) * inp[0] + pcs::rot_element(t, 10 + 9 * a + 3 * r) * inp[1]" \
+                         "     + pcs::rot_element(t, 11 + 9 * a + 3 * r) * inp[2];" \
+                         "   out[6 * r + 3 + a] = r == a ? 1.0 : 0.0; }"
+
+        op_fun = projection() + extrinsic3D() + rigidTform3d() + face_transform()  # fix one face: the gauge against the pose
+
+    (``pcs::rot_terms`` / ``pcs::rot_element``: the library's Rodrigues rotation, element q < 9 of R or 9 + 9 a + 3 row + col of
+    dR / dr_a, csrc/ba_device.hpp.)
 
     A TEMPLATED source (round 5) — ``template = True`` on the LAST block, ``num_inp = 0`` — receives the detection's template point
     as ``inp`` (three doubles), exactly like the reference's ``inp[:3] = t_data[int(datum[2])]`` (afb:138, afb:374-375, afb:582;
@@ -200,7 +275,8 @@ class optimisation_function:  # afb:111-685
         `a + b + c` builds intermediate partial chains (afb:735-748), so validity is checked on use, not on construction
         (an invalid composition raises NotImplementedError from the chain compiler)."""
         kinds = tuple(type(b) for b in self.function_blocks)
-        if kinds in _CHAINS:
+        shares = any(getattr(b.params, "mod_function", None) is not None or int(b.params.link_type) == int(key_type.SINGLE) for b in self.function_blocks)
+        if kinds in _CHAINS and not shares:   # shared parameters (param_type's mod_function, SINGLE) exist in generated kernels only
             return _CHAINS[kinds]
         from .chain_compiler import ChainSpec
 

@@ -6,6 +6,10 @@ default (products of csrc/ba_blockrow.hpp, the host between every two) and — o
 source of tests/helpers.py (a board that bends, one flex model per image) on the rigs of BASELINE's configs.
     python tools/genchain_lm.py --config 1 2 3 [--chain division] [--dense] [--trace] [--python-bodies]
 
+``--chain single | faces | template``: chains with SHARED parameter groups (param_type's mod_function / key_type.SINGLE) — one lens for
+every camera; one rigid transform per face of the cube (tests/shared_blocks.py) — and, next to them, the un-shared generated kernel of
+`projection + extrinsic3D + template_points` (an identity table is dropped, the chain still takes the generated path).
+
 ``--python-bodies`` runs the same user blocks written with Python bodies (tests/python_blocks.py, translated to device code by
 pycamset_amd/block_translate.py) instead of their hand-written device-string twins (tests/helpers.py): the A/B of the translator."""
 import argparse
@@ -22,6 +26,7 @@ import torch
 
 import helpers as H
 import python_blocks as PB
+import shared_blocks as SB
 from pycamset_amd import function_blocks as fb
 from pycamset_amd import handlers, synthetic
 from pycamset_amd.device_solver import lm_solve
@@ -49,6 +54,32 @@ def problem(number: int, which: str, python_bodies: bool = False):
                  rig.poses_true + 1e-3 * rng.standard_normal(rig.poses_true.shape), flex.copy()]
         start[3][:, 4] = 0.0
         unfixed = [None, fix_ext, None, free_flex]
+    elif which in ("single", "template"):   # one lens for every camera / the same chain un-shared, both through the generated kernel
+        def chain():
+            lens = fb.projection()
+            lens.params = fb.param_type(fb.key_type.SINGLE, 9) if which == "single" else fb.param_type(fb.key_type.PER_CAM, 9, lambda c: c)
+            return fb.optimisation_function([lens, fb.extrinsic3D(), fb.template_points()])
+
+        intr = rig.intr_true[:1] if which == "single" else rig.intr_true
+        truth = [intr, rig.extr_true, rig.poses_true]
+        start = [intr * (1 + 1e-3 * rng.standard_normal(intr.shape)), rig.extr_true + 1e-3 * rng.standard_normal(rig.extr_true.shape),
+                 rig.poses_true + 1e-3 * rng.standard_normal(rig.poses_true.shape)]
+        unfixed = [None, fix_ext, None]
+    elif which == "faces":   # the target as rigid faces: one transform per face (key -> face) in front of the rigid template
+        per_face = rig.n_keys // 6
+
+        def chain():
+            return fb.optimisation_function([fb.projection(), fb.extrinsic3D(), fb.rigidTform3d(), SB.face_transform(fb, lambda k: k // per_face)])
+
+        faces = np.concatenate([rng.normal(0, 0.01, (6, 3)), rng.normal(0, 5e-4, (6, 3))], axis=1)
+        faces[0] = 0.0
+        truth = [rig.intr_true, rig.extr_true, rig.poses_true, faces]
+        start = [rig.intr_true * (1 + 1e-3 * rng.standard_normal(rig.intr_true.shape)), rig.extr_true + 1e-3 * rng.standard_normal(rig.extr_true.shape),
+                 rig.poses_true + 1e-3 * rng.standard_normal(rig.poses_true.shape), faces + 1e-3 * rng.standard_normal(faces.shape)]
+        start[3][0] = 0.0
+        free_face = np.ones((6, 6), dtype=bool)
+        free_face[0] = False
+        unfixed = [None, fix_ext, None, free_face]
     elif which == "divfree":   # the lens model AND free points (key-linked trailing entities); the poses hold the frame
         def chain():
             return ub["division_projection"]() + fb.extrinsic3D() + fb.rigidTform3d() + fb.free_point()
@@ -86,7 +117,7 @@ def main():
     ap.add_argument("--max-iter", type=int, default=40)
     ap.add_argument("--phases", action="store_true", help="time the build with parts of the contraction switched off")
     ap.add_argument("--no-cg", action="store_true")
-    ap.add_argument("--chain", choices=("flex", "division", "divfree"), default="flex")
+    ap.add_argument("--chain", choices=("flex", "division", "divfree", "single", "template", "faces"), default="flex")
     ap.add_argument("--two-launch", action="store_true", help="slab preparation as a launch of its own in front of the evaluation")
     ap.add_argument("--deterministic", action="store_true", help="the ordered contraction and step (the same bits on every run)")
     ap.add_argument("--dense", action="store_true", help="the dense form of the normal equations also where the chain has the blocked one")
