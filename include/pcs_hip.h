@@ -502,6 +502,23 @@ enum { PCS_LOSS_LINEAR = 0, PCS_LOSS_HUBER = 1, PCS_LOSS_SOFT_L1 = 2, PCS_LOSS_C
 int pcs_set_loss(pcs_engine *h, int kind, double f_scale);
 /* The current setting (kind and f_scale may be NULL); PCS_ERR_ARG for a NULL handle. */
 int pcs_get_loss(pcs_engine *h, int *kind, double *f_scale);
+/* Noise weights of the engine's normal equations (since pcs_version() 112): inv_sigma[i] = 1 / sigma_i, the reciprocal pixel noise of detection i of the current
+ * table, in table order (isotropic: one value for the u and the v of a detection).  A weight whitens in front of the loss of pcs_set_loss:
+ * f -> f / sigma before rho, row of J -> (s / sigma) J, so a build minimises  sum rho(((f / sigma) / f_scale)^2) f_scale^2  — scipy's
+ * least_squares(loss=, f_scale=) applied to the whitened residual f / sigma and Jacobian row J / sigma — and returns H = J~^T J~,
+ * g = J~^T r~ and the cost word sum rho0, all of the whitened system (linear loss: sum (f / sigma)^2).
+ *   inv_sigma = NULL clears the weights (n is then ignored).  Otherwise n must equal pcs_n_detections and every value must be finite
+ *   and > 0: PCS_ERR_ARG if not, and for a NULL handle; a refused call leaves the previous weights in force.
+ *   The weights belong to the detection table: pcs_set_detections* clears them.  The values are copied.
+ * Affects what pcs_set_loss affects: pcs_normal_equations*, pcs_normal_blocks_device, pcs_lm_trial* and, through those, the
+ * device-steered and sharded LM loops, in both contraction orders (option "deterministic" keeps its same-bits guarantee).
+ * Does NOT affect pcs_eval* and the compact paths (the drop-in closures keep returning the raw residuals and J), pcs_matfree (its
+ * products use the raw J), the group statistics (pcs_residual_stats*: raw pixels), nor generated chains (pcs_genchain_*).
+ * Without weights the builds take the path the loss alone selects: the same bits as an engine on which pcs_set_weights was never called. */
+int pcs_set_weights(pcs_engine *h, const double *inv_sigma, int64_t n);
+/* The current weights: *n = their number (0 = none set); up to `capacity` of them are copied to inv_sigma.  inv_sigma or n may be NULL
+ * (not both): pcs_get_weights(h, NULL, 0, &n) is the "are weights set" query.  PCS_ERR_ARG for a NULL handle or a negative capacity. */
+int pcs_get_weights(pcs_engine *h, double *inv_sigma, int64_t capacity, int64_t *n);
 /*
  * Batched n-view triangulation.
  * Replaces: nb_triangulate_full (compiled_helpers.py:609-643) = per point nb_undistort (ch:409-431) +

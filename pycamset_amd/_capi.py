@@ -200,6 +200,8 @@ SYMBOLS = {
     "pcs_set_option": (c_int, [_P, c_char_p, c_int64]),
     "pcs_set_loss": (c_int, [_P, c_int, c_double]),
     "pcs_get_loss": (c_int, [_P, POINTER(c_int), POINTER(c_double)]),
+    "pcs_set_weights": (c_int, [_P, POINTER(c_double), c_int64]),
+    "pcs_get_weights": (c_int, [_P, POINTER(c_double), c_int64, POINTER(c_int64)]),
     "pcs_device_buffers": (c_int, [_P, POINTER(_P), POINTER(_P)]),
 }
 

@@ -93,6 +93,9 @@ __device__ __forceinline__ double2v load_uv(const DetTable &t, const int64_t i) 
 // (2 rho2 f^2 = 2 z rho''(z): f_scale drops out of s).  FP64 throughout.  A NaN residual gives NaN s, rf and rho0, as in numpy (the
 // clamp is written as `x < EPS ? EPS : x`, which keeps a NaN).  `kind` is wave-uniform wherever the kernels call this.
 constexpr int LOSS_LINEAR = 0, LOSS_HUBER = 1, LOSS_SOFT_L1 = 2, LOSS_CAUCHY = 3, LOSS_ARCTAN = 4;
+// Kernel-side only (never a pcs_set_loss kind): the linear loss on the robust path — what a build with noise weights (pcs_set_weights) and no
+// loss launches with.  robust_rho's final branch takes it: s = 1, rho0 = f_scale^2 z, rf = f.
+constexpr int LOSS_LINEAR_WHITENED = 5;
 #ifndef __HIPCC_RTC__   // generated chains take no robust loss (yet): their hiprtc builds need none of this
 // rho(z) of the two losses with a transcendental rho (cauchy: log1p, arctan: atan) — rho0 only, the weights are rational.  Out of line:
 // inlined into the normal-equations kernel next to the other losses' code, the two of them raised its register allocation for EVERY

@@ -43,6 +43,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "ba_device.hpp"
 #include "ba_matfree.hpp"  // wave_sum
 
@@ -94,6 +96,15 @@ struct NormalArgs {
     int32_t debug;  // profiling switches (results are wrong while set): 2 no flush atomics, 8 no MFMA phase, 16 no evaluation,
                     // 32 run boundaries ignored, 64 no LDS image writes, 128 flush = clear only; host side: 256 / 512 / 1024 skip the shared /
                     // (cam, key) / (image, key) pass
+    // Noise weights (pcs_set_weights): 1 / sigma per detection in the order this pass walks its table (the pass's sorted copy, or the
+    // table's own array read through `order`), or NULL = none: the kernels then take the path `loss` alone selects.  A weight whitens in
+    // front of the loss — f -> f / sigma before rho, row scale s -> s / sigma — so a weighted build takes the robust path whatever the
+    // loss: without one the host launches with loss = LOSS_LINEAR_WHITENED (s = 1, rho0 = f^2; inv_f_scale = f_scale_sq = 1), and its
+    // cost comes from sum rho0.  "Robust" therefore stays `loss != LOSS_LINEAR` in the kernels, and this pointer is read on the robust
+    // path only: tested outside it, it stayed in scalar registers across the tile loop of the plain path, whose 106 are all taken (the
+    // template chain's shared pass then spilled eight more of them to lanes and re-read kernel arguments in the loop: 88.7 -> 92.2 us
+    // on rig-32, profiles/r19).
+    const double *inv_sigma;
 };
 
 constexpr int PASS_SHARED = 0, PASS_CAMKEY = 1, PASS_IMGKEY = 2;
@@ -191,6 +202,8 @@ __host__ __device__ __forceinline__ int entry_descriptor(const int m, const int 
 }
 
 // Robust loss (ba_normal_mfma_kernel): scale one lane's two rows of the LDS image by their weights and replace its residual by r~;
+// `inv_sigma_tab[idx]`: the detection's noise weight 1 / sigma (NormalArgs::inv_sigma; NULL = none, 1.0: the products below are then exact),
+// applied to the residual in front of the loss and to the row scale behind it.  Loaded in here: still a leaf.
 // returns the lane's (rho0_u, rho0_v) — for cauchy / arctan (z_u, z_v) instead: their rho is log1p / atan, which the kernel calls itself
 // (robust_rho_transcendental), so that this function stays a LEAF.  Out of line because of registers: the runtime switch must not
 // raise the kernel's allocation for the linear loss.  Inlined, the loss code ran next to live state of the tile loop (179 -> 188 VGPRs,
@@ -199,10 +212,11 @@ __host__ __device__ __forceinline__ int entry_descriptor(const int m, const int 
 // registers: +1 to +7 VGPRs against the parent, the same waves per SIMD and zero scratch in every instantiation (profiles/r06).
 template <int CHAIN, int PASS, int KS>
 __device__ __attribute__((noinline)) double2v robust_scale_row(const int kind, const double r0, const double r1, const double inv_f_scale,
-                                                               const double f_scale_sq, unsigned char *dst) {
+                                                               const double f_scale_sq, const double *inv_sigma_tab, const int idx, unsigned char *dst) {
+    const double inv_sigma = inv_sigma_tab ? inv_sigma_tab[idx] : 1.0;
     double q0, q1, f0, f1;
-    const double s0 = robust_rho<true>(kind, r0, inv_f_scale, f_scale_sq, q0, f0);
-    const double s1 = robust_rho<true>(kind, r1, inv_f_scale, f_scale_sq, q1, f1);
+    const double s0 = robust_rho<true>(kind, r0 * inv_sigma, inv_f_scale, f_scale_sq, q0, f0) * inv_sigma;
+    const double s1 = robust_rho<true>(kind, r1 * inv_sigma, inv_f_scale, f_scale_sq, q1, f1) * inv_sigma;
 #pragma unroll
     for (int s = 0; s < normal_slots(CHAIN, PASS); ++s) {
         double *q = reinterpret_cast<double *>(dst + s * KS);
@@ -270,7 +284,7 @@ __global__ __launch_bounds__(64, 2) void ba_normal_mfma_kernel(const NormalArgs 
     for (int m = 0; m < NM; ++m)
 #pragma unroll
         for (int r = 0; r < 4; ++r) ent[m][r] = entry_descriptor<CHAIN, PASS>(m, lane, r, tg);
-    const bool robust = a.loss != LOSS_LINEAR;   // uniform over the launch
+    const bool robust = a.loss != LOSS_LINEAR;   // uniform over the launch: a loss is set, or noise weights are (NormalArgs::inv_sigma)
     if (PASS == PASS_SHARED && robust) {   // the (r, r) entry sums r~^2: not the cost, which comes from rho_acc below
 #pragma unroll
         for (int m = 0; m < NM; ++m)
@@ -465,7 +479,21 @@ __global__ __launch_bounds__(64, 2) void ba_normal_mfma_kernel(const NormalArgs 
                     // Robust loss: the lane's two rows are scaled by their weights and its residual replaced by r~, in the image, after J
                     // has gone there (scaling J in registers kept all of it live across the loss code).  Every pass re-evaluates the
                     // detection: the same weights.
-                    const double2v q = robust_scale_row<CHAIN, PASS, KS>(a.loss, r0, r1, a.inv_f_scale, a.f_scale_sq, dst);
+                    // Noise weights: the leaf call loads the lane's 1 / sigma itself, from the table and the detection's index handed to it
+                    // HERE, where J has left the registers.  Requested beside load_uv the weight is live through the evaluation: +5 VGPRs,
+                    // and three 64-row instantiations run one wave per SIMD fewer (free / shared 124 -> 129, self / (cam, key) 166 -> 171,
+                    // self / (image, key) 168 -> 173); requested in front of the image writes the last of those still goes 168 -> 169.  The
+                    // price of this place is one exposed load per tile, on the weighted path only.
+                    // The table's pointer is read from the kernel arguments (`a` is the only one: offset 0 of the segment) at an offset the
+                    // compiler cannot see through: read as a.inv_sigma it is fetched with the other arguments at the kernel's entry and
+                    // kept across the tile loop in scalar registers, all 106 of which are taken — the (image, key) instantiation then needs
+                    // 66 spill lanes instead of 64, a second spill register, 169 VGPRs and loses its third wave (profiles/r19).
+                    int w_off = (int)offsetof(NormalArgs, inv_sigma);
+                    asm volatile("" : "+s"(w_off));
+                    using KernArg = const __attribute__((address_space(4))) char *;
+                    const double *inv_sigma = *reinterpret_cast<const double *const __attribute__((address_space(4))) *>((KernArg)__builtin_amdgcn_kernarg_segment_ptr() + w_off);
+                    const int det = (int)tile * 64 + lane;   // a valid lane: inside the table (at most 2^31 rows: the host checks)
+                    const double2v q = robust_scale_row<CHAIN, PASS, KS>(a.loss, r0, r1, a.inv_f_scale, a.f_scale_sq, inv_sigma, a.order ? a.order[det] : det, dst);
                     if (PASS == PASS_SHARED) {
                         if (a.loss == LOSS_CAUCHY || a.loss == LOSS_ARCTAN)
                             rho_acc += a.f_scale_sq * robust_rho_transcendental(a.loss, q.x) + a.f_scale_sq * robust_rho_transcendental(a.loss, q.y);
@@ -648,6 +676,7 @@ __global__ __launch_bounds__(64, 3) void ba_normal_imgkey_kernel(const NormalArg
     const int64_t tile1 = min(tile0 + (int64_t)a.tiles_per_wave, a.n_tiles);
     // robust loss: the row weights of the detection come from its own residual, so the measurement is read as well (requested with the
     // index words; the pass's sorted table carries it when a loss is set) and the projection eval_detection forms anyway is finished
+    // (noise weights whiten in front of the loss: they take the same path, with this tile's weight loaded beside the index words)
     const bool robust = a.loss != LOSS_LINEAR;   // uniform over the launch
     DetWords nxt_w{};
     double2v nxt_m{};
@@ -666,6 +695,8 @@ __global__ __launch_bounds__(64, 3) void ba_normal_imgkey_kernel(const NormalArg
             nxt_w = load_words(a.tab, icn);
             if (robust) nxt_m = load_uv(a.tab, icn);
         }
+        double isg = 1.0;
+        if (robust && a.inv_sigma) isg = a.inv_sigma[det_index(tile)];
         asm volatile("" ::: "memory");
         // S = A_x R_e = the pose-translation columns of the detection's block (everything else eval_detection forms is dead code here)
         T Su[3], Sv[3];
@@ -687,8 +718,8 @@ __global__ __launch_bounds__(64, 3) void ba_normal_imgkey_kernel(const NormalArg
             for (int j = 0; j < 3; ++j) { Su[j] = J[18 + j]; Sv[j] = J[P + 18 + j]; }
             if (robust) {
                 double q0, q1, f0, f1;
-                const double s0 = robust_rho(a.loss, u - m.x, a.inv_f_scale, a.f_scale_sq, q0, f0);
-                const double s1 = robust_rho(a.loss, v - m.y, a.inv_f_scale, a.f_scale_sq, q1, f1);
+                const double s0 = robust_rho(a.loss, (u - m.x) * isg, a.inv_f_scale, a.f_scale_sq, q0, f0) * isg;
+                const double s1 = robust_rho(a.loss, (v - m.y) * isg, a.inv_f_scale, a.f_scale_sq, q1, f1) * isg;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) { Su[j] *= s0; Sv[j] *= s1; }
             }

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void normal_reduce_final_kernel(const NormalAr
         __shared__ double red[256];
         double s = 0.0;
         // linear loss: the groups' (r, r) entries; robust loss: sum rho0, one word per wave of the shared pass (the (r, r) entries sum r~^2)
-        const bool robust = a.loss != LOSS_LINEAR;
+        const bool robust = a.loss != LOSS_LINEAR;   // (noise weights without a loss arrive as LOSS_LINEAR_WHITENED: the robust path too)
         const double *src = robust ? a.wave_cost : ra.G + 255;
         const int64_t stride = robust ? 1 : RED_G;
         const int cnt = robust ? ra.n_waves : ra.n_grp;

@@ -77,6 +77,7 @@ struct DetStore {
     DetColumns h;                   // host copies of the index columns (visiting orders, CSR structure, segment tables)
     DevBuf packed, cam, img, key;   // the packed word, or the three arrays
     DevBuf uv;                      // float or double measurements
+    DevBuf w;                       // noise weights, 1 / sigma per detection in table order (double), or empty = none (pcs_set_weights)
     int key_bits = 0, img_bits = 0;
     bool uv_f32 = false;
     int64_t n = 0;                  // 0 = "no detections set"
@@ -92,7 +93,7 @@ struct DetStore {
     }
 
     void release() {
-        for (DevBuf *b : {&packed, &cam, &img, &key, &uv}) b->release();
+        for (DevBuf *b : {&packed, &cam, &img, &key, &uv, &w}) b->release();
         h = DetColumns{};
         n = 0;
     }
@@ -126,6 +127,20 @@ struct DetStore {
             HIPCHK(hipMemcpy(uv.p, uv_host, sizeof(double) * 2 * count, hipMemcpyHostToDevice));
         }
         n = count;
+        return PCS_OK;
+    }
+
+    // The table's noise weights: n checked values (the caller has validated them and waited for everything that reads the old ones), or
+    // NULL = none.  They belong to the table: upload() and release() drop them.  A failed allocation or copy leaves "no weights".
+    int set_weights(const double *inv_sigma) {
+        w.release();
+        if (!inv_sigma || n == 0) return PCS_OK;
+        if (const int rc = w.grow(n, sizeof(double))) return rc;
+        const hipError_t e = hipMemcpy(w.p, inv_sigma, sizeof(double) * n, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            w.release();
+            return fail(PCS_ERR_HIP, "uploading the noise weights failed: %s", hipGetErrorString(e));
+        }
         return PCS_OK;
     }
 };

@@ -97,7 +97,7 @@ struct pcs_engine {
     DevBuf d_order_ck, d_order_ik;   // (cam, key) / (image, key) orders for the point passes
     // the detection table copied out in the visiting orders (index words; measurements except for the (image, key) pass): the
     // passes then stream their inputs instead of gathering 4 + 16 scattered bytes per detection through the order
-    void *d_sorted[3][5] = {};   // per pass (shared — only for a scattered table —, (cam, key), (image, key)): packed, cam, img, key, uv
+    void *d_sorted[3][6] = {};   // per pass (shared — only for a scattered table —, (cam, key), (image, key)): packed, cam, img, key, uv, noise weights
     int sort_tables = 1;         // option: 0 = walk the original table through the visiting order (A/B)
     bool point_orders_tried = false;
     int normal_rows = 64;        // detections per LDS image of the normal-equations kernel (64 or 32)
@@ -244,6 +244,14 @@ static void free_sorted_tables(pcs_engine *h) {
             if (b) (void)hipFree(b);
             b = nullptr;
         }
+}
+
+// the passes' sorted copies of the noise weights (pcs_set_weights replaces the weights, not the table); the caller has waited
+static void free_sorted_weights(pcs_engine *h) {
+    for (auto &t : h->d_sorted) {
+        if (t[5]) (void)hipFree(t[5]);
+        t[5] = nullptr;
+    }
 }
 
 // everything a new detection table replaces (a smaller table gives its memory back); the caller has waited for the work that reads it
@@ -511,6 +519,34 @@ int pcs_get_loss(pcs_engine *h, int *kind, double *f_scale) {
     return PCS_OK;
 }
 
+int pcs_set_weights(pcs_engine *h, const double *inv_sigma, int64_t n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_set_weights: bad arguments");
+    if (inv_sigma) {   // everything is checked before anything changes: a refused call leaves the previous weights in force
+        if (n != h->det.n) return fail(PCS_ERR_ARG, "pcs_set_weights: %lld weights for a table of %lld detections", (long long)n, (long long)h->det.n);
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(inv_sigma[i]) || !(inv_sigma[i] > 0.0))
+                return fail(PCS_ERR_ARG, "pcs_set_weights: weight %lld = %g must be finite and > 0", (long long)i, inv_sigma[i]);
+    }
+    if (!inv_sigma && !h->det.w.p) return PCS_OK;   // nothing set, nothing to clear: no device call
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(wait_done_host(h));   // a build that reads the old weights (or their sorted copies) may still run
+    HIPCHK(hipStreamSynchronize(h->stream));
+    free_sorted_weights(h);
+    return h->det.set_weights(inv_sigma);
+}
+
+int pcs_get_weights(pcs_engine *h, double *inv_sigma, int64_t capacity, int64_t *n) {
+    if (!h || capacity < 0 || (!inv_sigma && !n)) return fail(PCS_ERR_ARG, "pcs_get_weights: bad arguments");
+    const int64_t have = h->det.w.p ? h->det.n : 0;
+    if (n) *n = have;
+    const int64_t m = std::min(have, capacity);
+    if (inv_sigma && m > 0) {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipMemcpy(inv_sigma, h->det.w.p, sizeof(double) * m, hipMemcpyDeviceToHost));
+    }
+    return PCS_OK;
+}
+
 }  // extern "C"
 
 // ---- launch plumbing ---------------------------------------------------------------------------
@@ -770,6 +806,20 @@ static int ensure_imgkey_uv(pcs_engine *h, hipStream_t s) {
     return PCS_OK;
 }
 
+// Noise weights (pcs_set_weights) in the visiting order of `pass`, beside the pass's sorted index words and measurements: gathered at the first
+// weighted build after they were set, on the build's stream like ensure_imgkey_uv's measurements, and kept until the weights or the table change.
+static int ensure_sorted_weights(pcs_engine *h, int pass, const int32_t *order, hipStream_t s) {
+    void **t = h->d_sorted[pass];
+    if (t[5] || !h->det.w.p || !order || h->det.n <= 0) return PCS_OK;
+    const hipError_t e = gather_rows<uint64_t>(order, h->det.w.p, &t[5], h->det.n, s);
+    if (e != hipSuccess) {
+        if (t[5]) (void)hipFree(t[5]);
+        t[5] = nullptr;
+        return fail(PCS_ERR_HIP, "noise weights: gathering them into the visiting order of pass %d failed: %s", pass, hipGetErrorString(e));
+    }
+    return PCS_OK;
+}
+
 // ---- deterministic mode: the static tables of the ordered second pass (csrc/ba_reduce.hpp) ---------------------------------------------
 // For MFMA pass `pass` (0 shared, 1 (cam, key)) walked with `tpw` tiles per wave: segments = maximal stretches of detections inside one
 // run and one wave; logical runs = the segments of one key pair (one stretch in a sorted table; several when a pair re-appears);
@@ -965,6 +1015,8 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
     a.n_params = h->n_params;
     a.debug = h->normal_debug;
     a.loss = h->loss; a.inv_f_scale = 1.0 / h->f_scale; a.f_scale_sq = h->f_scale * h->f_scale;
+    const bool weighted = h->det.w.p != nullptr;   // noise weights: the robust path, with the linear kind when no loss is set (f_scale plays no part)
+    if (weighted && h->loss == LOSS_LINEAR) a.loss = LOSS_LINEAR_WHITENED, a.inv_f_scale = a.f_scale_sq = 1.0;
     a.stop = t.stop;
     a.sel = t.sel; a.alt = t.alt_out;
     // every wave walks a contiguous range of tiles, so its register accumulators survive across tiles.  One-wave
@@ -991,16 +1043,23 @@ static int enqueue_normal(pcs_engine *h, const double *d_prm, double *d_H, doubl
         a.order = pass == PASS_SHARED ? h->d_order.as<int32_t>() : pass == PASS_CAMKEY ? h->d_order_ck.as<int32_t>() : h->d_order_ik.as<int32_t>();
         if (pass != PASS_SHARED && !a.order) return fail(PCS_ERR_STATE, "normal equations: key-sorted visiting order missing");
         a.tab = h->det.table();
+        a.inv_sigma = h->det.w.as<const double>();   // table order, read through a.order like the table itself
         if (a.order && h->sort_tables) {   // the pass's own copy of the table, already in visiting order
-            if (pass == PASS_IMGKEY && h->loss) {   // a robust loss weighs the (image, key) pass's rows by their residuals: it needs the measurements too
+            if (pass == PASS_IMGKEY && (h->loss || weighted)) {   // a robust loss (noise weights) weighs the (image, key) pass's rows by their residuals: it needs the measurements too
                 const int rc = ensure_imgkey_uv(h, s);
                 if (rc) return rc;
             }
             void *const *t = h->d_sorted[pass];
-            if ((t[0] || t[1]) && (t[4] || pass == PASS_IMGKEY)) {   // index words AND measurements, or neither
+            const bool have_table = (t[0] || t[1]) && (t[4] || pass == PASS_IMGKEY);   // index words AND measurements, or neither
+            if (have_table && weighted) {
+                const int rc = ensure_sorted_weights(h, pass, a.order, s);
+                if (rc) return rc;
+            }
+            if (have_table) {
                 a.tab.packed = static_cast<const uint32_t *>(t[0]);
                 a.tab.cam = static_cast<const int32_t *>(t[1]); a.tab.img = static_cast<const int32_t *>(t[2]); a.tab.key = static_cast<const int32_t *>(t[3]);
                 if (t[4]) a.tab.uv = t[4];
+                if (weighted) a.inv_sigma = static_cast<const double *>(t[5]);   // ... and the weights in the same order
                 a.order = nullptr;
             }
         }

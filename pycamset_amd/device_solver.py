@@ -35,7 +35,7 @@ import time
 import numpy as np
 
 from ._capi import LOSS_IDS
-from .engine import Engine
+from .engine import Engine, expand_sigma
 
 
 class JacobianOperator:
@@ -704,9 +704,31 @@ class _CholeskyStep:
         return delta.cpu().numpy(), 1, pred
 
 
-def _blocked_solver(eng, mask, reduce_fn, loss, f_scale) -> BlockedNormalEquations:
-    """The engine's cached solver state for this mask, collective, layout and loss (one state per engine: a miss drops the previous one)."""
-    key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())), loss, f_scale)
+def _n_cams_of(op_fun, dd) -> int:
+    """Cameras of the layout ``op_fun._engine_for(dd)`` creates: what a per-camera ``sigma`` is measured against, known before any device work."""
+    seen = int(dd[:, 0].max()) + 1 if dd.shape[0] else 0
+    counts = getattr(op_fun, "counts", None)
+    return seen if counts is None else int(counts[0]) if dd.shape[0] == 0 else max(int(counts[0]), seen)
+
+
+@contextlib.contextmanager
+def _engine_settings(eng, loss, f_scale, inv_sigma):
+    """The engine's loss and noise weights for one solve; both are restored afterwards (a failed solve included)."""
+    saved_loss, saved_w = eng.loss(), eng.weights()
+    eng.set_loss(loss, f_scale)
+    try:
+        eng.set_weights(inv_sigma=inv_sigma)
+        yield
+    finally:
+        eng.set_loss(*saved_loss)
+        eng.set_weights(inv_sigma=saved_w)
+
+
+def _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma=None) -> BlockedNormalEquations:
+    """The engine's cached solver state for this mask, collective, layout, loss and noise weights (one state per engine: a miss drops the
+    previous one)."""
+    key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())), loss, f_scale,
+           None if inv_sigma is None else hash(inv_sigma.tobytes()))
     cache = eng.__dict__.setdefault("_blocked_solvers", {})
     ne = cache.get(key)
     if ne is None:
@@ -719,7 +741,7 @@ def _blocked_solver(eng, mask, reduce_fn, loss, f_scale) -> BlockedNormalEquatio
 
 def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float = 1e-8, gtol: float = 1e-8,
              cg_tol: float = 1e-3, cg_max_iter: int = 200, lam0: float | None = None, lam_grow0: float | None = None, reduce_fn=None, verbose: int = 0,
-             operator=None, linear_solver: str = "auto", loss: str = "linear", f_scale: float = 1.0) -> DeviceLMResult:
+             operator=None, linear_solver: str = "auto", loss: str = "linear", f_scale: float = 1.0, sigma=None) -> DeviceLMResult:
     """Levenberg-Marquardt (Marquardt scaling D = diag(J^T J)) for a pycamset_amd handler.  The damped
     normal equations are solved by Jacobi-PCG on matrix-free J^T J products (``linear_solver='pcg'``) or
     by a Cholesky factorisation of the block-reduced J^T J (``'cholesky'``).  Every quantity that depends
@@ -740,7 +762,14 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
     ``loss`` / ``f_scale``: scipy ``least_squares``'s robust losses ('linear', 'huber', 'soft_l1', 'cauchy', 'arctan'), applied to each
     scalar residual with scipy's linearisation (include/pcs_hip.h pcs_set_loss): the result's ``cost`` is scipy's ``0.5 * sum rho0`` and
     ``grad`` is J^T (rho1 f).  The engine's loss is set for the solve and restored afterwards.  Hand-fused chains with the blocked step
-    only: a robust loss with ``linear_solver='pcg'``, with a caller's ``operator`` or with a generated chain raises NotImplementedError."""
+    only: a robust loss with ``linear_solver='pcg'``, with a caller's ``operator`` or with a generated chain raises NotImplementedError.
+
+    ``sigma``: the detections' pixel noise — ``None``, an (N,) array per detection of ``handler._flat_detections()``, a (C,) array per
+    camera, or ``{"camera": arr}`` (``engine.expand_sigma``; a bare array is refused when N == C).  Each detection's residual and
+    Jacobian rows are whitened by 1 / sigma in front of the loss: the solve minimises ``sum rho(((f / sigma) / f_scale)^2) f_scale^2``,
+    scipy's ``least_squares(loss=, f_scale=)`` on the whitened closures; ``cost`` and ``grad`` are those of the whitened system.  A
+    sharded solve gives every rank the sigmas of its own detections (``sharding.shard_sigma``).  The engine's weights are set for the
+    solve and restored afterwards; the same combinations as for a robust loss raise NotImplementedError."""
     if loss not in LOSS_IDS:
         raise ValueError(f"unknown loss {loss!r}: expected one of {sorted(LOSS_IDS)}")
     f_scale = float(f_scale)
@@ -754,19 +783,31 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
                                   "a robust loss needs the blocked normal equations (linear_solver='cholesky' or 'auto')")
     if robust and operator is not None:
         raise NotImplementedError(f"loss={loss!r} with a caller-supplied operator: the operator's products know nothing of the loss")
+    weighted = sigma is not None
+    if weighted and linear_solver == "pcg":
+        raise NotImplementedError("sigma: the matrix-free products of linear_solver='pcg' use the raw Jacobian; "
+                                  "noise weights need the blocked normal equations (linear_solver='cholesky' or 'auto')")
+    if weighted and operator is not None:
+        raise NotImplementedError("sigma with a caller-supplied operator: the operator's products know nothing of the weights")
     op_fun = handler.op_fun
     lam0_exact, lam0_pcg = (LAM0_EXACT, 1e-3) if lam0 is None else (float(lam0), float(lam0))
     grow0 = LAM_GROW0 if lam_grow0 is None else float(lam_grow0)
     if operator is None:
         dd = handler._flat_detections()
+        inv_sigma = 1.0 / expand_sigma(sigma, dd[:, 0], _n_cams_of(op_fun, dd)) if weighted else None   # checked before any device work
         eng = op_fun._engine_for(dd)
         op_fun._bind_template(eng, handler._template_arg())
         if robust and not isinstance(eng, Engine):
             raise NotImplementedError(f"loss={loss!r}: generated chains (ChainProblem) build their normal equations without a robust loss")
+        if weighted and not isinstance(eng, Engine):
+            raise NotImplementedError("sigma: generated chains (ChainProblem) build their normal equations without noise weights")
         if linear_solver == "auto":   # blocked J^T J while its regions fit comfortably; beyond that matrix-free CG
             linear_solver = "cholesky" if blocked_fits(eng) else "pcg"
         if robust and linear_solver == "pcg":
             raise NotImplementedError(f"loss={loss!r}: this system is too large for the blocked normal equations (linear_solver='auto' chose "
+                                      "'pcg', whose matrix-free products use the raw Jacobian)")
+        if weighted and linear_solver == "pcg":
+            raise NotImplementedError("sigma: this system is too large for the blocked normal equations (linear_solver='auto' chose "
                                       "'pcg', whose matrix-free products use the raw Jacobian)")
         if linear_solver == "cholesky":
             # the solver's device workspace (two packed states, V, S, a stream) lives with the engine: a second solve on the same
@@ -776,17 +817,15 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
             # (... and the loss: nothing in the state depends on it — the engine's loss is set per solve below — but a state is never
             # carried from one loss to another.  The cache holds ONE state: a miss drops the previous one, so a sweep over f_scale
             # re-allocates per value instead of accumulating workspaces)
-            ne = _blocked_solver(eng, mask, reduce_fn, loss, f_scale)
+            # (... and the noise weights, in the same way: the engine's weights are set per solve below, and a state is never carried
+            # from one set of weights to another, or from a weighted solve to an unweighted one)
+            ne = _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma)
             ne.spd_algorithm = "auto"
             ps0 = op_fun.build_param_list(*handler.get_bundle_adjustment_inputs(np.array(x0, dtype=np.float64)))
             if not isinstance(eng, Engine):   # generated chains: linear only (checked above)
                 return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
-            saved_loss = eng.loss()
-            eng.set_loss(loss, f_scale)
-            try:
+            with _engine_settings(eng, loss, f_scale, inv_sigma):
                 return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
-            finally:
-                eng.set_loss(*saved_loss)
         operator = JacobianOperator(eng, handler._jac_mask(), reduce_fn=reduce_fn)
     elif linear_solver == "auto":
         linear_solver = "cholesky" if hasattr(operator, "build") else "pcg"
@@ -915,12 +954,16 @@ def _covariance_plan(ne: BlockedNormalEquations, layout):
     return plan, trail
 
 
-def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: float = 1e-10, reduce_fn=None) -> ParameterCovariance:
+def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: float = 1e-10, reduce_fn=None, sigma=None) -> ParameterCovariance:
     """Marginal covariance blocks and standard errors of the parameters at ``x`` (the free vector, scipy's ``result.x`` order), from
     the blocked normal equations on the device: H = J'J with the linear loss and no damping, fixed parameters
     as identity rows and columns; sigma^2 = sum r^2 / (2N - n_free), or 1 with ``absolute_sigma`` (scipy curve_fit's meaning);
     the leading blocks are sigma^2 S^-1 (S = A - V V' = L L', column blocks of L^-1), the trailing ones
     sigma^2 L_e^-T (I + Z_e' Z_e) L_e^-1 with Z = L^-1 V formed in place of V.  Only the blocks come back to the host.
+
+    ``sigma``: the detections' pixel noise, as ``lm_solve(sigma=)`` takes it.  H then comes from the weighted build, H = J~'J~ with the
+    rows of J and the residuals divided by sigma; sigma^2 = sum (f / sigma)^2 / (2N - n_free), the variance of unit weight, and ``cost``
+    is half that sum; ``absolute_sigma=True`` — the sigmas ARE the noise — gives inv(H) as it stands.  Hand-fused chains only.
 
     Raises np.linalg.LinAlgError when H is singular or nearly so (a non-positive pivot, a trailing block that is not positive
     definite, or min L_ii^2 / H_ii below ``rcond``): a free gauge or an unobserved parameter.  ValueError for a wrong ``len(x)``
@@ -936,6 +979,7 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
     if x.shape[0] != n_free:
         raise ValueError(f"x has {x.shape[0]} entries, the handler has {n_free} free parameters")
     dd = handler._flat_detections()
+    inv_sigma = None if sigma is None else 1.0 / expand_sigma(sigma, dd[:, 0], _n_cams_of(handler.op_fun, dd))
     dof = 2 * int(dd.shape[0]) - n_free
     if dof <= 0:
         raise ValueError(f"no degrees of freedom left: 2N = {2 * int(dd.shape[0])} residuals for {n_free} free parameters")
@@ -949,7 +993,9 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
     op_fun._bind_template(eng, handler._template_arg())
     if not blocked_fits(eng):
         raise NotImplementedError("this system is too large for the blocked normal equations (device_solver.blocked_fits)")
-    ne = _blocked_solver(eng, mask, None, "linear", 1.0)
+    if inv_sigma is not None and not isinstance(eng, Engine):
+        raise NotImplementedError("sigma: generated chains (ChainProblem) build their normal equations without noise weights")
+    ne = _blocked_solver(eng, mask, None, "linear", 1.0, inv_sigma)
     ne.stream.synchronize()   # a speculative trial of the last solve may still be draining on this state
     torch = ne.torch
     from .engine import cov_block_gram, cov_trsm, dense_spd_solve, schur_syrk
@@ -959,12 +1005,11 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
         ne._cov_plan = (plan_key,) + _covariance_plan(ne, layout)
     _, plan, trail_desc = ne._cov_plan
     robust = isinstance(eng, Engine)
-    saved_loss = eng.loss() if robust else None
     nl, nt, dev = ne.n_lead, ne.n_trail, eng.device
     try:
-        if robust:
-            eng.set_loss("linear", 1.0)
-        with torch.cuda.device(ne.dev), torch.cuda.stream(ne.stream):
+        # hand-fused chains: the linear loss and these weights (none: the raw build) for the build below, the engine's own restored afterwards
+        settings = _engine_settings(eng, "linear", 1.0, inv_sigma) if robust else contextlib.nullcontext()
+        with settings, torch.cuda.device(ne.dev), torch.cuda.stream(ne.stream):
             stream = ne.stream.cuda_stream
             ps = torch.from_numpy(np.ascontiguousarray(op_fun.build_param_list(*slabs), dtype=np.float64)).to(ne.dev)
             ne.build(ps, 0)
@@ -1029,8 +1074,6 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
     finally:
         ne.status.zero_()
         ne.stream.synchronize()
-        if robust:
-            eng.set_loss(*saved_loss)
     sumsq = float(host[-1])
     at = 0
     chunks = []

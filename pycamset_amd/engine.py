@@ -24,6 +24,39 @@ def _f64c(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def expand_sigma(sigma, cam, n_cams: int):
+    """Per-detection pixel noise from what ``Engine.set_weights`` / ``lm_solve(sigma=)`` / ``parameter_covariance(sigma=)`` accept:
+    ``None`` (-> None); an ``(N,)`` array, one sigma per detection in table order; a ``(C,)`` array, one per camera, expanded through the
+    table's camera column ``cam``; or ``{"camera": arr}`` / ``{"detection": arr}``, which say which of the two is meant — required
+    when N == C, where a bare array is refused as ambiguous.  Every value must be finite and > 0.  -> float64 (N,)."""
+    if sigma is None:
+        return None
+    cam = np.asarray(cam).astype(np.int64).ravel()
+    n, kind = cam.shape[0], None
+    if isinstance(sigma, dict):
+        if len(sigma) != 1 or next(iter(sigma)) not in ("camera", "detection"):
+            raise ValueError("sigma as a dict must be {'camera': array} or {'detection': array}")
+        kind, sigma = next(iter(sigma.items()))
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim != 1:
+        raise ValueError(f"sigma must be one-dimensional: ({n},) per detection or ({n_cams},) per camera, got shape {s.shape}")
+    if kind is None:
+        if n == n_cams and s.shape[0] == n:
+            raise ValueError(f"sigma of length {n} is ambiguous: the table has {n} detections and {n_cams} cameras; "
+                             "pass {'camera': sigma} or {'detection': sigma}")
+        kind = "detection" if s.shape[0] == n else "camera" if s.shape[0] == n_cams else None
+    want = n if kind == "detection" else n_cams
+    if kind is None or s.shape[0] != want:
+        raise ValueError(f"sigma has {s.shape[0]} entries: expected {n} (one per detection) or {n_cams} (one per camera)")
+    if not np.all(np.isfinite(s) & (s > 0.0)):
+        raise ValueError("every sigma must be finite and > 0")
+    if kind == "camera":
+        if n and (cam.min() < 0 or cam.max() >= n_cams):
+            raise ValueError("the table's camera column refers to cameras outside the per-camera sigma")
+        s = s[cam]
+    return np.ascontiguousarray(s, dtype=np.float64)
+
+
 class _PinnedBlock:
     """Owner of one page-locked host allocation; NumPy views keep it alive through ``base``."""
 
@@ -138,6 +171,7 @@ class Engine:
         check(lib().pcs_set_detections_table(self._h, _dp(det5), det5.shape[0]))
         self.n = det5.shape[0]
         self.nnz = None
+        self._cam = det5[:, 0].astype(np.int32)   # what set_weights expands a per-camera sigma through; a new table has no weights
 
     def set_detections(self, cam, img, key, uv):
         cam = np.ascontiguousarray(cam, dtype=np.int32)
@@ -151,6 +185,7 @@ class Engine:
         check(lib().pcs_set_detections(self._h, cam.ctypes.data_as(i32), img.ctypes.data_as(i32), key.ctypes.data_as(i32), _dp(uv), n))
         self.n = n
         self.nnz = None
+        self._cam = cam.copy()
 
     def set_template(self, points: np.ndarray):
         points = _f64c(points).reshape(-1, 3)
@@ -176,6 +211,32 @@ class Engine:
         k, fs = ctypes.c_int(0), c_double(0.0)
         check(lib().pcs_get_loss(self._h, byref(k), byref(fs)))
         return {v: n for n, v in _capi.LOSS_IDS.items()}[k.value], fs.value
+
+    def set_weights(self, sigma=None, *, inv_sigma=None):
+        """Pixel noise of the detections for every normal-equation build of this engine (the builds ``set_loss`` affects): ``sigma`` as
+        ``expand_sigma`` takes it — (N,) per detection, (C,) per camera, or ``{"camera": arr}`` — whitens each detection's residual and
+        Jacobian rows by 1 / sigma in front of the loss (include/pcs_hip.h pcs_set_weights).  ``None`` clears the weights; so does a new
+        detection table.  ``inv_sigma``: the (N,) reciprocals themselves, as the C ABI takes them.  ``eval*``, the matrix-free products
+        and the group statistics keep the raw pixels."""
+        if sigma is not None and inv_sigma is not None:
+            raise ValueError("give sigma or inv_sigma, not both")
+        if sigma is not None:
+            inv_sigma = 1.0 / expand_sigma(sigma, self.__dict__.get("_cam", np.zeros(0, np.int32)), self.n_cams)
+        if inv_sigma is None:
+            check(lib().pcs_set_weights(self._h, None, 0))
+            return
+        w = _f64c(inv_sigma).ravel()
+        check(lib().pcs_set_weights(self._h, _dp(w), w.shape[0]))
+
+    def weights(self):
+        """The current 1 / sigma per detection (float64 (N,)), or None when no weights are set."""
+        n = c_int64(0)
+        check(lib().pcs_get_weights(self._h, None, 0, byref(n)))
+        if n.value == 0:
+            return None
+        w = np.empty(n.value)
+        check(lib().pcs_get_weights(self._h, _dp(w), n.value, None))
+        return w
 
     def option(self, key: str, default: int) -> int:
         """The value last given to ``set_option(key, ...)`` through this object, else ``default`` (the library's own default)."""

@@ -29,6 +29,23 @@ def padded_shard(det: np.ndarray, rank: int, world: int) -> np.ndarray:
     return np.ascontiguousarray(det[idx])
 
 
+def shard_sigma(sigma, n_total: int, rank: int, world: int):
+    """Rank ``rank``'s part of a pixel-noise argument (``lm_solve(sigma=)``) for a table split into the UNPADDED ranges
+    ``det[rank * per : (rank + 1) * per]`` that sums over shards use: the same slice of a per-detection ``(n_total,)`` array (possibly
+    empty for the last ranks), as ``{"detection": slice}`` so that a short shard is never mistaken for a per-camera array; ``None`` and a
+    per-camera argument (``{"camera": arr}``, or an array of another length, which the rank's solve expands through its own camera
+    column) go to every rank unchanged."""
+    if sigma is None or (isinstance(sigma, dict) and "detection" not in sigma):
+        return sigma
+    s = np.asarray(sigma["detection"] if isinstance(sigma, dict) else sigma, dtype=np.float64)
+    if s.ndim != 1 or s.shape[0] != n_total:
+        if isinstance(sigma, dict):
+            raise ValueError(f"sigma has {s.shape[0] if s.ndim == 1 else s.shape} entries, the table {n_total} detections")
+        return sigma
+    per = shard_rows(n_total, world)
+    return {"detection": np.ascontiguousarray(s[rank * per: (rank + 1) * per])}
+
+
 class ShardedEvaluator:
     """Evaluate one rank's shard and (optionally) all-gather the blocks.
 

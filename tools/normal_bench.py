@@ -2,7 +2,9 @@
 """Time the block-reduced normal-equations kernel (H = J^T J, g, cost) and the dense solve that follows it.
 
 --loss=huber,cauchy,...  A/B of robust losses (Engine.set_loss) against the linear loss instead: the losses alternate with
-'linear' in rounds of ten builds each on the same engine, default geometry; prints the median kernel time of every round."""
+'linear' in rounds of ten builds each on the same engine, default geometry; prints the median kernel time of every round.
+--weights  (with --loss) every round also times each of them, 'linear' included, with noise weights set (Engine.set_weights, 1 / sigma
+log-uniform over [0.25, 4]): the entries marked '+w'."""
 import sys, time
 from pathlib import Path
 import numpy as np
@@ -35,9 +37,15 @@ for cfg, chain, shuffle in configs:
     loss_arg = [a for a in sys.argv[1:] if a.startswith("--loss=")]
     if loss_arg:
         losses = [x for x in loss_arg[0].split("=", 1)[1].split(",") if x]
+        entries = ["linear"] + losses
+        if "--weights" in sys.argv:
+            entries += [x + "+w" for x in entries]
+            inv_sigma = np.exp(np.random.default_rng(1).uniform(np.log(0.25), np.log(4.0), det.shape[0]))
         for rnd in range(3):
-            for loss in ["linear"] + losses:
-                e.set_loss(loss, 1.0)
+            for loss in entries:
+                e.set_loss(loss.split("+")[0], 1.0)
+                if "--weights" in sys.argv:
+                    e.set_weights(inv_sigma=inv_sigma if loss.endswith("+w") else None)
                 for _ in range(2):
                     e.normal_equations_device(ps, Hd.data_ptr(), gd.data_ptr(), cd.data_ptr())
                 e.synchronize()
