@@ -604,6 +604,25 @@ int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, 
                    int32_t *d_info, double *d_resid, void *stream);
 int pcs_tri_refined(pcs_triangulator *t, double *pts, double *rms, int32_t *info, double *resid);
 int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms);
+/* Robust loss of the refinement (since pcs_version() 113).  The kinds, the formulas and the validation are those of pcs_set_loss, applied
+ * to each scalar residual (u and v separately): H = sum s^2 J'J, g = sum J' rho1 f.  The cost the accept rule, ftol and the test of the
+ * start look at is sum rho0; the depth test, the damping, xtol, gtol (on the robust g) and the statuses keep their rules.  d_rms stays the
+ * plain pixel RMS and d_resid the raw residuals.  The setting belongs to the handle and survives new cameras and observations;
+ * PCS_LOSS_LINEAR, the default, launches the kernel of a handle on which no loss was ever set.
+ *   pcs_tri_set_refine_loss  mirrors pcs_set_loss.  PCS_ERR_ARG (the previous setting stays in force): NULL handle, a kind outside
+ *                            PCS_LOSS_*, an f_scale that is not finite and > 0.
+ *   pcs_tri_get_refine_loss  mirrors pcs_get_loss (either pointer may be NULL).
+ *   pcs_tri_refine_costs     mirrors pcs_tri_refined for one more output: cost (n_pts, 2) = 0.5 sum rho0 (scipy's cost) at the returned
+ *                            point and at the DLT point, always handle-owned (blocking).  A point that was not refined has the cost
+ *                            of its unchanged start in both columns, as its RMS has: finite for a start behind a camera, NaN for a
+ *                            non-finite start and for a point without views — under every loss, linear included.  After a LINEAR
+ *                            refinement the costs are derived in this call, 0.5 n rms^2 from the RMS that refinement wrote (read on
+ *                            the device where it wrote it: the handle's output or the caller's d_rms, which must still hold it);
+ *                            the refinement itself queues what it queued before a loss existed.  PCS_ERR_ARG: NULL handle or array;
+ *                            PCS_ERR_STATE: no refinement since the last run. */
+int pcs_tri_set_refine_loss(pcs_triangulator *t, int kind, double f_scale);
+int pcs_tri_get_refine_loss(pcs_triangulator *t, int *kind, double *f_scale);
+int pcs_tri_refine_costs(pcs_triangulator *t, double *cost);
 
 /* ------------------------------------------------------------------------------------------------
  * Batched target-pose estimation, PnP (csrc/ba_pnp.hpp).  Since pcs_version() 105.
@@ -717,6 +736,24 @@ int pcs_rigpose_run(pcs_rig_localiser *p, int max_iter, double ftol, double xtol
                     double *d_pose, double *d_rms, int32_t *d_info, double *d_hess, double *d_resid, void *stream);
 int pcs_rigpose_results(pcs_rig_localiser *p, double *pose, double *rms, int32_t *info, double *hess, double *resid);
 int pcs_rigpose_last_kernel_ms(pcs_rig_localiser *p, float *kernel_ms);
+/* Robust loss of the per-image solve (since pcs_version() 113; the reference's commented `loss = "cauchy"` on the least_squares call
+ * find_target.py:9-82 goes through).  The kinds, the formulas and the validation are those of pcs_set_loss, applied to each scalar
+ * residual (u and v separately): H = sum s^2 J'J, g = sum J' rho1 f.  The cost the accept rule, ftol and the test of the start look at
+ * is sum rho0; the depth test, the damping, xtol, gtol (on the robust g) and the statuses keep their rules.  d_rms stays the plain pixel
+ * RMS and d_resid the raw residuals; d_hess holds the robust H.  The setting belongs to the handle and survives new cameras and
+ * observations; PCS_LOSS_LINEAR, the default, launches the kernel of a handle on which no loss was ever set.
+ *   pcs_rigpose_set_loss  mirrors pcs_set_loss.  PCS_ERR_ARG (the previous setting stays in force): NULL handle, a kind outside
+ *                         PCS_LOSS_*, an f_scale that is not finite and > 0.
+ *   pcs_rigpose_get_loss  mirrors pcs_get_loss (either pointer may be NULL).
+ *   pcs_rigpose_costs     mirrors pcs_rigpose_results for one more output: cost (n_groups, 2) = 0.5 sum rho0 (scipy's cost) at the
+ *                         returned pose and at the start, NaN when not estimated, always handle-owned (blocking).  After a LINEAR run
+ *                         the costs are derived in this call, 0.5 n rms^2 from the RMS that run wrote (read on the device where it
+ *                         wrote it: the handle's output or the caller's d_rms, which must still hold it); the run itself queues
+ *                         what it queued before a loss existed.  PCS_ERR_ARG: NULL handle or array; PCS_ERR_STATE: no run on the
+ *                         current inputs. */
+int pcs_rigpose_set_loss(pcs_rig_localiser *p, int kind, double f_scale);
+int pcs_rigpose_get_loss(pcs_rig_localiser *p, int *kind, double *f_scale);
+int pcs_rigpose_costs(pcs_rig_localiser *p, double *cost);
 
 /* ------------------------------------------------------------------------------------------------
  * Camera intrinsics from planar target views (csrc/ba_intrinsics.hpp).  Since pcs_version() 106.

@@ -146,6 +146,9 @@ SYMBOLS = {
     "pcs_tri_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_tri_refine": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, _P, _P, _P, _P, _P]),
     "pcs_tri_refined": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
+    "pcs_tri_set_refine_loss": (c_int, [_P, c_int, c_double]),
+    "pcs_tri_get_refine_loss": (c_int, [_P, POINTER(c_int), POINTER(c_double)]),
+    "pcs_tri_refine_costs": (c_int, [_P, POINTER(c_double)]),
     "pcs_tri_last_refine_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_pnp_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_pnp_destroy": (c_int, [_P]),
@@ -165,6 +168,9 @@ SYMBOLS = {
     "pcs_rigpose_run": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "pcs_rigpose_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_double)]),
     "pcs_rigpose_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_rigpose_set_loss": (c_int, [_P, c_int, c_double]),
+    "pcs_rigpose_get_loss": (c_int, [_P, POINTER(c_int), POINTER(c_double)]),
+    "pcs_rigpose_costs": (c_int, [_P, POINTER(c_double)]),
     "pcs_intr_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_intr_destroy": (c_int, [_P]),
     "pcs_intr_set_template": (c_int, [_P, POINTER(c_double)]),

@@ -84,13 +84,27 @@ def check_refine_options(max_iter, ftol, xtol, gtol):
     return tuple(out)
 
 
+def check_loss(loss, f_scale):
+    """Validate ``loss`` / ``f_scale`` the way ``device_solver.lm_solve`` does (ValueError) -> (name, float(f_scale))."""
+    if loss not in _capi.LOSS_IDS:
+        raise ValueError(f"unknown loss {loss!r}: expected one of {sorted(_capi.LOSS_IDS)}")
+    try:
+        fs = float(f_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"f_scale must be finite and > 0, got {f_scale!r}") from None
+    if not (np.isfinite(fs) and fs > 0.0):
+        raise ValueError(f"f_scale must be finite and > 0, got {f_scale}")
+    return loss, fs
+
+
 @dataclass
 class TriangulationResult:
     """Refined triangulation (``refine_triangulation``, ``multi_cam_triangulate(return_result=True)``, ``Triangulator.refined``).
 
     points, points_dlt: (n, 3) refined and DLT points; rms, rms_dlt: (n,) RMS reprojection error sqrt(sum_v |r_v|^2 / n_v) in pixels at
-    them (rms <= rms_dlt); n_views, iterations (LM trials), status (TRI_*): (n,) int32; residuals: (n_obs, 2) uv - pi(points) in the
-    observation order, or None."""
+    them (rms <= rms_dlt without a loss); n_views, iterations (LM trials), status (TRI_*): (n,) int32; residuals: (n_obs, 2)
+    uv - pi(points) in the observation order, or None; cost: (n,) scipy's 0.5 sum rho0 of the refinement's loss at the points (half
+    the sum of squares without one), or None for a result that was not fetched with it."""
     points: np.ndarray
     points_dlt: np.ndarray
     rms: np.ndarray
@@ -99,6 +113,7 @@ class TriangulationResult:
     iterations: np.ndarray
     status: np.ndarray
     residuals: np.ndarray | None = None
+    cost: np.ndarray | None = None
 
 
 def _cached_handle(cache: dict, key, factory):
@@ -236,6 +251,24 @@ class Triangulator(_Handle):
                    self._addr(d_pts), self._addr(d_rms), self._addr(d_info), self._addr(d_resid), _stream_arg(stream))
         self._refined_residuals = bool(residuals) and not d_resid
 
+    def set_refine_loss(self, loss: str = "linear", f_scale: float = 1.0):
+        """The robust loss of ``refine`` (include/pcs_hip.h pcs_tri_set_refine_loss): scipy's 'linear' (the default), 'huber',
+        'soft_l1', 'cauchy', 'arctan' on each scalar residual, ``f_scale`` in pixels.  It stays with the handle until it is set again."""
+        loss, f_scale = check_loss(loss, f_scale)
+        self._call("pcs_tri_set_refine_loss", self._h, self._capi.LOSS_IDS[loss], f_scale)
+
+    def get_refine_loss(self):
+        """The current (loss, f_scale) of ``set_refine_loss``."""
+        k, fs = self._ct.c_int(), self._ct.c_double()
+        self._call("pcs_tri_get_refine_loss", self._h, self._ct.byref(k), self._ct.byref(fs))
+        return {v: n for n, v in self._capi.LOSS_IDS.items()}[k.value], fs.value
+
+    def refine_costs(self) -> np.ndarray:
+        """Wait for the last ``refine``: (n_pts, 2) scipy's cost 0.5 sum rho0 at the refined point and at the DLT point."""
+        cost = np.empty((max(self.n_pts, 0), 2))
+        self._call("pcs_tri_refine_costs", self._h, self._ptr(cost))
+        return cost
+
     def refined(self, points_dlt: np.ndarray | None = None) -> "TriangulationResult":
         """Wait for the last ``refine`` and return its handle-owned outputs.  ``points_dlt``: the start points, when the run wrote
         them to a caller buffer (otherwise they are fetched from the handle)."""
@@ -245,7 +278,7 @@ class Triangulator(_Handle):
         self._call("pcs_tri_refined", self._h, self._ptr(pts), self._ptr(rms), self._ptr(info), self._ptr(resid))
         start = self.points() if points_dlt is None else np.asarray(points_dlt, dtype=np.float64).reshape(n, 3)
         return TriangulationResult(points=pts, points_dlt=start, rms=rms[:, 0].copy(), rms_dlt=rms[:, 1].copy(), n_views=info[:, 2].copy(),
-                                   iterations=info[:, 0].copy(), status=info[:, 1].copy(), residuals=resid)
+                                   iterations=info[:, 0].copy(), status=info[:, 1].copy(), residuals=resid, cost=self.refine_costs()[:, 0].copy())
 
     def last_refine_ms(self) -> float:
         return self._ms("pcs_tri_last_refine_ms")
@@ -280,18 +313,21 @@ def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0) -> 
 def _empty_result(return_residuals: bool) -> TriangulationResult:
     z, i = np.empty((0, 3)), np.empty(0, dtype=np.int32)
     return TriangulationResult(points=z, points_dlt=z.copy(), rms=np.empty(0), rms_dlt=np.empty(0), n_views=i, iterations=i.copy(), status=i.copy(),
-                               residuals=np.empty((0, 2)) if return_residuals else None)
+                               residuals=np.empty((0, 2)) if return_residuals else None, cost=np.empty(0))
 
 
 def refine_triangulation(data, proj, start_inds, intr, dist, *, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"],
                          xtol: float = REFINE_DEFAULTS["xtol"], gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False,
-                         device: int = 0) -> TriangulationResult:
+                         device: int = 0, loss: str = "linear", f_scale: float = 1.0) -> TriangulationResult:
     """``nb_triangulate_full`` followed by the per-point refinement of the reprojection error in the measured (distorted) pixels
     (include/pcs_hip.h pcs_tri_refine): DLT and refinement are queued back to back on the device, one synchronisation at the end.
     ``data`` rows = [cam, ..., u, v] sorted by point, ``start_inds`` (n_pts + 1).  Returns a ``TriangulationResult``; with
-    ``return_residuals`` its ``residuals`` are (n_obs, 2) in the rows' order."""
+    ``return_residuals`` its ``residuals`` are (n_obs, 2) in the rows' order.  ``loss`` / ``f_scale``: a robust loss on each scalar
+    residual (``Triangulator.set_refine_loss``); the DLT start is the plain one, ``rms`` stays the plain pixel RMS and ``residuals`` the
+    raw ones (``diagnostics.robust_weights`` lists what was down-weighted)."""
     global last_triangulate_kernel_ms
     opts = check_refine_options(max_iter, ftol, xtol, gtol)
+    loss, f_scale = check_loss(loss, f_scale)
     data = np.asarray(data, dtype=np.float64)
     P = np.asarray(proj, dtype=np.float64)
     start = np.asarray(start_inds, dtype=np.int64)
@@ -303,6 +339,7 @@ def refine_triangulation(data, proj, start_inds, intr, dist, *, max_iter: int = 
     tri.set_cameras(P, intr, dist)
     tri.set_observations(data[:, 0].astype(np.int32), data[:, -2:], start)
     tri.run()
+    tri.set_refine_loss(loss, f_scale)   # the handle is shared between calls: every call states its loss
     tri.refine(*opts, residuals=return_residuals)
     res = tri.refined()
     last_triangulate_kernel_ms = tri.last_kernel_ms()
@@ -311,7 +348,7 @@ def refine_triangulation(data, proj, start_inds, intr, dist, *, max_iter: int = 
 
 def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: int = 0, *, refine: bool = False, return_result: bool = False,
                           max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
-                          gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False):
+                          gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False, loss: str = "linear", f_scale: float = 1.0):
     """``CameraSet.multi_cam_triangulate`` for a detection table (cameras/camera_set.py:343-402, the array branch): ``data`` rows =
     [cam, image, key..., u, v] as ``TargetDetection.get_data`` returns them; the features seen by more than one camera are
     triangulated, in order of first appearance.  Grouping (``np.unique`` twice in the reference: 0.37 s for 1e6 rows) AND
@@ -322,8 +359,9 @@ def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: 
     ftol, xtol, gtol), grouping, DLT and refinement queued back to back, one synchronisation at the end.  ``return_result=True``
     returns the ``TriangulationResult`` (points, RMS errors, status, with ``return_residuals`` the residuals in the order of the kept
     rows) instead of the points; without ``refine`` it carries the DLT points and their RMS (a refinement with max_iter = 0).  The
-    default returns the DLT points, as before."""
+    default returns the DLT points, as before.  ``loss`` / ``f_scale``: the robust loss of the refinement (``refine_triangulation``)."""
     global last_triangulate_kernel_ms
+    loss, f_scale = check_loss(loss, f_scale)
     with_result = refine or return_result
     if with_result:
         opts = check_refine_options(max_iter if refine else 0, ftol, xtol, gtol)
@@ -343,7 +381,7 @@ def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: 
         if not with_result:
             return nb_triangulate_full(rec, P, start, intr, D, device=device)
         return out(refine_triangulation(rec, P, start, intr, D, max_iter=opts[0], ftol=opts[1], xtol=opts[2], gtol=opts[3],
-                                        return_residuals=return_residuals, device=device))
+                                        return_residuals=return_residuals, device=device, loss=loss, f_scale=f_scale))
     if n_pts == 0:
         return empty()
     tri.run()
@@ -351,6 +389,7 @@ def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: 
         pts = tri.points()
         last_triangulate_kernel_ms = tri.last_kernel_ms()
         return pts
+    tri.set_refine_loss(loss, f_scale)
     tri.refine(*opts, residuals=return_residuals)
     res = tri.refined()
     last_triangulate_kernel_ms = tri.last_kernel_ms()
@@ -979,7 +1018,11 @@ class ImagePoses:
     detections of the image at the pose / at the start (rms <= rms_init); ``status`` (RIGPOSE_*), ``iterations`` (LM trials),
     ``n_points`` (detections), ``n_cams`` (cameras that contributed): (I,) int32; ``hessian`` (I, 6, 6) = J'J at the pose for the update
     R <- exp([d omega]x) R, t <- t + d t; ``residuals`` (N, 2) uv - projection in the table's row order, or None.  Images without
-    detections, with fewer than ``min_points`` or without a usable start: NaN, status 0."""
+    detections, with fewer than ``min_points`` or without a usable start: NaN, status 0.
+
+    ``loss`` / ``f_scale``: the robust loss the poses minimise (``localise_target``); ``cost`` / ``cost_init`` (I,) scipy's
+    0.5 sum rho0 at the pose / at the start (half the sum of squares for 'linear'; cost <= cost_init).  Under a loss ``hessian`` is the
+    robust sum s^2 J'J, ``rms`` stays the plain pixel RMS (it may exceed ``rms_init``) and ``residuals`` the raw ones."""
     poses: np.ndarray
     poses_init: np.ndarray
     rms: np.ndarray
@@ -990,11 +1033,16 @@ class ImagePoses:
     n_cams: np.ndarray
     hessian: np.ndarray
     residuals: np.ndarray | None = None
+    cost: np.ndarray | None = None
+    cost_init: np.ndarray | None = None
+    loss: str = "linear"
+    f_scale: float = 1.0
 
     def covariance(self, absolute_sigma: bool = False) -> np.ndarray:
         """(I, 6, 6) = sigma^2 inv(H) in the coordinates (d omega, d t) of the update, sigma^2 = sum r^2 / (2 n - 6), or 1 with
-        ``absolute_sigma`` (the meanings of ``device_solver.parameter_covariance``).  NaN for an image that was not estimated, has no
-        degree of freedom left (2 n <= 6) or a singular H (a NumPy batch inverse on the host; nothing raises)."""
+        ``absolute_sigma`` (the meanings of ``device_solver.parameter_covariance``).  Under a loss H is the returned robust H and
+        sigma^2 = 2 cost / (2 n - 6).  NaN for an image that was not estimated, has no degree of freedom left (2 n <= 6) or a singular H
+        (a NumPy batch inverse on the host; nothing raises)."""
         I = self.hessian.shape[0]
         out = np.full((I, 6, 6), np.nan)
         n = self.n_points.astype(np.float64)
@@ -1013,7 +1061,12 @@ class ImagePoses:
                 inv = np.linalg.inv(H)
             except np.linalg.LinAlgError:
                 continue
-            s2 = 1.0 if absolute_sigma else self.rms[i] ** 2 * n[i] / dof
+            if absolute_sigma:
+                s2 = 1.0
+            elif self.loss != "linear":
+                s2 = 2.0 * self.cost[i] / dof
+            else:
+                s2 = self.rms[i] ** 2 * n[i] / dof
             out[i] = s2 * inv
         return out
 
@@ -1076,6 +1129,24 @@ class RigLocaliser(_Handle):
                    None, None, None, None, None, _stream_arg(stream))
         self._residuals = bool(residuals)
 
+    def set_loss(self, loss: str = "linear", f_scale: float = 1.0):
+        """The robust loss of ``run`` (include/pcs_hip.h pcs_rigpose_set_loss): scipy's 'linear' (the default), 'huber', 'soft_l1',
+        'cauchy', 'arctan' on each scalar residual, ``f_scale`` in pixels.  It stays with the handle until it is set again."""
+        loss, f_scale = check_loss(loss, f_scale)
+        self._call("pcs_rigpose_set_loss", self._h, self._capi.LOSS_IDS[loss], f_scale)
+
+    def get_loss(self):
+        """The current (loss, f_scale) of ``set_loss``."""
+        k, fs = self._ct.c_int(), self._ct.c_double()
+        self._call("pcs_rigpose_get_loss", self._h, self._ct.byref(k), self._ct.byref(fs))
+        return {v: n for n, v in self._capi.LOSS_IDS.items()}[k.value], fs.value
+
+    def costs(self) -> np.ndarray:
+        """Wait for the last ``run``: (n, 2) scipy's cost 0.5 sum rho0 at the returned pose and at the start (NaN: not estimated)."""
+        cost = np.empty((self.n_groups, 2))
+        self._call("pcs_rigpose_costs", self._h, self._ptr(cost))
+        return cost
+
     def results(self):
         """Wait for the last ``run``: (pose (n, 6), rms (n, 2), info (n, 4) int32, hessian (n, 21), residuals or None)."""
         n = self.n_groups
@@ -1127,7 +1198,9 @@ def _rig_localiser(device: int, n_cams: int, n_keys: int) -> RigLocaliser:
 def rig_pose_start(dct, points, intr, ext, n_imgs: int, min_points: int = 6, device: int = 0) -> np.ndarray:
     """A start (I, 6) for ``localise_target`` from the existing pieces: the per-view poses of ``estimate_view_poses``, every camera's
     estimate W[c', i] = inv(E_c') M[c', i] of the image's pose and its error over ALL detections of the image
-    (``rig_candidate_scores``); the image takes the finite candidate of lowest error, ties to the lowest camera.  NaN where there is none."""
+    (``rig_candidate_scores``); the image takes the finite candidate of lowest error, ties to the lowest camera.  NaN where there is none.
+    The start is linear whatever loss ``localise_target`` runs with: the PnP and the scores take no loss, an outlier moves the start
+    and the robust solve works from there."""
     from .pose_seeding import pose_from_4x4, to_4x4
 
     vp = estimate_view_poses(dct, points, intr, n_imgs=n_imgs, min_points=min_points, device=device)
@@ -1179,7 +1252,7 @@ def check_localise_arguments(dct, points, intr, ext, n_imgs, poses_init, min_poi
 def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_init=None, min_points: int = 6,
                     max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
                     gtol: float = REFINE_DEFAULTS["gtol"], group_lanes: int | None = None, return_residuals: bool = False,
-                    device: int = 0) -> ImagePoses:
+                    device: int = 0, loss: str = "linear", f_scale: float = 1.0) -> ImagePoses:
     """The pose of the known target in every image of a rig whose cameras are held fixed, on the device (include/pcs_hip.h
     pcs_rigpose_run): what the reference's ``find_target_poses`` (optimisation/find_target.py:9-82) gets from a bundle adjustment with
     every camera's "ext" / "int" / "dst" fixed, as one independent 6-parameter problem per image.
@@ -1188,14 +1261,21 @@ def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_
     template (K, 3); ``intr``: (C, 9) rows [fx, cx, fy, cy, k0, k1, p0, p1, k2]; ``ext``: (C, 3, 4) world -> camera, the convention of
     ``rig_candidate_scores``; ``n_imgs``: images of the result (default: largest image index + 1); ``poses_init``: (I, 6) starts (NaN
     rows are not estimated), default ``rig_pose_start``; ``group_lanes``: 16 or 64 lanes per image, default by the mean number of
-    detections per image (include/pcs_hip.h)."""
+    detections per image (include/pcs_hip.h).
+
+    ``loss`` / ``f_scale``: scipy ``least_squares``'s robust losses ('linear', 'huber', 'soft_l1', 'cauchy', 'arctan') on each scalar
+    residual, ``f_scale`` in pixels (include/pcs_hip.h pcs_rigpose_set_loss; the reference's commented ``loss = "cauchy"``).  The
+    default start stays the linear one (``rig_pose_start``).  ``diagnostics.robust_weights(res.residuals, loss, f_scale)`` lists what
+    was down-weighted."""
     global last_rigpose_kernel_ms
+    loss, f_scale = check_loss(loss, f_scale)
     d, pts, K, E, I, start, min_points, opts, lanes = check_localise_arguments(dct, points, intr, ext, n_imgs, poses_init, min_points, max_iter, ftol, xtol,
                                                                                gtol, group_lanes)
     out = ImagePoses(poses=np.full((I, 6), np.nan), poses_init=np.full((I, 6), np.nan), rms=np.full(I, np.nan), rms_init=np.full(I, np.nan),
                      status=np.zeros(I, dtype=np.int32), iterations=np.zeros(I, dtype=np.int32), n_points=np.zeros(I, dtype=np.int32),
                      n_cams=np.zeros(I, dtype=np.int32), hessian=np.full((I, 6, 6), np.nan),
-                     residuals=np.empty((d.shape[0], 2)) if return_residuals else None)
+                     residuals=np.empty((d.shape[0], 2)) if return_residuals else None, cost=np.full(I, np.nan), cost_init=np.full(I, np.nan),
+                     loss=loss, f_scale=f_scale)
     if start is not None:
         out.poses_init[:] = start
     if d.shape[0] == 0:
@@ -1211,8 +1291,11 @@ def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_
     loc.set_template(pts)
     loc.set_observations(ds[:, 2].astype(np.int32), ds[:, 0].astype(np.int32), ds[:, 3:5], first)
     loc.set_start(start[ids])
+    loc.set_loss(loss, f_scale)   # the handle is shared between calls: every call states its loss
     loc.run(*opts, min_points=min_points, group_lanes=lanes or None, residuals=return_residuals)
     pose, rms, info, hess, resid = loc.results()
+    cost = loc.costs()
+    out.cost[ids], out.cost_init[ids] = cost[:, 0], cost[:, 1]
     last_rigpose_kernel_ms = loc.last_kernel_ms()
     out.poses[ids] = pose
     out.rms[ids], out.rms_init[ids] = rms[:, 0], rms[:, 1]

@@ -138,6 +138,20 @@ __device__ __forceinline__ double robust_rho(const int kind, const double f, con
     rf = rho1 * f / s;
     return s;
 }
+// The loss of a robust group-LM launch (ba_rigpose.hpp, ba_tri_refine.hpp): a kind other than LOSS_LINEAR with 1 / f_scale and
+// f_scale^2, uniform over the launch.  The linear instantiations of those kernels take none.
+struct GroupLoss {
+    int kind;
+    double inv_f_scale, f_scale_sq;
+};
+// Those kernels end in a parameter pack `Robust... robust`: empty for the linear instantiation, whose signature and code are then
+// those of a kernel that knows no loss, or (GroupLoss, double *cost_out) for the robust one.  These read the pack.
+template <class... Robust> struct is_robust_pack { static constexpr bool ok = sizeof...(Robust) == 0; };
+template <> struct is_robust_pack<GroupLoss, double *> { static constexpr bool ok = true; };
+__device__ __forceinline__ GroupLoss robust_loss() { return {LOSS_LINEAR, 1.0, 1.0}; }
+__device__ __forceinline__ GroupLoss robust_loss(const GroupLoss loss, double *) { return loss; }
+__device__ __forceinline__ double *robust_cost_out() { return nullptr; }
+__device__ __forceinline__ double *robust_cost_out(const GroupLoss, double *cost_out) { return cost_out; }
 #endif
 
 // broadcast lane `src`'s value to the whole wave through scalar registers (v_readlane_b32)

@@ -30,6 +30,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_device.hpp"
 #include "ba_triangulate.hpp"
 
 namespace pcs {
@@ -464,6 +465,28 @@ __device__ __forceinline__ void pnp_accumulate(double (&s)[PNP_SUMS], const doub
     for (int i = 0; i < 6; ++i) s[21 + i] = fma(Ju[i], ru, fma(Jv[i], rv, s[21 + i]));
     s[27] = fma(ru, ru, fma(rv, rv, s[27]));
     s[28] += front ? 0.0 : 1.0;   // behind the camera (NaN depths are not > 0 either)
+}
+
+// The robust twin of pnp_accumulate (the robust rigpose_lm_kernel; pnp_lm_kernel takes no loss): u and v are scaled separately by
+// robust_rho — row s J, residual rho1 f / s — so that s[0..21) = sum s^2 J'J, s[21..27) = sum J' rho1 f and s[27] = sum rho0, the cost
+// the loop watches.  `raw` takes the plain sum of squares, which the reported RMS needs.
+__device__ __forceinline__ void pnp_accumulate_robust(double (&s)[PNP_SUMS], double &raw, const GroupLoss &loss, const double ru, const double rv,
+                                                      const double (&Ju)[6], const double (&Jv)[6], const bool front) {
+    double q0, q1, fu, fv, Su[6], Sv[6];
+    const double su = robust_rho(loss.kind, ru, loss.inv_f_scale, loss.f_scale_sq, q0, fu);
+    const double sv = robust_rho(loss.kind, rv, loss.inv_f_scale, loss.f_scale_sq, q1, fv);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) Su[i] = su * Ju[i], Sv[i] = sv * Jv[i];
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j, ++k) s[k] = fma(Su[i], Su[j], fma(Sv[i], Sv[j], s[k]));
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s[21 + i] = fma(Su[i], fu, fma(Sv[i], fv, s[21 + i]));
+    s[27] += q0 + q1;
+    s[28] += front ? 0.0 : 1.0;
+    raw = fma(ru, ru, fma(rv, rv, raw));
 }
 
 // (H + lam diag(H)) d = g; false when the damped system is not positive definite or d is not finite

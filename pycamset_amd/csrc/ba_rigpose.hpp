@@ -45,14 +45,23 @@ __device__ __forceinline__ void rigpose_point(const double (&R)[9], const double
     Jv[0] = Y1 * b2 - Y2 * b1; Jv[1] = Y2 * b0 - Y0 * b2; Jv[2] = Y0 * b1 - Y1 * b0; Jv[3] = b0; Jv[4] = b1; Jv[5] = b2;
 }
 
-template <int G>
+// The trailing pack is empty (the linear instantiation: the plain sum of squares, signature and code of a kernel that knows no loss;
+// profiles/r20/README.md) or (GroupLoss loss, double *cost_out), the robust one: the sums come from pnp_accumulate_robust, so the cost
+// every rule of the loop looks at (accept, ftol, usable start) is sum rho0, gtol looks at the robust g and hess_out receives the robust
+// H; the RMS is still the plain one (one more sum per pass), and cost_out (n_imgs, 2) receives 0.5 sum rho0 at the result and at the
+// start (NaN where no pose was estimated).
+template <int G, class... Robust>
 __global__ __launch_bounds__(256) void rigpose_lm_kernel(const int32_t *__restrict__ key, const int32_t *__restrict__ cam, const double2 *__restrict__ uv,
                                                          const int64_t *__restrict__ start, const double *__restrict__ cam_tab,
                                                          const double *__restrict__ ext_tab, const double *__restrict__ pts, const int64_t n_imgs,
                                                          const int32_t *__restrict__ order, const double *__restrict__ pose_start, const int max_iter,
                                                          const double ftol, const double xtol, const double gtol, const int min_points,
                                                          double *__restrict__ pose_out, double *__restrict__ rms_out, int32_t *__restrict__ info_out,
-                                                         double *__restrict__ hess_out, double *__restrict__ resid_out) {
+                                                         double *__restrict__ hess_out, double *__restrict__ resid_out, const Robust... robust) {
+    static_assert(is_robust_pack<Robust...>::ok, "the pack is empty (linear) or (GroupLoss, double *cost_out) (robust)");
+    constexpr bool ROBUST = sizeof...(Robust) != 0;
+    const GroupLoss loss = robust_loss(robust...);
+    double *const cost_out = robust_cost_out(robust...);
     static_assert(G == 16 || G == 32 || G == 64, "a group is a power-of-two part of one wave");
     const int64_t gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
     const int g = threadIdx.x & (G - 1);
@@ -64,18 +73,21 @@ __global__ __launch_bounds__(256) void rigpose_lm_kernel(const int32_t *__restri
     const bool enough = live && n > 0 && n >= min_points;
 
     // one pass: the group's sums at (R, t) (every lane of the group gets identical bits)
-    auto pass = [&](const double (&R)[9], const double (&t)[3], double (&s)[PNP_SUMS]) {
+    auto pass = [&](const double (&R)[9], const double (&t)[3], double (&s)[PNP_SUMS], double &raw) {
 #pragma unroll
         for (int k = 0; k < PNP_SUMS; ++k) s[k] = 0.0;
+        if constexpr (ROBUST) raw = 0.0;
         for (int64_t q = s0 + g; q < s1; q += G) {
             const int64_t c = cam[q];
             double ru, rv, Ju[6], Jv[6];
             bool front;
             rigpose_point(R, t, cam_tab + c * TRI_CAM_STRIDE + 22, ext_tab + c * RIGPOSE_EXT_STRIDE, pts + 3 * (int64_t)key[q], uv[q], ru, rv, Ju, Jv, front);
-            pnp_accumulate(s, ru, rv, Ju, Jv, front);
+            if constexpr (ROBUST) pnp_accumulate_robust(s, raw, loss, ru, rv, Ju, Jv, front);
+            else pnp_accumulate(s, ru, rv, Ju, Jv, front);
         }
 #pragma unroll
         for (int k = 0; k < PNP_SUMS; ++k) s[k] = group_sum<G>(s[k]);
+        if constexpr (ROBUST) raw = group_sum<G>(raw);
     };
 
     // cameras that contribute: the runs of the (non-decreasing) camera column inside the image
@@ -90,6 +102,7 @@ __global__ __launch_bounds__(256) void rigpose_lm_kernel(const int32_t *__restri
 #pragma unroll
     for (int k = 0; k < 6; ++k) fin = fin && isfinite(ps[k]);
     double R[9], t[3] = {ps[3], ps[4], ps[5]}, cur[PNP_SUMS], cost0 = 0.0;
+    double raw = 0.0, raw0 = 0.0, raw_t = 0.0;   // ROBUST only: the plain sums of squares at the pose, at the start and of a trial
     {
         const double r[3] = {ps[0], ps[1], ps[2]};
         pnp_rodrigues(r, R);
@@ -99,8 +112,9 @@ __global__ __launch_bounds__(256) void rigpose_lm_kernel(const int32_t *__restri
     int status = PNP_NOT_ESTIMATED, it = 0;
     bool done = true, moved = false;
     if (fin) {   // cost, H and g at the start
-        pass(R, t, cur);
+        pass(R, t, cur, raw);
         cost0 = cur[27];
+        if constexpr (ROBUST) raw0 = raw;
         done = !(isfinite(cur[27]) && cur[28] == 0.0);   // not estimated from this start
     }
     const bool usable = !done;
@@ -127,7 +141,7 @@ __global__ __launch_bounds__(256) void rigpose_lm_kernel(const int32_t *__restri
 #pragma unroll
                 for (int k = 0; k < 3; ++k) Rt[3 * r + k] = dR[3 * r] * R[k] + dR[3 * r + 1] * R[3 + k] + dR[3 * r + 2] * R[6 + k];
             const double tt[3] = {t[0] + d[3], t[1] + d[4], t[2] + d[5]};
-            pass(Rt, tt, s);
+            pass(Rt, tt, s, raw_t);
             ++it;
             const double step = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
             const double size = sqrt(3.0 + t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);   // Frobenius size of [R | t]
@@ -140,6 +154,7 @@ __global__ __launch_bounds__(256) void rigpose_lm_kernel(const int32_t *__restri
 #pragma unroll
                 for (int k = 0; k < PNP_SUMS; ++k) cur[k] = s[k];
                 moved = true;
+                if constexpr (ROBUST) raw = raw_t;
                 lam = fmax(lam * 0.1, PNP_LAMBDA_MIN);
                 if (flat || small) { status = PNP_CONVERGED; done = true; }
             } else {
@@ -165,8 +180,12 @@ __global__ __launch_bounds__(256) void rigpose_lm_kernel(const int32_t *__restri
 #pragma unroll
         for (int k = 0; k < 6; ++k) pose_out[6 * j + k] = best[k];
         const double inv_n = 1.0 / (double)n;
-        rms_out[2 * j + 0] = est ? sqrt(cur[27] * inv_n) : __builtin_nan("");
-        rms_out[2 * j + 1] = est ? sqrt(cost0 * inv_n) : __builtin_nan("");
+        rms_out[2 * j + 0] = est ? sqrt((ROBUST ? raw : cur[27]) * inv_n) : __builtin_nan("");
+        rms_out[2 * j + 1] = est ? sqrt((ROBUST ? raw0 : cost0) * inv_n) : __builtin_nan("");
+        if constexpr (ROBUST) {
+            cost_out[2 * j + 0] = est ? 0.5 * cur[27] : __builtin_nan("");
+            cost_out[2 * j + 1] = est ? 0.5 * cost0 : __builtin_nan("");
+        }
         info_out[4 * j + 0] = est ? it : 0;
         info_out[4 * j + 1] = est ? status : PNP_NOT_ESTIMATED;
         info_out[4 * j + 2] = (int32_t)n;

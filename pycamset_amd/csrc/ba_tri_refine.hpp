@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_device.hpp"
 #include "ba_triangulate.hpp"
 
 namespace pcs {
@@ -79,6 +80,29 @@ __device__ __forceinline__ void refine_accumulate(double (&s)[TRI_REFINE_SUMS], 
     s[10] += front ? 0.0 : 1.0;   // behind the camera (NaN depths are not > 0 either)
 }
 
+// The robust twin of refine_accumulate: u and v are scaled separately by robust_rho — row s J, residual rho1 f / s — so that
+// s[0..6) = sum s^2 J'J, s[6..9) = sum J' rho1 f and s[9] = sum rho0, the cost the loop watches.  `raw` takes the plain sum of
+// squares, which the reported RMS needs.
+__device__ __forceinline__ void refine_accumulate_robust(double (&s)[TRI_REFINE_SUMS], double &raw, const GroupLoss &loss, const double ru, const double rv,
+                                                         const double (&J)[2][3], const bool front) {
+    double q0, q1, fu, fv;
+    const double su = robust_rho(loss.kind, ru, loss.inv_f_scale, loss.f_scale_sq, q0, fu);
+    const double sv = robust_rho(loss.kind, rv, loss.inv_f_scale, loss.f_scale_sq, q1, fv);
+    const double S[2][3] = {{su * J[0][0], su * J[0][1], su * J[0][2]}, {sv * J[1][0], sv * J[1][1], sv * J[1][2]}};
+    s[0] = fma(S[0][0], S[0][0], fma(S[1][0], S[1][0], s[0]));
+    s[1] = fma(S[0][0], S[0][1], fma(S[1][0], S[1][1], s[1]));
+    s[2] = fma(S[0][0], S[0][2], fma(S[1][0], S[1][2], s[2]));
+    s[3] = fma(S[0][1], S[0][1], fma(S[1][1], S[1][1], s[3]));
+    s[4] = fma(S[0][1], S[0][2], fma(S[1][1], S[1][2], s[4]));
+    s[5] = fma(S[0][2], S[0][2], fma(S[1][2], S[1][2], s[5]));
+    s[6] = fma(S[0][0], fu, fma(S[1][0], fv, s[6]));
+    s[7] = fma(S[0][1], fu, fma(S[1][1], fv, s[7]));
+    s[8] = fma(S[0][2], fu, fma(S[1][2], fv, s[8]));
+    s[9] += q0 + q1;
+    s[10] += front ? 0.0 : 1.0;
+    raw = fma(ru, ru, fma(rv, rv, raw));
+}
+
 // (H + lam diag(H)) d = g by LDL' on the packed upper triangle; false when a pivot is not positive (or not finite)
 __device__ __forceinline__ bool refine_solve(const double (&H)[6], const double (&g)[3], const double lam, double (&d)[3]) {
     const double a00 = H[0] * (1.0 + lam), a11 = H[3] * (1.0 + lam), a22 = H[5] * (1.0 + lam);
@@ -99,13 +123,21 @@ __device__ __forceinline__ bool refine_solve(const double (&H)[6], const double 
     return pd && isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
 }
 
-template <int G, int V>
+// The trailing pack is empty (the linear instantiation: the plain sum of squares, signature and code of a kernel that knows no loss;
+// profiles/r20/README.md) or (GroupLoss loss, double *cost_out), the robust one: the sums come from refine_accumulate_robust, the cost
+// every rule of the loop looks at is sum rho0, the RMS is still the plain one (one more sum per pass), and cost_out (n_pts, 2) receives
+// 0.5 sum rho0 at the result and at the start.
+template <int G, int V, class... Robust>
 __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *__restrict__ cam, const double2 *__restrict__ uv,
                                                                  const int64_t *__restrict__ start, const double *__restrict__ cam_tab,
                                                                  const double *__restrict__ pts_dlt, int64_t n_pts, const int32_t *__restrict__ order,
                                                                  int max_iter, double ftol, double xtol, double gtol,
                                                                  double *__restrict__ pts_out, double *__restrict__ rms_out, int32_t *__restrict__ info_out,
-                                                                 double *__restrict__ resid_out) {
+                                                                 double *__restrict__ resid_out, const Robust... robust) {
+    static_assert(is_robust_pack<Robust...>::ok, "the pack is empty (linear) or (GroupLoss, double *cost_out) (robust)");
+    constexpr bool ROBUST = sizeof...(Robust) != 0;
+    const GroupLoss loss = robust_loss(robust...);
+    double *const cost_out = robust_cost_out(robust...);
     const int64_t gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
     const int g = threadIdx.x & (G - 1);
     const bool live = gid < n_pts;   // whole groups are live or dead; a dead group never takes part in a pass
@@ -132,9 +164,10 @@ __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *
         }
     }
     // one pass: the group's sums at X (every lane of the group gets identical bits)
-    auto pass = [&](const double X0, const double X1, const double X2, double (&s)[TRI_REFINE_SUMS]) {
+    auto pass = [&](const double X0, const double X1, const double X2, double (&s)[TRI_REFINE_SUMS], double &raw) {
 #pragma unroll
         for (int k = 0; k < TRI_REFINE_SUMS; ++k) s[k] = 0.0;
+        if constexpr (ROBUST) raw = 0.0;
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             if (v >= nv_w) break;
@@ -142,7 +175,8 @@ __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *
                 double ru, rv, J[2][3];
                 bool front;
                 refine_view(cam_tab + (int64_t)cm[v] * TRI_CAM_STRIDE, m[v].x, m[v].y, X0, X1, X2, ru, rv, J, front);
-                refine_accumulate(s, ru, rv, J, front);
+                if constexpr (ROBUST) refine_accumulate_robust(s, raw, loss, ru, rv, J, front);
+                else refine_accumulate(s, ru, rv, J, front);
             }
         }
         for (int64_t q = s0 + g + (int64_t)V * G; q < s1; q += G) {   // views beyond the registers
@@ -150,21 +184,25 @@ __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *
             double ru, rv, J[2][3];
             bool front;
             refine_view(cam_tab + (int64_t)cam[q] * TRI_CAM_STRIDE, mq.x, mq.y, X0, X1, X2, ru, rv, J, front);
-            refine_accumulate(s, ru, rv, J, front);
+            if constexpr (ROBUST) refine_accumulate_robust(s, raw, loss, ru, rv, J, front);
+            else refine_accumulate(s, ru, rv, J, front);
         }
         if constexpr (G > 1) {
 #pragma unroll
             for (int k = 0; k < TRI_REFINE_SUMS; ++k) s[k] = group_sum<G>(s[k]);
+            if constexpr (ROBUST) raw = group_sum<G>(raw);
         }
     };
 
     double X[3] = {pts_dlt[3 * j + 0], pts_dlt[3 * j + 1], pts_dlt[3 * j + 2]};
     double H[6] = {0, 0, 0, 0, 0, 0}, gr[3] = {0, 0, 0}, cost = 0.0, cost_dlt = 0.0;
+    double raw = 0.0, raw_dlt = 0.0, raw_t = 0.0;   // ROBUST only: the plain sums of squares at the point, at the start and of a trial
     int status = TRI_REFINE_NOT_REFINED, it = 0;
     bool done = !live;
     if (live) {   // the start: cost, H and g at the DLT point
         double s[TRI_REFINE_SUMS];
-        pass(X[0], X[1], X[2], s);
+        pass(X[0], X[1], X[2], s, raw);
+        if constexpr (ROBUST) raw_dlt = raw;
 #pragma unroll
         for (int k = 0; k < 6; ++k) H[k] = s[k];
         gr[0] = s[6]; gr[1] = s[7]; gr[2] = s[8];
@@ -187,7 +225,7 @@ __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *
         if (trial) {
             const double T0 = X[0] + d[0], T1 = X[1] + d[1], T2 = X[2] + d[2];
             double s[TRI_REFINE_SUMS];
-            pass(T0, T1, T2, s);
+            pass(T0, T1, T2, s, raw_t);
             ++it;
             const double step = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
             const double size = sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
@@ -199,6 +237,7 @@ __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *
                 for (int k = 0; k < 6; ++k) H[k] = s[k];
                 gr[0] = s[6]; gr[1] = s[7]; gr[2] = s[8];
                 cost = s[9];
+                if constexpr (ROBUST) raw = raw_t;
                 lam = fmax(lam * 0.1, TRI_REFINE_LAMBDA_MIN);
                 if (flat || small) { status = TRI_REFINE_CONVERGED; done = true; }
             } else {
@@ -216,8 +255,13 @@ __global__ __launch_bounds__(256) void triangulate_refine_kernel(const int32_t *
         pts_out[3 * j + 0] = X[0];
         pts_out[3 * j + 1] = X[1];
         pts_out[3 * j + 2] = X[2];
-        rms_out[2 * j + 0] = sqrt(cost / n_v);
-        rms_out[2 * j + 1] = sqrt(cost_dlt / n_v);
+        rms_out[2 * j + 0] = sqrt((ROBUST ? raw : cost) / n_v);
+        rms_out[2 * j + 1] = sqrt((ROBUST ? raw_dlt : cost_dlt) / n_v);
+        if constexpr (ROBUST) {
+            // a point that was not refined has the cost of its unchanged start in both; without views NaN, like its RMS (0 / 0)
+            cost_out[2 * j + 0] = s1 > s0 ? 0.5 * cost : __builtin_nan("");
+            cost_out[2 * j + 1] = s1 > s0 ? 0.5 * cost_dlt : __builtin_nan("");
+        }
         info_out[3 * j + 0] = it;
         info_out[3 * j + 1] = status;
         info_out[3 * j + 2] = (int32_t)(s1 - s0);

@@ -471,6 +471,17 @@ __global__ __launch_bounds__(256) void tri_order_scatter_kernel(const int64_t *_
     order[pos] = (int32_t)j;
 }
 
+// The linear group-LM kernels (ba_tri_refine.hpp, ba_rigpose.hpp) write no cost: 0.5 sum r^2 = 0.5 n rms^2 from what they did write
+// (n from the start indices), so that pcs_rigpose_costs / pcs_tri_refine_costs answer after a linear run as well.  One thread per group.
+__global__ __launch_bounds__(256) void group_cost_from_rms_kernel(const double *__restrict__ rms, const int64_t *__restrict__ start, const int64_t n_groups,
+                                                                  double *__restrict__ cost_out) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_groups) return;
+    const double half_n = 0.5 * (double)(start[j + 1] - start[j]);
+    cost_out[2 * j + 0] = half_n * (rms[2 * j + 0] * rms[2 * j + 0]);
+    cost_out[2 * j + 1] = half_n * (rms[2 * j + 1] * rms[2 * j + 1]);
+}
+
 // ---- the grouping in front of the triangulation, on the device (round 5) ---------------------------------------------------------------------
 // CameraSet.multi_cam_triangulate (cameras/camera_set.py:371-378) finds, with two np.unique calls over the (image, key...) columns of the
 // detection table, the features seen by more than one camera, keeps their rows in table order and builds start_ind = cumulative counts

@@ -121,6 +121,29 @@ static int check_lm_options(const char *who, int max_iter, double ftol, double x
     return PCS_OK;
 }
 
+// The loss of a batched handle (pcs_rigpose_set_loss, pcs_tri_set_refine_loss): the checks of pcs_set_loss.  Nothing changes on a refusal.
+struct HandleLoss {
+    int kind = PCS_LOSS_LINEAR;
+    double f_scale = 1.0;
+    GroupLoss args() const { return {kind, 1.0 / f_scale, f_scale * f_scale}; }
+};
+
+static int set_handle_loss(const char *who, HandleLoss *l, int kind, double f_scale) {
+    if (!l) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (kind < PCS_LOSS_LINEAR || kind > PCS_LOSS_ARCTAN) return fail(PCS_ERR_ARG, "%s: kind %d not in [0, 4] (linear, huber, soft_l1, cauchy, arctan)", who, kind);
+    if (!std::isfinite(f_scale) || !(f_scale > 0.0)) return fail(PCS_ERR_ARG, "%s: f_scale must be finite and > 0 (got %g)", who, f_scale);
+    l->kind = kind;
+    l->f_scale = f_scale;
+    return PCS_OK;
+}
+
+static int get_handle_loss(const char *who, const HandleLoss *l, int *kind, double *f_scale) {
+    if (!l) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (kind) *kind = l->kind;
+    if (f_scale) *f_scale = l->f_scale;
+    return PCS_OK;
+}
+
 // The grouped table of a set_observations call: start_inds runs from 0 to n_obs and never decreases, and every observation's key lies
 // in [0, n_keys).  `group_ok(j)` checks the handle's own per-group columns (0, or the code of its refusal);
 // it runs in group order right behind group j's start index, so that the first bad GROUP decides the refusal, ahead of any bad key.
@@ -213,6 +236,29 @@ static int fetch_slots(const HandleCore &c, const OutSlot *sl, int n, int owned,
             HIPCHK(hipMemcpyAsync(sl[i].ptr, sl[i].buf.p, sl[i].elem_bytes * (size_t)sl[i].count, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
     return PCS_OK;
+}
+
+// The (n_groups, 2) costs of a run, always handle-owned.  A robust run writes them itself.  A LINEAR run stays what it was before the
+// handles knew a loss — no buffer, no launch: its costs are derived when they are asked for, 0.5 n rms^2 from the RMS the run wrote
+// (group_cost_from_rms_kernel), read where the run wrote it.
+struct LinearCosts {
+    const double *rms = nullptr;      // the (n_groups, 2) RMS of the last linear run: handle-owned or the caller's device buffer
+    const int64_t *start = nullptr;   // its start indices
+    bool pending = false;             // not derived yet
+};
+
+static int fetch_costs(const HandleCore &c, DevBuf &cost, LinearCosts &lin, double *host, int64_t n_groups, const char *who) {
+    if (lin.pending && n_groups) {
+        HIPCHK(hipSetDevice(c.device));
+        HIPCHK(c.fence.wait_host());   // the run first (it may be queued on a caller stream); growing frees, which needs the host to wait anyway
+        if (const int rc = cost.grow(n_groups, 2 * sizeof(double))) return rc;
+        hipLaunchKernelGGL(group_cost_from_rms_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, c.stream, lin.rms, lin.start, n_groups,
+                           cost.as<double>());
+        HIPCHK(hipGetLastError());
+        lin.pending = false;
+    }
+    const OutSlot out{1, cost, host, n_groups, 2 * sizeof(double)};
+    return fetch_slots(c, &out, 1, 1, n_groups != 0, who, "");   // copies on the same stream, behind the kernel
 }
 
 // The visiting order of n groups given by their start indices: groups of like size side by side, so that a wave does not mix small and

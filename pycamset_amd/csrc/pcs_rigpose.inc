@@ -15,6 +15,9 @@ struct pcs_rig_localiser {
     DevBuf order, hist;               // images by observation count (enqueue_group_order), built by the first run of a set of observations
     bool order_valid = false;
     DevBuf pose, rms, info, hess, res;   // handle-owned outputs
+    DevBuf cost;                         // (n_groups, 2) 0.5 sum rho0 at the pose and at the start of the last run: always handle-owned
+    LinearCosts lin;                     // a linear run derives them in pcs_rigpose_costs
+    HandleLoss loss;                     // pcs_rigpose_set_loss: the handle's, whatever cameras and observations follow
     int owned = 0;            // PCS_RIGPOSE_OUT_* bits: which outputs of the last run are handle-owned
     bool run_valid = false;   // a run since the inputs were last set
 };
@@ -44,7 +47,7 @@ int pcs_rigpose_create(pcs_rig_localiser **out, int device, int64_t n_cams, int6
 int pcs_rigpose_destroy(pcs_rig_localiser *p) {
     if (!p) return PCS_OK;
     p->core.destroy({&p->tab, &p->ext, &p->pts, &p->key, &p->cam, &p->uv, &p->start, &p->pose0, &p->order, &p->hist, &p->pose, &p->rms, &p->info, &p->hess,
-                     &p->res},
+                     &p->res, &p->cost},
                     {&p->timer});
     delete p;
     return PCS_OK;
@@ -138,16 +141,25 @@ static std::array<OutSlot, RIGPOSE_SLOTS> rigpose_out_slots(pcs_rig_localiser *p
 
 }  // extern "C"
 
+// PCS_LOSS_LINEAR launches the kernel a handle without a loss always launched; any other kind its robust twin, which writes the costs itself
 template <int G>
 static void rigpose_launch(pcs_rig_localiser *p, hipStream_t s, int max_iter, double ftol, double xtol, double gtol, int min_points, const OutSlot *out,
                            bool want_resid) {
     const int64_t ng = p->n_groups;
     const dim3 grid((unsigned)((ng * G + 255) / 256));
-    hipLaunchKernelGGL((rigpose_lm_kernel<G>), grid, dim3(256), 0, s, p->key.as<const int32_t>(), p->cam.as<const int32_t>(), p->uv.as<const double2>(),
-                       p->start.as<const int64_t>(), p->tab.as<const double>(), p->ext.as<const double>(), p->pts.as<const double>(), ng,
-                       p->order.as<const int32_t>(), p->pose0.as<const double>(), max_iter, ftol, xtol, gtol, min_points, out[RIGPOSE_SLOT_POSE].as<double>(),
-                       out[RIGPOSE_SLOT_RMS].as<double>(), out[RIGPOSE_SLOT_INFO].as<int32_t>(), out[RIGPOSE_SLOT_HESS].as<double>(),
-                       want_resid ? out[RIGPOSE_SLOT_RESID].as<double>() : nullptr);
+    if (p->loss.kind == PCS_LOSS_LINEAR)
+        hipLaunchKernelGGL((rigpose_lm_kernel<G>), grid, dim3(256), 0, s, p->key.as<const int32_t>(), p->cam.as<const int32_t>(),
+                           p->uv.as<const double2>(), p->start.as<const int64_t>(), p->tab.as<const double>(), p->ext.as<const double>(),
+                           p->pts.as<const double>(), ng, p->order.as<const int32_t>(), p->pose0.as<const double>(), max_iter, ftol, xtol, gtol, min_points,
+                           out[RIGPOSE_SLOT_POSE].as<double>(), out[RIGPOSE_SLOT_RMS].as<double>(), out[RIGPOSE_SLOT_INFO].as<int32_t>(),
+                           out[RIGPOSE_SLOT_HESS].as<double>(), want_resid ? out[RIGPOSE_SLOT_RESID].as<double>() : nullptr);
+    else
+        hipLaunchKernelGGL((rigpose_lm_kernel<G, GroupLoss, double *>), grid, dim3(256), 0, s, p->key.as<const int32_t>(), p->cam.as<const int32_t>(),
+                           p->uv.as<const double2>(), p->start.as<const int64_t>(), p->tab.as<const double>(), p->ext.as<const double>(),
+                           p->pts.as<const double>(), ng, p->order.as<const int32_t>(), p->pose0.as<const double>(), max_iter, ftol, xtol, gtol, min_points,
+                           out[RIGPOSE_SLOT_POSE].as<double>(), out[RIGPOSE_SLOT_RMS].as<double>(), out[RIGPOSE_SLOT_INFO].as<int32_t>(),
+                           out[RIGPOSE_SLOT_HESS].as<double>(), want_resid ? out[RIGPOSE_SLOT_RESID].as<double>() : nullptr, p->loss.args(),
+                           p->cost.as<double>());
 }
 
 extern "C" {
@@ -165,10 +177,12 @@ int pcs_rigpose_run(pcs_rig_localiser *p, int max_iter, double ftol, double xtol
     auto out = rigpose_out_slots(p, d_pose, d_rms, d_info, d_hess, d_resid);
     const int n_out = want_resid ? RIGPOSE_SLOTS : RIGPOSE_SLOTS - 1;
     const int64_t ng = p->n_groups;
-    bool grows = !p->order_valid && p->order.grows(ng);
+    const bool robust = p->loss.kind != PCS_LOSS_LINEAR;
+    bool grows = (!p->order_valid && p->order.grows(ng)) || (robust && p->cost.grows(ng));
     const int owned = owned_slots(out.data(), n_out, &grows);
     if (ng == 0) {
         p->owned = owned;
+        p->lin.pending = false;
         p->run_valid = true;
         p->timer.timed = false;   // nothing ran: no time of an earlier run is reported for this one
         return PCS_OK;
@@ -178,6 +192,7 @@ int pcs_rigpose_run(pcs_rig_localiser *p, int max_iter, double ftol, double xtol
     HIPCHK(p->core.fence.before_run(s, grows));   // outputs and the order are shared between runs
     int rc = grow_owned_slots(out.data(), n_out);
     if (!rc && !p->order_valid) rc = p->order.grow(ng, sizeof(int32_t));
+    if (!rc && robust) rc = p->cost.grow(ng, 2 * sizeof(double));
     if (rc) return rc;
     HIPCHK(hipEventRecord(p->timer.e0, s));   // after every allocation: nothing is queued by a call that fails in one
     if (!p->order_valid) {
@@ -189,6 +204,7 @@ int pcs_rigpose_run(pcs_rig_localiser *p, int max_iter, double ftol, double xtol
     else rigpose_launch<16>(p, s, max_iter, ftol, xtol, gtol, min_points, out.data(), want_resid);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(p->timer.e1, s));
+    p->lin = {out[RIGPOSE_SLOT_RMS].as<double>(), p->start.as<int64_t>(), !robust};
     p->timer.timed = true;
     p->owned = owned;
     p->run_valid = true;
@@ -202,6 +218,18 @@ int pcs_rigpose_results(pcs_rig_localiser *p, double *pose, double *rms, int32_t
     const auto out = rigpose_out_slots(p, pose, rms, info, hess, resid);
     return fetch_slots(p->core, out.data(), RIGPOSE_SLOTS, p->owned, p->n_groups != 0, "pcs_rigpose_results",
                        "the last run wrote some of these outputs to caller buffers (or computed no residuals)");
+}
+
+int pcs_rigpose_set_loss(pcs_rig_localiser *p, int kind, double f_scale) { return set_handle_loss("pcs_rigpose_set_loss", p ? &p->loss : nullptr, kind, f_scale); }
+
+int pcs_rigpose_get_loss(pcs_rig_localiser *p, int *kind, double *f_scale) {
+    return get_handle_loss("pcs_rigpose_get_loss", p ? &p->loss : nullptr, kind, f_scale);
+}
+
+int pcs_rigpose_costs(pcs_rig_localiser *p, double *cost) {
+    if (!p || !cost) return fail(PCS_ERR_ARG, "pcs_rigpose_costs: bad arguments");
+    if (!p->run_valid) return fail(PCS_ERR_STATE, "pcs_rigpose_costs: no run on the current inputs (pcs_rigpose_run first)");
+    return fetch_costs(p->core, p->cost, p->lin, cost, p->n_groups, "pcs_rigpose_costs");
 }
 
 int pcs_rigpose_last_kernel_ms(pcs_rig_localiser *p, float *kernel_ms) {

@@ -25,6 +25,9 @@ struct pcs_triangulator {
     bool run_valid = false;          // a run since the cameras / observations were last set
     const double *run_pts = nullptr; // where that run wrote its points (handle-owned or the caller's buffer)
     DevBuf rpts, rrms, rres, rinfo;  // handle-owned refinement outputs
+    DevBuf rcost;                    // (n_pts, 2) 0.5 sum rho0 at the point and at the DLT point of the last refinement: always handle-owned
+    LinearCosts rlin;                // a linear refinement derives them in pcs_tri_refine_costs
+    HandleLoss refine_loss;          // pcs_tri_set_refine_loss: the handle's, whatever cameras and observations follow
     int refine_owned = 0;            // PCS_TRI_OUT_* bits: which outputs of the last refinement are handle-owned
     bool refine_valid = false;       // a refinement since the last run (pcs_tri_refined has something to return)
 };
@@ -79,7 +82,7 @@ int pcs_tri_launch_config(pcs_triangulator *t, int32_t out[4]) {
 int pcs_tri_destroy(pcs_triangulator *t) {
     if (!t) return PCS_OK;
     t->core.destroy({&t->tab, &t->cam, &t->uv, &t->start, &t->scr, &t->scl, &t->pts, &t->count, &t->block_sums, &t->totals, &t->order, &t->hist, &t->rpts,
-                     &t->rrms, &t->rres, &t->rinfo},
+                     &t->rrms, &t->rres, &t->rinfo, &t->rcost},
                     {&t->timer, &t->refine_timer});
     delete t;
     return PCS_OK;
@@ -276,9 +279,11 @@ int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, 
     const bool want_resid = flags & PCS_TRI_REFINE_RESIDUALS;
     auto out = tri_out_slots(t, d_pts, d_rms, d_info, d_resid);
     const int n_out = want_resid ? TRI_SLOTS : TRI_SLOTS - 1;
-    bool grows = false;
+    const bool robust = t->refine_loss.kind != PCS_LOSS_LINEAR;
+    bool grows = robust && t->rcost.grows(t->n_pts);
     const int owned = owned_slots(out.data(), n_out, &grows);
     if (t->n_pts == 0) {
+        t->rlin.pending = false;
         t->refine_owned = owned;
         t->refine_valid = true;
         return PCS_OK;
@@ -287,13 +292,25 @@ int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, 
     hipStream_t s = t->core.stream_or(stream);
     HIPCHK(t->core.fence.before_run(s, grows));   // the run (or an earlier refinement) first: this reads its points and shares the outputs
     if (const int rc = grow_owned_slots(out.data(), n_out)) return rc;
+    if (robust)
+        if (const int rc = t->rcost.grow(t->n_pts, 2 * sizeof(double))) return rc;
     constexpr int G = 4, V = 6;   // the DLT kernel's default geometry (profiles/r09: resources and time)
     const dim3 grid((unsigned)((t->n_pts * G + 255) / 256));
-    hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->refine_timer.e0, t->refine_timer.e1, 0, t->cur_cam,
-                          (const double2 *)t->cur_uv, t->cur_start, t->tab.as<const double>(), t->run_pts, t->n_pts,
-                          t->order_valid ? t->order.as<const int32_t>() : nullptr, max_iter, ftol, xtol, gtol, out[TRI_SLOT_POINTS].as<double>(),
-                          out[TRI_SLOT_RMS].as<double>(), out[TRI_SLOT_INFO].as<int32_t>(), want_resid ? out[TRI_SLOT_RESID].as<double>() : nullptr);
+    // PCS_LOSS_LINEAR launches the kernel a handle without a loss always launched; any other kind its robust twin, which writes the costs itself
+    if (!robust) {
+        hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->refine_timer.e0, t->refine_timer.e1, 0, t->cur_cam,
+                              (const double2 *)t->cur_uv, t->cur_start, t->tab.as<const double>(), t->run_pts, t->n_pts,
+                              t->order_valid ? t->order.as<const int32_t>() : nullptr, max_iter, ftol, xtol, gtol, out[TRI_SLOT_POINTS].as<double>(),
+                              out[TRI_SLOT_RMS].as<double>(), out[TRI_SLOT_INFO].as<int32_t>(), want_resid ? out[TRI_SLOT_RESID].as<double>() : nullptr);
+    } else {
+        hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V, GroupLoss, double *>), grid, dim3(256), 0, s, t->refine_timer.e0, t->refine_timer.e1, 0, t->cur_cam,
+                              (const double2 *)t->cur_uv, t->cur_start, t->tab.as<const double>(), t->run_pts, t->n_pts,
+                              t->order_valid ? t->order.as<const int32_t>() : nullptr, max_iter, ftol, xtol, gtol, out[TRI_SLOT_POINTS].as<double>(),
+                              out[TRI_SLOT_RMS].as<double>(), out[TRI_SLOT_INFO].as<int32_t>(), want_resid ? out[TRI_SLOT_RESID].as<double>() : nullptr,
+                              t->refine_loss.args(), t->rcost.as<double>());
+    }
     HIPCHK(hipGetLastError());
+    t->rlin = {out[TRI_SLOT_RMS].as<double>(), t->cur_start, !robust};
     t->refine_timer.timed = true;
     t->refine_owned = owned;
     t->refine_valid = true;
@@ -307,6 +324,20 @@ int pcs_tri_refined(pcs_triangulator *t, double *pts, double *rms, int32_t *info
     const auto out = tri_out_slots(t, pts, rms, info, resid);
     return fetch_slots(t->core, out.data(), TRI_SLOTS, t->refine_owned, t->n_pts != 0, "pcs_tri_refined",
                        "the last refinement wrote some of these outputs to caller buffers (or computed no residuals)");
+}
+
+int pcs_tri_set_refine_loss(pcs_triangulator *t, int kind, double f_scale) {
+    return set_handle_loss("pcs_tri_set_refine_loss", t ? &t->refine_loss : nullptr, kind, f_scale);
+}
+
+int pcs_tri_get_refine_loss(pcs_triangulator *t, int *kind, double *f_scale) {
+    return get_handle_loss("pcs_tri_get_refine_loss", t ? &t->refine_loss : nullptr, kind, f_scale);
+}
+
+int pcs_tri_refine_costs(pcs_triangulator *t, double *cost) {
+    if (!t || !cost) return fail(PCS_ERR_ARG, "pcs_tri_refine_costs: bad arguments");
+    if (!t->refine_valid) return fail(PCS_ERR_STATE, "pcs_tri_refine_costs: no refinement since the last run (pcs_tri_refine first)");
+    return fetch_costs(t->core, t->rcost, t->rlin, cost, t->n_pts, "pcs_tri_refine_costs");
 }
 
 int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms) {

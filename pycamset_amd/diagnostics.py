@@ -40,6 +40,29 @@ def mad_outliers(values, out_thresh: float = 3):
     return found if found.size else None
 
 
+def robust_weights(residuals, loss: str = "linear", f_scale: float = 1.0) -> np.ndarray:
+    """rho'(z), z = (f / f_scale)^2, per scalar residual f: the weight a robust loss of ``lm_solve``, ``localise_target`` or
+    ``refine_triangulation`` gives that residual in J' rho1 f (1 = full weight; scipy ``least_squares``'s rho[1]).  Same shape as
+    ``residuals``; NaN stays NaN.  Thresholding it (say < 0.5) lists the detections a solve down-weighted."""
+    from .compiled_helpers import check_loss
+
+    loss, f_scale = check_loss(loss, f_scale)
+    f = np.asarray(residuals, dtype=np.float64)
+    z = (f / f_scale) ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if loss == "huber":
+            w = np.where(z <= 1.0, 1.0, 1.0 / np.sqrt(z))
+        elif loss == "soft_l1":
+            w = 1.0 / np.sqrt(1.0 + z)
+        elif loss == "cauchy":
+            w = 1.0 / (1.0 + z)
+        elif loss == "arctan":
+            w = 1.0 / (1.0 + z * z)
+        else:
+            w = np.ones_like(z)
+    return np.where(np.isnan(f), np.nan, w)
+
+
 @dataclass
 class GroupStats:
     """The statistics of one grouping, one entry per group (``per_view``: shaped (C, I)).  ``count``: detections with a finite error;

@@ -36,7 +36,7 @@ def _table(detection_or_dct, points):
 def find_target_poses(detection_or_dct, points, intr, ext, **opts) -> ch.ImagePoses:
     """The target pose of every image (ft:50-82) -> ``compiled_helpers.ImagePoses``; ``opts`` are ``localise_target``'s
     (``n_imgs``, ``poses_init``, ``min_points``, ``max_iter``, ``ftol``, ``xtol``, ``gtol``, ``group_lanes``, ``return_residuals``,
-    ``device``)."""
+    ``device``, and ``loss`` / ``f_scale``: the robust loss the reference's ``least_squares`` call carries commented out)."""
     d, pts, stated = _table(detection_or_dct, points)
     if stated is not None:
         opts.setdefault("n_imgs", stated)
@@ -45,7 +45,8 @@ def find_target_poses(detection_or_dct, points, intr, ext, **opts) -> ch.ImagePo
 
 def find_target_pose_at_timestep(detection_or_dct, points, intr, ext, im_num: int = 0, **opts):
     """The target pose of ONE image (ft:9-47: the detections of a single time step) -> (pose (6,), rms, status).  ``im_num`` selects the
-    image of the table (the reference files every detection under image 0, ft:29); ``poses_init``, if given, is the (6,) start."""
+    image of the table (the reference files every detection under image 0, ft:29); ``poses_init``, if given, is the (6,) start;
+    ``loss`` / ``f_scale`` as in ``find_target_poses``."""
     if isinstance(im_num, bool) or not isinstance(im_num, (int, np.integer)) or im_num < 0:
         raise ValueError(f"im_num must be an integer >= 0, got {im_num!r}")
     if "n_imgs" in opts:

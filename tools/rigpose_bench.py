@@ -2,13 +2,15 @@
 """Times the per-image target pose in a calibrated rig (compiled_helpers.RigLocaliser, include/pcs_hip.h pcs_rigpose_run) at both group
 widths, and the only other way to the same answer: device_solver.lm_solve through a handler with every camera in ``fixed_params``.
 
-    python tools/rigpose_bench.py --shape tracking|rig32|sweep:CAMS:VIS [--images N] [--reps 7] [--joint] [--seed-eval] [--out FILE]
+    python tools/rigpose_bench.py --shape tracking|rig32|sweep:CAMS:VIS [--images N] [--reps 7] [--loss KIND] [--f-scale F] [--joint] [--seed-eval]
+                                  [--out FILE]
 
 tracking: 8 cameras x 1e5 images of the 25-point board at visibility 0.2 (~40 detections per image); rig32: BASELINE config 3
 (32 cameras x 200 images, ~5 000 detections per image); sweep:CAMS:VIS: CAMS cameras x 2 000 images of the 96-point cube at visibility VIS
 (96 CAMS VIS detections per image), the shapes between the two that place the width rule's threshold.  Kernel time is the handle's event pair (``last_kernel_ms``: ordering of the
 images + the LM kernel); host time is a host clock around run() + results(), which ends in a device synchronise.  The widths are
-timed alternately after two warm-up calls each; median, minimum and maximum of ``--reps`` calls are printed as one JSON line per case."""
+timed alternately after two warm-up calls each; median, minimum and maximum of ``--reps`` calls are printed as one JSON line per case.
+``--loss`` runs the robust instantiation of the kernel (RigLocaliser.set_loss; linear, the default, is the kernel without a loss)."""
 import argparse
 import json
 import statistics
@@ -58,6 +60,8 @@ def main():
     ap.add_argument("--shape", required=True, help="tracking, rig32 or sweep:CAMS:VIS")
     ap.add_argument("--images", type=int, default=0)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--loss", default="linear", help="linear (default), huber, soft_l1, cauchy or arctan")
+    ap.add_argument("--f-scale", type=float, default=1.0)
     ap.add_argument("--joint", action="store_true", help="also time lm_solve with every camera fixed on the same table")
     ap.add_argument("--seed-eval", action="store_true", help="LM evaluations of the joint solve from a seed with and without refine_poses")
     ap.add_argument("--out", default="")
@@ -80,6 +84,8 @@ def main():
     loc.set_cameras(rig.intr_true)
     loc.set_extrinsics(E)
     loc.set_template(rig.points)
+    if a.loss != "linear":   # a library without the robust kernels still runs the linear case
+        loc.set_loss(a.loss, a.f_scale)
     t0 = time.perf_counter()
     loc.set_observations(ds[:, 2].astype(np.int32), ds[:, 0].astype(np.int32), ds[:, 3:5], first)
     loc.set_start(start[ids])
@@ -98,7 +104,7 @@ def main():
     for lanes in (16, 64):
         pose, rms, info, hess, _ = out[lanes]
         cost = float(np.nansum(rms[:, 0] ** 2 * info[:, 2]))
-        emit(case="localise", shape=a.shape, lanes=lanes, kernel_ms=summary(kernel[lanes]), host_ms=summary(host[lanes]), sum_r2=cost,
+        emit(case="localise", shape=a.shape, lanes=lanes, loss=a.loss, f_scale=a.f_scale, kernel_ms=summary(kernel[lanes]), host_ms=summary(host[lanes]), sum_r2=cost,
              sum_r2_start=float(np.nansum(rms[:, 1] ** 2 * info[:, 2])), trials_mean=float(info[:, 0].mean()), trials_max=int(info[:, 0].max()),
              status_counts=np.bincount(info[:, 1], minlength=4).tolist())
     d = np.abs(out[16][0] - out[64][0])

@@ -2,7 +2,8 @@
 """Triangulation refinement (pcs_tri_refine) at config 3 (the rig of tools/tri_bench.py): DLT alone against DLT + refinement as
 device-event kernel times, the iteration histogram, RMS before and after, and the work the refinement did (view evaluations).
 
-    python tools/tri_refine_bench.py [--reps 20] [--residuals]
+    python tools/tri_refine_bench.py [--reps 20] [--residuals] [--loss KIND] [--f-scale F]
+``--loss`` runs the robust instantiation of the refinement kernel (Triangulator.set_refine_loss; linear, the default, is the kernel without a loss).
 Kernel times from rocprofv3 in a separate run:
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o tri_refine -- python tools/tri_refine_bench.py --reps 5
 """
@@ -19,6 +20,8 @@ from pycamset_amd import compiled_helpers as hc  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--residuals", action="store_true", help="also write the per-observation residuals")
+ap.add_argument("--loss", default="linear", help="linear (default), huber, soft_l1, cauchy or arctan")
+ap.add_argument("--f-scale", type=float, default=1.0)
 args = ap.parse_args()
 
 rig = synthetic.config_rig(3)
@@ -37,6 +40,8 @@ print(f"config 3: {n_obs} observations, {n_pts} points, views/point {views.min()
 tri = hc.Triangulator(rig.n_cams)
 tri.set_cameras(P, Kc, D)
 tri.set_observations(rec[:, 0].astype(np.int32), rec[:, -2:], start)
+if args.loss != "linear":   # a library without the robust kernel still runs the linear case
+    tri.set_refine_loss(args.loss, args.f_scale)
 for _ in range(3):   # warm-up: code objects, visiting order, buffers
     tri.run(); tri.refine(residuals=args.residuals); tri.refined()
 dlt_alone, dlt, ref = [], [], []
@@ -48,7 +53,8 @@ for _ in range(args.reps):   # DLT + refinement, back to back on the handle's st
 res = tri.refined()
 med = lambda x: float(np.median(x)) * 1e3   # noqa: E731  (us)
 print(f"device events, median of {args.reps}:  DLT alone {med(dlt_alone):7.1f} us   |   DLT {med(dlt):7.1f} us + refinement {med(ref):7.1f} us "
-      f"= {med(dlt) + med(ref):7.1f} us   (refinement / DLT = {np.median(ref) / np.median(dlt):.2f}){'  [with residuals]' if args.residuals else ''}")
+      f"= {med(dlt) + med(ref):7.1f} us   (refinement / DLT = {np.median(ref) / np.median(dlt):.2f}){'  [with residuals]' if args.residuals else ''}"
+      f"  [loss {args.loss}, f_scale {args.f_scale:g}; refinement min {min(ref) * 1e3:.1f} max {max(ref) * 1e3:.1f} us]")
 
 its = res.iterations
 hist = np.bincount(its, minlength=hc.REFINE_DEFAULTS["max_iter"] + 1)
@@ -56,7 +62,7 @@ print("iterations (LM trials) histogram: " + "  ".join(f"{k}:{v}" for k, v in en
 names = {hc.TRI_NOT_REFINED: "not refined", hc.TRI_CONVERGED: "converged", hc.TRI_MAX_ITER: "max_iter", hc.TRI_NO_DECREASE: "no decrease"}
 print("status: " + "  ".join(f"{names[k]}:{v}" for k, v in enumerate(np.bincount(res.status, minlength=4)) if v))
 print(f"RMS reprojection error [px]: DLT mean {res.rms_dlt.mean():.6f} median {np.median(res.rms_dlt):.6f}  ->  refined mean {res.rms.mean():.6f} "
-      f"median {np.median(res.rms):.6f};  never worse: {bool(np.all(res.rms <= res.rms_dlt))}")
+      f"median {np.median(res.rms):.6f};  never worse: {bool(np.all(res.rms <= res.rms_dlt))}" + (" (the plain RMS may rise under a loss)" if args.loss != "linear" else ""))
 print(f"point moved by the refinement [m]: median {np.median(np.linalg.norm(res.points - res.points_dlt, axis=1)):.3e}, "
       f"max {np.max(np.linalg.norm(res.points - res.points_dlt, axis=1)):.3e}")
 # work: one pass over a point's views at the start and one per trial
