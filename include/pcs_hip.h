@@ -202,7 +202,8 @@ int pcs_normal_blocks_device(pcs_engine *h, const double *d_param_str, double *d
  *                      on a rejected or failed step), *d_status <- 0, and d_stats[12] = {accepted (-1: bit 2 of *d_status was set — the dense solve
  *                      did not complete, the trial is void), max |g|, relative cost drop, |step|,
  *                      |x| over the free parameters, new sum r^2, old sum r^2, lambda used, 0, 0, 0, the next lambda} — the one vector the host reads per trial
- *                      ([8] .. [10] are the stop code, the trial number and the current state of the device-steered loop, pcs_lm_trial). */
+ *                      ([8] .. [10] are the stop code, the trial number and the current state of the device-steered loop, pcs_lm_trial).
+ *                      With a prior (pcs_set_prior) added to both states, "sum r^2" in [5] and [6] is the augmented sum, prior term included. */
 int pcs_schur_prepare(pcs_engine *h, double *d_packed, const uint8_t *d_fixed, const double *d_lambda, double *d_linvt, double *d_u,
                       double *d_V, double *d_S, double *d_rhs, double *d_dvec, double *d_gm, int32_t *d_status, void *stream);
 int pcs_schur_finish(pcs_engine *h, const double *d_linvt, const double *d_u, const double *d_w, const double *d_xlead, const uint8_t *d_fixed,
@@ -432,6 +433,13 @@ int pcs_genchain_normal_layout(const pcs_genchain *h, int64_t *out5);
 int pcs_genchain_normal_blocks_device(pcs_genchain *h, const double *d_param_str, double *d_packed, void *stream);
 int pcs_genchain_lm_trial_build(pcs_genchain *h, const pcs_lm_buffers *b, void *stream);
 int pcs_genchain_lm_trial_finish(pcs_genchain *h, const pcs_lm_buffers *b, void *stream);
+/* The Gaussian parameter prior of a generated chain (since pcs_version() 114): pcs_set_prior / pcs_get_prior / pcs_prior_add_device with
+ * the same rules, the same store and the same kernels.  The packed state is the one pcs_genchain_normal_layout describes at the time of
+ * the call, so a change of option "dense_normal" is followed (dense: the diagonal entry of every parameter is A[i, i]).
+ * pcs_genchain_normal_blocks_device stays the raw sum over the detections; pcs_genchain_lm_trial_finish adds the prior to the trial state. */
+int pcs_genchain_set_prior(pcs_genchain *h, const double *mean, const double *inv_sigma, int64_t n);
+int pcs_genchain_get_prior(pcs_genchain *h, double *mean, double *inv_sigma, int64_t capacity, int64_t *n);
+int pcs_genchain_prior_add_device(pcs_genchain *h, const double *d_param_str, double *d_packed, void *stream);
 int pcs_genchain_lm_trial(pcs_genchain *h, const pcs_lm_buffers *b, void *stream);
 int pcs_genchain_set_option(pcs_genchain *h, const char *key, int64_t value);
 /* The pieces of a trial as calls of their own — pcs_schur_prepare / pcs_schur_finish / pcs_lm_decide for the handle's layout — for a
@@ -519,6 +527,35 @@ int pcs_set_weights(pcs_engine *h, const double *inv_sigma, int64_t n);
 /* The current weights: *n = their number (0 = none set); up to `capacity` of them are copied to inv_sigma.  inv_sigma or n may be NULL
  * (not both): pcs_get_weights(h, NULL, 0, &n) is the "are weights set" query.  PCS_ERR_ARG for a NULL handle or a negative capacity. */
 int pcs_get_weights(pcs_engine *h, double *inv_sigma, int64_t capacity, int64_t *n);
+/* Gaussian parameter prior of the engine's LM solve (since pcs_version() 114): what is known about a parameter, "about mean[i], give or
+ * take sigma_i", over the parameter string p.  With w_i = inv_sigma[i] = 1 / sigma_i the objective becomes
+ *     Phi(p) = sum over the detection rows of rho(...)  +  sum_i (w_i (p_i - mean[i]))^2 ,
+ * the first sum being what the build computes (pcs_set_loss and pcs_set_weights included); the prior rows never pass through the loss
+ * and are never whitened by the detections' sigma — scipy's extra rows (x - mu) / sigma, a Ceres prior block.  In a packed state
+ * [A | B | C | g | cost] the diagonal entry of parameter i (A[i, i] of a leading column, the diagonal of its entity's C block for a
+ * trailing one) gains w_i^2, g_i gains w_i^2 (p_i - mean[i]) and the cost word gains the sum; Marquardt scaling, the damped step, the
+ * predicted reduction and gain ratio, gtol, ftol and the covariance all read those three places.
+ *   pcs_set_prior   n must equal pcs_n_params; inv_sigma[i] finite and >= 0, 0 = no prior on that entry; mean[i] finite where
+ *                   inv_sigma[i] > 0.  inv_sigma = NULL clears the prior.  PCS_ERR_ARG if not, and for a NULL handle; a refused call leaves
+ *                   the previous prior in force.  The values are copied; only entries with inv_sigma > 0 cost device memory or time.
+ *                   The prior belongs to the HANDLE: pcs_set_detections* keeps it.
+ *   pcs_get_prior   *n = pcs_n_params when a prior is set, else 0; up to `capacity` values each go to mean and inv_sigma (any of the
+ *                   three may be NULL, not all).
+ *   pcs_prior_add_device   adds the prior at d_param_str to d_packed, a packed state of the handle's layout (pcs_normal_layout) built at
+ *                   that string; asynchronous on `stream`.  No prior set: nothing is queued.
+ * The RAW builds do NOT include the prior: pcs_normal_equations*, pcs_normal_blocks_device, pcs_eval* and pcs_matfree stay the sums over
+ * the detections — they are what a loop over observation shards all-reduces, and the prior must enter ONCE, behind that sum.  It is
+ * added by pcs_prior_add_device (the first state of a loop, after the all-reduce) and by pcs_lm_trial_finish, which — when a prior is
+ * set — adds it to the trial state at the trial string in front of the decision, following flags[2] / PCS_LM_FIXED_TRIAL_BUFFER as the
+ * decision does and behind the stop word like every kernel of a trial.  Every rank adds the same bits: no rank is special.  The stats
+ * words [5] and [6] of a trial ("new / old sum r^2") are then the augmented sums.
+ * The kernels (csrc/ba_prior.hpp) use plain adds — every destination has one writer — and sum the cost term in a fixed order in BOTH
+ * contraction modes: option "deterministic" keeps its same-bits guarantee.  Up to 1 024 entries: one launch of one workgroup; more:
+ * one launch of ceil(n / 1 024) workgroups and a one-workgroup launch that adds their partial sums in workgroup order.
+ * Without a prior every entry point queues the launches it queued before and computes the same bits. */
+int pcs_set_prior(pcs_engine *h, const double *mean, const double *inv_sigma, int64_t n);
+int pcs_get_prior(pcs_engine *h, double *mean, double *inv_sigma, int64_t capacity, int64_t *n);
+int pcs_prior_add_device(pcs_engine *h, const double *d_param_str, double *d_packed, void *stream);
 /*
  * Batched n-view triangulation.
  * Replaces: nb_triangulate_full (compiled_helpers.py:609-643) = per point nb_undistort (ch:409-431) +

@@ -208,6 +208,12 @@ SYMBOLS = {
     "pcs_get_loss": (c_int, [_P, POINTER(c_int), POINTER(c_double)]),
     "pcs_set_weights": (c_int, [_P, POINTER(c_double), c_int64]),
     "pcs_get_weights": (c_int, [_P, POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_set_prior": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64]),
+    "pcs_get_prior": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_prior_add_device": (c_int, [_P, _P, _P, _P]),
+    "pcs_genchain_set_prior": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64]),
+    "pcs_genchain_get_prior": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_genchain_prior_add_device": (c_int, [_P, _P, _P, _P]),
     "pcs_device_buffers": (c_int, [_P, POINTER(_P), POINTER(_P)]),
 }
 

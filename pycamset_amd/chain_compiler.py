@@ -751,6 +751,27 @@ class ChainEngine:
         check(lib().pcs_genchain_lm_decide(self._h, *(c_void_p(p) for p in (d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed, d_status, d_lambda, d_stats)),
                                            _stream_arg(stream)))
 
+    # -- the Gaussian parameter prior (include/pcs_hip.h pcs_genchain_set_prior): Engine's three methods on this handle kind ------------
+    _PRIOR_PREFIX = "pcs_genchain_"
+
+    def _prior_fn(self, name: str):
+        return getattr(lib(), self._PRIOR_PREFIX + name)
+
+    def set_prior(self, mean=None, sigma=None, *, inv_sigma=None):
+        from .engine import Engine
+
+        return Engine.set_prior(self, mean, sigma, inv_sigma=inv_sigma)
+
+    def prior(self):
+        from .engine import Engine
+
+        return Engine.prior(self)
+
+    def prior_add_device(self, d_param_str: int, d_packed: int, stream: int | None = None):
+        from .engine import Engine
+
+        return Engine.prior_add_device(self, d_param_str, d_packed, stream)
+
     def set_option(self, key: str, value: int):
         """Engine's option interface as far as the LM driver uses it: "spd_timeout_us", "timing" and "deterministic" (the ORDERED
         contraction of csrc/ba_blockgram.hpp: every sum in a fixed order, the same bits on every run) reach the handle; "timing_every"

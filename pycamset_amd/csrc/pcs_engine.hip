@@ -33,6 +33,7 @@
 #include "ba_reduce.hpp"
 #include "ba_schur.hpp"
 #include "ba_lm_fused.hpp"
+#include "ba_prior.hpp"
 #include "ba_dense_chol.hpp"
 #include "ba_chol_persist.hpp"
 #include "ba_covariance.hpp"
@@ -92,6 +93,7 @@ struct pcs_engine {
     bool lazy_any_stream = false;   // "lazy_done_event" = 2: also on caller streams (the caller keeps the stream alive until it resets the option)
     // static inputs
     DetStore det;                      // the detection table (pcs_dettable.inc); det.n = number of detections
+    PriorStore prior;                  // the Gaussian parameter prior (pcs_set_prior); the handle's, not the table's
     bool pack_indices = true;          // option "pack_indices" (A/B switch; takes effect at the next upload)
     DevBuf d_order;              // (cam, image)-sorted visiting order of a scattered table (normal equations), or empty
     DevBuf d_order_ck, d_order_ik;   // (cam, key) / (image, key) orders for the point passes
@@ -334,6 +336,7 @@ int pcs_destroy(pcs_engine *h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     release_table(h);   // what belongs to the detection table; then the buffers that outlive a table
+    h->prior.release();
     for (DevBuf *b : {&h->d_param, &h->d_cam_slab, &h->d_pose_slab, &h->d_points, &h->d_sink, &h->d_vin, &h->d_vout, &h->d_cost, &h->d_H, &h->d_im_points, &h->d_cam_tab})
         b->release();
     if (h->h_param) (void)hipHostFree(h->h_param);
@@ -545,6 +548,23 @@ int pcs_get_weights(pcs_engine *h, double *inv_sigma, int64_t capacity, int64_t 
         HIPCHK(hipMemcpy(inv_sigma, h->det.w.p, sizeof(double) * m, hipMemcpyDeviceToHost));
     }
     return PCS_OK;
+}
+
+int pcs_set_prior(pcs_engine *h, const double *mean, const double *inv_sigma, int64_t n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_set_prior: bad arguments");
+    if (const int rc = PriorStore::check("pcs_set_prior", mean, inv_sigma, n, h->n_params)) return rc;
+    if (!inv_sigma && h->prior.h_w.empty()) return PCS_OK;   // nothing set, nothing to clear: no device call
+    HIPCHK(hipSetDevice(h->device));
+    if (h->prior.set_writes_device(inv_sigma)) {   // a trial's finish half that reads the old lists may be queued on any stream
+        HIPCHK(wait_done_host(h));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return h->prior.set(mean, inv_sigma, h->n_params);
+}
+
+int pcs_get_prior(pcs_engine *h, double *mean, double *inv_sigma, int64_t capacity, int64_t *n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_get_prior: bad arguments");
+    return h->prior.get("pcs_get_prior", mean, inv_sigma, capacity, n);
 }
 
 }  // extern "C"
@@ -1526,6 +1546,11 @@ int pcs_normal_blocks_device(pcs_engine *h, const double *d_param_str, double *d
     return enqueue_normal(h, d_param_str, d_packed, d_g, d_g + h->n_params, s, true);
 }
 
+int pcs_prior_add_device(pcs_engine *h, const double *d_param_str, double *d_packed, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_prior_add_device: bad arguments");
+    return prior_add_piece("pcs_prior_add_device", h->device, h->prior, block_layout(h), h->n_params, d_param_str, d_packed, stream ? (hipStream_t)stream : h->stream);
+}
+
 // The pieces of a trial for a loop the host steers (pcs_solver.inc: schur_prepare_piece, schur_finish_piece, lm_decide_piece).
 int pcs_schur_prepare(pcs_engine *h, double *d_packed, const uint8_t *d_fixed, const double *d_lambda, double *d_linvt, double *d_u,
                       double *d_V, double *d_S, double *d_rhs, double *d_dvec, double *d_gm, int32_t *d_status, void *stream) {
@@ -1569,7 +1594,7 @@ int pcs_lm_trial_finish(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
     const int rc = lm_check(h, b, "pcs_lm_trial_finish");
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    return enqueue_lm_finish(h->n_cu, h->n_params, block_layout(h).packed_len(h->n_params), b, stream ? (hipStream_t)stream : h->stream);
+    return enqueue_lm_finish(h->n_cu, h->n_params, block_layout(h), h->prior, b, stream ? (hipStream_t)stream : h->stream);
 }
 
 int pcs_lm_trial(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {

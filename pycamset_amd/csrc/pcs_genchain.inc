@@ -30,6 +30,7 @@ struct pcs_genchain {
     DevBuf d_param, d_tmpl, d_slab[GENERIC_MAX_GROUPS];
     DevBuf d_sink;
     DetStore det;                   // the detection table (pcs_dettable.inc); det.n = number of detections
+    PriorStore prior;               // the Gaussian parameter prior (pcs_genchain_set_prior); the handle's, not the table's
     bool have_template = false;
     DevBuf d_resid, d_jac, d_data;
     DevBuf d_keep;      // per detection, uint64: bit j set = local column j is free
@@ -82,6 +83,7 @@ int pcs_genchain_destroy(pcs_genchain *h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->det.release();
+    h->prior.release();
     for (DevBuf *b : {&h->d_param, &h->d_tmpl, &h->d_sink, &h->d_resid, &h->d_jac, &h->d_data, &h->d_keep, &h->d_row_off, &h->d_vin, &h->d_vout, &h->d_gram_ws}) b->release();
     for (DevBuf &b : h->d_slab) b.release();
     for (DevBuf &b : h->d_blk_map) b.release();
@@ -719,6 +721,27 @@ int pcs_genchain_normal_blocks_device(pcs_genchain *h, const double *d_param_str
     return genchain_enqueue_normal(h, d_param_str, d_packed, stream ? (hipStream_t)stream : h->stream, nullptr);
 }
 
+// The prior of a generated chain: pcs_set_prior / pcs_get_prior / pcs_prior_add_device for this handle kind (the same store, the same kernels;
+// the layout is genchain_layout, so a change of "dense_normal" is followed).
+int pcs_genchain_set_prior(pcs_genchain *h, const double *mean, const double *inv_sigma, int64_t n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_set_prior: bad arguments");
+    if (const int rc = PriorStore::check("pcs_genchain_set_prior", mean, inv_sigma, n, h->n_params)) return rc;
+    if (!inv_sigma && h->prior.h_w.empty()) return PCS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (h->prior.set_writes_device(inv_sigma)) HIPCHK(hipDeviceSynchronize());   // a trial's finish half that reads the old lists may be queued on any stream
+    return h->prior.set(mean, inv_sigma, h->n_params);
+}
+
+int pcs_genchain_get_prior(pcs_genchain *h, double *mean, double *inv_sigma, int64_t capacity, int64_t *n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_get_prior: bad arguments");
+    return h->prior.get("pcs_genchain_get_prior", mean, inv_sigma, capacity, n);
+}
+
+int pcs_genchain_prior_add_device(pcs_genchain *h, const double *d_param_str, double *d_packed, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_prior_add_device: bad arguments");
+    return prior_add_piece("pcs_genchain_prior_add_device", h->device, h->prior, genchain_layout(h), h->n_params, d_param_str, d_packed, stream ? (hipStream_t)stream : h->stream);
+}
+
 // One Levenberg-Marquardt trial of a generated chain in two halves, like pcs_lm_trial_build / pcs_lm_trial_finish (same buffers, same
 // shared build — pcs_solver.inc enqueue_lm_trial_build —, same decision kernel, same read-back).  The generated evaluation kernel reads its
 // parameter string from a fixed address, so the trial is always built at ps[1] into packed[1] and an accepted one is copied over state 0:
@@ -761,7 +784,7 @@ int pcs_genchain_lm_trial_finish(pcs_genchain *h, const pcs_lm_buffers *b, void 
     if (rc) return rc;
     if (!(b->mode & PCS_LM_FIXED_TRIAL_BUFFER)) return fail(PCS_ERR_ARG, "pcs_genchain_lm_trial_finish: mode must hold PCS_LM_FIXED_TRIAL_BUFFER");
     HIPCHK(hipSetDevice(h->device));
-    return enqueue_lm_finish(h->n_cu, h->n_params, genchain_layout(h).packed_len(h->n_params), b, stream ? (hipStream_t)stream : h->stream);
+    return enqueue_lm_finish(h->n_cu, h->n_params, genchain_layout(h), h->prior, b, stream ? (hipStream_t)stream : h->stream);
 }
 
 int pcs_genchain_lm_trial(pcs_genchain *h, const pcs_lm_buffers *b, void *stream) {

@@ -27,6 +27,80 @@ struct DevBuf {
     }
 };
 
+// The Gaussian parameter prior of an engine handle (pcs_set_prior / pcs_genchain_set_prior; kernels: csrc/ba_prior.hpp): the entries with
+// weight > 0 only — index into the parameter string, mean, 1 / sigma — on the device, so that a prior on a few intrinsics of a
+// million-point problem costs nothing per point; plus the partial cost sums of a list longer than one workgroup's share.  It belongs to
+// the HANDLE, not to its detection table: a new table keeps it.  The host keeps the arrays as they were given (pcs_get_prior).
+struct PriorStore {
+    DevBuf data, partial;                    // data: [index (int64) | mean | 1 / sigma], n words of 8 bytes each: ONE upload per pcs_set_prior
+    int64_t n = 0;                           // entries with weight > 0; 0 = no prior
+    std::vector<double> h_mean, h_w;         // the n_params values of the last accepted call (empty: none)
+    bool active() const { return n > 0; }
+    int64_t workgroups() const { return (n + PRIOR_PER_WG - 1) / PRIOR_PER_WG; }
+    const int64_t *idx() const { return data.as<const int64_t>(); }
+    const double *mean() const { return data.as<const double>() + n; }
+    const double *w() const { return data.as<const double>() + 2 * n; }
+    // "no prior"; the device buffers stay for the next one (a solve sets and clears its prior: no allocation per solve), and whatever
+    // is still queued keeps reading what it was given
+    void clear() {
+        n = 0;
+        h_mean.clear(), h_w.clear();
+    }
+    void release() {
+        data.release(), partial.release();
+        clear();
+    }
+    // everything is checked before anything changes: a refused call leaves the previous prior in force
+    static int check(const char *who, const double *mean_in, const double *inv_sigma, int64_t n_in, int64_t n_params) {
+        if (!inv_sigma) return PCS_OK;
+        if (!mean_in) return fail(PCS_ERR_ARG, "%s: inv_sigma without mean", who);
+        if (n_in != n_params) return fail(PCS_ERR_ARG, "%s: %lld values for a parameter string of %lld", who, (long long)n_in, (long long)n_params);
+        for (int64_t i = 0; i < n_in; ++i) {
+            if (!std::isfinite(inv_sigma[i]) || !(inv_sigma[i] >= 0.0))
+                return fail(PCS_ERR_ARG, "%s: inv_sigma %lld = %g must be finite and >= 0", who, (long long)i, inv_sigma[i]);
+            if (inv_sigma[i] > 0.0 && !std::isfinite(mean_in[i])) return fail(PCS_ERR_ARG, "%s: mean %lld = %g must be finite where inv_sigma > 0", who, (long long)i, mean_in[i]);
+        }
+        return PCS_OK;
+    }
+    // does replacing the prior by these values write device memory that a queued launch may still read?  (the caller then waits first)
+    bool set_writes_device(const double *inv_sigma) const { return inv_sigma && data.p; }
+    // checked values (or inv_sigma = NULL: none).  A failed allocation or copy leaves "no prior".
+    int set(const double *mean_in, const double *inv_sigma, int64_t n_params) {
+        clear();
+        if (!inv_sigma) return PCS_OK;
+        int64_t m = 0;
+        for (int64_t i = 0; i < n_params; ++i) m += inv_sigma[i] > 0.0 ? 1 : 0;
+        std::vector<uint64_t> words(3 * (size_t)m);
+        int64_t k = 0;
+        for (int64_t i = 0; i < n_params; ++i)
+            if (inv_sigma[i] > 0.0) {
+                words[k] = (uint64_t)i;
+                memcpy(&words[m + k], &mean_in[i], sizeof(double));
+                memcpy(&words[2 * m + k], &inv_sigma[i], sizeof(double));
+                ++k;
+            }
+        if (m > 0) {
+            if (const int rc = data.grow(3 * m, sizeof(uint64_t))) return rc;
+            if (m > PRIOR_PER_WG)
+                if (const int rc = partial.grow((m + PRIOR_PER_WG - 1) / PRIOR_PER_WG, sizeof(double))) return rc;
+            const hipError_t e = hipMemcpy(data.p, words.data(), sizeof(uint64_t) * words.size(), hipMemcpyHostToDevice);
+            if (e != hipSuccess) return fail(PCS_ERR_HIP, "uploading the parameter prior failed: %s", hipGetErrorString(e));
+        }
+        h_mean.assign(mean_in, mean_in + n_params), h_w.assign(inv_sigma, inv_sigma + n_params);
+        n = m;
+        return PCS_OK;
+    }
+    int get(const char *who, double *mean_out, double *inv_sigma, int64_t capacity, int64_t *n_out) const {
+        if (capacity < 0 || (!mean_out && !inv_sigma && !n_out)) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+        const int64_t have = (int64_t)h_w.size();
+        if (n_out) *n_out = have;
+        const int64_t m = std::min(have, capacity);
+        if (mean_out && m > 0) memcpy(mean_out, h_mean.data(), sizeof(double) * m);
+        if (inv_sigma && m > 0) memcpy(inv_sigma, h_w.data(), sizeof(double) * m);
+        return PCS_OK;
+    }
+};
+
 // Ordering of a handle's runs across streams: `done` is recorded after every run; whatever touches what a run reads or writes next
 // waits for it first.  (pcs_engine.hip's flush_done / mark_done are the lazily recording variant of this for the engine.)
 struct RunFence {

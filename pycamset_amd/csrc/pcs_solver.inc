@@ -372,9 +372,42 @@ static int enqueue_lm_trial_build(const LmTrialDesc &d, const pcs_lm_buffers *b,
     return build_trial(s, d.fused);
 }
 
-// The second half of a trial for a state of n_packed doubles ([blocks | g | cost]; pcs_engine and pcs_genchain alike).
-static int enqueue_lm_finish(int n_cu, int64_t n_params, int64_t n_packed, const pcs_lm_buffers *b, hipStream_t s) {
+// The handle's prior (PriorStore, csrc/ba_prior.hpp) onto a packed state of layout L.  One state: packed / ps with sel = NULL.  A trial's
+// finish half: both states and both strings with the selector, the prior goes to the TRIAL ones exactly as lm_decide_kernel reads them; behind
+// the stop word like every kernel of a trial.  No prior: nothing is queued.
+struct PriorTarget { double *packed[2]; const double *ps[2]; const int32_t *sel = nullptr, *stop = nullptr; };
+static int enqueue_prior_add(const PriorStore &pr, const BlockLayout &L, int64_t n_params, const PriorTarget &t, hipStream_t s) {
+    if (!pr.active()) return PCS_OK;
+    PriorArgs a{};
+    a.idx = pr.idx(); a.mean = pr.mean(); a.w = pr.w(); a.n = pr.n;
+    a.packed[0] = t.packed[0]; a.packed[1] = t.packed[1]; a.ps[0] = t.ps[0]; a.ps[1] = t.ps[1]; a.sel = t.sel; a.stop = t.stop;
+    a.n_lead = L.n_lead; a.trail_off = L.trail_off; a.c_off = L.a_len() + L.b_len(); a.g_off = L.h_len(); a.n_params = n_params; a.tb = L.tb;
+    const int64_t wgs = pr.workgroups();
+    if (wgs > INT32_MAX) return fail(PCS_ERR_ARG, "the parameter prior is too long for one launch");
+    a.partial = wgs > 1 ? pr.partial.as<double>() : nullptr;
+    a.n_partial = (int32_t)wgs;
+    hipLaunchKernelGGL(prior_add_kernel, dim3((unsigned)wgs), dim3(PRIOR_THREADS), 0, s, a);
+    if (wgs > 1) hipLaunchKernelGGL(prior_cost_kernel, dim3(1), dim3(PRIOR_THREADS), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return PCS_OK;
+}
+// pcs_prior_add_device / pcs_genchain_prior_add_device
+static int prior_add_piece(const char *who, int device, const PriorStore &pr, const BlockLayout &L, int64_t n_params, const double *d_param_str, double *d_packed, hipStream_t s) {
+    if (!d_param_str || !d_packed) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (!pr.active()) return PCS_OK;
+    HIPCHK(hipSetDevice(device));
+    PriorTarget t{{d_packed, d_packed}, {d_param_str, d_param_str}};
+    return enqueue_prior_add(pr, L, n_params, t, s);
+}
+
+// The second half of a trial for a state of layout L ([blocks | g | cost]; pcs_engine and pcs_genchain alike).
+static int enqueue_lm_finish(int n_cu, int64_t n_params, const BlockLayout &L, const PriorStore &prior, const pcs_lm_buffers *b, hipStream_t s) {
+    const int64_t n_packed = L.packed_len(n_params);
     const bool fixed_buffer = (b->mode & PCS_LM_FIXED_TRIAL_BUFFER) != 0;
+    if (prior.active()) {   // the prior at the trial string onto the trial state (behind a sharded loop's all-reduce), in front of the decision
+        PriorTarget t{{b->packed[0], b->packed[1]}, {b->ps[0], b->ps[1]}, b->flags + 2, b->flags};
+        if (const int rc = enqueue_prior_add(prior, L, n_params, t, s)) return rc;
+    }
     LmDecideArgs a{};
     a.tail[0] = b->packed[0] + n_packed - 1; a.tail[1] = b->packed[1] + n_packed - 1;
     a.ps2[0] = b->ps[0]; a.ps2[1] = b->ps[1];

@@ -237,6 +237,9 @@ class BlockedNormalEquations:
             else:
                 self.eng.normal_blocks_device(ps.data_ptr(), buf.data_ptr(), stream)
             self.reduce(buf)
+            # the engine's parameter prior (set_prior) enters ONCE, behind the sum over the ranks, with the same bits on every rank;
+            # nothing is queued when none is set.  (The trials of the device-steered loop get it from lm_trial_finish.)
+            self.eng.prior_add_device(ps.data_ptr(), buf.data_ptr(), stream)
 
     def solve(self, slot: int, lam, ps=None, ps_out=None):
         """Enqueue the damped step (H + lam diag(H)) delta = -g for the state in packed[slot]: ``self.delta`` (n_params,
@@ -635,7 +638,7 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
 @dataclass
 class DeviceLMResult:
     x: np.ndarray
-    cost: float                 # 0.5 * sum rho0 (0.5 * sum r^2 for the linear loss), like scipy's OptimizeResult.cost
+    cost: float                 # 0.5 * sum rho0 (0.5 * sum r^2 for the linear loss), like scipy's OptimizeResult.cost; with a prior: of the augmented objective
     grad: np.ndarray
     optimality: float
     nit: int
@@ -647,7 +650,91 @@ class DeviceLMResult:
     # one float64 array per decided trial (void ones included), in the read-back layout of include/pcs_hip.h (pcs_lm_trial stats):
     # accepted (1 / 0, -1 void), max |g|, relative cost drop, |step|, |x|, new and old sum r^2, lambda used, stop code after the trial,
     # trial number, current state after it, lambda for the next trial.  The PCG / host loop puts NaN where it has no such number.
+    # With a prior the two sums are those of the augmented objective (the prior's sum included).
     trials: list = field(default_factory=list)
+    prior_cost: float = 0.0     # 0.5 * sum (((x - prior_mean) / prior_sigma)^2) at x: the prior's share of ``cost`` (0.0 without a prior)
+
+
+def _free_prior(x0, prior_mean, prior_sigma):
+    """``lm_solve`` / ``parameter_covariance``'s prior on the FREE vector -> (mean, weight = 1 / sigma) as float64 arrays of x0's
+    length, or None without one.  ``np.inf`` in ``prior_sigma`` = no prior on that entry; every other value finite and > 0.
+    ``prior_mean=None`` = ``x0``.  ValueError for wrong shapes or values — nothing else is touched."""
+    if prior_sigma is None:
+        if prior_mean is not None:
+            raise ValueError("prior_mean without prior_sigma: a prior needs its standard deviations")
+        return None
+    x0 = np.asarray(x0, dtype=np.float64).ravel()
+    sig = np.asarray(prior_sigma, dtype=np.float64)
+    sig = np.full(x0.shape, float(sig)) if sig.ndim == 0 else sig
+    if sig.shape != x0.shape:
+        raise ValueError(f"prior_sigma has shape {sig.shape}: expected one value per free parameter, {x0.shape}")
+    if np.any(np.isnan(sig)) or not np.all(sig > 0.0):
+        raise ValueError("every prior_sigma must be > 0 (np.inf: no prior on that entry)")
+    mu = x0.copy() if prior_mean is None else np.asarray(prior_mean, dtype=np.float64)
+    mu = np.full(x0.shape, float(mu)) if mu.ndim == 0 else mu
+    if mu.shape != x0.shape:
+        raise ValueError(f"prior_mean has shape {mu.shape}: expected one value per free parameter, {x0.shape}")
+    w = np.where(np.isinf(sig), 0.0, 1.0 / sig)
+    if not np.all(np.isfinite(mu[w > 0.0])):
+        raise ValueError("prior_mean must be finite wherever prior_sigma is finite")
+    return np.where(w > 0.0, mu, 0.0), w
+
+
+def _string_prior(mask, prior):
+    """The free-vector prior as (mean, inv_sigma) over the parameter string: free entry k is string entry ``np.flatnonzero(mask)[k]`` —
+    the index the loop's result read-back uses.  Fixed parameters get no entry."""
+    if prior is None:
+        return None
+    free = np.flatnonzero(mask)
+    if free.shape[0] != prior[0].shape[0]:
+        raise ValueError(f"the prior has {prior[0].shape[0]} entries, the handler has {free.shape[0]} free parameters")
+    mean, w = np.zeros(mask.shape[0]), np.zeros(mask.shape[0])
+    mean[free], w[free] = prior
+    return mean, w
+
+
+def _prior_half_sum(prior, x) -> float:
+    return 0.0 if prior is None else 0.5 * float(np.sum((prior[1] * (np.asarray(x, dtype=np.float64) - prior[0])) ** 2))
+
+
+class _PriorOperator:
+    """A host operator (JacobianOperator, or one with ``build`` / ``solve``) plus a prior on the free vector: gradient, diagonal,
+    ``jtjv``, the normal matrix and the sum of squares each gain their prior term.  The free vector is read off the parameter string
+    (``free``: the string indices of the free parameters)."""
+
+    def __init__(self, op, free, prior):
+        self._op, self._free = op, np.asarray(free)
+        self._mu, self._w = prior
+        self._d = np.zeros_like(self._w)
+
+    def __getattr__(self, name):   # jv, jtu, solve, as_linear_operator, ...: the operator's own
+        return getattr(self.__dict__["_op"], name)
+
+    def _at(self, ps):
+        self._d = self._w * (np.asarray(ps, dtype=np.float64).ravel()[self._free] - self._mu)
+
+    def linearize(self, ps):
+        self._at(ps)
+        self._op.linearize(ps)
+
+    def grad(self):
+        g, c = self._op.grad()
+        return g + self._w * self._d, c + float(self._d @ self._d)
+
+    def diag(self):
+        return self._op.diag() + self._w ** 2
+
+    def jtjv(self, v):
+        return self._op.jtjv(v) + self._w ** 2 * v
+
+    def build(self, ps):
+        import torch
+
+        self._at(ps)
+        H, g, c = self._op.build(ps)
+        H = H.clone()
+        torch.diagonal(H).add_(torch.from_numpy(self._w ** 2).to(H.device))
+        return H, g + torch.from_numpy(self._w * self._d).to(g.device), c + float(self._d @ self._d)
 
 
 class _PcgStep:
@@ -712,23 +799,37 @@ def _n_cams_of(op_fun, dd) -> int:
 
 
 @contextlib.contextmanager
-def _engine_settings(eng, loss, f_scale, inv_sigma):
-    """The engine's loss and noise weights for one solve; both are restored afterwards (a failed solve included)."""
-    saved_loss, saved_w = eng.loss(), eng.weights()
-    eng.set_loss(loss, f_scale)
+def _engine_settings(eng, loss, f_scale, inv_sigma, prior=None):
+    """The engine's loss, noise weights and parameter prior (``(mean, inv_sigma)`` over the string, or None) for one solve; all are
+    restored afterwards (a failed solve included).  A generated chain has no loss and no weights to set: the prior only."""
+    fused = isinstance(eng, Engine)
+    saved_loss, saved_w = (eng.loss(), eng.weights()) if fused else (None, None)
+    saved_prior = eng.prior()
+    if fused:
+        eng.set_loss(loss, f_scale)
     try:
-        eng.set_weights(inv_sigma=inv_sigma)
+        if fused:
+            eng.set_weights(inv_sigma=inv_sigma)
+        if prior is None:
+            eng.set_prior()
+        else:
+            eng.set_prior(prior[0], inv_sigma=prior[1])
         yield
     finally:
-        eng.set_loss(*saved_loss)
-        eng.set_weights(inv_sigma=saved_w)
+        if fused:
+            eng.set_loss(*saved_loss)
+            eng.set_weights(inv_sigma=saved_w)
+        if saved_prior is None:
+            eng.set_prior()
+        else:
+            eng.set_prior(saved_prior[0], inv_sigma=saved_prior[1])
 
 
-def _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma=None) -> BlockedNormalEquations:
-    """The engine's cached solver state for this mask, collective, layout, loss and noise weights (one state per engine: a miss drops the
-    previous one)."""
+def _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma=None, prior=None) -> BlockedNormalEquations:
+    """The engine's cached solver state for this mask, collective, layout, loss, noise weights and prior (one state per engine: a miss
+    drops the previous one)."""
     key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())), loss, f_scale,
-           None if inv_sigma is None else hash(inv_sigma.tobytes()))
+           None if inv_sigma is None else hash(inv_sigma.tobytes()), None if prior is None else hash(prior[0].tobytes() + prior[1].tobytes()))
     cache = eng.__dict__.setdefault("_blocked_solvers", {})
     ne = cache.get(key)
     if ne is None:
@@ -741,7 +842,8 @@ def _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma=None) -> Bloc
 
 def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float = 1e-8, gtol: float = 1e-8,
              cg_tol: float = 1e-3, cg_max_iter: int = 200, lam0: float | None = None, lam_grow0: float | None = None, reduce_fn=None, verbose: int = 0,
-             operator=None, linear_solver: str = "auto", loss: str = "linear", f_scale: float = 1.0, sigma=None) -> DeviceLMResult:
+             operator=None, linear_solver: str = "auto", loss: str = "linear", f_scale: float = 1.0, sigma=None,
+             prior_mean=None, prior_sigma=None) -> DeviceLMResult:
     """Levenberg-Marquardt (Marquardt scaling D = diag(J^T J)) for a pycamset_amd handler.  The damped
     normal equations are solved by Jacobi-PCG on matrix-free J^T J products (``linear_solver='pcg'``) or
     by a Cholesky factorisation of the block-reduced J^T J (``'cholesky'``).  Every quantity that depends
@@ -769,7 +871,17 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
     Jacobian rows are whitened by 1 / sigma in front of the loss: the solve minimises ``sum rho(((f / sigma) / f_scale)^2) f_scale^2``,
     scipy's ``least_squares(loss=, f_scale=)`` on the whitened closures; ``cost`` and ``grad`` are those of the whitened system.  A
     sharded solve gives every rank the sigmas of its own detections (``sharding.shard_sigma``).  The engine's weights are set for the
-    solve and restored afterwards; the same combinations as for a robust loss raise NotImplementedError."""
+    solve and restored afterwards; the same combinations as for a robust loss raise NotImplementedError.
+
+    ``prior_mean`` / ``prior_sigma``: a Gaussian prior on the free vector, in the order of ``x0`` (scipy's ``result.x`` order): the
+    solve minimises the objective above plus ``sum (((x - prior_mean) / prior_sigma)^2)`` — scipy's extra rows ``(x - mu) / sigma``,
+    outside the loss and the detections' sigma.  ``np.inf`` in ``prior_sigma`` puts no prior on that entry, every other value must
+    be finite and > 0; ``prior_mean=None`` is ``x0`` (a Tikhonov pull to the start).  ``handlers.slab_prior`` builds the two arrays
+    from per-group values.  Works on every path: the blocked loops add the prior on the device (include/pcs_hip.h pcs_set_prior; set
+    for the solve and restored afterwards), ``linear_solver='pcg'`` and a caller's ``operator`` add it on the host; with ``loss`` and
+    ``sigma`` on hand-fused chains, with the linear loss on generated chains.  The result's ``cost`` and ``grad`` are those of the
+    augmented objective, ``prior_cost`` is the prior's half sum at ``x``.  ValueError for wrong shapes or values, before any device work."""
+    prior = _free_prior(x0, prior_mean, prior_sigma)
     if loss not in LOSS_IDS:
         raise ValueError(f"unknown loss {loss!r}: expected one of {sorted(LOSS_IDS)}")
     f_scale = float(f_scale)
@@ -819,16 +931,25 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
             # re-allocates per value instead of accumulating workspaces)
             # (... and the noise weights, in the same way: the engine's weights are set per solve below, and a state is never carried
             # from one set of weights to another, or from a weighted solve to an unweighted one)
-            ne = _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma)
+            # (... and the prior, likewise: set per solve below, never carried from one solve's prior to another's)
+            sprior = _string_prior(mask, prior)
+            ne = _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma, sprior)
             ne.spd_algorithm = "auto"
             ps0 = op_fun.build_param_list(*handler.get_bundle_adjustment_inputs(np.array(x0, dtype=np.float64)))
-            if not isinstance(eng, Engine):   # generated chains: linear only (checked above)
+            if not isinstance(eng, Engine) and sprior is None:   # generated chains: linear only (checked above); no prior: nothing to set
                 return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
-            with _engine_settings(eng, loss, f_scale, inv_sigma):
-                return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
+            with _engine_settings(eng, loss, f_scale, inv_sigma, sprior):
+                res = _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
+            res.prior_cost = _prior_half_sum(prior, res.x)
+            return res
         operator = JacobianOperator(eng, handler._jac_mask(), reduce_fn=reduce_fn)
     elif linear_solver == "auto":
         linear_solver = "cholesky" if hasattr(operator, "build") else "pcg"
+    if prior is not None:   # the host paths: the operator's products gain the prior terms
+        free = np.flatnonzero(np.asarray(handler._jac_mask(), dtype=bool))
+        if free.shape[0] != prior[0].shape[0]:
+            raise ValueError(f"the prior has {prior[0].shape[0]} entries, the handler has {free.shape[0]} free parameters")
+        operator = _PriorOperator(operator, free, prior)
     step = _PcgStep(operator, cg_tol, cg_max_iter) if linear_solver == "pcg" else _CholeskyStep(operator)
 
     def param_str(x):
@@ -901,7 +1022,7 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
         if it == max_iter:
             trials[-1][8] = 5
     return DeviceLMResult(x=x, cost=0.5 * st["sumsq"], grad=st["g"], optimality=float(np.max(np.abs(st["g"]))), nit=it, nfev=nfev,
-                          n_jtjv=n_lin, status=status, message=message, history=history, trials=trials)
+                          n_jtjv=n_lin, status=status, message=message, history=history, trials=trials, prior_cost=_prior_half_sum(prior, x))
 
 
 @dataclass
@@ -909,8 +1030,8 @@ class ParameterCovariance:
     std: np.ndarray          # (n_free,) standard errors, in the order of x
     blocks: list             # one array per slab of handler.get_bundle_adjustment_inputs(x): (rows, w, w); 0 at fixed entries
     sigma2: float            # the residual variance used (1.0 with absolute_sigma)
-    dof: int                 # 2N - n_free
-    cost: float              # 0.5 sum r^2 at x
+    dof: int                 # 2N - n_free (+ the number of prior entries)
+    cost: float              # 0.5 sum r^2 at x (+ the prior's half sum)
     min_pivot: float = 0.0   # smallest L_ii^2 / H_ii over the free parameters (the rank test against rcond)
 
 
@@ -954,7 +1075,8 @@ def _covariance_plan(ne: BlockedNormalEquations, layout):
     return plan, trail
 
 
-def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: float = 1e-10, reduce_fn=None, sigma=None) -> ParameterCovariance:
+def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: float = 1e-10, reduce_fn=None, sigma=None,
+                         prior_mean=None, prior_sigma=None) -> ParameterCovariance:
     """Marginal covariance blocks and standard errors of the parameters at ``x`` (the free vector, scipy's ``result.x`` order), from
     the blocked normal equations on the device: H = J'J with the linear loss and no damping, fixed parameters
     as identity rows and columns; sigma^2 = sum r^2 / (2N - n_free), or 1 with ``absolute_sigma`` (scipy curve_fit's meaning);
@@ -965,6 +1087,11 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
     rows of J and the residuals divided by sigma; sigma^2 = sum (f / sigma)^2 / (2N - n_free), the variance of unit weight, and ``cost``
     is half that sum; ``absolute_sigma=True`` — the sigmas ARE the noise — gives inv(H) as it stands.  Hand-fused chains only.
 
+    ``prior_mean`` / ``prior_sigma``: the Gaussian prior of ``lm_solve`` on the free vector.  H then includes the prior's diagonal
+    1 / sigma^2 — what makes a gauge-free self-calibration or an unobserved entity invertible —, the prior rows count as observations:
+    sigma^2 = (sum r^2 + sum ((x - mean) / sigma)^2) / (2N + n_prior - n_free), and the degrees-of-freedom test uses the same count.
+    ``prior_mean`` is required unless ``absolute_sigma=True``, where the mean plays no part.  Generated chains included.
+
     Raises np.linalg.LinAlgError when H is singular or nearly so (a non-positive pivot, a trailing block that is not positive
     definite, or min L_ii^2 / H_ii below ``rcond``): a free gauge or an unobserved parameter.  ValueError for a wrong ``len(x)``
     or 2N - n_free <= 0, NotImplementedError for sharded systems (``reduce_fn``)."""
@@ -974,15 +1101,19 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
     if not (np.isfinite(rcond) and rcond >= 0.0):
         raise ValueError(f"rcond must be finite and >= 0, got {rcond}")
     x = np.asarray(x, dtype=np.float64).ravel()
+    if prior_sigma is not None and prior_mean is None and not absolute_sigma:
+        raise ValueError("prior_sigma without prior_mean: the variance of unit weight needs the prior's residuals (or pass absolute_sigma=True)")
+    prior = _free_prior(x, prior_mean, prior_sigma)   # shapes and values, before the handler is touched
+    n_prior = 0 if prior is None else int(np.count_nonzero(prior[1]))
     mask = np.asarray(handler._jac_mask(), dtype=bool)
     n_free = int(mask.sum())
     if x.shape[0] != n_free:
         raise ValueError(f"x has {x.shape[0]} entries, the handler has {n_free} free parameters")
     dd = handler._flat_detections()
     inv_sigma = None if sigma is None else 1.0 / expand_sigma(sigma, dd[:, 0], _n_cams_of(handler.op_fun, dd))
-    dof = 2 * int(dd.shape[0]) - n_free
+    dof = 2 * int(dd.shape[0]) + n_prior - n_free
     if dof <= 0:
-        raise ValueError(f"no degrees of freedom left: 2N = {2 * int(dd.shape[0])} residuals for {n_free} free parameters")
+        raise ValueError(f"no degrees of freedom left: 2N = {2 * int(dd.shape[0])} residuals and {n_prior} prior rows for {n_free} free parameters")
     slabs = handler.get_bundle_adjustment_inputs(x)
     layout, n_str = _slab_layout(slabs)
     if n_str != mask.shape[0]:
@@ -995,7 +1126,8 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
         raise NotImplementedError("this system is too large for the blocked normal equations (device_solver.blocked_fits)")
     if inv_sigma is not None and not isinstance(eng, Engine):
         raise NotImplementedError("sigma: generated chains (ChainProblem) build their normal equations without noise weights")
-    ne = _blocked_solver(eng, mask, None, "linear", 1.0, inv_sigma)
+    sprior = _string_prior(mask, prior)
+    ne = _blocked_solver(eng, mask, None, "linear", 1.0, inv_sigma, sprior)
     ne.stream.synchronize()   # a speculative trial of the last solve may still be draining on this state
     torch = ne.torch
     from .engine import cov_block_gram, cov_trsm, dense_spd_solve, schur_syrk
@@ -1004,11 +1136,11 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
     if getattr(ne, "_cov_plan", (None,))[0] != plan_key:
         ne._cov_plan = (plan_key,) + _covariance_plan(ne, layout)
     _, plan, trail_desc = ne._cov_plan
-    robust = isinstance(eng, Engine)
     nl, nt, dev = ne.n_lead, ne.n_trail, eng.device
     try:
         # hand-fused chains: the linear loss and these weights (none: the raw build) for the build below, the engine's own restored afterwards
-        settings = _engine_settings(eng, "linear", 1.0, inv_sigma) if robust else contextlib.nullcontext()
+        # (a generated chain: the prior only)
+        settings = _engine_settings(eng, "linear", 1.0, inv_sigma, sprior)
         with settings, torch.cuda.device(ne.dev), torch.cuda.stream(ne.stream):
             stream = ne.stream.cuda_stream
             ps = torch.from_numpy(np.ascontiguousarray(op_fun.build_param_list(*slabs), dtype=np.float64)).to(ne.dev)

@@ -57,6 +57,36 @@ def expand_sigma(sigma, cam, n_cams: int):
     return np.ascontiguousarray(s, dtype=np.float64)
 
 
+def prior_arrays(n_params: int, mean, sigma=None, inv_sigma=None):
+    """(mean, inv_sigma) as the C ABI takes a parameter prior (include/pcs_hip.h pcs_set_prior): two float64 (n_params,) arrays, or
+    (None, None) for "no prior".  ``sigma``: the standard deviations, ``np.inf`` = no prior on that entry, every other value finite and
+    > 0; ``inv_sigma``: their reciprocals, 0 = no prior on that entry.  One of the two.  ValueError for anything else."""
+    if sigma is not None and inv_sigma is not None:
+        raise ValueError("give sigma or inv_sigma, not both")
+    if sigma is None and inv_sigma is None:
+        if mean is not None:
+            raise ValueError("a prior mean needs sigma (or inv_sigma)")
+        return None, None
+    if mean is None:
+        raise ValueError("a prior needs its mean")
+    m = np.array(np.broadcast_to(np.asarray(mean, dtype=np.float64), (n_params,)) if np.ndim(mean) == 0 else mean, dtype=np.float64).ravel()
+    v = np.asarray(sigma if sigma is not None else inv_sigma, dtype=np.float64)
+    v = np.array(np.broadcast_to(v, (n_params,)) if v.ndim == 0 else v, dtype=np.float64).ravel()
+    if m.shape[0] != n_params or v.shape[0] != n_params:
+        raise ValueError(f"the prior has {m.shape[0]} means and {v.shape[0]} sigmas for {n_params} parameters")
+    if sigma is not None:
+        if np.any(np.isnan(v)) or not np.all(v > 0.0):
+            raise ValueError("every prior sigma must be > 0 (np.inf: no prior on that entry)")
+        w = np.where(np.isinf(v), 0.0, 1.0 / v)
+    else:
+        if not np.all(np.isfinite(v) & (v >= 0.0)):
+            raise ValueError("every prior inv_sigma must be finite and >= 0 (0: no prior on that entry)")
+        w = v
+    if not np.all(np.isfinite(m[w > 0.0])):
+        raise ValueError("the prior mean must be finite wherever a sigma is given")
+    return np.ascontiguousarray(np.where(w > 0.0, m, 0.0)), np.ascontiguousarray(w)
+
+
 class _PinnedBlock:
     """Owner of one page-locked host allocation; NumPy views keep it alive through ``base``."""
 
@@ -237,6 +267,38 @@ class Engine:
         w = np.empty(n.value)
         check(lib().pcs_get_weights(self._h, _dp(w), n.value, None))
         return w
+
+    def set_prior(self, mean=None, sigma=None, *, inv_sigma=None):
+        """Gaussian prior on the parameter string for the LM solve of this engine (include/pcs_hip.h pcs_set_prior): ``mean`` and
+        ``sigma`` are (n_params,) arrays in parameter-string order; ``sigma[i] = np.inf`` (``inv_sigma[i] = 0``) puts no prior on entry
+        i.  The objective gains ``sum (((p - mean) / sigma)^2)``, outside the loss and the detections' noise weights.  ``set_prior()``
+        clears it; a new detection table keeps it.  The raw builds (``normal_blocks_device``, ``normal_equations*``, ``eval*``, the
+        matrix-free products) stay the sums over the detections: ``prior_add_device`` and ``lm_trial_finish`` add the prior."""
+        m, w = prior_arrays(self.n_params, mean, sigma, inv_sigma)
+        if w is None:
+            check(self._prior_fn("set_prior")(self._h, None, None, 0))
+            return
+        check(self._prior_fn("set_prior")(self._h, _dp(m), _dp(w), self.n_params))
+
+    def prior(self):
+        """The current prior as (mean, inv_sigma), float64 (n_params,) each, or None when none is set."""
+        n = c_int64(0)
+        check(self._prior_fn("get_prior")(self._h, None, None, 0, byref(n)))
+        if n.value == 0:
+            return None
+        m, w = np.empty(n.value), np.empty(n.value)
+        check(self._prior_fn("get_prior")(self._h, _dp(m), _dp(w), n.value, None))
+        return m, w
+
+    def prior_add_device(self, d_param_str: int, d_packed: int, stream: int | None = None):
+        """Adds the prior at the DEVICE-resident parameter string to the packed state ``d_packed`` that was built there; asynchronous.
+        Nothing is queued when no prior is set."""
+        check(self._prior_fn("prior_add_device")(self._h, c_void_p(d_param_str), c_void_p(d_packed), _stream_arg(stream)))
+
+    _PRIOR_PREFIX = "pcs_"
+
+    def _prior_fn(self, name: str):
+        return getattr(lib(), self._PRIOR_PREFIX + name)
 
     def option(self, key: str, default: int) -> int:
         """The value last given to ``set_option(key, ...)`` through this object, else ``default`` (the library's own default)."""

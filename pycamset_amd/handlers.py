@@ -429,18 +429,27 @@ class TemplateBundleHandler:  # th:80-240
 
 
 class SelfBundleHandler(TemplateBundleHandler):  # sbh:109-260
-    """Self-calibration: the 3-D target points are free too (chain S), 7-DoF gauge fixed."""
+    """Self-calibration: the 3-D target points are free too (chain S), 7-DoF gauge fixed.
+
+    ``options={"gauge": "free"}`` leaves the seven gauge scalars free (unseen features stay fixed): the gauge is then held by a prior
+    on the points at their nominal positions — ``slab_prior(handler, {"bdpt": tolerance})`` handed to ``lm_solve`` /
+    ``parameter_covariance`` — instead of pinned coordinates; the result stays in the nominal frame and scale.  The default,
+    ``"fixed"``, is the reference's mask."""
 
     chain = "self"
 
     def _point_mask(self, visible_feature_mask):
+        gauge = self.problem_opts.get("gauge", "fixed")
+        if gauge not in ("fixed", "free"):
+            raise ValueError(f'options["gauge"] must be "fixed" or "free", got {gauge!r}')
         pts = self.flat_point_data.reshape((-1, 3))
         self.fixed_inds = find_not_colinear_pts(pts)  # sbh:153-158: 3 + 3 + 1 coordinates fix the 7-DoF gauge
         i0, i1, i2 = self.fixed_inds
         feat_unfixed = np.ones(self.flat_point_data.shape[0], dtype=bool)
-        feat_unfixed[3 * i0 : 3 * i0 + 3] = False
-        feat_unfixed[3 * i1 : 3 * i1 + 3] = False
-        feat_unfixed[3 * i2] = False
+        if gauge == "fixed":
+            feat_unfixed[3 * i0 : 3 * i0 + 3] = False
+            feat_unfixed[3 * i1 : 3 * i1 + 3] = False
+            feat_unfixed[3 * i2] = False
         n_points = int(np.prod(self.point_data.shape[:2]))  # sbh:161
         if visible_feature_mask is not None:
             self.visible_feature_mask = np.asarray(visible_feature_mask, dtype=bool)
@@ -460,6 +469,57 @@ class FreePointBundleHandler(TemplateBundleHandler):  # fph:102-201
     def _point_mask(self, visible_feature_mask):
         return np.ones(self.flat_point_data.shape[0], dtype=bool)  # fph:130
 
+
+def slab_prior(handler, sigmas, means=None):
+    """(prior_mean, prior_sigma) on the handler's FREE vector — what ``lm_solve`` / ``parameter_covariance`` /
+    ``problem_opts["prior"]`` take — from per-group values.
+
+    Bundle handlers: ``sigmas`` is a dict over the groups ``"intr"`` (C, 9), ``"extr"`` (C, 6), ``"pose"`` (I, 6) and ``"bdpt"`` (the
+    point scalars; (K, 3) or flat); a ``ChainProblem``: a list with one entry per slab.  Each entry is anything that broadcasts to its
+    slab — a scalar, a row, the full array; ``None``, a missing group or ``np.inf`` mean no prior there.  Only the free entries (the
+    per-row masks, the per-scalar point mask) reach the result, in free-vector order.  ``means``: the same structure; a group without
+    one takes the handler's current slab — for ``"bdpt"`` the nominal ``point_data``."""
+    if isinstance(handler, ChainProblem):
+        slabs = [(i, s, m) for i, (s, m) in enumerate(zip(handler.slabs, handler.unfixed))]
+        if isinstance(sigmas, dict) or len(sigmas) != len(slabs):
+            raise ValueError(f"sigmas: one entry (or None) per slab of the ChainProblem, {len(slabs)} in all")
+        if means is not None and len(means) != len(slabs):
+            raise ValueError(f"means: one entry (or None) per slab of the ChainProblem, {len(slabs)} in all")
+        pick = lambda d, k: None if d is None else d[k]   # noqa: E731
+    else:
+        bp = handler.bundlePrimitive
+        unknown = set(sigmas) - set(bp.groups) | (set(means or {}) - set(bp.groups))
+        if unknown:
+            raise ValueError(f"unknown parameter groups {sorted(unknown)}: this handler has {list(bp.groups)}")
+        slabs = []
+        for g in bp.groups:
+            slab_name, mask_name, width = _GROUP[g]
+            slab, mask = getattr(bp, slab_name), np.asarray(getattr(bp, mask_name), dtype=bool)
+            if g == "bdpt":   # the nominal target, not the primitive's working copy (a solve scatters its iterates into that)
+                slab = np.asarray(handler.point_data, dtype=np.float64).reshape(-1)
+            slabs.append((g, slab, mask if width == 1 else np.repeat(mask[:, None], width, axis=1)))
+        pick = lambda d, k: None if d is None else d.get(k)   # noqa: E731
+    mean_parts, sigma_parts = [], []
+    for key, slab, mask in slabs:
+        slab = np.asarray(slab, dtype=np.float64)
+
+        def spread(v, what):
+            v = np.asarray(v, dtype=np.float64)
+            if v.size == slab.size:
+                return v.reshape(slab.shape)
+            try:
+                return np.broadcast_to(v, slab.shape)
+            except ValueError:
+                raise ValueError(f"{what}[{key!r}] of shape {v.shape} does not broadcast to the slab {slab.shape}") from None
+
+        sg, mu = pick(sigmas, key), pick(means, key)
+        sg = np.full(slab.shape, np.inf) if sg is None else spread(sg, "sigmas")
+        mu = slab if mu is None else spread(mu, "means")
+        if np.any(np.isnan(sg)) or not np.all(sg > 0.0):
+            raise ValueError(f"sigmas[{key!r}]: every value must be > 0 (np.inf: no prior)")
+        mean_parts.append(np.asarray(mu)[mask])
+        sigma_parts.append(np.asarray(sg)[mask])
+    return np.concatenate(mean_parts).astype(np.float64), np.concatenate(sigma_parts).astype(np.float64)
 
 
 class ChainProblem:

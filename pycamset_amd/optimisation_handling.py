@@ -35,14 +35,43 @@ def make_optimisation_function(param_handler, threads: int = 1):
     return loss_fn, jac_fn, x0
 
 
+def _with_prior_rows(loss_fn, jac_fn, prior):
+    """The closures of the augmented problem: residual rows ``w (x - mean)`` behind the detections' and the matching diagonal rows
+    behind the Jacobian's, for the entries with w = 1 / sigma > 0."""
+    from scipy.sparse import csr_array, vstack
+
+    mean, w = prior
+    idx = np.flatnonzero(w > 0.0)
+    rows = csr_array((w[idx], (np.arange(idx.shape[0]), idx)), shape=(idx.shape[0], w.shape[0]))
+
+    def fun(x):
+        return np.concatenate([loss_fn(x), w[idx] * (x[idx] - mean[idx])])
+
+    def jac(x):
+        return vstack([jac_fn(x), rows], format="csr")
+
+    return fun, (jac if jac_fn is not None else None)
+
+
 def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy", linear_solver: str = "auto"):
     """Solve the handler's problem; returns (result, parameter slabs at the solution) — oh:52-117.
     ``solver='device'`` runs device_solver.lm_solve with ``linear_solver`` in {'auto', 'cholesky', 'pcg'}.
     Optional ``problem_opts['loss']`` / ``['f_scale']`` (scipy's names, default 'linear' / 1.0 — the reference's call carries the
-    commented ``# loss = "cauchy"``, oh:96) go to whichever solver runs."""
+    commented ``# loss = "cauchy"``, oh:96) go to whichever solver runs.  Optional ``problem_opts['prior'] = (mean, sigma)``: a
+    Gaussian prior on the free vector (``device_solver.lm_solve``'s ``prior_mean`` / ``prior_sigma``; ``handlers.slab_prior`` builds
+    one).  The device solver takes it as it is; for scipy the rows ``(x - mean) / sigma`` are appended to the residual closure and the
+    matching diagonal rows to the Jacobian closure, so both solvers minimise the same function — with the linear loss: scipy's robust
+    losses would apply to the appended rows too."""
     loss_fn, jac_fn, x0 = make_optimisation_function(param_handler, threads)
     opts = param_handler.problem_opts
     loss, f_scale = opts.get("loss", "linear"), opts.get("f_scale", 1.0)
+    prior = None
+    if opts.get("prior") is not None:
+        from .device_solver import _free_prior
+
+        prior_mean, prior_sigma = opts["prior"]
+        prior = _free_prior(x0, prior_mean, prior_sigma)
+    n_rows = 2 * param_handler._flat_detections().shape[0]
     start_error = mean_reprojection_error(loss_fn(x0))
     log.info("%d parameters, %d residuals, start error %.2f px", len(x0), 2 * param_handler._flat_detections().shape[0], start_error)
     if not np.isfinite(start_error) or start_error > 150:  # the reference's sanity threshold (oh:80-83)
@@ -51,12 +80,19 @@ def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy"
     if solver == "device":
         from .device_solver import lm_solve
 
-        result = lm_solve(param_handler, x0, max_iter=opts["max_nfev"], linear_solver=linear_solver, loss=loss, f_scale=f_scale)
+        result = lm_solve(param_handler, x0, max_iter=opts["max_nfev"], linear_solver=linear_solver, loss=loss, f_scale=f_scale,
+                          **({} if prior is None else {"prior_mean": prior_mean, "prior_sigma": prior_sigma}))
         end_error = mean_reprojection_error(loss_fn(result.x))
     else:
-        result = least_squares(loss_fn, x0, jac=jac_fn if jac_fn is not None else "2-point", x_scale="jac",
+        fun, jac = loss_fn, jac_fn
+        if prior is not None:
+            if loss != "linear":
+                raise NotImplementedError("problem_opts['prior'] with solver='scipy' and a robust loss: scipy would pass the prior rows "
+                                          "through the loss (solver='device' keeps them outside it)")
+            fun, jac = _with_prior_rows(loss_fn, jac_fn, prior)
+        result = least_squares(fun, x0, jac=jac if jac is not None else "2-point", x_scale="jac",
                                max_nfev=opts["max_nfev"], verbose=opts["verbosity"], loss=loss, f_scale=f_scale)
-        end_error = mean_reprojection_error(result.fun)
+        end_error = mean_reprojection_error(result.fun[:n_rows])
     log.info("solved in %.2f s, final error %.2f px", time.perf_counter() - tic, end_error)
     if end_error > 5:  # oh:105-107
         log.critical("remaining error is very large: check the result")
