@@ -689,8 +689,30 @@ int pcs_tri_refine_costs(pcs_triangulator *t, double *cost);
  *                             PCS_ERR_ARG: NULL handle, max_iter < 0, a negative or non-finite tolerance, min_points < 1, unknown flags.
  *   pcs_pnp_results           copy handle-owned outputs of the last run to the host (any pointer may be NULL; blocking)
  *                             (replaces the Mat_ac array of template_handler.py:485-491)
- *   pcs_pnp_last_kernel_ms    device time of the last run: ordering of the views, start and LM kernels.  PCS_ERR_STATE when the
- *                             last run had no views and so queued nothing.
+ *   pcs_pnp_last_kernel_ms    device time of the last run: ordering of the views, start and LM kernels, and the consensus stage
+ *                             when it is on.  PCS_ERR_STATE when the last run had no views and so queued nothing.
+ *
+ * Consensus sampling (csrc/ba_pnp_consensus.hpp; since pcs_version() 115), opt-in: what cv2.solvePnPRansac is to cv2.solvePnPGeneric,
+ * at the same place in the pipeline (abstract_target.py:345-405).  One detection with a wrong id bends the linear start of its view;
+ * with the stage on, n_hypotheses samples of sample_size detections per view are fitted by the same linear start, both of its poses are
+ * scored on every detection of the view by sum min(e^2, inlier_px^2), and start and LM then run on the detections within inlier_px of
+ * the best candidate.  The sampler is counter-based, keyed by (seed, camera, observations of the view, hypothesis); the hypothesis
+ * count is fixed, so two runs agree bit for bit, and a table without outliers gives the bits of the plain run.
+ *   pcs_pnp_set_consensus     n_hypotheses = 0 (the default) turns the stage off: pcs_pnp_run then queues what it always queued and
+ *                             allocates nothing more (cv2.solvePnPGeneric).  Otherwise cv2.solvePnPRansac's iterationsCount,
+ *                             its minimal sample (here 4 <= sample_size <= 16: the linear start, no P3P), reprojectionError and the
+ *                             seed of its generator.  PCS_ERR_ARG: NULL handle, a negative count, n_hypotheses > 4096, sample_size
+ *                             outside [4, 16], inlier_px not finite or <= 0; a refused call keeps the previous setting.
+ *   pcs_pnp_get_consensus     the setting in force (any pointer may be NULL; cv2.solvePnPRansac's arguments, which it does not keep)
+ *   pcs_pnp_consensus_results copy what the stage of the last run found to the host (cv2.solvePnPRansac's `inliers`; blocking, any
+ *                             pointer may be NULL): inlier (n_obs) one flag per observation; cinfo (n_views, 4) int32 {inliers, winning
+ *                             hypothesis or -1, hypotheses with a finite candidate, consensus used}; score (n_views) the winner's
+ *                             sum min(e^2, inlier_px^2) (+inf: no finite candidate, NaN: consensus not used).  A view with fewer
+ *                             observations than sample_size takes the plain path (all flagged, consensus used = 0); a view whose
+ *                             best candidate has fewer than min_points inliers, or no finite candidate, is not estimated; a NaN
+ *                             measurement is never an inlier.  With the stage on, d_rms is over the inliers, d_info keeps the
+ *                             view's observation count, d_resid holds the residuals of ALL observations at the returned pose.
+ *                             PCS_ERR_STATE when the last run had no consensus stage.
  */
 typedef struct pcs_pose_estimator pcs_pose_estimator;
 #define PCS_PNP_RESIDUALS 1
@@ -711,6 +733,9 @@ int pcs_pnp_run(pcs_pose_estimator *p, int max_iter, double ftol, double xtol, d
                 double *d_pose_init, double *d_pose_alt, double *d_rms, int32_t *d_info, double *d_resid, void *stream);
 int pcs_pnp_results(pcs_pose_estimator *p, double *pose, double *pose_init, double *pose_alt, double *rms, int32_t *info, double *resid);
 int pcs_pnp_last_kernel_ms(pcs_pose_estimator *p, float *kernel_ms);
+int pcs_pnp_set_consensus(pcs_pose_estimator *p, int n_hypotheses, int sample_size, double inlier_px, uint64_t seed);
+int pcs_pnp_get_consensus(pcs_pose_estimator *p, int *n_hypotheses, int *sample_size, double *inlier_px, uint64_t *seed);
+int pcs_pnp_consensus_results(pcs_pose_estimator *p, uint8_t *inlier, int32_t *cinfo, double *score);
 
 /* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.

@@ -158,6 +158,9 @@ SYMBOLS = {
     "pcs_pnp_run": (c_int, [_P, c_int, c_double, c_double, c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "pcs_pnp_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double)]),
     "pcs_pnp_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_pnp_set_consensus": (c_int, [_P, c_int, c_int, c_double, c_uint64]),
+    "pcs_pnp_get_consensus": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_uint64)]),
+    "pcs_pnp_consensus_results": (c_int, [_P, POINTER(c_uint8), POINTER(c_int32), POINTER(c_double)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),

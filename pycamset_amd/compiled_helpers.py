@@ -463,6 +463,23 @@ class ViewPoses:
     iterations: np.ndarray
     n_points: np.ndarray
     residuals: np.ndarray | None = None
+    inliers: np.ndarray | None = None
+    n_inliers: np.ndarray | None = None
+    hypothesis: np.ndarray | None = None
+
+
+def check_consensus_options(consensus, sample_size, inlier_px, seed):
+    """Validate the consensus options on the host (ValueError) before anything is queued: the checks of pcs_pnp_set_consensus."""
+    for name, v, lo, hi in (("consensus", consensus, 0, 4096), ("sample_size", sample_size, 4, 16), ("seed", seed, 0, 2 ** 64 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+    try:
+        px = float(inlier_px)
+    except (TypeError, ValueError):
+        raise ValueError(f"inlier_px must be a finite number > 0, got {inlier_px!r}") from None
+    if not (np.isfinite(px) and px > 0.0):
+        raise ValueError(f"inlier_px must be a finite number > 0, got {inlier_px!r}")
+    return int(consensus), int(sample_size), px, int(seed)
 
 
 class PoseEstimator(_Handle):
@@ -520,6 +537,24 @@ class PoseEstimator(_Handle):
     def last_kernel_ms(self) -> float:
         return self._ms("pcs_pnp_last_kernel_ms")
 
+    def set_consensus(self, n_hypotheses: int = 0, sample_size: int = 6, inlier_px: float = 8.0, seed: int = 0):
+        """The consensus stage of the runs that follow (pcs_pnp_set_consensus: cv2.solvePnPRansac's iterationsCount, minimal sample,
+        reprojectionError and seed); ``n_hypotheses = 0`` turns it off."""
+        self._call("pcs_pnp_set_consensus", self._h, *check_consensus_options(n_hypotheses, sample_size, inlier_px, seed))
+
+    def get_consensus(self):
+        """(n_hypotheses, sample_size, inlier_px, seed) in force."""
+        h, s, px, seed = self._ct.c_int(0), self._ct.c_int(0), self._ct.c_double(0.0), self._ct.c_uint64(0)
+        self._call("pcs_pnp_get_consensus", self._h, self._ct.byref(h), self._ct.byref(s), self._ct.byref(px), self._ct.byref(seed))
+        return int(h.value), int(s.value), float(px.value), int(seed.value)
+
+    def consensus_results(self):
+        """Wait for the last ``run`` with a consensus stage: (inlier (n_obs,) bool, cinfo (n_views, 4) int32 = [inliers, winning
+        hypothesis, finite hypotheses, consensus used], score (n_views,))."""
+        inlier, cinfo, score = np.zeros(self.n_obs, dtype=np.uint8), np.zeros((self.n_views, 4), dtype=np.int32), np.empty(self.n_views)
+        self._call("pcs_pnp_consensus_results", self._h, self._ptr(inlier), self._ptr(cinfo), self._ptr(score))
+        return inlier.astype(bool), cinfo, score
+
 
 def check_min_points(min_points) -> int:
     if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= int(min_points) < 2 ** 31:
@@ -555,16 +590,28 @@ def _pose_estimator(device: int, n_cams: int, n_keys: int) -> PoseEstimator:
 
 def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_points: int = 6, max_iter: int = REFINE_DEFAULTS["max_iter"],
                         ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"], gtol: float = REFINE_DEFAULTS["gtol"],
-                        return_residuals: bool = False, device: int = 0) -> ViewPoses:
+                        return_residuals: bool = False, device: int = 0, consensus: int = 0, sample_size: int = 6, inlier_px: float = 8.0,
+                        seed: int = 0) -> ViewPoses:
     """The pose of the known target in every (camera, image) view, on the device (include/pcs_hip.h pcs_pnp_run): what the reference's
     ``target_pose_in_cam_image`` (calibration_targets/abstract_target.py:345-405, cv2.solvePnPGeneric and the solution of lowest error)
     gives ``estimate_camera_relative_poses`` (optimisation/template_handler.py:484-491) per camera and image.
 
     ``dct``: the flattened (N, 5) table [cam, im, key, u, v] in any order; ``points``: the template (K, 3) (or ``target.point_data``);
-    ``intr``: (C, 9) rows [fx, cx, fy, cy, k0, k1, p0, p1, k2]; ``n_imgs``: images of the result (default: largest image index + 1)."""
+    ``intr``: (C, 9) rows [fx, cx, fy, cy, k0, k1, p0, p1, k2]; ``n_imgs``: images of the result (default: largest image index + 1).
+
+    ``consensus`` > 0 puts consensus sampling in front (pcs_pnp_set_consensus; cv2.solvePnPRansac in place of cv2.solvePnPGeneric):
+    that many hypotheses per view, each the linear start of ``sample_size`` random detections, are scored on all detections of the view
+    by sum min(e^2, inlier_px^2); start and LM then use the detections within ``inlier_px`` of the best one, and the result gains
+    ``inliers``, ``n_inliers`` and ``hypothesis``.  A detection with a wrong id (tens to hundreds of pixels off) then no longer bends
+    its view.  Where the defaults come from: 8 px is OpenCV's ``solvePnPRansac`` default ``reprojectionError``; 6 is the fewest points the
+    3-D DLT takes and the default of ``min_points``; a good value of ``consensus`` is 64, log(1 - 0.999) / log(1 - 0.7^6) = 55 rounded up:
+    three nines of confidence at 30 % outliers.  ``seed`` keys the counter-based sampler; the hypothesis count is fixed (no early
+    exit), so two calls agree bit for bit, and a table without outliers gives the bits of ``consensus=0``.  The cached handle is
+    shared: every call states its setting."""
     global last_pnp_kernel_ms
     opts = check_refine_options(max_iter, ftol, xtol, gtol)
     min_points = check_min_points(min_points)
+    cons = check_consensus_options(consensus, sample_size, inlier_px, seed)
     d = np.asarray(dct, dtype=np.float64)
     pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     K = np.asarray(intr, dtype=np.float64)
@@ -580,6 +627,9 @@ def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_poi
                     rms=np.full((C, I), np.nan), rms_init=np.full((C, I), np.nan), status=np.zeros((C, I), dtype=np.int32),
                     iterations=np.zeros((C, I), dtype=np.int32), n_points=np.zeros((C, I), dtype=np.int32),
                     residuals=np.empty((d.shape[0], 2)) if return_residuals else None)
+    if cons[0] > 0:
+        out.inliers = np.zeros(d.shape[0], dtype=bool)
+        out.n_inliers, out.hypothesis = np.zeros((C, I), dtype=np.int32), np.full((C, I), -1, dtype=np.int32)
     if d.shape[0] == 0:
         return out
     order, ids, start = group_by_view(d, I)
@@ -588,10 +638,18 @@ def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_poi
     est.set_cameras(K)
     est.set_template(pts)
     est.set_observations(ds[:, 2].astype(np.int32), ds[:, 3:5], start, (ids // I).astype(np.int32))
+    est.set_consensus(*cons)   # the handle is shared: every call states its setting
     est.run(*opts, min_points=min_points, residuals=return_residuals)
     pose, init, alt, rms, info, resid = est.results()
     last_pnp_kernel_ms = est.last_kernel_ms()
     c, i = ids // I, ids % I
+    if cons[0] > 0:
+        inl, cinfo, _ = est.consensus_results()
+        if order is None:
+            out.inliers = inl
+        else:
+            out.inliers[order] = inl
+        out.n_inliers[c, i], out.hypothesis[c, i] = cinfo[:, 0], cinfo[:, 1]
     out.poses[c, i], out.poses_init[c, i], out.poses_alt[c, i] = pose, init, alt
     out.rms[c, i], out.rms_init[c, i] = rms[:, 0], rms[:, 1]
     out.iterations[c, i], out.status[c, i], out.n_points[c, i] = info[:, 0], info[:, 1], info[:, 2]
@@ -1195,15 +1253,18 @@ def _rig_localiser(device: int, n_cams: int, n_keys: int) -> RigLocaliser:
     return _cached_handle(_rigpose_cache, (int(device), int(n_cams), int(n_keys)), lambda: RigLocaliser(n_cams, n_keys, device))
 
 
-def rig_pose_start(dct, points, intr, ext, n_imgs: int, min_points: int = 6, device: int = 0) -> np.ndarray:
+def rig_pose_start(dct, points, intr, ext, n_imgs: int, min_points: int = 6, device: int = 0, consensus: int = 0, sample_size: int = 6,
+                   inlier_px: float = 8.0, seed: int = 0) -> np.ndarray:
     """A start (I, 6) for ``localise_target`` from the existing pieces: the per-view poses of ``estimate_view_poses``, every camera's
     estimate W[c', i] = inv(E_c') M[c', i] of the image's pose and its error over ALL detections of the image
     (``rig_candidate_scores``); the image takes the finite candidate of lowest error, ties to the lowest camera.  NaN where there is none.
     The start is linear whatever loss ``localise_target`` runs with: the PnP and the scores take no loss, an outlier moves the start
-    and the robust solve works from there."""
+    and the robust solve works from there — unless ``consensus`` > 0 puts consensus sampling in front of the per-view poses
+    (``estimate_view_poses``: ``consensus``, ``sample_size``, ``inlier_px``, ``seed``), which keeps gross outliers out of the candidates."""
     from .pose_seeding import pose_from_4x4, to_4x4
 
-    vp = estimate_view_poses(dct, points, intr, n_imgs=n_imgs, min_points=min_points, device=device)
+    vp = estimate_view_poses(dct, points, intr, n_imgs=n_imgs, min_points=min_points, device=device, consensus=consensus, sample_size=sample_size,
+                             inlier_px=inlier_px, seed=seed)
     W, errors = rig_candidate_scores(dct, points, intr, vp.poses, ext, n_imgs, device=device)
     W, errors = np.asarray(W, dtype=np.float64).reshape(-1, n_imgs, 3, 4), np.asarray(errors, dtype=np.float64).reshape(-1, n_imgs)
     finite = np.isfinite(errors) & np.isfinite(W.reshape(W.shape[0], n_imgs, 12)).all(axis=-1)
@@ -1252,7 +1313,7 @@ def check_localise_arguments(dct, points, intr, ext, n_imgs, poses_init, min_poi
 def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_init=None, min_points: int = 6,
                     max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
                     gtol: float = REFINE_DEFAULTS["gtol"], group_lanes: int | None = None, return_residuals: bool = False,
-                    device: int = 0, loss: str = "linear", f_scale: float = 1.0) -> ImagePoses:
+                    device: int = 0, loss: str = "linear", f_scale: float = 1.0, start_consensus: int = 0) -> ImagePoses:
     """The pose of the known target in every image of a rig whose cameras are held fixed, on the device (include/pcs_hip.h
     pcs_rigpose_run): what the reference's ``find_target_poses`` (optimisation/find_target.py:9-82) gets from a bundle adjustment with
     every camera's "ext" / "int" / "dst" fixed, as one independent 6-parameter problem per image.
@@ -1265,8 +1326,10 @@ def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_
 
     ``loss`` / ``f_scale``: scipy ``least_squares``'s robust losses ('linear', 'huber', 'soft_l1', 'cauchy', 'arctan') on each scalar
     residual, ``f_scale`` in pixels (include/pcs_hip.h pcs_rigpose_set_loss; the reference's commented ``loss = "cauchy"``).  The
-    default start stays the linear one (``rig_pose_start``).  ``diagnostics.robust_weights(res.residuals, loss, f_scale)`` lists what
-    was down-weighted."""
+    default start stays the linear one (``rig_pose_start``); ``start_consensus`` > 0 (64 is a good value) gives its per-view poses that
+    many consensus hypotheses (``estimate_view_poses(consensus=...)``), so that a wrong id cannot put every residual of an image beyond
+    ``f_scale`` before the robust solve begins.  ``diagnostics.robust_weights(res.residuals, loss, f_scale)`` lists what was
+    down-weighted."""
     global last_rigpose_kernel_ms
     loss, f_scale = check_loss(loss, f_scale)
     d, pts, K, E, I, start, min_points, opts, lanes = check_localise_arguments(dct, points, intr, ext, n_imgs, poses_init, min_points, max_iter, ftol, xtol,
@@ -1283,7 +1346,7 @@ def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_
     order, ids, first = group_by_image(d)
     ds = d if order is None else d[order]
     if start is None:
-        start = rig_pose_start(ds, pts, K, E, I, min_points=min_points, device=device)
+        start = rig_pose_start(ds, pts, K, E, I, min_points=min_points, device=device, consensus=check_consensus_options(start_consensus, 6, 8.0, 0)[0])
         out.poses_init[:] = start
     loc = _rig_localiser(device, K.shape[0], pts.shape[0])
     loc.set_cameras(K)

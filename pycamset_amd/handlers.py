@@ -283,7 +283,8 @@ class TemplateBundleHandler:  # th:80-240
             "no start vector has been set: compute one from the detections with calc_initial_params() (template_handler.py:302-346, "
             "device PnP) and hand it to set_initial_params(), or supply your own")
 
-    def calc_initial_params(self, intr=None, *, seeding: str = "reference", refine_poses: bool = False) -> np.ndarray:  # th:302-346
+    def calc_initial_params(self, intr=None, *, seeding: str = "reference", refine_poses: bool = False,
+                            view_consensus: int | None = None) -> np.ndarray:  # th:302-346
         """A start vector from the detections: per-view target poses on the device (``compiled_helpers.estimate_view_poses``), the view
         graph of ``pose_seeding.estimate_camera_relative_poses`` (th:468-601), then the free entries in slab order — unfixed intrinsics,
         extrinsics and poses (plus, for the self and free chains, the free point scalars of the template).  ``intr``: (C, 9) rows
@@ -300,8 +301,15 @@ class TemplateBundleHandler:  # th:80-240
         ``refine_poses``: the seeded pose of an image is ONE camera's estimate, the candidate of lowest error.  When true, every image's
         pose is refined over the detections of all cameras with the seeded extrinsics and intrinsics held fixed
         (``compiled_helpers.localise_target``) before the vector is assembled; an image that could not be refined keeps its seeded pose
-        and the reference image, whose pose is exactly 0 and fixed, is left alone.  Off by default."""
+        and the reference image, whose pose is exactly 0 and fixed, is left alone.  Off by default.
+
+        ``view_consensus``: hypotheses per view of the consensus sampling in front of the per-view poses
+        (``compiled_helpers.estimate_view_poses(consensus=...)``; 64 is a good value), so that detections with a wrong id do not bend
+        the start; default ``options["view_consensus"]``, else 0 (off)."""
         from .pose_seeding import estimate_camera_relative_poses, estimate_camera_relative_poses_graph
+
+        if view_consensus is None:
+            view_consensus = self.problem_opts.get("view_consensus", 0)
 
         if seeding not in ("reference", "graph", "auto"):
             raise ValueError(f"seeding must be 'reference', 'graph' or 'auto', got {seeding!r}")
@@ -322,7 +330,7 @@ class TemplateBundleHandler:  # th:80-240
                 intr[idc] = self.fixed_params[name]["int"]
         n_imgs = bp.poses.shape[0] if "pose" in bp.groups else self.detection.max_ims
         args = (self._flat_detections(), self.point_data.reshape((-1, 3)), intr, n_cams, n_imgs)
-        refs = {"ref_cam": self.problem_opts.get("ref_cam", 0), "ref_pose": self.problem_opts.get("ref_pose", 0)}
+        refs = {"ref_cam": self.problem_opts.get("ref_cam", 0), "ref_pose": self.problem_opts.get("ref_pose", 0), "view_consensus": view_consensus}
         if seeding == "graph":
             seeded = estimate_camera_relative_poses_graph(*args, **refs)
         else:

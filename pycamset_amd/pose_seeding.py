@@ -11,6 +11,7 @@ One deviation on purpose: the reference appends the final per-image costs to the
 2 I values; this returns the I final ones."""
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass
 
 import numpy as np
@@ -62,17 +63,32 @@ def intrinsic_matrices(intr: np.ndarray) -> np.ndarray:
     return K
 
 
+def default_view_pose_fn(view_pose_fn, view_consensus: int):
+    """The ``view_pose_fn`` of the seedings: the caller's, or the device's ``estimate_view_poses`` — with ``view_consensus`` > 0 its
+    consensus sampling with that many hypotheses (``functools.partial(estimate_view_poses, consensus=...)``; a caller who wants other
+    ``sample_size`` / ``inlier_px`` / ``seed`` passes such a partial as ``view_pose_fn`` itself)."""
+    from . import compiled_helpers as ch
+
+    if view_pose_fn is not None:
+        if view_consensus:
+            raise ValueError("view_consensus goes with the default view_pose_fn; bind the keyword into your own with functools.partial")
+        return view_pose_fn
+    n_hyp = ch.check_consensus_options(view_consensus, 6, 8.0, 0)[0]
+    return functools.partial(ch.estimate_view_poses, consensus=n_hyp) if n_hyp else ch.estimate_view_poses
+
+
 def estimate_camera_relative_poses(dct, points, intr, n_cams: int, n_imgs: int, ref_cam: int = 0, ref_pose: int = 0, *, view_pose_fn=None,
-                                   cost_fn=None):
+                                   cost_fn=None, view_consensus: int = 0):
     """-> (extr (C, 6), poses (I, 6), per_im_error (I,), missing (I,) bool).
 
     ``dct`` (N, 5) flattened detections, ``points`` (K, 3) template, ``intr`` (C, 9).  ``view_pose_fn(dct, points, intr, n_imgs=...)``
     returns an object with ``poses`` (C, I, 6) (default: the device's ``estimate_view_poses``); ``cost_fn`` has the signature of
     ``bundle_adjustment_costfn`` (default: the device's).  ``ref_cam`` is accepted for the reference's signature; as there, the world
-    frame is the target of the reference pose, whichever camera is named.  ``missing[i]``: no camera estimated image i."""
+    frame is the target of the reference pose, whichever camera is named.  ``missing[i]``: no camera estimated image i.
+    ``view_consensus`` > 0: the default ``view_pose_fn`` with that many consensus hypotheses per view (``default_view_pose_fn``)."""
     from . import compiled_helpers as ch
 
-    view_pose_fn = ch.estimate_view_poses if view_pose_fn is None else view_pose_fn
+    view_pose_fn = default_view_pose_fn(view_pose_fn, view_consensus)
     cost_fn = ch.bundle_adjustment_costfn if cost_fn is None else cost_fn
     dct = np.ascontiguousarray(dct, dtype=np.float64)
     points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
@@ -190,7 +206,7 @@ class RigGraphInfo:
 
 
 def estimate_camera_relative_poses_graph(dct, points, intr, n_cams: int, n_imgs: int, ref_cam: int = 0, ref_pose: int = 0, *, view_pose_fn=None,
-                                         edge_fn=None, score_fn=None, return_graph: bool = False):
+                                         edge_fn=None, score_fn=None, return_graph: bool = False, view_consensus: int = 0):
     """-> (extr (C, 6), poses (I, 6), per_im_error (I,), missing (I,) bool) like ``estimate_camera_relative_poses``, for any rig whose
     co-visibility graph is connected: no image has to be seen by every camera.
 
@@ -206,10 +222,12 @@ def estimate_camera_relative_poses_graph(dct, points, intr, n_cams: int, n_imgs:
        and takes the pose of the previous non-missing image (of the first one, when none precedes it).
     4. The world becomes the target of ``ref_pose`` (of the first non-missing image, when that one is missing): that pose is exactly 0.
 
-    ``per_im_error`` is NaN for missing images.  ``return_graph=True`` appends a ``RigGraphInfo``."""
+    ``per_im_error`` is NaN for missing images.  ``return_graph=True`` appends a ``RigGraphInfo``.  ``view_consensus`` > 0: the default
+    ``view_pose_fn`` with that many consensus hypotheses per view (``default_view_pose_fn``): the medoid of step 1 protects an edge
+    against a wrong VIEW, the consensus repairs a view that holds wrong detections."""
     from . import compiled_helpers as ch
 
-    view_pose_fn = ch.estimate_view_poses if view_pose_fn is None else view_pose_fn
+    view_pose_fn = default_view_pose_fn(view_pose_fn, view_consensus)
     edge_fn = ch.rig_edge_consensus if edge_fn is None else edge_fn
     score_fn = ch.rig_candidate_scores if score_fn is None else score_fn
     dct = np.ascontiguousarray(dct, dtype=np.float64)
@@ -299,7 +317,9 @@ def resect_cameras(dct, points, intr, image_poses, *, view_pose_fn=None, **opts)
     held fixed — a camera added to a calibrated rig.  No kernel of its own: the world points T_i X_k of all images form one "template"
     of I * K points with key' = i * K + k, every camera is one view of it, and the batched PnP
     (``view_pose_fn(dct', points', intr, n_imgs=1, **opts)``, default ``compiled_helpers.estimate_view_poses``) does the rest.
-    ``image_poses`` (I, 6) = [rotvec, t], target -> world; images with a NaN pose are dropped from the table first."""
+    ``image_poses`` (I, 6) = [rotvec, t], target -> world; images with a NaN pose are dropped from the table first.  ``opts`` reach
+    ``estimate_view_poses`` as they are: ``consensus=64`` (with ``sample_size``, ``inlier_px``, ``seed``) resects every camera from
+    the consensus of its detections, so that a few wrong ids do not bend the new camera."""
     from . import compiled_helpers as ch
 
     view_pose_fn = ch.estimate_view_poses if view_pose_fn is None else view_pose_fn
