@@ -660,6 +660,35 @@ int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms);
 int pcs_tri_set_refine_loss(pcs_triangulator *t, int kind, double f_scale);
 int pcs_tri_get_refine_loss(pcs_triangulator *t, int *kind, double *f_scale);
 int pcs_tri_refine_costs(pcs_triangulator *t, double *cost);
+/* View-pair consensus in front of the triangulation (csrc/ba_tri_consensus.hpp; since pcs_version() 116), opt-in: what the two-view RANSAC
+ * of COLMAP's and OpenCV's n-view triangulation is to their DLT.  One mismatched view drags the DLT start of its point, and the refinement
+ * starts there.  With the stage on, n_hypotheses PAIRS of views per point are triangulated by the same kernel pcs_tri_run launches
+ * (pcs_tri_launch_config), each candidate is scored on every view of the point by sum min(e^2, inlier_px^2) — e the reprojection error in
+ * the measured pixels, the projection of pcs_tri_refine; inlier_px^2 for a view with a non-finite measurement or projection or a depth
+ * <= 0 — and the DLT of pcs_tri_run and pcs_tri_refine then work on the views within inlier_px of the best candidate (ties: the lower
+ * hypothesis).  A point with V views takes all V (V - 1) / 2 pairs in lexicographic order when they are at most n_hypotheses; otherwise
+ * the pairs come from a counter-based sampler keyed by (seed, index of the point in the handle's observations, V, hypothesis): one
+ * 64-bit draw r gives a = r mod V and b = (r >> 32) mod (V - 1), bumped past a.  The hypothesis count is fixed, so two runs agree bit for
+ * bit, and a table without outliers gives the bits of the plain run.  The stage waits for nothing on the host.
+ *   pcs_tri_set_consensus     n_hypotheses = 0 (the default) turns the stage off: pcs_tri_run and pcs_tri_refine then queue what they
+ *                             always queued and allocate nothing more.  PCS_ERR_ARG: NULL handle, a negative count, n_hypotheses > 256,
+ *                             inlier_px not finite or <= 0; a refused call keeps the previous setting.  The setting belongs to the
+ *                             handle and survives new cameras and observations, however they are set (host, device,
+ *                             pcs_tri_group_device).
+ *   pcs_tri_get_consensus     the setting in force (any pointer may be NULL)
+ *   pcs_tri_consensus_results copy what the stage of the last run found to the host (blocking, any pointer may be NULL): inlier (n_obs)
+ *                             one flag per observation; cinfo (n_pts, 4) int32 {inliers, winning hypothesis or -1, hypotheses with a
+ *                             finite candidate, consensus used}; score (n_pts) the winner's sum (+inf: no finite candidate, NaN:
+ *                             consensus not used).  A point with fewer than 3 views takes the plain path (all flagged, consensus used
+ *                             = 0); a point without a finite candidate, or whose winner has fewer than 2 inliers, keeps no row (inliers
+ *                             0) and is not determined: three NaNs, like a point without views; a NaN measurement is never an inlier.
+ *                             With the stage on, d_rms of pcs_tri_refine is over the inliers, d_info keeps the point's full view count,
+ *                             d_resid holds the residuals of ALL observations at the returned point, and pcs_tri_refine_costs counts
+ *                             the inliers.  pcs_tri_last_kernel_ms and pcs_tri_last_refine_ms include the stage's kernels.
+ *                             PCS_ERR_STATE when the last run had no consensus stage. */
+int pcs_tri_set_consensus(pcs_triangulator *t, int n_hypotheses, double inlier_px, uint64_t seed);
+int pcs_tri_get_consensus(pcs_triangulator *t, int *n_hypotheses, double *inlier_px, uint64_t *seed);
+int pcs_tri_consensus_results(pcs_triangulator *t, uint8_t *inlier, int32_t *cinfo, double *score);
 
 /* ------------------------------------------------------------------------------------------------
  * Batched target-pose estimation, PnP (csrc/ba_pnp.hpp).  Since pcs_version() 105.

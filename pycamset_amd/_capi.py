@@ -150,6 +150,9 @@ SYMBOLS = {
     "pcs_tri_get_refine_loss": (c_int, [_P, POINTER(c_int), POINTER(c_double)]),
     "pcs_tri_refine_costs": (c_int, [_P, POINTER(c_double)]),
     "pcs_tri_last_refine_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_tri_set_consensus": (c_int, [_P, c_int, c_double, c_uint64]),
+    "pcs_tri_get_consensus": (c_int, [_P, POINTER(c_int), POINTER(c_double), POINTER(c_uint64)]),
+    "pcs_tri_consensus_results": (c_int, [_P, POINTER(c_uint8), POINTER(c_int32), POINTER(c_double)]),
     "pcs_pnp_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_pnp_destroy": (c_int, [_P]),
     "pcs_pnp_set_cameras": (c_int, [_P, POINTER(c_double)]),

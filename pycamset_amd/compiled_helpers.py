@@ -104,7 +104,10 @@ class TriangulationResult:
     points, points_dlt: (n, 3) refined and DLT points; rms, rms_dlt: (n,) RMS reprojection error sqrt(sum_v |r_v|^2 / n_v) in pixels at
     them (rms <= rms_dlt without a loss); n_views, iterations (LM trials), status (TRI_*): (n,) int32; residuals: (n_obs, 2)
     uv - pi(points) in the observation order, or None; cost: (n,) scipy's 0.5 sum rho0 of the refinement's loss at the points (half
-    the sum of squares without one), or None for a result that was not fetched with it."""
+    the sum of squares without one), or None for a result that was not fetched with it.  With the consensus stage (``consensus`` > 0):
+    inliers (n_obs,) bool, the rows the points were computed from; n_inliers (n,) int32; consensus_used (n,) bool (False: fewer than
+    three views, the plain path); score (n,) the winner's sum min(e^2, inlier_px^2); rms is over the inliers, n_views the full count
+    and residuals cover every row.  All four are None when the stage was off."""
     points: np.ndarray
     points_dlt: np.ndarray
     rms: np.ndarray
@@ -114,6 +117,22 @@ class TriangulationResult:
     status: np.ndarray
     residuals: np.ndarray | None = None
     cost: np.ndarray | None = None
+    inliers: np.ndarray | None = None
+    n_inliers: np.ndarray | None = None
+    consensus_used: np.ndarray | None = None
+    score: np.ndarray | None = None
+
+
+TRI_CONSENSUS_MAX = 256   # hypotheses per point that pcs_tri_set_consensus takes
+
+
+def check_tri_consensus_options(consensus, inlier_px, seed):
+    """Validate the consensus options of the triangulation on the host (ValueError) before anything is queued: the checks of
+    pcs_tri_set_consensus (``check_consensus_options`` with its own hypothesis limit and no sample size: a sample is a pair of views)."""
+    if isinstance(consensus, bool) or not isinstance(consensus, (int, np.integer)) or not 0 <= int(consensus) <= TRI_CONSENSUS_MAX:
+        raise ValueError(f"consensus must be an integer in [0, {TRI_CONSENSUS_MAX}], got {consensus!r}")
+    _, _, px, sd = check_consensus_options(0, 4, inlier_px, seed)
+    return int(consensus), px, sd
 
 
 def _cached_handle(cache: dict, key, factory):
@@ -283,6 +302,33 @@ class Triangulator(_Handle):
     def last_refine_ms(self) -> float:
         return self._ms("pcs_tri_last_refine_ms")
 
+    def set_consensus(self, n_hypotheses: int = 0, inlier_px: float = 8.0, seed: int = 0):
+        """The consensus stage of the runs that follow (pcs_tri_set_consensus): ``n_hypotheses`` view pairs per point are triangulated
+        and scored on all views of the point, DLT and refinement work on the views within ``inlier_px`` of the best.  0 = off (the
+        default).  It stays with the handle until it is set again."""
+        self._call("pcs_tri_set_consensus", self._h, *check_tri_consensus_options(n_hypotheses, inlier_px, seed))
+
+    def get_consensus(self):
+        """The current (n_hypotheses, inlier_px, seed) of ``set_consensus``."""
+        h, px, seed = self._ct.c_int(), self._ct.c_double(), self._ct.c_uint64()
+        self._call("pcs_tri_get_consensus", self._h, self._ct.byref(h), self._ct.byref(px), self._ct.byref(seed))
+        return h.value, px.value, seed.value
+
+    def consensus_results(self):
+        """Wait for the last ``run`` with a consensus stage: (inlier (n_obs,) bool, cinfo (n_pts, 4) int32 = [inliers, winning
+        hypothesis, finite hypotheses, consensus used], score (n_pts,))."""
+        n = max(self.n_pts, 0)
+        inlier, cinfo, score = np.empty(self._n_obs, dtype=np.uint8), np.empty((n, 4), dtype=np.int32), np.empty(n)
+        self._call("pcs_tri_consensus_results", self._h, self._ptr(inlier), self._ptr(cinfo), self._ptr(score))
+        return inlier.astype(bool), cinfo, score
+
+    def with_consensus(self, res: "TriangulationResult") -> "TriangulationResult":
+        """``res`` with what the stage of the last ``run`` found (nothing when that run had none)."""
+        if self.get_consensus()[0] > 0:
+            inl, cinfo, score = self.consensus_results()
+            res.inliers, res.n_inliers, res.consensus_used, res.score = inl, cinfo[:, 0].copy(), cinfo[:, 3] != 0, score
+        return res
+
 
 _tri_cache: dict = {}
 
@@ -291,11 +337,13 @@ def _triangulator(device: int, n_cams: int) -> Triangulator:
     return _cached_handle(_tri_cache, (int(device), int(n_cams)), lambda: Triangulator(n_cams, device))
 
 
-def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0) -> np.ndarray:
+def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0, *, consensus: int = 0, inlier_px: float = 8.0, seed: int = 0) -> np.ndarray:
     """``data`` rows = [cam, ..., u, v] sorted by point; ``start_inds`` (n_pts + 1) like the reference
     (compiled_helpers.py:609-643).  Returns (n_pts, 3).  A ``Triangulator`` per (device, camera count) is kept
-    across calls: camera table and buffers are reused."""
+    across calls: camera table and buffers are reused.  ``consensus`` > 0 puts the view-pair consensus in front
+    (``Triangulator.set_consensus``; 64 is a good value): the points come from the views within ``inlier_px`` of the best pair."""
     global last_triangulate_kernel_ms
+    cons = check_tri_consensus_options(consensus, inlier_px, seed)
     data = np.asarray(data, dtype=np.float64)
     P = np.asarray(proj, dtype=np.float64)
     start = np.asarray(start_inds, dtype=np.int64)
@@ -304,6 +352,7 @@ def nb_triangulate_full(data, proj, start_inds, intr, dist, device: int = 0) -> 
     tri = _triangulator(device, P.shape[0])
     tri.set_cameras(P, intr, dist)
     tri.set_observations(data[:, 0].astype(np.int32), data[:, -2:], start)
+    tri.set_consensus(*cons)   # the handle is shared: every call states its setting
     tri.run()
     pts = tri.points()
     last_triangulate_kernel_ms = tri.last_kernel_ms()
@@ -318,16 +367,21 @@ def _empty_result(return_residuals: bool) -> TriangulationResult:
 
 def refine_triangulation(data, proj, start_inds, intr, dist, *, max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"],
                          xtol: float = REFINE_DEFAULTS["xtol"], gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False,
-                         device: int = 0, loss: str = "linear", f_scale: float = 1.0) -> TriangulationResult:
+                         device: int = 0, loss: str = "linear", f_scale: float = 1.0, consensus: int = 0, inlier_px: float = 8.0,
+                         seed: int = 0) -> TriangulationResult:
     """``nb_triangulate_full`` followed by the per-point refinement of the reprojection error in the measured (distorted) pixels
     (include/pcs_hip.h pcs_tri_refine): DLT and refinement are queued back to back on the device, one synchronisation at the end.
     ``data`` rows = [cam, ..., u, v] sorted by point, ``start_inds`` (n_pts + 1).  Returns a ``TriangulationResult``; with
     ``return_residuals`` its ``residuals`` are (n_obs, 2) in the rows' order.  ``loss`` / ``f_scale``: a robust loss on each scalar
     residual (``Triangulator.set_refine_loss``); the DLT start is the plain one, ``rms`` stays the plain pixel RMS and ``residuals`` the
-    raw ones (``diagnostics.robust_weights`` lists what was down-weighted)."""
+    raw ones (``diagnostics.robust_weights`` lists what was down-weighted).  ``consensus`` > 0 (64 is a good value) puts the view-pair
+    consensus in front of the DLT (``Triangulator.set_consensus``, with ``inlier_px`` and ``seed``): a loss only helps while the start
+    is in the right basin, the stage keeps a mismatched view out of the start.  The result then carries ``inliers``, ``n_inliers``,
+    ``consensus_used`` and ``score``; two calls agree bit for bit, and a table without outliers gives the bits of ``consensus=0``."""
     global last_triangulate_kernel_ms
     opts = check_refine_options(max_iter, ftol, xtol, gtol)
     loss, f_scale = check_loss(loss, f_scale)
+    cons = check_tri_consensus_options(consensus, inlier_px, seed)
     data = np.asarray(data, dtype=np.float64)
     P = np.asarray(proj, dtype=np.float64)
     start = np.asarray(start_inds, dtype=np.int64)
@@ -338,17 +392,19 @@ def refine_triangulation(data, proj, start_inds, intr, dist, *, max_iter: int = 
     tri = _triangulator(device, P.shape[0])
     tri.set_cameras(P, intr, dist)
     tri.set_observations(data[:, 0].astype(np.int32), data[:, -2:], start)
+    tri.set_consensus(*cons)             # the handle is shared between calls: every call states its setting
     tri.run()
-    tri.set_refine_loss(loss, f_scale)   # the handle is shared between calls: every call states its loss
+    tri.set_refine_loss(loss, f_scale)   # ... and its loss
     tri.refine(*opts, residuals=return_residuals)
-    res = tri.refined()
+    res = tri.with_consensus(tri.refined())
     last_triangulate_kernel_ms = tri.last_kernel_ms()
     return res
 
 
 def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: int = 0, *, refine: bool = False, return_result: bool = False,
                           max_iter: int = REFINE_DEFAULTS["max_iter"], ftol: float = REFINE_DEFAULTS["ftol"], xtol: float = REFINE_DEFAULTS["xtol"],
-                          gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False, loss: str = "linear", f_scale: float = 1.0):
+                          gtol: float = REFINE_DEFAULTS["gtol"], return_residuals: bool = False, loss: str = "linear", f_scale: float = 1.0,
+                          consensus: int = 0, inlier_px: float = 8.0, seed: int = 0):
     """``CameraSet.multi_cam_triangulate`` for a detection table (cameras/camera_set.py:343-402, the array branch): ``data`` rows =
     [cam, image, key..., u, v] as ``TargetDetection.get_data`` returns them; the features seen by more than one camera are
     triangulated, in order of first appearance.  Grouping (``np.unique`` twice in the reference: 0.37 s for 1e6 rows) AND
@@ -359,9 +415,12 @@ def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: 
     ftol, xtol, gtol), grouping, DLT and refinement queued back to back, one synchronisation at the end.  ``return_result=True``
     returns the ``TriangulationResult`` (points, RMS errors, status, with ``return_residuals`` the residuals in the order of the kept
     rows) instead of the points; without ``refine`` it carries the DLT points and their RMS (a refinement with max_iter = 0).  The
-    default returns the DLT points, as before.  ``loss`` / ``f_scale``: the robust loss of the refinement (``refine_triangulation``)."""
+    default returns the DLT points, as before.  ``loss`` / ``f_scale``: the robust loss of the refinement (``refine_triangulation``).
+    ``consensus`` / ``inlier_px`` / ``seed``: the view-pair consensus in front of the DLT (``refine_triangulation``), on both grouping
+    paths; the result carries its ``inliers`` (in the order of the kept rows), ``n_inliers``, ``consensus_used`` and ``score``."""
     global last_triangulate_kernel_ms
     loss, f_scale = check_loss(loss, f_scale)
+    cons = check_tri_consensus_options(consensus, inlier_px, seed)
     with_result = refine or return_result
     if with_result:
         opts = check_refine_options(max_iter if refine else 0, ftol, xtol, gtol)
@@ -379,11 +438,13 @@ def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: 
     if tri is None:                                                         # host grouping
         rec, start = group_reconstructable(table)
         if not with_result:
-            return nb_triangulate_full(rec, P, start, intr, D, device=device)
+            return nb_triangulate_full(rec, P, start, intr, D, device=device, consensus=cons[0], inlier_px=cons[1], seed=cons[2])
         return out(refine_triangulation(rec, P, start, intr, D, max_iter=opts[0], ftol=opts[1], xtol=opts[2], gtol=opts[3],
-                                        return_residuals=return_residuals, device=device, loss=loss, f_scale=f_scale))
+                                        return_residuals=return_residuals, device=device, loss=loss, f_scale=f_scale, consensus=cons[0],
+                                        inlier_px=cons[1], seed=cons[2]))
     if n_pts == 0:
         return empty()
+    tri.set_consensus(*cons)   # the handle is shared: every call states its setting
     tri.run()
     if not with_result:
         pts = tri.points()
@@ -391,7 +452,7 @@ def multi_cam_triangulate(data, proj, intr, dist, distort: bool = True, device: 
         return pts
     tri.set_refine_loss(loss, f_scale)
     tri.refine(*opts, residuals=return_residuals)
-    res = tri.refined()
+    res = tri.with_consensus(tri.refined())
     last_triangulate_kernel_ms = tri.last_kernel_ms()
     return out(res)
 

@@ -41,6 +41,7 @@
 #include "ba_tri_refine.hpp"
 #include "ba_pnp.hpp"
 #include "ba_pnp_consensus.hpp"
+#include "ba_tri_consensus.hpp"
 #include "ba_rigpose.hpp"
 #include "ba_intrinsics.hpp"
 #include "ba_riggraph.hpp"

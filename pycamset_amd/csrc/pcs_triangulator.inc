@@ -1,4 +1,5 @@
-// pcs_triangulator.inc — host side of the batched triangulation (included by pcs_engine.hip; kernels: ba_triangulate.hpp, ba_tri_refine.hpp).
+// pcs_triangulator.inc — host side of the batched triangulation (included by pcs_engine.hip; kernels: ba_triangulate.hpp, ba_tri_refine.hpp,
+// ba_tri_consensus.hpp).
 // Fence, buffers and output slots are those of pcs_handle.inc (DESIGN.md, "Batched handles").
 extern "C" {
 // ---- batched triangulation (SURVEY f4): a handle that owns the camera table, the observation buffers and the
@@ -30,6 +31,14 @@ struct pcs_triangulator {
     HandleLoss refine_loss;          // pcs_tri_set_refine_loss: the handle's, whatever cameras and observations follow
     int refine_owned = 0;            // PCS_TRI_OUT_* bits: which outputs of the last refinement are handle-owned
     bool refine_valid = false;       // a refinement since the last run (pcs_tri_refined has something to return)
+    // the consensus stage (pcs_tri_set_consensus; kernels: ba_tri_consensus.hpp).  cons_hyp = 0: off, and none of these buffers exists.
+    int cons_hyp = 0;
+    double cons_px = 8.0;
+    uint64_t cons_seed = 0;
+    bool cons_ran = false;                         // the last run had the stage: it and its refinement work on the compacted table
+    DevBuf s_cam, s_uv, s_start, h_pts;            // the pseudo-points of the sampled pairs and their hypotheses
+    DevBuf score, flag, cinfo, best;               // (n_pts, H) scores; per observation flag; per point record and winning score
+    DevBuf c_cam, c_uv, c_start, c_order;          // the table compacted to inliers and its visiting order
 };
 
 int pcs_tri_create(pcs_triangulator **out, int device, int64_t n_cams) {
@@ -82,7 +91,8 @@ int pcs_tri_launch_config(pcs_triangulator *t, int32_t out[4]) {
 int pcs_tri_destroy(pcs_triangulator *t) {
     if (!t) return PCS_OK;
     t->core.destroy({&t->tab, &t->cam, &t->uv, &t->start, &t->scr, &t->scl, &t->pts, &t->count, &t->block_sums, &t->totals, &t->order, &t->hist, &t->rpts,
-                     &t->rrms, &t->rres, &t->rinfo, &t->rcost},
+                     &t->rrms, &t->rres, &t->rinfo, &t->rcost, &t->s_cam, &t->s_uv, &t->s_start, &t->h_pts, &t->score, &t->flag, &t->cinfo, &t->best,
+                     &t->c_cam, &t->c_uv, &t->c_start, &t->c_order},
                     {&t->timer, &t->refine_timer});
     delete t;
     return PCS_OK;
@@ -193,11 +203,140 @@ int pcs_tri_group_device(pcs_triangulator *t, int64_t n, const int32_t *d_cam, c
     return PCS_OK;
 }
 
+// One launch of the triangulation kernel that tri_launch names, on any table: the handle's observations, the pseudo-points of the
+// consensus stage, the table compacted to inliers.  e0 / e1: the events of hipExtLaunchKernelGGL around the kernel, or NULL.
+static void tri_launch_dlt(pcs_triangulator *t, const TriLaunch &launch, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const int32_t *cam, const double *uv,
+                           const int64_t *start, double *d_pts, int64_t n_pts, const int32_t *order) {
+    const int lanes = launch.lanes;
+    const dim3 grid((unsigned)((n_pts * lanes + 255) / 256));
+#define PCS_TRI_LAUNCH(G_)                                                                                                                       \
+    hipExtLaunchKernelGGL(triangulate_kernel<G_>, grid, dim3(256), 0, s, e0, e1, 0, cam, (const double2 *)uv, start, t->tab.as<const double>(), \
+                          t->scr.as<double4>(), t->scl.as<double2>(), d_pts, n_pts)
+#define PCS_TRI_LAUNCH_REG(G_, V_)                                                                                                                       \
+    hipExtLaunchKernelGGL((triangulate_reg_kernel<G_, V_>), grid, dim3(256), 0, s, e0, e1, 0, cam, (const double2 *)uv, start, t->tab.as<const double>(), \
+                          t->scr.as<double4>(), t->scl.as<double2>(), d_pts, n_pts, order)
+    if (launch.reg_views == 0) {   // round 3's form (views in the global scratch, IEEE divides): kept for A/B (PCS_TRI_VARIANT=0)
+        if (lanes == 1) PCS_TRI_LAUNCH(1);
+        else if (lanes == 2) PCS_TRI_LAUNCH(2);
+        else if (lanes == 8) PCS_TRI_LAUNCH(8);
+        else if (lanes == 16) PCS_TRI_LAUNCH(16);
+        else PCS_TRI_LAUNCH(4);
+    } else {                 // views in registers (6 or 8 per lane; further ones in the scratch), divide-free rotations
+        if (lanes == 1) PCS_TRI_LAUNCH_REG(1, 8);
+        else if (lanes == 2) PCS_TRI_LAUNCH_REG(2, 8);
+        else if (lanes == 8) PCS_TRI_LAUNCH_REG(8, 8);
+        else if (lanes == 16) PCS_TRI_LAUNCH_REG(16, 8);
+        else if (launch.reg_views == 8) PCS_TRI_LAUNCH_REG(4, 8);
+        else PCS_TRI_LAUNCH_REG(4, 6);   // 24 views in registers at 156 VGPRs (three waves per SIMD): 47 us against 52 us for (4, 8); (4, 3) — four waves
+                                         // per SIMD, 12 register views, the rest through the scratch records — 53 us, (4, 4) 49 us (profiles/r05/tri_bench_r05.log)
+    }
+#undef PCS_TRI_LAUNCH_REG
+#undef PCS_TRI_LAUNCH
+}
+
+constexpr int TRI_CONS_MAX_HYP = 256;   // hypotheses per point that pcs_tri_set_consensus takes
+constexpr int TRI_CONS_G = 4;           // lanes per point and per (point, hypothesis) of the stage: the DLT kernel's default
+
+// The stage in front of the DLT (the two-view RANSAC in front of an n-view triangulation).  Everything is checked before anything
+// changes: a refused call keeps the previous setting.
+int pcs_tri_set_consensus(pcs_triangulator *t, int n_hypotheses, double inlier_px, uint64_t seed) {
+    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_set_consensus: NULL handle");
+    if (n_hypotheses < 0 || n_hypotheses > TRI_CONS_MAX_HYP || !std::isfinite(inlier_px) || !(inlier_px > 0.0))
+        return fail(PCS_ERR_ARG, "pcs_tri_set_consensus: bad arguments (0 <= n_hypotheses <= %d, inlier_px finite and > 0)", TRI_CONS_MAX_HYP);
+    t->cons_hyp = n_hypotheses;
+    t->cons_px = inlier_px;
+    t->cons_seed = seed;
+    return PCS_OK;
+}
+
+int pcs_tri_get_consensus(pcs_triangulator *t, int *n_hypotheses, double *inlier_px, uint64_t *seed) {
+    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_get_consensus: NULL handle");
+    if (n_hypotheses) *n_hypotheses = t->cons_hyp;
+    if (inlier_px) *inlier_px = t->cons_px;
+    if (seed) *seed = t->cons_seed;
+    return PCS_OK;
+}
+
+// A run with the consensus stage: used counts and their scan, sample, hypotheses by the handle's unchanged triangulation kernel on the
+// pseudo-points, score, select, scan, compact; then the order and the DLT, unchanged, on the compacted table.  No host synchronisation:
+// the compacted table is never longer than the handle's, so nothing on the host needs its total.
+static int tri_run_consensus(pcs_triangulator *t, double *d_pts, void *stream) {
+    const TriLaunch launch = tri_launch(t);
+    const int64_t np = t->n_pts, H = t->cons_hyp, nh = np * H, no = std::max<int64_t>(1, t->n_obs);
+    if (np > 0 && nh > ((int64_t)INT32_MAX * 256) / 16)
+        return fail(PCS_ERR_ARG, "pcs_tri_run: %lld points x %lld hypotheses are more than one launch takes", (long long)np, (long long)H);
+    const bool sorted = launch.sorted && np < (1ll << 31);
+    // the scratch kernel keeps a record per observation, pseudo-points included; the register kernels hold two views in registers
+    const int64_t scr_need = launch.reg_views == 0 ? std::max<int64_t>(no, 2 * nh) : no;
+    struct Need { DevBuf &buf; int64_t count; size_t bytes; };
+    const Need need[] = {{t->scr, scr_need, 4 * sizeof(double)}, {t->scl, scr_need, 2 * sizeof(double)},
+                         {t->s_cam, 2 * nh, sizeof(int32_t)}, {t->s_uv, 2 * nh, 2 * sizeof(double)}, {t->s_start, nh + 1, sizeof(int64_t)},
+                         {t->h_pts, nh, 3 * sizeof(double)}, {t->score, nh, sizeof(double)}, {t->flag, no, sizeof(uint8_t)},
+                         {t->cinfo, np, 4 * sizeof(int32_t)}, {t->best, np, sizeof(double)}, {t->c_cam, no, sizeof(int32_t)},
+                         {t->c_uv, no, 2 * sizeof(double)}, {t->c_start, np + 1, sizeof(int64_t)}, {t->c_order, sorted ? np : 1, sizeof(int32_t)}};
+    OutSlot out{1, t->pts, d_pts, np, 3 * sizeof(double)};
+    bool grows = false;
+    for (const Need &n : need) grows = grows || n.buf.grows(std::max<int64_t>(1, n.count));
+    const bool owned = owned_slots(&out, 1, &grows);
+    if (np == 0) {
+        t->run_valid = true;
+        t->run_pts = d_pts;
+        t->cons_ran = true;
+        return PCS_OK;
+    }
+    HIPCHK(hipSetDevice(t->core.device));
+    hipStream_t s = t->core.stream_or(stream);
+    HIPCHK(t->core.fence.before_run(s, grows));
+    int rc = grow_owned_slots(&out, 1);
+    for (const Need &n : need)
+        if (!rc) rc = n.buf.grow(std::max<int64_t>(1, n.count), n.bytes);
+    if (rc) return rc;
+    d_pts = out.as<double>();
+    HIPCHK(hipEventRecord(t->timer.e0, s));   // after every allocation: nothing is queued by a call that fails in one
+    const int32_t *cam = t->cur_cam;
+    const double2 *uv = (const double2 *)t->cur_uv;
+    const int64_t *start = t->cur_start;
+    const double *tab = t->tab.as<const double>();
+    const double tau2 = t->cons_px * t->cons_px;
+    constexpr int G = TRI_CONS_G;
+    const dim3 per_pt((unsigned)((np + 255) / 256)), pt_groups((unsigned)((np * G + 255) / 256)), hyp_groups((unsigned)((nh * G + 255) / 256));
+    // c_start first holds the row bases of the pseudo-table (the scan of the used counts), then the starts of the compacted table
+    hipLaunchKernelGGL(tri_cons_used_kernel, per_pt, dim3(256), 0, s, start, np, (int)H, t->cinfo.as<int32_t>());
+    hipLaunchKernelGGL(tri_count_scan_kernel, dim3(1), dim3(TRI_SCAN_THREADS), 0, s, t->cinfo.as<const int32_t>(), np, t->c_start.as<int64_t>());
+    hipLaunchKernelGGL(tri_sample_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, cam, uv, start, t->c_start.as<const int64_t>(), np, (int)H,
+                       t->cons_seed, t->s_cam.as<int32_t>(), t->s_uv.as<double2>(), t->s_start.as<int64_t>());
+    tri_launch_dlt(t, launch, s, nullptr, nullptr, t->s_cam.as<const int32_t>(), t->s_uv.as<const double>(), t->s_start.as<const int64_t>(),
+                   t->h_pts.as<double>(), nh, nullptr);
+    hipLaunchKernelGGL((tri_score_kernel<G, false>), hyp_groups, dim3(256), 0, s, cam, uv, start, tab, np, (int)H, t->h_pts.as<const double>(), tau2,
+                       t->score.as<double>(), (double *)nullptr);
+    hipLaunchKernelGGL((tri_select_kernel<G>), pt_groups, dim3(256), 0, s, cam, uv, start, tab, np, (int)H, t->h_pts.as<const double>(),
+                       t->score.as<const double>(), tau2, t->flag.as<uint8_t>(), t->cinfo.as<int32_t>(), t->best.as<double>());
+    hipLaunchKernelGGL(tri_count_scan_kernel, dim3(1), dim3(TRI_SCAN_THREADS), 0, s, t->cinfo.as<const int32_t>(), np, t->c_start.as<int64_t>());
+    hipLaunchKernelGGL((pnp_compact_kernel<G>), pt_groups, dim3(256), 0, s, cam, uv, start, t->flag.as<const uint8_t>(), t->c_start.as<const int64_t>(), np,
+                       t->c_cam.as<int32_t>(), t->c_uv.as<double2>());
+    HIPCHK(hipGetLastError());
+    if (sorted)
+        if ((rc = enqueue_group_order(t->c_start.as<int64_t>(), np, t->hist.as<int32_t>(), t->c_order.as<int32_t>(), s))) return rc;
+    tri_launch_dlt(t, launch, s, nullptr, nullptr, t->c_cam.as<const int32_t>(), t->c_uv.as<const double>(), t->c_start.as<const int64_t>(), d_pts, np,
+                   sorted ? t->c_order.as<const int32_t>() : nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(t->timer.e1, s));
+    t->timer.timed = true;
+    t->out_owned = owned;
+    t->run_valid = true;
+    t->run_pts = d_pts;
+    t->cons_ran = true;
+    HIPCHK(t->core.fence.after_run(s));
+    return PCS_OK;
+}
+
 int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
     if (!t) return fail(PCS_ERR_ARG, "pcs_tri_run: bad arguments");
     if (!t->have_cams) return fail(PCS_ERR_STATE, "pcs_tri_run: cameras not set");
     if (t->n_pts < 0) return fail(PCS_ERR_STATE, "pcs_tri_run: observations not set");
     t->refine_valid = false;
+    if (t->cons_hyp > 0) return tri_run_consensus(t, d_pts, stream);
+    t->cons_ran = false;
     if (t->n_pts == 0) {
         t->run_valid = true;
         t->run_pts = d_pts;
@@ -218,36 +357,12 @@ int pcs_tri_run(pcs_triangulator *t, double *d_pts, void *stream) {
     if (!rc && need_order) rc = t->order.grow(t->n_pts, sizeof(int32_t));
     if (rc) return rc;
     d_pts = out.as<double>();
-    const int lanes = launch.lanes;
-    const dim3 grid((unsigned)((t->n_pts * lanes + 255) / 256));
     if (need_order) {
         if ((rc = enqueue_group_order(t->cur_start, t->n_pts, t->hist.as<int32_t>(), t->order.as<int32_t>(), s))) return rc;
         t->order_valid = true;
     }
-#define PCS_TRI_LAUNCH(G_)                                                                                                                   \
-    hipExtLaunchKernelGGL(triangulate_kernel<G_>, grid, dim3(256), 0, s, t->timer.e0, t->timer.e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
-                          t->cur_start, t->tab.as<const double>(), t->scr.as<double4>(), t->scl.as<double2>(), d_pts, t->n_pts)
-#define PCS_TRI_LAUNCH_REG(G_, V_)                                                                                                                   \
-    hipExtLaunchKernelGGL((triangulate_reg_kernel<G_, V_>), grid, dim3(256), 0, s, t->timer.e0, t->timer.e1, 0, t->cur_cam, (const double2 *)t->cur_uv, \
-                          t->cur_start, t->tab.as<const double>(), t->scr.as<double4>(), t->scl.as<double2>(), d_pts, t->n_pts,                          \
-                          t->order_valid ? t->order.as<const int32_t>() : nullptr)
-    if (launch.reg_views == 0) {   // round 3's form (views in the global scratch, IEEE divides): kept for A/B (PCS_TRI_VARIANT=0)
-        if (lanes == 1) PCS_TRI_LAUNCH(1);
-        else if (lanes == 2) PCS_TRI_LAUNCH(2);
-        else if (lanes == 8) PCS_TRI_LAUNCH(8);
-        else if (lanes == 16) PCS_TRI_LAUNCH(16);
-        else PCS_TRI_LAUNCH(4);
-    } else {                 // views in registers (6 or 8 per lane; further ones in the scratch), divide-free rotations
-        if (lanes == 1) PCS_TRI_LAUNCH_REG(1, 8);
-        else if (lanes == 2) PCS_TRI_LAUNCH_REG(2, 8);
-        else if (lanes == 8) PCS_TRI_LAUNCH_REG(8, 8);
-        else if (lanes == 16) PCS_TRI_LAUNCH_REG(16, 8);
-        else if (launch.reg_views == 8) PCS_TRI_LAUNCH_REG(4, 8);
-        else PCS_TRI_LAUNCH_REG(4, 6);   // 24 views in registers at 156 VGPRs (three waves per SIMD): 47 us against 52 us for (4, 8); (4, 3) — four waves
-                                         // per SIMD, 12 register views, the rest through the scratch records — 53 us, (4, 4) 49 us (profiles/r05/tri_bench_r05.log)
-    }
-#undef PCS_TRI_LAUNCH_REG
-#undef PCS_TRI_LAUNCH
+    tri_launch_dlt(t, launch, s, t->timer.e0, t->timer.e1, t->cur_cam, t->cur_uv, t->cur_start, d_pts, t->n_pts,
+                   t->order_valid ? t->order.as<const int32_t>() : nullptr);
     HIPCHK(hipGetLastError());
     t->timer.timed = true;
     t->out_owned = owned;
@@ -296,6 +411,35 @@ int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, 
         if (const int rc = t->rcost.grow(t->n_pts, 2 * sizeof(double))) return rc;
     constexpr int G = 4, V = 6;   // the DLT kernel's default geometry (profiles/r09: resources and time)
     const dim3 grid((unsigned)((t->n_pts * G + 255) / 256));
+    if (t->cons_ran) {   // the last run had the consensus stage: the same kernels on the table compacted to its inliers
+        const int32_t *c_order = tri_launch(t).sorted && t->n_pts < (1ll << 31) ? t->c_order.as<const int32_t>() : nullptr;
+        int32_t *info = out[TRI_SLOT_INFO].as<int32_t>();
+        HIPCHK(hipEventRecord(t->refine_timer.e0, s));
+        if (!robust) {
+            hipLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->c_cam.as<const int32_t>(), t->c_uv.as<const double2>(),
+                               t->c_start.as<const int64_t>(), t->tab.as<const double>(), t->run_pts, t->n_pts, c_order, max_iter, ftol, xtol, gtol,
+                               out[TRI_SLOT_POINTS].as<double>(), out[TRI_SLOT_RMS].as<double>(), info, (double *)nullptr);
+        } else {
+            hipLaunchKernelGGL((triangulate_refine_kernel<G, V, GroupLoss, double *>), grid, dim3(256), 0, s, t->c_cam.as<const int32_t>(),
+                               t->c_uv.as<const double2>(), t->c_start.as<const int64_t>(), t->tab.as<const double>(), t->run_pts, t->n_pts, c_order, max_iter,
+                               ftol, xtol, gtol, out[TRI_SLOT_POINTS].as<double>(), out[TRI_SLOT_RMS].as<double>(), info, (double *)nullptr,
+                               t->refine_loss.args(), t->rcost.as<double>());
+        }
+        // what callers see: the full view count in info, and the residuals of ALL observations at the returned point, outliers included
+        hipLaunchKernelGGL(tri_consensus_finish_kernel, dim3((unsigned)((t->n_pts + 255) / 256)), dim3(256), 0, s, t->cur_start, t->n_pts, info);
+        if (want_resid)
+            hipLaunchKernelGGL((tri_score_kernel<TRI_CONS_G, true>), grid, dim3(256), 0, s, t->cur_cam, (const double2 *)t->cur_uv, t->cur_start,
+                               t->tab.as<const double>(), t->n_pts, 1, (const double *)out[TRI_SLOT_POINTS].as<double>(), 0.0, (double *)nullptr,
+                               out[TRI_SLOT_RESID].as<double>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(t->refine_timer.e1, s));
+        t->rlin = {out[TRI_SLOT_RMS].as<double>(), t->c_start.as<const int64_t>(), !robust};   // 0.5 n rms^2 with n the inliers
+        t->refine_timer.timed = true;
+        t->refine_owned = owned;
+        t->refine_valid = true;
+        HIPCHK(t->core.fence.after_run(s));
+        return PCS_OK;
+    }
     // PCS_LOSS_LINEAR launches the kernel a handle without a loss always launched; any other kind its robust twin, which writes the costs itself
     if (!robust) {
         hipExtLaunchKernelGGL((triangulate_refine_kernel<G, V>), grid, dim3(256), 0, s, t->refine_timer.e0, t->refine_timer.e1, 0, t->cur_cam,
@@ -338,6 +482,16 @@ int pcs_tri_refine_costs(pcs_triangulator *t, double *cost) {
     if (!t || !cost) return fail(PCS_ERR_ARG, "pcs_tri_refine_costs: bad arguments");
     if (!t->refine_valid) return fail(PCS_ERR_STATE, "pcs_tri_refine_costs: no refinement since the last run (pcs_tri_refine first)");
     return fetch_costs(t->core, t->rcost, t->rlin, cost, t->n_pts, "pcs_tri_refine_costs");
+}
+
+// What the consensus stage of the last run found: blocking, any pointer may be NULL.
+int pcs_tri_consensus_results(pcs_triangulator *t, uint8_t *inlier, int32_t *cinfo, double *score) {
+    if (!t) return fail(PCS_ERR_ARG, "pcs_tri_consensus_results: NULL handle");
+    if (!t->run_valid) return fail(PCS_ERR_STATE, "pcs_tri_consensus_results: no run on the current cameras and observations (pcs_tri_run first)");
+    if (!t->cons_ran) return fail(PCS_ERR_STATE, "pcs_tri_consensus_results: the last run had no consensus stage (pcs_tri_set_consensus)");
+    const OutSlot out[] = {{1, t->flag, inlier, t->n_obs, sizeof(uint8_t)}, {2, t->cinfo, cinfo, t->n_pts, 4 * sizeof(int32_t)},
+                           {4, t->best, score, t->n_pts, sizeof(double)}};
+    return fetch_slots(t->core, out, 3, 7, t->n_pts != 0, "pcs_tri_consensus_results", "");
 }
 
 int pcs_tri_last_refine_ms(pcs_triangulator *t, float *kernel_ms) {

@@ -2,8 +2,10 @@
 """Triangulation refinement (pcs_tri_refine) at config 3 (the rig of tools/tri_bench.py): DLT alone against DLT + refinement as
 device-event kernel times, the iteration histogram, RMS before and after, and the work the refinement did (view evaluations).
 
-    python tools/tri_refine_bench.py [--reps 20] [--residuals] [--loss KIND] [--f-scale F]
+    python tools/tri_refine_bench.py [--reps 20] [--residuals] [--loss KIND] [--f-scale F] [--consensus H] [--inlier-px PX]
 ``--loss`` runs the robust instantiation of the refinement kernel (Triangulator.set_refine_loss; linear, the default, is the kernel without a loss).
+``--consensus H`` puts the view-pair consensus in front (Triangulator.set_consensus; 0, the default, is the run without the stage): "DLT" is then
+the stage and the DLT on the inliers, "refinement" the refinement of the inliers with the finish step.
 Kernel times from rocprofv3 in a separate run:
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o tri_refine -- python tools/tri_refine_bench.py --reps 5
 """
@@ -22,6 +24,8 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--residuals", action="store_true", help="also write the per-observation residuals")
 ap.add_argument("--loss", default="linear", help="linear (default), huber, soft_l1, cauchy or arctan")
 ap.add_argument("--f-scale", type=float, default=1.0)
+ap.add_argument("--consensus", type=int, default=0, help="hypotheses per point of the view-pair consensus (0: off)")
+ap.add_argument("--inlier-px", type=float, default=8.0)
 args = ap.parse_args()
 
 rig = synthetic.config_rig(3)
@@ -42,6 +46,8 @@ tri.set_cameras(P, Kc, D)
 tri.set_observations(rec[:, 0].astype(np.int32), rec[:, -2:], start)
 if args.loss != "linear":   # a library without the robust kernel still runs the linear case
     tri.set_refine_loss(args.loss, args.f_scale)
+if args.consensus > 0:      # ... and one without the stage the plain run
+    tri.set_consensus(args.consensus, args.inlier_px, 0)
 for _ in range(3):   # warm-up: code objects, visiting order, buffers
     tri.run(); tri.refine(residuals=args.residuals); tri.refined()
 dlt_alone, dlt, ref = [], [], []
@@ -54,8 +60,13 @@ res = tri.refined()
 med = lambda x: float(np.median(x)) * 1e3   # noqa: E731  (us)
 print(f"device events, median of {args.reps}:  DLT alone {med(dlt_alone):7.1f} us   |   DLT {med(dlt):7.1f} us + refinement {med(ref):7.1f} us "
       f"= {med(dlt) + med(ref):7.1f} us   (refinement / DLT = {np.median(ref) / np.median(dlt):.2f}){'  [with residuals]' if args.residuals else ''}"
-      f"  [loss {args.loss}, f_scale {args.f_scale:g}; refinement min {min(ref) * 1e3:.1f} max {max(ref) * 1e3:.1f} us]")
+      f"  [loss {args.loss}, f_scale {args.f_scale:g}; consensus {args.consensus}; refinement min {min(ref) * 1e3:.1f} max {max(ref) * 1e3:.1f} us]")
 
+if args.consensus > 0:
+    inl, cinfo, _ = tri.consensus_results()
+    used = cinfo[:, 3] != 0
+    print(f"consensus: {args.consensus} hypotheses, inlier_px {args.inlier_px:g}: used at {int(used.sum())} of {n_pts} points, {int(inl.sum())} inliers of {n_obs} "
+          f"observations, {int(np.sum(used & (cinfo[:, 0] == 0)))} points without a kept row; DLT min {min(dlt) * 1e3:.1f} max {max(dlt) * 1e3:.1f} us")
 its = res.iterations
 hist = np.bincount(its, minlength=hc.REFINE_DEFAULTS["max_iter"] + 1)
 print("iterations (LM trials) histogram: " + "  ".join(f"{k}:{v}" for k, v in enumerate(hist) if v))
