@@ -237,3 +237,130 @@ def test_ranks_on_their_own_gpus_over_rccl(tmp_path):
     world = min(8, torch.cuda.device_count())
     mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), "nccl"), nprocs=world, join=True)
     assert all((tmp_path / f"ok{r}").exists() for r in range(world))
+
+
+# ---- real shards with noise weights, a robust loss and a prior through lm_solve, one process per rank ------------------------------------
+SPAWN_TIME_LIMIT = 300.0        # seconds: a rank left alone in a collective ends the test instead of hanging the suite
+
+
+def _spawn(fn, args, world):
+    import time
+    ctx = mp.spawn(fn, args=args, nprocs=world, join=False)
+    deadline = time.monotonic() + SPAWN_TIME_LIMIT
+    while not ctx.join(timeout=2.0):          # raises as soon as one rank has failed (and ends the others)
+        if time.monotonic() > deadline:
+            for proc in ctx.processes:
+                proc.kill()
+            pytest.fail(f"the ranks did not finish within {SPAWN_TIME_LIMIT:.0f} s")
+
+
+def _settings_worker(rank, world, port, out_dir, backend="gloo"):
+    """Three ranks hold 60 %, 40 % and none of the ring-4 table (tests/sharded_sum_reference.py ``split(det, "empty")``), each with
+    its own slice of a per-detection sigma; every setting is solved sharded and — on rank 0 — unsharded on the whole table."""
+    import datetime
+    sys.path.insert(0, str(REPO))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    rccl = backend == "nccl"
+    device = rank if rccl else 0
+    torch.cuda.set_device(device)
+    limit = datetime.timedelta(seconds=120)
+    if rccl:
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", device), timeout=limit)
+    else:
+        dist.init_process_group("gloo", rank=rank, world_size=world, timeout=limit)
+    try:
+        from pycamset_amd import handlers, sharding
+        from pycamset_amd.detections import TargetDetection
+        from pycamset_amd.device_solver import lm_solve
+        from tests import prior_reference as PR
+        from tests import sharded_sum_reference as S
+
+        assert world == 3
+        vec_reduce = sharding.allreduce_sum_fn(device=torch.device("cuda", device) if rccl else None)
+        mat_reduce = sharding.allreduce_sum_tensor_fn() if rccl else sharding.allreduce_sum_fn()
+        gathered = [None] * world
+
+        def same_on_every_rank(res):
+            dist.all_gather_object(gathered, (res.x, res.nit, res.nfev, res.status))
+            assert all(np.array_equal(gathered[0][0], g[0]) and gathered[0][1:] == g[1:] for g in gathered), [g[1:] for g in gathered]
+
+        def from_rank0(value):
+            box = [value]
+            dist.broadcast_object_list(box, src=0)
+            return box[0]
+
+        for chain in ("template", "self"):
+            for setting in ("weights", "weights+huber", "prior", "prior+weights+huber"):
+                p = S.problem("ring4", chain, setting)
+                rig, det, n = p.rig, p.det, p.det.shape[0]
+                names = [f"cam_{i}" for i in range(rig.n_cams)]
+                vis = np.isin(np.arange(rig.n_keys), det[:, 2])
+                cls, extra = (handlers.TemplateBundleHandler, {}) if chain == "template" else (handlers.SelfBundleHandler, {"visible_feature_mask": vis})
+
+                def handler(rows):     # the GLOBAL layout on every rank: counts, max_ims and, for self, the visibility mask
+                    return cls(_Camset(rig.n_cams), _Target(rig.points), TargetDetection(names, rows, max_ims=rig.n_imgs),
+                               fixed_params={"cam_0": {"ext": rig.extr_true[0].copy()}}, options={"verbosity": 0}, counts=p.counts, device=device, **extra)
+
+                def solve(h, reduce_fn, sigma, **kw):
+                    prior = {} if p.free_prior is None else dict(prior_mean=p.free_prior[0], prior_sigma=p.free_prior[1])
+                    return lm_solve(h, p.x0.copy(), max_iter=200, reduce_fn=reduce_fn, loss=p.loss, f_scale=p.f_scale, sigma=sigma, **prior, **kw)
+
+                def check_against(res, one, tol, what):
+                    cost = from_rank0(None if one is None else one.cost)
+                    assert abs(res.cost - cost) <= tol * cost, (what, rank, res.cost, cost)
+                    if p.free_prior is not None:       # the prior is counted once, whatever the number of ranks
+                        w = PR.weights_of(p.free_prior[1])
+                        assert res.prior_cost > 0.0 and abs(res.prior_cost - PR.prior_half_sum(res.x, p.free_prior[0], w)) <= 1e-12 * res.prior_cost, (what, rank)
+                    same_on_every_rank(res)
+
+                what = f"{chain} {setting}"
+                parts = p.parts("empty")
+                mine = det[parts[rank]]
+                assert [det[r].shape[0] for r in parts] == [(6 * n) // 10, n - (6 * n) // 10, 0]
+                sig = None if p.sigma is None else {"detection": p.sigma["detection"][parts[rank]]}
+                h_shard = handler(mine)
+                h_full = handler(det) if rank == 0 else None
+                assert np.array_equal(h_shard._jac_mask(), p.mask)
+                res = solve(h_shard, mat_reduce, sig)
+                one = solve(h_full, None, p.sigma) if rank == 0 else None
+                check_against(res, one, 1e-9, what)
+                if setting == "prior":     # matrix-free products: _PriorOperator wraps the REDUCED products, it is not reduced itself
+                    cg = solve(h_shard, vec_reduce, None, linear_solver="pcg")
+                    cg1 = solve(h_full, None, None, linear_solver="pcg") if rank == 0 else None
+                    assert cg.n_jtjv > cg.nfev
+                    check_against(cg, cg1, 1e-3, what + " pcg")
+                if setting == "weights" and chain == "template":
+                    # the split of sharding.shard_rows, the sigma through sharding.shard_sigma: the slices match
+                    per = sharding.shard_rows(n, world)
+                    rows = slice(rank * per, (rank + 1) * per)
+                    part = sharding.shard_sigma(p.sigma, n, rank, world)
+                    assert np.array_equal(part["detection"], p.sigma["detection"][rows]) and part["detection"].shape[0] == det[rows].shape[0]
+                    bare = sharding.shard_sigma(p.sigma["detection"], n, rank, world)
+                    assert np.array_equal(bare["detection"], part["detection"])
+                    eq = solve(handler(det[rows]), mat_reduce, part)
+                    check_against(eq, one, 1e-9, what + " shard_rows")
+                torch.cuda.synchronize()
+                eng = h_shard.op_fun._engine_for(h_shard._flat_detections())
+                assert eng.n == mine.shape[0]
+                assert eng.prior() is None and eng.weights() is None and eng.loss() == ("linear", 1.0), (what, rank)
+        Path(out_dir, f"ok{rank}").write_text("ok")
+    finally:
+        dist.destroy_process_group()
+
+
+def test_three_ranks_with_weights_loss_and_prior_on_one_gpu(tmp_path):
+    """60 % / 40 % / empty shards of ring-4 over gloo, template and self: linear + sigma, huber + sigma, linear + prior (also through
+    linear_solver="pcg"), huber + sigma + prior, each against the unsharded solve of the whole table: cost within 1e-9 relative (1e-3
+    for pcg), the prior's half sum counted once, the same (x, nit, nfev, status) bits on every rank, the engines' settings restored."""
+    world = 3
+    _spawn(_settings_worker, (world, _free_port(), str(tmp_path), "gloo"), world)
+    assert all((tmp_path / f"ok{r}").exists() for r in range(world))
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 3, reason="RCCL needs one GPU per rank: this box has fewer than three")
+def test_three_ranks_with_weights_loss_and_prior_over_rccl(tmp_path):
+    """The same worker with backend nccl (RCCL), one device per rank: the device-steered sharded loop under a real all-reduce."""
+    world = 3
+    _spawn(_settings_worker, (world, _free_port(), str(tmp_path), "nccl"), world)
+    assert all((tmp_path / f"ok{r}").exists() for r in range(world))

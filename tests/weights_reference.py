@@ -37,20 +37,21 @@ def chain_inputs(chain):
     return rig, rig.detections, orc.build_param_list(*H.chain_slabs(rig, chain)), (rig.points if chain == "template" else None)
 
 
-def whitened_jacobian(chain, det, ps, tm, w):
-    """(J~ = diag(w) J as CSR over the full parameter string, f~ = w f)."""
-    dense, r = orc.full_jac_dense(chain, det, ps, tm, with_resid=True)
-    idx, ptr, _ = orc.csr_structure(chain, det, np.ones(ps.shape[0], bool))
+def whitened_jacobian(chain, det, ps, tm, w, counts=None):
+    """(J~ = diag(w) J as CSR over the full parameter string, f~ = w f).  ``counts``: the (cameras, images, keys) of the layout when
+    ``det`` is a slice of a larger table (a rank's shard) that may not reach the last index of each."""
+    dense, r = orc.full_jac_dense(chain, det, ps, tm, with_resid=True, counts=counts)
+    idx, ptr, _ = orc.csr_structure(chain, det, np.ones(ps.shape[0], bool), counts=counts)
     J = csr_array((dense.reshape(-1), idx, ptr), shape=(2 * det.shape[0], ps.shape[0]))
     wr = rows_of(w)
     return csr_array(diags(wr) @ J), wr * r.reshape(-1)
 
 
-def weighted_system(chain, det, ps, tm, w, loss="linear", f_scale=1.0):
+def weighted_system(chain, det, ps, tm, w, loss="linear", f_scale=1.0, counts=None):
     """(J~^T J~, J~^T r~, sum rho0, slack of H) of the whitened system through scipy's loss and scale_for_robust_loss_function; the slack
     is that of ``_oracle_system``: rows where rho1 + 2 rho2 f^2 cancels to rounding level (huber beyond f_scale) carry a weight^2 of
     anything in [EPS, a few EPS], bounded by 16 EPS |J~_i|^T |J~_i| summed over those rows."""
-    J, f = whitened_jacobian(chain, det, ps, tm, w)
+    J, f = whitened_jacobian(chain, det, ps, tm, w, counts)
     if loss == "linear":
         return (J.T @ J).toarray(), J.T @ f, float(f @ f), 0.0
     rho = construct_loss_function(f.size, loss, f_scale)(f, cost_only=False)
