@@ -6,7 +6,8 @@ marker does.  ``calc_initial_params`` seeds the calibration twice: with the plai
 linear start) and with ``view_consensus=64`` (64 hypotheses of 6 detections per view, scored on all of them; start and LM use the
 detections within 8 px of the best one — cv2.solvePnPRansac in place of cv2.solvePnPGeneric).  Both starts are then solved with
 ``lm_solve(loss="cauchy")``.  Printed: how far each seed's camera and image poses are from the truth, what the consensus flagged, and
-the focal errors after the solve.
+the focal errors after the solve.  The intrinsics are given here; where they have to be estimated from the same detections first, the
+stage in front needs its own consensus: ``examples/outlier_intrinsics.py`` (``intrinsics_consensus=64``).
 
     python examples/outlier_seeding.py [--hypotheses 64] [--moved 0.03]
 """

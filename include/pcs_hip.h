@@ -877,7 +877,33 @@ int pcs_rigpose_costs(pcs_rig_localiser *p, double *cost);
  *                              PCS_ERR_ARG: NULL handle, unknown model, min_points < 4, a non-finite or non-positive res.
  *   pcs_intr_results           copy handle-owned outputs of the last run to the host (any pointer may be NULL; blocking)
  *                              (replaces the camera matrix cv2.calibrateCamera returns, abstract_target.py:313-333)
- *   pcs_intr_last_kernel_ms    device time of the last run: both kernels.
+ *   pcs_intr_last_kernel_ms    device time of the last run: both kernels, and the consensus stage when it is on.
+ *
+ * Consensus sampling (csrc/ba_intr_consensus.hpp; since pcs_version() 117), opt-in: what cv2.findHomography(..., RANSAC) is to the plain
+ * fit, at the same place in the pipeline (abstract_target.py:263-343).  One detection with a wrong id bends the homography of its group,
+ * and a few bent homographies lose the camera.  With the stage on, n_hypotheses samples of sample_size detections per group are fitted
+ * by the same homography kernel, every hypothesis is scored on all detections of the group by sum min(e^2, inlier_px^2) of the transfer
+ * error e = uv - H q (tau^2 for a non-finite term and for a point beyond the plane's horizon), and the homography and camera kernels
+ * then run on the detections within inlier_px of the best hypothesis.  The sampler is the PnP stage's: counter-based, keyed by (seed,
+ * camera, observations of the group, hypothesis); the hypothesis count is fixed, so two runs agree bit for bit, and a table without
+ * outliers gives the bits of the plain run.  A homography knows no lens distortion: inlier_px has to cover what the lens bends.
+ *   pcs_intr_set_consensus     n_hypotheses = 0 (the default) turns the stage off: pcs_intr_run then queues what it always queued and
+ *                              allocates nothing more.  Otherwise cv2.findHomography's maxIters, the sample (4 <= sample_size <= 16),
+ *                              ransacReprojThreshold and the seed of the generator.  PCS_ERR_ARG: NULL handle, a negative count,
+ *                              n_hypotheses > 4096, sample_size outside [4, 16], inlier_px not finite or <= 0; a refused call keeps
+ *                              the previous setting.
+ *   pcs_intr_get_consensus     the setting in force (any pointer may be NULL; cv2.findHomography's arguments, which it does not keep)
+ *   pcs_intr_consensus_results copy what the stage of the last run found to the host (cv2.findHomography's `mask`; blocking, any
+ *                              pointer may be NULL): inlier (n_obs) one flag per observation; cinfo (n_groups, 4) int32 {inliers, winning
+ *                              hypothesis or -1, hypotheses with a finite homography, consensus used}; score (n_groups) the winner's
+ *                              sum min(e^2, inlier_px^2) (+inf: no finite hypothesis, NaN: consensus not used).  A group with fewer
+ *                              observations than max(sample_size, min_points) takes the plain path (all flagged, consensus used = 0);
+ *                              so does a group without a finite hypothesis (all flagged, consensus used = 1), whose status then names
+ *                              the reason as the plain run does (NOT_PLANAR, NOT_FINITE); a group whose winner has fewer than
+ *                              min_points inliers is PCS_INTR_GROUP_TOO_FEW; a NaN measurement is never an inlier.  With the stage on,
+ *                              d_group_info keeps the group's observation count, and the camera's normalising centre weights the
+ *                              groups by their inlier counts: every output is the plain run's on the inlier rows.
+ *                              PCS_ERR_STATE when the last run had no consensus stage.
  */
 typedef struct pcs_intrinsics_estimator pcs_intrinsics_estimator;
 enum { PCS_INTR_MODEL_AUTO = 0, PCS_INTR_MODEL_FULL = 1, PCS_INTR_MODEL_FOCAL = 2 };
@@ -906,6 +932,9 @@ int pcs_intr_run(pcs_intrinsics_estimator *p, int model, int min_points, const d
 int pcs_intr_results(pcs_intrinsics_estimator *p, double *intr, int32_t *cam_info, double *eig_ratio, double *homographies, double *frames,
                      int32_t *group_info, double *pixel_stats);
 int pcs_intr_last_kernel_ms(pcs_intrinsics_estimator *p, float *kernel_ms);
+int pcs_intr_set_consensus(pcs_intrinsics_estimator *p, int n_hypotheses, int sample_size, double inlier_px, uint64_t seed);
+int pcs_intr_get_consensus(pcs_intrinsics_estimator *p, int *n_hypotheses, int *sample_size, double *inlier_px, uint64_t *seed);
+int pcs_intr_consensus_results(pcs_intrinsics_estimator *p, uint8_t *inlier, int32_t *cinfo, double *score);
 
 /* ------------------------------------------------------------------------------------------------
  * View-graph seeding of a rig (csrc/ba_riggraph.hpp).  Since pcs_version() 107.

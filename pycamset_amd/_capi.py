@@ -185,6 +185,9 @@ SYMBOLS = {
     "pcs_intr_results": (c_int, [_P, POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int32),
                                  POINTER(c_double)]),
     "pcs_intr_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_intr_set_consensus": (c_int, [_P, c_int, c_int, c_double, c_uint64]),
+    "pcs_intr_get_consensus": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_uint64)]),
+    "pcs_intr_consensus_results": (c_int, [_P, POINTER(c_uint8), POINTER(c_int32), POINTER(c_double)]),
     "pcs_rig_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64, c_int64]),
     "pcs_rig_destroy": (c_int, [_P]),
     "pcs_rig_set_cameras": (c_int, [_P, POINTER(c_double)]),

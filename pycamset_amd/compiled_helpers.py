@@ -737,7 +737,12 @@ class IntrinsicsEstimate:
     constrain the model).  Per (camera, image, board) group: ``homographies`` (G, 3, 3) pixels <- metric plane frame, ``plane_frames``
     (G, 9) = [centroid, e1, e2] of that frame in template coordinates, ``group_status`` (INTR_GROUP_*), ``group_counts``,
     ``group_index`` (G, 3) = [cam, im, board].  With ``refine=True``: ``intr_init`` the closed form, ``intr`` the refined rows,
-    ``rms_init`` / ``rms`` (C,) RMS reprojection error in pixels before and after, ``lm`` the ``DeviceLMResult``."""
+    ``rms_init`` / ``rms`` (C,) RMS reprojection error in pixels before and after, ``lm`` the ``DeviceLMResult``.  With the consensus
+    stage (``consensus`` > 0): ``inliers`` (N,) bool in the order of the caller's table, the rows the homographies (and the refinement)
+    were computed from; per group ``group_inliers`` (G,) int32, ``group_hypothesis`` (G,) int32 the winning hypothesis (-1: none),
+    ``group_consensus_used`` (G,) bool (False: fewer observations than max(sample_size, min_points), the plain path) and
+    ``group_score`` (G,) the winner's sum min(e^2, inlier_px^2) (+inf: no finite hypothesis, NaN: not used); ``group_counts`` stays the
+    observation count.  All five are None without the stage."""
     intr: np.ndarray
     status: np.ndarray
     n_groups: np.ndarray
@@ -751,6 +756,11 @@ class IntrinsicsEstimate:
     rms_init: np.ndarray | None = None
     rms: np.ndarray | None = None
     lm: object | None = None
+    inliers: np.ndarray | None = None
+    group_inliers: np.ndarray | None = None
+    group_hypothesis: np.ndarray | None = None
+    group_consensus_used: np.ndarray | None = None
+    group_score: np.ndarray | None = None
 
 
 class IntrinsicsEstimator(_Handle):
@@ -762,7 +772,7 @@ class IntrinsicsEstimator(_Handle):
     def __init__(self, n_cams: int, n_keys: int, device: int = 0):
         super().__init__(device, n_cams, n_keys)
         self.n_cams, self.n_keys, self.device = int(n_cams), int(n_keys), int(device)
-        self.n_groups = 0
+        self.n_groups, self.n_obs = 0, 0
 
     def set_template(self, points):
         pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
@@ -780,10 +790,10 @@ class IntrinsicsEstimator(_Handle):
         if start.ndim != 1 or start.shape[0] < 1 or gcam.shape != (start.shape[0] - 1,) or uv.shape != (key.shape[0], 2):
             raise ValueError("expected key (n_obs,), uv (n_obs, 2), start_inds (n_groups + 1,), group_cam (n_groups,)")
         self._call("pcs_intr_set_observations", self._h, key.shape[0], self._ptr(key), self._ptr(uv), start.shape[0] - 1, self._ptr(start), self._ptr(gcam))
-        self.n_groups = start.shape[0] - 1
+        self.n_groups, self.n_obs = start.shape[0] - 1, key.shape[0]
 
     def run(self, model: str = "auto", min_points: int = 13, res=None, stream: int | None = None):
-        """Queue the two kernels (asynchronous; handle-owned outputs, fetched with ``results()``).  ``res``: (n_cams, 2) = (h, w) or None."""
+        """Queue the two kernels, behind the consensus stage when ``set_consensus`` turned it on (asynchronous; handle-owned outputs, fetched with ``results()``).  ``res``: (n_cams, 2) = (h, w) or None."""
         model_id, min_points = check_intrinsics_options(model, min_points)
         r = None if res is None else check_res(res, self.n_cams)
         self._call("pcs_intr_run", self._h, model_id, min_points, self._ptr(r), None, None, None, None, None, None, None, _stream_arg(stream))
@@ -799,6 +809,24 @@ class IntrinsicsEstimator(_Handle):
 
     def last_kernel_ms(self) -> float:
         return self._ms("pcs_intr_last_kernel_ms")
+
+    def set_consensus(self, n_hypotheses: int = 0, sample_size: int = 6, inlier_px: float = 8.0, seed: int = 0):
+        """The consensus stage of the runs that follow (pcs_intr_set_consensus: cv2.findHomography's maxIters, the sample,
+        ransacReprojThreshold and a seed); ``n_hypotheses = 0`` turns it off."""
+        self._call("pcs_intr_set_consensus", self._h, *check_consensus_options(n_hypotheses, sample_size, inlier_px, seed))
+
+    def get_consensus(self):
+        """(n_hypotheses, sample_size, inlier_px, seed) in force."""
+        h, s, px, seed = self._ct.c_int(0), self._ct.c_int(0), self._ct.c_double(0.0), self._ct.c_uint64(0)
+        self._call("pcs_intr_get_consensus", self._h, self._ct.byref(h), self._ct.byref(s), self._ct.byref(px), self._ct.byref(seed))
+        return int(h.value), int(s.value), float(px.value), int(seed.value)
+
+    def consensus_results(self):
+        """Wait for the last ``run`` with a consensus stage: (inlier (n_obs,) bool, cinfo (n_groups, 4) int32 = [inliers, winning
+        hypothesis, finite hypotheses, consensus used], score (n_groups,))."""
+        inlier, cinfo, score = np.zeros(self.n_obs, dtype=np.uint8), np.zeros((self.n_groups, 4), dtype=np.int32), np.empty(self.n_groups)
+        self._call("pcs_intr_consensus_results", self._h, self._ptr(inlier), self._ptr(cinfo), self._ptr(score))
+        return inlier.astype(bool), cinfo, score
 
 
 def check_intrinsics_options(model, min_points):
@@ -846,7 +874,8 @@ def _intrinsics_estimator(device: int, n_cams: int, n_keys: int) -> IntrinsicsEs
 
 
 def estimate_intrinsics(dct, points, *, n_cams: int | None = None, n_imgs: int | None = None, board_of_key=None, res=None, model: str = "auto",
-                        min_points: int = 13, refine: bool = False, device: int = 0, **lm_opts) -> IntrinsicsEstimate:
+                        min_points: int = 13, refine: bool = False, device: int = 0, consensus: int = 0, sample_size: int = 6,
+                        inlier_px: float = 8.0, seed: int = 0, **lm_opts) -> IntrinsicsEstimate:
     """Camera intrinsics from the detections of a target made of planar boards, on the device (include/pcs_hip.h pcs_intr_run): what the
     reference's ``AbstractTarget.initial_calibration`` (calibration_targets/abstract_target.py:263-343) gets from cv2.calibrateCamera,
     as Zhang's closed form with zero skew (``model="full"``) or OpenCV's initCameraMatrix2D form (``"focal"``: the principal point
@@ -858,9 +887,21 @@ def estimate_intrinsics(dct, points, *, n_cams: int | None = None, n_imgs: int |
 
     ``refine=True`` runs the device LM (``device_solver.lm_solve``, options ``lm_opts``) on projection + extrinsic3D + template
     points with every extrinsic fixed at identity, one free pose per (camera, image) view (started by ``estimate_view_poses`` at the
-    closed form) and all nine intrinsics of every estimated camera free.  Cameras and views without an estimate stay out of it."""
+    closed form) and all nine intrinsics of every estimated camera free.  Cameras and views without an estimate stay out of it.
+
+    ``consensus`` > 0 puts consensus sampling in front of the homographies (pcs_intr_set_consensus; cv2.findHomography's RANSAC in place
+    of the plain fit): that many hypotheses per group, each the homography of ``sample_size`` random detections, are scored on all
+    detections of the group by sum min(e^2, inlier_px^2); the closed form then uses the detections within ``inlier_px`` of the best one,
+    and the result gains ``inliers``, ``group_inliers``, ``group_hypothesis``, ``group_consensus_used`` and ``group_score``.  A detection
+    with a wrong id (tens to hundreds of pixels off) then no longer costs its camera the estimate.  64 is a good value (see
+    ``estimate_view_poses``); ``seed`` keys the counter-based sampler and the hypothesis count is fixed, so two calls agree bit for bit,
+    and a table without outliers gives the bits of ``consensus=0``.  A homography cannot model lens distortion: ``inlier_px`` must
+    cover what the lens moves a detection by, or good rows at the image's edge are lost.  With ``refine=True`` the per-view poses and
+    the LM run on the inlier rows only: rows beyond ``inlier_px`` are kept out of the refinement too.  The cached handle is shared:
+    every call states its setting."""
     global last_intrinsics_kernel_ms
     check_intrinsics_options(model, min_points)
+    cons = check_consensus_options(consensus, sample_size, inlier_px, seed)
     if lm_opts and not refine:
         raise ValueError(f"options {sorted(lm_opts)} belong to the refinement: pass refine=True")
     d = np.asarray(dct, dtype=np.float64)
@@ -882,6 +923,9 @@ def estimate_intrinsics(dct, points, *, n_cams: int | None = None, n_imgs: int |
         out = IntrinsicsEstimate(intr=np.full((C, 9), np.nan), status=z, n_groups=z.copy(), eig_ratio=np.full(C, np.nan), homographies=np.empty((0, 3, 3)),
                                  plane_frames=np.empty((0, 9)), group_status=np.empty(0, dtype=np.int32), group_counts=np.empty(0, dtype=np.int32),
                                  group_index=np.empty((0, 3), dtype=np.int64))
+        if cons[0] > 0:
+            out.inliers, out.group_inliers, out.group_hypothesis = np.zeros(d.shape[0], dtype=bool), z[:0].copy(), z[:0].copy()
+            out.group_consensus_used, out.group_score = np.zeros(0, dtype=bool), np.empty(0)
     else:
         order, gid, start = group_by_board(d, I, bok, n_boards)
         ds = d if order is None else d[order]
@@ -889,13 +933,22 @@ def estimate_intrinsics(dct, points, *, n_cams: int | None = None, n_imgs: int |
         est = _intrinsics_estimator(device, C, K)
         est.set_template(pts)
         est.set_observations(ds[:, 2].astype(np.int32), ds[:, 3:5], start, index[:, 0].astype(np.int32))
+        est.set_consensus(*cons)   # the handle is shared: every call states its setting
         est.run(model, min_points, r)
         intr, cinfo, eig, H, frames, ginfo, _ = est.results()
         last_intrinsics_kernel_ms = est.last_kernel_ms()
         out = IntrinsicsEstimate(intr=intr, status=cinfo[:, 0].copy(), n_groups=cinfo[:, 1].copy(), eig_ratio=eig, homographies=H.reshape(-1, 3, 3),
                                  plane_frames=frames, group_status=ginfo[:, 0].copy(), group_counts=ginfo[:, 1].copy(), group_index=index)
+        if cons[0] > 0:
+            inl, gc, out.group_score = est.consensus_results()
+            if order is None:
+                out.inliers = inl
+            else:
+                out.inliers = np.zeros(d.shape[0], dtype=bool)
+                out.inliers[order] = inl
+            out.group_inliers, out.group_hypothesis, out.group_consensus_used = gc[:, 0].copy(), gc[:, 1].copy(), gc[:, 3] != 0
     if refine:
-        _refine_intrinsics(out, d, pts, I, device, lm_opts)
+        _refine_intrinsics(out, d if out.inliers is None else d[out.inliers], pts, I, device, lm_opts)
     return out
 
 

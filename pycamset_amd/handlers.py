@@ -284,7 +284,7 @@ class TemplateBundleHandler:  # th:80-240
             "device PnP) and hand it to set_initial_params(), or supply your own")
 
     def calc_initial_params(self, intr=None, *, seeding: str = "reference", refine_poses: bool = False,
-                            view_consensus: int | None = None) -> np.ndarray:  # th:302-346
+                            view_consensus: int | None = None, intrinsics_consensus: int | None = None) -> np.ndarray:  # th:302-346
         """A start vector from the detections: per-view target poses on the device (``compiled_helpers.estimate_view_poses``), the view
         graph of ``pose_seeding.estimate_camera_relative_poses`` (th:468-601), then the free entries in slab order — unfixed intrinsics,
         extrinsics and poses (plus, for the self and free chains, the free point scalars of the template).  ``intr``: (C, 9) rows
@@ -305,11 +305,18 @@ class TemplateBundleHandler:  # th:80-240
 
         ``view_consensus``: hypotheses per view of the consensus sampling in front of the per-view poses
         (``compiled_helpers.estimate_view_poses(consensus=...)``; 64 is a good value), so that detections with a wrong id do not bend
-        the start; default ``options["view_consensus"]``, else 0 (off)."""
+        the start; default ``options["view_consensus"]``, else 0 (off).
+
+        ``intrinsics_consensus``: hypotheses per (camera, image, board) group of the consensus sampling in front of the planar
+        homographies (``compiled_helpers.estimate_intrinsics(consensus=...)``; 64 is a good value), used where the intrinsics are
+        estimated from the detections: without it a few wrong ids cost a camera its estimate before ``view_consensus`` is ever
+        reached; default ``options["intrinsics_consensus"]``, else 0 (off)."""
         from .pose_seeding import estimate_camera_relative_poses, estimate_camera_relative_poses_graph
 
         if view_consensus is None:
             view_consensus = self.problem_opts.get("view_consensus", 0)
+        if intrinsics_consensus is None:
+            intrinsics_consensus = self.problem_opts.get("intrinsics_consensus", 0)
 
         if seeding not in ("reference", "graph", "auto"):
             raise ValueError(f"seeding must be 'reference', 'graph' or 'auto', got {seeding!r}")
@@ -321,7 +328,7 @@ class TemplateBundleHandler:  # th:80-240
                 intr = np.stack([np.concatenate((np.asarray(self.camset[idc].intrinsic)[[0, 0, 1, 1], [0, 2, 1, 2]].squeeze(),
                                                  np.asarray(self.camset[idc].distortion_coefs).squeeze()), axis=0) for idc in range(n_cams)])
             except (TypeError, AttributeError, KeyError, IndexError):
-                intr = self._estimate_initial_intrinsics(n_cams)
+                intr = self._estimate_initial_intrinsics(n_cams, intrinsics_consensus)
         intr = np.array(intr, dtype=np.float64)
         if intr.shape != (n_cams, 9):
             raise ValueError(f"intr must be ({n_cams}, 9), got {intr.shape}")
@@ -394,7 +401,7 @@ class TemplateBundleHandler:  # th:80-240
             self.missing_poses[images] = True
         return np.array(found_all, dtype=np.int64)
 
-    def _estimate_initial_intrinsics(self, n_cams: int) -> np.ndarray:
+    def _estimate_initial_intrinsics(self, n_cams: int, consensus: int = 0) -> np.ndarray:
         """(C, 9) from the detections alone.  A key's board is its index along the FIRST key axis of ``target.point_data`` — the face of a
         Ccube, whether its points are laid out (faces, n, 3) or (faces, rows, cols, 3) — and a target with one key axis, (n, 3), is
         one board.  A free camera without an estimate raises: its rows would be NaN."""
@@ -412,7 +419,8 @@ class TemplateBundleHandler:  # th:80-240
         no_intr = "calc_initial_params: the camset holds no intrinsics (camset[idc].intrinsic / .distortion_coefs)"
         try:
             est = ch.estimate_intrinsics(self._flat_detections(), self.point_data.reshape((-1, 3)), n_cams=n_cams, n_imgs=n_imgs,
-                                         board_of_key=board_of_key, res=res, refine=True, device=self.op_fun.device)
+                                         board_of_key=board_of_key, res=res, refine=True, device=self.op_fun.device,
+                                         consensus=consensus)
         except ch._capi.PcsError as e:
             if e.code != ch._capi.PCS_ERR_NODEVICE:
                 raise
