@@ -440,6 +440,17 @@ int pcs_genchain_lm_trial_finish(pcs_genchain *h, const pcs_lm_buffers *b, void 
 int pcs_genchain_set_prior(pcs_genchain *h, const double *mean, const double *inv_sigma, int64_t n);
 int pcs_genchain_get_prior(pcs_genchain *h, double *mean, double *inv_sigma, int64_t capacity, int64_t *n);
 int pcs_genchain_prior_add_device(pcs_genchain *h, const double *d_param_str, double *d_packed, void *stream);
+
+/* The box bounds of a generated chain (since pcs_version() 118): pcs_set_bounds and its companions with the same meaning, the same store
+ * and the same kernels.  pcs_genchain_lm_trial_build consults them (a bounded trial takes the non-fused sequence), and
+ * pcs_genchain_lm_trial_finish decides on the truncated step. */
+int pcs_genchain_set_bounds(pcs_genchain *h, const double *lo, const double *hi, int64_t n);
+int pcs_genchain_get_bounds(pcs_genchain *h, double *lo, double *hi, int64_t capacity, int64_t *n);
+int pcs_genchain_bounds_trials(pcs_genchain *h, double *alpha_active, int64_t n_trials, int64_t *n_truncated);
+int pcs_genchain_bounds_active_device(pcs_genchain *h, const double *d_ps, const double *d_packed, const uint8_t *d_fixed, uint8_t *d_fixed_eff, void *stream);
+int pcs_genchain_bounds_truncate_device(pcs_genchain *h, const double *d_ps_in, double *d_delta, double *d_ps_out, double *d_alpha, void *stream);
+int pcs_genchain_lm_decide_bounded(pcs_genchain *h, const double *d_cost_old, const double *d_cost_new, const double *d_dvec, const double *d_gm, const double *d_delta,
+                                   const double *d_ps, const uint8_t *d_fixed_eff, const double *d_alpha, int32_t *d_status, double *d_lambda, double *d_stats, void *stream);
 int pcs_genchain_lm_trial(pcs_genchain *h, const pcs_lm_buffers *b, void *stream);
 int pcs_genchain_set_option(pcs_genchain *h, const char *key, int64_t value);
 /* The pieces of a trial as calls of their own — pcs_schur_prepare / pcs_schur_finish / pcs_lm_decide for the handle's layout — for a
@@ -556,6 +567,53 @@ int pcs_get_weights(pcs_engine *h, double *inv_sigma, int64_t capacity, int64_t 
 int pcs_set_prior(pcs_engine *h, const double *mean, const double *inv_sigma, int64_t n);
 int pcs_get_prior(pcs_engine *h, double *mean, double *inv_sigma, int64_t capacity, int64_t *n);
 int pcs_prior_add_device(pcs_engine *h, const double *d_param_str, double *d_packed, void *stream);
+
+/* Box bounds on the parameters of the engine's LM solve (since pcs_version() 118): lo[i] <= p[i] <= hi[i] over the parameter string,
+ * -inf / +inf = none — what scipy least_squares(bounds=) is to the reference's call (optimisation_handling.py:88-98).  The method is an
+ * active set plus a step cut at the first bound (csrc/ba_bounds.hpp); per trial, on the device, behind the stop word:
+ *   1. from the CURRENT state: fixed_eff[i] = fixed[i] || lo[i] == hi[i] || (p[i] <= lo[i] && g[i] > 0) || (p[i] >= hi[i] && g[i] < 0)
+ *      || (pinned[i] && p[i] on a bound); the Schur step reads fixed_eff where it reads `fixed` without bounds.
+ *   2. behind the step d: alpha = min(1, min_i alpha_i), alpha_i the fraction of d[i] that takes p[i] to the bound it moves towards
+ *      (ties: the lowest index); p_new = min(max(p + alpha d, lo), hi), the entry that sets alpha exactly on its bound; delta = p_new - p.
+ *      An entry ON a bound whose step points out of the box (it would make alpha = 0) is PINNED instead: its component of the step is
+ *      dropped, it takes no part in alpha, and — the handle's only memory — it joins the active set of the following trials until a
+ *      trial is accepted.
+ *   3. the decision: predicted reduction -(1 - alpha / 2) g'delta + 0.5 lambda delta'D delta; max |g| and |x| over fixed_eff (the
+ *      projected gradient); a truncated trial (alpha < 1) triggers neither the ftol nor the xtol stop, counts towards the limits and
+ *      takes the damping rule as usual, except that an accepted one never LOWERS lambda (the gain ratio of a cut step says nothing
+ *      about the whole one).
+ * With bounds set, pcs_lm_trial_build takes the NON-fused sequence plus two one-workgroup launches (the fused completion prepares the
+ * slabs at the trial string in the launch that writes it); pcs_lm_trial_finish decides as in 3.  Without bounds every entry point
+ * queues the launches it queued before and computes the same bits.
+ *   pcs_set_bounds   n must equal pcs_n_params; no NaN, lo[i] <= hi[i] (lo[i] == hi[i] acts as fixed).  lo = hi = NULL clears the
+ *                    bounds.  PCS_ERR_ARG if not, and for a NULL handle; a refused call leaves the previous bounds in force.  The values
+ *                    are copied.  The bounds belong to the HANDLE: pcs_set_detections* keeps them.  Synchronises the device before it
+ *                    overwrites lists a queued trial may still read; resets what pcs_bounds_trials reports.
+ *   pcs_get_bounds   *n = pcs_n_params when bounds are set, else 0; up to `capacity` values each go to lo and hi (any of the three
+ *                    outputs may be NULL).
+ *   pcs_bounds_trials   after a loop of pcs_lm_trial* calls whose stream the caller has synchronised: alpha_active[2 k], [2 k + 1] =
+ *                    alpha and the number of entries the bounds added to the mask in trial k + 1 (ctrl[8]), for the first n_trials
+ *                    trials (NaN beyond the 4096 the handle records); *n_truncated = decided trials with alpha < 1 since pcs_set_bounds.
+ *                    PCS_ERR_STATE without bounds.
+ * For a loop the host steers (all pointers device memory; PCS_ERR_STATE without bounds):
+ *   pcs_bounds_active_device    step 1 at the string d_ps and the packed state d_packed built there: d_fixed_eff (n_params bytes)
+ *   pcs_bounds_truncate_device  step 2: d_delta in place, d_ps_out = the trial string (must differ from d_ps_in), *d_alpha
+ *   pcs_bounds_active_sel_device / pcs_bounds_truncate_sel_device   the same two for a caller that keeps TWO states and a selector word
+ *                               as pcs_lm_trial_build does: strings d_ps0 / d_ps1 and packed states d_packed0 / d_packed1; *d_sel != 0
+ *                               names state 1 as the current one, the trial string is written into the other state's.
+ *   pcs_lm_decide_bounded       pcs_lm_decide with step 3's predicted reduction; d_fixed_eff where pcs_lm_decide takes d_fixed.  The
+ *                               ftol / xtol rule of a truncated trial is the caller's (it reads *d_alpha); an accepted trial clears the
+ *                               handle's pins, and so does a void one. */
+int pcs_set_bounds(pcs_engine *h, const double *lo, const double *hi, int64_t n);
+int pcs_get_bounds(pcs_engine *h, double *lo, double *hi, int64_t capacity, int64_t *n);
+int pcs_bounds_trials(pcs_engine *h, double *alpha_active, int64_t n_trials, int64_t *n_truncated);
+int pcs_bounds_active_device(pcs_engine *h, const double *d_ps, const double *d_packed, const uint8_t *d_fixed, uint8_t *d_fixed_eff, void *stream);
+int pcs_bounds_truncate_device(pcs_engine *h, const double *d_ps_in, double *d_delta, double *d_ps_out, double *d_alpha, void *stream);
+int pcs_bounds_active_sel_device(pcs_engine *h, const double *d_ps0, const double *d_ps1, const double *d_packed0, const double *d_packed1, const uint8_t *d_fixed,
+                                 uint8_t *d_fixed_eff, const int32_t *d_sel, void *stream);
+int pcs_bounds_truncate_sel_device(pcs_engine *h, double *d_ps0, double *d_ps1, double *d_delta, double *d_alpha, const int32_t *d_sel, void *stream);
+int pcs_lm_decide_bounded(pcs_engine *h, const double *d_cost_old, const double *d_cost_new, const double *d_dvec, const double *d_gm, const double *d_delta,
+                          const double *d_ps, const uint8_t *d_fixed_eff, const double *d_alpha, int32_t *d_status, double *d_lambda, double *d_stats, void *stream);
 /*
  * Batched n-view triangulation.
  * Replaces: nb_triangulate_full (compiled_helpers.py:609-643) = per point nb_undistort (ch:409-431) +

@@ -223,6 +223,20 @@ SYMBOLS = {
     "pcs_genchain_set_prior": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64]),
     "pcs_genchain_get_prior": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64)]),
     "pcs_genchain_prior_add_device": (c_int, [_P, _P, _P, _P]),
+    "pcs_set_bounds": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64]),
+    "pcs_get_bounds": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_bounds_trials": (c_int, [_P, POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_bounds_active_device": (c_int, [_P, _P, _P, _P, _P, _P]),
+    "pcs_bounds_truncate_device": (c_int, [_P, _P, _P, _P, _P, _P]),
+    "pcs_lm_decide_bounded": (c_int, [_P] * 13),
+    "pcs_bounds_active_sel_device": (c_int, [_P] * 9),
+    "pcs_bounds_truncate_sel_device": (c_int, [_P] * 7),
+    "pcs_genchain_set_bounds": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64]),
+    "pcs_genchain_get_bounds": (c_int, [_P, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_genchain_bounds_trials": (c_int, [_P, POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_genchain_bounds_active_device": (c_int, [_P, _P, _P, _P, _P, _P]),
+    "pcs_genchain_bounds_truncate_device": (c_int, [_P, _P, _P, _P, _P, _P]),
+    "pcs_genchain_lm_decide_bounded": (c_int, [_P] * 13),
     "pcs_device_buffers": (c_int, [_P, POINTER(_P), POINTER(_P)]),
 }
 

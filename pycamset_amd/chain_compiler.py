@@ -772,6 +772,37 @@ class ChainEngine:
 
         return Engine.prior_add_device(self, d_param_str, d_packed, stream)
 
+    # -- box bounds (include/pcs_hip.h pcs_genchain_set_bounds): Engine's methods on this handle kind -----------------------------------
+    def set_bounds(self, lo=None, hi=None):
+        from .engine import Engine
+
+        return Engine.set_bounds(self, lo, hi)
+
+    def bounds(self):
+        from .engine import Engine
+
+        return Engine.bounds(self)
+
+    def bounds_trials(self, n_trials: int):
+        from .engine import Engine
+
+        return Engine.bounds_trials(self, n_trials)
+
+    def bounds_active_device(self, d_ps, d_packed, d_fixed, d_fixed_eff, stream=None):
+        from .engine import Engine
+
+        return Engine.bounds_active_device(self, d_ps, d_packed, d_fixed, d_fixed_eff, stream)
+
+    def bounds_truncate_device(self, d_ps_in, d_delta, d_ps_out, d_alpha, stream=None):
+        from .engine import Engine
+
+        return Engine.bounds_truncate_device(self, d_ps_in, d_delta, d_ps_out, d_alpha, stream)
+
+    def lm_decide_bounded(self, *args, stream=None):
+        from .engine import Engine
+
+        return Engine.lm_decide_bounded(self, *args, stream=stream)
+
     def set_option(self, key: str, value: int):
         """Engine's option interface as far as the LM driver uses it: "spd_timeout_us", "timing" and "deterministic" (the ORDERED
         contraction of csrc/ba_blockgram.hpp: every sum in a fixed order, the same bits on every run) reach the handle; "timing_every"

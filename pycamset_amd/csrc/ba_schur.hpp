@@ -622,6 +622,16 @@ struct LmDecideArgs {
     int64_t n_free;
     double *result;
     double *stats_host;                     // optional: the 12 numbers again, in mapped page-locked host memory the host has filled with LM_SENTINEL
+    // optional (box bounds, csrc/ba_bounds.hpp): *alpha = the fraction of the step that bounds_truncate_kernel kept.  `delta` is then the
+    // truncated step, `fixed` the effective mask, and the predicted reduction is -(1 - alpha / 2) g'delta + 0.5 lambda delta'D delta;
+    // a truncated trial (alpha < 1) triggers neither the ftol nor the xtol stop.  NULL: the arithmetic and the bits of a loop without bounds.
+    const double *alpha;
+    // optional, with alpha: bound_log[2 k], [2 k + 1] <- alpha and *n_active of trial k + 1 (ctrl[8]; the first bound_log_trials trials),
+    // *n_truncated += 1 for a decided trial with alpha < 1
+    const int32_t *n_active;
+    double *bound_log, *n_truncated;
+    int32_t bound_log_trials;
+    uint8_t *pin;                           // optional, with alpha: n_params bytes (ba_bounds.hpp), cleared when the trial is accepted or void
 };
 constexpr int LM_STATS = 12;
 // (the host side of the read-back protocol: pycamset_amd/device_solver.py LM_SENTINEL = a quiet NaN with a payload, 0x7FF8DEAD00000001)
@@ -647,6 +657,8 @@ __global__ __launch_bounds__(1024) void lm_decide_kernel(const LmDecideArgs a) {
     const double lam = *a.lambda, c_old = a.tail[cur][0], c_new = a.tail[tri][0];
     const int st = *a.status;
     const double votes = a.use_votes ? a.tail[tri][1] : 0.0;
+    const double alpha = a.alpha ? *a.alpha : 1.0;
+    const bool truncated = alpha < 1.0;
     double cv[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (a.ctrl) {
 #pragma unroll
@@ -684,7 +696,7 @@ __global__ __launch_bounds__(1024) void lm_decide_kernel(const LmDecideArgs a) {
         }
     }
     if (tid == 0) {
-        const double pred = 0.5 * (lam * s_dd - s_gd);
+        const double pred = a.alpha ? 0.5 * lam * s_dd - (1.0 - 0.5 * alpha) * s_gd : 0.5 * (lam * s_dd - s_gd);
         const double actual = 0.5 * (c_old - c_new);
         const bool ok = st == 0 && pred == pred && fabs(pred) < 1.0e300;
         const double rho = pred > 0.0 ? actual / pred : -1.0;
@@ -703,8 +715,8 @@ __global__ __launch_bounds__(1024) void lm_decide_kernel(const LmDecideArgs a) {
             else if (acc) {
                 c[1] = 0.0;
                 c[2] = cv[2] + 1.0;
-                if (rel_drop <= cv[4]) code = 3.0;
-                else if (step_norm <= cv[5] * (cv[5] + x_norm)) code = 4.0;
+                if (!truncated && rel_drop <= cv[4]) code = 3.0;
+                else if (!truncated && step_norm <= cv[5] * (cv[5] + x_norm)) code = 4.0;
                 else if (cv[2] + 1.0 >= cv[3]) code = 5.0;
             } else {
                 c[1] = cv[1] + 1.0;
@@ -715,8 +727,14 @@ __global__ __launch_bounds__(1024) void lm_decide_kernel(const LmDecideArgs a) {
             c[0] = code;
             *a.accept_flag = acc ? 1 : 0;
             *a.stop_flag = code != 0.0 ? 1 : 0;
+            if (a.alpha && a.bound_log) {
+                const int64_t k = (int64_t)trial_no - 1;
+                if (k >= 0 && k < a.bound_log_trials) { a.bound_log[2 * k] = alpha; a.bound_log[2 * k + 1] = a.n_active ? (double)*a.n_active : 0.0; }
+                if (truncated && !void_trial && a.n_truncated) *a.n_truncated += 1.0;
+            }
         }
-        const double lam_next = (!void_trial && code != 1.0) ? (acc ? fmax(lam * factor, 1e-12) : lam * grow) : lam;
+        // (the gain ratio of a step cut at a bound says nothing about the whole step: an accepted cut trial does not shed damping)
+        const double lam_next = (!void_trial && code != 1.0) ? (acc ? fmax(lam * ((truncated && factor < 1.0) ? 1.0 : factor), 1e-12) : lam * grow) : lam;
         *a.lambda = lam_next;
         *a.status = 0;
         const int now = (acc && a.sel && !a.keep_sel) ? tri : cur;           // the state the next trial starts from
@@ -727,6 +745,7 @@ __global__ __launch_bounds__(1024) void lm_decide_kernel(const LmDecideArgs a) {
             if (a.ctrl || (i != 8 && i != 9)) a.stats[i] = out[i];
         red[1][0] = code;                    // for the other threads: does the loop end here, and in which state
         red[1][1] = acc ? 1.0 : 0.0;
+        red[1][3] = void_trial ? 1.0 : 0.0;
         red[1][2] = acc ? c_new : c_old;
         // the trial's read-back straight into the host's page-locked buffer (no copy launch, no fence: the host has filled the twelve
         // words with a NaN pattern no arithmetic produces and waits until none is left — the words may land in any order).  Not for the
@@ -735,6 +754,11 @@ __global__ __launch_bounds__(1024) void lm_decide_kernel(const LmDecideArgs a) {
 #pragma unroll
             for (int i = 0; i < LM_STATS; ++i) a.stats_host[i] = out[i];
         }
+    }
+    if (a.pin) {                             // box bounds: an accepted trial releases the pinned entries, and so does a void one — the step that
+        __syncthreads();                     // set them was never solved (uniform branch: a kernel argument)
+        if (red[1][1] != 0.0 || red[1][3] != 0.0)
+            for (int64_t i = tid; i < a.n_params; i += 1024) a.pin[i] = 0;
     }
     if (!a.ctrl) return;
     __syncthreads();

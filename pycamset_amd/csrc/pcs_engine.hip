@@ -34,6 +34,7 @@
 #include "ba_schur.hpp"
 #include "ba_lm_fused.hpp"
 #include "ba_prior.hpp"
+#include "ba_bounds.hpp"
 #include "ba_dense_chol.hpp"
 #include "ba_chol_persist.hpp"
 #include "ba_covariance.hpp"
@@ -97,6 +98,7 @@ struct pcs_engine {
     // static inputs
     DetStore det;                      // the detection table (pcs_dettable.inc); det.n = number of detections
     PriorStore prior;                  // the Gaussian parameter prior (pcs_set_prior); the handle's, not the table's
+    BoundStore bounds;                 // the box bounds of the LM solve (pcs_set_bounds); the handle's, not the table's
     bool pack_indices = true;          // option "pack_indices" (A/B switch; takes effect at the next upload)
     DevBuf d_order;              // (cam, image)-sorted visiting order of a scattered table (normal equations), or empty
     DevBuf d_order_ck, d_order_ik;   // (cam, key) / (image, key) orders for the point passes
@@ -340,6 +342,7 @@ int pcs_destroy(pcs_engine *h) {
     (void)hipStreamSynchronize(h->stream);
     release_table(h);   // what belongs to the detection table; then the buffers that outlive a table
     h->prior.release();
+    h->bounds.release();
     for (DevBuf *b : {&h->d_param, &h->d_cam_slab, &h->d_pose_slab, &h->d_points, &h->d_sink, &h->d_vin, &h->d_vout, &h->d_cost, &h->d_H, &h->d_im_points, &h->d_cam_tab})
         b->release();
     if (h->h_param) (void)hipHostFree(h->h_param);
@@ -568,6 +571,29 @@ int pcs_set_prior(pcs_engine *h, const double *mean, const double *inv_sigma, in
 int pcs_get_prior(pcs_engine *h, double *mean, double *inv_sigma, int64_t capacity, int64_t *n) {
     if (!h) return fail(PCS_ERR_ARG, "pcs_get_prior: bad arguments");
     return h->prior.get("pcs_get_prior", mean, inv_sigma, capacity, n);
+}
+
+int pcs_set_bounds(pcs_engine *h, const double *lo, const double *hi, int64_t n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_set_bounds: bad arguments");
+    if (const int rc = BoundStore::check("pcs_set_bounds", lo, hi, n, h->n_params)) return rc;
+    if (!lo && !h->bounds.active()) return PCS_OK;   // nothing set, nothing to clear: no device call
+    HIPCHK(hipSetDevice(h->device));
+    if (h->bounds.set_writes_device(lo)) {   // a trial that reads the old lists may be queued on any stream
+        HIPCHK(wait_done_host(h));
+        HIPCHK(hipDeviceSynchronize());
+    }
+    return h->bounds.set(lo, hi, h->n_params);
+}
+
+int pcs_get_bounds(pcs_engine *h, double *lo, double *hi, int64_t capacity, int64_t *n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_get_bounds: bad arguments");
+    return h->bounds.get("pcs_get_bounds", lo, hi, capacity, n);
+}
+
+int pcs_bounds_trials(pcs_engine *h, double *alpha_active, int64_t n_trials, int64_t *n_truncated) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_bounds_trials: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    return h->bounds.trials("pcs_bounds_trials", alpha_active, n_trials, n_truncated);
 }
 
 }  // extern "C"
@@ -1554,6 +1580,29 @@ int pcs_prior_add_device(pcs_engine *h, const double *d_param_str, double *d_pac
     return prior_add_piece("pcs_prior_add_device", h->device, h->prior, block_layout(h), h->n_params, d_param_str, d_packed, stream ? (hipStream_t)stream : h->stream);
 }
 
+// The two bound kernels as calls of their own, for a loop the host steers (pcs_solver.inc: bounds_active_piece, bounds_truncate_piece).
+int pcs_bounds_active_device(pcs_engine *h, const double *d_ps, const double *d_packed, const uint8_t *d_fixed, uint8_t *d_fixed_eff, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_bounds_active_device: bad arguments");
+    return bounds_active_piece("pcs_bounds_active_device", h->device, h->bounds, block_layout(h), h->n_params, d_ps, d_packed, d_fixed, d_fixed_eff, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pcs_bounds_truncate_device(pcs_engine *h, const double *d_ps_in, double *d_delta, double *d_ps_out, double *d_alpha, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_bounds_truncate_device: bad arguments");
+    return bounds_truncate_piece("pcs_bounds_truncate_device", h->device, h->bounds, h->n_params, d_ps_in, d_delta, d_ps_out, d_alpha, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pcs_bounds_active_sel_device(pcs_engine *h, const double *d_ps0, const double *d_ps1, const double *d_packed0, const double *d_packed1, const uint8_t *d_fixed,
+                                 uint8_t *d_fixed_eff, const int32_t *d_sel, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_bounds_active_sel_device: bad arguments");
+    return bounds_active_sel_piece("pcs_bounds_active_sel_device", h->device, h->bounds, block_layout(h), h->n_params, d_ps0, d_ps1, d_packed0, d_packed1, d_fixed, d_fixed_eff, d_sel,
+                                   stream ? (hipStream_t)stream : h->stream);
+}
+
+int pcs_bounds_truncate_sel_device(pcs_engine *h, double *d_ps0, double *d_ps1, double *d_delta, double *d_alpha, const int32_t *d_sel, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_bounds_truncate_sel_device: bad arguments");
+    return bounds_truncate_sel_piece("pcs_bounds_truncate_sel_device", h->device, h->bounds, h->n_params, d_ps0, d_ps1, d_delta, d_alpha, d_sel, stream ? (hipStream_t)stream : h->stream);
+}
+
 // The pieces of a trial for a loop the host steers (pcs_solver.inc: schur_prepare_piece, schur_finish_piece, lm_decide_piece).
 int pcs_schur_prepare(pcs_engine *h, double *d_packed, const uint8_t *d_fixed, const double *d_lambda, double *d_linvt, double *d_u,
                       double *d_V, double *d_S, double *d_rhs, double *d_dvec, double *d_gm, int32_t *d_status, void *stream) {
@@ -1573,6 +1622,13 @@ int pcs_lm_decide(pcs_engine *h, const double *d_cost_old, const double *d_cost_
     return lm_decide_piece("pcs_lm_decide", h->device, h->n_params, stream ? (hipStream_t)stream : h->stream, d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed, d_status, d_lambda, d_stats);
 }
 
+int pcs_lm_decide_bounded(pcs_engine *h, const double *d_cost_old, const double *d_cost_new, const double *d_dvec, const double *d_gm, const double *d_delta,
+                          const double *d_ps, const uint8_t *d_fixed_eff, const double *d_alpha, int32_t *d_status, double *d_lambda, double *d_stats, void *stream) {
+    if (!h || !d_alpha) return fail(PCS_ERR_ARG, "pcs_lm_decide_bounded: bad arguments");
+    if (!h->bounds.active()) return fail(PCS_ERR_STATE, "pcs_lm_decide_bounded: no bounds set");
+    return lm_decide_piece("pcs_lm_decide_bounded", h->device, h->n_params, stream ? (hipStream_t)stream : h->stream, d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed_eff, d_status, d_lambda, d_stats, d_alpha, h->bounds.pin());
+}
+
 // One Levenberg-Marquardt trial in two halves (pcs_solver.inc: enqueue_lm_trial_build, enqueue_lm_finish).
 int pcs_lm_trial_build(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
     const int rc = lm_check(h, b, "pcs_lm_trial_build");
@@ -1581,7 +1637,8 @@ int pcs_lm_trial_build(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
     LmTrialDesc d;
     d.who = "pcs_lm_trial_build"; d.device = h->device; d.n_cu = h->n_cu; d.n_params = h->n_params; d.L = block_layout(h);
     d.deterministic = h->deterministic != 0; d.spd_timeout_us = h->spd_timeout_us;
-    d.fused = h->fused_trial && d.L.n_lead > 0 && d.L.n_ent > 0 && h->det.n > 0;
+    d.bounds = &h->bounds;
+    d.fused = h->fused_trial && d.L.n_lead > 0 && d.L.n_ent > 0 && h->det.n > 0 && !h->bounds.active();
     d.selector = true;
     d.empty_zero_state = h->det.n == 0;
     d.slabs = FinishSlabs{h->d_cam_slab.as<double>(), h->d_pose_slab.as<double>(), h->d_points.as<double>(), h->n_cams, h->n_imgs, h->n_keys, h->extr_off, h->pose_off, h->point_off,
@@ -1597,7 +1654,7 @@ int pcs_lm_trial_finish(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {
     const int rc = lm_check(h, b, "pcs_lm_trial_finish");
     if (rc) return rc;
     HIPCHK(hipSetDevice(h->device));
-    return enqueue_lm_finish(h->n_cu, h->n_params, block_layout(h), h->prior, b, stream ? (hipStream_t)stream : h->stream);
+    return enqueue_lm_finish(h->n_cu, h->n_params, block_layout(h), h->prior, h->bounds, b, stream ? (hipStream_t)stream : h->stream);
 }
 
 int pcs_lm_trial(pcs_engine *h, const pcs_lm_buffers *b, void *stream) {

@@ -31,6 +31,7 @@ struct pcs_genchain {
     DevBuf d_sink;
     DetStore det;                   // the detection table (pcs_dettable.inc); det.n = number of detections
     PriorStore prior;               // the Gaussian parameter prior (pcs_genchain_set_prior); the handle's, not the table's
+    BoundStore bounds;              // the box bounds of the LM solve (pcs_genchain_set_bounds); the handle's, not the table's
     bool have_template = false;
     DevBuf d_resid, d_jac, d_data;
     DevBuf d_keep;      // per detection, uint64: bit j set = local column j is free
@@ -84,6 +85,7 @@ int pcs_genchain_destroy(pcs_genchain *h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->det.release();
     h->prior.release();
+    h->bounds.release();
     for (DevBuf *b : {&h->d_param, &h->d_tmpl, &h->d_sink, &h->d_resid, &h->d_jac, &h->d_data, &h->d_keep, &h->d_row_off, &h->d_vin, &h->d_vout, &h->d_gram_ws}) b->release();
     for (DevBuf &b : h->d_slab) b.release();
     for (DevBuf &b : h->d_blk_map) b.release();
@@ -742,6 +744,45 @@ int pcs_genchain_prior_add_device(pcs_genchain *h, const double *d_param_str, do
     return prior_add_piece("pcs_genchain_prior_add_device", h->device, h->prior, genchain_layout(h), h->n_params, d_param_str, d_packed, stream ? (hipStream_t)stream : h->stream);
 }
 
+// The box bounds of a generated chain: pcs_set_bounds / pcs_get_bounds / pcs_bounds_trials / pcs_bounds_active_device /
+// pcs_bounds_truncate_device / pcs_lm_decide_bounded for this handle kind (the same store, the same kernels).
+int pcs_genchain_set_bounds(pcs_genchain *h, const double *lo, const double *hi, int64_t n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_set_bounds: bad arguments");
+    if (const int rc = BoundStore::check("pcs_genchain_set_bounds", lo, hi, n, h->n_params)) return rc;
+    if (!lo && !h->bounds.active()) return PCS_OK;
+    HIPCHK(hipSetDevice(h->device));
+    if (h->bounds.set_writes_device(lo)) HIPCHK(hipDeviceSynchronize());   // a trial that reads the old lists may be queued on any stream
+    return h->bounds.set(lo, hi, h->n_params);
+}
+
+int pcs_genchain_get_bounds(pcs_genchain *h, double *lo, double *hi, int64_t capacity, int64_t *n) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_get_bounds: bad arguments");
+    return h->bounds.get("pcs_genchain_get_bounds", lo, hi, capacity, n);
+}
+
+int pcs_genchain_bounds_trials(pcs_genchain *h, double *alpha_active, int64_t n_trials, int64_t *n_truncated) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_bounds_trials: bad arguments");
+    HIPCHK(hipSetDevice(h->device));
+    return h->bounds.trials("pcs_genchain_bounds_trials", alpha_active, n_trials, n_truncated);
+}
+
+int pcs_genchain_bounds_active_device(pcs_genchain *h, const double *d_ps, const double *d_packed, const uint8_t *d_fixed, uint8_t *d_fixed_eff, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_bounds_active_device: bad arguments");
+    return bounds_active_piece("pcs_genchain_bounds_active_device", h->device, h->bounds, genchain_layout(h), h->n_params, d_ps, d_packed, d_fixed, d_fixed_eff, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pcs_genchain_bounds_truncate_device(pcs_genchain *h, const double *d_ps_in, double *d_delta, double *d_ps_out, double *d_alpha, void *stream) {
+    if (!h) return fail(PCS_ERR_ARG, "pcs_genchain_bounds_truncate_device: bad arguments");
+    return bounds_truncate_piece("pcs_genchain_bounds_truncate_device", h->device, h->bounds, h->n_params, d_ps_in, d_delta, d_ps_out, d_alpha, stream ? (hipStream_t)stream : h->stream);
+}
+
+int pcs_genchain_lm_decide_bounded(pcs_genchain *h, const double *d_cost_old, const double *d_cost_new, const double *d_dvec, const double *d_gm, const double *d_delta,
+                                   const double *d_ps, const uint8_t *d_fixed_eff, const double *d_alpha, int32_t *d_status, double *d_lambda, double *d_stats, void *stream) {
+    if (!h || !d_alpha) return fail(PCS_ERR_ARG, "pcs_genchain_lm_decide_bounded: bad arguments");
+    if (!h->bounds.active()) return fail(PCS_ERR_STATE, "pcs_genchain_lm_decide_bounded: no bounds set");
+    return lm_decide_piece("pcs_genchain_lm_decide_bounded", h->device, h->n_params, stream ? (hipStream_t)stream : h->stream, d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed_eff, d_status, d_lambda, d_stats, d_alpha, h->bounds.pin());
+}
+
 // One Levenberg-Marquardt trial of a generated chain in two halves, like pcs_lm_trial_build / pcs_lm_trial_finish (same buffers, same
 // shared build — pcs_solver.inc enqueue_lm_trial_build —, same decision kernel, same read-back).  The generated evaluation kernel reads its
 // parameter string from a fixed address, so the trial is always built at ps[1] into packed[1] and an accepted one is copied over state 0:
@@ -754,7 +795,8 @@ int pcs_genchain_lm_trial_build(pcs_genchain *h, const pcs_lm_buffers *b, void *
     LmTrialDesc d;
     d.who = "pcs_genchain_lm_trial_build"; d.device = h->device; d.n_cu = h->n_cu; d.n_params = h->n_params; d.L = genchain_layout(h);
     d.deterministic = h->deterministic; d.spd_timeout_us = h->spd_timeout_us;
-    d.fused = d.L.n_ent > 0 && d.L.n_lead > 0;   // with trailing entities always (without the slab preparation the completion does for the engines)
+    d.bounds = &h->bounds;
+    d.fused = d.L.n_ent > 0 && d.L.n_lead > 0 && !h->bounds.active();   // with trailing entities always (without the slab preparation the completion does for the engines)
     d.finish_zeroes = true;   // (selector and empty_zero_state stay off: one state, and an empty table is refused by genchain_enqueue_normal with "no detections set")
     return enqueue_lm_trial_build(d, b, stream ? (hipStream_t)stream : h->stream,
                                   [&](hipStream_t s, bool) { return genchain_enqueue_normal(h, b->ps[1], b->packed[1], s, b->flags, true); });
@@ -784,7 +826,7 @@ int pcs_genchain_lm_trial_finish(pcs_genchain *h, const pcs_lm_buffers *b, void 
     if (rc) return rc;
     if (!(b->mode & PCS_LM_FIXED_TRIAL_BUFFER)) return fail(PCS_ERR_ARG, "pcs_genchain_lm_trial_finish: mode must hold PCS_LM_FIXED_TRIAL_BUFFER");
     HIPCHK(hipSetDevice(h->device));
-    return enqueue_lm_finish(h->n_cu, h->n_params, genchain_layout(h), h->prior, b, stream ? (hipStream_t)stream : h->stream);
+    return enqueue_lm_finish(h->n_cu, h->n_params, genchain_layout(h), h->prior, h->bounds, b, stream ? (hipStream_t)stream : h->stream);
 }
 
 int pcs_genchain_lm_trial(pcs_genchain *h, const pcs_lm_buffers *b, void *stream) {

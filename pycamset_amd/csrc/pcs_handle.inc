@@ -101,6 +101,95 @@ struct PriorStore {
     }
 };
 
+// The box bounds of an engine handle (pcs_set_bounds / pcs_genchain_set_bounds; kernels: csrc/ba_bounds.hpp): lo and hi over the whole
+// parameter string on the device (-inf / +inf = none), the effective mask a trial's Schur step reads in place of the caller's, and the
+// words a trial leaves behind: alpha, the number of truncated trials, the number of active entries, and (alpha, active entries) of the
+// first BOUNDS_LOG_TRIALS trials of the loop.  It belongs to the HANDLE, not to its detection table: a new table keeps it.  The host
+// keeps the arrays as they were given (pcs_get_bounds).
+struct BoundStore {
+    DevBuf pins;                             // n bytes: entries pinned by the last rejected trials (csrc/ba_bounds.hpp)
+    DevBuf data, eff, words;                 // data: [lo | hi], 2 n doubles, ONE upload per pcs_set_bounds; eff: n bytes; words: [alpha | truncated trials | active entries (int32) | log]
+    int64_t n = 0;                           // n_params while bounds are set; 0 = none
+    std::vector<double> h_lo, h_hi;
+    static constexpr int64_t WORDS = 3 + 2 * (int64_t)BOUNDS_LOG_TRIALS;
+    bool active() const { return n > 0; }
+    const double *lo() const { return data.as<const double>(); }
+    const double *hi() const { return data.as<const double>() + n; }
+    uint8_t *fixed_eff() const { return eff.as<uint8_t>(); }
+    uint8_t *pin() const { return pins.as<uint8_t>(); }
+    double *alpha() const { return words.as<double>(); }
+    double *n_truncated() const { return words.as<double>() + 1; }
+    int32_t *n_active() const { return reinterpret_cast<int32_t *>(words.as<double>() + 2); }
+    double *log() const { return words.as<double>() + 3; }
+    // "no bounds"; the device buffers stay for the next ones (a solve sets and clears its bounds: no allocation per solve)
+    void clear() {
+        n = 0;
+        h_lo.clear(), h_hi.clear();
+    }
+    void release() {
+        data.release(), eff.release(), words.release(), pins.release();
+        clear();
+    }
+    // everything is checked before anything changes: a refused call leaves the previous bounds in force
+    static int check(const char *who, const double *lo_in, const double *hi_in, int64_t n_in, int64_t n_params) {
+        if (!lo_in && !hi_in) return PCS_OK;
+        if (!lo_in || !hi_in) return fail(PCS_ERR_ARG, "%s: lo and hi come together (both NULL: no bounds)", who);
+        if (n_in != n_params) return fail(PCS_ERR_ARG, "%s: %lld values for a parameter string of %lld", who, (long long)n_in, (long long)n_params);
+        for (int64_t i = 0; i < n_in; ++i) {
+            if (lo_in[i] != lo_in[i] || hi_in[i] != hi_in[i]) return fail(PCS_ERR_ARG, "%s: bound %lld is NaN", who, (long long)i);
+            if (lo_in[i] > hi_in[i]) return fail(PCS_ERR_ARG, "%s: lo %lld = %g > hi = %g", who, (long long)i, lo_in[i], hi_in[i]);
+        }
+        return PCS_OK;
+    }
+    // does replacing the bounds by these values write device memory that a queued launch may still read?  (the caller then waits first)
+    bool set_writes_device(const double *lo_in) const { return lo_in && data.p; }
+    // checked values (or NULL: none).  A failed allocation or copy leaves "no bounds".
+    int set(const double *lo_in, const double *hi_in, int64_t n_params) {
+        clear();
+        if (!lo_in || n_params <= 0) return PCS_OK;
+        if (const int rc = data.grow(2 * n_params, sizeof(double))) return rc;
+        if (const int rc = eff.grow(n_params, 1)) return rc;
+        if (const int rc = pins.grow(n_params, 1)) return rc;
+        if (const int rc = words.grow(WORDS, sizeof(double))) return rc;
+        std::vector<double> both(2 * (size_t)n_params);
+        memcpy(both.data(), lo_in, sizeof(double) * n_params);
+        memcpy(both.data() + n_params, hi_in, sizeof(double) * n_params);
+        hipError_t e = hipMemcpy(data.p, both.data(), sizeof(double) * both.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset(eff.p, 0, (size_t)n_params);
+        if (e == hipSuccess) e = hipMemset(pins.p, 0, (size_t)n_params);
+        if (e == hipSuccess) e = hipMemset(words.p, 0, sizeof(double) * WORDS);
+        const double one = 1.0;
+        if (e == hipSuccess) e = hipMemcpy(words.p, &one, sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return fail(PCS_ERR_HIP, "uploading the parameter bounds failed: %s", hipGetErrorString(e));
+        h_lo.assign(lo_in, lo_in + n_params), h_hi.assign(hi_in, hi_in + n_params);
+        n = n_params;
+        return PCS_OK;
+    }
+    int get(const char *who, double *lo_out, double *hi_out, int64_t capacity, int64_t *n_out) const {
+        if (capacity < 0 || (!lo_out && !hi_out && !n_out)) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+        const int64_t have = (int64_t)h_lo.size();
+        if (n_out) *n_out = have;
+        const int64_t m = std::min(have, capacity);
+        if (lo_out && m > 0) memcpy(lo_out, h_lo.data(), sizeof(double) * m);
+        if (hi_out && m > 0) memcpy(hi_out, h_hi.data(), sizeof(double) * m);
+        return PCS_OK;
+    }
+    // pcs_bounds_trials: what the decided trials of the last loop left (the caller has synchronised the loop's stream)
+    int trials(const char *who, double *alpha_active, int64_t n_trials, int64_t *truncated) const {
+        if (n_trials < 0 || (n_trials > 0 && !alpha_active)) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+        if (!active()) return fail(PCS_ERR_STATE, "%s: no bounds set", who);
+        const int64_t m = std::min<int64_t>(n_trials, BOUNDS_LOG_TRIALS);
+        if (m > 0) HIPCHK(hipMemcpy(alpha_active, log(), sizeof(double) * 2 * m, hipMemcpyDeviceToHost));
+        for (int64_t k = 2 * m; k < 2 * n_trials; ++k) alpha_active[k] = std::nan("");
+        if (truncated) {
+            double t = 0.0;
+            HIPCHK(hipMemcpy(&t, n_truncated(), sizeof(double), hipMemcpyDeviceToHost));
+            *truncated = (int64_t)t;
+        }
+        return PCS_OK;
+    }
+};
+
 // Ordering of a handle's runs across streams: `done` is recorded after every run; whatever touches what a run reads or writes next
 // waits for it first.  (pcs_engine.hip's flush_done / mark_done are the lazily recording variant of this for the engine.)
 struct RunFence {

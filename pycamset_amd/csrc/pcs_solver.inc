@@ -154,12 +154,15 @@ static int schur_finish_piece(const char *who, int device, const BlockLayout &L,
     return enqueue_schur_finish(L, st, 256, s);
 }
 static int lm_decide_piece(const char *who, int device, int64_t n_params, hipStream_t s, const double *d_cost_old, const double *d_cost_new, const double *d_dvec,
-                           const double *d_gm, const double *d_delta, const double *d_ps, const uint8_t *d_fixed, int32_t *d_status, double *d_lambda, double *d_stats) {
+                           const double *d_gm, const double *d_delta, const double *d_ps, const uint8_t *d_fixed, int32_t *d_status, double *d_lambda, double *d_stats,
+                           const double *d_alpha = nullptr, uint8_t *d_pin = nullptr) {
     if (!d_cost_old || !d_cost_new || !d_dvec || !d_gm || !d_delta || !d_ps || !d_fixed || !d_status || !d_lambda || !d_stats) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
     HIPCHK(hipSetDevice(device));
     LmDecideArgs a{};
     a.tail[0] = d_cost_old; a.tail[1] = d_cost_new; a.ps2[0] = a.ps2[1] = d_ps;
     a.dvec = d_dvec; a.gm = d_gm; a.delta = d_delta; a.fixed = d_fixed; a.status = d_status; a.lambda = d_lambda; a.stats = d_stats; a.n_params = n_params;
+    a.alpha = d_alpha;   // pcs_lm_decide_bounded; NULL: pcs_lm_decide
+    a.pin = d_pin;
     hipLaunchKernelGGL(lm_decide_kernel, dim3(1), dim3(1024), 0, s, a);
     HIPCHK(hipGetLastError());
     return PCS_OK;
@@ -318,8 +321,72 @@ struct LmTrialDesc {
     bool selector = false;            // flags[2] selects the current one of two states (the engine); false: state 0 is always current (generated chains: sel = NULL, alt = 0)
     bool finish_zeroes = false;       // the NON-fused completion zeroes packed[1] on the way (generated chains: their contraction sums into it); false: the build's own prologue does (the engine)
     FinishSlabs slabs;                // what the fused completion prepares for the build (the engine's slabs; empty for a generated chain)
+    const BoundStore *bounds = nullptr;   // the handle's box bounds (csrc/ba_bounds.hpp).  Active: the caller leaves `fused` off — the fused completion prepares the engine's slabs at the trial string in the launch that writes it, and a truncation behind it would leave them stale
     bool empty_zero_state = false;    // the table is empty AND that means a zeroed trial state for a sharded loop's all-reduce (the engine: n == 0; needs PCS_LM_FIXED_TRIAL_BUFFER); a generated chain leaves it false: its build refuses an empty table
 };
+
+// The handle's box bounds (BoundStore, csrc/ba_bounds.hpp) around a Schur step.  `ps`, `g`: the strings and the gradients of the two states, the
+// current one named by *sel (NULL: state 0); one launch of one workgroup each, behind the stop word like every kernel of a trial.
+struct BoundsTarget { double *ps[2]; const double *g[2]; const int32_t *sel = nullptr, *stop = nullptr; };
+static BoundsArgs bounds_args(const BoundStore &bs, int64_t n_params, const BoundsTarget &t) {
+    BoundsArgs a{};
+    a.lo = bs.lo(); a.hi = bs.hi(); a.pin = bs.pin(); a.n_params = n_params;
+    a.ps[0] = t.ps[0]; a.ps[1] = t.ps[1]; a.g[0] = t.g[0]; a.g[1] = t.g[1]; a.sel = t.sel; a.stop = t.stop;
+    return a;
+}
+// fixed_eff <- fixed or "on a bound with the gradient pointing out" at the current state; *n_active <- how many entries the bounds added
+static int enqueue_bounds_active(const BoundStore &bs, int64_t n_params, const BoundsTarget &t, const uint8_t *fixed, uint8_t *fixed_eff, int32_t *n_active, hipStream_t s) {
+    BoundsArgs a = bounds_args(bs, n_params, t);
+    a.fixed = fixed; a.fixed_eff = fixed_eff; a.n_active = n_active;
+    hipLaunchKernelGGL(bounds_active_kernel, dim3(1), dim3(BOUNDS_THREADS), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return PCS_OK;
+}
+// the step `delta` from the current string cut at the first bound: delta, the trial string and *alpha
+static int enqueue_bounds_truncate(const BoundStore &bs, int64_t n_params, const BoundsTarget &t, double *delta, double *alpha, hipStream_t s) {
+    BoundsArgs a = bounds_args(bs, n_params, t);
+    a.delta = delta; a.alpha = alpha;
+    hipLaunchKernelGGL(bounds_truncate_kernel, dim3(1), dim3(BOUNDS_THREADS), 0, s, a);
+    HIPCHK(hipGetLastError());
+    return PCS_OK;
+}
+// pcs_bounds_active_device / pcs_bounds_truncate_device and their pcs_genchain_* twins
+static int bounds_active_piece(const char *who, int device, const BoundStore &bs, const BlockLayout &L, int64_t n_params, const double *d_ps, const double *d_packed,
+                               const uint8_t *d_fixed, uint8_t *d_fixed_eff, hipStream_t s) {
+    if (!d_ps || !d_packed || !d_fixed || !d_fixed_eff) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (!bs.active()) return fail(PCS_ERR_STATE, "%s: no bounds set", who);
+    HIPCHK(hipSetDevice(device));
+    double *ps = const_cast<double *>(d_ps);   // (read only by this kernel)
+    const BoundsTarget t{{ps, ps}, {d_packed + L.h_len(), d_packed + L.h_len()}};
+    return enqueue_bounds_active(bs, n_params, t, d_fixed, d_fixed_eff, bs.n_active(), s);
+}
+// the same two for a caller that keeps TWO states and a selector word, as pcs_lm_trial_build does (pcs_bounds_*_sel_device)
+static int bounds_active_sel_piece(const char *who, int device, const BoundStore &bs, const BlockLayout &L, int64_t n_params, const double *d_ps0, const double *d_ps1,
+                                   const double *d_packed0, const double *d_packed1, const uint8_t *d_fixed, uint8_t *d_fixed_eff, const int32_t *d_sel, hipStream_t s) {
+    if (!d_ps0 || !d_ps1 || !d_packed0 || !d_packed1 || !d_fixed || !d_fixed_eff || !d_sel) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (!bs.active()) return fail(PCS_ERR_STATE, "%s: no bounds set", who);
+    HIPCHK(hipSetDevice(device));
+    BoundsTarget t{{const_cast<double *>(d_ps0), const_cast<double *>(d_ps1)}, {d_packed0 + L.h_len(), d_packed1 + L.h_len()}};   // (read only by this kernel)
+    t.sel = d_sel;
+    return enqueue_bounds_active(bs, n_params, t, d_fixed, d_fixed_eff, bs.n_active(), s);
+}
+static int bounds_truncate_sel_piece(const char *who, int device, const BoundStore &bs, int64_t n_params, double *d_ps0, double *d_ps1, double *d_delta, double *d_alpha,
+                                     const int32_t *d_sel, hipStream_t s) {
+    if (!d_ps0 || !d_ps1 || d_ps0 == d_ps1 || !d_delta || !d_alpha || !d_sel) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (!bs.active()) return fail(PCS_ERR_STATE, "%s: no bounds set", who);
+    HIPCHK(hipSetDevice(device));
+    BoundsTarget t{{d_ps0, d_ps1}, {nullptr, nullptr}};
+    t.sel = d_sel;
+    return enqueue_bounds_truncate(bs, n_params, t, d_delta, d_alpha, s);
+}
+static int bounds_truncate_piece(const char *who, int device, const BoundStore &bs, int64_t n_params, const double *d_ps_in, double *d_delta, double *d_ps_out,
+                                 double *d_alpha, hipStream_t s) {
+    if (!d_ps_in || !d_delta || !d_ps_out || !d_alpha || d_ps_in == d_ps_out) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (!bs.active()) return fail(PCS_ERR_STATE, "%s: no bounds set", who);
+    HIPCHK(hipSetDevice(device));
+    const BoundsTarget t{{const_cast<double *>(d_ps_in), d_ps_out}, {nullptr, nullptr}};
+    return enqueue_bounds_truncate(bs, n_params, t, d_delta, d_alpha, s);
+}
 
 // build_trial(stream, fused) = the handle's own normal equations at ps[1] into packed[1]; fused: the completion has done its prologue's work.
 // (The guards on n_lead > 0 never bite: every layout either handle kind makes has leading columns.)
@@ -332,6 +399,15 @@ static int enqueue_lm_trial_build(const LmTrialDesc &d, const pcs_lm_buffers *b,
     st.stop = b->flags;
     if (d.selector) { st.sel = b->flags + 2; st.alt = alt_pk; }
     st.out_alt = -alt_pk;
+    // box bounds: the active set of the CURRENT state (for a sharded loop the all-reduced one with the prior added: the same bits on every
+    // rank) takes the place of the caller's mask in the step; nothing is queued without bounds
+    const bool bounded = d.bounds && d.bounds->active();
+    if (bounded && d.fused) return fail(PCS_ERR_STATE, "%s: a bounded trial takes the non-fused sequence", d.who);
+    const BoundsTarget bt{{b->ps[0], b->ps[1]}, {b->packed[0] + L.h_len(), b->packed[1] + L.h_len()}, st.sel, st.stop};
+    if (bounded) {
+        if (const int brc = enqueue_bounds_active(*d.bounds, d.n_params, bt, b->fixed, d.bounds->fixed_eff(), d.bounds->n_active(), s)) return brc;
+        st.fixed = d.bounds->fixed_eff();
+    }
     // the one-launch Cholesky wants its hand-over workspace at the fill value: the preparation sets it on the way (one launch fewer)
     const bool prefill = L.n_lead > 0 && dense_spd_is_one_launch(d.device, L.n_lead, b->spd_algorithm);
     if (prefill) { st.fill = b->spd_work; st.fill_n = cp_work_doubles((L.n_lead + 31) / 32); }
@@ -362,6 +438,10 @@ static int enqueue_lm_trial_build(const LmTrialDesc &d, const pcs_lm_buffers *b,
     // trial state in ONE launch; else the step, the trial string and the vote
     rc = d.fused ? enqueue_schur_finish_fused(L, d.n_params, d.n_cu, d.slabs, st, s) : enqueue_schur_finish(L, st, d.n_cu, s);
     if (rc) return rc;
+    if (bounded) {   // the step stops at the first bound it meets, in front of the build (whose own prologue prepares the slabs from the trial string)
+        rc = enqueue_bounds_truncate(*d.bounds, d.n_params, bt, b->delta, d.bounds->alpha(), s);
+        if (rc) return rc;
+    }
     if (d.empty_zero_state) {
         // a rank whose observation shard is empty (ceil(N / world) rows per rank can leave the last ranks without any) contributes zeros
         // to the all-reduce of the trial state; the vote word behind it stays
@@ -401,7 +481,7 @@ static int prior_add_piece(const char *who, int device, const PriorStore &pr, co
 }
 
 // The second half of a trial for a state of layout L ([blocks | g | cost]; pcs_engine and pcs_genchain alike).
-static int enqueue_lm_finish(int n_cu, int64_t n_params, const BlockLayout &L, const PriorStore &prior, const pcs_lm_buffers *b, hipStream_t s) {
+static int enqueue_lm_finish(int n_cu, int64_t n_params, const BlockLayout &L, const PriorStore &prior, const BoundStore &bounds, const pcs_lm_buffers *b, hipStream_t s) {
     const int64_t n_packed = L.packed_len(n_params);
     const bool fixed_buffer = (b->mode & PCS_LM_FIXED_TRIAL_BUFFER) != 0;
     if (prior.active()) {   // the prior at the trial string onto the trial state (behind a sharded loop's all-reduce), in front of the decision
@@ -414,6 +494,10 @@ static int enqueue_lm_finish(int n_cu, int64_t n_params, const BlockLayout &L, c
     a.sel = b->flags + 2;
     a.dvec = b->dvec; a.gm = b->gm; a.delta = b->delta; a.fixed = b->fixed; a.status = b->status; a.lambda = b->lambda; a.stats = b->stats;
     a.n_params = n_params;
+    if (bounds.active()) {   // the decision on the truncated step: the effective mask, alpha, and the trial's record for the host
+        a.fixed = bounds.fixed_eff(); a.alpha = bounds.alpha(); a.n_active = bounds.n_active();
+        a.bound_log = bounds.log(); a.bound_log_trials = BOUNDS_LOG_TRIALS; a.n_truncated = bounds.n_truncated(); a.pin = bounds.pin();
+    }
     a.ctrl = b->ctrl; a.stop_flag = b->flags; a.accept_flag = b->flags + 1;
     a.use_votes = (b->mode & PCS_LM_VOTES) ? 1 : 0;
     a.keep_sel = fixed_buffer ? 1 : 0;

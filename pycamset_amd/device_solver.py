@@ -35,7 +35,7 @@ import time
 import numpy as np
 
 from ._capi import LOSS_IDS
-from .engine import Engine, expand_sigma
+from .engine import Engine, bounds_arrays, expand_sigma
 
 
 class JacobianOperator:
@@ -196,6 +196,11 @@ class BlockedNormalEquations:
         self.syrk_work_len = schur_syrk_work_len(self.n_lead, self.n_trail) if self.n_trail else 0
         self.syrk_work = torch.empty(max(1, self.syrk_work_len), **f64)
         self._cons = None   # sharded host-steered loop only: the ranks' consensus step (n_params + 2)
+        # box bounds (engine.set_bounds) in the host-steered pieces: the effective mask of the last `solve` and the fraction of its step
+        # that `truncate` kept.  (The device-steered loop keeps both in the handle.)
+        self.fixed_eff = torch.zeros_like(self.fixed)
+        self.alpha = torch.ones(1, **f64)
+        self.bounded = False   # set by lm_solve: the engine carries bounds for this solve
         self.spd_algorithm = "auto"   # 'launches' after a one-launch solve ran out of time (another process held the compute units)
 
     def cost(self, slot):
@@ -241,12 +246,21 @@ class BlockedNormalEquations:
             # nothing is queued when none is set.  (The trials of the device-steered loop get it from lm_trial_finish.)
             self.eng.prior_add_device(ps.data_ptr(), buf.data_ptr(), stream)
 
-    def solve(self, slot: int, lam, ps=None, ps_out=None):
+    def solve(self, slot: int, lam, ps=None, ps_out=None, truncate=True):
         """Enqueue the damped step (H + lam diag(H)) delta = -g for the state in packed[slot]: ``self.delta`` (n_params,
         parameter-string order, 0 where fixed) and — given the current parameter string ``ps`` — the trial string
-        ``ps_out = ps + delta``.  Device work only; ``self.status`` becomes non-zero when a factorisation fails."""
+        ``ps_out = ps + delta``.  Device work only; ``self.status`` becomes non-zero when a factorisation fails.
+        With ``self.bounded`` (needs ``ps``): the active set of the state takes the place of the mask (``self.fixed_eff``), and — unless
+        ``truncate=False``: the caller calls ``truncate`` itself — the step is cut at the first bound (``self.alpha``)."""
+        fixed = self.fixed
+        if self.bounded:
+            if ps is None:
+                raise ValueError("a bounded step needs the current parameter string")
+            fixed = self.fixed_eff
         with self.on_stream() as stream:
-            self.eng.schur_prepare(self.packed[slot].data_ptr(), self.fixed.data_ptr(), lam.data_ptr(), self.linvt.data_ptr(), self.u.data_ptr(),
+            if self.bounded:
+                self.eng.bounds_active_device(ps.data_ptr(), self.packed[slot].data_ptr(), self.fixed.data_ptr(), fixed.data_ptr(), stream)
+            self.eng.schur_prepare(self.packed[slot].data_ptr(), fixed.data_ptr(), lam.data_ptr(), self.linvt.data_ptr(), self.u.data_ptr(),
                                    self.V.data_ptr(), self.S.data_ptr(), self.rhs.data_ptr(), self.dvec.data_ptr(), self.gm.data_ptr(),
                                    self.status.data_ptr(), stream)
             ldv = self.V.shape[1]
@@ -267,9 +281,16 @@ class BlockedNormalEquations:
                 w = self.w
             else:
                 w = self.u
-            self.eng.schur_finish(self.linvt.data_ptr(), self.u.data_ptr(), w.data_ptr(), xl.data_ptr(), self.fixed.data_ptr(), self.delta.data_ptr(),
+            self.eng.schur_finish(self.linvt.data_ptr(), self.u.data_ptr(), w.data_ptr(), xl.data_ptr(), fixed.data_ptr(), self.delta.data_ptr(),
                                   ps.data_ptr() if ps is not None else 0, ps_out.data_ptr() if ps is not None else 0, stream)
+        if self.bounded and truncate:
+            self.truncate(ps, ps_out)
         return self.delta
+
+    def truncate(self, ps, ps_out):
+        """The step of the last ``solve`` cut at the first bound: ``self.delta`` and ``ps_out`` in place, ``self.alpha``."""
+        with self.on_stream() as stream:
+            self.eng.bounds_truncate_device(ps.data_ptr(), self.delta.data_ptr(), ps_out.data_ptr(), self.alpha.data_ptr(), stream)
 
     def _consensus_step(self, ps, ps_out):
         """Sharded host-steered loop WITHOUT the engine's deterministic mode: every rank has solved the SAME all-reduced system, but
@@ -293,6 +314,11 @@ class BlockedNormalEquations:
         updates ``lam`` in place, clears ``status`` and fills ``stats`` (12 doubles) — what the host reads once per trial."""
         last = 8 * (self.n_packed - 1)
         with self.on_stream() as stream:
+            if self.bounded:
+                self.eng.lm_decide_bounded(self.packed[cur].data_ptr() + last, self.packed[new].data_ptr() + last, self.dvec.data_ptr(), self.gm.data_ptr(),
+                                           self.delta.data_ptr(), ps.data_ptr(), self.fixed_eff.data_ptr(), self.alpha.data_ptr(), self.status.data_ptr(),
+                                           lam.data_ptr(), stats.data_ptr(), stream=stream)
+                return
             self.eng.lm_decide(self.packed[cur].data_ptr() + last, self.packed[new].data_ptr() + last, self.dvec.data_ptr(), self.gm.data_ptr(),
                                self.delta.data_ptr(), ps.data_ptr(), self.fixed.data_ptr(), self.status.data_ptr(), lam.data_ptr(), stats.data_ptr(),
                                stream)
@@ -329,7 +355,10 @@ class BlockedNormalEquations:
     def predicted_reduction(self, lam):
         """(0.5 (lam d'D d - g'd), step is valid) of the last ``solve`` as device tensors (tests; the loop uses ``decide``)."""
         torch = self.torch
-        pred = 0.5 * (lam[0] * torch.dot(self.dvec, self.delta * self.delta) - torch.dot(self.gm, self.delta))
+        if self.bounded:
+            pred = 0.5 * lam[0] * torch.dot(self.dvec, self.delta * self.delta) - (1.0 - 0.5 * self.alpha[0]) * torch.dot(self.gm, self.delta)
+        else:
+            pred = 0.5 * (lam[0] * torch.dot(self.dvec, self.delta * self.delta) - torch.dot(self.gm, self.delta))
         return pred, (self.status[0] == 0) & torch.isfinite(pred)
 
     def gradient(self, slot: int, lam=None):
@@ -519,16 +548,24 @@ def _lm_loop_device(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, ft
         g, x, cost = out[:n_free].copy(), out[n_free: 2 * n_free].copy(), 0.5 * float(out[-1])
         if not history:
             history.append(cost)
+        bound_trials, n_truncated = [], 0
+        if ne.bounded:   # alpha and the active count of every decided trial, kept by the handle (one read-back, behind the loop)
+            torch.cuda.current_stream().synchronize()
+            log, n_truncated = eng.bounds_trials(len(trials))
+            bound_trials = [(float(a), int(n)) if a == a else (float("nan"), -1) for a, n in log]
     return DeviceLMResult(x=x, cost=cost, grad=g, optimality=float(np.max(np.abs(g))) if g.size else 0.0, nit=it, nfev=nfev,
                           n_jtjv=n_lin, status=STOP_STATUS.get(code, 0), message=STOP_MESSAGES.get(code, f"stopped ({code})"), history=history,
-                          trials=trials)
+                          trials=trials, bound_trials=bound_trials, n_truncated=n_truncated)
 
 
 def _gain_ratio(ne: BlockedNormalEquations, stats) -> float:
     """actual / predicted reduction of the trial `stats` describes (host-steered loop; the device-steered one has it in the kernel)."""
     torch = ne.torch
     lam_used = float(stats[7])
-    pred = 0.5 * float((lam_used * torch.dot(ne.dvec, ne.delta * ne.delta) - torch.dot(ne.gm, ne.delta)).item())
+    if ne.bounded:
+        pred = float((0.5 * lam_used * torch.dot(ne.dvec, ne.delta * ne.delta) - (1.0 - 0.5 * ne.alpha[0]) * torch.dot(ne.gm, ne.delta)).item())
+    else:
+        pred = 0.5 * float((lam_used * torch.dot(ne.dvec, ne.delta * ne.delta) - torch.dot(ne.gm, ne.delta)).item())
     return 0.5 * (float(stats[6]) - float(stats[5])) / pred if pred > 0 else -1.0
 
 
@@ -557,15 +594,20 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
         it = 0
         any_accepted = False
         trials = []
+        bound_trials, n_truncated = [], 0
+        truncated = False
         for it in range(1, max_iter + 1):
             accepted = False
             stop = False
             retry = 0
             while retry < REJECTION_LIMIT:   # damping retries
-                ne.solve(cur, lam, ps, ps_new)
+                consensus = ne.reduce_fn is not None and not deterministic
+                ne.solve(cur, lam, ps, ps_new, truncate=not consensus)
                 if ne.reduce_fn is not None:
-                    if not deterministic:
+                    if consensus:
                         ne._consensus_step(ps, ps_new)
+                        if ne.bounded:   # the ranks' ONE step is what the bounds cut
+                            ne.truncate(ps, ps_new)
                     ne.packed[new][ne.n_packed] = (ne.status[0] & 4).to(torch.float64)     # this rank's vote: "my dense solve gave up"
                 n_lin += 1
                 ne.build(ps_new, new)                                                        # the all-reduce sums the votes with the blocks
@@ -581,6 +623,10 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
                 # completed below where this loop's own rules change lambda
                 trials.append(stats)
                 stats[9], stats[10] = len(trials), cur
+                if ne.bounded:   # alpha and the entries the bounds added to the mask (the device-steered loop: pcs_bounds_trials)
+                    ab = torch.stack([ne.alpha[0], ((ne.fixed_eff != 0) & (ne.fixed == 0)).sum().to(torch.float64)]).cpu().numpy()
+                    bound_trials.append((float(ab[0]), int(ab[1])))
+                    truncated = ab[0] < 1.0
                 if stats[0] < 0:   # the one-launch dense solve gave up waiting on SOME rank (status bit 2): nothing of this trial is valid —
                     stats[8] = 9
                     ne.spd_algorithm = "launches"   # every rank repeats it with the launch-per-column form (the decision left the damping alone)
@@ -589,6 +635,7 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
                     continue
                 stats[8] = 0
                 retry += 1
+                n_truncated += 1 if truncated else 0
                 gmax = float(stats[1])
                 if verbose:
                     print(f"  it {it}: lam {stats[7]:.2e} cost {0.5 * stats[6]:.6e} -> {0.5 * stats[5]:.6e} accepted {bool(stats[0])}")
@@ -599,7 +646,8 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
                 if stats[0] > 0:
                     accepted = any_accepted = True
                     # pcs_lm_decide applied the classic 1/3; a gain ratio above LAM_FAST[0] earns LAM_FAST[1] (the device-steered loop's rule)
-                    if _gain_ratio(ne, stats) > LAM_FAST[0]:
+                    # (not for a step cut at a bound: pcs_lm_decide_bounded left lambda alone, and so does this rule)
+                    if not truncated and _gain_ratio(ne, stats) > LAM_FAST[0]:
                         stats[11] = max(float(stats[7]) * LAM_FAST[1], 1e-12)
                         lam.fill_(stats[11])
                     ps, ps_new = ps_new, ps
@@ -618,11 +666,11 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
             if not accepted:
                 status, message = 2, "no further decrease (damping exhausted)"
                 break
-            if rel_drop <= ftol:
+            if not truncated and rel_drop <= ftol:       # (a truncated trial's small drop and small step say nothing about convergence)
                 status, message = 3, "ftol reached"
                 trials[-1][8] = 3
                 break
-            if step_norm <= xtol * (xtol + x_norm):
+            if not truncated and step_norm <= xtol * (xtol + x_norm):
                 status, message = 4, "xtol reached"
                 trials[-1][8] = 4
                 break
@@ -632,7 +680,7 @@ def _lm_loop_blocked(ne: BlockedNormalEquations, ps0: np.ndarray, *, max_iter, f
         x = ps[ne.free_idx].cpu().numpy()
         cost = 0.5 * float(ne.cost(cur).item())
     return DeviceLMResult(x=x, cost=cost, grad=g, optimality=float(np.max(np.abs(g))) if g.size else 0.0, nit=it, nfev=nfev,
-                          n_jtjv=n_lin, status=status, message=message, history=history, trials=trials)
+                          n_jtjv=n_lin, status=status, message=message, history=history, trials=trials, bound_trials=bound_trials, n_truncated=n_truncated)
 
 
 @dataclass
@@ -653,6 +701,58 @@ class DeviceLMResult:
     # With a prior the two sums are those of the augmented objective (the prior's sum included).
     trials: list = field(default_factory=list)
     prior_cost: float = 0.0     # 0.5 * sum (((x - prior_mean) / prior_sigma)^2) at x: the prior's share of ``cost`` (0.0 without a prior)
+    # box bounds (lm_solve(bounds=)); None / 0 / empty without them
+    active_mask: np.ndarray | None = None   # scipy's convention over the free vector: -1 at the lower bound, +1 at the upper, 0 otherwise
+    n_truncated: int = 0                    # decided trials whose step was cut at a bound (alpha < 1)
+    bound_trials: list = field(default_factory=list)   # per decided trial, parallel to ``trials``: (alpha, entries the bounds added to the mask)
+
+
+def _free_bounds(x0, bounds):
+    """``lm_solve``'s ``bounds`` on the FREE vector -> (lo, hi) as float64 arrays of x0's length, or None for ``None`` and for bounds that
+    are all infinite.  scipy's forms: ``(lo, hi)`` with scalars or arrays, or an object with ``lb`` / ``ub`` (``scipy.optimize.Bounds``).
+    ValueError for wrong shapes, NaN, ``lo > hi`` or an ``x0`` outside the box, naming the first offending index — nothing else is touched."""
+    if bounds is None:
+        return None
+    if hasattr(bounds, "lb") and hasattr(bounds, "ub"):
+        lo, hi = bounds.lb, bounds.ub
+    else:
+        try:
+            lo, hi = bounds
+        except (TypeError, ValueError):
+            raise ValueError("bounds must be (lo, hi) or a scipy.optimize.Bounds") from None
+    x0 = np.asarray(x0, dtype=np.float64).ravel()
+    fb = bounds_arrays(x0.shape[0], lo, hi, "bounds")
+    if fb is None:
+        return None
+    bad = (x0 < fb[0]) | (x0 > fb[1])
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"`x0` is infeasible: x0[{k}] = {x0[k]} lies outside [{fb[0][k]}, {fb[1][k]}]")
+    return fb
+
+
+def _string_bounds(mask, fb):
+    """The free-vector bounds as (lo, hi) over the parameter string (``_string_prior``'s indexing); fixed parameters get none."""
+    if fb is None:
+        return None
+    free = np.flatnonzero(mask)
+    if free.shape[0] != fb[0].shape[0]:
+        raise ValueError(f"the bounds have {fb[0].shape[0]} entries, the handler has {free.shape[0]} free parameters")
+    lo, hi = np.full(mask.shape[0], -np.inf), np.full(mask.shape[0], np.inf)
+    lo[free], hi[free] = fb
+    return lo, hi
+
+
+def _bound_result(res, fb):
+    """``active_mask`` of a bounded solve: the active set of the FINAL state — on a bound with the gradient pointing out of the box, what
+    bounds_active_kernel computes for a trial —, and the optimality as the projected gradient."""
+    lo, hi = fb
+    am = np.zeros(res.x.shape[0], dtype=np.int64)
+    am[(res.x <= lo) & ((res.grad > 0.0) | (lo == hi))] = -1
+    am[(res.x >= hi) & (res.grad < 0.0)] = 1
+    res.active_mask = am
+    res.optimality = float(np.max(np.abs(res.grad[am == 0]))) if np.any(am == 0) else 0.0
+    return res
 
 
 def _free_prior(x0, prior_mean, prior_sigma):
@@ -799,12 +899,14 @@ def _n_cams_of(op_fun, dd) -> int:
 
 
 @contextlib.contextmanager
-def _engine_settings(eng, loss, f_scale, inv_sigma, prior=None):
-    """The engine's loss, noise weights and parameter prior (``(mean, inv_sigma)`` over the string, or None) for one solve; all are
-    restored afterwards (a failed solve included).  A generated chain has no loss and no weights to set: the prior only."""
+def _engine_settings(eng, loss, f_scale, inv_sigma, prior=None, bounds=None):
+    """The engine's loss, noise weights, parameter prior (``(mean, inv_sigma)`` over the string, or None) and box bounds (``(lo, hi)`` over
+    the string, or None) for one solve; all are restored afterwards (a failed solve included).  A generated chain has no loss and no
+    weights to set: the prior and the bounds only."""
     fused = isinstance(eng, Engine)
     saved_loss, saved_w = (eng.loss(), eng.weights()) if fused else (None, None)
     saved_prior = eng.prior()
+    saved_bounds = eng.bounds()
     if fused:
         eng.set_loss(loss, f_scale)
     try:
@@ -814,8 +916,16 @@ def _engine_settings(eng, loss, f_scale, inv_sigma, prior=None):
             eng.set_prior()
         else:
             eng.set_prior(prior[0], inv_sigma=prior[1])
+        if bounds is not None:
+            eng.set_bounds(*bounds)
+        elif saved_bounds is not None:
+            eng.set_bounds()
         yield
     finally:
+        if saved_bounds is not None:
+            eng.set_bounds(*saved_bounds)
+        elif bounds is not None:
+            eng.set_bounds()
         if fused:
             eng.set_loss(*saved_loss)
             eng.set_weights(inv_sigma=saved_w)
@@ -825,11 +935,13 @@ def _engine_settings(eng, loss, f_scale, inv_sigma, prior=None):
             eng.set_prior(saved_prior[0], inv_sigma=saved_prior[1])
 
 
-def _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma=None, prior=None) -> BlockedNormalEquations:
-    """The engine's cached solver state for this mask, collective, layout, loss, noise weights and prior (one state per engine: a miss
-    drops the previous one)."""
+def _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma=None, prior=None, bounds=None) -> BlockedNormalEquations:
+    """The engine's cached solver state for this mask, collective, layout, loss, noise weights, prior and bounds (one state per engine: a
+    miss drops the previous one)."""
     key = (hash(mask.tobytes()), id(reduce_fn), tuple(sorted(eng.normal_layout().items())), loss, f_scale,
            None if inv_sigma is None else hash(inv_sigma.tobytes()), None if prior is None else hash(prior[0].tobytes() + prior[1].tobytes()))
+    if bounds is not None:   # (appended: a solve without bounds keeps the key it had)
+        key += (hash(bounds[0].tobytes() + bounds[1].tobytes()),)
     cache = eng.__dict__.setdefault("_blocked_solvers", {})
     ne = cache.get(key)
     if ne is None:
@@ -843,7 +955,7 @@ def _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma=None, prior=N
 def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float = 1e-8, gtol: float = 1e-8,
              cg_tol: float = 1e-3, cg_max_iter: int = 200, lam0: float | None = None, lam_grow0: float | None = None, reduce_fn=None, verbose: int = 0,
              operator=None, linear_solver: str = "auto", loss: str = "linear", f_scale: float = 1.0, sigma=None,
-             prior_mean=None, prior_sigma=None) -> DeviceLMResult:
+             prior_mean=None, prior_sigma=None, bounds=None) -> DeviceLMResult:
     """Levenberg-Marquardt (Marquardt scaling D = diag(J^T J)) for a pycamset_amd handler.  The damped
     normal equations are solved by Jacobi-PCG on matrix-free J^T J products (``linear_solver='pcg'``) or
     by a Cholesky factorisation of the block-reduced J^T J (``'cholesky'``).  Every quantity that depends
@@ -880,8 +992,27 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
     from per-group values.  Works on every path: the blocked loops add the prior on the device (include/pcs_hip.h pcs_set_prior; set
     for the solve and restored afterwards), ``linear_solver='pcg'`` and a caller's ``operator`` add it on the host; with ``loss`` and
     ``sigma`` on hand-fused chains, with the linear loss on generated chains.  The result's ``cost`` and ``grad`` are those of the
-    augmented objective, ``prior_cost`` is the prior's half sum at ``x``.  ValueError for wrong shapes or values, before any device work."""
+    augmented objective, ``prior_cost`` is the prior's half sum at ``x``.  ValueError for wrong shapes or values, before any device work.
+
+    ``bounds``: box bounds on the free vector in the order of ``x0``, in scipy ``least_squares``'s forms — ``(lo, hi)`` with scalars or
+    arrays, or a ``scipy.optimize.Bounds``; ``-np.inf`` / ``np.inf`` = no bound.  ``handlers.slab_bounds`` builds the two arrays from
+    per-group values.  The method ("Parameter bounds"; include/pcs_hip.h pcs_set_bounds): per trial an active set — on a
+    bound with the gradient pointing out — joins the fixed parameters of the step, the step is cut at the first bound it meets, and the
+    decision uses the cut step's predicted reduction; gtol tests the projected gradient, a cut trial triggers neither ftol nor xtol and
+    never lowers the damping.
+    Every blocked loop takes it (device- and host-steered, sharded, generated chains), with ``loss``, ``sigma`` and the prior; the
+    engine's bounds are set for the solve and restored afterwards.  ``bounds=None`` or all infinite sets nothing: the launches and the
+    bits of a solve without the argument.  The result's ``active_mask`` follows scipy (-1 lower, +1 upper, 0 free), ``n_truncated``
+    counts the cut trials, ``optimality`` is the projected gradient's maximum.  ValueError before any device work for wrong shapes,
+    NaN, ``lo > hi`` or an infeasible ``x0``; NotImplementedError for ``linear_solver='pcg'``, a caller's ``operator`` and systems
+    beyond ``blocked_fits``."""
     prior = _free_prior(x0, prior_mean, prior_sigma)
+    fbounds = _free_bounds(x0, bounds)
+    if fbounds is not None and linear_solver == "pcg":
+        raise NotImplementedError("bounds: the matrix-free step of linear_solver='pcg' has no active set; "
+                                  "bounds need the blocked normal equations (linear_solver='cholesky' or 'auto')")
+    if fbounds is not None and operator is not None:
+        raise NotImplementedError("bounds with a caller-supplied operator: the host loop knows nothing of bounds")
     if loss not in LOSS_IDS:
         raise ValueError(f"unknown loss {loss!r}: expected one of {sorted(LOSS_IDS)}")
     f_scale = float(f_scale)
@@ -921,6 +1052,11 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
         if weighted and linear_solver == "pcg":
             raise NotImplementedError("sigma: this system is too large for the blocked normal equations (linear_solver='auto' chose "
                                       "'pcg', whose matrix-free products use the raw Jacobian)")
+        if fbounds is not None and linear_solver == "pcg":
+            raise NotImplementedError("bounds: this system is too large for the blocked normal equations (linear_solver='auto' chose "
+                                      "'pcg', whose matrix-free step has no active set)")
+        if fbounds is not None and not blocked_fits(eng):
+            raise NotImplementedError("bounds: this system is too large for the blocked normal equations (device_solver.blocked_fits)")
         if linear_solver == "cholesky":
             # the solver's device workspace (two packed states, V, S, a stream) lives with the engine: a second solve on the same
             # table and mask — the usual case: a calibration re-run with other start values or tolerances — allocates nothing
@@ -932,16 +1068,21 @@ def lm_solve(handler, x0, *, max_iter: int = 50, ftol: float = 1e-8, xtol: float
             # (... and the noise weights, in the same way: the engine's weights are set per solve below, and a state is never carried
             # from one set of weights to another, or from a weighted solve to an unweighted one)
             # (... and the prior, likewise: set per solve below, never carried from one solve's prior to another's)
+            # (... and the bounds, likewise)
             sprior = _string_prior(mask, prior)
-            ne = _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma, sprior)
+            sbounds = _string_bounds(mask, fbounds)
+            ne = _blocked_solver(eng, mask, reduce_fn, loss, f_scale, inv_sigma, sprior, sbounds)
             ne.spd_algorithm = "auto"
+            ne.bounded = sbounds is not None   # the loops' pieces consult the engine's bounds (set below) only then
             ps0 = op_fun.build_param_list(*handler.get_bundle_adjustment_inputs(np.array(x0, dtype=np.float64)))
-            if not isinstance(eng, Engine) and sprior is None:   # generated chains: linear only (checked above); no prior: nothing to set
+            # generated chains: linear only (checked above); no prior and no bounds, here or left on the engine by its owner
+            # (ChainEngine.set_bounds is public; the settings below set them aside for the solve): nothing to set
+            if not isinstance(eng, Engine) and sprior is None and sbounds is None and eng.bounds() is None:
                 return _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
-            with _engine_settings(eng, loss, f_scale, inv_sigma, sprior):
+            with _engine_settings(eng, loss, f_scale, inv_sigma, sprior, sbounds):
                 res = _lm_solve_blocked(ne, ps0, max_iter=max_iter, ftol=ftol, xtol=xtol, gtol=gtol, lam0=lam0_exact, lam_grow0=grow0, verbose=verbose)
             res.prior_cost = _prior_half_sum(prior, res.x)
-            return res
+            return res if fbounds is None else _bound_result(res, fbounds)
         operator = JacobianOperator(eng, handler._jac_mask(), reduce_fn=reduce_fn)
     elif linear_solver == "auto":
         linear_solver = "cholesky" if hasattr(operator, "build") else "pcg"
@@ -1091,6 +1232,9 @@ def parameter_covariance(handler, x, *, absolute_sigma: bool = False, rcond: flo
     1 / sigma^2 — what makes a gauge-free self-calibration or an unobserved entity invertible —, the prior rows count as observations:
     sigma^2 = (sum r^2 + sum ((x - mean) / sigma)^2) / (2N + n_prior - n_free), and the degrees-of-freedom test uses the same count.
     ``prior_mean`` is required unless ``absolute_sigma=True``, where the mean plays no part.  Generated chains included.
+
+    Box bounds (``lm_solve(bounds=)``) are not known here: a parameter that ended on a bound is not free to vary, so fix the parameters
+    of the solve's ``active_mask`` through the handler's mask before asking for the covariance of the others.
 
     Raises np.linalg.LinAlgError when H is singular or nearly so (a non-positive pivot, a trailing block that is not positive
     definite, or min L_ii^2 / H_ii below ``rcond``): a free gauge or an unobserved parameter.  ValueError for a wrong ``len(x)``

@@ -87,6 +87,30 @@ def prior_arrays(n_params: int, mean, sigma=None, inv_sigma=None):
     return np.ascontiguousarray(np.where(w > 0.0, m, 0.0)), np.ascontiguousarray(w)
 
 
+def bounds_arrays(n: int, lo, hi, what: str = "bounds"):
+    """(lo, hi) as float64 (n,) arrays from scalars, arrays or None (= no bound on that side), or None when every entry is infinite.
+    ValueError for wrong shapes, NaN or ``lo > hi``; the text names the first offending index."""
+    def side(v, fill):
+        v = np.asarray(fill if v is None else v, dtype=np.float64)
+        if v.ndim == 0:
+            return np.full(n, float(v))
+        v = np.array(v, dtype=np.float64).ravel()
+        if v.shape[0] != n:
+            raise ValueError(f"{what}: {v.shape[0]} values for {n} parameters")
+        return v
+    lo, hi = side(lo, -np.inf), side(hi, np.inf)
+    bad = np.isnan(lo) | np.isnan(hi)
+    if bad.any():
+        raise ValueError(f"{what}: NaN at index {int(np.flatnonzero(bad)[0])}")
+    bad = lo > hi
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"{what}: lower bound {lo[k]} > upper bound {hi[k]} at index {k}")
+    if np.all(lo == -np.inf) and np.all(hi == np.inf):
+        return None
+    return np.ascontiguousarray(lo), np.ascontiguousarray(hi)
+
+
 class _PinnedBlock:
     """Owner of one page-locked host allocation; NumPy views keep it alive through ``base``."""
 
@@ -299,6 +323,58 @@ class Engine:
 
     def _prior_fn(self, name: str):
         return getattr(lib(), self._PRIOR_PREFIX + name)
+
+    def set_bounds(self, lo=None, hi=None):
+        """Box bounds on the parameter string for the LM solve of this engine (include/pcs_hip.h pcs_set_bounds): ``lo`` and ``hi`` are
+        scalars or (n_params,) arrays in parameter-string order, ``-np.inf`` / ``np.inf`` (or ``None`` for one side) = no bound there;
+        ``lo[i] == hi[i]`` acts as fixed.  ``set_bounds()`` — and bounds that are all infinite — clear them; a new detection table keeps
+        them.  With bounds set a trial (``lm_trial*``) takes the non-fused sequence plus two one-workgroup launches; without, nothing
+        changes.  ValueError for wrong shapes, NaN or ``lo > hi``, naming the first offending index."""
+        b = None if lo is None and hi is None else bounds_arrays(self.n_params, lo, hi)
+        if b is None:
+            check(self._prior_fn("set_bounds")(self._h, None, None, 0))
+            return
+        check(self._prior_fn("set_bounds")(self._h, _dp(b[0]), _dp(b[1]), self.n_params))
+
+    def bounds(self):
+        """The current bounds as (lo, hi), float64 (n_params,) each, or None when none are set."""
+        n = c_int64(0)
+        check(self._prior_fn("get_bounds")(self._h, None, None, 0, byref(n)))
+        if n.value == 0:
+            return None
+        lo, hi = np.empty(n.value), np.empty(n.value)
+        check(self._prior_fn("get_bounds")(self._h, _dp(lo), _dp(hi), n.value, None))
+        return lo, hi
+
+    def bounds_trials(self, n_trials: int):
+        """((n_trials, 2) array of [alpha, entries the bounds added to the mask] per decided trial, number of truncated trials) of the
+        device-steered loop since ``set_bounds``; the caller has synchronised the loop's stream."""
+        out = np.empty((max(0, int(n_trials)), 2))
+        nt = c_int64(0)
+        check(self._prior_fn("bounds_trials")(self._h, _dp(out) if out.size else None, out.shape[0], byref(nt)))
+        return out, int(nt.value)
+
+    def bounds_active_device(self, d_ps: int, d_packed: int, d_fixed: int, d_fixed_eff: int, stream: int | None = None):
+        """The active set at the DEVICE-resident string ``d_ps`` and the packed state built there: ``d_fixed_eff`` (n_params bytes) <-
+        the caller's mask plus every entry on a bound whose gradient points out of the box; asynchronous."""
+        check(self._prior_fn("bounds_active_device")(self._h, *(c_void_p(p) for p in (d_ps, d_packed, d_fixed, d_fixed_eff)), _stream_arg(stream)))
+
+    def bounds_truncate_device(self, d_ps_in: int, d_delta: int, d_ps_out: int, d_alpha: int, stream: int | None = None):
+        """The step ``d_delta`` from ``d_ps_in`` cut at the first bound: ``d_delta`` in place, the trial string ``d_ps_out`` and the
+        fraction kept ``*d_alpha``; asynchronous."""
+        check(self._prior_fn("bounds_truncate_device")(self._h, *(c_void_p(p) for p in (d_ps_in, d_delta, d_ps_out, d_alpha)), _stream_arg(stream)))
+
+    def bounds_active_sel_device(self, d_ps0, d_ps1, d_packed0, d_packed1, d_fixed, d_fixed_eff, d_sel, stream=None):
+        """``bounds_active_device`` for two states and a selector word (``*d_sel != 0``: state 1 is current), as ``lm_trial_build`` runs it."""
+        check(lib().pcs_bounds_active_sel_device(self._h, *(c_void_p(p) for p in (d_ps0, d_ps1, d_packed0, d_packed1, d_fixed, d_fixed_eff, d_sel)), _stream_arg(stream)))
+
+    def bounds_truncate_sel_device(self, d_ps0, d_ps1, d_delta, d_alpha, d_sel, stream=None):
+        """``bounds_truncate_device`` for two strings and a selector word: the trial string goes into the state that is not current."""
+        check(lib().pcs_bounds_truncate_sel_device(self._h, *(c_void_p(p) for p in (d_ps0, d_ps1, d_delta, d_alpha, d_sel)), _stream_arg(stream)))
+
+    def lm_decide_bounded(self, d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed_eff, d_alpha, d_status, d_lambda, d_stats, stream=None):
+        check(self._prior_fn("lm_decide_bounded")(self._h, *(c_void_p(p) for p in (d_cost_old, d_cost_new, d_dvec, d_gm, d_delta, d_ps, d_fixed_eff, d_alpha,
+                                                                                 d_status, d_lambda, d_stats)), _stream_arg(stream)))
 
     def option(self, key: str, default: int) -> int:
         """The value last given to ``set_option(key, ...)`` through this object, else ``default`` (the library's own default)."""

@@ -538,6 +538,63 @@ def slab_prior(handler, sigmas, means=None):
     return np.concatenate(mean_parts).astype(np.float64), np.concatenate(sigma_parts).astype(np.float64)
 
 
+def slab_bounds(handler, lo_per_group, hi_per_group):
+    """(lo, hi) on the handler's FREE vector — what ``lm_solve(bounds=)`` / ``problem_opts["bounds"]`` take — from per-group values;
+    the mirror of ``slab_prior``.
+
+    Bundle handlers: each argument is a dict over the groups ``"intr"`` (C, 9), ``"extr"`` (C, 6), ``"pose"`` (I, 6) and ``"bdpt"``, or
+    ``None``; a ``ChainProblem``: a list with one entry per slab, or ``None``.  Each entry is anything that broadcasts to its slab — a
+    scalar, a row, the full array — with ``-np.inf`` / ``np.inf`` for no bound; ``None`` or a missing group means no bound there; or
+    ``("rel", width)``: the handler's current slab minus (``lo``) or plus (``hi``) ``width * |slab|``, ``width`` broadcasting likewise.
+    Only the free entries reach the result, in free-vector order."""
+    if isinstance(handler, ChainProblem):
+        slabs = [(i, s, m) for i, (s, m) in enumerate(zip(handler.slabs, handler.unfixed))]
+        for name, d in (("lo_per_group", lo_per_group), ("hi_per_group", hi_per_group)):
+            if d is not None and (isinstance(d, dict) or len(d) != len(slabs)):
+                raise ValueError(f"{name}: one entry (or None) per slab of the ChainProblem, {len(slabs)} in all")
+        pick = lambda d, k: None if d is None else d[k]   # noqa: E731
+    else:
+        bp = handler.bundlePrimitive
+        unknown = (set(lo_per_group or {}) | set(hi_per_group or {})) - set(bp.groups)
+        if unknown:
+            raise ValueError(f"unknown parameter groups {sorted(unknown)}: this handler has {list(bp.groups)}")
+        slabs = []
+        for g in bp.groups:
+            slab_name, mask_name, width = _GROUP[g]
+            slab, mask = getattr(bp, slab_name), np.asarray(getattr(bp, mask_name), dtype=bool)
+            if g == "bdpt":
+                slab = np.asarray(handler.point_data, dtype=np.float64).reshape(-1)
+            slabs.append((g, slab, mask if width == 1 else np.repeat(mask[:, None], width, axis=1)))
+        pick = lambda d, k: None if d is None else d.get(k)   # noqa: E731
+    lo_parts, hi_parts = [], []
+    for key, slab, mask in slabs:
+        slab = np.asarray(slab, dtype=np.float64)
+        mask = np.ones(slab.shape, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
+
+        def side(v, sign, what):
+            if v is None:
+                return np.full(slab.shape, sign * np.inf)
+            rel = isinstance(v, tuple) and len(v) == 2 and isinstance(v[0], str)
+            if rel and v[0] != "rel":
+                raise ValueError(f"{what}[{key!r}]: expected ('rel', width), got {v[0]!r}")
+            a = np.asarray(v[1] if rel else v, dtype=np.float64)
+            try:
+                a = a.reshape(slab.shape) if a.size == slab.size else np.broadcast_to(a, slab.shape)
+            except ValueError:
+                raise ValueError(f"{what}[{key!r}] of shape {a.shape} does not broadcast to the slab {slab.shape}") from None
+            if np.any(np.isnan(a)) or (rel and np.any(a < 0.0)):
+                raise ValueError(f"{what}[{key!r}]: NaN or a negative relative width")
+            return slab + sign * a * np.abs(slab) if rel else np.array(a)
+
+        lo_parts.append(side(pick(lo_per_group, key), -1.0, "lo_per_group")[mask])
+        hi_parts.append(side(pick(hi_per_group, key), 1.0, "hi_per_group")[mask])
+    lo, hi = np.concatenate(lo_parts).astype(np.float64), np.concatenate(hi_parts).astype(np.float64)
+    if np.any(lo > hi):
+        k = int(np.flatnonzero(lo > hi)[0])
+        raise ValueError(f"slab_bounds: lower bound {lo[k]} > upper bound {hi[k]} at free index {k}")
+    return lo, hi
+
+
 class ChainProblem:
     """The handler protocol for ANY chain of function blocks — what ``device_solver.lm_solve`` and a scipy caller need from a
     handler (template_handler.py:154-240: ``op_fun``, ``make_loss_fun``, ``make_loss_jac``, ``get_bundle_adjustment_inputs``) without

@@ -61,7 +61,9 @@ def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy"
     Gaussian prior on the free vector (``device_solver.lm_solve``'s ``prior_mean`` / ``prior_sigma``; ``handlers.slab_prior`` builds
     one).  The device solver takes it as it is; for scipy the rows ``(x - mean) / sigma`` are appended to the residual closure and the
     matching diagonal rows to the Jacobian closure, so both solvers minimise the same function — with the linear loss: scipy's robust
-    losses would apply to the appended rows too."""
+    losses would apply to the appended rows too.  Optional ``problem_opts['bounds']``: box bounds on the free vector in scipy's forms
+    (``(lo, hi)`` or a ``scipy.optimize.Bounds``; ``handlers.slab_bounds`` builds the arrays), handed to whichever solver runs:
+    ``lm_solve(bounds=)`` or ``least_squares(bounds=)``."""
     loss_fn, jac_fn, x0 = make_optimisation_function(param_handler, threads)
     opts = param_handler.problem_opts
     loss, f_scale = opts.get("loss", "linear"), opts.get("f_scale", 1.0)
@@ -71,6 +73,11 @@ def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy"
 
         prior_mean, prior_sigma = opts["prior"]
         prior = _free_prior(x0, prior_mean, prior_sigma)
+    bounds = opts.get("bounds")
+    if bounds is not None:
+        from .device_solver import _free_bounds
+
+        _free_bounds(x0, bounds)   # shapes, values and the start, checked the same way for both solvers
     n_rows = 2 * param_handler._flat_detections().shape[0]
     start_error = mean_reprojection_error(loss_fn(x0))
     log.info("%d parameters, %d residuals, start error %.2f px", len(x0), 2 * param_handler._flat_detections().shape[0], start_error)
@@ -81,7 +88,8 @@ def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy"
         from .device_solver import lm_solve
 
         result = lm_solve(param_handler, x0, max_iter=opts["max_nfev"], linear_solver=linear_solver, loss=loss, f_scale=f_scale,
-                          **({} if prior is None else {"prior_mean": prior_mean, "prior_sigma": prior_sigma}))
+                          **({} if prior is None else {"prior_mean": prior_mean, "prior_sigma": prior_sigma}),
+                          **({} if bounds is None else {"bounds": bounds}))
         end_error = mean_reprojection_error(loss_fn(result.x))
     else:
         fun, jac = loss_fn, jac_fn
@@ -91,7 +99,8 @@ def run_bundle_adjustment(param_handler, threads: int = 1, solver: str = "scipy"
                                           "through the loss (solver='device' keeps them outside it)")
             fun, jac = _with_prior_rows(loss_fn, jac_fn, prior)
         result = least_squares(fun, x0, jac=jac if jac is not None else "2-point", x_scale="jac",
-                               max_nfev=opts["max_nfev"], verbose=opts["verbosity"], loss=loss, f_scale=f_scale)
+                               max_nfev=opts["max_nfev"], verbose=opts["verbosity"], loss=loss, f_scale=f_scale,
+                               **({} if bounds is None else {"bounds": bounds}))
         end_error = mean_reprojection_error(result.fun[:n_rows])
     log.info("solved in %.2f s, final error %.2f px", time.perf_counter() - tic, end_error)
     if end_error > 5:  # oh:105-107

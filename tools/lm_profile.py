@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--config", type=int, default=3)
     ap.add_argument("--chain", default="template")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--bounds", action="store_true",
+                    help="also time whole solves with box bounds set on the focal lengths and principal points (+- 50 % of the start: none binds) — the "
+                         "non-fused trial plus the two launches of csrc/ba_bounds.hpp; run under rocprofv3 --kernel-trace for the per-trial kernels")
     ap.add_argument("--loss", default="",
                     help="comma-separated robust losses: after the phases, the whole solve alternates between 'linear' and each of them "
                          "(three rounds; lm_solve(loss=...), f_scale 1) — run under rocprofv3 --kernel-trace for the per-trial kernels")
@@ -152,6 +155,20 @@ def main():
             dt = time.perf_counter() - t0
             print(f"  lm_solve loss {loss}: {dt * 1e3:.2f} ms for {res.nfev} evaluations ({dt / res.nfev * 1e3:.3f} ms each), cost {res.cost:.6e}, "
                   f"{res.message}")
+    if a.bounds:
+        lo, hi = np.full(x0.shape, -np.inf), np.full(x0.shape, np.inf)
+        n_intr = 9 * int(np.count_nonzero(h.bundlePrimitive.intr_unfixed))
+        for j in range(4):
+            lo[j:n_intr:9], hi[j:n_intr:9] = 0.5 * x0[j:n_intr:9], 1.5 * x0[j:n_intr:9]
+        for rnd in range(3):
+            for name, kw in (("none", {}), ("wide", {"bounds": (lo, hi)})):
+                lm_solve(h, x0.copy(), max_iter=2, **kw)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = lm_solve(h, x0.copy(), max_iter=30, **kw)
+                dt = time.perf_counter() - t0
+                print(f"  lm_solve bounds {name}: {dt * 1e3:.2f} ms for {res.nfev} evaluations ({dt / res.nfev * 1e3:.3f} ms each), cost {res.cost:.6e}, "
+                      f"{res.n_truncated} cut trials, {res.message}")
 
 
 if __name__ == "__main__":
