@@ -825,6 +825,61 @@ int pcs_pnp_get_consensus(pcs_pose_estimator *p, int *n_hypotheses, int *sample_
 int pcs_pnp_consensus_results(pcs_pose_estimator *p, uint8_t *inlier, int32_t *cinfo, double *score);
 
 /* ------------------------------------------------------------------------------------------------
+ * Two-view relative pose by consensus (csrc/ba_twoview.hpp).  Since pcs_version() 119.
+ * The host counterpart is cv2.findEssentialMat(..., RANSAC) followed by cv2.recoverPose: the one estimate of target-free bundle
+ * adjustment (FreePointBundleHandler) that needs no 3-D knowledge.  The reference has none (free_point_handler.py:235 asks the
+ * primitive for a pose_end it lacks).
+ * A pair p of cameras (a, b), a < b, owns rows [start_inds[p], start_inds[p+1]) of a correspondence table (uv_a, uv_b) in measured
+ * pixels.  Per pair: both pixels are undistorted (five fixed-point steps); n_hypotheses samples of eight rows are fitted by the
+ * normalised eight-point method and projected onto the essential manifold; every hypothesis is scored on all rows of the pair by
+ * sum min(e^2, inlier_px^2), e^2 the Sampson distance in undistorted pixels; the lowest score wins (ties: the lower hypothesis); the
+ * same fit over the winner's inliers gives E, and of its four (R, +-t) the one with the most inliers in front of both cameras is
+ * returned (ties: the lower candidate).  The sampler is counter-based, keyed by (seed, pair index, rows of the pair, hypothesis);
+ * the hypothesis count is fixed and every sum has a fixed order: two runs agree bit for bit, and a pair's result does not depend
+ * on the other pairs of the table.  The eight-point method degenerates for coplanar points and for a pure rotation: status,
+ * n_front and parallax report that.
+ *   pcs_twoview_create             n_cams >= 2 cameras
+ *   pcs_twoview_set_cameras        intr (n_cams, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2]
+ *   pcs_twoview_set_correspondences  host arrays, copied: uv_a, uv_b (n_corr, 2), start_inds (n_pairs + 1), pair_cams (n_pairs, 2)
+ *                                  int32.  Checked without touching the device, and a refused call keeps the previous table:
+ *                                  PCS_ERR_RANGE a camera outside [0, n_cams); PCS_ERR_ARG a >= b, start_inds not running from 0 to
+ *                                  n_corr or decreasing, a non-finite pixel.
+ *   pcs_twoview_set_consensus      1 <= n_hypotheses <= 256 (else PCS_ERR_RANGE; default 64), inlier_px finite and > 0 (else
+ *                                  PCS_ERR_ARG; default 2), seed.  A refused call keeps the previous setting.
+ *   pcs_twoview_get_consensus      the setting in force (any pointer may be NULL)
+ *   pcs_twoview_run                queue the kernels on `stream` (NULL = the handle's stream).  group_lanes: 16 or 64 lanes per
+ *                                  pair in the scoring, selection and final kernels, 0 = 64 from a mean of 256 rows per pair on.
+ *                                  flags: none defined, pass 0.  d_T (n_pairs, 12), a device buffer of the caller or NULL =
+ *                                  handle-owned: [R | t] row-major, X_b = R X_a + t, |t| = 1; NaN unless the status is OK.
+ *   pcs_twoview_results            copy the outputs of the last run to the host (any pointer may be NULL; blocking): T (n_pairs, 12);
+ *                                  info (n_pairs, 5) int32 {rows, inliers, inliers in front of both cameras, status
+ *                                  PCS_TWOVIEW_*, winning hypothesis or -1}; stats (n_pairs, 3) {the winner's score (+inf: no
+ *                                  usable hypothesis, NaN: too few rows), RMS Sampson distance over the inliers at the final E,
+ *                                  parallax: RMS angle between the two rays of the front inliers, radians} (the last two NaN unless
+ *                                  OK); inlier (n_corr) one flag per row, e^2 <= inlier_px^2 at the winning hypothesis.
+ *   pcs_twoview_last_kernel_ms     device time of the stages of the last run, kernel_ms[5] = {undistort, hypotheses, scores,
+ *                                  selection, final}.  PCS_ERR_STATE when the last run had no pairs and so queued nothing.
+ */
+typedef struct pcs_two_view pcs_two_view;
+enum {
+    PCS_TWOVIEW_OK = 0,
+    PCS_TWOVIEW_TOO_FEW = 1,        /* fewer than max(8, min_points) rows */
+    PCS_TWOVIEW_DEGENERATE = 2,     /* no usable hypothesis, fewer than 8 inliers, or the fit over the inliers lost rank */
+    PCS_TWOVIEW_NO_CHEIRALITY = 3   /* no inlier in front of both cameras */
+};
+enum { PCS_TWOVIEW_OUT_T = 1, PCS_TWOVIEW_OUT_INFO = 2, PCS_TWOVIEW_OUT_STATS = 4, PCS_TWOVIEW_OUT_INLIER = 8 };
+int pcs_twoview_create(pcs_two_view **out, int device, int64_t n_cams);
+int pcs_twoview_destroy(pcs_two_view *p);
+int pcs_twoview_set_cameras(pcs_two_view *p, const double *intr);
+int pcs_twoview_set_correspondences(pcs_two_view *p, int64_t n_corr, const double *uv_a, const double *uv_b, int64_t n_pairs, const int64_t *start_inds,
+                                    const int32_t *pair_cams);
+int pcs_twoview_set_consensus(pcs_two_view *p, int n_hypotheses, double inlier_px, uint64_t seed);
+int pcs_twoview_get_consensus(pcs_two_view *p, int *n_hypotheses, double *inlier_px, uint64_t *seed);
+int pcs_twoview_run(pcs_two_view *p, int min_points, int group_lanes, int flags, double *d_T, void *stream);
+int pcs_twoview_results(pcs_two_view *p, double *T, int32_t *info, double *stats, uint8_t *inlier);
+int pcs_twoview_last_kernel_ms(pcs_two_view *p, float *kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

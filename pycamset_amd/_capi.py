@@ -41,6 +41,8 @@ TRI_NOT_REFINED, TRI_CONVERGED, TRI_MAX_ITER, TRI_NO_DECREASE = 0, 1, 2, 3
 PNP_RESIDUALS = 1                        # include/pcs_hip.h PCS_PNP_RESIDUALS
 # include/pcs_hip.h PCS_PNP_*: per-view status of the pose estimation
 PNP_NOT_ESTIMATED, PNP_CONVERGED, PNP_MAX_ITER, PNP_NO_DECREASE = 0, 1, 2, 3
+# include/pcs_hip.h PCS_TWOVIEW_*: per-pair status of the two-view consensus
+TWOVIEW_OK, TWOVIEW_TOO_FEW, TWOVIEW_DEGENERATE, TWOVIEW_NO_CHEIRALITY = 0, 1, 2, 3
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -164,6 +166,15 @@ SYMBOLS = {
     "pcs_pnp_set_consensus": (c_int, [_P, c_int, c_int, c_double, c_uint64]),
     "pcs_pnp_get_consensus": (c_int, [_P, POINTER(c_int), POINTER(c_int), POINTER(c_double), POINTER(c_uint64)]),
     "pcs_pnp_consensus_results": (c_int, [_P, POINTER(c_uint8), POINTER(c_int32), POINTER(c_double)]),
+    "pcs_twoview_create": (c_int, [POINTER(_P), c_int, c_int64]),
+    "pcs_twoview_destroy": (c_int, [_P]),
+    "pcs_twoview_set_cameras": (c_int, [_P, POINTER(c_double)]),
+    "pcs_twoview_set_correspondences": (c_int, [_P, c_int64, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64), POINTER(c_int32)]),
+    "pcs_twoview_set_consensus": (c_int, [_P, c_int, c_double, c_uint64]),
+    "pcs_twoview_get_consensus": (c_int, [_P, POINTER(c_int), POINTER(c_double), POINTER(c_uint64)]),
+    "pcs_twoview_run": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "pcs_twoview_results": (c_int, [_P, POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_uint8)]),
+    "pcs_twoview_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),

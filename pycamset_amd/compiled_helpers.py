@@ -722,6 +722,192 @@ def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_poi
     return out
 
 
+# ---- two-view relative pose by consensus (row f10: the first estimate of a target-free seed) -------------------------------------------
+from ._capi import TWOVIEW_DEGENERATE, TWOVIEW_NO_CHEIRALITY, TWOVIEW_OK, TWOVIEW_TOO_FEW  # noqa: E402,F401
+last_twoview_kernel_ms = None
+TWOVIEW_STAGES = ("undistort", "hypotheses", "scores", "selection", "final")
+
+
+@dataclass
+class TwoViewResult:
+    """Relative poses of camera pairs (``estimate_two_view``).  ``pairs`` (P, 2) cameras (a, b), a < b; ``T`` (P, 3, 4) = [R | t] with
+    X_b = R X_a + t and |t| = 1, NaN unless ``status`` is TWOVIEW_OK; ``n``, ``n_inliers``, ``n_front`` (inliers in front of both
+    cameras), ``status`` (TWOVIEW_*), ``hypothesis`` (the winner, -1: none) (P,) int32; ``score`` the winner's sum min(e^2, inlier_px^2),
+    ``rms`` the RMS Sampson distance over the inliers in undistorted pixels, ``parallax`` the RMS angle between the two rays of the front
+    inliers in radians (P,).  The correspondence table: pair p owns rows ``start[p]:start[p + 1]`` of ``keys``, ``uv_a``, ``uv_b`` and
+    ``inliers`` (n_corr,), ascending in the key."""
+    pairs: np.ndarray
+    T: np.ndarray
+    n: np.ndarray
+    n_inliers: np.ndarray
+    n_front: np.ndarray
+    status: np.ndarray
+    hypothesis: np.ndarray
+    score: np.ndarray
+    rms: np.ndarray
+    parallax: np.ndarray
+    start: np.ndarray
+    keys: np.ndarray
+    uv_a: np.ndarray
+    uv_b: np.ndarray
+    inliers: np.ndarray
+
+
+def check_twoview_options(consensus, inlier_px, seed, min_points, group_lanes=0):
+    """Validate the options of the two-view consensus on the host (ValueError) before anything is queued: the checks of
+    pcs_twoview_set_consensus and pcs_twoview_run."""
+    for name, v, lo, hi in (("consensus", consensus, 1, 256), ("seed", seed, 0, 2 ** 64 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+    try:
+        px = float(inlier_px)
+    except (TypeError, ValueError):
+        raise ValueError(f"inlier_px must be a finite number > 0, got {inlier_px!r}") from None
+    if not (np.isfinite(px) and px > 0.0):
+        raise ValueError(f"inlier_px must be a finite number > 0, got {inlier_px!r}")
+    if isinstance(group_lanes, bool) or group_lanes not in (0, 16, 64):
+        raise ValueError(f"group_lanes must be 0 (by size), 16 or 64, got {group_lanes!r}")
+    return int(consensus), px, int(seed), check_min_points(min_points), int(group_lanes)
+
+
+class TwoViewEstimator(_Handle):
+    """Owner of one ``pcs_two_view`` handle (include/pcs_hip.h): camera table, correspondence copies, stage buffers and outputs stay on
+    the device across calls."""
+
+    _create, _destroy = "pcs_twoview_create", "pcs_twoview_destroy"
+
+    def __init__(self, n_cams: int, device: int = 0):
+        super().__init__(device, n_cams)
+        self.n_cams, self.device = int(n_cams), int(device)
+        self.n_pairs, self.n_corr = 0, 0
+
+    def set_cameras(self, intr):
+        K = np.ascontiguousarray(intr, dtype=np.float64)
+        if K.shape != (self.n_cams, 9):
+            raise ValueError(f"expected intr ({self.n_cams}, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2]")
+        self._call("pcs_twoview_set_cameras", self._h, self._ptr(K))
+
+    def set_correspondences(self, uv_a, uv_b, start_inds, pair_cams):
+        """Host arrays sorted by pair: uv_a, uv_b (n_corr, 2) measured pixels, start_inds (n_pairs + 1,), pair_cams (n_pairs, 2) int with
+        a < b.  Shapes raise ValueError; values are checked by the handle (PcsError) without touching the device."""
+        ua = np.ascontiguousarray(uv_a, dtype=np.float64)
+        ub = np.ascontiguousarray(uv_b, dtype=np.float64)
+        start = np.ascontiguousarray(start_inds, dtype=np.int64)
+        pc = np.ascontiguousarray(pair_cams, dtype=np.int32)
+        if start.ndim != 1 or start.shape[0] < 1 or pc.shape != (start.shape[0] - 1, 2) or ua.ndim != 2 or ua.shape[1] != 2 or ub.shape != ua.shape:
+            raise ValueError("expected uv_a, uv_b (n_corr, 2), start_inds (n_pairs + 1,), pair_cams (n_pairs, 2)")
+        self._call("pcs_twoview_set_correspondences", self._h, ua.shape[0], self._ptr(ua), self._ptr(ub), start.shape[0] - 1, self._ptr(start), self._ptr(pc))
+        self.n_pairs, self.n_corr = start.shape[0] - 1, ua.shape[0]
+
+    def set_consensus(self, n_hypotheses: int = 64, inlier_px: float = 2.0, seed: int = 0):
+        """Hypotheses per pair, inlier threshold in undistorted pixels and the seed of the sampler, for the runs that follow."""
+        self._call("pcs_twoview_set_consensus", self._h, int(n_hypotheses), float(inlier_px), int(seed))
+
+    def get_consensus(self):
+        """(n_hypotheses, inlier_px, seed) in force."""
+        h, px, seed = self._ct.c_int(0), self._ct.c_double(0.0), self._ct.c_uint64(0)
+        self._call("pcs_twoview_get_consensus", self._h, self._ct.byref(h), self._ct.byref(px), self._ct.byref(seed))
+        return int(h.value), float(px.value), int(seed.value)
+
+    def run(self, min_points: int = 16, group_lanes: int = 0, d_T: int | None = None, stream: int | None = None):
+        """Queue the five stages (asynchronous; handle-owned outputs, fetched with ``results()``)."""
+        self._call("pcs_twoview_run", self._h, int(min_points), int(group_lanes), 0, self._addr(d_T), _stream_arg(stream))
+        self._own_T = d_T is None
+
+    def results(self):
+        """Wait for the last ``run``: (T (n_pairs, 3, 4) or None when the run wrote it to a caller buffer, info (n_pairs, 5) int32 =
+        [n, inliers, front, status, winning hypothesis], stats (n_pairs, 3) = [score, rms, parallax], inlier (n_corr,) bool)."""
+        n = self.n_pairs
+        T = np.empty((n, 3, 4)) if getattr(self, "_own_T", True) else None
+        info, stats, inl = np.empty((n, 5), dtype=np.int32), np.empty((n, 3)), np.zeros(self.n_corr, dtype=np.uint8)
+        self._call("pcs_twoview_results", self._h, self._ptr(T), self._ptr(info), self._ptr(stats), self._ptr(inl))
+        return T, info, stats, inl.astype(bool)
+
+    def last_kernel_ms(self) -> dict:
+        """Device time of every stage of the last run, milliseconds by stage name (TWOVIEW_STAGES)."""
+        ms = (self._ct.c_float * len(TWOVIEW_STAGES))()
+        self._call("pcs_twoview_last_kernel_ms", self._h, ms)
+        return dict(zip(TWOVIEW_STAGES, (float(v) for v in ms)))
+
+
+def shared_keys(dct, n_cams: int):
+    """Per camera the pixel of every key it sees, that of the lowest image where a camera sees a key in several:
+    (keys (n,) ascending, uv (n, 2)) per camera."""
+    d = np.asarray(dct, dtype=np.float64)
+    out = []
+    for c in range(int(n_cams)):
+        rows = d[d[:, 0] == c]
+        rows = rows[np.lexsort((rows[:, 1], rows[:, 2]))]   # by key, then image
+        first = np.ones(rows.shape[0], dtype=bool)
+        first[1:] = rows[1:, 2] != rows[:-1, 2]
+        out.append((rows[first, 2].astype(np.int64), rows[first, 3:5]))
+    return out
+
+
+_twoview_cache: dict = {}
+
+
+def _twoview_estimator(device: int, n_cams: int) -> TwoViewEstimator:
+    return _cached_handle(_twoview_cache, (int(device), int(n_cams)), lambda: TwoViewEstimator(n_cams, device))
+
+
+def estimate_two_view(dct, intr, *, pairs=None, consensus: int = 64, inlier_px: float = 2.0, seed: int = 0, min_points: int = 16,
+                      group_lanes: int = 0, device: int = 0) -> TwoViewResult:
+    """The relative pose of camera pairs from their shared image points alone, on the device (include/pcs_hip.h pcs_twoview_run): what
+    cv2.findEssentialMat(..., RANSAC) + cv2.recoverPose give on the host, and the first step of a target-free seed (``seed_scene``).
+
+    ``dct``: the flat (N, 5) table [cam, im, key, u, v] in any order — a point is a key, two cameras correspond where both see it, and
+    a camera that sees a key in several images contributes the lowest; ``intr``: (C, 9) rows [fx, cx, fy, cy, k0, k1, p0, p1, k2];
+    ``pairs``: (P, 2) cameras with a < b (default: every pair with at least ``min_points`` shared keys).  ``consensus`` hypotheses of
+    eight correspondences each (64: log(1 - 0.999) / log(1 - 0.75^8) = 66 draws give three nines at 25 % wrong matches) are scored by
+    sum min(e^2, inlier_px^2) of the Sampson distance in undistorted pixels; the winner's inliers are refitted.  The hypothesis
+    count is fixed and the sampler counter-based (``seed``): two calls agree bit for bit.  A pair with fewer than max(8, min_points)
+    correspondences, a degenerate one (coplanar points, no baseline) or one without a point in front of both cameras keeps NaN in
+    ``T``; ``status``, ``n_front`` and ``parallax`` say why."""
+    global last_twoview_kernel_ms
+    H, px, seed, min_points, lanes = check_twoview_options(consensus, inlier_px, seed, min_points, group_lanes)
+    d = np.asarray(dct, dtype=np.float64)
+    K = np.asarray(intr, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 5 or K.ndim != 2 or K.shape[1] != 9 or K.shape[0] < 2:
+        raise ValueError("expected dct (N, 5) = [cam, im, key, u, v] and intr (C, 9) of at least two cameras")
+    C = K.shape[0]
+    if not np.all(np.isfinite(d)) or not np.all(np.isfinite(K)):
+        raise ValueError("dct and intr must be finite")
+    if d.shape[0] and (d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 2].min() < 0):
+        raise ValueError("camera index of the table outside the intrinsics, or a negative key")
+    seen = shared_keys(d, C)
+    if pairs is None:
+        pc = np.array([(a, b) for a in range(C) for b in range(a + 1, C)
+                       if np.intersect1d(seen[a][0], seen[b][0], assume_unique=True).shape[0] >= min_points], dtype=np.int32).reshape(-1, 2)
+    else:
+        pc = np.asarray(pairs)
+        if pc.ndim != 2 or pc.shape[1] != 2 or not np.issubdtype(pc.dtype, np.integer):
+            raise ValueError("pairs must be an integer array (P, 2)")
+        if pc.shape[0] and (pc.min() < 0 or pc.max() >= C or np.any(pc[:, 0] >= pc[:, 1])):
+            raise ValueError(f"pairs must hold cameras in [0, {C}) with a < b")
+        pc = pc.astype(np.int32)
+    keys, ua, ub, start = [], [], [], [0]
+    for a, b in pc:
+        common, ia, ib = np.intersect1d(seen[a][0], seen[b][0], assume_unique=True, return_indices=True)
+        keys.append(common)
+        ua.append(seen[a][1][ia])
+        ub.append(seen[b][1][ib])
+        start.append(start[-1] + common.shape[0])
+    keys = np.concatenate(keys) if keys else np.zeros(0, dtype=np.int64)
+    ua = np.concatenate(ua).reshape(-1, 2) if ua else np.zeros((0, 2))
+    ub = np.concatenate(ub).reshape(-1, 2) if ub else np.zeros((0, 2))
+    start = np.array(start, dtype=np.int64)
+    est = _twoview_estimator(device, C)
+    est.set_cameras(K)
+    est.set_correspondences(ua, ub, start, pc)
+    est.set_consensus(H, px, seed)   # the handle is shared: every call states its setting
+    est.run(min_points=min_points, group_lanes=lanes)
+    T, info, stats, inl = est.results()
+    last_twoview_kernel_ms = est.last_kernel_ms() if pc.shape[0] else None
+    return TwoViewResult(pairs=pc, T=T, n=info[:, 0], n_inliers=info[:, 1], n_front=info[:, 2], status=info[:, 3], hypothesis=info[:, 4],
+                         score=stats[:, 0], rms=stats[:, 1], parallax=stats[:, 2], start=start, keys=keys, uv_a=ua, uv_b=ub, inliers=inl)
+
+
 # ---- intrinsics from planar views (row f6: the rough intrinsics calc_initial_params starts from) -------------------------------------
 # per-camera and per-group status of the estimate (include/pcs_hip.h PCS_INTR_*, PCS_INTR_GROUP_*)
 from ._capi import (INTR_FOCAL, INTR_FOCAL_FALLBACK, INTR_FULL, INTR_GROUP_FIT_FAILED, INTR_GROUP_NOT_FINITE,  # noqa: E402,F401

@@ -48,6 +48,7 @@
 #include "ba_intr_consensus.hpp"
 #include "ba_riggraph.hpp"
 #include "ba_groupstats.hpp"
+#include "ba_twoview.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -59,6 +60,7 @@ using namespace pcs;
 #include "pcs_dettable.inc"
 #include "pcs_triangulator.inc"
 #include "pcs_pnp.inc"
+#include "pcs_twoview.inc"
 #include "pcs_rigpose.inc"
 #include "pcs_intrinsics.inc"
 #include "pcs_rig.inc"

@@ -323,18 +323,7 @@ class TemplateBundleHandler:  # th:80-240
 
         bp = self.bundlePrimitive
         n_cams = bp.intr.shape[0]
-        if intr is None:
-            try:
-                intr = np.stack([np.concatenate((np.asarray(self.camset[idc].intrinsic)[[0, 0, 1, 1], [0, 2, 1, 2]].squeeze(),
-                                                 np.asarray(self.camset[idc].distortion_coefs).squeeze()), axis=0) for idc in range(n_cams)])
-            except (TypeError, AttributeError, KeyError, IndexError):
-                intr = self._estimate_initial_intrinsics(n_cams, intrinsics_consensus)
-        intr = np.array(intr, dtype=np.float64)
-        if intr.shape != (n_cams, 9):
-            raise ValueError(f"intr must be ({n_cams}, 9), got {intr.shape}")
-        for idc, name in enumerate(self.cam_names):   # a fixed camera's intrinsics are the fixed ones
-            if "int" in self.fixed_params.get(name, {}):
-                intr[idc] = self.fixed_params[name]["int"]
+        intr = self._initial_intrinsics(intr, intrinsics_consensus)
         n_imgs = bp.poses.shape[0] if "pose" in bp.groups else self.detection.max_ims
         args = (self._flat_detections(), self.point_data.reshape((-1, 3)), intr, n_cams, n_imgs)
         refs = {"ref_cam": self.problem_opts.get("ref_cam", 0), "ref_pose": self.problem_opts.get("ref_pose", 0), "view_consensus": view_consensus}
@@ -358,6 +347,24 @@ class TemplateBundleHandler:  # th:80-240
         if "bdpt" in bp.groups:
             parts.append(self.flat_point_data[bp.bdpt_unfixed])
         return np.concatenate(parts)
+
+    def _initial_intrinsics(self, intr, intrinsics_consensus: int) -> np.ndarray:
+        """The (C, 9) intrinsics a seeding starts from: the caller's, else the camset's (th:321-329), else the device's estimate from
+        the planar views; a fixed camera's are the fixed ones."""
+        n_cams = self.bundlePrimitive.intr.shape[0]
+        if intr is None:
+            try:
+                intr = np.stack([np.concatenate((np.asarray(self.camset[idc].intrinsic)[[0, 0, 1, 1], [0, 2, 1, 2]].squeeze(),
+                                                 np.asarray(self.camset[idc].distortion_coefs).squeeze()), axis=0) for idc in range(n_cams)])
+            except (TypeError, AttributeError, KeyError, IndexError):
+                intr = self._estimate_initial_intrinsics(n_cams, intrinsics_consensus)
+        intr = np.array(intr, dtype=np.float64)
+        if intr.shape != (n_cams, 9):
+            raise ValueError(f"intr must be ({n_cams}, 9), got {intr.shape}")
+        for idc, name in enumerate(self.cam_names):   # a fixed camera's intrinsics are the fixed ones
+            if "int" in self.fixed_params.get(name, {}):
+                intr[idc] = self.fixed_params[name]["int"]
+        return intr
 
     def _refine_seeded_poses(self, dct, points, intr, extr, poses) -> np.ndarray:
         """``calc_initial_params(refine_poses=True)``: the seeded image poses refined per image with every camera fixed at its seeded
@@ -484,6 +491,42 @@ class FreePointBundleHandler(TemplateBundleHandler):  # fph:102-201
 
     def _point_mask(self, visible_feature_mask):
         return np.ones(self.flat_point_data.shape[0], dtype=bool)  # fph:130
+
+    def calc_initial_params(self, intr=None, *, seeding: str = "reference", scene_opts: dict | None = None, **kw) -> np.ndarray:
+        """``seeding="scene"``: the start vector of a scene nobody measured, from the detections alone
+        (``pose_seeding.seed_scene``: two-view consensus, triangulation, resection in rounds; the reference has no such start,
+        fph:235).  Intrinsics are found as for the other seedings (``intr``, the camset's, or the planar estimate); ``scene_opts``
+        reach ``seed_scene`` (``baseline``, ``consensus``, ``inlier_px``, ``seed``, ``min_points``, ``resect_opts``, ``tri_opts``),
+        ``ref_cam`` comes from ``options["ref_cam"]``.  The world is ``ref_cam``'s camera frame and the first pair's baseline has
+        length ``baseline``: fixed extrinsics must be given in that gauge.  The seed is kept on ``scene_seed``.  ValueError names the
+        cameras and keys with a free entry that got no seed.  Every other ``seeding`` is ``TemplateBundleHandler.calc_initial_params``,
+        which starts the points at ``flat_point_data``."""
+        if seeding != "scene":
+            if scene_opts is not None:
+                raise ValueError("scene_opts belongs to seeding='scene'")
+            return super().calc_initial_params(intr, seeding=seeding, **kw)
+        from .pose_seeding import seed_scene
+
+        unknown = set(kw) - {"intrinsics_consensus"}
+        if unknown:
+            raise ValueError(f"seeding='scene' takes intr, scene_opts and intrinsics_consensus, not {sorted(unknown)}")
+        cons = kw.get("intrinsics_consensus")
+        bp = self.bundlePrimitive
+        n_cams = bp.intr.shape[0]
+        intr = self._initial_intrinsics(intr, self.problem_opts.get("intrinsics_consensus", 0) if cons is None else cons)
+        seed = seed_scene(self._flat_detections(), intr, n_cams, ref_cam=self.problem_opts.get("ref_cam", 0), **dict(scene_opts or {}))
+        self.scene_seed = seed
+        points = np.full((self.flat_point_data.shape[0] // 3, 3), np.nan)
+        points[: seed.points.shape[0]] = seed.points
+        flat = points.ravel()
+        no_cam = [self.cam_names[c] for c in np.nonzero(np.asarray(bp.extr_unfixed, dtype=bool) & ~seed.placed)[0]]
+        no_key = np.unique(np.nonzero(np.asarray(bp.bdpt_unfixed, dtype=bool) & ~np.isfinite(flat))[0] // 3)
+        if no_cam or no_key.shape[0]:
+            shown = ", ".join(str(k) for k in no_key[:20]) + (", ..." if no_key.shape[0] > 20 else "")
+            raise ValueError(f"seeding='scene' left free entries without a seed: cameras {no_cam} were not placed, "
+                             f"{no_key.shape[0]} keys were not triangulated ({shown})")
+        self.missing_poses = np.zeros(self.detection.max_ims, dtype=bool)
+        return np.concatenate([intr[bp.intr_unfixed].ravel(), seed.extr[bp.extr_unfixed].ravel(), flat[bp.bdpt_unfixed]])
 
 
 def slab_prior(handler, sigmas, means=None):

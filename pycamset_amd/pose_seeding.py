@@ -345,3 +345,132 @@ def resect_cameras(dct, points, intr, image_poses, *, view_pose_fn=None, **opts)
     return CameraResection(poses=np.asarray(vp.poses, dtype=np.float64).reshape(C, 6), rms=col("rms", np.nan, np.float64),
                            rms_init=col("rms_init", np.nan, np.float64), status=col("status", 0, np.int32),
                            iterations=col("iterations", 0, np.int32), n_points=col("n_points", 0, np.int32), images=known)
+
+
+# ---- target-free seeding: incremental reconstruction from the detections alone ------------------------------------
+@dataclass
+class SceneSeed:
+    """What ``seed_scene`` returns.  ``extr`` (C, 6) = [rotvec, t] world -> camera, NaN for a camera that was not placed; ``points``
+    (K, 3), NaN where not triangulated; ``placed`` (C,) bool; ``round_of_camera`` (C,) int: 0 for the first pair, r for a camera
+    resected in round r, -1 for one never placed; ``n_views`` (K,) placed cameras a point was triangulated from and ``rms`` (K,) its RMS
+    reprojection error in pixels; ``first_pair`` (a, b); ``frame_cam``: the camera whose frame is the world — ``ref_cam`` when it was
+    placed, else the first pair's camera a; ``two_view``: the ``TwoViewResult`` of all pairs."""
+    extr: np.ndarray
+    points: np.ndarray
+    placed: np.ndarray
+    round_of_camera: np.ndarray
+    n_views: np.ndarray
+    rms: np.ndarray
+    first_pair: tuple
+    frame_cam: int
+    two_view: object
+
+
+def _triangulate_placed(seen, M, K, placed, n_keys, triangulate_fn, tri_opts):
+    """Every key that at least two placed cameras see, through ``refine_triangulation``: (points (n_keys, 3), n_views, rms), NaN / 0 elsewhere."""
+    cams = np.nonzero(placed)[0]
+    rows = np.concatenate([np.column_stack([np.full(seen[c][0].shape[0], c, dtype=np.float64), seen[c][0], seen[c][1]]) for c in cams])
+    rows = rows[np.lexsort((rows[:, 0], rows[:, 1]))]   # by key, then camera
+    count = np.bincount(rows[:, 1].astype(np.int64), minlength=n_keys)
+    rows = rows[count[rows[:, 1].astype(np.int64)] >= 2]
+    points, n_views, rms = np.full((n_keys, 3), np.nan), np.zeros(n_keys, dtype=np.int32), np.full(n_keys, np.nan)
+    if rows.shape[0] == 0:
+        return points, n_views, rms
+    keys = rows[:, 1].astype(np.int64)
+    head = np.ones(keys.shape[0], dtype=bool)
+    head[1:] = keys[1:] != keys[:-1]
+    start = np.concatenate([np.nonzero(head)[0], [keys.shape[0]]]).astype(np.int64)
+    Km = intrinsic_matrices(K)
+    Mp = np.where(placed[:, None, None], M, np.eye(4))   # a camera that is not placed is never referenced
+    res = triangulate_fn(rows[:, [0, 2, 3]], Km @ Mp[:, :3, :], start, Km, K[:, 4:9], **tri_opts)
+    ok = np.all(np.isfinite(res.points), axis=1)
+    k = keys[head][ok]
+    points[k], n_views[k], rms[k] = res.points[ok], np.asarray(res.n_views)[ok], np.asarray(res.rms)[ok]
+    return points, n_views, rms
+
+
+def seed_scene(dct, intr, n_cams: int, *, ref_cam: int = 0, baseline: float = 1.0, consensus: int = 64, inlier_px: float = 2.0, seed: int = 0,
+               min_points: int = 16, resect_opts: dict | None = None, tri_opts: dict | None = None, two_view_fn=None, triangulate_fn=None,
+               view_pose_fn=None) -> SceneSeed:
+    """A start for target-free bundle adjustment (``FreePointBundleHandler``) from the flat (N, 5) table [cam, im, key, u, v] and the
+    intrinsics (C, 9) alone: incremental reconstruction on the device's batched handles.
+
+    1. ``compiled_helpers.estimate_two_view`` on every pair with at least ``min_points`` shared keys.  The first pair is the OK pair
+       with the largest n_front * sin(parallax) (many points and a wide baseline; ties: the lower pair).  Its camera a gets the
+       identity, its camera b the pair's [R | baseline * t]: the scale of a scene without a target is free, ``baseline`` sets it.
+    2. Every key that at least two placed cameras see is triangulated and refined (``compiled_helpers.refine_triangulation``;
+       ``tri_opts`` reach it, e.g. ``consensus=64``).  While the first pair is alone, only its inliers are triangulated; once a third
+       camera is placed every key is, from every placed camera that sees it.
+    3. Rounds: every camera not placed yet that sees at least ``min_points`` triangulated keys is resected against them in one batched
+       call (``compiled_helpers.estimate_view_poses`` with the triangulated points as template; ``resect_opts`` reach it, e.g.
+       ``consensus=64``); a camera whose PnP did not converge stays unplaced.  Then step 2 again.  A round that places nothing ends it.
+    4. The world moves to ``ref_cam``'s camera frame; when ``ref_cam`` was not placed it stays with the first pair's camera a
+       (``frame_cam`` says which).
+
+    ``two_view_fn``, ``triangulate_fn``, ``view_pose_fn``: replacements with the signatures of the three device entry points."""
+    from . import compiled_helpers as ch
+
+    two_view_fn = ch.estimate_two_view if two_view_fn is None else two_view_fn
+    triangulate_fn = ch.refine_triangulation if triangulate_fn is None else triangulate_fn
+    view_pose_fn = ch.estimate_view_poses if view_pose_fn is None else view_pose_fn
+    resect_opts, tri_opts = dict(resect_opts or {}), dict(tri_opts or {})
+    d = np.asarray(dct, dtype=np.float64)
+    K = np.asarray(intr, dtype=np.float64)
+    C = int(n_cams)
+    if d.ndim != 2 or d.shape[1] != 5 or K.shape != (C, 9) or C < 2:
+        raise ValueError("expected dct (N, 5) = [cam, im, key, u, v] and intr (n_cams, 9) of at least two cameras")
+    if isinstance(ref_cam, bool) or not isinstance(ref_cam, (int, np.integer)) or not 0 <= int(ref_cam) < C:
+        raise ValueError(f"ref_cam must be a camera index in [0, {C}), got {ref_cam!r}")
+    if not (np.isfinite(baseline) and baseline > 0.0):
+        raise ValueError(f"baseline must be a finite number > 0, got {baseline!r}")
+    ch.check_twoview_options(consensus, inlier_px, seed, min_points)
+    if not np.all(np.isfinite(d)) or (d.shape[0] and (d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 2].min() < 0)):
+        raise ValueError("the table must be finite, with cameras inside the intrinsics and keys >= 0")
+    n_keys = int(d[:, 2].max()) + 1 if d.shape[0] else 0
+    tv = two_view_fn(d, K, consensus=consensus, inlier_px=inlier_px, seed=seed, min_points=min_points)
+    with np.errstate(invalid="ignore"):
+        quality = np.where(tv.status == ch.TWOVIEW_OK, tv.n_front * np.sin(tv.parallax), -np.inf)
+    if quality.shape[0] == 0 or not np.max(quality) > 0.0:
+        raise ValueError("no camera pair has a relative pose: too few shared keys, or only degenerate pairs (coplanar points, no baseline)")
+    p0 = int(np.argmax(quality))
+    a, b = (int(c) for c in tv.pairs[p0])
+    M = np.full((C, 4, 4), np.nan)
+    M[a] = np.eye(4)
+    M[b] = np.eye(4)
+    M[b, :3, :3], M[b, :3, 3] = tv.T[p0, :, :3], float(baseline) * tv.T[p0, :, 3]
+    placed = np.zeros(C, dtype=bool)
+    placed[[a, b]] = True
+    round_of = np.full(C, -1, dtype=np.int64)
+    round_of[[a, b]] = 0
+    seen = ch.shared_keys(d, C)
+    rows0 = slice(int(tv.start[p0]), int(tv.start[p0 + 1]))
+    dropped = tv.keys[rows0][~tv.inliers[rows0]]
+    pair_only = list(seen)   # what the first triangulation sees: the pair's correspondences without its outliers
+    for c in (a, b):
+        keep = ~np.isin(seen[c][0], dropped)
+        pair_only[c] = (seen[c][0][keep], seen[c][1][keep])
+    rnd = 0
+    while True:
+        points, n_views, rms = _triangulate_placed(pair_only if rnd == 0 else seen, M, K, placed, n_keys, triangulate_fn, tri_opts)
+        have = np.all(np.isfinite(points), axis=1)
+        cand = [c for c in range(C) if not placed[c] and int(np.sum(have[seen[c][0]])) >= min_points]
+        if not cand:
+            break
+        table = np.concatenate([np.column_stack([np.full(int(np.sum(have[seen[c][0]])), c, dtype=np.float64), np.zeros(int(np.sum(have[seen[c][0]]))),
+                                                 seen[c][0][have[seen[c][0]]], seen[c][1][have[seen[c][0]]]]) for c in cand])
+        vp = view_pose_fn(table, np.where(have[:, None], points, 0.0), K, n_imgs=1, min_points=min_points, **resect_opts)
+        poses, status = np.asarray(vp.poses).reshape(C, 6), np.asarray(vp.status).reshape(C)
+        new = [c for c in cand if status[c] == ch.PNP_CONVERGED and np.all(np.isfinite(poses[c]))]
+        if not new:
+            break
+        rnd += 1
+        M[new] = pose_to_4x4(poses[new])
+        placed[new], round_of[new] = True, rnd
+    frame = int(ref_cam) if placed[ref_cam] else a
+    if frame != a:
+        F = M[frame].copy()
+        M = np.where(placed[:, None, None], M @ rigid_inverse(F), np.nan)
+        points = points @ F[:3, :3].T + F[:3, 3]
+    M[frame] = np.eye(4)
+    return SceneSeed(extr=pose_from_4x4(M), points=points, placed=placed, round_of_camera=round_of, n_views=n_views, rms=rms, first_pair=(a, b),
+                     frame_cam=frame, two_view=tv)
