@@ -847,6 +847,25 @@ int pcs_pnp_consensus_results(pcs_pose_estimator *p, uint8_t *inlier, int32_t *c
  *   pcs_twoview_set_consensus      1 <= n_hypotheses <= 256 (else PCS_ERR_RANGE; default 64), inlier_px finite and > 0 (else
  *                                  PCS_ERR_ARG; default 2), seed.  A refused call keeps the previous setting.
  *   pcs_twoview_get_consensus      the setting in force (any pointer may be NULL)
+ *   pcs_twoview_set_solver         since pcs_version() 120, opt-in (csrc/ba_fivepoint.hpp).  solver: PCS_TWOVIEW_EIGHT_POINT (default,
+ *                                  everything above) or PCS_TWOVIEW_FIVE_POINT, else PCS_ERR_ARG; refine_iters in [0, 50] (default
+ *                                  0), else PCS_ERR_RANGE.  A refused call keeps the previous setting.
+ *                                  FIVE_POINT: for scenes that are (mostly) one plane, where the eight-point method degenerates.
+ *                                  Every hypothesis is Nister's five-point solver on five sampled rows, in normalised camera
+ *                                  coordinates: up to ten essential matrices, the real roots of a degree-10 polynomial found by a
+ *                                  Sturm chain with fixed iteration counts.  A candidate's score is the smallest, over its four
+ *                                  (R, +-t), of sum min(e^2, inlier_px^2) in which a row that is not in front of both cameras counts
+ *                                  inlier_px^2 (ties: the lower candidate); the lowest score of a pair wins (ties: the lower
+ *                                  hypothesis, then the lower root).  Inlier flags: e^2 <= inlier_px^2 and in front under the
+ *                                  winner.  There is no refit over the inliers (it degenerates on a plane): the winner's (R, t) is
+ *                                  the model.  Statuses: TOO_FEW below max(5, min_points) rows; DEGENERATE without a usable
+ *                                  candidate or with fewer than 6 inliers; info's winning hypothesis stays the sample's index.
+ *                                  refine_iters > 0, with either solver: behind the final model at most refine_iters trials of a
+ *                                  5-parameter Levenberg-Marquardt on R <- exp(omega) R, t <- exp(nu) t (nu across t) over the
+ *                                  signed Sampson residuals of the inliers, with the damping, accept and stop rules of
+ *                                  pcs_tri_refine (ftol = xtol = 1e-10).  The inlier flags stay the winner's; the count in front, the
+ *                                  RMS and the parallax are taken at the refined pose.  Its time counts under "final".
+ *   pcs_twoview_get_solver         the setting in force (any pointer may be NULL)
  *   pcs_twoview_run                queue the kernels on `stream` (NULL = the handle's stream).  group_lanes: 16 or 64 lanes per
  *                                  pair in the scoring, selection and final kernels, 0 = 64 from a mean of 256 rows per pair on.
  *                                  flags: none defined, pass 0.  d_T (n_pairs, 12), a device buffer of the caller or NULL =
@@ -863,10 +882,11 @@ int pcs_pnp_consensus_results(pcs_pose_estimator *p, uint8_t *inlier, int32_t *c
 typedef struct pcs_two_view pcs_two_view;
 enum {
     PCS_TWOVIEW_OK = 0,
-    PCS_TWOVIEW_TOO_FEW = 1,        /* fewer than max(8, min_points) rows */
-    PCS_TWOVIEW_DEGENERATE = 2,     /* no usable hypothesis, fewer than 8 inliers, or the fit over the inliers lost rank */
+    PCS_TWOVIEW_TOO_FEW = 1,        /* fewer than max(8, min_points) rows (five-point solver: max(5, min_points)) */
+    PCS_TWOVIEW_DEGENERATE = 2,     /* no usable hypothesis, fewer than 8 inliers (five-point solver: 6), or the fit over the inliers lost rank */
     PCS_TWOVIEW_NO_CHEIRALITY = 3   /* no inlier in front of both cameras */
 };
+enum { PCS_TWOVIEW_EIGHT_POINT = 0, PCS_TWOVIEW_FIVE_POINT = 1 };
 enum { PCS_TWOVIEW_OUT_T = 1, PCS_TWOVIEW_OUT_INFO = 2, PCS_TWOVIEW_OUT_STATS = 4, PCS_TWOVIEW_OUT_INLIER = 8 };
 int pcs_twoview_create(pcs_two_view **out, int device, int64_t n_cams);
 int pcs_twoview_destroy(pcs_two_view *p);
@@ -875,6 +895,8 @@ int pcs_twoview_set_correspondences(pcs_two_view *p, int64_t n_corr, const doubl
                                     const int32_t *pair_cams);
 int pcs_twoview_set_consensus(pcs_two_view *p, int n_hypotheses, double inlier_px, uint64_t seed);
 int pcs_twoview_get_consensus(pcs_two_view *p, int *n_hypotheses, double *inlier_px, uint64_t *seed);
+int pcs_twoview_set_solver(pcs_two_view *p, int solver, int refine_iters);
+int pcs_twoview_get_solver(pcs_two_view *p, int *solver, int *refine_iters);
 int pcs_twoview_run(pcs_two_view *p, int min_points, int group_lanes, int flags, double *d_T, void *stream);
 int pcs_twoview_results(pcs_two_view *p, double *T, int32_t *info, double *stats, uint8_t *inlier);
 int pcs_twoview_last_kernel_ms(pcs_two_view *p, float *kernel_ms);

@@ -43,6 +43,8 @@ PNP_RESIDUALS = 1                        # include/pcs_hip.h PCS_PNP_RESIDUALS
 PNP_NOT_ESTIMATED, PNP_CONVERGED, PNP_MAX_ITER, PNP_NO_DECREASE = 0, 1, 2, 3
 # include/pcs_hip.h PCS_TWOVIEW_*: per-pair status of the two-view consensus
 TWOVIEW_OK, TWOVIEW_TOO_FEW, TWOVIEW_DEGENERATE, TWOVIEW_NO_CHEIRALITY = 0, 1, 2, 3
+# include/pcs_hip.h PCS_TWOVIEW_EIGHT_POINT / PCS_TWOVIEW_FIVE_POINT: the hypothesis solver of pcs_twoview_set_solver
+TWOVIEW_EIGHT_POINT, TWOVIEW_FIVE_POINT = 0, 1
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -172,6 +174,8 @@ SYMBOLS = {
     "pcs_twoview_set_correspondences": (c_int, [_P, c_int64, POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64), POINTER(c_int32)]),
     "pcs_twoview_set_consensus": (c_int, [_P, c_int, c_double, c_uint64]),
     "pcs_twoview_get_consensus": (c_int, [_P, POINTER(c_int), POINTER(c_double), POINTER(c_uint64)]),
+    "pcs_twoview_set_solver": (c_int, [_P, c_int, c_int]),
+    "pcs_twoview_get_solver": (c_int, [_P, POINTER(c_int), POINTER(c_int)]),
     "pcs_twoview_run": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "pcs_twoview_results": (c_int, [_P, POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_uint8)]),
     "pcs_twoview_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),

@@ -726,6 +726,17 @@ def estimate_view_poses(dct, points, intr, *, n_imgs: int | None = None, min_poi
 from ._capi import TWOVIEW_DEGENERATE, TWOVIEW_NO_CHEIRALITY, TWOVIEW_OK, TWOVIEW_TOO_FEW  # noqa: E402,F401
 last_twoview_kernel_ms = None
 TWOVIEW_STAGES = ("undistort", "hypotheses", "scores", "selection", "final")
+TWOVIEW_SOLVERS = {"eight-point": 0, "five-point": 1}   # include/pcs_hip.h PCS_TWOVIEW_EIGHT_POINT / PCS_TWOVIEW_FIVE_POINT
+TWOVIEW_MAX_REFINE = 50
+
+
+def check_twoview_solver(solver, refine_iters):
+    """Validate the solver options on the host (ValueError): the checks of pcs_twoview_set_solver.  -> (code, refine_iters)."""
+    if solver not in TWOVIEW_SOLVERS:
+        raise ValueError(f"solver must be one of {sorted(TWOVIEW_SOLVERS)}, got {solver!r}")
+    if isinstance(refine_iters, bool) or not isinstance(refine_iters, (int, np.integer)) or not 0 <= int(refine_iters) <= TWOVIEW_MAX_REFINE:
+        raise ValueError(f"refine_iters must be an integer in [0, {TWOVIEW_MAX_REFINE}], got {refine_iters!r}")
+    return TWOVIEW_SOLVERS[solver], int(refine_iters)
 
 
 @dataclass
@@ -809,6 +820,18 @@ class TwoViewEstimator(_Handle):
         self._call("pcs_twoview_get_consensus", self._h, self._ct.byref(h), self._ct.byref(px), self._ct.byref(seed))
         return int(h.value), float(px.value), int(seed.value)
 
+    def set_solver(self, solver: str = "eight-point", refine_iters: int = 0):
+        """The hypothesis solver ("eight-point", or "five-point" for scenes that are mostly one plane) and the number of LM trials that
+        refine the final pose on the essential manifold (0: none), for the runs that follow."""
+        code, iters = check_twoview_solver(solver, refine_iters)
+        self._call("pcs_twoview_set_solver", self._h, code, iters)
+
+    def get_solver(self):
+        """(solver name, refine_iters) in force."""
+        code, iters = self._ct.c_int(0), self._ct.c_int(0)
+        self._call("pcs_twoview_get_solver", self._h, self._ct.byref(code), self._ct.byref(iters))
+        return {v: k for k, v in TWOVIEW_SOLVERS.items()}[int(code.value)], int(iters.value)
+
     def run(self, min_points: int = 16, group_lanes: int = 0, d_T: int | None = None, stream: int | None = None):
         """Queue the five stages (asynchronous; handle-owned outputs, fetched with ``results()``)."""
         self._call("pcs_twoview_run", self._h, int(min_points), int(group_lanes), 0, self._addr(d_T), _stream_arg(stream))
@@ -852,7 +875,7 @@ def _twoview_estimator(device: int, n_cams: int) -> TwoViewEstimator:
 
 
 def estimate_two_view(dct, intr, *, pairs=None, consensus: int = 64, inlier_px: float = 2.0, seed: int = 0, min_points: int = 16,
-                      group_lanes: int = 0, device: int = 0) -> TwoViewResult:
+                      group_lanes: int = 0, device: int = 0, solver: str = "eight-point", refine_iters: int = 0) -> TwoViewResult:
     """The relative pose of camera pairs from their shared image points alone, on the device (include/pcs_hip.h pcs_twoview_run): what
     cv2.findEssentialMat(..., RANSAC) + cv2.recoverPose give on the host, and the first step of a target-free seed (``seed_scene``).
 
@@ -863,9 +886,15 @@ def estimate_two_view(dct, intr, *, pairs=None, consensus: int = 64, inlier_px: 
     sum min(e^2, inlier_px^2) of the Sampson distance in undistorted pixels; the winner's inliers are refitted.  The hypothesis
     count is fixed and the sampler counter-based (``seed``): two calls agree bit for bit.  A pair with fewer than max(8, min_points)
     correspondences, a degenerate one (coplanar points, no baseline) or one without a point in front of both cameras keeps NaN in
-    ``T``; ``status``, ``n_front`` and ``parallax`` say why."""
+    ``T``; ``status``, ``n_front`` and ``parallax`` say why.
+
+    ``solver="five-point"`` is for scenes that are (mostly) one plane — boards, walls, floors — where the eight-point method degenerates:
+    every hypothesis is Nister's five-point solver on five rows, scored with a cheirality term over its four (R, +-t), and the winner's
+    pose is the model (TOO_FEW below max(5, min_points) rows, DEGENERATE below 6 inliers).  ``refine_iters`` > 0, with either solver,
+    refines the final pose by that many LM trials at most over the Sampson residuals of the inliers, on the essential manifold."""
     global last_twoview_kernel_ms
     H, px, seed, min_points, lanes = check_twoview_options(consensus, inlier_px, seed, min_points, group_lanes)
+    check_twoview_solver(solver, refine_iters)
     d = np.asarray(dct, dtype=np.float64)
     K = np.asarray(intr, dtype=np.float64)
     if d.ndim != 2 or d.shape[1] != 5 or K.ndim != 2 or K.shape[1] != 9 or K.shape[0] < 2:
@@ -901,6 +930,7 @@ def estimate_two_view(dct, intr, *, pairs=None, consensus: int = 64, inlier_px: 
     est.set_cameras(K)
     est.set_correspondences(ua, ub, start, pc)
     est.set_consensus(H, px, seed)   # the handle is shared: every call states its setting
+    est.set_solver(solver, refine_iters)
     est.run(min_points=min_points, group_lanes=lanes)
     T, info, stats, inl = est.results()
     last_twoview_kernel_ms = est.last_kernel_ms() if pc.shape[0] else None

@@ -49,6 +49,7 @@
 #include "ba_riggraph.hpp"
 #include "ba_groupstats.hpp"
 #include "ba_twoview.hpp"
+#include "ba_fivepoint.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side

@@ -1,4 +1,4 @@
-// pcs_twoview.inc — host side of the two-view consensus (included by pcs_engine.hip; kernels: ba_twoview.hpp).  Fence, buffers and output
+// pcs_twoview.inc — host side of the two-view consensus (included by pcs_engine.hip; kernels: ba_twoview.hpp, ba_fivepoint.hpp).  Fence, buffers and output
 // slots are those of pcs_handle.inc (DESIGN.md, "Batched handles").
 extern "C" {
 // ---- two-view relative pose (SURVEY f10): a handle that owns the camera table, the correspondence copies, the stage buffers and the outputs.
@@ -17,7 +17,9 @@ struct pcs_two_view {
     int n_hyp = 64;
     double inlier_px = 2.0;
     uint64_t seed = 0;
+    int solver = TV_SOLVER_EIGHT_POINT, refine_iters = 0;   // pcs_twoview_set_solver
     DevBuf und, hyp_F, hyp_ok, score, sel, best;   // undistorted rows; per (pair, hypothesis) F, usable flag and score; per pair the selection
+    DevBuf hyp_E, slot_T;                          // five-point solver: per slot (ten per hypothesis) E and the best of its four [R | t]
     DevBuf T, info, stats, flag;                   // handle-owned outputs
     int owned = 0;
     bool run_valid = false;
@@ -45,7 +47,7 @@ int pcs_twoview_create(pcs_two_view **out, int device, int64_t n_cams) {
 int pcs_twoview_destroy(pcs_two_view *p) {
     if (!p) return PCS_OK;
     p->core.destroy({&p->tab, &p->uva, &p->uvb, &p->start, &p->pcams, &p->cpair, &p->order, &p->hist, &p->und, &p->hyp_F, &p->hyp_ok, &p->score, &p->sel,
-                     &p->best, &p->T, &p->info, &p->stats, &p->flag},
+                     &p->best, &p->hyp_E, &p->slot_T, &p->T, &p->info, &p->stats, &p->flag},
                     {});
     for (hipEvent_t &e : p->ev)
         if (e) (void)hipEventDestroy(e);
@@ -120,11 +122,81 @@ int pcs_twoview_get_consensus(pcs_two_view *p, int *n_hypotheses, double *inlier
     return PCS_OK;
 }
 
+static_assert(TV_SOLVER_EIGHT_POINT == PCS_TWOVIEW_EIGHT_POINT && TV_SOLVER_FIVE_POINT == PCS_TWOVIEW_FIVE_POINT, "solver codes of pcs_hip.h");
+
+// The hypothesis solver and the refinement behind the final model.  Everything is checked before anything changes: a refused call keeps
+// the previous setting.
+int pcs_twoview_set_solver(pcs_two_view *p, int solver, int refine_iters) {
+    if (!p) return fail(PCS_ERR_ARG, "pcs_twoview_set_solver: NULL handle");
+    if (solver != TV_SOLVER_EIGHT_POINT && solver != TV_SOLVER_FIVE_POINT)
+        return fail(PCS_ERR_ARG, "pcs_twoview_set_solver: solver %d is neither PCS_TWOVIEW_EIGHT_POINT nor PCS_TWOVIEW_FIVE_POINT", solver);
+    if (refine_iters < 0 || refine_iters > TV_REFINE_MAX_ITERS)
+        return fail(PCS_ERR_RANGE, "pcs_twoview_set_solver: refine_iters %d outside [0, %d]", refine_iters, TV_REFINE_MAX_ITERS);
+    p->solver = solver;
+    p->refine_iters = refine_iters;
+    return PCS_OK;
+}
+
+int pcs_twoview_get_solver(pcs_two_view *p, int *solver, int *refine_iters) {
+    if (!p) return fail(PCS_ERR_ARG, "pcs_twoview_get_solver: NULL handle");
+    if (solver) *solver = p->solver;
+    if (refine_iters) *refine_iters = p->refine_iters;
+    return PCS_OK;
+}
+
 enum { TV_SLOT_T, TV_SLOT_INFO, TV_SLOT_STATS, TV_SLOT_INLIER, TV_SLOTS };
 static std::array<OutSlot, TV_SLOTS> tv_out_slots(pcs_two_view *p, void *o_T, void *o_info, void *o_stats, void *o_inlier) {
     const int64_t np = p->n_pairs;
     return {{{PCS_TWOVIEW_OUT_T, p->T, o_T, np, 12 * sizeof(double)}, {PCS_TWOVIEW_OUT_INFO, p->info, o_info, np, 5 * sizeof(int32_t)},
              {PCS_TWOVIEW_OUT_STATS, p->stats, o_stats, np, 3 * sizeof(double)}, {PCS_TWOVIEW_OUT_INLIER, p->flag, o_inlier, p->n_corr, sizeof(uint8_t)}}};
+}
+
+// The refinement behind either final kernel (it counts under "final"), the last event and the fence: the end of every run.
+static int twoview_finish_run(pcs_two_view *p, OutSlot *out, int owned, bool wide, hipStream_t s) {
+    if (p->refine_iters > 0) {
+        const dim3 pair_g((unsigned)((p->n_pairs * (wide ? 64 : 16) + 255) / 256));
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, pair_g, dim3(256), 0, s, p->und.as<const double4>(), p->start.as<const int64_t>(), p->pcams.as<const int32_t>(),
+                               p->tab.as<const double>(), p->n_pairs, p->order.as<const int32_t>(), p->refine_iters, (const uint8_t *)out[TV_SLOT_INLIER].as<uint8_t>(),
+                               out[TV_SLOT_T].as<double>(), out[TV_SLOT_INFO].as<int32_t>(), out[TV_SLOT_STATS].as<double>());
+        };
+        if (wide) launch(tv_refine_kernel<64>);
+        else launch(tv_refine_kernel<16>);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->ev[5], s));
+    p->timed = true;
+    p->owned = owned;
+    p->run_valid = true;
+    HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+// Stages 2 .. 5 of a run with the five-point solver (ba_fivepoint.hpp): ten candidate slots per hypothesis, scored with cheirality.
+static int twoview_run_five_point(pcs_two_view *p, OutSlot *out, int owned, bool wide, int n_min, double tau2, hipStream_t s) {
+    const int64_t np = p->n_pairs, H = p->n_hyp, nh = np * H, ns = nh * TV5_SLOTS;
+    const int G = wide ? 64 : 16, HS = (int)(H * TV5_SLOTS);
+    const double4 *und = p->und.as<const double4>();
+    const int64_t *start = p->start.as<const int64_t>();
+    const int32_t *pcams = p->pcams.as<const int32_t>(), *order = p->order.as<const int32_t>();
+    const double *tab = p->tab.as<const double>();
+    const dim3 hyp16((unsigned)((nh * 16 + 255) / 256)), slot_g((unsigned)((ns * G + 255) / 256)), pair_g((unsigned)((np * G + 255) / 256));
+    hipLaunchKernelGGL(tv5_hypothesis_kernel, hyp16, dim3(256), 0, s, und, start, pcams, tab, np, (int)H, p->seed, p->hyp_E.as<double>(), p->hyp_F.as<double>(),
+                       p->hyp_ok.as<uint8_t>());
+    HIPCHK(hipEventRecord(p->ev[2], s));
+    const double *hyp_E = p->hyp_E.as<const double>(), *hyp_F = p->hyp_F.as<const double>(), *score = p->score.as<const double>(), *slot_T = p->slot_T.as<const double>();
+    uint8_t *flag = out[TV_SLOT_INLIER].as<uint8_t>();
+    if (wide) hipLaunchKernelGGL((tv5_score_kernel<64>), slot_g, dim3(256), 0, s, und, start, pcams, tab, np, HS, hyp_E, hyp_F, p->hyp_ok.as<const uint8_t>(), tau2, p->score.as<double>(), p->slot_T.as<double>());
+    else hipLaunchKernelGGL((tv5_score_kernel<16>), slot_g, dim3(256), 0, s, und, start, pcams, tab, np, HS, hyp_E, hyp_F, p->hyp_ok.as<const uint8_t>(), tau2, p->score.as<double>(), p->slot_T.as<double>());
+    HIPCHK(hipEventRecord(p->ev[3], s));
+    if (wide) hipLaunchKernelGGL((tv5_select_kernel<64>), pair_g, dim3(256), 0, s, und, start, pcams, tab, np, order, HS, n_min, hyp_F, slot_T, score, tau2, flag, p->sel.as<int32_t>(), p->best.as<double>());
+    else hipLaunchKernelGGL((tv5_select_kernel<16>), pair_g, dim3(256), 0, s, und, start, pcams, tab, np, order, HS, n_min, hyp_F, slot_T, score, tau2, flag, p->sel.as<int32_t>(), p->best.as<double>());
+    HIPCHK(hipEventRecord(p->ev[4], s));
+    if (wide) hipLaunchKernelGGL((tv5_final_kernel<64>), pair_g, dim3(256), 0, s, und, start, pcams, tab, np, order, HS, n_min, (const uint8_t *)flag, p->sel.as<const int32_t>(),
+                                 p->best.as<const double>(), slot_T, out[TV_SLOT_T].as<double>(), out[TV_SLOT_INFO].as<int32_t>(), out[TV_SLOT_STATS].as<double>());
+    else hipLaunchKernelGGL((tv5_final_kernel<16>), pair_g, dim3(256), 0, s, und, start, pcams, tab, np, order, HS, n_min, (const uint8_t *)flag, p->sel.as<const int32_t>(),
+                            p->best.as<const double>(), slot_T, out[TV_SLOT_T].as<double>(), out[TV_SLOT_INFO].as<int32_t>(), out[TV_SLOT_STATS].as<double>());
+    return twoview_finish_run(p, out, owned, wide, s);
 }
 
 int pcs_twoview_run(pcs_two_view *p, int min_points, int group_lanes, int flags, double *d_T, void *stream) {
@@ -133,13 +205,16 @@ int pcs_twoview_run(pcs_two_view *p, int min_points, int group_lanes, int flags,
         return fail(PCS_ERR_ARG, "pcs_twoview_run: bad options (min_points >= 1, group_lanes 0, 16 or 64, no flags)");
     if (!p->have_cams || p->n_pairs < 0) return fail(PCS_ERR_STATE, "pcs_twoview_run: cameras or correspondences not set");
     auto out = tv_out_slots(p, d_T, nullptr, nullptr, nullptr);
+    const bool five = p->solver == TV_SOLVER_FIVE_POINT;
     const int64_t np = p->n_pairs, H = p->n_hyp, nh = np * H, nc = std::max<int64_t>(1, p->n_corr);
-    if (nh > INT32_MAX / 64) return fail(PCS_ERR_ARG, "pcs_twoview_run: %lld pairs x %lld hypotheses are more than one launch takes", (long long)np, (long long)H);
+    const int64_t ns = five ? nh * TV5_SLOTS : nh;   // scored candidates: ten slots per hypothesis of the five-point solver
+    if (ns > INT32_MAX / 64) return fail(PCS_ERR_ARG, "pcs_twoview_run: %lld pairs x %lld hypotheses are more than one launch takes", (long long)np, (long long)H);
     struct Need { DevBuf &buf; int64_t count; size_t bytes; };
-    const Need need[] = {{p->und, nc, 4 * sizeof(double)}, {p->hyp_F, nh, 9 * sizeof(double)}, {p->hyp_ok, nh, sizeof(uint8_t)}, {p->score, nh, sizeof(double)},
-                         {p->sel, np, 2 * sizeof(int32_t)}, {p->best, np, sizeof(double)}, {p->order, np, sizeof(int32_t)}};
+    const Need need[] = {{p->und, nc, 4 * sizeof(double)}, {p->hyp_F, ns, 9 * sizeof(double)}, {p->hyp_ok, ns, sizeof(uint8_t)}, {p->score, ns, sizeof(double)},
+                         {p->sel, np, 2 * sizeof(int32_t)}, {p->best, np, sizeof(double)}, {p->order, np, sizeof(int32_t)},
+                         {p->hyp_E, five ? ns : -1, 9 * sizeof(double)}, {p->slot_T, five ? ns : -1, 12 * sizeof(double)}};   // -1: not needed by this solver
     bool grows = false;
-    for (const Need &n : need) grows = grows || n.buf.grows(std::max<int64_t>(1, n.count));
+    for (const Need &n : need) grows = grows || (n.count >= 0 && n.buf.grows(std::max<int64_t>(1, n.count)));
     const int owned = owned_slots(out.data(), TV_SLOTS, &grows);
     if (np == 0) {
         p->owned = owned;
@@ -152,14 +227,14 @@ int pcs_twoview_run(pcs_two_view *p, int min_points, int group_lanes, int flags,
     HIPCHK(p->core.fence.before_run(s, grows));
     int rc = grow_owned_slots(out.data(), TV_SLOTS);
     for (const Need &n : need)
-        if (!rc) rc = n.buf.grow(std::max<int64_t>(1, n.count), n.bytes);
+        if (!rc && n.count >= 0) rc = n.buf.grow(std::max<int64_t>(1, n.count), n.bytes);
     if (rc) return rc;
     if (!p->order_valid) {   // after every allocation: nothing is queued by a call that fails in one
         if ((rc = enqueue_group_order(p->start.as<int64_t>(), np, p->hist.as<int32_t>(), p->order.as<int32_t>(), s))) return rc;
         p->order_valid = true;
     }
     const bool wide = group_lanes == 64 || (group_lanes == 0 && p->n_corr >= TV_WIDE_MEAN * np);
-    const int G = wide ? 64 : 16, n_min = std::max(TV_SAMPLE, min_points);
+    const int G = wide ? 64 : 16, n_min = std::max(five ? TV5_SAMPLE : TV_SAMPLE, min_points);
     const double tau2 = p->inlier_px * p->inlier_px;
     const double4 *und = p->und.as<const double4>();
     const int64_t *start = p->start.as<const int64_t>();
@@ -171,6 +246,7 @@ int pcs_twoview_run(pcs_two_view *p, int min_points, int group_lanes, int flags,
         hipLaunchKernelGGL(tv_undistort_kernel, dim3((unsigned)((p->n_corr + 255) / 256)), dim3(256), 0, s, p->uva.as<const double2>(), p->uvb.as<const double2>(),
                            p->cpair.as<const int32_t>(), pcams, tab, p->n_corr, p->und.as<double4>());
     HIPCHK(hipEventRecord(p->ev[1], s));
+    if (five) return twoview_run_five_point(p, out.data(), owned, wide, n_min, tau2, s);
     hipLaunchKernelGGL(tv_hypothesis_kernel, hyp16, dim3(256), 0, s, und, start, pcams, tab, np, (int)H, p->seed, p->hyp_F.as<double>(), p->hyp_ok.as<uint8_t>());
     HIPCHK(hipEventRecord(p->ev[2], s));
     const double *hyp_F = p->hyp_F.as<const double>(), *score = p->score.as<const double>();
@@ -185,13 +261,7 @@ int pcs_twoview_run(pcs_two_view *p, int min_points, int group_lanes, int flags,
                                  p->best.as<const double>(), out[TV_SLOT_T].as<double>(), out[TV_SLOT_INFO].as<int32_t>(), out[TV_SLOT_STATS].as<double>());
     else hipLaunchKernelGGL((tv_final_kernel<16>), pair_g, dim3(256), 0, s, und, start, pcams, tab, np, order, n_min, (const uint8_t *)flag, p->sel.as<const int32_t>(),
                             p->best.as<const double>(), out[TV_SLOT_T].as<double>(), out[TV_SLOT_INFO].as<int32_t>(), out[TV_SLOT_STATS].as<double>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(p->ev[5], s));
-    p->timed = true;
-    p->owned = owned;
-    p->run_valid = true;
-    HIPCHK(p->core.fence.after_run(s));
-    return PCS_OK;
+    return twoview_finish_run(p, out.data(), owned, wide, s);
 }
 
 int pcs_twoview_results(pcs_two_view *p, double *T, int32_t *info, double *stats, uint8_t *inlier) {

@@ -496,7 +496,8 @@ class FreePointBundleHandler(TemplateBundleHandler):  # fph:102-201
         """``seeding="scene"``: the start vector of a scene nobody measured, from the detections alone
         (``pose_seeding.seed_scene``: two-view consensus, triangulation, resection in rounds; the reference has no such start,
         fph:235).  Intrinsics are found as for the other seedings (``intr``, the camset's, or the planar estimate); ``scene_opts``
-        reach ``seed_scene`` (``baseline``, ``consensus``, ``inlier_px``, ``seed``, ``min_points``, ``resect_opts``, ``tri_opts``),
+        reach ``seed_scene`` (``baseline``, ``consensus``, ``inlier_px``, ``seed``, ``min_points``, ``resect_opts``, ``tri_opts``, and
+        ``two_view_solver="five-point"`` / ``two_view_refine`` for a scene that is mostly one plane),
         ``ref_cam`` comes from ``options["ref_cam"]``.  The world is ``ref_cam``'s camera frame and the first pair's baseline has
         length ``baseline``: fixed extrinsics must be given in that gauge.  The seed is kept on ``scene_seed``.  ValueError names the
         cameras and keys with a free entry that got no seed.  Every other ``seeding`` is ``TemplateBundleHandler.calc_initial_params``,

@@ -391,13 +391,16 @@ def _triangulate_placed(seen, M, K, placed, n_keys, triangulate_fn, tri_opts):
 
 def seed_scene(dct, intr, n_cams: int, *, ref_cam: int = 0, baseline: float = 1.0, consensus: int = 64, inlier_px: float = 2.0, seed: int = 0,
                min_points: int = 16, resect_opts: dict | None = None, tri_opts: dict | None = None, two_view_fn=None, triangulate_fn=None,
-               view_pose_fn=None) -> SceneSeed:
+               view_pose_fn=None, two_view_solver: str = "eight-point", two_view_refine: int = 0) -> SceneSeed:
     """A start for target-free bundle adjustment (``FreePointBundleHandler``) from the flat (N, 5) table [cam, im, key, u, v] and the
     intrinsics (C, 9) alone: incremental reconstruction on the device's batched handles.
 
     1. ``compiled_helpers.estimate_two_view`` on every pair with at least ``min_points`` shared keys.  The first pair is the OK pair
        with the largest n_front * sin(parallax) (many points and a wide baseline; ties: the lower pair).  Its camera a gets the
        identity, its camera b the pair's [R | baseline * t]: the scale of a scene without a target is free, ``baseline`` sets it.
+       ``two_view_solver="five-point"`` is for scenes that are mostly one plane (boards, walls, floors), where the eight-point
+       hypotheses degenerate; ``two_view_refine`` > 0 refines every pair's pose by that many LM trials at most (``estimate_two_view``'s
+       ``solver`` and ``refine_iters``; a ``two_view_fn`` of the caller's receives them only when they differ from the defaults).
     2. Every key that at least two placed cameras see is triangulated and refined (``compiled_helpers.refine_triangulation``;
        ``tri_opts`` reach it, e.g. ``consensus=64``).  While the first pair is alone, only its inliers are triangulated; once a third
        camera is placed every key is, from every placed camera that sees it.
@@ -424,10 +427,12 @@ def seed_scene(dct, intr, n_cams: int, *, ref_cam: int = 0, baseline: float = 1.
     if not (np.isfinite(baseline) and baseline > 0.0):
         raise ValueError(f"baseline must be a finite number > 0, got {baseline!r}")
     ch.check_twoview_options(consensus, inlier_px, seed, min_points)
+    ch.check_twoview_solver(two_view_solver, two_view_refine)
+    solver_opts = {} if (two_view_solver, int(two_view_refine)) == ("eight-point", 0) else {"solver": two_view_solver, "refine_iters": int(two_view_refine)}
     if not np.all(np.isfinite(d)) or (d.shape[0] and (d[:, 0].min() < 0 or d[:, 0].max() >= C or d[:, 2].min() < 0)):
         raise ValueError("the table must be finite, with cameras inside the intrinsics and keys >= 0")
     n_keys = int(d[:, 2].max()) + 1 if d.shape[0] else 0
-    tv = two_view_fn(d, K, consensus=consensus, inlier_px=inlier_px, seed=seed, min_points=min_points)
+    tv = two_view_fn(d, K, consensus=consensus, inlier_px=inlier_px, seed=seed, min_points=min_points, **solver_opts)
     with np.errstate(invalid="ignore"):
         quality = np.where(tv.status == ch.TWOVIEW_OK, tv.n_front * np.sin(tv.parallax), -np.inf)
     if quality.shape[0] == 0 or not np.max(quality) > 0.0:

@@ -5,7 +5,7 @@ The rig-32 table (32 cameras on two rings, 200 poses of the Ccube target) read a
 free point, key' = image * K + key.  Every camera pair with at least ``--min-points`` shared points is one pair of the handle.  Printed
 per hypothesis count: the device time of every stage (events around the launches), their sum, and what came out.
 
-    python tools/twoview_bench.py [--imgs 200] [--hypotheses 16 64 256] [--repeat 5] [--json out.json]
+    python tools/twoview_bench.py [--imgs 200] [--hypotheses 16 64 256] [--solver five-point] [--refine 10] [--repeat 5] [--json out.json]
 """
 import argparse
 import json
@@ -33,13 +33,16 @@ def main():
     ap.add_argument("--hypotheses", type=int, nargs="+", default=[16, 64, 256])
     ap.add_argument("--min-points", type=int, default=16)
     ap.add_argument("--inlier-px", type=float, default=2.0)
+    ap.add_argument("--solver", choices=sorted(ch.TWOVIEW_SOLVERS), default="eight-point")
+    ap.add_argument("--refine", type=int, default=0, help="LM trials that refine the final pose (0: none)")
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--json", type=str, default=None)
     a = ap.parse_args()
     rig = synthetic.config_rig(3, n_imgs=a.imgs)
     det = free_chain_table(rig)
     t0 = time.perf_counter()
-    first = ch.estimate_two_view(det, rig.intr, consensus=a.hypotheses[0], inlier_px=a.inlier_px, min_points=a.min_points)
+    first = ch.estimate_two_view(det, rig.intr, consensus=a.hypotheses[0], inlier_px=a.inlier_px, min_points=a.min_points, solver=a.solver,
+                                 refine_iters=a.refine)
     host_s = time.perf_counter() - t0
     n_pairs, n_corr = first.pairs.shape[0], first.uv_a.shape[0]
     print(f"rig-32 free-chain table: {det.shape[0]} detections, {n_pairs} pairs, {n_corr} correspondences "
@@ -47,6 +50,8 @@ def main():
     est = ch.TwoViewEstimator(rig.n_cams)
     est.set_cameras(rig.intr)
     est.set_correspondences(first.uv_a, first.uv_b, first.start, first.pairs)
+    est.set_solver(a.solver, a.refine)
+    print(f"solver {a.solver}, {a.refine} refinement trials")
     out = []
     for H in a.hypotheses:
         est.set_consensus(H, a.inlier_px, 0)
@@ -64,7 +69,8 @@ def main():
               f"{row['pairs_ok']} / {n_pairs} pairs OK, inliers {row['inlier_fraction']:.3f}, median RMS {row['median_rms_px']} px")
     est.close()
     if a.json:
-        Path(a.json).write_text(json.dumps({"detections": int(det.shape[0]), "pairs": n_pairs, "correspondences": n_corr, "runs": out}, indent=1))
+        Path(a.json).write_text(json.dumps({"detections": int(det.shape[0]), "pairs": n_pairs, "correspondences": n_corr, "solver": a.solver, "refine_iters": a.refine,
+                                              "runs": out}, indent=1))
 
 
 if __name__ == "__main__":
