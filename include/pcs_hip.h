@@ -902,6 +902,66 @@ int pcs_twoview_results(pcs_two_view *p, double *T, int32_t *info, double *stats
 int pcs_twoview_last_kernel_ms(pcs_two_view *p, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rigid / similarity registration of 3-D point sets, absolute orientation (csrc/ba_align.hpp).  Since pcs_version() 121.
+ * Replaces: n_estimate_rigid_transform (optimisation/compiled_helpers.py:727-762), a Kabsch fit of one pair of point sets by an SVD, and
+ *           what its caller SelfBundleHandler.apply_gauge_transform (optimisation/self_bundle_handler.py:339-410) needs from it; batched,
+ *           weighted, with the Umeyama scale and an opt-in consensus stage, which the reference lacks.
+ * Problem j owns rows [start_inds[j], start_inds[j+1]) of a table of source points x, destination points y and optional weights w.  Per
+ * problem: (s, R, t) with y ~ s R x + t in the weighted least-squares sense, s = 1 for the rigid model.  A row with a non-finite
+ * coordinate or with w = 0 takes no part and is not counted.  Centroids first, then the cross-covariance S of the centred rows; the
+ * rotation is Horn's unit quaternion, the largest eigenvector of the symmetric 4 x 4 N(S) by cyclic Jacobi, a proper rotation for planar
+ * and for mirrored sets alike; s = l1 / sum w |x~|^2; t = y_mean - s R x_mean.  conditioning = (l1 - l2) / (l1 - l4) of N's eigenvalues
+ * = (sigma_2 +- sigma_3) / (sigma_1 + sigma_2) of S's singular values: 0 for collinear points.  No floating-point atomics, every sum in
+ * a fixed order: for a given group width two runs give the same bits, and a problem's result does not depend on its neighbours.
+ *   pcs_align_create            a handle on `device` (no counterpart)
+ *   pcs_align_destroy           frees the handle (no counterpart)
+ *   pcs_align_set_points        host arrays, copied: src, dst (n_rows, 3), weights (n_rows) or NULL = 1 (compiled_helpers.py:727-762 takes
+ *                               v0, v1 of one problem, unweighted), start_inds (n_problems + 1).  Checked without touching the device, and
+ *                               a refused call keeps the previous table: PCS_ERR_ARG start_inds not running from 0 to n_rows or
+ *                               decreasing, a weight that is negative or not finite.  Non-finite coordinates are data: the row is skipped.
+ *   pcs_align_set_consensus     opt-in, in front of the fit (no counterpart).  0 <= n_hypotheses <= 256 (else PCS_ERR_RANGE; default 0 =
+ *                               off), inlier_dist finite and > 0 when n_hypotheses > 0 (else PCS_ERR_ARG), seed.  Every hypothesis is the
+ *                               same closed form on three rows drawn by the counter-based sampler of pcs_pnp_set_consensus, keyed by
+ *                               (seed, problem index, rows of the problem, hypothesis); it is scored on all rows of the problem by
+ *                               sum min(d^2, inlier_dist^2), d = |y - s R x - t|, a skipped row counting inlier_dist^2; the lowest
+ *                               score wins (ties: the lower hypothesis); the fit then runs on the rows with d <= inlier_dist at the
+ *                               winner.  A problem of fewer than three rows skips the stage.  A refused call keeps the previous setting.
+ *   pcs_align_get_consensus     the setting in force (any pointer may be NULL)
+ *   pcs_align_run               queue the kernels on `stream` (NULL = the handle's stream); the fit of compiled_helpers.py:727-762 for every
+ *                               problem.  model: PCS_ALIGN_RIGID or PCS_ALIGN_SIMILARITY; min_points >= 3; rank_tol in [0, 1): a problem
+ *                               whose conditioning is <= rank_tol is DEGENERATE; group_lanes: 16 or 64 lanes per problem, 0 = 64 from a
+ *                               mean of 256 rows per problem on; flags: none defined, pass 0.  d_T (n_problems, 12), a device buffer of
+ *                               the caller or NULL = handle-owned: [R | t] row-major; NaN unless the status is OK.
+ *   pcs_align_results           copy the outputs of the last run to the host (any pointer may be NULL; blocking; no counterpart): T
+ *                               (n_problems, 12); scale (n_problems); info (n_problems, 4) int32 {rows used, inliers (rows used without
+ *                               consensus), status PCS_ALIGN_*, winning hypothesis or -1}; stats (n_problems, 3) {weighted RMS of d over
+ *                               the rows used, the winner's score (NaN without consensus, +inf without a usable hypothesis),
+ *                               conditioning (NaN where no fit was tried)}; inlier (n_rows) one flag per row: it entered the fit; dist
+ *                               (n_rows) d of every row at the result.  T, scale, RMS and dist are NaN unless the status is OK.
+ *   pcs_align_last_kernel_ms    device time of the stages of the last run, kernel_ms[4] = {hypotheses, scores, selection, fit} (no
+ *                               counterpart).  PCS_ERR_STATE when the last run had no problems and so queued nothing.
+ */
+typedef struct pcs_point_aligner pcs_point_aligner;
+enum {
+    PCS_ALIGN_OK = 0,
+    PCS_ALIGN_TOO_FEW = 1,        /* fewer than min_points usable rows */
+    PCS_ALIGN_DEGENERATE = 2,     /* conditioning <= rank_tol: collinear or coincident points */
+    PCS_ALIGN_NONFINITE = 3,      /* every row has a non-finite coordinate, or the fit overflowed */
+    PCS_ALIGN_NO_CONSENSUS = 4    /* enough usable rows, fewer than min_points inliers */
+};
+enum { PCS_ALIGN_RIGID = 0, PCS_ALIGN_SIMILARITY = 1 };
+enum { PCS_ALIGN_OUT_T = 1, PCS_ALIGN_OUT_SCALE = 2, PCS_ALIGN_OUT_INFO = 4, PCS_ALIGN_OUT_STATS = 8, PCS_ALIGN_OUT_INLIER = 16, PCS_ALIGN_OUT_DIST = 32 };
+int pcs_align_create(pcs_point_aligner **out, int device);
+int pcs_align_destroy(pcs_point_aligner *p);
+int pcs_align_set_points(pcs_point_aligner *p, int64_t n_rows, const double *src, const double *dst, const double *weights, int64_t n_problems,
+                         const int64_t *start_inds);
+int pcs_align_set_consensus(pcs_point_aligner *p, int n_hypotheses, double inlier_dist, uint64_t seed);
+int pcs_align_get_consensus(pcs_point_aligner *p, int *n_hypotheses, double *inlier_dist, uint64_t *seed);
+int pcs_align_run(pcs_point_aligner *p, int model, int min_points, double rank_tol, int group_lanes, int flags, double *d_T, void *stream);
+int pcs_align_results(pcs_point_aligner *p, double *T, double *scale, int32_t *info, double *stats, uint8_t *inlier, double *dist);
+int pcs_align_last_kernel_ms(pcs_point_aligner *p, float *kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

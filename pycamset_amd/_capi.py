@@ -45,6 +45,9 @@ PNP_NOT_ESTIMATED, PNP_CONVERGED, PNP_MAX_ITER, PNP_NO_DECREASE = 0, 1, 2, 3
 TWOVIEW_OK, TWOVIEW_TOO_FEW, TWOVIEW_DEGENERATE, TWOVIEW_NO_CHEIRALITY = 0, 1, 2, 3
 # include/pcs_hip.h PCS_TWOVIEW_EIGHT_POINT / PCS_TWOVIEW_FIVE_POINT: the hypothesis solver of pcs_twoview_set_solver
 TWOVIEW_EIGHT_POINT, TWOVIEW_FIVE_POINT = 0, 1
+# include/pcs_hip.h PCS_ALIGN_*: per-problem status of the point-set registration, and its models
+ALIGN_OK, ALIGN_TOO_FEW, ALIGN_DEGENERATE, ALIGN_NONFINITE, ALIGN_NO_CONSENSUS = 0, 1, 2, 3, 4
+ALIGN_MODEL_IDS = {"rigid": 0, "similarity": 1}
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -179,6 +182,14 @@ SYMBOLS = {
     "pcs_twoview_run": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "pcs_twoview_results": (c_int, [_P, POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_uint8)]),
     "pcs_twoview_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_align_create": (c_int, [POINTER(_P), c_int]),
+    "pcs_align_destroy": (c_int, [_P]),
+    "pcs_align_set_points": (c_int, [_P, c_int64, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "pcs_align_set_consensus": (c_int, [_P, c_int, c_double, c_uint64]),
+    "pcs_align_get_consensus": (c_int, [_P, POINTER(c_int), POINTER(c_double), POINTER(c_uint64)]),
+    "pcs_align_run": (c_int, [_P, c_int, c_int, c_double, c_int, c_int, _P, _P]),
+    "pcs_align_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_uint8), POINTER(c_double)]),
+    "pcs_align_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),

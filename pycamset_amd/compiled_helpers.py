@@ -1700,3 +1700,233 @@ def localise_target(dct, points, intr, ext, *, n_imgs: int | None = None, poses_
         else:
             out.residuals[order] = resid
     return out
+
+
+# ---- registration of 3-D point sets (row f11: n_estimate_rigid_transform, ch:727-762, batched) ----------------------------------------
+# per-problem status of the registration (include/pcs_hip.h PCS_ALIGN_*)
+from ._capi import ALIGN_DEGENERATE, ALIGN_MODEL_IDS, ALIGN_NO_CONSENSUS, ALIGN_NONFINITE, ALIGN_OK, ALIGN_TOO_FEW  # noqa: E402,F401
+
+ALIGN_STAGES = ("hypotheses", "scores", "selection", "fit")
+ALIGN_CONSENSUS_MAX = 256   # hypotheses per problem that pcs_align_set_consensus takes
+last_align_kernel_ms = None
+
+
+@dataclass
+class Alignment:
+    """Registrations of P point-set problems (``align_points``): ``dst ~ scale * R @ src + t``.  ``R`` (P, 3, 3), ``t`` (P, 3),
+    ``scale`` (P,) (1 for the rigid model) and ``rms`` (P,), the weighted RMS distance over the rows used, are NaN unless ``status``
+    (ALIGN_*) is ALIGN_OK; ``n_used`` rows entered the fit, ``n_inliers`` of them by consensus (= ``n_used`` without), ``hypothesis``
+    the winner (-1: none) and ``score`` its sum min(d^2, inlier_dist^2) (NaN without consensus); ``conditioning`` (P,) in [0, 1], 0 for
+    collinear points (NaN where no fit was tried).  Per row of the table: ``inliers`` (n,) bool, the row entered the fit, and
+    ``distances`` (n,), |dst - scale R src - t|; problem p owns rows ``start[p]:start[p + 1]``."""
+    R: np.ndarray
+    t: np.ndarray
+    scale: np.ndarray
+    rms: np.ndarray
+    status: np.ndarray
+    n_used: np.ndarray
+    n_inliers: np.ndarray
+    inliers: np.ndarray
+    conditioning: np.ndarray
+    hypothesis: np.ndarray
+    score: np.ndarray
+    distances: np.ndarray
+    start: np.ndarray
+
+    def matrix(self) -> np.ndarray:
+        """(P, 4, 4) homogeneous transforms with scale * R in the upper left block."""
+        M = np.zeros((self.R.shape[0], 4, 4))
+        M[:, :3, :3], M[:, :3, 3], M[:, 3, 3] = self.scale[:, None, None] * self.R, self.t, 1.0
+        return M
+
+    def apply(self, points) -> np.ndarray:
+        """scale * R @ x + t: ``points`` (n, 3) in the table's layout (every problem's rows by its own transform), or (P, K, 3)."""
+        X = np.asarray(points, dtype=np.float64)
+        if X.ndim == 3 and X.shape[0] == self.R.shape[0] and X.shape[2] == 3:
+            return np.einsum("p,pij,pkj->pki", self.scale, self.R, X) + self.t[:, None, :]
+        if X.ndim != 2 or X.shape != (int(self.start[-1]), 3):
+            raise ValueError(f"expected points ({int(self.start[-1])}, 3) in the table's rows or ({self.R.shape[0]}, K, 3)")
+        prob = np.repeat(np.arange(self.R.shape[0]), np.diff(self.start))
+        return np.einsum("n,nij,nj->ni", self.scale[prob], self.R[prob], X) + self.t[prob]
+
+
+def check_align_options(model, consensus, inlier_dist, seed, min_points, rank_tol, group_lanes=0):
+    """Validate the options of the registration on the host (ValueError) before anything is queued: the checks of
+    pcs_align_set_consensus and pcs_align_run.  -> (model code, consensus, inlier_dist, seed, min_points, rank_tol, group_lanes)."""
+    if model not in ALIGN_MODEL_IDS:
+        raise ValueError(f"model must be one of {sorted(ALIGN_MODEL_IDS)}, got {model!r}")
+    for name, v, lo, hi in (("consensus", consensus, 0, ALIGN_CONSENSUS_MAX), ("seed", seed, 0, 2 ** 64 - 1), ("min_points", min_points, 3, 2 ** 31 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in [{lo}, {hi}], got {v!r}")
+    dist = 0.0
+    if int(consensus) > 0:
+        if inlier_dist is None:
+            raise ValueError("consensus > 0 needs inlier_dist, the largest distance of an inlier in the units of dst")
+        try:
+            dist = float(inlier_dist)
+        except (TypeError, ValueError):
+            raise ValueError(f"inlier_dist must be a finite number > 0, got {inlier_dist!r}") from None
+        if not (np.isfinite(dist) and dist > 0.0):
+            raise ValueError(f"inlier_dist must be a finite number > 0, got {inlier_dist!r}")
+    try:
+        tol = float(rank_tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"rank_tol must be a number in [0, 1), got {rank_tol!r}") from None
+    if not 0.0 <= tol < 1.0:
+        raise ValueError(f"rank_tol must be a number in [0, 1), got {rank_tol!r}")
+    if isinstance(group_lanes, bool) or group_lanes not in (0, 16, 64):
+        raise ValueError(f"group_lanes must be 0 (by size), 16 or 64, got {group_lanes!r}")
+    return ALIGN_MODEL_IDS[model], int(consensus), dist, int(seed), int(min_points), tol, int(group_lanes)
+
+
+class PointAligner(_Handle):
+    """Owner of one ``pcs_point_aligner`` handle (include/pcs_hip.h): the point table, the stage buffers and the outputs stay on the
+    device across calls."""
+
+    _create, _destroy = "pcs_align_create", "pcs_align_destroy"
+
+    def __init__(self, device: int = 0):
+        super().__init__(device)
+        self.device = int(device)
+        self.n_problems, self.n_rows = 0, 0
+
+    def set_points(self, src, dst, start_inds, weights=None):
+        """Host arrays sorted by problem: src, dst (n, 3), start_inds (P + 1,), weights (n,) >= 0 or None.  Shapes raise ValueError;
+        values are checked by the handle (PcsError) without touching the device.  Non-finite coordinates are data: the row is skipped."""
+        x = np.ascontiguousarray(src, dtype=np.float64)
+        y = np.ascontiguousarray(dst, dtype=np.float64)
+        start = np.ascontiguousarray(start_inds, dtype=np.int64)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if start.ndim != 1 or start.shape[0] < 1 or x.ndim != 2 or x.shape[1] != 3 or y.shape != x.shape or (w is not None and w.shape != (x.shape[0],)):
+            raise ValueError("expected src, dst (n, 3), start_inds (P + 1,) and weights (n,) or None")
+        self._call("pcs_align_set_points", self._h, x.shape[0], self._ptr(x), self._ptr(y), self._ptr(w), start.shape[0] - 1, self._ptr(start))
+        self.n_problems, self.n_rows = start.shape[0] - 1, x.shape[0]
+
+    def set_consensus(self, n_hypotheses: int = 0, inlier_dist: float = 0.0, seed: int = 0):
+        """Hypotheses per problem (0: no consensus stage), inlier distance in the units of dst and the seed of the sampler, for the runs
+        that follow."""
+        self._call("pcs_align_set_consensus", self._h, int(n_hypotheses), float(inlier_dist), int(seed))
+
+    def get_consensus(self):
+        """(n_hypotheses, inlier_dist, seed) in force."""
+        h, d, seed = self._ct.c_int(0), self._ct.c_double(0.0), self._ct.c_uint64(0)
+        self._call("pcs_align_get_consensus", self._h, self._ct.byref(h), self._ct.byref(d), self._ct.byref(seed))
+        return int(h.value), float(d.value), int(seed.value)
+
+    def run(self, model: str = "rigid", min_points: int = 3, rank_tol: float = 1e-10, group_lanes: int = 0, d_T: int | None = None,
+            stream: int | None = None):
+        """Queue the stages (asynchronous; handle-owned outputs, fetched with ``results()``)."""
+        self._call("pcs_align_run", self._h, ALIGN_MODEL_IDS[model], int(min_points), float(rank_tol), int(group_lanes), 0, self._addr(d_T), _stream_arg(stream))
+        self._own_T = d_T is None
+
+    def results(self):
+        """Wait for the last ``run``: (T (P, 3, 4) or None when the run wrote it to a caller buffer, scale (P,), info (P, 4) int32 =
+        [rows used, inliers, status, winning hypothesis], stats (P, 3) = [rms, score, conditioning], inlier (n,) bool, dist (n,))."""
+        n = self.n_problems
+        T = np.empty((n, 3, 4)) if getattr(self, "_own_T", True) else None
+        scale, info, stats = np.empty(n), np.empty((n, 4), dtype=np.int32), np.empty((n, 3))
+        inl, dist = np.zeros(self.n_rows, dtype=np.uint8), np.empty(self.n_rows)
+        self._call("pcs_align_results", self._h, self._ptr(T), self._ptr(scale), self._ptr(info), self._ptr(stats), self._ptr(inl), self._ptr(dist))
+        return T, scale, info, stats, inl.astype(bool), dist
+
+    def last_kernel_ms(self) -> dict:
+        """Device time of every stage of the last run, milliseconds by stage name (ALIGN_STAGES)."""
+        ms = (self._ct.c_float * len(ALIGN_STAGES))()
+        self._call("pcs_align_last_kernel_ms", self._h, ms)
+        return dict(zip(ALIGN_STAGES, (float(v) for v in ms)))
+
+
+_align_cache: dict = {}
+
+
+def _point_aligner(device: int) -> PointAligner:
+    return _cached_handle(_align_cache, int(device), lambda: PointAligner(device))
+
+
+def align_points(src, dst, start_inds=None, *, weights=None, model: str = "rigid", consensus: int = 0, inlier_dist=None, seed: int = 0,
+                 min_points: int = 3, rank_tol: float = 1e-10, group_lanes: int = 0, device: int = 0) -> Alignment:
+    """Register 3-D point sets on the device (include/pcs_hip.h pcs_align_run): per problem the rotation, translation and, for
+    ``model="similarity"``, scale with ``dst ~ scale * R @ src + t`` in the weighted least-squares sense — the reference's
+    ``n_estimate_rigid_transform`` (ch:727-762), batched, by Horn's unit-quaternion closed form.
+
+    ``src``, ``dst``: (n, 3) rows sorted by problem with ``start_inds`` (P + 1,), or (P, K, 3) stacks, or one (K, 3) problem
+    (``start_inds`` None).  A row with a non-finite coordinate or with weight 0 takes no part.  Planar sets and mirrored destinations
+    give proper rotations; collinear ones are refused (``status`` ALIGN_DEGENERATE, ``conditioning`` <= ``rank_tol``).
+
+    ``consensus`` > 0: that many hypotheses of three rows each per problem, scored by sum min(d^2, inlier_dist^2); the fit runs on the
+    rows within ``inlier_dist`` (units of dst, required) of the winner.  64 hypotheses find an all-inlier triple at 30 % outliers but for
+    a chance of (1 - 0.7^3)^64 = 2e-12.  The sampler is counter-based (``seed``): two calls agree bit for bit."""
+    global last_align_kernel_ms
+    code, H, dist, seed, min_points, tol, lanes = check_align_options(model, consensus, inlier_dist, seed, min_points, rank_tol, group_lanes)
+    x, y = np.asarray(src, dtype=np.float64), np.asarray(dst, dtype=np.float64)
+    if x.shape != y.shape or x.ndim not in (2, 3) or x.shape[-1] != 3:
+        raise ValueError("expected src and dst of one shape, (n, 3) or (P, K, 3)")
+    w = None if weights is None else np.asarray(weights, dtype=np.float64)
+    if start_inds is None:
+        P, K = (1, x.shape[0]) if x.ndim == 2 else x.shape[:2]
+        start = np.arange(P + 1, dtype=np.int64) * K
+    else:
+        if x.ndim != 2:
+            raise ValueError("start_inds goes with src and dst (n, 3)")
+        start = np.asarray(start_inds, dtype=np.int64)
+        if start.ndim != 1 or start.shape[0] < 1 or start[0] != 0 or start[-1] != x.shape[0] or np.any(np.diff(start) < 0):
+            raise ValueError("start_inds must run from 0 to n without decreasing")
+    x, y = x.reshape(-1, 3), y.reshape(-1, 3)
+    if w is not None:
+        if w.size != x.shape[0]:
+            raise ValueError(f"expected {x.shape[0]} weights, one per row")
+        w = w.reshape(-1)
+        if not np.all(np.isfinite(w)) or np.any(w < 0.0):
+            raise ValueError("weights must be finite and >= 0")
+    al = _point_aligner(device)
+    al.set_points(x, y, start, w)
+    al.set_consensus(H, dist, seed)   # the handle is shared: every call states its setting
+    al.run(model=model, min_points=min_points, rank_tol=tol, group_lanes=lanes)
+    T, scale, info, stats, inl, d = al.results()
+    last_align_kernel_ms = al.last_kernel_ms() if start.shape[0] > 1 else None
+    return Alignment(R=T[:, :, :3].copy(), t=T[:, :, 3].copy(), scale=scale, rms=stats[:, 0], status=info[:, 2], n_used=info[:, 0], n_inliers=info[:, 1],
+                     inliers=inl, conditioning=stats[:, 2], hypothesis=info[:, 3], score=stats[:, 1], distances=d, start=start)
+
+
+def register_target(points_by_image, template, **opts):
+    """The pose of a known target in every image from 3-D points of its features: ``points_by_image`` (I, K, 3), NaN where a feature
+    was not reconstructed, ``template`` (K, 3).  One registration per image over the finite rows (``align_points``; ``opts`` are its
+    options: weights (I, K), consensus, inlier_dist, min_points, ...), template -> image points.  -> poses (I, 6) = [rotvec, t], NaN
+    where the image's status is not ALIGN_OK.  ``register_target.last`` holds the ``Alignment`` of the last call."""
+    from .pose_seeding import pose_from_4x4, to_4x4
+
+    pts, tmpl = np.asarray(points_by_image, dtype=np.float64), np.asarray(template, dtype=np.float64)
+    if pts.ndim != 3 or pts.shape[2] != 3 or tmpl.shape != pts.shape[1:]:
+        raise ValueError("expected points_by_image (I, K, 3) and template (K, 3)")
+    if opts.get("model", "rigid") != "rigid":
+        raise ValueError("a target pose is rigid: model must be 'rigid'")
+    res = align_points(np.broadcast_to(tmpl, pts.shape), pts, **opts)
+    register_target.last = res
+    poses = np.full((pts.shape[0], 6), np.nan)
+    ok = res.status == ALIGN_OK
+    if np.any(ok):
+        poses[ok] = pose_from_4x4(to_4x4(np.concatenate([res.R[ok], res.t[ok][:, :, None]], axis=2)))
+    return poses
+
+
+def rig_pose_start_3d(dct, points, intr, ext, n_imgs: int, min_points: int = 6, device: int = 0, consensus: int = 0, inlier_dist=None,
+                      seed: int = 0) -> np.ndarray:
+    """A start (I, 6) for ``localise_target`` with the signature of ``rig_pose_start``, from 3-D points: every (image, key) feature that
+    two or more cameras of the rig see is triangulated (the grouping of ``multi_cam_triangulate``, ``nb_triangulate_full`` with the rig's
+    projection matrices), and every image's pose is one registration of the template onto its points (``register_target``): no
+    per-view PnP and no planar ambiguity.  NaN where an image has fewer than ``min_points`` triangulated features.  ``consensus`` /
+    ``inlier_dist`` (units of the template) / ``seed``: the consensus stage of ``align_points``."""
+    d = np.asarray(dct, dtype=np.float64)
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    K, E = np.asarray(intr, dtype=np.float64), np.asarray(ext, dtype=np.float64)
+    C = K.shape[0]
+    Kmat = np.zeros((C, 3, 3))
+    Kmat[:, 0, 0], Kmat[:, 0, 2], Kmat[:, 1, 1], Kmat[:, 1, 2], Kmat[:, 2, 2] = K[:, 0], K[:, 1], K[:, 2], K[:, 3], 1.0
+    by_image = np.full((int(n_imgs), pts.shape[0], 3), np.nan)
+    if d.shape[0]:
+        rec, start = group_reconstructable(d[np.lexsort((d[:, 0], d[:, 2], d[:, 1]))])   # a feature's rows side by side, by camera
+        if start.shape[0] > 1:
+            X = nb_triangulate_full(rec, Kmat @ E, start, Kmat, K[:, 4:9], device=device)
+            head = rec[start[:-1]]
+            by_image[head[:, 1].astype(np.int64), head[:, 2].astype(np.int64)] = X
+    return register_target(by_image, pts, min_points=max(3, int(min_points)), device=device, consensus=consensus, inlier_dist=inlier_dist, seed=seed)

@@ -33,13 +33,23 @@ def _table(detection_or_dct, points):
     return d, pts.reshape(-1, 3), None
 
 
-def find_target_poses(detection_or_dct, points, intr, ext, **opts) -> ch.ImagePoses:
+def find_target_poses(detection_or_dct, points, intr, ext, *, start: str = "pnp", **opts) -> ch.ImagePoses:
     """The target pose of every image (ft:50-82) -> ``compiled_helpers.ImagePoses``; ``opts`` are ``localise_target``'s
     (``n_imgs``, ``poses_init``, ``min_points``, ``max_iter``, ``ftol``, ``xtol``, ``gtol``, ``group_lanes``, ``return_residuals``,
-    ``device``, and ``loss`` / ``f_scale``: the robust loss the reference's ``least_squares`` call carries commented out)."""
+    ``device``, and ``loss`` / ``f_scale``: the robust loss the reference's ``least_squares`` call carries commented out).
+
+    ``start``: where the solve begins when ``poses_init`` is not given.  ``"pnp"`` (default) is ``localise_target``'s own start, the
+    best per-view PnP candidate (``compiled_helpers.rig_pose_start``); ``"triangulation"`` registers the template onto the features
+    that two or more cameras triangulate (``compiled_helpers.rig_pose_start_3d``): no planar ambiguity, for rigs whose cameras overlap."""
+    if start not in ("pnp", "triangulation"):
+        raise ValueError(f"start must be 'pnp' or 'triangulation', got {start!r}")
     d, pts, stated = _table(detection_or_dct, points)
     if stated is not None:
         opts.setdefault("n_imgs", stated)
+    if start == "triangulation" and opts.get("poses_init") is None and d.shape[0]:
+        n_imgs = opts.get("n_imgs")
+        n_imgs = int(d[:, 1].max()) + 1 if n_imgs is None else int(n_imgs)
+        opts["poses_init"] = ch.rig_pose_start_3d(d, pts, intr, ext, n_imgs, min_points=opts.get("min_points", 6), device=opts.get("device", 0))
     return ch.localise_target(d, pts, intr, ext, **opts)
 
 

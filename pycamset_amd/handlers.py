@@ -483,6 +483,68 @@ class SelfBundleHandler(TemplateBundleHandler):  # sbh:109-260
         feat_unfixed[: 3 * n_points][np.repeat(~self.visible_feature_mask, 3)] = False  # sbh:167-169: unseen features are fixed
         return feat_unfixed
 
+    def gauge_distance_scale(self, point_estimate) -> float:  # sbh:359-377
+        """The reference's scale of a self-calibrated target: the mean ratio of nominal to estimated distance over the pairs of
+        ``target.valid_map`` (n, 2), or, for ``valid_map`` True, over all pairs of visible features whose nominal distance is
+        ``target.square_size``.  (The reference's array branch calls a function it does not define, sbh:373; the pairs it names are taken.)"""
+        pts = np.asarray(point_estimate, dtype=np.float64).reshape((-1, 3))
+        ref = np.asarray(self.target.point_data, dtype=np.float64).reshape((-1, 3))
+        valid_map = getattr(self.target, "valid_map", True)
+        if isinstance(valid_map, (bool, np.bool_)):
+            if not valid_map:
+                raise ValueError("Target has given a valid map of False, which indicates no distance comparisons are valid.")
+            vis = np.nonzero(self.visible_feature_mask)[0]
+            a, b = np.triu_indices(vis.shape[0], k=1)
+            a, b = vis[a], vis[b]
+            keep = np.isclose(np.linalg.norm(ref[a] - ref[b], axis=1), self.target.square_size)
+            a, b = a[keep], b[keep]
+        elif isinstance(valid_map, np.ndarray) and valid_map.ndim == 2 and valid_map.shape[1] >= 2:
+            a, b = valid_map[:, 0].astype(np.int64), valid_map[:, 1].astype(np.int64)
+        else:
+            raise ValueError("The target.valid_map property either needs to be true, for all comparisons being valid, or a nx2 list of index pairs.")
+        if a.shape[0] == 0:
+            raise ValueError("no pair of features to compare distances over")
+        return float(np.mean(np.linalg.norm(ref[a] - ref[b], axis=1) / np.linalg.norm(pts[a] - pts[b], axis=1)))
+
+    def apply_gauge_transform(self, proj, extr, poses, point_estimate, *, scale: str = "similarity", consensus: int = 0, inlier_dist=None,
+                              seed: int = 0, device: int = 0):  # sbh:339-410
+        """Bring a self-calibration back to the nominal frame and scale of the target: the similarity that best fits the estimated
+        features to ``target.point_data`` over the visible ones, applied so that the calibration is preserved — points X' = U (s X),
+        poses U P U^-1 and extrinsics E U^-1 with their translations times s (sbh:378-409), intrinsics untouched — so every residual
+        stays what it was, and a first pose that is the identity stays the identity.
+
+        ``scale="similarity"``: s, R and t from one registration on the device (``compiled_helpers.align_points``, the Umeyama scale);
+        ``"distances"``: the reference's s (``gauge_distance_scale``) and a rigid registration of the scaled points.  ``consensus`` /
+        ``inlier_dist`` / ``seed``: the consensus stage of the registration, against a few features that moved.  Returns new arrays
+        (proj, extr (C, 6), poses (I, 6), points (K, 3)); ValueError when the registration is refused, where the reference logs and
+        returns the identity."""
+        from . import compiled_helpers as ch
+        from .pose_seeding import pose_from_4x4, pose_to_4x4, rigid_inverse
+
+        if scale not in ("similarity", "distances"):
+            raise ValueError(f"scale must be 'similarity' or 'distances', got {scale!r}")
+        pts = np.array(point_estimate, dtype=np.float64).reshape((-1, 3))
+        ref = np.asarray(self.target.point_data, dtype=np.float64).reshape((-1, 3))
+        vm = np.asarray(self.visible_feature_mask, dtype=bool)
+        opts = {"consensus": consensus, "inlier_dist": inlier_dist, "seed": seed, "device": device}
+        if scale == "distances":
+            s = self.gauge_distance_scale(pts)
+            al = ch.align_points(s * pts[vm], ref[vm], model="rigid", **opts)
+        else:
+            al = ch.align_points(pts[vm], ref[vm], model="similarity", **opts)
+            s = float(al.scale[0])
+        if al.status[0] != ch.ALIGN_OK:
+            raise ValueError(f"apply_gauge_transform: the registration onto the nominal target was refused (status {int(al.status[0])}, "
+                             f"{int(al.n_used[0])} features used)")
+        self.gauge_alignment = al
+        U = np.eye(4)
+        U[:3, :3], U[:3, 3] = al.R[0], al.t[0]
+        Ui = rigid_inverse(U)
+        P, E = pose_to_4x4(np.asarray(poses, dtype=np.float64)), pose_to_4x4(np.asarray(extr, dtype=np.float64))
+        P[..., :3, 3] *= s
+        E[..., :3, 3] *= s
+        return proj, pose_from_4x4(E @ Ui), pose_from_4x4(U @ P @ Ui), s * pts @ U[:3, :3].T + U[:3, 3]
+
 
 class FreePointBundleHandler(TemplateBundleHandler):  # fph:102-201
     """Classic bundle adjustment of world points without a target pose (chain F)."""
@@ -497,7 +559,9 @@ class FreePointBundleHandler(TemplateBundleHandler):  # fph:102-201
         (``pose_seeding.seed_scene``: two-view consensus, triangulation, resection in rounds; the reference has no such start,
         fph:235).  Intrinsics are found as for the other seedings (``intr``, the camset's, or the planar estimate); ``scene_opts``
         reach ``seed_scene`` (``baseline``, ``consensus``, ``inlier_px``, ``seed``, ``min_points``, ``resect_opts``, ``tri_opts``, and
-        ``two_view_solver="five-point"`` / ``two_view_refine`` for a scene that is mostly one plane),
+        ``two_view_solver="five-point"`` / ``two_view_refine`` for a scene that is mostly one plane); ``scene_opts["control_points"]``
+        (K, 3), NaN where unknown, brings the seed into the frame and scale of those points (``pose_seeding.align_scene``, with
+        ``scene_opts["align_opts"]`` as its options): fixed extrinsics must then be given in THAT frame;
         ``ref_cam`` comes from ``options["ref_cam"]``.  The world is ``ref_cam``'s camera frame and the first pair's baseline has
         length ``baseline``: fixed extrinsics must be given in that gauge.  The seed is kept on ``scene_seed``.  ValueError names the
         cameras and keys with a free entry that got no seed.  Every other ``seeding`` is ``TemplateBundleHandler.calc_initial_params``,
@@ -506,8 +570,12 @@ class FreePointBundleHandler(TemplateBundleHandler):  # fph:102-201
             if scene_opts is not None:
                 raise ValueError("scene_opts belongs to seeding='scene'")
             return super().calc_initial_params(intr, seeding=seeding, **kw)
-        from .pose_seeding import seed_scene
+        from .pose_seeding import align_scene, seed_scene
 
+        scene_opts = dict(scene_opts or {})
+        control_points, align_opts = scene_opts.pop("control_points", None), scene_opts.pop("align_opts", None)
+        if align_opts is not None and control_points is None:
+            raise ValueError("scene_opts['align_opts'] belongs to scene_opts['control_points']")
         unknown = set(kw) - {"intrinsics_consensus"}
         if unknown:
             raise ValueError(f"seeding='scene' takes intr, scene_opts and intrinsics_consensus, not {sorted(unknown)}")
@@ -515,7 +583,9 @@ class FreePointBundleHandler(TemplateBundleHandler):  # fph:102-201
         bp = self.bundlePrimitive
         n_cams = bp.intr.shape[0]
         intr = self._initial_intrinsics(intr, self.problem_opts.get("intrinsics_consensus", 0) if cons is None else cons)
-        seed = seed_scene(self._flat_detections(), intr, n_cams, ref_cam=self.problem_opts.get("ref_cam", 0), **dict(scene_opts or {}))
+        seed = seed_scene(self._flat_detections(), intr, n_cams, ref_cam=self.problem_opts.get("ref_cam", 0), **scene_opts)
+        if control_points is not None:
+            seed = align_scene(seed, control_points, **dict(align_opts or {}))
         self.scene_seed = seed
         points = np.full((self.flat_point_data.shape[0] // 3, 3), np.nan)
         points[: seed.points.shape[0]] = seed.points

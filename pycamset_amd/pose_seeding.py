@@ -479,3 +479,38 @@ def seed_scene(dct, intr, n_cams: int, *, ref_cam: int = 0, baseline: float = 1.
     M[frame] = np.eye(4)
     return SceneSeed(extr=pose_from_4x4(M), points=points, placed=placed, round_of_camera=round_of, n_views=n_views, rms=rms, first_pair=(a, b),
                      frame_cam=frame, two_view=tv)
+
+
+def align_scene(seed: SceneSeed, reference_points, *, model: str = "similarity", **opts) -> SceneSeed:
+    """Bring a seeded scene into the frame and scale of a few known points: ``reference_points`` (K, 3) holds the surveyed position of
+    every key that has one and NaN elsewhere.  One registration on the device (``compiled_helpers.align_points``; ``opts`` are its
+    options, e.g. ``consensus=64, inlier_dist=...`` against wrong control points) gives X' = s R X + t over the keys that are both
+    triangulated and known; the points move to X' and every placed camera gets R_c' = R_c R', t_c' = s t_c - R_c' t, so that a point
+    in a camera's frame is s times what it was and every reprojection stays where it is.  ``model="rigid"`` keeps the seed's scale
+    (s = 1).  ``frame_cam`` becomes -1: the world is no camera's frame any more.  ValueError when the registration is refused
+    (fewer than ``min_points`` common keys, collinear control points); the ``Alignment`` is kept on the result as ``alignment``."""
+    from dataclasses import replace
+
+    from . import compiled_helpers as ch
+
+    ref = np.asarray(reference_points, dtype=np.float64)
+    pts = np.asarray(seed.points, dtype=np.float64)
+    if ref.ndim != 2 or ref.shape[1] != 3 or ref.shape[0] > pts.shape[0]:
+        raise ValueError(f"expected reference_points (K, 3) with K <= {pts.shape[0]} keys, NaN where unknown")
+    full = np.full_like(pts, np.nan)
+    full[: ref.shape[0]] = ref
+    al = ch.align_points(pts, full, model=model, **opts)
+    if al.status[0] != ch.ALIGN_OK:
+        names = {ch.ALIGN_TOO_FEW: "too few keys are both triangulated and known", ch.ALIGN_DEGENERATE: "the control points are collinear",
+                 ch.ALIGN_NONFINITE: "no key is both triangulated and known", ch.ALIGN_NO_CONSENSUS: "too few control points agree"}
+        raise ValueError(f"align_scene: {names[int(al.status[0])]} ({int(al.n_used[0])} rows used)")
+    s, R, t = float(al.scale[0]), al.R[0], al.t[0]
+    M = pose_to_4x4(seed.extr)
+    placed = np.asarray(seed.placed, dtype=bool)
+    Rc = M[:, :3, :3] @ R.T
+    M[:, :3, 3] = s * M[:, :3, 3] - Rc @ t
+    M[:, :3, :3] = Rc
+    extr = np.where(placed[:, None], pose_from_4x4(np.where(placed[:, None, None], M, np.nan)), np.nan)
+    out = replace(seed, extr=extr, points=s * pts @ R.T + t, frame_cam=-1)
+    out.alignment = al
+    return out
