@@ -962,6 +962,66 @@ int pcs_align_results(pcs_point_aligner *p, double *T, double *scale, int32_t *i
 int pcs_align_last_kernel_ms(pcs_point_aligner *p, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * A calibration applied to points and images: rays, undistortion and rectified remap (csrc/ba_imagemap.hpp).  Since
+ * pcs_version() 122.
+ * Replaces: nb_undistort_arr / nb_distort (optimisation/compiled_helpers.py:373-490); sensor_map / vector_cam_points
+ *           (utils/general_utils.py:432-483) and Camera._compute_world_sensor_map / im_to_world_ray (cameras/camera.py:162-177, :460-493);
+ *           Camera.undistort (cameras/camera.py:451-458) and undistort_im / remap_im / rectify_camera_images
+ *           (reconstruction/reconstruction_utils.py:12-107), i.e. cv2.undistort, cv2.initUndistortRectifyMap and cv2.remap.
+ * Points, maps and images are DEVICE buffers of the caller, used in place; every call is queued on `stream` (NULL = the handle's stream).
+ * All coordinate arithmetic is FP64.  Every argument is checked on the host before the device is touched (PCS_ERR_ARG, or PCS_ERR_STATE
+ * for a call that needs cameras or extrinsics that were not set); pcs_last_error names the argument.
+ *   pcs_imap_create          a handle on `device` (no counterpart)
+ *   pcs_imap_destroy         frees the handle (no counterpart)
+ *   pcs_imap_set_cameras     host arrays, copied: intr (n_cams, 9) = [fx, cx, fy, cy, k0, k1, p0, p1, k2] as for pcs_pnp_set_cameras, finite
+ *                            with non-zero focal lengths; ext (n_cams, 12) world -> camera rows [R | t] as for pcs_rigpose_set_extrinsics,
+ *                            or NULL (Camera.intrinsic / distortion_coefs / extrinsic).  Resets the view.
+ *   pcs_imap_set_view        the new camera of pcs_imap_build_maps and of the fused remap, per camera: R_new (n_cams, 9) row-major, the
+ *                            rectifying rotation R of cv2.initUndistortRectifyMap (source camera frame -> new frame), NULL = identity;
+ *                            K_new (n_cams, 4) = [fx, cx, fy, cy], NULL = the camera's own, which is cv2.undistort(img, K, d, None, K).
+ *   pcs_imap_points          one thread per point.  d_in (n, 2) pixels; d_cam (n) int32 camera per row, or NULL = cam_all for every row; a
+ *                            row whose camera lies outside the table gives NaN.  mode PCS_IMAP_UNDISTORT: nb_undistort_arr's fixed point,
+ *                            `iters` steps (5 in the reference; 0 .. 100), d_out (n, 2).  PCS_IMAP_DISTORT: nb_distort, d_out (n, 2).
+ *                            PCS_IMAP_RAY: vector_cam_points — undistort (unless PCS_IMAP_NO_DISTORT), K^-1, z = 1 or unit length
+ *                            (PCS_IMAP_NORMALISED), camera frame or rotated to the world by R_e^T (PCS_IMAP_WORLD), d_out (n, 3).
+ *   pcs_imap_rays            sensor_map / world_sensor_map of camera `cam`: every pixel (x, y) of a width x height sensor through the ray
+ *                            path, d_out (height, width, 3) in image order, out_dtype PCS_F64 or PCS_F32 (the FP64 result rounded once).
+ *                            With d_depth (height, width; depth_dtype PCS_F64 or PCS_F32) the output is position + ray * depth,
+ *                            im_to_world_ray(depth_im=) for the whole image (position = 0 in the camera frame); a depth that is not
+ *                            finite gives three NaNs.
+ *   pcs_imap_build_maps      cv2.initUndistortRectifyMap for camera `cam` and its view: per destination pixel X = R_new^T K_new^-1 (u, v, 1),
+ *                            x = X / Z, y = Y / Z, forward distortion, the camera's K; d_out (2, height, width), plane 0 the source x,
+ *                            plane 1 the source y, PCS_F32 or PCS_F64.  Z <= 0 gives NaN.
+ *   pcs_imap_remap           cv2.remap, batched: n_img (<= 65535) images d_src (n_img, src_height, src_pitch BYTES) -> d_dst (n_img,
+ *                            dst_height, dst_pitch BYTES), interleaved channels 1, 3 or 4, dtype PCS_IMAP_U8 or PCS_IMAP_F32.  cams (n_img) is
+ *                            a HOST array: the camera of every image.  d_map NULL: FUSED, the coordinate of pcs_imap_build_maps is computed
+ *                            in registers and no map is written or read.  Otherwise MAPPED: d_map (n_maps, 2, dst_height, dst_width) of
+ *                            map_dtype PCS_F32 or PCS_F64, and image i reads map cams[i].  interpolation: PCS_IMAP_NEAREST (ties to even),
+ *                            PCS_IMAP_BILINEAR, PCS_IMAP_BICUBIC (a = -0.75, cv2.INTER_CUBIC).  A tap outside the source takes border[c]
+ *                            (border: `channels` host values, NULL = 0; BORDER_CONSTANT); where no tap lies inside, the value is the
+ *                            border.  floor, not truncation, for negative coordinates; exact FP64 weights; PCS_IMAP_U8 results are rounded
+ *                            half-to-even and saturated (OpenCV's 1/32-pixel weight tables are not reproduced).  d_valid (n_img,
+ *                            dst_height, dst_width) uint8 or NULL: 1 where every tap lay inside the source.
+ *   pcs_imap_last_kernel_ms  device time of the handle's last launch (no counterpart)
+ */
+typedef struct pcs_image_mapper pcs_image_mapper;
+enum { PCS_IMAP_UNDISTORT = 0, PCS_IMAP_DISTORT = 1, PCS_IMAP_RAY = 2 };
+enum { PCS_IMAP_NORMALISED = 1, PCS_IMAP_WORLD = 2, PCS_IMAP_NO_DISTORT = 4 };
+enum { PCS_IMAP_NEAREST = 0, PCS_IMAP_BILINEAR = 1, PCS_IMAP_BICUBIC = 2 };
+enum { PCS_IMAP_U8 = 0, PCS_IMAP_F32 = 1 };
+int pcs_imap_create(pcs_image_mapper **out, int device);
+int pcs_imap_destroy(pcs_image_mapper *p);
+int pcs_imap_set_cameras(pcs_image_mapper *p, int64_t n_cams, const double *intr, const double *ext);
+int pcs_imap_set_view(pcs_image_mapper *p, const double *R_new, const double *K_new);
+int pcs_imap_points(pcs_image_mapper *p, int mode, int64_t n, const int32_t *d_cam, int cam_all, const double *d_in, int iters, int flags, double *d_out, void *stream);
+int pcs_imap_rays(pcs_image_mapper *p, int cam, int width, int height, int flags, int iters, const void *d_depth, int depth_dtype, void *d_out, int out_dtype, void *stream);
+int pcs_imap_build_maps(pcs_image_mapper *p, int cam, int width, int height, void *d_out, int out_dtype, void *stream);
+int pcs_imap_remap(pcs_image_mapper *p, int64_t n_img, const int32_t *cams, const void *d_src, int src_width, int src_height, int channels, int dtype, int64_t src_pitch,
+                   void *d_dst, int dst_width, int dst_height, int64_t dst_pitch, const void *d_map, int map_dtype, int64_t n_maps, int interpolation, const double *border,
+                   uint8_t *d_valid, void *stream);
+int pcs_imap_last_kernel_ms(pcs_image_mapper *p, float *kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

@@ -48,6 +48,11 @@ TWOVIEW_EIGHT_POINT, TWOVIEW_FIVE_POINT = 0, 1
 # include/pcs_hip.h PCS_ALIGN_*: per-problem status of the point-set registration, and its models
 ALIGN_OK, ALIGN_TOO_FEW, ALIGN_DEGENERATE, ALIGN_NONFINITE, ALIGN_NO_CONSENSUS = 0, 1, 2, 3, 4
 ALIGN_MODEL_IDS = {"rigid": 0, "similarity": 1}
+# include/pcs_hip.h PCS_IMAP_*: point modes, ray flags, interpolations and image types of the image mapper
+IMAP_UNDISTORT, IMAP_DISTORT, IMAP_RAY = 0, 1, 2
+IMAP_NORMALISED, IMAP_WORLD, IMAP_NO_DISTORT = 1, 2, 4
+IMAP_INTERP_IDS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+IMAP_DTYPE_IDS = {"uint8": 0, "float32": 1}
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -190,6 +195,16 @@ SYMBOLS = {
     "pcs_align_run": (c_int, [_P, c_int, c_int, c_double, c_int, c_int, _P, _P]),
     "pcs_align_results": (c_int, [_P, POINTER(c_double), POINTER(c_double), POINTER(c_int32), POINTER(c_double), POINTER(c_uint8), POINTER(c_double)]),
     "pcs_align_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_imap_create": (c_int, [POINTER(_P), c_int]),
+    "pcs_imap_destroy": (c_int, [_P]),
+    "pcs_imap_set_cameras": (c_int, [_P, c_int64, POINTER(c_double), POINTER(c_double)]),
+    "pcs_imap_set_view": (c_int, [_P, POINTER(c_double), POINTER(c_double)]),
+    "pcs_imap_points": (c_int, [_P, c_int, c_int64, _P, c_int, _P, c_int, c_int, _P, _P]),
+    "pcs_imap_rays": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P]),
+    "pcs_imap_build_maps": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P]),
+    "pcs_imap_remap": (c_int, [_P, c_int64, POINTER(c_int32), _P, c_int, c_int, c_int, c_int, c_int64, _P, c_int, c_int, c_int64, _P, c_int, c_int64, c_int,
+                               POINTER(c_double), _P, _P]),
+    "pcs_imap_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),
