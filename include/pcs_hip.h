@@ -1022,6 +1022,62 @@ int pcs_imap_remap(pcs_image_mapper *p, int64_t n_img, const int32_t *cams, cons
 int pcs_imap_last_kernel_ms(pcs_image_mapper *p, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dense stereo on a rectified pair: block matching, disparity to points, compaction (csrc/ba_stereo.hpp).  Since
+ * pcs_version() 123.
+ * Replaces: the second half of stereo_reconstruct (reconstruction/reconstruction_utils.py:170-223): cv2.StereoBM_create(...).compute / 16,
+ *           cv2.reprojectImageTo3D, and the NaN / inf / depth mask of depth_image_ptcloud_mask (:24-38) and disparity_to_ptcld (:110-137)
+ *           with the masked cloud and the left image's grey value per point.
+ * OpenCV's StereoBM is NOT reproduced bit for bit (its NORMALIZED_RESPONSE prefilter, its SIMD rounding and its dispDescale are its own).
+ * The rule is all integers: two runs, and any tiling, give the same bits.  tests/stereo_reference.py states it in NumPy.
+ *   prefilter (cap > 0)  P = clip(g, -cap, cap) + cap, g the 3 x 3 horizontal Sobel response with the rows clamped; columns 0 and W - 1
+ *                        are cap.  cap = 0: P = I (texture_threshold must then be 0).
+ *   cost                 C(y, x, d) = sum over the block x block window of |P_L(y + j, x + i) - P_R(y + j, x + i - d)|, d = u_L - u_R in
+ *                        [min_disp, min_disp + num_disp - 1]; defined where both windows lie inside the image.
+ *   strict pixels        a left pixel competes only if C is defined for every d of the range; every other pixel has PCS_STEREO_NOT_STRICT.
+ *   winner               d* the smallest d of the smallest cost C*.
+ *   PCS_STEREO_TEXTURE   (cap > 0) sum over the window of |P_L - cap| < texture_threshold.
+ *   PCS_STEREO_UNIQUENESS  (uniqueness_ratio u > 0) some d with |d - d*| >= 2 has 100 C(d) <= (100 + u) C*.
+ *   PCS_STEREO_LEFT_RIGHT  (lr_max_diff >= 0) |d* - d_R(y, x - d*)| > lr_max_diff, d_R the winner anchored in the right image over the d
+ *                        for which the cost is defined (the range is clamped per pixel).
+ *   PCS_STEREO_VALIDITY  (validity planes) valid_left(y, x) = 0 or valid_right(y, x - d*) = 0.
+ *   sub-pixel            m = C(d* - 1), p = C(d* + 1), den = 2 (m + p - 2 C*); 0 when d* is an end of the range or den = 0, else
+ *                        floor((32 (m - p) + den) / (2 den)): 16 (m - p) / den rounded half up, in [-8, 8].
+ *   pcs_stereo_create    a handle on `device` (no counterpart); it owns the workspace: the two prefiltered planes, the right-anchored
+ *                        disparity and the compaction's counts, O(n width height) bytes — the cost volume is never stored
+ *   pcs_stereo_destroy   frees the handle (no counterpart)
+ *   pcs_stereo_match     StereoBM.compute over n (<= 32767) pairs: d_left / d_right (n, height, pitch BYTES) 8-bit single channel;
+ *                        min_disp in [-1024, 1024], num_disp in [1, 1024], block odd in [3, 31], prefilter_cap in [0, 63],
+ *                        texture_threshold >= 0, uniqueness_ratio in [0, 100], lr_max_diff >= -1 (-1: no left-right pass);
+ *                        d_valid_left / d_valid_right (n, height, width) uint8 or both NULL.  d_disp (n, height, width) int16 = 16 d* +
+ *                        offset where the status is 0 and 16 (min_disp - 1) elsewhere (cv2's convention); d_cost int32 or NULL: C* on
+ *                        strict pixels, -1 elsewhere; d_status uint8 or NULL: the bits above, each evaluated on every strict pixel.
+ *   pcs_stereo_reproject cv2.reprojectImageTo3D and the reference's mask: (X, Y, Z, Wh) = Q (x, y, disp / 16, 1) in FP64, point =
+ *                        (X, Y, Z) / Wh.  Q: HOST (n_Q, 16) row-major, n_Q = 1 (one for all) or n.  mask = disp != invalid_disp (a value
+ *                        outside int16: every disparity counts) and all three coordinates finite and z_lo <= z <= z_hi (-inf / +inf: no
+ *                        bound).  T: HOST 3 x 4 rigid transform applied to the masked points (the z of the mask is the one before it), or
+ *                        NULL.  d_points (n, height, width, 3) of dtype PCS_F64 or PCS_F32 (the FP64 result rounded once), three NaNs where
+ *                        the mask is 0; d_mask (n, height, width) uint8; d_counts (n) int64 on the DEVICE or NULL: the mask's sum per pair.
+ *   pcs_stereo_compact   the masked cloud: the points with mask != 0 of pair 0, then pair 1, ..., each in row-major pixel order, packed into
+ *                        d_out_points (room for every pixel), with d_values (n, height, values_pitch BYTES; the left image) into d_out_values
+ *                        (both or neither); d_counts (n) int64 on the DEVICE.  Stable, without atomics.
+ *   pcs_stereo_last_kernel_ms  device time of the handle's last call (no counterpart)
+ * Every argument is checked on the host before the device is touched (PCS_ERR_ARG; pcs_last_error names the argument); the handle is
+ * looked at last.  All buffers are DEVICE buffers of the caller unless marked HOST; calls are queued on `stream` (NULL = the handle's).
+ */
+typedef struct pcs_stereo_matcher pcs_stereo_matcher;
+enum { PCS_STEREO_NOT_STRICT = 1, PCS_STEREO_TEXTURE = 2, PCS_STEREO_UNIQUENESS = 4, PCS_STEREO_LEFT_RIGHT = 8, PCS_STEREO_VALIDITY = 16 };
+int pcs_stereo_create(pcs_stereo_matcher **out, int device);
+int pcs_stereo_destroy(pcs_stereo_matcher *p);
+int pcs_stereo_match(pcs_stereo_matcher *p, int64_t n, int width, int height, const uint8_t *d_left, int64_t left_pitch, const uint8_t *d_right, int64_t right_pitch, int min_disp,
+                     int num_disp, int block, int prefilter_cap, int texture_threshold, int uniqueness_ratio, int lr_max_diff, const uint8_t *d_valid_left,
+                     const uint8_t *d_valid_right, int16_t *d_disp, int32_t *d_cost, uint8_t *d_status, void *stream);
+int pcs_stereo_reproject(pcs_stereo_matcher *p, int64_t n, int width, int height, const int16_t *d_disp, int invalid_disp, const double *Q, int64_t n_Q, double z_lo, double z_hi,
+                         const double *T, void *d_points, int dtype, uint8_t *d_mask, int64_t *d_counts, void *stream);
+int pcs_stereo_compact(pcs_stereo_matcher *p, int64_t n, int width, int height, const void *d_points, int dtype, const uint8_t *d_mask, const uint8_t *d_values,
+                       int64_t values_pitch, void *d_out_points, uint8_t *d_out_values, int64_t *d_counts, void *stream);
+int pcs_stereo_last_kernel_ms(pcs_stereo_matcher *p, float *kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

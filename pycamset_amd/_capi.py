@@ -53,6 +53,8 @@ IMAP_UNDISTORT, IMAP_DISTORT, IMAP_RAY = 0, 1, 2
 IMAP_NORMALISED, IMAP_WORLD, IMAP_NO_DISTORT = 1, 2, 4
 IMAP_INTERP_IDS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 IMAP_DTYPE_IDS = {"uint8": 0, "float32": 1}
+# include/pcs_hip.h PCS_STEREO_*: status bits of the stereo matcher
+STEREO_NOT_STRICT, STEREO_TEXTURE, STEREO_UNIQUENESS, STEREO_LEFT_RIGHT, STEREO_VALIDITY = 1, 2, 4, 8, 16
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -205,6 +207,12 @@ SYMBOLS = {
     "pcs_imap_remap": (c_int, [_P, c_int64, POINTER(c_int32), _P, c_int, c_int, c_int, c_int, c_int64, _P, c_int, c_int, c_int64, _P, c_int, c_int64, c_int,
                                POINTER(c_double), _P, _P]),
     "pcs_imap_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_stereo_create": (c_int, [POINTER(_P), c_int]),
+    "pcs_stereo_destroy": (c_int, [_P]),
+    "pcs_stereo_match": (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "pcs_stereo_reproject": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, POINTER(c_double), c_int64, c_double, c_double, POINTER(c_double), _P, c_int, _P, _P, _P]),
+    "pcs_stereo_compact": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P]),
+    "pcs_stereo_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),
