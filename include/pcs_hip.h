@@ -500,7 +500,14 @@ int pcs_kernel_ms_samples(pcs_engine *h, int64_t capacity, float *slab_prep_ms, 
  * it, not after every step, for work on the engine's own or the default stream; 2: on caller streams too — the caller then keeps
  * the stream alive until it resets the option, which records what is pending; 0: after every enqueue), "timing_every" (0: no start / stop
  * events at all, neither around evaluations nor around normal-equations builds),
- * "matfree_lds", "xcd_remap", "waves_per_wg", "pack_indices", "normal_rows", "normal_imgkey_product",
+ * "matfree_lds" (how the transposed pcs_matfree operators — ops 1 to 4 — add up their n_params sums.  1, the default: in
+ * workgroup-private LDS accumulators, flushed with one global f64 atomic per non-zero entry and workgroup — taken whenever they fit,
+ * i.e. up to 13 740 parameters (150 KiB with the four reduction panels); larger strings take the other form on their own.  0: always
+ * wave sums and global f64 atomics, no LDS (an A/B switch, and the way to test the form large strings get).  Same results up to the
+ * order of the sums; op 0, J v, has no sums and ignores it),
+ * "pack_indices" (1, the default: one packed 32-bit index word per detection where camera, image and key fit; 0: three int32 arrays;
+ * takes effect at the next pcs_set_detections*),
+ * "xcd_remap", "waves_per_wg", "normal_rows", "normal_imgkey_product",
  * "normal_imgkey_wgs_per_cu", "normal_sort_tables"; "normal_debug" is a bit mask of profiling switches of pcs_normal_equations — phases
  * or whole passes are skipped and the results are wrong while it is non-zero); see DESIGN.md.
  * Unknown keys -> PCS_ERR_ARG. */

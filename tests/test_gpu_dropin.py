@@ -267,7 +267,8 @@ def test_run_bundle_adjustment_caller_with_both_solvers():
 @pytest.mark.parametrize("chain", ["template", "self", "free"])
 def test_matrix_free_products_match_sparse_products_of_the_oracle_jacobian(chain):
     """J v, J^T u, J^T J v, diag(J^T J), J^T r and the cost, against scipy.sparse products of the
-    oracle's Jacobian.  f64 atomics reorder the sums: |a - b| <= 1e-10 * max|ref|."""
+    oracle's Jacobian.  f64 atomics reorder the sums: |a - b| <= 1e-10 * max|ref|.  tests/test_gpu_matfree.py holds the same
+    products to a bound per entry (tests/matfree_reference.py), at every tile shape and in both accumulator forms."""
     from pycamset_amd.engine import Engine
     rig = synthetic.config_rig(1)
     ps = orc.build_param_list(*H.chain_slabs(rig, chain))
