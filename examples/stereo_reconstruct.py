@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """A calibrated pair to a point cloud on the device: the reference's ``stereo_reconstruct`` (reconstruction/reconstruction_utils.py:
-170-223) with pycamset_amd — rectify both images in one fused remap each, match blocks, reproject, mask by depth, compact.
+170-223) with pycamset_amd — rectify both images in one fused remap each, match blocks (or, with ``--method sgm``, the reference's
+``matlab=True`` branch: semi-global matching on a census cost), reproject, mask by depth, compact.
 
 The scene is synthetic so that the example needs no files: an analytically textured plane one metre in front of two distorted cameras
 12 cm apart.  Every pixel's ray (``imaging.pixel_rays``) is intersected with the plane and the texture is evaluated there.
 
-    python examples/stereo_reconstruct.py
+    python examples/stereo_reconstruct.py [--method sgm]
 """
+import argparse
 import sys
 from pathlib import Path
 
@@ -42,12 +44,16 @@ def render(K, E):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--method", choices=("block", "sgm"), default="block")
+    method = ap.parse_args().method
     Ea, Eb = extrinsics()
     A, B = render(INTR[0], Ea), render(INTR[1], Eb)
-    (points, grey), = stereo.stereo_reconstruct(A, B, INTR[0], Ea, INTR[1], Eb, num_disp=64, block=15, depth_range=(0.2, 3.0), frame="world", lr_max_diff=1)
+    options = dict(block=15) if method == "block" else dict(census=(9, 7), p1=8, p2=32, paths=8)
+    (points, grey), = stereo.stereo_reconstruct(A, B, INTR[0], Ea, INTR[1], Eb, num_disp=64, depth_range=(0.2, 3.0), frame="world", lr_max_diff=1, method=method, **options)
     _, _, Q, disp, min_disp = stereo.stereo_reconstruct.last
     ok = disp != 16 * (min_disp - 1)
-    print(f"{W} x {H} pair: {int(ok.sum())} of {ok.size} pixels matched, median disparity {np.median(disp[ok]) / 16:.2f} px")
+    print(f"{W} x {H} pair, {method}: {int(ok.sum())} of {ok.size} pixels matched, median disparity {np.median(disp[ok]) / 16:.2f} px")
     step = Z0 * Z0 / (Q[2, 3] / abs(Q[3, 2]))
     err = np.abs(points[:, 2] - Z0)
     print(f"{len(points)} points in the world; distance from the plane Z = {Z0}: median {np.median(err):.5f}, 95 % {np.quantile(err, 0.95):.5f} "

@@ -1085,6 +1085,48 @@ int pcs_stereo_compact(pcs_stereo_matcher *p, int64_t n, int width, int height, 
 int pcs_stereo_last_kernel_ms(pcs_stereo_matcher *p, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Semi-global matching on a rectified pair: census cost, 4 / 8-path aggregation (csrc/ba_stereo_sgm.hpp).  Since
+ * pcs_version() 124.
+ * Replaces: matlab_stereo (reconstruction/reconstruction_utils.py:140-167), the matlab=True branch of stereo_reconstruct, which starts a
+ *           MATLAB engine per call for disparitySGM(im0, im1, 'DisparityRange', ..., 'UniquenessThreshold', ...).
+ * Neither MATLAB's disparitySGM nor OpenCV's StereoSGBM is reproduced bit for bit.  The rule is all integers: two runs, any order of the
+ * directions and any chunking of the batch give the same bits.  tests/sgm_reference.py states it in NumPy.  Handle, status bits, the
+ * int16 disparity in sixteenths, pcs_stereo_reproject and pcs_stereo_compact are those of the block matcher above.  There is no
+ * prefilter: the census runs on the raw bytes.
+ *   census               window census_w x census_h (both odd, >= 3, census_w census_h - 1 <= 64), rw = census_w / 2, rh = census_h / 2.
+ *                        The descriptor of a pixel whose window lies inside the image has one bit per window position other than the
+ *                        centre: 1 iff that neighbour is LESS THAN the centre.
+ *   cost                 C(y, x, d) = popcount(c_L(y, x) xor c_R(y, x - d)), d = u_L - u_R in [min_disp, min_disp + num_disp - 1], defined
+ *                        where both windows lie inside their images; 0 <= C <= 64.
+ *   strict pixels        a left pixel competes only if C is defined for every d of the range: rows rh .. H - 1 - rh, columns
+ *                        rw + max(d_max, 0) .. W - 1 - rw + min(min_disp, 0).  Every other pixel has PCS_STEREO_NOT_STRICT, disparity
+ *                        16 (min_disp - 1) and cost -1.  An empty rectangle is a valid call.
+ *   aggregation          directions r = (0, +-1), (+-1, 0) (paths = 4) and (+-1, +-1) (paths = 8).  At a strict pixel p: if p - r is not
+ *                        strict the path starts here, L_r(p, d) = C(p, d); else, with M = min_j L_r(p - r, j),
+ *                        L_r(p, d) = C(p, d) + min(L_r(p - r, d), L_r(p - r, d - 1) + P1, L_r(p - r, d + 1) + P1, M + P2) - M,
+ *                        a term whose disparity leaves the range omitted.  S(p, d) = sum over r of L_r(p, d).  0 <= P1 <= P2 <= 1023,
+ *                        so L_r <= 64 + P2 <= 1087 and S <= 8 * 1087 < 2^14: S is held in 16 bits.
+ *   winner               d* the smallest d of the smallest S; cost = S(d*).
+ *   PCS_STEREO_UNIQUENESS  (uniqueness_ratio u > 0) some d with |d - d*| >= 2 has 100 S(d) <= (100 + u) S*.
+ *   PCS_STEREO_LEFT_RIGHT  (lr_max_diff >= 0) |d* - d_R(y, x - d*)| > lr_max_diff, d_R(y, x2) the smallest d minimising S(y, x2 + d, d) over
+ *                        the d for which (y, x2 + d) is strict: read from the SAME S, there is no second aggregation.
+ *   PCS_STEREO_VALIDITY  as above.  PCS_STEREO_TEXTURE is never set: a census has no texture measure.
+ *   sub-pixel            the block matcher's floor division on S(d* - 1), S*, S(d* + 1).
+ *   pcs_stereo_sgm       over n (<= 32767) pairs; min_disp in [-1024, 1024], num_disp in [1, 256], p1 / p2 the penalties, paths 4 or 8,
+ *                        uniqueness_ratio in [0, 100], lr_max_diff >= -1; images, validity planes and the three outputs as in
+ *                        pcs_stereo_match.  The matching-cost volume is never stored; S (2 height width Dpad bytes per pair, Dpad =
+ *                        num_disp rounded up to 4) and the census planes (16 height width bytes per pair) are workspace of the handle,
+ *                        and the batch is walked in chunks of pairs that fit the workspace limit.
+ *   pcs_stereo_set_sgm_workspace  the limit in bytes (0: the default, 16 GiB).  pcs_stereo_sgm answers a limit below one pair's need with
+ *                        PCS_ERR_ARG and the needed byte count in pcs_last_error().  Chunking does not change a bit of the output.
+ * Every argument is checked on the host before the device is touched; the handle is looked at last.
+ */
+int pcs_stereo_sgm(pcs_stereo_matcher *p, int64_t n, int width, int height, const uint8_t *d_left, int64_t left_pitch, const uint8_t *d_right, int64_t right_pitch, int min_disp,
+                   int num_disp, int census_w, int census_h, int p1, int p2, int paths, int uniqueness_ratio, int lr_max_diff, const uint8_t *d_valid_left,
+                   const uint8_t *d_valid_right, int16_t *d_disp, int32_t *d_cost, uint8_t *d_status, void *stream);
+int pcs_stereo_set_sgm_workspace(pcs_stereo_matcher *p, int64_t bytes);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

@@ -213,6 +213,8 @@ SYMBOLS = {
     "pcs_stereo_reproject": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, POINTER(c_double), c_int64, c_double, c_double, POINTER(c_double), _P, c_int, _P, _P, _P]),
     "pcs_stereo_compact": (c_int, [_P, c_int64, c_int, c_int, _P, c_int, _P, _P, c_int64, _P, _P, _P, _P]),
     "pcs_stereo_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_stereo_sgm": (c_int, [_P, c_int64, c_int, c_int, _P, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "pcs_stereo_set_sgm_workspace": (c_int, [_P, c_int64]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),

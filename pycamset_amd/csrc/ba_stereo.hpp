@@ -112,6 +112,31 @@ __device__ inline uint32_t stereo_cost_of(const uint32_t (&run)[K], int dl) {
     return v;
 }
 
+// the uniqueness rule on the winner's cost c and the smallest cost c2 at |d - d*| >= 2 (STEREO_INF: there is none)
+__device__ inline bool stereo_not_unique(uint32_t c2, uint32_t c, int uniq) { return uniq > 0 && c2 != STEREO_INF && 100u * c2 <= (uint32_t)(100 + uniq) * c; }
+
+// the sub-pixel offset in sixteenths from the costs m, c, p at d* - 1, d*, d* + 1 (dl = d* - min_disp): floor((32 (m - p) + den) / (2 den))
+__device__ inline int stereo_subpixel(int dl, int D, int m, int c, int p) {
+    int off = 0;
+    if (dl > 0 && dl < D - 1) {
+        const int den = 2 * (m + p - 2 * c);
+        if (den != 0) {
+            const int num = 32 * (m - p) + den, dd = 2 * den;   // dd > 0; floor division
+            off = num / dd;
+            if (num % dd != 0 && num < 0) --off;
+        }
+    }
+    return off;
+}
+
+// the two lookups every finished pixel makes: the left-right check against d_R and the validity planes (row: offset of the pixel's row)
+__device__ inline int stereo_lookup_bits(int d, int64_t at, int lr, const int16_t *dR, const uint8_t *vL, const uint8_t *vR) {
+    int st = 0;
+    if (lr >= 0 && abs(d - (int)dR[at - d]) > lr) st |= STEREO_LEFT_RIGHT;
+    if (vL && (vL[at] == 0 || vR[at - d] == 0)) st |= STEREO_VALIDITY;
+    return st;
+}
+
 template <bool RIGHT, int K>
 __global__ __launch_bounds__(64) void stereo_match_kernel(const StereoMatchArgs a) {
     extern __shared__ __align__(16) unsigned char stereo_smem[];
@@ -223,18 +248,9 @@ __global__ __launch_bounds__(64) void stereo_match_kernel(const StereoMatchArgs 
                     for (int i = 0; i <= 2 * r; ++i) s += tex[t + i];
                     if (s < a.tex_thr) st |= STEREO_TEXTURE;
                 }
-                if (a.uniq > 0 && my_c2 != STEREO_INF && 100u * my_c2 <= (uint32_t)(100 + a.uniq) * my_c) st |= STEREO_UNIQUENESS;
-                if (a.lr >= 0 && abs(d - (int)a.dR[row + x - d]) > a.lr) st |= STEREO_LEFT_RIGHT;
-                if (a.vL && (a.vL[row + x] == 0 || a.vR[row + x - d] == 0)) st |= STEREO_VALIDITY;
-                int off = 0;
-                if (my_dl > 0 && my_dl < D - 1) {
-                    const int den = 2 * ((int)my_m + (int)my_p - 2 * (int)my_c);
-                    if (den != 0) {
-                        const int num = 32 * ((int)my_m - (int)my_p) + den, dd = 2 * den;   // dd > 0; floor division
-                        off = num / dd;
-                        if (num % dd != 0 && num < 0) --off;
-                    }
-                }
+                if (stereo_not_unique(my_c2, my_c, a.uniq)) st |= STEREO_UNIQUENESS;
+                st |= stereo_lookup_bits(d, row + x, a.lr, a.dR, a.vL, a.vR);
+                const int off = stereo_subpixel(my_dl, D, (int)my_m, (int)my_c, (int)my_p);
                 a.disp[row + x] = (int16_t)(st ? a.inv : 16 * d + off);
                 if (a.cost) a.cost[row + x] = (int32_t)my_c;
                 if (a.status) a.status[row + x] = (uint8_t)st;

@@ -53,6 +53,7 @@
 #include "ba_align.hpp"
 #include "ba_imagemap.hpp"
 #include "ba_stereo.hpp"
+#include "ba_stereo_sgm.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side

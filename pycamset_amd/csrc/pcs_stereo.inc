@@ -1,12 +1,15 @@
-// pcs_stereo.inc — host side of the stereo matcher (included by pcs_engine.hip; kernels: ba_stereo.hpp).  The handle owns the workspace:
-// the two prefiltered planes, the right-anchored disparity, the compaction's block counts and offsets, and the Q / T matrices of the
-// last reprojection — O(n H W) bytes, never the cost volume.  Images, disparities and points are the caller's device buffers.  Fence
+// pcs_stereo.inc — host side of the stereo matchers (included by pcs_engine.hip; kernels: ba_stereo.hpp, ba_stereo_sgm.hpp).  The handle
+// owns the workspace: the two prefiltered planes, the right-anchored disparity, the compaction's block counts and offsets, and the Q / T
+// matrices of the last reprojection — O(n H W) bytes, never the matching-cost volume — and, once pcs_stereo_sgm has run, the aggregated
+// volume S and the census planes of one chunk of pairs, under the limit of pcs_stereo_set_sgm_workspace.  Images, disparities and points are the caller's device buffers.  Fence
 // and timer are those of pcs_handle.inc (DESIGN.md, "Batched handles").
 struct pcs_stereo_matcher {
     HandleCore core;
     KernelTimer timer;
     DevBuf planes, dr, blk, off, qt;   // planes: uint8 (2, n, H, W); dr: int16 (n, H, W); blk: int32 (NB); off: int64 (NB + 1); qt: double (12 + 16 n_Q)
     std::vector<double> h_qt;          // what qt holds (the same Q frame after frame is uploaded once)
+    DevBuf sgm;                        // pcs_stereo_sgm: [S uint16 (nc, H, W, Dpad)] [descriptors uint64 (2, nc, H, W)] of one chunk of nc pairs
+    int64_t sgm_limit = 0;             // bytes sgm may take; 0: SGM_DEFAULT_WORKSPACE
 };
 
 static_assert(STEREO_NOT_STRICT == PCS_STEREO_NOT_STRICT && STEREO_TEXTURE == PCS_STEREO_TEXTURE && STEREO_UNIQUENESS == PCS_STEREO_UNIQUENESS &&
@@ -180,6 +183,68 @@ static void stereo_launch_scan(pcs_stereo_matcher *p, int64_t n, int64_t nblk, i
     hipLaunchKernelGGL(stereo_scan_kernel, dim3(1), dim3(1024), 0, s, p->blk.as<const int32_t>(), n * nblk, (int)nblk, (int)n, p->off.as<int64_t>(), d_counts);
 }
 
+// ---- semi-global matching (ba_stereo_sgm.hpp) -------------------------------------------------------------------------------------------
+// S takes 2 H W Dpad bytes per pair (2.6 GB at 2448 x 2048 with 256 disparities), so a batch is walked in chunks of pairs whose S and
+// census planes fit the handle's limit.  The default holds six such pairs: the path kernel's parallelism is lines x pairs, and one
+// line is one wave.
+constexpr int64_t SGM_DEFAULT_WORKSPACE = (int64_t)16 << 30;
+
+struct SgmPlan {
+    int rw, rh, K, Dpad;
+    int xs0, xs1, ys0, ys1;   // the strict rectangle (ends exclusive; empty: xs1 == xs0 or ys1 == ys0)
+    int64_t pair_bytes;       // sgm_pair_bytes: S and the two census planes of one pair
+};
+
+static SgmPlan sgm_plan(int W, int H, int min_disp, int D, int census_w, int census_h) {
+    SgmPlan t{};
+    t.rw = census_w / 2, t.rh = census_h / 2, t.K = sgm_k(D), t.Dpad = sgm_dpad(D);
+    const int dmax = min_disp + D - 1;
+    t.xs0 = t.rw + std::max(dmax, 0), t.xs1 = std::max(W - t.rw + std::min(min_disp, 0), t.xs0);
+    t.ys0 = t.rh, t.ys1 = std::max(H - t.rh, t.ys0);
+    t.pair_bytes = sgm_pair_bytes(W, H, t.Dpad);
+    return t;
+}
+
+// Every argument of pcs_stereo_sgm but the handle: nothing here touches the device.
+static int sgm_check(const char *who, int64_t n, int width, int height, const void *d_left, int64_t left_pitch, const void *d_right, int64_t right_pitch, int min_disp, int num_disp,
+                     int census_w, int census_h, int p1, int p2, int paths, int uniqueness_ratio, int lr_max_diff, const void *d_valid_left, const void *d_valid_right,
+                     const void *d_disp) {
+    if (const int rc = stereo_check_shape(who, n, width, height)) return rc;
+    if (min_disp < -STEREO_MAX_DISP || min_disp > STEREO_MAX_DISP) return fail(PCS_ERR_ARG, "%s: min_disp %d outside [-%d, %d]", who, min_disp, STEREO_MAX_DISP, STEREO_MAX_DISP);
+    if (num_disp < 1 || num_disp > SGM_MAX_DISP) return fail(PCS_ERR_ARG, "%s: num_disp %d outside [1, %d]", who, num_disp, SGM_MAX_DISP);
+    if (census_w < 3 || census_w % 2 == 0) return fail(PCS_ERR_ARG, "%s: census_w %d must be odd and >= 3", who, census_w);
+    if (census_h < 3 || census_h % 2 == 0) return fail(PCS_ERR_ARG, "%s: census_h %d must be odd and >= 3", who, census_h);
+    if ((int64_t)census_w * census_h - 1 > SGM_MAX_BITS)
+        return fail(PCS_ERR_ARG, "%s: the census window %d x %d has %lld bits, more than %d", who, census_w, census_h, (long long)census_w * census_h - 1, SGM_MAX_BITS);
+    if (p1 < 0 || p1 > p2) return fail(PCS_ERR_ARG, "%s: p1 %d outside [0, p2 = %d]", who, p1, p2);
+    if (p2 > SGM_MAX_P) return fail(PCS_ERR_ARG, "%s: p2 %d above %d", who, p2, SGM_MAX_P);
+    if (paths != 4 && paths != 8) return fail(PCS_ERR_ARG, "%s: paths %d must be 4 or 8", who, paths);
+    if (uniqueness_ratio < 0 || uniqueness_ratio > 100) return fail(PCS_ERR_ARG, "%s: uniqueness_ratio %d outside [0, 100]", who, uniqueness_ratio);
+    if (lr_max_diff < -1) return fail(PCS_ERR_ARG, "%s: lr_max_diff %d must be >= -1 (-1: no left-right check)", who, lr_max_diff);
+    if (left_pitch < width) return fail(PCS_ERR_ARG, "%s: left_pitch %lld below the row size %d", who, (long long)left_pitch, width);
+    if (right_pitch < width) return fail(PCS_ERR_ARG, "%s: right_pitch %lld below the row size %d", who, (long long)right_pitch, width);
+    if ((d_valid_left == nullptr) != (d_valid_right == nullptr)) return fail(PCS_ERR_ARG, "%s: d_valid_left and d_valid_right come together", who);
+    if (n > 0 && (!d_left || !d_right)) return fail(PCS_ERR_ARG, "%s: d_left and d_right (the images) must be given", who);
+    if (n > 0 && !d_disp) return fail(PCS_ERR_ARG, "%s: d_disp must be given", who);
+    return PCS_OK;
+}
+
+// pairs per chunk under `limit` bytes (0: the default); 0 when not even one pair fits
+static int64_t sgm_chunk_pairs(int64_t n, int64_t pair_bytes, int64_t limit) { return std::min(n, (limit > 0 ? limit : SGM_DEFAULT_WORKSPACE) / pair_bytes); }
+
+template <int K>
+static void sgm_launch_paths(const SgmArgs &a, int paths, hipStream_t s) {
+    static const int dirs[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {1, -1}, {-1, 1}, {-1, -1}};   // (dy, dx)
+    const int Ws = a.xs1 - a.xs0, Hs = a.ys1 - a.ys0;
+    for (int i = 0; i < paths; ++i) {
+        const int dy = dirs[i][0], dx = dirs[i][1], group = dy == 0 ? SGM_HORIZONTAL : dx == 0 ? SGM_VERTICAL : SGM_DIAGONAL;
+        const dim3 grid((unsigned)((sgm_line_count(group, Ws, Hs) + SGM_WAVES - 1) / SGM_WAVES), (unsigned)a.nc), block(64 * SGM_WAVES);
+        if (group == SGM_HORIZONTAL) hipLaunchKernelGGL((sgm_path_kernel<SGM_HORIZONTAL, K>), grid, block, 0, s, a, dy, dx, (int)(i == 0));
+        else if (group == SGM_VERTICAL) hipLaunchKernelGGL((sgm_path_kernel<SGM_VERTICAL, K>), grid, block, 0, s, a, dy, dx, 0);
+        else hipLaunchKernelGGL((sgm_path_kernel<SGM_DIAGONAL, K>), grid, block, 0, s, a, dy, dx, 0);
+    }
+}
+
 extern "C" {
 int pcs_stereo_create(pcs_stereo_matcher **out, int device) {
     if (!out) return fail(PCS_ERR_ARG, "pcs_stereo_create: bad arguments");
@@ -199,7 +264,7 @@ int pcs_stereo_create(pcs_stereo_matcher **out, int device) {
 
 int pcs_stereo_destroy(pcs_stereo_matcher *p) {
     if (!p) return PCS_OK;
-    p->core.destroy({&p->planes, &p->dr, &p->blk, &p->off, &p->qt}, {&p->timer});
+    p->core.destroy({&p->planes, &p->dr, &p->blk, &p->off, &p->qt, &p->sgm}, {&p->timer});
     delete p;
     return PCS_OK;
 }
@@ -243,6 +308,74 @@ int pcs_stereo_match(pcs_stereo_matcher *p, int64_t n, int width, int height, co
             }
             a.x_begin = t.xs0, a.x_end = t.xs1;
             return stereo_launch_match<false>(t.K, a, dim3((unsigned)((t.xs1 - t.xs0 + t.TW - 1) / t.TW), gy, (unsigned)n), t.lds, s);
+        });
+}
+
+int pcs_stereo_set_sgm_workspace(pcs_stereo_matcher *p, int64_t bytes) {
+    if (bytes < 0) return fail(PCS_ERR_ARG, "pcs_stereo_set_sgm_workspace: bytes %lld must be >= 0 (0: the default of %lld)", (long long)bytes, (long long)SGM_DEFAULT_WORKSPACE);
+    if (!p) return fail(PCS_ERR_ARG, "pcs_stereo_set_sgm_workspace: NULL handle");
+    p->sgm_limit = bytes;
+    return PCS_OK;
+}
+
+int pcs_stereo_sgm(pcs_stereo_matcher *p, int64_t n, int width, int height, const uint8_t *d_left, int64_t left_pitch, const uint8_t *d_right, int64_t right_pitch, int min_disp,
+                   int num_disp, int census_w, int census_h, int p1, int p2, int paths, int uniqueness_ratio, int lr_max_diff, const uint8_t *d_valid_left,
+                   const uint8_t *d_valid_right, int16_t *d_disp, int32_t *d_cost, uint8_t *d_status, void *stream) {
+    const char *who = "pcs_stereo_sgm";
+    if (const int rc = sgm_check(who, n, width, height, d_left, left_pitch, d_right, right_pitch, min_disp, num_disp, census_w, census_h, p1, p2, paths, uniqueness_ratio,
+                                 lr_max_diff, d_valid_left, d_valid_right, d_disp))
+        return rc;
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (n == 0) return PCS_OK;
+    const SgmPlan t = sgm_plan(width, height, min_disp, num_disp, census_w, census_h);
+    const bool empty = t.xs1 <= t.xs0 || t.ys1 <= t.ys0;   // no strict pixel: everything is invalid and only the fill is launched
+    const int64_t chunk = empty ? 0 : sgm_chunk_pairs(n, t.pair_bytes, p->sgm_limit);
+    if (!empty && chunk < 1)
+        return fail(PCS_ERR_ARG, "%s: one pair of this shape needs %lld bytes of workspace, the limit is %lld (pcs_stereo_set_sgm_workspace)", who, (long long)t.pair_bytes,
+                    (long long)(p->sgm_limit > 0 ? p->sgm_limit : SGM_DEFAULT_WORKSPACE));
+    const int64_t npix = n * height * width, HW = (int64_t)height * width;
+    const bool lr = lr_max_diff >= 0;
+    const int last_stage = stereo_env_int("PCS_SGM_LAST_STAGE", 1, 4);   // measurements: stop after the census (1), the paths (2), d_R (3)
+    return stereo_run(
+        p, stream, p->sgm.grows(chunk * t.pair_bytes) || (lr && p->dr.grows(npix)),
+        [&]() -> int {
+            if (const int rc = p->sgm.grow(chunk * t.pair_bytes, 1)) return rc;
+            return lr ? p->dr.grow(npix, sizeof(int16_t)) : PCS_OK;
+        },
+        [&](hipStream_t s) -> int {
+            const unsigned gx = (unsigned)((width + 255) / 256);
+            const int inv = 16 * (min_disp - 1);
+            hipLaunchKernelGGL(stereo_fill_kernel, dim3(gx, (unsigned)height, (unsigned)n), dim3(256), 0, s, width, height, t.xs0, t.xs1, t.ys0, t.ys1, inv, d_disp, d_cost, d_status);
+            if (empty) return PCS_OK;
+            const int Ws = t.xs1 - t.xs0, Hs = t.ys1 - t.ys0;
+            for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+                const int nc = (int)std::min(chunk, n - c0);
+                uint16_t *S = p->sgm.as<uint16_t>();
+                uint64_t *cen = reinterpret_cast<uint64_t *>(p->sgm.as<unsigned char>() + 2 * sgm_s_offset(nc, 0, 0, width, height, t.Dpad));
+                hipLaunchKernelGGL(sgm_census_kernel, dim3(gx, (unsigned)height, (unsigned)(2 * nc)), dim3(256), 0, s, d_left + c0 * height * left_pitch,
+                                   d_right + c0 * height * right_pitch, left_pitch, right_pitch, width, height, t.rw, t.rh, nc, cen);
+                if (last_stage == 1) continue;
+                SgmArgs a{};
+                a.cen = cen, a.S = S, a.W = width, a.H = height, a.nc = nc, a.dmin = min_disp, a.D = num_disp, a.Dpad = t.Dpad;
+                a.xs0 = t.xs0, a.xs1 = t.xs1, a.ys0 = t.ys0, a.ys1 = t.ys1, a.p1 = p1, a.p2 = p2;
+                if (t.K == 1) sgm_launch_paths<1>(a, paths, s);
+                else if (t.K == 2) sgm_launch_paths<2>(a, paths, s);
+                else sgm_launch_paths<4>(a, paths, s);
+                if (last_stage == 2) continue;
+                SgmSelectArgs q{};
+                q.S = S, q.W = width, q.H = height, q.dmin = min_disp, q.D = num_disp, q.Dpad = t.Dpad, q.xs0 = t.xs0, q.xs1 = t.xs1, q.ys0 = t.ys0, q.ys1 = t.ys1;
+                q.pair0 = c0, q.dR = p->dr.as<int16_t>(), q.uniq = uniqueness_ratio, q.lr = lr_max_diff, q.inv = inv;
+                q.vL = d_valid_left, q.vR = d_valid_right, q.disp = d_disp, q.cost = d_cost, q.status = d_status;
+                if (lr)
+                    hipLaunchKernelGGL(sgm_right_kernel, dim3((unsigned)((Ws + num_disp - 1 + SGM_RIGHT_TX - 1) / SGM_RIGHT_TX), (unsigned)Hs, (unsigned)nc), dim3(SGM_RIGHT_TX), 0, s,
+                                       q);
+                if (last_stage == 3) continue;
+                const dim3 grid((unsigned)((Ws + 63) / 64), (unsigned)Hs, (unsigned)nc);
+                if (t.K == 1) hipLaunchKernelGGL(sgm_select_kernel<1>, grid, dim3(64), 0, s, q);
+                else if (t.K == 2) hipLaunchKernelGGL(sgm_select_kernel<2>, grid, dim3(64), 0, s, q);
+                else hipLaunchKernelGGL(sgm_select_kernel<4>, grid, dim3(64), 0, s, q);
+            }
+            return PCS_OK;
         });
 }
 

@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Times the stereo matcher (pycamset_amd/stereo.py, csrc/ba_stereo.hpp) on one device at a rig's size: one and sixteen 2448 x 2048 pairs,
-256 and 64 disparities, blocks 5, 15 and 25, with and without the left-right pass; then the reprojection and the compaction.
+256 and 64 disparities, blocks 5, 15 and 25, with and without the left-right pass; then the reprojection and the compaction.  With --sgm:
+semi-global matching (csrc/ba_stereo_sgm.hpp) at 64, 128 and 256 disparities and 4 and 8 paths, stage by stage, with the traffic of the
+aggregated volume against the time of the path kernels.
 
 Every row: `reps` back-to-back calls between two device events after a warm-up of the same shape, repeated `runs` times; the median
 per-call time with the smallest and largest run, and the (pixel, disparity) window costs per second, counting the strict pixels times
 the disparities (twice that with the left-right pass, whose second sweep is anchored in the right image).
 
     python tools/stereo_bench.py --out result.json
+    python tools/stereo_bench.py --sgm --blocks 15 --out sgm.json
 """
 from __future__ import annotations
 
@@ -29,6 +32,12 @@ def main():
     ap.add_argument("--tile-columns", type=int, nargs="+", default=[0], help="PCS_STEREO_TILE_COLUMNS per row; 0: the library's own choice")
     ap.add_argument("--strip-rows", type=int, nargs="+", default=[0], help="PCS_STEREO_STRIP_ROWS per row; 0: the library's own choice")
     ap.add_argument("--no-cloud", action="store_true", help="skip the reprojection and compaction rows")
+    ap.add_argument("--sgm", action="store_true", help="time semi-global matching stage by stage instead, next to the block matcher at the first of --blocks")
+    ap.add_argument("--sgm-disparities", type=int, nargs="+", default=[64, 128, 256])
+    ap.add_argument("--paths", type=int, nargs="+", default=[4, 8])
+    ap.add_argument("--census", type=int, nargs=2, default=[9, 7], help="census window, width height")
+    ap.add_argument("--p1", type=int, default=8)
+    ap.add_argument("--p2", type=int, default=32)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
@@ -66,6 +75,37 @@ def main():
         rows.append(row)
         print(f"{name:58s} {med:10.3f} ms  [{min(ms):.3f} .. {max(ms):.3f}]  {row['G_per_s']:8.2f} G {unit}/s", flush=True)
 
+    def sgm_rows(n, left, right, disp):
+        """--sgm: per (D, paths) the call cut off after the census, after the paths, complete without and with the left-right check
+        (PCS_SGM_LAST_STAGE); the stage times are the differences of the medians.  Traffic model of the paths: every direction reads and
+        writes S on the strict rectangle, 2 Hs Ws Dpad bytes each way, and the first one only writes."""
+        for D in a.sgm_disparities:
+            rw, rh = a.census[0] // 2, a.census[1] // 2
+            Ws, Hs, Dpad = max(W - 2 * rw - (D - 1), 0), max(H - 2 * rh, 0), (D + 3) & ~3
+            for block in a.blocks[:1]:
+                for lr in (-1, 1):
+                    timed(f"block match {n:2d} x {W}x{H}  D={D:3d} block={block:2d} {'left-right' if lr >= 0 else 'one pass  '}",
+                          lambda: m.match(n, W, H, left.data_ptr(), W, right.data_ptr(), W, disp.data_ptr(), num_disp=D, block=block, lr_max_diff=lr, stream=stream),
+                          max(W - 2 * (block // 2) - (D - 1), 0) * max(H - 2 * (block // 2), 0) * n * D * (2 if lr >= 0 else 1), "(pixel, disparity)")
+            for paths in a.paths:
+                med = {}
+                for stage, lr, name in ((1, -1, "census"), (2, -1, "census + paths"), (4, -1, "complete, one pass"), (4, 1, "complete, left-right")):
+                    os.environ["PCS_SGM_LAST_STAGE"] = str(stage)
+                    timed(f"sgm {n:2d} x {W}x{H}  D={D:3d} paths={paths} {name}",
+                          lambda: m.match_sgm(n, W, H, left.data_ptr(), W, right.data_ptr(), W, disp.data_ptr(), num_disp=D, census=tuple(a.census), p1=a.p1, p2=a.p2, paths=paths,
+                                              lr_max_diff=lr, stream=stream), Ws * Hs * n * D * paths, "(pixel, disparity, path)")
+                    med[(stage, lr)] = rows[-1]["ms_median"]
+                os.environ.pop("PCS_SGM_LAST_STAGE", None)
+                t_paths = med[(2, -1)] - med[(1, -1)]
+                s_bytes = (2 * paths - 1) * 2 * Hs * Ws * Dpad * n
+                stages = {"census_ms": med[(1, -1)], "paths_ms": t_paths, "select_ms": med[(4, -1)] - med[(2, -1)], "right_ms": med[(4, 1)] - med[(4, -1)],
+                          "complete_one_pass_ms": med[(4, -1)], "complete_left_right_ms": med[(4, 1)], "S_bytes_moved": s_bytes,
+                          "S_TB_per_s": s_bytes / t_paths / 1e9 if t_paths > 0 else None, "share_of_8_TB_per_s": s_bytes / t_paths / 1e9 / 8.0 if t_paths > 0 else None}
+                rows.append({"row": f"sgm stages {n} pairs D={D} paths={paths}", **stages})
+                print(f"    stages: census {stages['census_ms']:.3f}  paths {t_paths:.3f} ({t_paths / paths:.3f} per direction)  select {stages['select_ms']:.3f}  "
+                      f"right {stages['right_ms']:.3f} ms;  S traffic {s_bytes / 1e9:.2f} GB at {stages['S_TB_per_s']:.3f} TB/s = {100 * stages['share_of_8_TB_per_s']:.1f} % of 8 TB/s",
+                      flush=True)
+
     for n in a.pairs:
         g = torch.Generator(device=dev).manual_seed(5)
         # smoothed noise; the right image is the left one shifted by 20 px, with its own noise
@@ -74,6 +114,9 @@ def main():
         left = (base[:, :, 32:] * 255).to(torch.uint8).contiguous()
         right = ((base[:, :, 12:W + 12] + 0.02 * torch.rand((n, H, W), device=dev, generator=g)).clamp(0, 1) * 255).to(torch.uint8).contiguous()
         disp = torch.empty((n, H, W), dtype=torch.int16, device=dev)
+        if a.sgm:
+            sgm_rows(n, left, right, disp)
+            continue
         for D in a.disparities:
             for block in a.blocks:
                 for lr in (-1, 1):
