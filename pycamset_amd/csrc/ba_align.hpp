@@ -16,7 +16,7 @@
 //
 // align_fit_kernel<G>      one group per problem, optional per-row mask (the consensus stage's flags): pass 1 sum w and both centroids,
 //                          pass 2 S and sum w |x~|^2, closed form, pass 3 weighted RMS of |y - s R x - t| and the per-row distances.
-// align_hypothesis_kernel  one thread per (problem, hypothesis): three rows by pnp_sample_positions (key: the problem index), the same
+// align_hypothesis_kernel  one thread per (problem, hypothesis): three rows by cons_sample_positions (ba_consensus.hpp; key: the problem index), the same
 //                          closed form in registers; [s R | t], NaN for a degenerate or non-finite triple.
 // align_score_kernel<G>    one group per (problem, hypothesis): sum min(d^2, tau^2) over all rows; a skipped row counts tau^2; +inf for a
 //                          NaN hypothesis.
@@ -25,8 +25,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_consensus.hpp"
 #include "ba_pnp.hpp"
-#include "ba_pnp_consensus.hpp"
 
 namespace pcs {
 
@@ -171,9 +171,9 @@ __global__ __launch_bounds__(256) void align_fit_kernel(const double *__restrict
         cx[k] = group_sum<G>(cx[k]) / sw;
         cy[k] = group_sum<G>(cy[k]) / sw;
     }
-    n_usable = group_sum_int<G>(n_usable);
-    n_used = group_sum_int<G>(n_used);
-    n_bad = group_sum_int<G>(n_bad);
+    n_usable = group_sum<G>(n_usable);
+    n_used = group_sum<G>(n_used);
+    n_bad = group_sum<G>(n_bad);
     int status = ALIGN_OK;
     if (n_usable < min_points) status = s1 > s0 && n_bad == s1 - s0 ? ALIGN_NONFINITE : ALIGN_TOO_FEW;
     else if (n_used < min_points) status = ALIGN_NO_CONSENSUS;
@@ -253,8 +253,8 @@ __global__ __launch_bounds__(256) void align_hypothesis_kernel(const double *__r
     double R[9], A[9], t[3];
     int status = ALIGN_TOO_FEW;
     if (n >= ALIGN_SAMPLE) {
-        int64_t pick[PNP_CONS_MAX_SAMPLE];
-        pnp_sample_positions(seed, (int32_t)p, n, h, ALIGN_SAMPLE, pick);
+        int64_t pick[CONS_MAX_SAMPLE];
+        cons_sample_positions(seed, (int32_t)p, n, h, ALIGN_SAMPLE, pick);
         AlignRow r[ALIGN_SAMPLE];
         bool usable = true;
         double sw = 0.0, cx[3] = {0.0, 0.0, 0.0}, cy[3] = {0.0, 0.0, 0.0};
@@ -324,13 +324,11 @@ __global__ __launch_bounds__(256) void align_score_kernel(const double *__restri
     const int64_t s0 = start[p], s1 = start[p + 1];
     double A[9], t[3], sum = INFINITY;
     if (align_load_hypothesis(hyp + 12 * gid, A, t)) {   // the same in every lane of the group
-        sum = 0.0;
-        for (int64_t o = s0 + g; o < s1; o += G) {
+        sum = cons_truncated_sum<G>(s0, s1, g, tau2, [&](const int64_t o, bool &usable) {
             const AlignRow r = align_load(src, dst, wt, o);
-            const double d2 = align_d2(A, t, r);
-            sum += r.usable && d2 <= tau2 ? d2 : tau2;
-        }
-        sum = group_sum<G>(sum);
+            usable = r.usable;
+            return align_d2(A, t, r);
+        });
     }
     if (g == 0) score[gid] = sum;
 }
@@ -347,27 +345,18 @@ __global__ __launch_bounds__(256) void align_select_kernel(const double *__restr
     if (p >= n_problems) return;
     const int64_t s0 = start[p], s1 = start[p + 1], n = s1 - s0;
     if (n < ALIGN_SAMPLE) {   // the plain path: every row goes on
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 1;
+        cons_flag_all<G>(s0, s1, g, flag, 1);
         if (g == 0) {
             sel[3 * p + 0] = (int32_t)n; sel[3 * p + 1] = -1; sel[3 * p + 2] = 0;
             best_out[p] = __builtin_nan("");
         }
         return;
     }
-    double best = INFINITY;
-    int best_k = INT32_MAX;
-    for (int k = g; k < H; k += G) {   // ascending inside a lane: of equal scores the lower hypothesis stays
-        const double s = score[p * H + k];
-        if (s < best) { best = s; best_k = k; }
-    }
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) {   // (score, hypothesis) is a total order: the minimum does not depend on the pairing
-        const double os = __shfl_xor(best, off, G);
-        const int ok = __shfl_xor(best_k, off, G);
-        if (os < best || (os == best && ok < best_k)) { best = os; best_k = ok; }
-    }
+    double best;
+    int best_k, n_fin;
+    cons_argmin<G>(score + p * H, H, g, best, best_k, n_fin, cons_count_none);
     if (best_k == INT32_MAX) {   // no finite hypothesis: no inlier
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 0;
+        cons_flag_all<G>(s0, s1, g, flag, 0);
         if (g == 0) {
             sel[3 * p + 0] = 0; sel[3 * p + 1] = -1; sel[3 * p + 2] = 1;
             best_out[p] = INFINITY;
@@ -376,14 +365,11 @@ __global__ __launch_bounds__(256) void align_select_kernel(const double *__restr
     }
     double A[9], t[3];
     align_load_hypothesis(hyp + 12 * (p * H + best_k), A, t);
-    int cnt = 0;
-    for (int64_t o = s0 + g; o < s1; o += G) {
+    const int cnt = cons_flag_inliers<G>(s0, s1, g, tau2, flag, [&](const int64_t o, bool &usable) {
         const AlignRow r = align_load(src, dst, wt, o);
-        const bool in = r.usable && align_d2(A, t, r) <= tau2;
-        flag[o] = in ? 1 : 0;
-        cnt += in ? 1 : 0;
-    }
-    cnt = group_sum_int<G>(cnt);
+        usable = r.usable;
+        return align_d2(A, t, r);
+    });
     if (g == 0) {
         sel[3 * p + 0] = cnt; sel[3 * p + 1] = best_k; sel[3 * p + 2] = 1;
         best_out[p] = best;

@@ -3,7 +3,7 @@
 // (boards, walls, floors); Nister's five-point solver does not.  Policy of DESIGN.md, "Batched handles", as in ba_twoview.hpp: group sums
 // are xor-butterflies, no floating-point atomics, no scratch, every iteration count fixed, two runs agree bit for bit.
 //
-// tv5_hypothesis_kernel  one group of 16 lanes per (pair, hypothesis): five rows drawn by pnp_sample_positions (sample size 5), rays in
+// tv5_hypothesis_kernel  one group of 16 lanes per (pair, hypothesis): five rows drawn by cons_sample_positions (sample size 5), rays in
 //                        normalised camera coordinates, the four eigenvectors of the smallest eigenvalues of the 9 x 9 moment matrix
 //                        (tv_sweep, the lane-distributed Jacobi of the eight-point fit), the ten cubic constraints as a 10 x 20 matrix
 //                        with ONE ROW PER LANE, Gauss-Jordan with partial pivoting by shuffles, the degree-10 polynomial in z, its Sturm
@@ -145,8 +145,8 @@ __global__ __launch_bounds__(256) void tv5_hypothesis_kernel(const double4 *__re
         }
         return;
     }
-    int64_t pick[PNP_CONS_MAX_SAMPLE];
-    pnp_sample_positions(seed, (int32_t)p, n, h, TV5_SAMPLE, pick);
+    int64_t pick[CONS_MAX_SAMPLE];
+    cons_sample_positions(seed, (int32_t)p, n, h, TV5_SAMPLE, pick);
     int64_t mine = 0;
 #pragma unroll
     for (int i = 0; i < TV5_SAMPLE; ++i)
@@ -492,21 +492,10 @@ __global__ __launch_bounds__(256) void tv5_select_kernel(const double4 *__restri
     const int64_t p = order[gid];
     const int64_t s0 = start[p], s1 = start[p + 1];
     double best = INFINITY;
-    int best_k = INT32_MAX;
-    if (s1 - s0 >= n_min) {
-        for (int k = g; k < HS; k += G) {   // ascending inside a lane: of equal scores the lower slot stays
-            const double s = score[p * HS + k];
-            if (s < best) { best = s; best_k = k; }
-        }
-#pragma unroll
-        for (int off = G / 2; off > 0; off >>= 1) {   // (score, slot) is a total order: the minimum does not depend on the pairing
-            const double os = __shfl_xor(best, off, G);
-            const int ok = __shfl_xor(best_k, off, G);
-            if (os < best || (os == best && ok < best_k)) { best = os; best_k = ok; }
-        }
-    }
+    int best_k = INT32_MAX, n_fin;
+    if (s1 - s0 >= n_min) cons_argmin<G>(score + p * HS, HS, g, best, best_k, n_fin, cons_count_none);
     if (best_k == INT32_MAX) {
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 0;
+        cons_flag_all<G>(s0, s1, g, flag, 0);
         if (g == 0) {
             sel[2 * p + 0] = 0; sel[2 * p + 1] = -1;
             best_out[p] = s1 - s0 >= n_min ? INFINITY : __builtin_nan("");
@@ -525,18 +514,14 @@ __global__ __launch_bounds__(256) void tv5_select_kernel(const double4 *__restri
     }
     const TvCams k(cam_tab, pair_cams[2 * p], pair_cams[2 * p + 1]);
     const TvAffine ia = k.inv_a(), ib = k.inv_b();
-    int cnt = 0;
-    for (int64_t o = s0 + g; o < s1; o += G) {
+    const int cnt = cons_flag_inliers<G>(s0, s1, g, tau2, flag, [&](const int64_t o, bool &usable) {   // usable: in front of both cameras
         const double4 m = und[o];
         const double xa = ia.p * m.x + ia.u, ya = ia.q * m.y + ia.v, xb = ib.p * m.z + ib.u, yb = ib.q * m.w + ib.v;
-        bool pos, neg;
+        bool neg;
         double unused;
-        tv_depth<false>(R, t, xa, ya, xb, yb, pos, neg, unused);
-        const bool in = tv_sampson(F, m) <= tau2 && pos;
-        flag[o] = in ? 1 : 0;
-        cnt += in ? 1 : 0;
-    }
-    cnt = group_sum_int<G>(cnt);
+        tv_depth<false>(R, t, xa, ya, xb, yb, usable, neg, unused);
+        return tv_sampson(F, m);
+    });
     if (g == 0) {
         sel[2 * p + 0] = cnt; sel[2 * p + 1] = best_k;
         best_out[p] = best;
@@ -576,8 +561,8 @@ __device__ __forceinline__ void tv_pose_stats(const double4 *__restrict__ und, c
         cnt += pos ? 1 : 0;
         ang += pos ? a * a : 0.0;
     }
-    n_front = group_sum_int<G>(cnt);
-    n_inl = group_sum_int<G>(n_inl);
+    n_front = group_sum<G>(cnt);
+    n_inl = group_sum<G>(n_inl);
     rms = sqrt(group_sum<G>(e2sum) / (double)n_inl);
     parallax = sqrt(group_sum<G>(ang) / (double)n_front);
 }

@@ -6,8 +6,8 @@
 // (camera, image, board) group, and Zhang's constraints of a bent homography lose the camera.  Here H hypotheses per group are fitted to
 // sample_size random detections each by the UNCHANGED intr_homography_kernel (ba_intrinsics.hpp) on the pseudo-groups that the UNCHANGED
 // pnp_sample_kernel (ba_pnp_consensus.hpp) draws, scored on all detections of the group by a truncated squared transfer error, and the
-// unchanged intr_homography_kernel / intr_camera_kernel then run on the table compacted to the winner's inliers (pnp_count_scan_kernel,
-// pnp_compact_kernel).  Every group and every (group, hypothesis) is one group of G lanes under the policy of DESIGN.md, "Batched
+// unchanged intr_homography_kernel / intr_camera_kernel then run on the table compacted to the winner's inliers (cons_count_scan_kernel,
+// cons_compact_kernel; the walks of scoring and selection are those of every consensus stage too, ba_consensus.hpp).  Every group and every (group, hypothesis) is one group of G lanes under the policy of DESIGN.md, "Batched
 // handles": xor-butterfly sums (every lane of a group holds identical bits), no floating-point atomics, every sum in a fixed order,
 // nothing of a neighbour or of the launch geometry enters a result.  The hypothesis count is fixed: two runs agree bit for bit.
 //
@@ -21,13 +21,13 @@
 //                     observations than max(sample_size, min_points) (consensus not used, score NaN) and (b) a group without a finite
 //                     hypothesis (used, score +inf).  (b) differs from the PnP stage on purpose: the group status is a diagnostic
 //                     here, and a collinear or non-finite group reports NOT_PLANAR / NOT_FINITE as the plain run does, not TOO_FEW.
-// intr_consensus_finish_kernel   the observation count of the group back into group_info[:, 1] (the final fit wrote the inlier count
-//                     there, which the camera kernel's pixel centroid has to weight by).
+// Behind the camera kernel cons_restore_count_kernel puts the observation count of the group back into group_info[:, 1] (the final fit
+// wrote the inlier count there, which the camera kernel's pixel centroid has to weight by).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_consensus.hpp"
 #include "ba_intrinsics.hpp"
-#include "ba_pnp_consensus.hpp"
 
 namespace pcs {
 
@@ -67,13 +67,7 @@ __global__ __launch_bounds__(256) void intr_score_kernel(const int32_t *__restri
     if (hyp_info[2 * gid] == INTR_GROUP_USED) {   // the same in every lane of the group
         IntrHypothesis hyp;
         hyp.load(hyp_H + 9 * gid, hyp_frame + 9 * gid);
-        s = 0.0;
-        for (int64_t o = s0 + g; o < s1; o += G) {
-            bool usable;
-            const double e2 = hyp.e2_of(pts + 3 * (int64_t)key[o], uv[o], usable);
-            s += usable && e2 <= tau2 ? e2 : tau2;
-        }
-        s = group_sum<G>(s);
+        s = cons_truncated_sum<G>(s0, s1, g, tau2, [&](const int64_t o, bool &usable) { return hyp.e2_of(pts + 3 * (int64_t)key[o], uv[o], usable); });
     }
     if (g == 0) score[gid] = s;
 }
@@ -90,30 +84,18 @@ __global__ __launch_bounds__(256) void intr_select_kernel(const int32_t *__restr
     if (j >= n_groups) return;
     const int64_t s0 = start[j], s1 = start[j + 1], n = s1 - s0;
     if (n < n_min) {   // (a) the plain path: every observation goes on
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 1;
+        cons_flag_all<G>(s0, s1, g, flag, 1);
         if (g == 0) {
             cinfo[4 * j + 0] = (int32_t)n; cinfo[4 * j + 1] = -1; cinfo[4 * j + 2] = 0; cinfo[4 * j + 3] = 0;
             best_out[j] = __builtin_nan("");
         }
         return;
     }
-    const double *sc = score + j * H;
-    double best = INFINITY;
-    int best_k = INT32_MAX, n_fin = 0;
-    for (int k = g; k < H; k += G) {   // ascending inside a lane: of equal scores the lower hypothesis stays
-        const double s = sc[k];
-        if (s < best) { best = s; best_k = k; }
-        n_fin += s < INFINITY ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) {   // (score, hypothesis) is a total order: the minimum does not depend on the pairing
-        const double os = __shfl_xor(best, off, G);
-        const int ok = __shfl_xor(best_k, off, G);
-        if (os < best || (os == best && ok < best_k)) { best = os; best_k = ok; }
-    }
-    n_fin = group_sum_int<G>(n_fin);
-    if (best_k == INT32_MAX) {   // (b) no finite hypothesis: the whole group goes on and the final fit names the reason
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 1;
+    double best;
+    int best_k, n_fin;
+    cons_argmin<G>(score + j * H, H, g, best, best_k, n_fin, [](int, const double s) { return s < INFINITY; });
+    if (best_k == INT32_MAX) {   // (b) no finite hypothesis: this stage alone flags the whole group 1, and the final fit names the reason
+        cons_flag_all<G>(s0, s1, g, flag, 1);
         if (g == 0) {
             cinfo[4 * j + 0] = (int32_t)n; cinfo[4 * j + 1] = -1; cinfo[4 * j + 2] = n_fin; cinfo[4 * j + 3] = 1;
             best_out[j] = INFINITY;
@@ -122,25 +104,12 @@ __global__ __launch_bounds__(256) void intr_select_kernel(const int32_t *__restr
     }
     IntrHypothesis hyp;
     hyp.load(hyp_H + 9 * (j * H + best_k), hyp_frame + 9 * (j * H + best_k));
-    int cnt = 0;
-    for (int64_t o = s0 + g; o < s1; o += G) {
-        bool usable;
-        const double e2 = hyp.e2_of(pts + 3 * (int64_t)key[o], uv[o], usable);
-        const bool in = usable && e2 <= tau2;
-        flag[o] = in ? 1 : 0;
-        cnt += in ? 1 : 0;
-    }
-    cnt = group_sum_int<G>(cnt);
+    const int cnt = cons_flag_inliers<G>(s0, s1, g, tau2, flag,
+                                         [&](const int64_t o, bool &usable) { return hyp.e2_of(pts + 3 * (int64_t)key[o], uv[o], usable); });
     if (g == 0) {
         cinfo[4 * j + 0] = cnt; cinfo[4 * j + 1] = best_k; cinfo[4 * j + 2] = n_fin; cinfo[4 * j + 3] = 1;
         best_out[j] = best;
     }
-}
-
-__global__ __launch_bounds__(256) void intr_consensus_finish_kernel(const int64_t *__restrict__ start, const int64_t n_groups, int32_t *__restrict__ group_info) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_groups) return;
-    group_info[2 * j + 1] = (int32_t)(start[j + 1] - start[j]);
 }
 
 }  // namespace pcs

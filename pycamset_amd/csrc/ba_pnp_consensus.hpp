@@ -8,10 +8,13 @@
 // "Batched handles": xor-butterfly sums (every lane of a group holds identical bits), no floating-point atomics, every sum in a fixed
 // order, nothing of a neighbour or of the launch geometry enters a result.  The hypothesis count is fixed: two runs agree bit for bit.
 //
-// pnp_sample_kernel   one thread per (view, hypothesis): sample_size distinct positions inside the view from a counter-based generator
-//                     (a splitmix64 finaliser: 64-bit multiplies, shifts, xors) keyed by (seed, camera, observations of the view,
-//                     hypothesis) and a partial Fisher-Yates; positions ascending; the sampled (key, uv) rows become a pseudo-view of
-//                     sample_size observations.  The view's rows arrive sorted by key, so the same table shuffled draws the same detections.
+// The generator, the walks of scoring and selection, and the scan, compaction and restored-count kernels are those of every consensus
+// stage (ba_consensus.hpp); here is what belongs to the target pose.
+//
+// pnp_sample_kernel   one thread per (view, hypothesis): sample_size distinct positions inside the view by cons_sample_positions, keyed
+//                     by (seed, camera, observations of the view, hypothesis); positions ascending; the sampled (key, uv) rows become a
+//                     pseudo-view of sample_size observations.  The view's rows arrive sorted by key, so the same table shuffled draws
+//                     the same detections.
 //                     A view with fewer observations than sample_size gets NaN rows (its hypotheses are NaN and never looked at).
 // pnp_score_kernel    one group per (view, hypothesis): sum min(e^2, tau^2) over the view's observations for the start and for the second
 //                     pose of the planar ambiguity in ONE walk, full Brown-Conrady projection (pnp_point); tau^2 for a non-finite
@@ -21,63 +24,15 @@
 //                     then one flag per observation, e^2 <= tau^2 at the winner, the inlier count and the number of hypotheses with a
 //                     finite candidate.  A view with fewer observations than sample_size is flagged whole (consensus not used); a view
 //                     without a finite candidate has no inlier.  Too few inliers for min_points: the kernels behind refuse the view.
-// pnp_count_scan_kernel / pnp_compact_kernel   exclusive scan of the inlier counts (one workgroup, integers), stable scatter of the flagged
-//                     rows by ballot and popcount: the order inside a view is preserved.
-// pnp_consensus_finish_kernel   the observation count of the view back into info[2] (the LM wrote the inlier count there).
+// Behind them cons_count_scan_kernel and cons_compact_kernel<16> make the table of the flagged rows, and cons_restore_count_kernel puts
+// the observation count of the view back into info[2] (the LM wrote the inlier count there).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_consensus.hpp"
 #include "ba_pnp.hpp"
 
 namespace pcs {
-
-constexpr int PNP_CONS_MAX_SAMPLE = 16;   // positions of a sample stay in registers (every index a compile-time constant)
-
-__device__ __forceinline__ uint64_t pnp_mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-constexpr uint64_t PNP_GOLDEN = 0x9e3779b97f4a7c15ull;
-
-// the sample of hypothesis h in a view of n observations of camera cam: S distinct positions in [0, n), ascending in pick[0 .. S)
-__device__ __forceinline__ void pnp_sample_positions(const uint64_t seed, const int32_t cam, const int64_t n, const int h, const int S,
-                                                     int64_t (&pick)[PNP_CONS_MAX_SAMPLE]) {
-    uint64_t k = pnp_mix64(seed + PNP_GOLDEN);
-    k = pnp_mix64(k ^ (uint64_t)(uint32_t)cam);
-    k = pnp_mix64(k ^ (uint64_t)n);
-    k = pnp_mix64(k ^ (uint64_t)(uint32_t)h);
-    // partial Fisher-Yates on the identity permutation, kept sparse: step i swaps positions i and j >= i; mj[i] = j now holds mv[i]
-    int64_t mj[PNP_CONS_MAX_SAMPLE], mv[PNP_CONS_MAX_SAMPLE];
-#pragma unroll
-    for (int i = 0; i < PNP_CONS_MAX_SAMPLE; ++i) {
-        pick[i] = INT64_MAX;
-        mj[i] = -1;
-        mv[i] = 0;
-        if (i < S) {
-            const uint64_t r = pnp_mix64(k + (uint64_t)(i + 1) * PNP_GOLDEN);
-            const int64_t j = i + (int64_t)(r % (uint64_t)(n - i));
-            int64_t vi = i, vj = j;
-#pragma unroll
-            for (int m = 0; m < i; ++m) {   // the latest entry of a position wins
-                if (mj[m] == i) vi = mv[m];
-                if (mj[m] == j) vj = mv[m];
-            }
-            mj[i] = j;
-            mv[i] = vi;
-            pick[i] = vj;
-        }
-    }
-    // ascending: odd-even transposition (the unused tail holds INT64_MAX and stays behind)
-#pragma unroll
-    for (int round = 0; round < PNP_CONS_MAX_SAMPLE; ++round)
-#pragma unroll
-        for (int i = round & 1; i + 1 < PNP_CONS_MAX_SAMPLE; i += 2) {
-            const int64_t a = pick[i], b = pick[i + 1];
-            pick[i] = a < b ? a : b;
-            pick[i + 1] = a < b ? b : a;
-        }
-}
 
 __global__ __launch_bounds__(256) void pnp_sample_kernel(const int32_t *__restrict__ key, const double2 *__restrict__ uv, const int64_t *__restrict__ start,
                                                          const int32_t *__restrict__ view_cam, const int64_t n_views, const int H, const int S,
@@ -101,10 +56,10 @@ __global__ __launch_bounds__(256) void pnp_sample_kernel(const int32_t *__restri
         }
         return;
     }
-    int64_t pick[PNP_CONS_MAX_SAMPLE];
-    pnp_sample_positions(seed, cam, n, h, S, pick);
+    int64_t pick[CONS_MAX_SAMPLE];
+    cons_sample_positions(seed, cam, n, h, S, pick);
 #pragma unroll
-    for (int i = 0; i < PNP_CONS_MAX_SAMPLE; ++i)
+    for (int i = 0; i < CONS_MAX_SAMPLE; ++i)
         if (i < S) {
             ok[i] = key[s0 + pick[i]];
             ouv[i] = uv[s0 + pick[i]];
@@ -192,13 +147,6 @@ __global__ __launch_bounds__(256) void pnp_score_kernel(const int32_t *__restric
     }
 }
 
-template <int G>
-__device__ __forceinline__ int group_sum_int(int x) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, G);
-    return x;
-}
-
 // cinfo (n_views, 4): inliers, winning hypothesis (-1: none), hypotheses with a finite candidate, consensus used
 template <int G>
 __global__ __launch_bounds__(256) void pnp_select_kernel(const int32_t *__restrict__ key, const double2 *__restrict__ uv, const int64_t *__restrict__ start,
@@ -212,30 +160,18 @@ __global__ __launch_bounds__(256) void pnp_select_kernel(const int32_t *__restri
     if (j >= n_views) return;
     const int64_t s0 = start[j], s1 = start[j + 1], n = s1 - s0;
     if (n < S) {   // the plain path: every observation goes on
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 1;
+        cons_flag_all<G>(s0, s1, g, flag, 1);
         if (g == 0) {
             cinfo[4 * j + 0] = (int32_t)n; cinfo[4 * j + 1] = -1; cinfo[4 * j + 2] = 0; cinfo[4 * j + 3] = 0;
             best_out[j] = __builtin_nan("");
         }
         return;
     }
-    const double *sc = score + 2 * j * H;
-    double best = INFINITY;
-    int best_k = INT32_MAX, n_fin = 0;
-    for (int k = g; k < 2 * H; k += G) {   // ascending inside a lane: of equal scores the lower candidate stays
-        const double s = sc[k];
-        if (s < best) { best = s; best_k = k; }
-        n_fin += !(k & 1) && s < INFINITY ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) {   // (score, candidate) is a total order: the minimum does not depend on the pairing
-        const double os = __shfl_xor(best, off, G);
-        const int ok = __shfl_xor(best_k, off, G);
-        if (os < best || (os == best && ok < best_k)) { best = os; best_k = ok; }
-    }
-    n_fin = group_sum_int<G>(n_fin);
+    double best;
+    int best_k, n_fin;   // candidate 2 h + c is pose c of hypothesis h: a hypothesis counts once, by its first pose
+    cons_argmin<G>(score + 2 * j * H, 2 * H, g, best, best_k, n_fin, [](const int k, const double s) { return !(k & 1) && s < INFINITY; });
     if (best_k == INT32_MAX) {   // no finite candidate: no inlier, the kernels behind refuse the empty view
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 0;
+        cons_flag_all<G>(s0, s1, g, flag, 0);
         if (g == 0) {
             cinfo[4 * j + 0] = 0; cinfo[4 * j + 1] = -1; cinfo[4 * j + 2] = n_fin; cinfo[4 * j + 3] = 1;
             best_out[j] = INFINITY;
@@ -249,73 +185,14 @@ __global__ __launch_bounds__(256) void pnp_select_kernel(const int32_t *__restri
         for (int k = 0; k < 9; ++k) cam[k] = ct[k];
     }
     pnp_load_pose(((best_k & 1) ? pose_b : pose_a) + 6 * (j * H + (best_k >> 1)), R, t);
-    int cnt = 0;
-    for (int64_t o = s0 + g; o < s1; o += G) {
+    const int cnt = cons_flag_inliers<G>(s0, s1, g, tau2, flag, [&](const int64_t o, bool &usable) {
         double ru, rv;
-        bool usable;
-        const double e2 = pnp_consensus_e2(R, t, cam, pts + 3 * (int64_t)key[o], uv[o], ru, rv, usable);
-        const bool in = usable && e2 <= tau2;
-        flag[o] = in ? 1 : 0;
-        cnt += in ? 1 : 0;
-    }
-    cnt = group_sum_int<G>(cnt);
+        return pnp_consensus_e2(R, t, cam, pts + 3 * (int64_t)key[o], uv[o], ru, rv, usable);
+    });
     if (g == 0) {
         cinfo[4 * j + 0] = cnt; cinfo[4 * j + 1] = best_k >> 1; cinfo[4 * j + 2] = n_fin; cinfo[4 * j + 3] = 1;
         best_out[j] = best;
     }
-}
-
-// one workgroup: c_start[j] = sum of cinfo[4 i] over i < j, c_start[n_views] = the total.  Integers: any order gives the same sums.
-__global__ __launch_bounds__(256) void pnp_count_scan_kernel(const int32_t *__restrict__ cinfo, const int64_t n_views, int64_t *__restrict__ c_start) {
-    __shared__ int64_t sm[256];
-    const int t = threadIdx.x;
-    int64_t carry = 0;
-    for (int64_t base = 0; base < n_views; base += 256) {
-        const int64_t v = base + t < n_views ? (int64_t)cinfo[4 * (base + t)] : 0;
-        sm[t] = v;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const int64_t add = t >= off ? sm[t - off] : 0;
-            __syncthreads();
-            sm[t] += add;
-            __syncthreads();
-        }
-        if (base + t < n_views) c_start[base + t] = carry + sm[t] - v;
-        carry += sm[255];
-        __syncthreads();
-    }
-    if (t == 0) c_start[n_views] = carry;
-}
-
-// one group per view: the flagged rows to [c_start[j], c_start[j + 1]) in their order.  The ballot is the wave's; a group reads its own 16 bits.
-template <int G>
-__global__ __launch_bounds__(256) void pnp_compact_kernel(const int32_t *__restrict__ key, const double2 *__restrict__ uv, const int64_t *__restrict__ start,
-                                                          const uint8_t *__restrict__ flag, const int64_t *__restrict__ c_start, const int64_t n_views,
-                                                          int32_t *__restrict__ c_key, double2 *__restrict__ c_uv) {
-    static_assert(G <= 16 && 64 % G == 0, "a group's bits are cut from the 64-bit ballot of its wave");
-    const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / G;
-    const int g = threadIdx.x & (G - 1);
-    if (j >= n_views) return;
-    const int shift = (threadIdx.x & 63) & ~(G - 1);
-    const int64_t s0 = start[j], s1 = start[j + 1], end = c_start[j + 1];
-    int64_t base = c_start[j];
-    for (int64_t c = s0; c < s1; c += G) {   // the trip count is the group's: the lanes of a group stay together
-        const int64_t o = c + g;
-        const bool f = o < s1 && flag[o] != 0;
-        const uint32_t bits = (uint32_t)(__ballot(f) >> shift) & ((1u << G) - 1u);
-        const int64_t pos = base + __popc(bits & ((1u << g) - 1u));
-        if (f && pos < end) {
-            c_key[pos] = key[o];
-            c_uv[pos] = uv[o];
-        }
-        base += __popc(bits);
-    }
-}
-
-__global__ __launch_bounds__(256) void pnp_consensus_finish_kernel(const int64_t *__restrict__ start, const int64_t n_views, int32_t *__restrict__ info) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_views) return;
-    info[3 * j + 2] = (int32_t)(start[j + 1] - start[j]);
 }
 
 }  // namespace pcs

@@ -10,11 +10,11 @@
 // nothing of a neighbour or of the launch geometry enters a result.  The hypothesis count is fixed: two runs agree bit for bit.
 //
 // tri_cons_used_kernel     one thread per point: how many of its H hypotheses are used — 0 below three views (the plain path),
-//                          min(H, V (V - 1) / 2) otherwise — into cinfo[4 j]; tri_count_scan_kernel turns them into the row bases of the
-//                          pseudo-table (integers).
+//                          min(H, V (V - 1) / 2) otherwise — into cinfo[4 j]; cons_count_scan_kernel (ba_consensus.hpp) turns them into
+//                          the row bases of the pseudo-table (integers).
 // tri_sample_kernel        one thread per (point, hypothesis): a pair of view positions a < b.  V (V - 1) / 2 <= H: all pairs in
 //                          lexicographic order, the hypotheses beyond the last pair unused.  Otherwise one 64-bit draw r of the counter-based
-//                          generator of ba_pnp_consensus.hpp (pnp_mix64) keyed by (seed, point index, V, hypothesis): a = r mod V,
+//                          generator of ba_consensus.hpp (cons_mix64) keyed by (seed, point index, V, hypothesis): a = r mod V,
 //                          b = (r >> 32) mod (V - 1) bumped past a; duplicate pairs are allowed.  The two (camera, uv) rows become a
 //                          pseudo-point of two views; an unused hypothesis repeats its start index, which the triangulation kernels answer
 //                          with three NaNs.
@@ -25,16 +25,13 @@
 //                          e^2 <= tau^2 at the winner with depth > 0, the inlier count and the number of finite hypotheses.  Fewer than
 //                          three views: flagged whole (consensus not used).  No finite candidate, or fewer than two inliers: no row is
 //                          kept and the kernels behind write NaN.
-// tri_count_scan_kernel    exclusive scan of the counts in cinfo[4 j] (integers: any order gives the same sums).  One workgroup of 1 024
-//                          threads, each with a contiguous stretch of the points: its sum, a scan of the 1 024 sums, its stretch again.
-//                          pnp_count_scan_kernel (ba_pnp_consensus.hpp) walks 256 points per step between barriers, which suits 6 400
-//                          views and costs 0.43 ms for 97 k points (profiles/r23).
-// pnp_compact_kernel (ba_pnp_consensus.hpp)   stable scatter of the flagged rows by ballot and popcount: the order inside a point is kept.
-// tri_consensus_finish_kernel   the full view count of the point back into info[2] (the refinement wrote the inlier count there).
+// Behind them cons_count_scan_kernel again and cons_compact_kernel<4> make the table of the flagged rows (the order inside a point is
+// kept), and cons_restore_count_kernel puts the full view count of the point back into info[2] (the refinement wrote the inlier count
+// there).  The walks of scoring and selection are those of every consensus stage (ba_consensus.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "ba_pnp_consensus.hpp"
+#include "ba_consensus.hpp"
 #include "ba_tri_refine.hpp"
 
 namespace pcs {
@@ -54,31 +51,6 @@ __global__ __launch_bounds__(256) void tri_cons_used_kernel(const int64_t *__res
     cinfo[4 * j] = (int32_t)tri_cons_used(start[j + 1] - start[j], H);
 }
 
-// c_start[j] = sum of cinfo[4 i] over i < j, c_start[n_pts] = the total.  Launched as ONE workgroup of TRI_SCAN_THREADS.
-constexpr int TRI_SCAN_THREADS = 1024;
-__global__ __launch_bounds__(TRI_SCAN_THREADS) void tri_count_scan_kernel(const int32_t *__restrict__ cinfo, const int64_t n_pts, int64_t *__restrict__ c_start) {
-    __shared__ int64_t sm[TRI_SCAN_THREADS];
-    const int t = threadIdx.x;
-    const int64_t chunk = (n_pts + TRI_SCAN_THREADS - 1) / TRI_SCAN_THREADS;
-    const int64_t lo = t * chunk < n_pts ? t * chunk : n_pts, hi = lo + chunk < n_pts ? lo + chunk : n_pts;
-    int64_t sum = 0;
-    for (int64_t i = lo; i < hi; ++i) sum += (int64_t)cinfo[4 * i];
-    sm[t] = sum;
-    __syncthreads();
-    for (int off = 1; off < TRI_SCAN_THREADS; off <<= 1) {
-        const int64_t add = t >= off ? sm[t - off] : 0;
-        __syncthreads();
-        sm[t] += add;
-        __syncthreads();
-    }
-    int64_t run = sm[t] - sum;
-    for (int64_t i = lo; i < hi; ++i) {
-        c_start[i] = run;
-        run += (int64_t)cinfo[4 * i];
-    }
-    if (t == TRI_SCAN_THREADS - 1) c_start[n_pts] = sm[t];
-}
-
 // the pair of hypothesis h of point j with V >= 3 views: positions a < b in [0, V)
 __device__ __forceinline__ void tri_cons_pair(const uint64_t seed, const int64_t j, const int64_t V, const int H, const int h, int64_t &a, int64_t &b) {
     if (V * (V - 1) / 2 <= (int64_t)H) {   // exhaustive: pair h in lexicographic order (V <= 23 here: at most 22 steps)
@@ -91,11 +63,11 @@ __device__ __forceinline__ void tri_cons_pair(const uint64_t seed, const int64_t
         b = a + 1 + rem;
         return;
     }
-    uint64_t k = pnp_mix64(seed + PNP_GOLDEN);
-    k = pnp_mix64(k ^ (uint64_t)j);
-    k = pnp_mix64(k ^ (uint64_t)V);
-    k = pnp_mix64(k ^ (uint64_t)(uint32_t)h);
-    const uint64_t r = pnp_mix64(k + PNP_GOLDEN);
+    uint64_t k = cons_mix64(seed + CONS_GOLDEN);
+    k = cons_mix64(k ^ (uint64_t)j);
+    k = cons_mix64(k ^ (uint64_t)V);
+    k = cons_mix64(k ^ (uint64_t)(uint32_t)h);
+    const uint64_t r = cons_mix64(k + CONS_GOLDEN);
     const int64_t p = (int64_t)(r % (uint64_t)V);
     int64_t q = (int64_t)((r >> 32) % (uint64_t)(V - 1));
     q += q >= p ? 1 : 0;
@@ -159,17 +131,13 @@ __global__ __launch_bounds__(256) void tri_score_kernel(const int32_t *__restric
             resid_out[2 * o + 1] = fin ? rv : __builtin_nan("");
         }
     } else {
-        double sum = 0.0;
-        if (fin) {
-            for (int64_t o = s0 + g; o < s1; o += G) {
+        double sum = INFINITY;
+        if (fin)
+            sum = cons_truncated_sum<G>(s0, s1, g, tau2, [&](const int64_t o, bool &usable) {
                 double ru, rv;
-                bool usable;
-                const double e2 = tri_consensus_e2(cam_tab, cam[o], uv[o], X0, X1, X2, ru, rv, usable);
-                sum += usable && e2 <= tau2 ? e2 : tau2;
-            }
-            sum = group_sum<G>(sum);
-        }
-        if (g == 0) score[gid] = fin ? sum : INFINITY;
+                return tri_consensus_e2(cam_tab, cam[o], uv[o], X0, X1, X2, ru, rv, usable);
+            });
+        if (g == 0) score[gid] = sum;
     }
 }
 
@@ -184,30 +152,18 @@ __global__ __launch_bounds__(256) void tri_select_kernel(const int32_t *__restri
     if (j >= n_pts) return;
     const int64_t s0 = start[j], s1 = start[j + 1], V = s1 - s0;
     if (V < TRI_CONS_MIN_VIEWS) {   // the plain path: every observation goes on
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 1;
+        cons_flag_all<G>(s0, s1, g, flag, 1);
         if (g == 0) {
             cinfo[4 * j + 0] = (int32_t)(V < 0 ? 0 : V); cinfo[4 * j + 1] = -1; cinfo[4 * j + 2] = 0; cinfo[4 * j + 3] = 0;
             best_out[j] = __builtin_nan("");
         }
         return;
     }
-    const double *sc = score + j * H;
-    double best = INFINITY;
-    int best_k = INT32_MAX, n_fin = 0;
-    for (int k = g; k < H; k += G) {   // ascending inside a lane: of equal scores the lower hypothesis stays
-        const double s = sc[k];
-        if (s < best) { best = s; best_k = k; }
-        n_fin += s < INFINITY ? 1 : 0;
-    }
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) {   // (score, hypothesis) is a total order: the minimum does not depend on the pairing
-        const double os = __shfl_xor(best, off, G);
-        const int ok = __shfl_xor(best_k, off, G);
-        if (os < best || (os == best && ok < best_k)) { best = os; best_k = ok; }
-    }
-    n_fin = group_sum_int<G>(n_fin);
+    double best;
+    int best_k, n_fin;
+    cons_argmin<G>(score + j * H, H, g, best, best_k, n_fin, [](int, const double s) { return s < INFINITY; });
     if (best_k == INT32_MAX) {   // no finite candidate: no row is kept, the kernels behind write NaN
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 0;
+        cons_flag_all<G>(s0, s1, g, flag, 0);
         if (g == 0) {
             cinfo[4 * j + 0] = 0; cinfo[4 * j + 1] = -1; cinfo[4 * j + 2] = n_fin; cinfo[4 * j + 3] = 1;
             best_out[j] = INFINITY;
@@ -216,31 +172,19 @@ __global__ __launch_bounds__(256) void tri_select_kernel(const int32_t *__restri
     }
     const double *X = cand + 3 * (j * H + best_k);
     const double X0 = X[0], X1 = X[1], X2 = X[2];
-    int cnt = 0;
-    for (int64_t o = s0 + g; o < s1; o += G) {
+    const auto e2_of = [&](const int64_t o, bool &usable) {
         double ru, rv;
-        bool usable;
-        const double e2 = tri_consensus_e2(cam_tab, cam[o], uv[o], X0, X1, X2, ru, rv, usable);
-        cnt += usable && e2 <= tau2 ? 1 : 0;
-    }
-    cnt = group_sum_int<G>(cnt);
-    const bool keep = cnt >= 2;   // one row determines no point: nothing is kept of such a winner
-    for (int64_t o = s0 + g; o < s1; o += G) {
-        double ru, rv;
-        bool usable;
-        const double e2 = tri_consensus_e2(cam_tab, cam[o], uv[o], X0, X1, X2, ru, rv, usable);
-        flag[o] = keep && usable && e2 <= tau2 ? 1 : 0;
-    }
+        return tri_consensus_e2(cam_tab, cam[o], uv[o], X0, X1, X2, ru, rv, usable);
+    };
+    // This stage alone counts before it flags: one row determines no point, so nothing is kept of a winner with fewer than two inliers.
+    const int cnt = cons_flag_inliers<G>(s0, s1, g, tau2, (uint8_t *)nullptr, e2_of);
+    const bool keep = cnt >= 2;
+    if (keep) cons_flag_inliers<G>(s0, s1, g, tau2, flag, e2_of);
+    else cons_flag_all<G>(s0, s1, g, flag, 0);
     if (g == 0) {
         cinfo[4 * j + 0] = keep ? cnt : 0; cinfo[4 * j + 1] = best_k; cinfo[4 * j + 2] = n_fin; cinfo[4 * j + 3] = 1;
         best_out[j] = best;
     }
-}
-
-__global__ __launch_bounds__(256) void tri_consensus_finish_kernel(const int64_t *__restrict__ start, const int64_t n_pts, int32_t *__restrict__ info) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_pts) return;
-    info[3 * j + 2] = (int32_t)(start[j + 1] - start[j]);
 }
 
 }  // namespace pcs

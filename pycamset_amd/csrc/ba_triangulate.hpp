@@ -22,6 +22,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_group.hpp"
+
 namespace pcs {
 
 constexpr int TRI_CAM_STRIDE = 32;  // P 12 | (10 unused) | fx cx fy cy | k0 k1 p0 p1 k2 | pad
@@ -89,13 +91,6 @@ __device__ __forceinline__ void givens_insert(double (&R)[4][4], double (&row)[4
 // with Givens rotations = QR of stacked triangular factors, still backward stable); the 4-vector and
 // norm sums of the inverse iteration are group reductions.  Pass 1 caches each view's Householder row
 // r_i and alpha_i (scratch, 48 B per observation) so the later passes do no sqrt / divide per view.
-template <int G>
-__device__ __forceinline__ double group_sum(double x) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, G);
-    return x;
-}
-
 template <int G>
 __global__ __launch_bounds__(256) void triangulate_kernel(const int32_t *__restrict__ cam, const double2 *__restrict__ uv,
                                                           const int64_t *__restrict__ start, const double *__restrict__ cam_tab,

@@ -8,8 +8,9 @@
 //
 // tv_undistort_kernel    one thread per correspondence: both pixels through undistort5 (ba_triangulate.hpp) to undistorted pixels, written
 //                        once and read by every later stage.
-// tv_hypothesis_kernel   one group of 16 lanes per (pair, hypothesis): eight rows drawn by pnp_sample_positions (stream key: the pair
-//                        index), the eight-point fit (tv_eight_point), the essential projection, F = K_b^-T E K_a^-1 and a usable flag.
+// tv_hypothesis_kernel   one group of 16 lanes per (pair, hypothesis): eight rows drawn by cons_sample_positions (ba_consensus.hpp;
+//                        stream key: the pair index), the eight-point fit (tv_eight_point), the essential projection,
+//                        F = K_b^-T E K_a^-1 and a usable flag.
 // tv_score_kernel<G>     one group per (pair, hypothesis): sum min(e^2, tau^2) of the Sampson distance over all rows of the pair; +inf
 //                        for an unusable hypothesis.
 // tv_select_kernel<G>    one group per pair: the lowest score wins, ties go to the lower hypothesis; inlier flags e^2 <= tau^2, their count.
@@ -27,8 +28,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ba_consensus.hpp"
 #include "ba_pnp.hpp"
-#include "ba_pnp_consensus.hpp"
 #include "ba_triangulate.hpp"
 
 namespace pcs {
@@ -272,8 +273,8 @@ __global__ __launch_bounds__(256) void tv_hypothesis_kernel(const double4 *__res
     double F[9];
     bool ok = false;
     if (n >= TV_SAMPLE) {   // the same in every lane of the group
-        int64_t pick[PNP_CONS_MAX_SAMPLE];
-        pnp_sample_positions(seed, (int32_t)p, n, h, TV_SAMPLE, pick);
+        int64_t pick[CONS_MAX_SAMPLE];
+        cons_sample_positions(seed, (int32_t)p, n, h, TV_SAMPLE, pick);
         int64_t mine = 0;
 #pragma unroll
         for (int i = 0; i < TV_SAMPLE; ++i)
@@ -310,12 +311,10 @@ __global__ __launch_bounds__(256) void tv_score_kernel(const double4 *__restrict
         double F[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) F[i] = hyp_F[9 * gid + i];
-        sum = 0.0;
-        for (int64_t o = s0 + g; o < s1; o += G) {
-            const double e2 = tv_sampson(F, und[o]);
-            sum += e2 <= tau2 ? e2 : tau2;   // a non-finite distance counts as an outlier
-        }
-        sum = group_sum<G>(sum);
+        sum = cons_truncated_sum<G>(s0, s1, g, tau2, [&](const int64_t o, bool &usable) {
+            usable = true;   // a non-finite distance fails the comparison and counts as an outlier
+            return tv_sampson(F, und[o]);
+        });
     }
     if (g == 0) score[gid] = sum;
 }
@@ -332,21 +331,10 @@ __global__ __launch_bounds__(256) void tv_select_kernel(const double4 *__restric
     const int64_t p = order[gid];
     const int64_t s0 = start[p], s1 = start[p + 1];
     double best = INFINITY;
-    int best_k = INT32_MAX;
-    if (s1 - s0 >= n_min) {
-        for (int k = g; k < H; k += G) {   // ascending inside a lane: of equal scores the lower hypothesis stays
-            const double s = score[p * H + k];
-            if (s < best) { best = s; best_k = k; }
-        }
-#pragma unroll
-        for (int off = G / 2; off > 0; off >>= 1) {   // (score, hypothesis) is a total order: the minimum does not depend on the pairing
-            const double os = __shfl_xor(best, off, G);
-            const int ok = __shfl_xor(best_k, off, G);
-            if (os < best || (os == best && ok < best_k)) { best = os; best_k = ok; }
-        }
-    }
+    int best_k = INT32_MAX, n_fin;
+    if (s1 - s0 >= n_min) cons_argmin<G>(score + p * H, H, g, best, best_k, n_fin, cons_count_none);
     if (best_k == INT32_MAX) {
-        for (int64_t o = s0 + g; o < s1; o += G) flag[o] = 0;
+        cons_flag_all<G>(s0, s1, g, flag, 0);
         if (g == 0) {
             sel[2 * p + 0] = 0; sel[2 * p + 1] = -1;
             best_out[p] = s1 - s0 >= n_min ? INFINITY : __builtin_nan("");
@@ -356,13 +344,10 @@ __global__ __launch_bounds__(256) void tv_select_kernel(const double4 *__restric
     double F[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) F[i] = hyp_F[9 * (p * H + best_k) + i];
-    int cnt = 0;
-    for (int64_t o = s0 + g; o < s1; o += G) {
-        const bool in = tv_sampson(F, und[o]) <= tau2;
-        flag[o] = in ? 1 : 0;
-        cnt += in ? 1 : 0;
-    }
-    cnt = group_sum_int<G>(cnt);
+    const int cnt = cons_flag_inliers<G>(s0, s1, g, tau2, flag, [&](const int64_t o, bool &usable) {
+        usable = true;
+        return tv_sampson(F, und[o]);
+    });
     if (g == 0) {
         sel[2 * p + 0] = cnt; sel[2 * p + 1] = best_k;
         best_out[p] = best;
@@ -454,7 +439,7 @@ __global__ __launch_bounds__(256) void tv_final_kernel(const double4 *__restrict
             int win = 0;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                cnt[c] = group_sum_int<G>(cnt[c]);
+                cnt[c] = group_sum<G>(cnt[c]);
                 ang[c] = group_sum<G>(ang[c]);
             }
             double ang_w = ang[0];

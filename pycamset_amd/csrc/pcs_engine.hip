@@ -41,6 +41,7 @@
 #include "ba_triangulate.hpp"
 #include "ba_tri_refine.hpp"
 #include "ba_pnp.hpp"
+#include "ba_consensus.hpp"
 #include "ba_pnp_consensus.hpp"
 #include "ba_tri_consensus.hpp"
 #include "ba_rigpose.hpp"

@@ -437,3 +437,13 @@ static int enqueue_group_order(const int64_t *d_start, int64_t n, int32_t *d_his
     HIPCHK(hipGetLastError());
     return PCS_OK;
 }
+
+// Behind the select kernel of a consensus stage with G lanes per problem: c_start = the exclusive scan of the inlier counts cinfo[4 j],
+// then the flagged rows of both columns of the table to (c_col, c_uv) in their order.  The caller checks hipGetLastError.
+template <int G>
+static void enqueue_compact_flagged(const int32_t *col, const double2 *uv, const int64_t *start, const uint8_t *flag, const int32_t *cinfo, int64_t n,
+                                    int64_t *c_start, int32_t *c_col, double2 *c_uv, hipStream_t s) {
+    hipLaunchKernelGGL(cons_count_scan_kernel, dim3(1), dim3(CONS_SCAN_THREADS), 0, s, cinfo, n, c_start);
+    hipLaunchKernelGGL((cons_compact_kernel<G>), dim3((unsigned)((n * G + 255) / 256)), dim3(256), 0, s, col, uv, start, flag, (const int64_t *)c_start, n,
+                       c_col, c_uv);
+}

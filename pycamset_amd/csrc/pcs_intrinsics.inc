@@ -119,10 +119,10 @@ constexpr int INTR_CONS_MAX_HYP = 4096;   // hypotheses per group that pcs_intr_
 // before anything changes: a refused call keeps the previous setting.
 int pcs_intr_set_consensus(pcs_intrinsics_estimator *p, int n_hypotheses, int sample_size, double inlier_px, uint64_t seed) {
     if (!p) return fail(PCS_ERR_ARG, "pcs_intr_set_consensus: NULL handle");
-    if (n_hypotheses < 0 || n_hypotheses > INTR_CONS_MAX_HYP || sample_size < 4 || sample_size > PNP_CONS_MAX_SAMPLE || !std::isfinite(inlier_px) ||
+    if (n_hypotheses < 0 || n_hypotheses > INTR_CONS_MAX_HYP || sample_size < 4 || sample_size > CONS_MAX_SAMPLE || !std::isfinite(inlier_px) ||
         !(inlier_px > 0.0))
         return fail(PCS_ERR_ARG, "pcs_intr_set_consensus: bad arguments (0 <= n_hypotheses <= %d, 4 <= sample_size <= %d, inlier_px finite and > 0)",
-                    INTR_CONS_MAX_HYP, PNP_CONS_MAX_SAMPLE);
+                    INTR_CONS_MAX_HYP, CONS_MAX_SAMPLE);
     p->cons_hyp = n_hypotheses;
     p->cons_sample = sample_size;
     p->cons_px = inlier_px;
@@ -185,9 +185,8 @@ static int intr_run_consensus(pcs_intrinsics_estimator *p, int model, int min_po
         hipLaunchKernelGGL((intr_select_kernel<INTR_G>), groups, dim3(256), 0, s, key, uv, start, pts, ng, (int)H, (int)std::max<int64_t>(S, min_points),
                            p->h_H.as<const double>(), p->h_frame.as<const double>(), p->score.as<const double>(), tau2, p->flag.as<uint8_t>(),
                            p->consinfo.as<int32_t>(), p->best.as<double>());
-        hipLaunchKernelGGL(pnp_count_scan_kernel, dim3(1), dim3(256), 0, s, p->consinfo.as<const int32_t>(), ng, p->c_start.as<int64_t>());
-        hipLaunchKernelGGL((pnp_compact_kernel<INTR_G>), groups, dim3(256), 0, s, key, uv, start, p->flag.as<const uint8_t>(), p->c_start.as<const int64_t>(), ng,
-                           p->c_key.as<int32_t>(), p->c_uv.as<double2>());
+        enqueue_compact_flagged<INTR_G>(key, uv, start, p->flag.as<const uint8_t>(), p->consinfo.as<const int32_t>(), ng, p->c_start.as<int64_t>(),
+                                        p->c_key.as<int32_t>(), p->c_uv.as<double2>(), s);
         hipLaunchKernelGGL((intr_homography_kernel<INTR_G>), groups, dim3(256), 0, s, p->c_key.as<const int32_t>(), p->c_uv.as<const double2>(),
                            p->c_start.as<const int64_t>(), pts, ng, min_points, d_H, out[INTR_SLOT_FRAME].as<double>(), d_ginfo, d_pix);
     }
@@ -196,7 +195,7 @@ static int intr_run_consensus(pcs_intrinsics_estimator *p, int model, int min_po
                        (const double *)d_pix, p->cam_start.as<const int64_t>(), d_res, nc, model, out[INTR_SLOT_INTR].as<double>(),
                        out[INTR_SLOT_CINFO].as<int32_t>(), out[INTR_SLOT_EIG].as<double>());
     if (ng > 0)
-        hipLaunchKernelGGL(intr_consensus_finish_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, p->start.as<const int64_t>(), ng, d_ginfo);
+        hipLaunchKernelGGL(cons_restore_count_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, p->start.as<const int64_t>(), ng, d_ginfo, 2, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(p->timer.e1, s));
     p->timer.timed = true;

@@ -113,10 +113,10 @@ static std::array<OutSlot, PNP_SLOTS> pnp_out_slots(pcs_pose_estimator *p, void 
 // before anything changes: a refused call keeps the previous setting.
 int pcs_pnp_set_consensus(pcs_pose_estimator *p, int n_hypotheses, int sample_size, double inlier_px, uint64_t seed) {
     if (!p) return fail(PCS_ERR_ARG, "pcs_pnp_set_consensus: NULL handle");
-    if (n_hypotheses < 0 || n_hypotheses > PNP_CONS_MAX_HYP || sample_size < 4 || sample_size > PNP_CONS_MAX_SAMPLE || !std::isfinite(inlier_px) ||
+    if (n_hypotheses < 0 || n_hypotheses > PNP_CONS_MAX_HYP || sample_size < 4 || sample_size > CONS_MAX_SAMPLE || !std::isfinite(inlier_px) ||
         !(inlier_px > 0.0))
         return fail(PCS_ERR_ARG, "pcs_pnp_set_consensus: bad arguments (0 <= n_hypotheses <= %d, 4 <= sample_size <= %d, inlier_px finite and > 0)",
-                    PNP_CONS_MAX_HYP, PNP_CONS_MAX_SAMPLE);
+                    PNP_CONS_MAX_HYP, CONS_MAX_SAMPLE);
     p->cons_hyp = n_hypotheses;
     p->cons_sample = sample_size;
     p->cons_px = inlier_px;
@@ -180,9 +180,8 @@ static int pnp_run_consensus(pcs_pose_estimator *p, int max_iter, double ftol, d
                        p->h_alt.as<const double>(), tau2, p->score.as<double>(), (double *)nullptr);
     hipLaunchKernelGGL((pnp_select_kernel<PNP_G>), view_groups, dim3(256), 0, s, key, uv, start, vcam, tab, pts, nv, (int)H, (int)S, p->h_init.as<const double>(),
                        p->h_alt.as<const double>(), p->score.as<const double>(), tau2, p->flag.as<uint8_t>(), p->cinfo.as<int32_t>(), p->best.as<double>());
-    hipLaunchKernelGGL(pnp_count_scan_kernel, dim3(1), dim3(256), 0, s, p->cinfo.as<const int32_t>(), nv, p->c_start.as<int64_t>());
-    hipLaunchKernelGGL((pnp_compact_kernel<PNP_G>), view_groups, dim3(256), 0, s, key, uv, start, p->flag.as<const uint8_t>(), p->c_start.as<const int64_t>(), nv,
-                       p->c_key.as<int32_t>(), p->c_uv.as<double2>());
+    enqueue_compact_flagged<PNP_G>(key, uv, start, p->flag.as<const uint8_t>(), p->cinfo.as<const int32_t>(), nv, p->c_start.as<int64_t>(), p->c_key.as<int32_t>(),
+                                   p->c_uv.as<double2>(), s);
     HIPCHK(hipGetLastError());
     if ((rc = enqueue_group_order(p->c_start.as<int64_t>(), nv, p->hist.as<int32_t>(), p->c_order.as<int32_t>(), s))) return rc;
     double *pose_init = out[PNP_SLOT_INIT].as<double>(), *pose_alt = out[PNP_SLOT_ALT].as<double>();
@@ -192,7 +191,7 @@ static int pnp_run_consensus(pcs_pose_estimator *p, int max_iter, double ftol, d
                        p->c_start.as<const int64_t>(), vcam, tab, pts, nv, p->c_order.as<const int32_t>(), (const double *)pose_init, (const double *)pose_alt,
                        max_iter, ftol, xtol, gtol, min_points, out[PNP_SLOT_POSE].as<double>(), out[PNP_SLOT_RMS].as<double>(), out[PNP_SLOT_INFO].as<int32_t>(),
                        (double *)nullptr);
-    hipLaunchKernelGGL(pnp_consensus_finish_kernel, per_view, dim3(256), 0, s, start, nv, out[PNP_SLOT_INFO].as<int32_t>());
+    hipLaunchKernelGGL(cons_restore_count_kernel, per_view, dim3(256), 0, s, start, nv, out[PNP_SLOT_INFO].as<int32_t>(), 3, 2);
     if (want_resid)   // of ALL observations at the returned pose, outliers included: the one-candidate mode of the scoring kernel
         hipLaunchKernelGGL((pnp_score_kernel<PNP_G, true>), view_groups, dim3(256), 0, s, key, uv, start, vcam, tab, pts, nv, 1,
                            (const double *)out[PNP_SLOT_POSE].as<double>(), (const double *)nullptr, tau2, (double *)nullptr, out[PNP_SLOT_RESID].as<double>());

@@ -302,7 +302,7 @@ static int tri_run_consensus(pcs_triangulator *t, double *d_pts, void *stream) {
     const dim3 per_pt((unsigned)((np + 255) / 256)), pt_groups((unsigned)((np * G + 255) / 256)), hyp_groups((unsigned)((nh * G + 255) / 256));
     // c_start first holds the row bases of the pseudo-table (the scan of the used counts), then the starts of the compacted table
     hipLaunchKernelGGL(tri_cons_used_kernel, per_pt, dim3(256), 0, s, start, np, (int)H, t->cinfo.as<int32_t>());
-    hipLaunchKernelGGL(tri_count_scan_kernel, dim3(1), dim3(TRI_SCAN_THREADS), 0, s, t->cinfo.as<const int32_t>(), np, t->c_start.as<int64_t>());
+    hipLaunchKernelGGL(cons_count_scan_kernel, dim3(1), dim3(CONS_SCAN_THREADS), 0, s, t->cinfo.as<const int32_t>(), np, t->c_start.as<int64_t>());
     hipLaunchKernelGGL(tri_sample_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, s, cam, uv, start, t->c_start.as<const int64_t>(), np, (int)H,
                        t->cons_seed, t->s_cam.as<int32_t>(), t->s_uv.as<double2>(), t->s_start.as<int64_t>());
     tri_launch_dlt(t, launch, s, nullptr, nullptr, t->s_cam.as<const int32_t>(), t->s_uv.as<const double>(), t->s_start.as<const int64_t>(),
@@ -311,9 +311,8 @@ static int tri_run_consensus(pcs_triangulator *t, double *d_pts, void *stream) {
                        t->score.as<double>(), (double *)nullptr);
     hipLaunchKernelGGL((tri_select_kernel<G>), pt_groups, dim3(256), 0, s, cam, uv, start, tab, np, (int)H, t->h_pts.as<const double>(),
                        t->score.as<const double>(), tau2, t->flag.as<uint8_t>(), t->cinfo.as<int32_t>(), t->best.as<double>());
-    hipLaunchKernelGGL(tri_count_scan_kernel, dim3(1), dim3(TRI_SCAN_THREADS), 0, s, t->cinfo.as<const int32_t>(), np, t->c_start.as<int64_t>());
-    hipLaunchKernelGGL((pnp_compact_kernel<G>), pt_groups, dim3(256), 0, s, cam, uv, start, t->flag.as<const uint8_t>(), t->c_start.as<const int64_t>(), np,
-                       t->c_cam.as<int32_t>(), t->c_uv.as<double2>());
+    enqueue_compact_flagged<G>(cam, uv, start, t->flag.as<const uint8_t>(), t->cinfo.as<const int32_t>(), np, t->c_start.as<int64_t>(), t->c_cam.as<int32_t>(),
+                               t->c_uv.as<double2>(), s);
     HIPCHK(hipGetLastError());
     if (sorted)
         if ((rc = enqueue_group_order(t->c_start.as<int64_t>(), np, t->hist.as<int32_t>(), t->c_order.as<int32_t>(), s))) return rc;
@@ -426,7 +425,7 @@ int pcs_tri_refine(pcs_triangulator *t, int max_iter, double ftol, double xtol, 
                                t->refine_loss.args(), t->rcost.as<double>());
         }
         // what callers see: the full view count in info, and the residuals of ALL observations at the returned point, outliers included
-        hipLaunchKernelGGL(tri_consensus_finish_kernel, dim3((unsigned)((t->n_pts + 255) / 256)), dim3(256), 0, s, t->cur_start, t->n_pts, info);
+        hipLaunchKernelGGL(cons_restore_count_kernel, dim3((unsigned)((t->n_pts + 255) / 256)), dim3(256), 0, s, t->cur_start, t->n_pts, info, 3, 2);
         if (want_resid)
             hipLaunchKernelGGL((tri_score_kernel<TRI_CONS_G, true>), grid, dim3(256), 0, s, t->cur_cam, (const double2 *)t->cur_uv, t->cur_start,
                                t->tab.as<const double>(), t->n_pts, 1, (const double *)out[TRI_SLOT_POINTS].as<double>(), 0.0, (double *)nullptr,

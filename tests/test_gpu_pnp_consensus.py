@@ -6,6 +6,8 @@ Tolerances.  Start and LM behind the stage are the unchanged kernels on the comp
 outputs are compared BITWISE with a plain run on those rows.  The winner's score is a sum of n <= 54 squared pixel errors of a pose that
 the device and NumPy compute with different rounding (reciprocals, summation order: 1e-6 relative in the start, the figure of
 tests/test_gpu_pnp.py, damped by the score's flatness near its minimum); the issue sets 1e-9 relative, which is asserted."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -13,7 +15,9 @@ from pycamset_amd import _capi, handlers, synthetic
 from pycamset_amd import compiled_helpers as hip_ch
 from pycamset_amd.detections import TargetDetection
 from tests import pnp_consensus_inputs as inp
+from tests import pnp_consensus_reference as cons_ref
 from tests import pnp_reference as ref
+from tests.intr_consensus_inputs import move_rows
 from tests.test_pnp_consensus_reference import restated
 from tests.test_pnp_reference import CUBE, DuckCamset, DuckTarget, assert_poses_close, pose_error, true_view_poses, truth_rig
 
@@ -223,6 +227,62 @@ def test_shapes_at_which_the_kernels_can_go_wrong():
     assert np.array_equal(one.inliers, base.inliers[det[:, 1] == 4]) and one.n_inliers[0, 4] == base.n_inliers[0, 4]
     e = run(det[:0], **CONS)
     assert np.all(np.isnan(e.poses)) and np.all(e.status == 0) and np.all(e.n_points == 0) and e.inliers.shape == (0,) and np.all(e.n_inliers == 0)
+
+
+# ---- view counts around one view per thread of the scan ------------------------------------------------------------------------------------
+SCAN_VIEWS = (1, 1023, 1025, 2049)
+SCAN_CONS = dict(consensus=4, sample_size=6, inlier_px=8.0, seed=0)
+# Chosen on the CPU: with these seeds tests/pnp_consensus_reference.py finds exactly the unmoved rows in each of the 2 049 views and
+# estimates every one of them from those rows, at 0.1 px of noise and at 0.3 px.  The linear start of six random corners is all a view
+# of six rows has (every sample is the view) and amplifies the noise; 0.1 px leaves a factor of three to the device's other rounding.
+SCAN_RIG_SEED, SCAN_DRAW_SEED = 41, 1
+SCAN_TARGET, SCAN_NOISE_PX = BOARD, 0.1
+
+
+@functools.lru_cache(maxsize=None)
+def scan_table():
+    """One camera, 2 049 images of the board of 17 x 17 corners, 6 to 12 detections per view by a seeded draw; a table of V views is its first
+    V images.  In every 7th view two detections are moved by 30 to 200 px.  With four hypotheses a moved row can sit in every sample of
+    its view, and a view of fewer than eight rows has no sample of six without one, so a view that is hit draws its count from 8 to 12
+    and its two moved rows come from outside the sample of hypothesis 0 (the sampler is a pure function of seed, camera, count and
+    hypothesis), which the test asserts.  -> (table, clean mask, intrinsics)."""
+    V, K = max(SCAN_VIEWS), SCAN_TARGET.shape[0]
+    rig = synthetic.make_rig("pnp-scan", 1, V, SCAN_TARGET, seed=SCAN_RIG_SEED, noise_px=SCAN_NOISE_PX)
+    det = rig.detections.copy()
+    assert det.shape[0] == V * K and np.array_equal(det[:, 1], np.repeat(np.arange(V), K))   # image by image, keys ascending
+    rng = np.random.default_rng(SCAN_DRAW_SEED)
+    keep, clean = np.zeros(det.shape[0], dtype=bool), np.ones(det.shape[0], dtype=bool)
+    for i in range(V):
+        hit = i % 7 == 0
+        n = int(rng.integers(8 if hit else 6, 13))
+        rows = np.sort(rng.permutation(np.arange(i * K, (i + 1) * K))[:n])
+        keep[rows] = True
+        if hit:
+            move_rows(det, clean, np.delete(rows, cons_ref.sample_positions(SCAN_CONS["seed"], 0, n, 0, 6)), 2, rng)
+    return det[keep], clean[keep], rig.intr_true
+
+
+@pytest.mark.parametrize("V", SCAN_VIEWS)
+def test_view_counts_on_either_side_of_one_view_per_scan_thread(V):
+    """The scan of the inlier counts gives each of its 1 024 threads a contiguous stretch of the views: V = 1 leaves 1 023 of them an
+    empty stretch, 1 023 and 1 025 lie on either side of one view per thread, 2 049 cuts the last stretch short.  As in
+    test_corrupted_table_gives_the_bits_of_the_clean_rows: exactly the unmoved rows, and the bits of the plain run on them."""
+    det, clean, intr = scan_table()
+    first = det[:, 1] < V
+    det, clean = det[first], clean[first]
+    counts = per_view_counts(det, np.ones_like(clean), 1, V)
+    assert counts.min() >= 6 and counts.max() <= 12 and (V == 1 or np.unique(counts).shape[0] == 7)
+    moved = per_view_counts(det, ~clean, 1, V)[0]
+    assert np.array_equal(moved, np.where(np.arange(V) % 7 == 0, 2, 0))
+    for i in np.nonzero(moved)[0]:   # at least one sample of the view holds no moved row (rows of a view: keys ascending, as on the device)
+        c = clean[det[:, 1] == i]
+        assert any(c[cons_ref.sample_positions(SCAN_CONS["seed"], 0, c.shape[0], h, 6)].all() for h in range(SCAN_CONS["consensus"]))
+    want = hip_ch.estimate_view_poses(det[clean], SCAN_TARGET, intr, n_imgs=V)
+    assert np.all(want.status != hip_ch.PNP_NOT_ESTIMATED)   # the input: every view is estimated from its unmoved rows
+    got = hip_ch.estimate_view_poses(det, SCAN_TARGET, intr, n_imgs=V, **SCAN_CONS)
+    assert np.array_equal(got.inliers, clean)
+    assert_same_bits(got, want)
+    assert np.array_equal(got.n_inliers, want.n_points) and np.array_equal(got.n_points, counts)
 
 
 def test_handle_state_between_consensus_and_plain_runs():

@@ -20,7 +20,7 @@ MIN_VIEWS = 3
 
 
 def mix64(z: int) -> int:
-    """The splitmix64 finaliser on Python integers (pnp_mix64)."""
+    """The splitmix64 finaliser on Python integers (cons_mix64)."""
     z &= MASK
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & MASK
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & MASK
