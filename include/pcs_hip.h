@@ -1127,6 +1127,70 @@ int pcs_stereo_sgm(pcs_stereo_matcher *p, int64_t n, int width, int height, cons
 int pcs_stereo_set_sgm_workspace(pcs_stereo_matcher *p, int64_t bytes);
 
 /* ------------------------------------------------------------------------------------------------
+ * Depth-map fusion across views: geometric consistency filter and merged cloud (csrc/ba_fusion.hpp).  Since
+ * pcs_version() 125.
+ * Replaces: the step the reference leaves to an external multi-view program.  It writes the rig out (CameraSet.write_to_txt,
+ *           cameras/camera_set.py:235-272; Camera.to_MVSnet_txt, cameras/camera.py:130-160; calc_pairs / write_pair_file,
+ *           reconstruction/acmmp_utils.py:24-83) and reads that program's fused cloud back.  What the program adds over per-view depth maps
+ *           is the geometric consistency check and fusion of MVSNet (filter_depth) / ACMMP / COLMAP; the rule below is the library's own,
+ *           in that spirit.  tests/fusion_reference.py states it in NumPy.
+ * Inputs.  V views of one size W x H.  View v is a DISTORTION-FREE pinhole, K_v = [fx, cx, fy, cy] and [R_v | t_v] world -> view: the maps
+ * are those of undistorted or rectified images (pixel (x, y) is the ray ((x - cx) / fx, (y - cy) / fy, 1)).  D_v (H, W) is a z-depth map,
+ * float32 or float64; a depth is INVALID when it is NaN, +-inf or <= 0.  Every view has an ordered neighbour list in CSR form (nbr_start
+ * (V + 1), nbr, int32) of at most 32 views, never itself, none twice.  Scalars px_tol > 0, rel_tol > 0, min_views in [1, 32].
+ * The rule.  All arithmetic is FP64, plain IEEE operations in the order written (no contraction), sums of three products taken left to
+ * right.  For the reference pixel (i, x, y) with valid z = D_i[y, x]:
+ *   1. back-projection   c = (z ((x - cx_i) / fx_i) - t_i0, z ((y - cy_i) / fy_i) - t_i1, z - t_i2), X = R_i^T c.
+ *   2. each neighbour j in list order is CONSISTENT when none of these fails (a comparison with a NaN fails):
+ *        Y = R_j X + t_j; fail unless Y_z > 0.
+ *        (u, v) = (fx_j (Y_x / Y_z) + cx_j, fy_j (Y_y / Y_z) + cy_j), q = (floor(u + 0.5), floor(v + 0.5)); fail unless q lies in
+ *        [0, W) x [0, H).
+ *        z_j = D_j[q]; fail if z_j is invalid.
+ *        X_j = the back-projection of q at z_j in view j (step 1 with j's parameters); Y' = R_i X_j + t_i; fail unless Y'_z > 0.
+ *        (x', y') = the projection of Y' by K_i; fail unless (x' - x)^2 + (y' - y)^2 <= px_tol^2 and |Y'_z - z| <= rel_tol z.
+ *   3. support (uint32) has bit k set when the k-th neighbour of the list is consistent; count = popcount(support); the pixel is KEPT
+ *      iff count >= min_views.
+ *   4. fused point F = (X + sum of X_j over the consistent neighbours, in list order) / (count + 1), each coordinate divided.  With T
+ *      (3 x 4, rigid) the point written is T (F, 1); it is rounded once to float32 or left as float64, and is three NaNs where the pixel
+ *      is not in the mask.  fused_depth = the z of the UNTRANSFORMED F in view i, (R_i F + t_i)_z, NaN where the pixel is not in the mask.
+ *   5. unique (opt-in): a kept pixel (i, x, y) is a DUPLICATE when, for some consistent neighbour j with j < i, the partner pixel q of
+ *      step 2 is itself kept by step 3 — kept BEFORE any duplicate marking, so the result does not depend on an order of evaluation.
+ *      Duplicates leave the mask: the lowest view owns a surface element.
+ *   6. status (uint8): PCS_FUSE_INVALID_DEPTH (the input depth is invalid; steps 1 to 5 are not taken and support = count = 0),
+ *      PCS_FUSE_FEW_VIEWS (a valid depth with count < min_views), PCS_FUSE_DUPLICATE.  mask = 1 iff status = 0.
+ * No atomics; two runs give identical bits.
+ *   pcs_fuse_create          a handle on `device` (no counterpart); it owns the view table, the neighbour lists and the workspace (the
+ *                            4-byte support word per pixel when the caller does not ask for it, and the block counts of d_counts)
+ *   pcs_fuse_destroy         frees the handle (no counterpart)
+ *   pcs_fuse_set_views       what write_to_txt / to_MVSnet_txt hand to the external program: the intrinsics and extrinsics of every
+ *                            view.  n_views in [1, 32767] (the compaction's limit), width and height in [1, 65535]; K HOST (n_views, 4),
+ *                            P HOST (n_views, 12) = [R | t] row-major; both are copied.  Finite, fx and fy != 0.  New views drop the
+ *                            neighbour lists.
+ *   pcs_fuse_set_neighbours  what write_pair_file hands over: HOST CSR lists for the n = n_views views.  nbr_start runs from 0 and never
+ *                            decreases, at most 32 entries per view, every index in [0, n), no view its own neighbour, none twice.
+ *   pcs_fuse_run             the external program's consistency filter and fusion.  d_depth (n_views, height, width) of depth_dtype;
+ *                            unique 0 or 1; T HOST 3 x 4 or NULL; d_points (n_views, height, width, 3) of points_dtype; d_mask uint8.
+ *                            Optional (NULL: not written): d_count uint8, d_support uint32, d_status uint8, d_fused_depth of fused_dtype
+ *                            (all (n_views, height, width)) and d_counts (n_views) int64 on the DEVICE, the mask's sum per view as
+ *                            pcs_stereo_reproject fills it, so that pcs_stereo_compact can follow unchanged.  dtypes: PCS_F64 or PCS_F32.
+ *                            Two launches: the check of every view, then (unique) the duplicate marking, which reads the support words.
+ *   pcs_fuse_last_kernel_ms  device time of the last run (no counterpart): the check kernel, the duplicate kernel (0 without unique) and
+ *                            the whole call, the counts included
+ * Every argument is checked on the host before the device is touched (PCS_ERR_ARG; pcs_last_error names the argument); the handle is
+ * looked at last.  All buffers are DEVICE buffers of the caller unless marked HOST; a run is queued on `stream` (NULL = the handle's).
+ */
+typedef struct pcs_depth_fuser pcs_depth_fuser;
+enum { PCS_FUSE_INVALID_DEPTH = 1, PCS_FUSE_FEW_VIEWS = 2, PCS_FUSE_DUPLICATE = 4, PCS_FUSE_MAX_NEIGHBOURS = 32 };
+int pcs_fuse_create(pcs_depth_fuser **out, int device);
+int pcs_fuse_destroy(pcs_depth_fuser *p);
+int pcs_fuse_set_views(pcs_depth_fuser *p, int64_t n_views, int width, int height, const double *K, const double *P);
+int pcs_fuse_set_neighbours(pcs_depth_fuser *p, const int32_t *nbr_start, const int32_t *nbr, int64_t n);
+int pcs_fuse_run(pcs_depth_fuser *p, const void *d_depth, int depth_dtype, double px_tol, double rel_tol, int min_views, int unique, const double *T, void *d_points,
+                 int points_dtype, uint8_t *d_mask, uint8_t *d_count, uint32_t *d_support, uint8_t *d_status, void *d_fused_depth, int fused_dtype, int64_t *d_counts,
+                 void *stream);
+int pcs_fuse_last_kernel_ms(pcs_depth_fuser *p, float *check_ms, float *unique_ms, float *total_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one
