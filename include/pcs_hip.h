@@ -1191,6 +1191,68 @@ int pcs_fuse_run(pcs_depth_fuser *p, const void *d_depth, int depth_dtype, doubl
 int pcs_fuse_last_kernel_ms(pcs_depth_fuser *p, float *check_ms, float *unique_ms, float *total_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Plane-sweep multi-view depth: from the images of a rig to one z-depth map per view (csrc/ba_sweep.hpp).  Since
+ * pcs_version() 126.
+ * Replaces: the depth estimation of the external multi-view program the reference writes its rig out for.  What the reference hands
+ *           over is a rig, per-view neighbour lists of up to nine views and a depth range cut into steps: ReconParams(mindist, maxdist,
+ *           steps = 192, max_n_view = 9) (reconstruction/acmmp_utils.py:6-21), the last line Camera.to_MVSnet_txt writes, `depth_min
+ *           interval steps depth_max` (cameras/camera.py:158-159), and calc_pairs.  Those are the inputs of a plane sweep.  Neither
+ *           MVSNet nor ACMMP is reproduced: the rule below is the library's own.  tests/sweep_reference.py states it in NumPy.
+ * Inputs.  V views of one size W x H, 8-bit single-channel images I_v (V, H, pitch BYTES).  View v is a DISTORTION-FREE pinhole,
+ * K_v = [fx, cx, fy, cy] and [R_v | t_v] world -> view (the conventions of pcs_fuse_set_views); ordered neighbour lists in CSR form as
+ * in pcs_fuse_set_neighbours, at most PCS_SWEEP_MAX_NEIGHBOURS = 16 per view.  A HOST table of plane depths z (n_z, D) float64, n_z = 1
+ * (one row for all views) or V, D in [1, PCS_SWEEP_MAX_PLANES = 1024], every z finite and > 0, strictly monotone along a row.  Census
+ * window cw x ch (the limits of pcs_stereo_sgm), rw = cw / 2, rh = ch / 2; box radius r in [0, 4]; truncate tau in
+ * [1, (cw ch - 1)(2 r + 1)^2]; uniqueness_ratio u in [0, 100].
+ * The rule, for reference view i, pixel p = (x, y), plane k and neighbour j of i's list:
+ *   1. warp.  The host forms, in FP64, plain operations in the order written, sums of three products left to right:
+ *        M = R_j R_i^T, c = t_j - M t_i; N = K_j M, i.e. N_0. = fx_j M_0. + cx_j M_2., N_1. = fy_j M_1. + cy_j M_2., N_2. = M_2.;
+ *        A_a0 = N_a0 / fx_i, A_a1 = N_a1 / fy_i, A_a2 = (N_a2 - A_a0 cx_i) - A_a1 cy_i   (A = K_j M K_i^-1);
+ *        b = K_j c = (fx_j c_0 + cx_j c_2, fy_j c_1 + cy_j c_2, c_2).
+ *      The device reads these 12 numbers and computes, in FP64, plain IEEE operations in the order written, no contraction:
+ *        n_a = z_k ((A_a0 x + A_a1 y) + A_a2) + b_a for a = 0, 1, 2; u = n_0 / n_2, v = n_1 / n_2.
+ *   2. sample (integers from here on).  q_u = floor(16 u + 0.5), q_v = floor(16 v + 0.5): the nearest sixteenth.  The sample is VALID
+ *      iff n_2 > 0, 0 <= q_u < 16 (W - 1) and 0 <= q_v < 16 (H - 1) (a comparison with a NaN fails).  x0 = q_u >> 4, f_x = q_u & 15,
+ *      likewise y0, f_y; g = (16 - f_x)(16 - f_y) I_j[y0, x0] + f_x (16 - f_y) I_j[y0, x0 + 1] + (16 - f_x) f_y I_j[y0 + 1, x0]
+ *      + f_x f_y I_j[y0 + 1, x0 + 1], in [0, 65280].
+ *   3. cost per neighbour.  W_jk(p) = g at reference pixel p.  Its census descriptor is that of pcs_stereo_sgm (one bit per window
+ *      position other than the centre, 1 iff that neighbour is LESS THAN the centre) and is valid iff every sample of the window is
+ *      valid; the reference descriptor is the census of I_i.  h(p, k, j) = popcount of the xor of the two.
+ *      C_j(p, k) = min(tau, sum of h(q, k, j) over the (2 r + 1)^2 box about p), and tau outright when a descriptor of the box is
+ *      invalid: occluded, out-of-view and behind-the-camera neighbours all cost tau.
+ *   4. merge.  C(p, k) = sum over the list of C_j(p, k): an integer, so the order of a list does not change a bit.  STRICT pixels are
+ *      those whose box and census footprint lies inside the reference image: rows rh + r .. H - 1 - rh - r, columns rw + r ..
+ *      W - 1 - rw - r.  An empty rectangle is a valid call.
+ *   5. decide.  k* the smallest k of the smallest C; cost = C* = C(p, k*).  Offset f: the block matcher's floor division (above,
+ *      "sub-pixel") on C(k* - 1), C*, C(k* + 1), 0 when k* is an end of the table.  level = 16 k* + f (int32).  status (uint8), the
+ *      first that applies set alone: PCS_SWEEP_NOT_STRICT; PCS_SWEEP_NO_VIEW: C* >= tau (list length), no neighbour scored below the
+ *      truncation at any plane (an empty list gives it on every strict pixel); PCS_SWEEP_UNIQUENESS: u > 0 and some k with
+ *      |k - k*| >= 2 has 100 C(k) <= (100 + u) C*.  depth = z[k*] + (|f| / 16)(z[k* + sign f] - z[k*]) in FP64 in that order, rounded
+ *      once for a float32 output, NaN wherever status != 0.  Non-strict pixels have level -16 and cost -1; level and cost of a strict
+ *      pixel are written whatever its status.
+ * No atomics; two runs, any tiling and any order of a neighbour list give identical bits.  The cost volume is never stored.
+ *   pcs_sweep_create          a handle on `device` (no counterpart); it owns the neighbour lists, the warp table and the plane table
+ *   pcs_sweep_destroy         frees the handle (no counterpart)
+ *   pcs_sweep_set_views       arguments and checks of pcs_fuse_set_views.  New views drop the neighbour lists.
+ *   pcs_sweep_set_neighbours  arguments and checks of pcs_fuse_set_neighbours, with at most 16 entries per view
+ *   pcs_sweep_run             d_images (n_views, height, pitch BYTES); z HOST (n_z, D); d_depth (n_views, height, width) of depth_dtype
+ *                             PCS_F64 or PCS_F32.  Optional (NULL: not written): d_level int32, d_cost int32, d_status uint8.
+ *   pcs_sweep_last_kernel_ms  device time of the last run's kernel (no counterpart)
+ * Every argument is checked on the host before the device is touched (PCS_ERR_ARG; pcs_last_error names the argument); the handle is
+ * looked at last, and with it n_z against the views and pitch against the width.  All buffers are DEVICE buffers of the caller unless
+ * marked HOST; a run is queued on `stream` (NULL = the handle's).
+ */
+typedef struct pcs_plane_sweeper pcs_plane_sweeper;
+enum { PCS_SWEEP_NOT_STRICT = 1, PCS_SWEEP_NO_VIEW = 2, PCS_SWEEP_UNIQUENESS = 4, PCS_SWEEP_MAX_NEIGHBOURS = 16, PCS_SWEEP_MAX_PLANES = 1024 };
+int pcs_sweep_create(pcs_plane_sweeper **out, int device);
+int pcs_sweep_destroy(pcs_plane_sweeper *p);
+int pcs_sweep_set_views(pcs_plane_sweeper *p, int64_t n_views, int width, int height, const double *K, const double *P);
+int pcs_sweep_set_neighbours(pcs_plane_sweeper *p, const int32_t *nbr_start, const int32_t *nbr, int64_t n);
+int pcs_sweep_run(pcs_plane_sweeper *p, const uint8_t *d_images, int64_t pitch, const double *z, int64_t n_z, int D, int census_w, int census_h, int box_radius, int truncate,
+                  int uniqueness_ratio, void *d_depth, int depth_dtype, int32_t *d_level, int32_t *d_cost, uint8_t *d_status, void *stream);
+int pcs_sweep_last_kernel_ms(pcs_plane_sweeper *p, float *kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

@@ -57,6 +57,8 @@ IMAP_DTYPE_IDS = {"uint8": 0, "float32": 1}
 STEREO_NOT_STRICT, STEREO_TEXTURE, STEREO_UNIQUENESS, STEREO_LEFT_RIGHT, STEREO_VALIDITY = 1, 2, 4, 8, 16
 # include/pcs_hip.h PCS_FUSE_*: status bits of the depth-map fusion and the width of its support word
 FUSE_INVALID_DEPTH, FUSE_FEW_VIEWS, FUSE_DUPLICATE, FUSE_MAX_NEIGHBOURS = 1, 2, 4, 32
+# include/pcs_hip.h PCS_SWEEP_*: status bits of the plane sweep and its limits
+SWEEP_NOT_STRICT, SWEEP_NO_VIEW, SWEEP_UNIQUENESS, SWEEP_MAX_NEIGHBOURS, SWEEP_MAX_PLANES = 1, 2, 4, 16, 1024
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -223,6 +225,12 @@ SYMBOLS = {
     "pcs_fuse_set_neighbours": (c_int, [_P, POINTER(c_int32), POINTER(c_int32), c_int64]),
     "pcs_fuse_run": (c_int, [_P, _P, c_int, c_double, c_double, c_int, c_int, POINTER(c_double), _P, c_int, _P, _P, _P, _P, _P, c_int, _P, _P]),
     "pcs_fuse_last_kernel_ms": (c_int, [_P, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
+    "pcs_sweep_create": (c_int, [POINTER(_P), c_int]),
+    "pcs_sweep_destroy": (c_int, [_P]),
+    "pcs_sweep_set_views": (c_int, [_P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
+    "pcs_sweep_set_neighbours": (c_int, [_P, POINTER(c_int32), POINTER(c_int32), c_int64]),
+    "pcs_sweep_run": (c_int, [_P, _P, c_int64, POINTER(c_double), c_int64, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
+    "pcs_sweep_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),

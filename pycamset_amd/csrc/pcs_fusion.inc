@@ -32,15 +32,15 @@ static int fuse_check_views(const char *who, int64_t n_views, int width, int hei
     return PCS_OK;
 }
 
-// Every argument of pcs_fuse_set_neighbours but the handle.
-static int fuse_check_neighbours(const char *who, const int32_t *nbr_start, const int32_t *nbr, int64_t n) {
+// Every argument of pcs_fuse_set_neighbours but the handle (and of pcs_sweep_set_neighbours, whose lists hold at most `cap` = 16).
+static int fuse_check_neighbours(const char *who, const int32_t *nbr_start, const int32_t *nbr, int64_t n, int cap = FUSE_MAX_NBR) {
     if (n < 1 || n > STEREO_MAX_PAIRS) return fail(PCS_ERR_ARG, "%s: n %lld outside [1, %lld]", who, (long long)n, (long long)STEREO_MAX_PAIRS);
     if (!nbr_start) return fail(PCS_ERR_ARG, "%s: nbr_start (n + 1) must be given", who);
     if (nbr_start[0] != 0) return fail(PCS_ERR_ARG, "%s: nbr_start must begin at 0 (got %d)", who, nbr_start[0]);
     for (int64_t v = 0; v < n; ++v) {
         const int64_t len = (int64_t)nbr_start[v + 1] - nbr_start[v];
         if (len < 0) return fail(PCS_ERR_ARG, "%s: nbr_start must be non-decreasing (view %lld)", who, (long long)v);
-        if (len > FUSE_MAX_NBR) return fail(PCS_ERR_ARG, "%s: nbr_start gives view %lld %lld neighbours, more than %d", who, (long long)v, (long long)len, FUSE_MAX_NBR);
+        if (len > cap) return fail(PCS_ERR_ARG, "%s: nbr_start gives view %lld %lld neighbours, more than %d", who, (long long)v, (long long)len, cap);
     }
     if (nbr_start[n] > 0 && !nbr) return fail(PCS_ERR_ARG, "%s: nbr must be given", who);
     for (int64_t v = 0; v < n; ++v)
