@@ -1253,6 +1253,86 @@ int pcs_sweep_run(pcs_plane_sweeper *p, const uint8_t *d_images, int64_t pitch, 
 int pcs_sweep_last_kernel_ms(pcs_plane_sweeper *p, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * TSDF volume and surface extraction: from z-depth maps to a quad mesh (csrc/ba_tsdf.hpp).  Since pcs_version() 127.
+ * Replaces: nothing the reference computes.  It draws everything as pyvista meshes, and leaves the step from views to a surface to the
+ *           external multi-view program and to whatever mesher the user runs on that program's cloud.  The depth maps of pcs_sweep_run /
+ *           pcs_stereo_* are what a volumetric fusion needs; it adds what pcs_fuse_run cannot give: free-space carving (a wrong depth in
+ *           one view is out-voted by the views that see through it) and a connected surface.  The volume is Curless and Levoy's truncated
+ *           signed distance with unit weights; the mesh is naive surface nets (Gibson), which need no case table.  The rule below is the
+ *           library's own; tests/tsdf_reference.py states it in NumPy.
+ * Inputs.  Views, intrinsics, extrinsics, depth maps and the validity of a depth are those of pcs_fuse_set_views / pcs_fuse_run:
+ * distortion-free pinholes K = [fx, cx, fy, cy], [R | t] world -> view, z-depth float32 or float64, invalid when NaN, +-inf or <= 0.
+ * All arithmetic is FP64, plain IEEE operations in the order written (no contraction), sums of three products taken left to right.
+ * Grid.  Origin o (3 doubles), voxel size s > 0, node counts (nx, ny, nz), each in [1, PCS_TSDF_MAX_DIM = 1024].  Node (i, j, k) is the
+ * world point X = (o0 + s i, o1 + s j, o2 + s k); its linear index is (k ny + j) nx + i, taken in int64_t.  Per node the volume holds sum
+ * (float32 by default, float64 opt-in) and weight (uint16), both 0 at the start.
+ * Integration of an ordered list of views v_0 .. v_{m-1} (indices into the view table; the default is all views in order), trunc > 0.
+ * For each node, S = double(sum), W = weight, and for each view of the list in order:
+ *   1. Y_a = ((R_a0 X0 + R_a1 X1) + R_a2 X2) + t_a.  Skip unless Y_z > 0.
+ *   2. u = fx (Y_x / Y_z) + cx, v = fy (Y_y / Y_z) + cy, q = (floor(u + 0.5), floor(v + 0.5)).  Skip unless q lies in [0, W) x [0, H).
+ *   3. d = D_v[q].  Skip if d is invalid.
+ *   4. sdf = d - Y_z.  Skip unless sdf >= -trunc: a node farther than trunc behind the seen surface is occluded, not observed.
+ *   5. S += min(1.0, sdf / trunc); W += 1.
+ * Then sum = S, rounded once to the volume's dtype, and weight = W.  A comparison with a NaN fails.  No atomics: one thread owns a node
+ * over the whole list, so the result depends only on the list order and two runs give the same bits.  A second integration continues
+ * from the stored values.  The host keeps the number of views integrated since the volume was zeroed and refuses (PCS_ERR_ARG, before
+ * the device is touched) a call that could take any weight past PCS_TSDF_MAX_WEIGHT = 65535.
+ * Extraction, min_weight in [1, 65535].  A node is OBSERVED iff weight >= min_weight; its value is D = double(sum) / double(weight); it
+ * is INSIDE iff it is observed and D < 0.  Cell (i, j, k) exists for i < nx - 1, j < ny - 1, k < nz - 1, with corners c = 0 .. 7 at node
+ * (i + (c & 1), j + (c >> 1 & 1), k + (c >> 2 & 1)).  A cell is ACTIVE iff all eight corners are observed and they are neither all inside
+ * nor all outside.
+ *   Vertex of an active cell.  Walk the twelve cell edges (a, b) in the order (0,1) (0,2) (0,4) (1,3) (1,5) (2,3) (2,6) (3,7) (4,5) (4,6)
+ *   (5,7) (6,7).  For an edge whose ends differ in INSIDE the crossing is p = the corner offset of a with the component along the edge's
+ *   axis replaced by t = D_a / (D_a - D_b).  The crossings are added in edge order, per component, and each component is divided by
+ *   their number: off.  The vertex is (o0 + s (i + off0), o1 + s (j + off1), o2 + s (k + off2)), rounded once to float32 or left as
+ *   float64.  Vertices are numbered in the order of the cells' linear index (k (ny - 1) + j)(nx - 1) + i; every active cell gets a
+ *   vertex, whether or not a quad uses it.
+ *   Quads.  The grid edge from node n = (i, j, k) to its successor along axis A (0 = x, 1 = y, 2 = z): both ends must be observed and
+ *   differ in INSIDE.  With (U, V) = (1, 2), (2, 0), (0, 1) for A = 0, 1, 2, the four cells around the edge are the cells at n offset by
+ *   (dU, dV) = (-1, -1), (0, -1), (0, 0), (-1, 0) along axes U, V.  The edge emits one quad iff all four cells exist and are ACTIVE: the
+ *   four vertex numbers in that order when n is INSIDE, in the reverse order otherwise, so that the quad's normal (v1 - v0) x (v3 - v0)
+ *   points from inside to outside.  Quads are ordered by (A, node linear index).
+ * Limits.  The ordered compaction is pcs_stereo_compact's, unchanged: the cell flags are nz - 1 "views" of (ny - 1)(nx - 1) pixels, the
+ * quad flags 3 nz of ny nx.  Its limits (32767 views; one workgroup scans the block counts, however many) admit every grid up to
+ * 1024^3, so PCS_TSDF_MAX_DIM is the only grid limit; vertex numbers are int32 (1023^3 < 2^31).  The volume is dense: 6 (float32 sum) or
+ * 10 bytes per node, and the extraction's workspace 8 more per node.
+ * Not done here: per-view weights, colour or intensity per vertex, marching cubes, a sparse or hashed volume, mesh smoothing or
+ * simplification, distorted views (undistort first, pcs_imap_*).
+ *   pcs_tsdf_create          a handle on `device` (no counterpart); it owns the view table, the volume and the extraction's workspace
+ *   pcs_tsdf_destroy         frees the handle (no counterpart)
+ *   pcs_tsdf_set_views       the arguments and checks of pcs_fuse_set_views.  The volume is kept.
+ *   pcs_tsdf_set_grid        origin HOST (3), finite; voxel finite and > 0; nx, ny, nz in [1, 1024]; sum_dtype PCS_F32 or PCS_F64.
+ *                            Allocates the volume and zeroes it.
+ *   pcs_tsdf_reset           zeroes the volume and the count of integrated views
+ *   pcs_tsdf_integrate       d_depth (n_views, height, width) of depth_dtype, the maps of ALL views of the table; views HOST (n_list)
+ *                            int32 indices into the table, copied, or NULL: all views in order (n_list is then ignored).  An empty
+ *                            list leaves the volume as it is.  One launch.
+ *   pcs_tsdf_volume_ptrs     the device pointers of sum (nz, ny, nx) and weight, for tests and callers (either may be NULL)
+ *   pcs_tsdf_extract_count   classifies the cells, numbers the vertices (a dense int32 cell -> vertex map, the hand-over to the quads),
+ *                            flags the quads and scans both; returns the two counts to the host (blocking)
+ *   pcs_tsdf_extract_write   fills d_vertices (n_vertices, 3) of vertex_dtype and d_quads (n_quads, 4) int32, buffers of exactly the
+ *                            counted sizes (NULL allowed for a count of 0).  PCS_ERR_ARG when no count preceded it or the volume
+ *                            changed since the count (an integration, a reset, a new grid).
+ *   pcs_tsdf_last_kernel_ms  device time of the last integration, of the last count (classification, numbering, quad flags, scans) and
+ *                            of the last write; any pointer may be NULL.  PCS_ERR_STATE when the part asked for has not run.
+ * Every argument is checked on the host before the device is touched (PCS_ERR_ARG; pcs_last_error names the argument); the handle is
+ * looked at last, and with it the view indices and the weight limit.  All buffers are DEVICE buffers of the caller unless marked HOST;
+ * a run is queued on `stream` (NULL = the handle's).
+ */
+typedef struct pcs_tsdf_volume pcs_tsdf_volume;
+enum { PCS_TSDF_MAX_DIM = 1024, PCS_TSDF_MAX_WEIGHT = 65535 };
+int pcs_tsdf_create(pcs_tsdf_volume **out, int device);
+int pcs_tsdf_destroy(pcs_tsdf_volume *p);
+int pcs_tsdf_set_views(pcs_tsdf_volume *p, int64_t n_views, int width, int height, const double *K, const double *P);
+int pcs_tsdf_set_grid(pcs_tsdf_volume *p, const double *origin, double voxel, int nx, int ny, int nz, int sum_dtype);
+int pcs_tsdf_reset(pcs_tsdf_volume *p);
+int pcs_tsdf_integrate(pcs_tsdf_volume *p, const void *d_depth, int depth_dtype, const int32_t *views, int64_t n_list, double trunc, void *stream);
+int pcs_tsdf_volume_ptrs(pcs_tsdf_volume *p, void **d_sum, uint16_t **d_weight);
+int pcs_tsdf_extract_count(pcs_tsdf_volume *p, int min_weight, int64_t *n_vertices, int64_t *n_quads, void *stream);
+int pcs_tsdf_extract_write(pcs_tsdf_volume *p, void *d_vertices, int vertex_dtype, int32_t *d_quads, void *stream);
+int pcs_tsdf_last_kernel_ms(pcs_tsdf_volume *p, float *integrate_ms, float *count_ms, float *write_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

@@ -6,7 +6,7 @@ first use and there is no CPU fallback.
 """
 from .detections import TargetDetection  # noqa: F401
 
-__all__ = ["TargetDetection", "Engine", "parameter_covariance", "ParameterCovariance", "handlers", "function_blocks", "compiled_helpers", "pose_seeding", "device_solver", "sharding", "synthetic", "imaging", "stereo", "fusion", "sweep"]
+__all__ = ["TargetDetection", "Engine", "parameter_covariance", "ParameterCovariance", "handlers", "function_blocks", "compiled_helpers", "pose_seeding", "device_solver", "sharding", "synthetic", "imaging", "stereo", "fusion", "sweep", "volume"]
 __version__ = "0.1.0"
 
 
@@ -18,7 +18,7 @@ def __getattr__(name):
         from . import device_solver
         return getattr(device_solver, name)
     if name in ("handlers", "function_blocks", "synthetic", "engine", "optimisation_handling", "sharding", "device_solver",
-                "compiled_helpers", "detections", "pose_seeding", "imaging", "stereo", "fusion", "sweep"):
+                "compiled_helpers", "detections", "pose_seeding", "imaging", "stereo", "fusion", "sweep", "volume"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -59,6 +59,8 @@ STEREO_NOT_STRICT, STEREO_TEXTURE, STEREO_UNIQUENESS, STEREO_LEFT_RIGHT, STEREO_
 FUSE_INVALID_DEPTH, FUSE_FEW_VIEWS, FUSE_DUPLICATE, FUSE_MAX_NEIGHBOURS = 1, 2, 4, 32
 # include/pcs_hip.h PCS_SWEEP_*: status bits of the plane sweep and its limits
 SWEEP_NOT_STRICT, SWEEP_NO_VIEW, SWEEP_UNIQUENESS, SWEEP_MAX_NEIGHBOURS, SWEEP_MAX_PLANES = 1, 2, 4, 16, 1024
+# include/pcs_hip.h PCS_TSDF_*: the limits of the TSDF volume
+TSDF_MAX_DIM, TSDF_MAX_WEIGHT = 1024, 65535
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -231,6 +233,16 @@ SYMBOLS = {
     "pcs_sweep_set_neighbours": (c_int, [_P, POINTER(c_int32), POINTER(c_int32), c_int64]),
     "pcs_sweep_run": (c_int, [_P, _P, c_int64, POINTER(c_double), c_int64, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     "pcs_sweep_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_tsdf_create": (c_int, [POINTER(_P), c_int]),
+    "pcs_tsdf_destroy": (c_int, [_P]),
+    "pcs_tsdf_set_views": (c_int, [_P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
+    "pcs_tsdf_set_grid": (c_int, [_P, POINTER(c_double), c_double, c_int, c_int, c_int, c_int]),
+    "pcs_tsdf_reset": (c_int, [_P]),
+    "pcs_tsdf_integrate": (c_int, [_P, _P, c_int, POINTER(c_int32), c_int64, c_double, _P]),
+    "pcs_tsdf_volume_ptrs": (c_int, [_P, POINTER(_P), POINTER(_P)]),
+    "pcs_tsdf_extract_count": (c_int, [_P, c_int, POINTER(c_int64), POINTER(c_int64), _P]),
+    "pcs_tsdf_extract_write": (c_int, [_P, _P, c_int, _P, _P]),
+    "pcs_tsdf_last_kernel_ms": (c_int, [_P, POINTER(c_float), POINTER(c_float), POINTER(c_float)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),

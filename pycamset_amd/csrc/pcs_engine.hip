@@ -57,6 +57,7 @@
 #include "ba_stereo_sgm.hpp"
 #include "ba_fusion.hpp"
 #include "ba_sweep.hpp"
+#include "ba_tsdf.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side
@@ -74,6 +75,7 @@ using namespace pcs;
 #include "pcs_stereo.inc"
 #include "pcs_fusion.inc"
 #include "pcs_sweep.inc"
+#include "pcs_tsdf.inc"
 #include "pcs_rigpose.inc"
 #include "pcs_intrinsics.inc"
 #include "pcs_rig.inc"

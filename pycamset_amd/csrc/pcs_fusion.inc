@@ -32,6 +32,16 @@ static int fuse_check_views(const char *who, int64_t n_views, int width, int hei
     return PCS_OK;
 }
 
+// The device's view table: per view K = [fx, cx, fy, cy], then the 3 x 4 [R | t] row-major (16 doubles; also pcs_tsdf_set_views)
+static std::vector<double> fuse_view_rows(int64_t n_views, const double *K, const double *P) {
+    std::vector<double> rows(16 * (size_t)n_views);
+    for (int64_t v = 0; v < n_views; ++v) {
+        std::copy(K + 4 * v, K + 4 * v + 4, rows.begin() + 16 * v);
+        std::copy(P + 12 * v, P + 12 * v + 12, rows.begin() + 16 * v + 4);
+    }
+    return rows;
+}
+
 // Every argument of pcs_fuse_set_neighbours but the handle (and of pcs_sweep_set_neighbours, whose lists hold at most `cap` = 16).
 static int fuse_check_neighbours(const char *who, const int32_t *nbr_start, const int32_t *nbr, int64_t n, int cap = FUSE_MAX_NBR) {
     if (n < 1 || n > STEREO_MAX_PAIRS) return fail(PCS_ERR_ARG, "%s: n %lld outside [1, %lld]", who, (long long)n, (long long)STEREO_MAX_PAIRS);
@@ -113,11 +123,7 @@ int pcs_fuse_set_views(pcs_depth_fuser *p, int64_t n_views, int width, int heigh
     const char *who = "pcs_fuse_set_views";
     if (const int rc = fuse_check_views(who, n_views, width, height, K, P)) return rc;
     if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
-    std::vector<double> rows(16 * (size_t)n_views);
-    for (int64_t v = 0; v < n_views; ++v) {
-        std::copy(K + 4 * v, K + 4 * v + 4, rows.begin() + 16 * v);
-        std::copy(P + 12 * v, P + 12 * v + 12, rows.begin() + 16 * v + 4);
-    }
+    const std::vector<double> rows = fuse_view_rows(n_views, K, P);
     HIPCHK(p->core.quiesce());   // a queued run may still read the old table
     p->n_views = 0, p->n_nbr_views = -1;
     const HostArray up[] = {{p->views, rows.data(), 16 * n_views, sizeof(double)}};

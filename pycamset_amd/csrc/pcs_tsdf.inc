@@ -1,0 +1,277 @@
+// pcs_tsdf.inc — host side of the TSDF volume and the surface-nets extraction (included by pcs_engine.hip behind pcs_fusion.inc; kernels:
+// ba_tsdf.hpp).  The handle owns the view table (the rows of pcs_fuse_set_views), the volume (sum and weight per node), the view list
+// of the last integration and the extraction's workspace: the cell flags, the cell -> vertex map, the quad flags and the block counts
+// and offsets of the two compactions (stereo_count_kernel / stereo_scan_kernel, unchanged).  Depth maps, vertices and quads are the
+// caller's device buffers.  Fence and timers are those of pcs_handle.inc (DESIGN.md, "Batched handles").
+struct pcs_tsdf_volume {
+    HandleCore core;
+    KernelTimer t_integrate, t_count, t_write;
+    DevBuf views, list, sum, weight, cflag, map, qflag, blk, coff, qoff;
+    int64_t n_views = 0, n_integrated = 0;   // n_integrated: views integrated since the volume was zeroed (no weight can exceed it)
+    int width = 0, height = 0;
+    TsdfGrid g{};
+    bool have_grid = false, f32 = true, counted = false;   // counted: an extract_count on the volume as it stands
+    int min_weight = 0;
+    int64_t n_vertices = 0, n_quads = 0;
+    int64_t nodes() const { return (int64_t)g.nx * g.ny * g.nz; }
+    int64_t cells() const { return (int64_t)(g.nx - 1) * (g.ny - 1) * (g.nz - 1); }
+};
+
+static_assert(TSDF_MAX_DIM == PCS_TSDF_MAX_DIM && TSDF_MAX_WEIGHT == PCS_TSDF_MAX_WEIGHT, "limits of pcs_hip.h");
+// the compaction's limits admit the largest grid: 3 nz "views" in blockIdx.y, and the one-workgroup scan walks any number of blocks
+static_assert(3 * TSDF_MAX_DIM <= 65535 && 3 * TSDF_MAX_DIM <= STEREO_MAX_PAIRS, "quad flags as 3 nz views of the compaction");
+
+// Every argument of pcs_tsdf_set_grid but the handle: nothing here touches the device.
+static int tsdf_check_grid(const char *who, const double *origin, double voxel, int nx, int ny, int nz, int sum_dtype) {
+    if (!origin) return fail(PCS_ERR_ARG, "%s: origin (3) must be given", who);
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(origin[c])) return fail(PCS_ERR_ARG, "%s: origin is not finite", who);
+    if (!std::isfinite(voxel) || !(voxel > 0.0)) return fail(PCS_ERR_ARG, "%s: voxel must be finite and > 0 (got %g)", who, voxel);
+    const int d[3] = {nx, ny, nz};
+    for (int c = 0; c < 3; ++c)
+        if (d[c] < 1 || d[c] > TSDF_MAX_DIM) return fail(PCS_ERR_ARG, "%s: n%c %d outside [1, %d]", who, "xyz"[c], d[c], TSDF_MAX_DIM);
+    if (sum_dtype != PCS_F64 && sum_dtype != PCS_F32) return fail(PCS_ERR_ARG, "%s: sum_dtype PCS_F64 or PCS_F32", who);
+    return PCS_OK;
+}
+
+// Every argument of pcs_tsdf_integrate that needs no handle.
+static int tsdf_check_integrate(const char *who, const void *d_depth, int depth_dtype, const int32_t *views, int64_t n_list, double trunc) {
+    if (depth_dtype != PCS_F64 && depth_dtype != PCS_F32) return fail(PCS_ERR_ARG, "%s: depth_dtype PCS_F64 or PCS_F32", who);
+    if (!std::isfinite(trunc) || !(trunc > 0.0)) return fail(PCS_ERR_ARG, "%s: trunc must be finite and > 0 (got %g)", who, trunc);
+    if (views && (n_list < 0 || n_list > TSDF_MAX_WEIGHT)) return fail(PCS_ERR_ARG, "%s: n_list %lld outside [0, %d]", who, (long long)n_list, TSDF_MAX_WEIGHT);
+    if (!d_depth) return fail(PCS_ERR_ARG, "%s: d_depth must be given", who);
+    return PCS_OK;
+}
+
+static TsdfExtractArgs tsdf_extract_args(const pcs_tsdf_volume *p) {
+    TsdfExtractArgs a{};
+    a.sum = p->sum.p, a.weight = p->weight.as<const uint16_t>(), a.g = p->g, a.min_weight = p->min_weight, a.map = p->map.as<int32_t>();
+    return a;
+}
+
+extern "C" {
+int pcs_tsdf_create(pcs_tsdf_volume **out, int device) {
+    if (!out) return fail(PCS_ERR_ARG, "pcs_tsdf_create: bad arguments");
+    *out = nullptr;
+    if (const int rc = open_device("pcs_tsdf_create", device)) return rc;
+    pcs_tsdf_volume *p = new pcs_tsdf_volume();
+    hipError_t e = p->core.create(device);
+    if (e == hipSuccess) e = p->t_integrate.create();
+    if (e == hipSuccess) e = p->t_count.create();
+    if (e == hipSuccess) e = p->t_write.create();
+    if (e != hipSuccess) {
+        const int rc = fail(PCS_ERR_HIP, "pcs_tsdf_create: %s", hipGetErrorString(e));
+        pcs_tsdf_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return PCS_OK;
+}
+
+int pcs_tsdf_destroy(pcs_tsdf_volume *p) {
+    if (!p) return PCS_OK;
+    p->core.destroy({&p->views, &p->list, &p->sum, &p->weight, &p->cflag, &p->map, &p->qflag, &p->blk, &p->coff, &p->qoff}, {&p->t_integrate, &p->t_count, &p->t_write});
+    delete p;
+    return PCS_OK;
+}
+
+// K and P are HOST arrays and are copied: the arguments and checks of pcs_fuse_set_views.  The volume is kept.
+int pcs_tsdf_set_views(pcs_tsdf_volume *p, int64_t n_views, int width, int height, const double *K, const double *P) {
+    const char *who = "pcs_tsdf_set_views";
+    if (const int rc = fuse_check_views(who, n_views, width, height, K, P)) return rc;
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    const std::vector<double> rows = fuse_view_rows(n_views, K, P);
+    HIPCHK(p->core.quiesce());   // a queued integration may still read the old table
+    p->n_views = 0;
+    const HostArray up[] = {{p->views, rows.data(), 16 * n_views, sizeof(double)}};
+    if (const int rc = upload_host_arrays(p->core, up, 1)) return rc;
+    p->n_views = n_views, p->width = width, p->height = height;
+    return PCS_OK;
+}
+
+static int tsdf_zero(pcs_tsdf_volume *p) {
+    const int64_t N = p->nodes();
+    HIPCHK(hipMemsetAsync(p->sum.p, 0, (size_t)N * (p->f32 ? sizeof(float) : sizeof(double)), p->core.stream));
+    HIPCHK(hipMemsetAsync(p->weight.p, 0, (size_t)N * sizeof(uint16_t), p->core.stream));
+    HIPCHK(hipStreamSynchronize(p->core.stream));
+    p->n_integrated = 0, p->counted = false;
+    return PCS_OK;
+}
+
+// Allocates the volume and zeroes it.
+int pcs_tsdf_set_grid(pcs_tsdf_volume *p, const double *origin, double voxel, int nx, int ny, int nz, int sum_dtype) {
+    const char *who = "pcs_tsdf_set_grid";
+    if (const int rc = tsdf_check_grid(who, origin, voxel, nx, ny, nz, sum_dtype)) return rc;
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    HIPCHK(p->core.quiesce());
+    p->have_grid = p->counted = false;
+    const int64_t N = (int64_t)nx * ny * nz;
+    if (const int rc = p->sum.grow(N * (sum_dtype == PCS_F32 ? 1 : 2), sizeof(float))) return rc;   // capacity counted in 4-byte words: either dtype fits
+    if (const int rc = p->weight.grow(N, sizeof(uint16_t))) return rc;
+    p->g.o[0] = origin[0], p->g.o[1] = origin[1], p->g.o[2] = origin[2], p->g.s = voxel, p->g.nx = nx, p->g.ny = ny, p->g.nz = nz;
+    p->f32 = sum_dtype == PCS_F32;
+    if (const int rc = tsdf_zero(p)) return rc;
+    p->have_grid = true;
+    return PCS_OK;
+}
+
+int pcs_tsdf_reset(pcs_tsdf_volume *p) {
+    const char *who = "pcs_tsdf_reset";
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (!p->have_grid) return fail(PCS_ERR_STATE, "%s: pcs_tsdf_set_grid comes first", who);
+    HIPCHK(p->core.quiesce());
+    return tsdf_zero(p);
+}
+
+// `views` is a HOST list of indices into the view table (NULL: all views in order); it is copied.
+int pcs_tsdf_integrate(pcs_tsdf_volume *p, const void *d_depth, int depth_dtype, const int32_t *views, int64_t n_list, double trunc, void *stream) {
+    const char *who = "pcs_tsdf_integrate";
+    if (const int rc = tsdf_check_integrate(who, d_depth, depth_dtype, views, n_list, trunc)) return rc;
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (p->n_views == 0 || !p->have_grid) return fail(PCS_ERR_STATE, "%s: pcs_tsdf_set_views and pcs_tsdf_set_grid come first", who);
+    const int64_t m = views ? n_list : p->n_views;
+    for (int64_t l = 0; views && l < m; ++l)
+        if (views[l] < 0 || views[l] >= p->n_views) return fail(PCS_ERR_ARG, "%s: views entry %lld is %d, outside [0, %lld)", who, (long long)l, views[l], (long long)p->n_views);
+    if (p->n_integrated + m > TSDF_MAX_WEIGHT)
+        return fail(PCS_ERR_ARG, "%s: views: %lld more after %lld integrated could take a weight past %d", who, (long long)m, (long long)p->n_integrated, TSDF_MAX_WEIGHT);
+    if (m == 0) return PCS_OK;   // an empty list: the volume stays as it is
+    HIPCHK(hipSetDevice(p->core.device));
+    if (views) HIPCHK(p->core.quiesce());   // a queued integration may still read the old list
+    hipStream_t s = p->core.stream_or(stream);
+    HIPCHK(p->core.fence.before_run(s, views && p->list.grows(m)));
+    if (views) {
+        if (const int rc = p->list.grow(m, sizeof(int32_t))) return rc;
+        HIPCHK(hipMemcpy(p->list.p, views, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice));
+    }
+    TsdfIntegrateArgs a{};
+    a.views = p->views.as<const double>(), a.list = views ? p->list.as<const int32_t>() : nullptr, a.n_list = (int)m, a.depth = d_depth, a.W = p->width, a.H = p->height;
+    a.g = p->g, a.trunc = trunc, a.sum = p->sum.p, a.weight = p->weight.as<uint16_t>();
+    const dim3 grid((unsigned)((p->g.nx + TSDF_TX - 1) / TSDF_TX), (unsigned)((p->g.ny + TSDF_TY - 1) / TSDF_TY), (unsigned)p->g.nz), block(TSDF_TX, TSDF_TY);
+    p->counted = false;
+    p->n_integrated += m;
+    HIPCHK(hipEventRecord(p->t_integrate.e0, s));
+    if (depth_dtype == PCS_F32) {
+        if (p->f32) hipLaunchKernelGGL((tsdf_integrate_kernel<float, float>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((tsdf_integrate_kernel<float, double>), grid, block, 0, s, a);
+    } else {
+        if (p->f32) hipLaunchKernelGGL((tsdf_integrate_kernel<double, float>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((tsdf_integrate_kernel<double, double>), grid, block, 0, s, a);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->t_integrate.e1, s));
+    p->t_integrate.timed = true;
+    HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+int pcs_tsdf_volume_ptrs(pcs_tsdf_volume *p, void **d_sum, uint16_t **d_weight) {
+    const char *who = "pcs_tsdf_volume_ptrs";
+    if (!p || (!d_sum && !d_weight)) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (!p->have_grid) return fail(PCS_ERR_STATE, "%s: pcs_tsdf_set_grid comes first", who);
+    if (d_sum) *d_sum = p->sum.p;
+    if (d_weight) *d_weight = p->weight.as<uint16_t>();
+    return PCS_OK;
+}
+
+// Classification, numbering and the quad flags, with the two scans; the two totals come back to the host (blocking).
+int pcs_tsdf_extract_count(pcs_tsdf_volume *p, int min_weight, int64_t *n_vertices, int64_t *n_quads, void *stream) {
+    const char *who = "pcs_tsdf_extract_count";
+    if (min_weight < 1 || min_weight > TSDF_MAX_WEIGHT) return fail(PCS_ERR_ARG, "%s: min_weight %d outside [1, %d]", who, min_weight, TSDF_MAX_WEIGHT);
+    if (!n_vertices || !n_quads) return fail(PCS_ERR_ARG, "%s: n_vertices and n_quads must be given", who);
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (!p->have_grid) return fail(PCS_ERR_STATE, "%s: pcs_tsdf_set_grid comes first", who);
+    p->counted = false;
+    p->min_weight = min_weight, p->n_vertices = p->n_quads = 0;
+    const int64_t C = p->cells(), N = p->nodes();
+    if (C > 0) {
+        const int cz = p->g.nz - 1, qz = 3 * p->g.nz;
+        const int64_t cHW = (int64_t)(p->g.nx - 1) * (p->g.ny - 1), qHW = (int64_t)p->g.nx * p->g.ny;
+        const int64_t cblk = (cHW + STEREO_PIX_PER_BLOCK - 1) / STEREO_PIX_PER_BLOCK, qblk = (qHW + STEREO_PIX_PER_BLOCK - 1) / STEREO_PIX_PER_BLOCK;
+        const int64_t cNB = cblk * cz, qNB = qblk * qz;
+        const bool grows = p->cflag.grows(C) || p->map.grows(C) || p->qflag.grows(3 * N) || p->blk.grows(std::max(cNB, qNB)) || p->coff.grows(cNB + 1) || p->qoff.grows(qNB + 1);
+        HIPCHK(hipSetDevice(p->core.device));
+        hipStream_t s = p->core.stream_or(stream);
+        HIPCHK(p->core.fence.before_run(s, grows));
+        if (const int rc = p->cflag.grow(C, 1)) return rc;
+        if (const int rc = p->map.grow(C, sizeof(int32_t))) return rc;
+        if (const int rc = p->qflag.grow(3 * N, 1)) return rc;
+        if (const int rc = p->blk.grow(std::max(cNB, qNB), sizeof(int32_t))) return rc;
+        if (const int rc = p->coff.grow(cNB + 1, sizeof(int64_t))) return rc;
+        if (const int rc = p->qoff.grow(qNB + 1, sizeof(int64_t))) return rc;
+        TsdfExtractArgs a = tsdf_extract_args(p);
+        const dim3 cgrid((unsigned)cblk, (unsigned)cz), qgrid((unsigned)qblk, (unsigned)qz), block(STEREO_PIX_PER_BLOCK);
+        HIPCHK(hipEventRecord(p->t_count.e0, s));
+        a.flag = p->cflag.as<uint8_t>(), a.nblk = (int)cblk, a.off = p->coff.as<const int64_t>();
+        if (p->f32) hipLaunchKernelGGL(tsdf_classify_kernel<float>, cgrid, block, 0, s, a);
+        else hipLaunchKernelGGL(tsdf_classify_kernel<double>, cgrid, block, 0, s, a);
+        hipLaunchKernelGGL(stereo_count_kernel, cgrid, block, 0, s, p->cflag.as<const uint8_t>(), cHW, (int)cblk, p->blk.as<int32_t>());
+        hipLaunchKernelGGL(stereo_scan_kernel, dim3(1), dim3(1024), 0, s, p->blk.as<const int32_t>(), cNB, (int)cblk, cz, p->coff.as<int64_t>(), (int64_t *)nullptr);
+        hipLaunchKernelGGL(tsdf_number_kernel, cgrid, block, 0, s, a);
+        a.flag = p->qflag.as<uint8_t>(), a.nblk = (int)qblk, a.off = p->qoff.as<const int64_t>();
+        if (p->f32) hipLaunchKernelGGL(tsdf_quad_flag_kernel<float>, qgrid, block, 0, s, a);
+        else hipLaunchKernelGGL(tsdf_quad_flag_kernel<double>, qgrid, block, 0, s, a);
+        hipLaunchKernelGGL(stereo_count_kernel, qgrid, block, 0, s, p->qflag.as<const uint8_t>(), qHW, (int)qblk, p->blk.as<int32_t>());
+        hipLaunchKernelGGL(stereo_scan_kernel, dim3(1), dim3(1024), 0, s, p->blk.as<const int32_t>(), qNB, (int)qblk, qz, p->qoff.as<int64_t>(), (int64_t *)nullptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(p->t_count.e1, s));
+        p->t_count.timed = true;
+        HIPCHK(hipMemcpyAsync(&p->n_vertices, p->coff.as<const int64_t>() + cNB, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&p->n_quads, p->qoff.as<const int64_t>() + qNB, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(p->core.fence.after_run(s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    *n_vertices = p->n_vertices, *n_quads = p->n_quads;
+    p->counted = true;
+    return PCS_OK;
+}
+
+// Fills d_vertices (n_vertices, 3) of vertex_dtype and d_quads (n_quads, 4) int32: the sizes the count returned.
+int pcs_tsdf_extract_write(pcs_tsdf_volume *p, void *d_vertices, int vertex_dtype, int32_t *d_quads, void *stream) {
+    const char *who = "pcs_tsdf_extract_write";
+    if (vertex_dtype != PCS_F64 && vertex_dtype != PCS_F32) return fail(PCS_ERR_ARG, "%s: vertex_dtype PCS_F64 or PCS_F32", who);
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (!p->have_grid || !p->counted) return fail(PCS_ERR_ARG, "%s: no pcs_tsdf_extract_count on the volume as it stands", who);
+    if ((p->n_vertices > 0 && !d_vertices) || (p->n_quads > 0 && !d_quads)) return fail(PCS_ERR_ARG, "%s: d_vertices and d_quads must be given", who);
+    if (p->n_vertices == 0) return PCS_OK;   // no vertex, so no quad
+    HIPCHK(hipSetDevice(p->core.device));
+    hipStream_t s = p->core.stream_or(stream);
+    HIPCHK(p->core.fence.before_run(s, false));
+    const int cz = p->g.nz - 1, qz = 3 * p->g.nz;
+    const int64_t cHW = (int64_t)(p->g.nx - 1) * (p->g.ny - 1), qHW = (int64_t)p->g.nx * p->g.ny;
+    const int64_t cblk = (cHW + STEREO_PIX_PER_BLOCK - 1) / STEREO_PIX_PER_BLOCK, qblk = (qHW + STEREO_PIX_PER_BLOCK - 1) / STEREO_PIX_PER_BLOCK;
+    const dim3 cgrid((unsigned)cblk, (unsigned)cz), qgrid((unsigned)qblk, (unsigned)qz), block(STEREO_PIX_PER_BLOCK);
+    TsdfExtractArgs a = tsdf_extract_args(p);
+    a.vertices = d_vertices, a.quads = d_quads;
+    HIPCHK(hipEventRecord(p->t_write.e0, s));
+    const bool v32 = vertex_dtype == PCS_F32;
+    if (v32 && p->f32) hipLaunchKernelGGL((tsdf_vertex_kernel<float, float>), cgrid, block, 0, s, a);
+    else if (v32) hipLaunchKernelGGL((tsdf_vertex_kernel<float, double>), cgrid, block, 0, s, a);
+    else if (p->f32) hipLaunchKernelGGL((tsdf_vertex_kernel<double, float>), cgrid, block, 0, s, a);
+    else hipLaunchKernelGGL((tsdf_vertex_kernel<double, double>), cgrid, block, 0, s, a);
+    if (p->n_quads > 0) {
+        a.flag = p->qflag.as<uint8_t>(), a.nblk = (int)qblk, a.off = p->qoff.as<const int64_t>();
+        if (p->f32) hipLaunchKernelGGL(tsdf_quad_write_kernel<float>, qgrid, block, 0, s, a);
+        else hipLaunchKernelGGL(tsdf_quad_write_kernel<double>, qgrid, block, 0, s, a);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->t_write.e1, s));
+    p->t_write.timed = true;
+    HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+// Device time of the last integration, of the last count (classification, numbering, quad flags and both scans) and of the last write;
+// any pointer may be NULL.
+int pcs_tsdf_last_kernel_ms(pcs_tsdf_volume *p, float *integrate_ms, float *count_ms, float *write_ms) {
+    const char *who = "pcs_tsdf_last_kernel_ms";
+    if (!p || (!integrate_ms && !count_ms && !write_ms)) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (integrate_ms)
+        if (const int rc = timer_ms(who, &p->t_integrate, integrate_ms, "no integration has run yet")) return rc;
+    if (count_ms)
+        if (const int rc = timer_ms(who, &p->t_count, count_ms, "no count has run yet")) return rc;
+    if (write_ms)
+        if (const int rc = timer_ms(who, &p->t_write, write_ms, "no write has run yet")) return rc;
+    return PCS_OK;
+}
+
+}  // extern "C"
