@@ -1333,6 +1333,69 @@ int pcs_tsdf_extract_write(pcs_tsdf_volume *p, void *d_vertices, int vertex_dtyp
 int pcs_tsdf_last_kernel_ms(pcs_tsdf_volume *p, float *integrate_ms, float *count_ms, float *write_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ray-cast of the TSDF volume: depth and normal maps of any view (csrc/ba_tsdf_raycast.hpp).  Since pcs_version() 128.
+ * Replaces: nothing the reference computes.  It is KinectFusion's surface prediction on the volume above: the model's depth in a view,
+ *           to hold against the measured depth map of that view, to fill its holes, to say which view sees a point, or to look at the
+ *           scene from a pose no camera had.  The rule below is the library's own; tests/raycast_reference.py states it in NumPy.
+ * The arithmetic is that of the block above: FP64, plain IEEE operations in the order written, no contraction, sums of three products
+ * taken left to right, and a comparison with a NaN fails.  The volume, OBSERVED (weight >= min_weight) and D = double(sum) /
+ * double(weight) are exactly those of the extraction.  n_a stands for (nx, ny, nz) and h_a = n_a - 1.
+ * Render views.  They are independent of the integration's: distortion-free pinholes K = [fx, cx, fy, cy] with [R | t] world -> view,
+ * and the call gives their width and height.  The host builds one table row per view: K, the nine entries of R, and the centre
+ * C_a = -((R_0a t_0 + R_1a t_1) + R_2a t_2).
+ * Ray of pixel (x, y).  r = ((x - cx) / fx, (y - cy) / fy, 1) and w_a = (R_0a r_0 + R_1a r_1) + R_2a r_2.  The world point at z-depth z
+ * is C + z w: the parameter is the z-depth, as in every depth map of the library.  In grid units gc_a = (C_a - o_a) / s, gw_a = w_a / s.
+ * Clip.  For each axis a: if gw_a == 0 the ray misses unless 0 <= gc_a <= h_a, and the axis bounds nothing; otherwise t0 = (0 - gc_a) /
+ * gw_a, t1 = (h_a - gc_a) / gw_a and the axis contributes lo = min(t0, t1), hi = max(t0, t1).  z0 = max(z_near, the lo's), z1 =
+ * min(z_far, the hi's).  The ray misses the box (status 3) unless every n_a >= 2 and z0 <= z1.
+ * March.  dz = step / sqrt((w_0^2 + w_1^2) + w_2^2): samples are `step` apart in space.  q = (z1 - z0) / dz and N = floor(q).  The ray
+ * also counts as missed (status 3) unless q <= 113513 (64 sqrt(3) 1024 + 1, rounded up), which holds for every R that is a rotation:
+ * the loop is bounded for any finite table.  Sample n = 0 .. N sits at z_n = z0 + n dz, a product and never an accumulated sum, so that a
+ * sample's position does not depend on which samples before it were evaluated.
+ * Sample T(g) at g_a = gc_a + z gw_a.  Cell c_a = min(max(floor(g_a), 0), n_a - 2); fraction f_a = min(max(g_a - c_a, 0), 1).  The sample
+ * is VALID iff the eight corners of cell c are OBSERVED.  Its value is the trilinear blend of the corners' D, each step in the form
+ * (1 - f) A + f B, along x, then y, then z.  The two-product form is deliberate: with f in [0, 1] and all corners > 0 the result is > 0
+ * exactly (short of underflow), and the skipping below rests on that.
+ * Hit.  The first n >= 1 at which samples n - 1 and n are both VALID with T_{n-1} > 0 and T_n <= 0.  The depth is z = z_{n-1} + dz
+ * (T_{n-1} / (T_{n-1} - T_n)).  A crossing from inside to outside, or one next to an invalid sample, is not a hit and the march goes on.
+ * If no n qualifies the status is 2.
+ * Normal at the hit point g = gc + z gw.  G_a = T(g + e_a) - T(g - e_a), central differences one node apart, taken in the order +x, -x,
+ * +y, -y, +z, -z.  Each of the six samples needs 0 <= its coordinate <= h_b on every axis b and must be VALID.  n = G / sqrt((G_0^2 +
+ * G_1^2) + G_2^2), in the world frame, pointing from inside to outside, stored as float32.  If a sample fails or |G| is not > 0 the
+ * normal is NaN and the status 1; the depth is kept.
+ * Outputs.  Depth (float32 or float64, the float64 value rounded once) is NaN where there is no hit: an invalid depth by the library's
+ * own convention, so the map feeds pcs_fuse_run and pcs_tsdf_integrate unchanged.  Status is a uint8: PCS_TSDF_RAY_HIT 0,
+ * PCS_TSDF_RAY_NO_NORMAL 1 (hit, no normal), PCS_TSDF_RAY_NO_CROSSING 2, PCS_TSDF_RAY_MISSED 3 (the box or the z-range).
+ * Skipping empty space.  A mask pass runs before the cast, once per call because it depends on min_weight: it flags every brick of 8^3
+ * cells one of whose corner nodes has weight >= min_weight and sum <= 0.  A sample whose cell lies in an unflagged brick is invalid or
+ * > 0, can never be the second sample of a hit and is not evaluated; it can be the first, so on reaching a sample in a flagged brick
+ * whose predecessor was skipped, the predecessor is evaluated for real.  flags bit 0, PCS_TSDF_RAYCAST_NO_SKIP, casts without the mask:
+ * every output has the same bits either way.
+ * Limits, checked on the host before the device is touched (PCS_ERR_ARG; pcs_last_error names the argument): views and sides as for
+ * pcs_fuse_set_views; min_weight in [1, 65535]; step finite with voxel / 64 <= step, so that N <= 64 sqrt(3) 1024 + 1 and the kernel has
+ * no open-ended loop; 0 <= z_near < z_far, where z_far may be +inf; a grid must be set.  The handle is looked at last.
+ *   pcs_tsdf_raycast                 K (n_views, 4) and P (n_views, 12) HOST, copied.  d_depth (n_views, height, width) of depth_dtype;
+ *                                    d_normal (n_views, height, width, 3) float32 or NULL: the six normal samples are then not taken
+ *                                    and status 1 is not produced; d_status (n_views, height, width) or NULL.  The call reads the
+ *                                    volume only: a preceding pcs_tsdf_extract_count stays valid for pcs_tsdf_extract_write, and the
+ *                                    integration's view table is kept.  Two launches (mask, cast), one with PCS_TSDF_RAYCAST_NO_SKIP.
+ *                                    The host waits for the handle's queued runs before it replaces the table of the render views.
+ *   pcs_tsdf_raycast_last_kernel_ms  device time of the last cast's mask pass and of its cast kernel; either pointer may be NULL.
+ *                                    PCS_ERR_STATE when the part asked for did not run.
+ *   pcs_tsdf_raycast_count_samples   for measurements: the last pcs_tsdf_raycast over again in a separate launch (its views, settings
+ *                                    and mask; none of its outputs is touched) that writes to d_samples (n_views, height, width) uint32
+ *                                    the number of samples each pixel's march and normal evaluated.  The cast itself counts nothing.
+ *                                    PCS_ERR_STATE when no cast ran on the volume as it stands.
+ * Not done here: colour or intensity per pixel, distorted render views, a hierarchy deeper than one brick level or a stride over whole
+ * bricks, a step that adapts to the distance value (it would tie a sample's position to the samples before it).
+ */
+enum { PCS_TSDF_RAY_HIT = 0, PCS_TSDF_RAY_NO_NORMAL = 1, PCS_TSDF_RAY_NO_CROSSING = 2, PCS_TSDF_RAY_MISSED = 3, PCS_TSDF_RAYCAST_NO_SKIP = 1 };
+int pcs_tsdf_raycast(pcs_tsdf_volume *p, int64_t n_views, int width, int height, const double *K, const double *P, int min_weight, double step, double z_near,
+                     double z_far, void *d_depth, int depth_dtype, float *d_normal, uint8_t *d_status, int flags, void *stream);
+int pcs_tsdf_raycast_last_kernel_ms(pcs_tsdf_volume *p, float *mask_ms, float *cast_ms);
+int pcs_tsdf_raycast_count_samples(pcs_tsdf_volume *p, uint32_t *d_samples, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.
  * Replaces: find_target_pose_at_timestep and find_target_poses (optimisation/find_target.py:9-82), which fix every camera's "ext", "int"
  *           and "dst" and run the whole bundle adjustment for the target poses that are left.  With the cameras fixed the problem is one

@@ -6,7 +6,7 @@ first use and there is no CPU fallback.
 """
 from .detections import TargetDetection  # noqa: F401
 
-__all__ = ["TargetDetection", "Engine", "parameter_covariance", "ParameterCovariance", "handlers", "function_blocks", "compiled_helpers", "pose_seeding", "device_solver", "sharding", "synthetic", "imaging", "stereo", "fusion", "sweep", "volume"]
+__all__ = ["TargetDetection", "Engine", "parameter_covariance", "ParameterCovariance", "handlers", "function_blocks", "compiled_helpers", "pose_seeding", "device_solver", "sharding", "synthetic", "imaging", "stereo", "fusion", "sweep", "volume", "raycast_views", "depth_residuals"]
 __version__ = "0.1.0"
 
 
@@ -17,6 +17,9 @@ def __getattr__(name):
     if name in ("parameter_covariance", "ParameterCovariance"):
         from . import device_solver
         return getattr(device_solver, name)
+    if name in ("raycast_views", "depth_residuals"):
+        from . import volume
+        return getattr(volume, name)
     if name in ("handlers", "function_blocks", "synthetic", "engine", "optimisation_handling", "sharding", "device_solver",
                 "compiled_helpers", "detections", "pose_seeding", "imaging", "stereo", "fusion", "sweep", "volume"):
         import importlib

@@ -58,6 +58,7 @@
 #include "ba_fusion.hpp"
 #include "ba_sweep.hpp"
 #include "ba_tsdf.hpp"
+#include "ba_tsdf_raycast.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side

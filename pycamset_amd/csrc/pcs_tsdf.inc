@@ -2,17 +2,20 @@
 // ba_tsdf.hpp).  The handle owns the view table (the rows of pcs_fuse_set_views), the volume (sum and weight per node), the view list
 // of the last integration and the extraction's workspace: the cell flags, the cell -> vertex map, the quad flags and the block counts
 // and offsets of the two compactions (stereo_count_kernel / stereo_scan_kernel, unchanged).  Depth maps, vertices and quads are the
-// caller's device buffers.  Fence and timers are those of pcs_handle.inc (DESIGN.md, "Batched handles").
+// caller's device buffers.  The ray-cast (kernels: ba_tsdf_raycast.hpp) adds the table of the render views and the brick mask; it reads
+// the volume only.  Fence and timers are those of pcs_handle.inc (DESIGN.md, "Batched handles").
 struct pcs_tsdf_volume {
     HandleCore core;
-    KernelTimer t_integrate, t_count, t_write;
-    DevBuf views, list, sum, weight, cflag, map, qflag, blk, coff, qoff;
+    KernelTimer t_integrate, t_count, t_write, t_mask, t_cast;
+    DevBuf views, list, sum, weight, cflag, map, qflag, blk, coff, qoff, rviews, brick;
     int64_t n_views = 0, n_integrated = 0;   // n_integrated: views integrated since the volume was zeroed (no weight can exceed it)
     int width = 0, height = 0;
     TsdfGrid g{};
     bool have_grid = false, f32 = true, counted = false;   // counted: an extract_count on the volume as it stands
     int min_weight = 0;
     int64_t n_vertices = 0, n_quads = 0;
+    TsdfRaycastArgs last_cast{};   // the last cast, for pcs_tsdf_raycast_count_samples; cast_views = 0: none on the volume as it stands
+    int64_t cast_views = 0;
     int64_t nodes() const { return (int64_t)g.nx * g.ny * g.nz; }
     int64_t cells() const { return (int64_t)(g.nx - 1) * (g.ny - 1) * (g.nz - 1); }
 };
@@ -43,6 +46,38 @@ static int tsdf_check_integrate(const char *who, const void *d_depth, int depth_
     return PCS_OK;
 }
 
+// Every argument of pcs_tsdf_raycast that needs no handle (the grid is looked at with the handle: step is held against its voxel).
+static int tsdf_check_raycast(const char *who, int64_t n_views, int width, int height, const double *K, const double *P, int min_weight, double step, double z_near,
+                              double z_far, const void *d_depth, int depth_dtype, int flags) {
+    if (const int rc = fuse_check_views(who, n_views, width, height, K, P)) return rc;
+    if (min_weight < 1 || min_weight > TSDF_MAX_WEIGHT) return fail(PCS_ERR_ARG, "%s: min_weight %d outside [1, %d]", who, min_weight, TSDF_MAX_WEIGHT);
+    if (!std::isfinite(step) || !(step > 0.0)) return fail(PCS_ERR_ARG, "%s: step must be finite and > 0 (got %g)", who, step);
+    if (!(z_near >= 0.0) || !(z_near < z_far)) return fail(PCS_ERR_ARG, "%s: z_near and z_far must satisfy 0 <= z_near < z_far (got %g, %g)", who, z_near, z_far);
+    if (depth_dtype != PCS_F64 && depth_dtype != PCS_F32) return fail(PCS_ERR_ARG, "%s: depth_dtype PCS_F64 or PCS_F32", who);
+    if (!d_depth) return fail(PCS_ERR_ARG, "%s: d_depth must be given", who);
+    if (flags & ~PCS_TSDF_RAYCAST_NO_SKIP) return fail(PCS_ERR_ARG, "%s: flags %d has bits other than PCS_TSDF_RAYCAST_NO_SKIP", who, flags);
+    return PCS_OK;
+}
+
+// The table of the render views: per view K = [fx, cx, fy, cy], the nine entries of R row-major, then the centre
+// C_a = -((R_0a t_0 + R_1a t_1) + R_2a t_2), in plain double operations in that order
+static std::vector<double> tsdf_render_rows(int64_t n_views, const double *K, const double *P) {
+    std::vector<double> rows(16 * (size_t)n_views);
+    for (int64_t v = 0; v < n_views; ++v) {
+        double *o = rows.data() + 16 * v;
+        const double *Pv = P + 12 * v;
+        std::copy(K + 4 * v, K + 4 * v + 4, o);
+        for (int k = 0; k < 9; ++k) o[4 + k] = Pv[k + k / 3];
+        for (int a = 0; a < 3; ++a) {
+            volatile double m0 = Pv[a] * Pv[3], m1 = Pv[4 + a] * Pv[7], m2 = Pv[8 + a] * Pv[11];   // each product rounded on its own: no contraction on the host either
+            volatile double sum = m0 + m1;
+            sum = sum + m2;
+            o[13 + a] = -sum;
+        }
+    }
+    return rows;
+}
+
 static TsdfExtractArgs tsdf_extract_args(const pcs_tsdf_volume *p) {
     TsdfExtractArgs a{};
     a.sum = p->sum.p, a.weight = p->weight.as<const uint16_t>(), a.g = p->g, a.min_weight = p->min_weight, a.map = p->map.as<int32_t>();
@@ -59,6 +94,8 @@ int pcs_tsdf_create(pcs_tsdf_volume **out, int device) {
     if (e == hipSuccess) e = p->t_integrate.create();
     if (e == hipSuccess) e = p->t_count.create();
     if (e == hipSuccess) e = p->t_write.create();
+    if (e == hipSuccess) e = p->t_mask.create();
+    if (e == hipSuccess) e = p->t_cast.create();
     if (e != hipSuccess) {
         const int rc = fail(PCS_ERR_HIP, "pcs_tsdf_create: %s", hipGetErrorString(e));
         pcs_tsdf_destroy(p);
@@ -70,7 +107,8 @@ int pcs_tsdf_create(pcs_tsdf_volume **out, int device) {
 
 int pcs_tsdf_destroy(pcs_tsdf_volume *p) {
     if (!p) return PCS_OK;
-    p->core.destroy({&p->views, &p->list, &p->sum, &p->weight, &p->cflag, &p->map, &p->qflag, &p->blk, &p->coff, &p->qoff}, {&p->t_integrate, &p->t_count, &p->t_write});
+    p->core.destroy({&p->views, &p->list, &p->sum, &p->weight, &p->cflag, &p->map, &p->qflag, &p->blk, &p->coff, &p->qoff, &p->rviews, &p->brick},
+                    {&p->t_integrate, &p->t_count, &p->t_write, &p->t_mask, &p->t_cast});
     delete p;
     return PCS_OK;
 }
@@ -94,7 +132,7 @@ static int tsdf_zero(pcs_tsdf_volume *p) {
     HIPCHK(hipMemsetAsync(p->sum.p, 0, (size_t)N * (p->f32 ? sizeof(float) : sizeof(double)), p->core.stream));
     HIPCHK(hipMemsetAsync(p->weight.p, 0, (size_t)N * sizeof(uint16_t), p->core.stream));
     HIPCHK(hipStreamSynchronize(p->core.stream));
-    p->n_integrated = 0, p->counted = false;
+    p->n_integrated = 0, p->counted = false, p->cast_views = 0;
     return PCS_OK;
 }
 
@@ -105,6 +143,7 @@ int pcs_tsdf_set_grid(pcs_tsdf_volume *p, const double *origin, double voxel, in
     if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
     HIPCHK(p->core.quiesce());
     p->have_grid = p->counted = false;
+    p->cast_views = 0;
     const int64_t N = (int64_t)nx * ny * nz;
     if (const int rc = p->sum.grow(N * (sum_dtype == PCS_F32 ? 1 : 2), sizeof(float))) return rc;   // capacity counted in 4-byte words: either dtype fits
     if (const int rc = p->weight.grow(N, sizeof(uint16_t))) return rc;
@@ -147,7 +186,7 @@ int pcs_tsdf_integrate(pcs_tsdf_volume *p, const void *d_depth, int depth_dtype,
     a.views = p->views.as<const double>(), a.list = views ? p->list.as<const int32_t>() : nullptr, a.n_list = (int)m, a.depth = d_depth, a.W = p->width, a.H = p->height;
     a.g = p->g, a.trunc = trunc, a.sum = p->sum.p, a.weight = p->weight.as<uint16_t>();
     const dim3 grid((unsigned)((p->g.nx + TSDF_TX - 1) / TSDF_TX), (unsigned)((p->g.ny + TSDF_TY - 1) / TSDF_TY), (unsigned)p->g.nz), block(TSDF_TX, TSDF_TY);
-    p->counted = false;
+    p->counted = false, p->cast_views = 0;
     p->n_integrated += m;
     HIPCHK(hipEventRecord(p->t_integrate.e0, s));
     if (depth_dtype == PCS_F32) {
@@ -257,6 +296,96 @@ int pcs_tsdf_extract_write(pcs_tsdf_volume *p, void *d_vertices, int vertex_dtyp
     HIPCHK(hipEventRecord(p->t_write.e1, s));
     p->t_write.timed = true;
     HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+// Depth, normal and status maps of n_views render views by marching the volume (the rule: include/pcs_hip.h).  K and P are HOST arrays
+// and are copied.  The volume, the integration's view table and a preceding count are left as they are.
+int pcs_tsdf_raycast(pcs_tsdf_volume *p, int64_t n_views, int width, int height, const double *K, const double *P, int min_weight, double step, double z_near,
+                     double z_far, void *d_depth, int depth_dtype, float *d_normal, uint8_t *d_status, int flags, void *stream) {
+    const char *who = "pcs_tsdf_raycast";
+    if (const int rc = tsdf_check_raycast(who, n_views, width, height, K, P, min_weight, step, z_near, z_far, d_depth, depth_dtype, flags)) return rc;
+    if (n_views > 65535) return fail(PCS_ERR_ARG, "%s: n_views %lld above 65535", who, (long long)n_views);   // blockIdx.z; fuse_check_views stops at 32767 already
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (!p->have_grid) return fail(PCS_ERR_ARG, "%s: no grid: pcs_tsdf_set_grid comes first", who);
+    if (!(step >= p->g.s / 64.0)) return fail(PCS_ERR_ARG, "%s: step %g is below voxel / 64 = %g", who, step, p->g.s / 64.0);
+    const std::vector<double> rows = tsdf_render_rows(n_views, K, P);
+    const bool cells = p->g.nx >= 2 && p->g.ny >= 2 && p->g.nz >= 2;   // no cells: every ray misses and no mask is made
+    const bool skip = cells && !(flags & PCS_TSDF_RAYCAST_NO_SKIP);
+    const int bx = cells ? (p->g.nx - 1 + 7) >> 3 : 1, by = cells ? (p->g.ny - 1 + 7) >> 3 : 1, bz = cells ? (p->g.nz - 1 + 7) >> 3 : 1;
+    const int64_t n_bricks = (int64_t)bx * by * bz;
+    HIPCHK(p->core.quiesce());   // a queued cast may still read the old table
+    p->cast_views = 0;
+    const HostArray up[] = {{p->rviews, rows.data(), 16 * n_views, sizeof(double)}};
+    if (const int rc = upload_host_arrays(p->core, up, 1)) return rc;
+    if (skip)
+        if (const int rc = p->brick.grow(n_bricks, 1)) return rc;
+    hipStream_t s = p->core.stream_or(stream);
+    HIPCHK(p->core.fence.before_run(s, false));
+    if (skip) {
+        TsdfMaskArgs m{};
+        m.sum = p->sum.p, m.weight = p->weight.as<const uint16_t>(), m.g = p->g, m.bx = bx, m.by = by, m.bz = bz, m.min_weight = min_weight, m.mask = p->brick.as<uint8_t>();
+        const dim3 grid((unsigned)((p->g.nx + TSDF_TX - 1) / TSDF_TX), (unsigned)((p->g.ny + TSDF_TY - 1) / TSDF_TY), (unsigned)p->g.nz), block(TSDF_TX, TSDF_TY);
+        HIPCHK(hipEventRecord(p->t_mask.e0, s));
+        HIPCHK(hipMemsetAsync(p->brick.p, 0, (size_t)n_bricks, s));
+        if (p->f32) hipLaunchKernelGGL(tsdf_brick_mask_kernel<float>, grid, block, 0, s, m);
+        else hipLaunchKernelGGL(tsdf_brick_mask_kernel<double>, grid, block, 0, s, m);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(p->t_mask.e1, s));
+    }
+    p->t_mask.timed = skip;
+    TsdfRaycastArgs a{};
+    a.views = p->rviews.as<const double>(), a.sum = p->sum.p, a.weight = p->weight.as<const uint16_t>(), a.mask = skip ? p->brick.as<const uint8_t>() : nullptr;
+    a.g = p->g, a.bx = bx, a.by = by, a.W = width, a.H = height, a.min_weight = min_weight, a.step = step, a.z_near = z_near, a.z_far = z_far;
+    a.depth = d_depth, a.normal = d_normal, a.status = d_status;
+    const dim3 grid((unsigned)((width + TSDF_RAY_BLOCK - 1) / TSDF_RAY_BLOCK), (unsigned)((height + TSDF_RAY_BLOCK - 1) / TSDF_RAY_BLOCK), (unsigned)n_views),
+        block(TSDF_RAY_BLOCK * TSDF_RAY_BLOCK);
+    HIPCHK(hipEventRecord(p->t_cast.e0, s));
+    if (depth_dtype == PCS_F32) {
+        if (p->f32) hipLaunchKernelGGL((tsdf_raycast_kernel<float, float>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((tsdf_raycast_kernel<double, float>), grid, block, 0, s, a);
+    } else {
+        if (p->f32) hipLaunchKernelGGL((tsdf_raycast_kernel<float, double>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((tsdf_raycast_kernel<double, double>), grid, block, 0, s, a);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->t_cast.e1, s));
+    p->t_cast.timed = true;
+    HIPCHK(p->core.fence.after_run(s));
+    p->last_cast = a, p->cast_views = n_views;
+    return PCS_OK;
+}
+
+// The bench's separate counting launch: the last pcs_tsdf_raycast over again (its views, settings and mask; none of its outputs is
+// touched), writing per pixel the number of samples the march and the normal evaluated.
+int pcs_tsdf_raycast_count_samples(pcs_tsdf_volume *p, uint32_t *d_samples, void *stream) {
+    const char *who = "pcs_tsdf_raycast_count_samples";
+    if (!d_samples) return fail(PCS_ERR_ARG, "%s: d_samples must be given", who);
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (!p->have_grid || p->cast_views == 0) return fail(PCS_ERR_STATE, "%s: no pcs_tsdf_raycast on the volume as it stands", who);
+    HIPCHK(hipSetDevice(p->core.device));
+    hipStream_t s = p->core.stream_or(stream);
+    HIPCHK(p->core.fence.before_run(s, false));
+    TsdfRaycastArgs a = p->last_cast;
+    a.samples = d_samples;
+    const dim3 grid((unsigned)((a.W + TSDF_RAY_BLOCK - 1) / TSDF_RAY_BLOCK), (unsigned)((a.H + TSDF_RAY_BLOCK - 1) / TSDF_RAY_BLOCK), (unsigned)p->cast_views),
+        block(TSDF_RAY_BLOCK * TSDF_RAY_BLOCK);
+    if (p->f32) hipLaunchKernelGGL((tsdf_raycast_kernel<float, float, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((tsdf_raycast_kernel<double, float, true>), grid, block, 0, s, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+// Device time of the last cast's mask pass (memset and mask kernel) and of its cast kernel; either pointer may be NULL.  PCS_ERR_STATE
+// when the part asked for did not run: no cast yet, or a mask asked for after a cast without one.
+int pcs_tsdf_raycast_last_kernel_ms(pcs_tsdf_volume *p, float *mask_ms, float *cast_ms) {
+    const char *who = "pcs_tsdf_raycast_last_kernel_ms";
+    if (!p || (!mask_ms && !cast_ms)) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (mask_ms)
+        if (const int rc = timer_ms(who, &p->t_mask, mask_ms, "the last cast made no mask")) return rc;
+    if (cast_ms)
+        if (const int rc = timer_ms(who, &p->t_cast, cast_ms, "no cast has run yet")) return rc;
     return PCS_OK;
 }
 

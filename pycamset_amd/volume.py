@@ -12,13 +12,17 @@ z-depths, float32 or float64, invalid where NaN, +-inf or <= 0.  NumPy arrays ar
 arrays; torch tensors on the device are used in place and the results are torch tensors.  There is no CPU fallback; the argument checks
 raise ValueError before anything touches the device.
 
-Not done here: per-view weights, colour or intensity per vertex, marching cubes, a sparse or hashed volume, mesh smoothing or
-simplification, distorted views (undistort first: ``imaging.undistort_images``)."""
+``raycast_views`` renders the volume back into any pinhole view by marching the distance field (csrc/ba_tsdf_raycast.hpp): the model's
+depth and normal per pixel, which says what a view sees of the surface; ``depth_residuals`` holds it against measured depth maps, the
+dense counterpart of the reprojection statistics.
+
+Not done here: per-view weights, colour or intensity per vertex (``raycast_views`` gives the visibility it needs), marching cubes, a
+sparse or hashed volume, mesh smoothing or simplification, distorted views (undistort first: ``imaging.undistort_images``)."""
 from __future__ import annotations
 
 import numpy as np
 
-from ._capi import TSDF_MAX_DIM, TSDF_MAX_WEIGHT
+from ._capi import TSDF_MAX_DIM, TSDF_MAX_WEIGHT, TSDF_RAYCAST_NO_SKIP
 from .compiled_helpers import _Handle
 from .engine import _stream_arg
 from .fusion import MAX_SIDE, MAX_VIEWS
@@ -140,6 +144,30 @@ class TsdfVolume(_Handle):
     def extract_write(self, d_vertices, f32, d_quads, stream=None):
         self._call("pcs_tsdf_extract_write", self._h, self._addr(d_vertices), int(bool(f32)), self._addr(d_quads), _stream_arg(stream))
 
+    def raycast(self, width, height, K, P, min_weight, step, z_near, z_far, d_depth, depth_f32, d_normal=None, d_status=None, skip=True, stream=None):
+        """The thin call of ``pcs_tsdf_raycast``: ``K`` (V, 4) and ``P`` (V, 12) on the host, the outputs raw device addresses
+        (``d_normal`` and ``d_status`` may be None)."""
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(-1, 4)
+        P = np.ascontiguousarray(P, dtype=np.float64).reshape(-1, 12)
+        self._call("pcs_tsdf_raycast", self._h, K.shape[0], int(width), int(height), self._ptr(K), self._ptr(P), int(min_weight), float(step), float(z_near), float(z_far),
+                   self._addr(d_depth), int(bool(depth_f32)), self._addr(d_normal), self._addr(d_status), 0 if skip else TSDF_RAYCAST_NO_SKIP, _stream_arg(stream))
+
+    def raycast_count_samples(self, d_samples, stream=None):
+        """For measurements: the last cast over again in a separate launch that writes the samples each pixel evaluated to ``d_samples``
+        (V, H, W) uint32; the cast's outputs are not touched."""
+        self._call("pcs_tsdf_raycast_count_samples", self._h, self._addr(d_samples), _stream_arg(stream))
+
+    def raycast_last_kernel_ms(self):
+        """-> (mask, cast) in ms of the last cast; NaN for a part that did not run."""
+        out = []
+        for k in range(2):
+            ms = self._ct.c_float(0.0)
+            args = [None, None]
+            args[k] = self._ct.byref(ms)
+            rc = getattr(self._capi.lib(), "pcs_tsdf_raycast_last_kernel_ms")(self._h, *args)
+            out.append(float(ms.value) if rc == 0 else float("nan"))
+        return tuple(out)
+
     def last_kernel_ms(self):
         """-> (integrate, count, write) in ms; NaN for a part that has not run."""
         out = []
@@ -211,6 +239,105 @@ def extract_surface(volume, min_weight=2, dtype=np.float32, triangles=False):
     if triangles:
         quads = quads_to_triangles(quads)
     return _result(verts, volume.as_tensor), _result(quads, volume.as_tensor)
+
+
+def check_raycast_args(n_views, width, height, K, ext, voxel, min_weight=2, step=None, z_near=0.0, z_far=np.inf, dtype=np.float32):
+    """The checks of pcs_tsdf_raycast on the host; the ValueError names the argument.  ``voxel``: of the volume that is cast.
+    -> (K (V, 4), P (V, 12), min_weight, step, z_near, z_far, f32)."""
+    if not 1 <= n_views <= MAX_VIEWS:
+        raise ValueError(f"K: between 1 and {MAX_VIEWS} views per call, got {n_views}")
+    for val, name in ((width, "width"), (height, "height")):
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer)) or not 1 <= val <= MAX_SIDE:
+            raise ValueError(f"{name}: expected an integer in [1, {MAX_SIDE}], got {val!r}")
+    Ka = np.asarray(K, dtype=np.float64)
+    if Ka.shape != (n_views, 4):
+        raise ValueError(f"K: expected ({n_views}, 4) rows [fx, cx, fy, cy], got shape {np.shape(K)}")
+    if not np.all(np.isfinite(Ka)) or np.any(Ka[:, 0] == 0) or np.any(Ka[:, 2] == 0):
+        raise ValueError("K: every entry must be finite and the focal lengths non-zero")
+    P = check_ext(ext, n_views)
+    if P is None or not np.all(np.isfinite(P)):
+        raise ValueError(f"ext: expected finite ({n_views}, 3, 4) world -> view")
+    if isinstance(min_weight, bool) or not isinstance(min_weight, (int, np.integer)) or not 1 <= min_weight <= TSDF_MAX_WEIGHT:
+        raise ValueError(f"min_weight: expected an integer in [1, {TSDF_MAX_WEIGHT}], got {min_weight!r}")
+    voxel = _number(voxel, "voxel")
+    step = voxel if step is None else _number(step, "step")
+    if not step >= voxel / 64.0:
+        raise ValueError(f"step: {step!r} is below voxel / 64 = {voxel / 64.0!r}")
+    for val, name in ((z_near, "z_near"), (z_far, "z_far")):
+        if isinstance(val, bool) or not isinstance(val, (int, float, np.integer, np.floating)) or val != val:
+            raise ValueError(f"{name}: expected a number, got {val!r}")
+    if not (0.0 <= z_near < z_far) or not np.isfinite(z_near):
+        raise ValueError(f"z_near: expected 0 <= z_near < z_far, got {z_near!r} and z_far {z_far!r}")
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"dtype: expected float32 or float64, got {dtype!r}")
+    return np.ascontiguousarray(Ka), P, int(min_weight), step, float(z_near), float(z_far), np.dtype(dtype) == np.dtype(np.float32)
+
+
+def _n_views(K):
+    shape = np.shape(K)
+    if len(shape) != 2:
+        raise ValueError(f"K: expected (V, 4) rows [fx, cx, fy, cy], got shape {shape}")
+    return shape[0]
+
+
+def raycast_views(volume, K, ext, width, height, *, min_weight=2, step=None, z_near=0.0, z_far=np.inf, dtype=np.float32, normals=True, status=False, skip=True):
+    """Depth and normal maps of a volume as seen by the pinhole views ``K`` (V, 4) = [fx, cx, fy, cy], ``ext`` (V, 3, 4) world -> view,
+    of ``width`` x ``height`` pixels, by marching the distance field (the rule of include/pcs_hip.h): the views need not be the ones that
+    were integrated.  ``min_weight``: a node counts when at least that many views saw it, as in ``extract_surface``.  ``step``: the
+    distance between samples along a ray, default the voxel size, at least voxel / 64.  ``z_near``, ``z_far``: the z-depth range.
+    -> depth (V, H, W) of ``dtype``, NaN where the ray meets no surface, and normals (V, H, W, 3) float32 in the world frame pointing
+    from inside to outside (None with ``normals=False``); with ``status=True`` also the uint8 status (0 hit, 1 hit without normal, 2 no
+    crossing, 3 missed the box or the z-range).  ``skip=False`` casts without the empty-space mask: the same bits, for measuring.
+    Tensors on the device when the volume was integrated from tensors on the device, NumPy otherwise."""
+    torch = _torch()
+    if not isinstance(volume, TsdfVolume) or volume.dims is None:
+        raise ValueError("volume: expected a TsdfVolume with a grid")
+    Ka, P, min_weight, step, z_near, z_far, f32 = check_raycast_args(_n_views(K), width, height, K, ext, volume.voxel, min_weight, step, z_near, z_far, dtype)
+    V, W, H = len(Ka), int(width), int(height)
+    dev = torch.device("cuda", volume.device)
+    depth = torch.empty((V, H, W), dtype=torch.float32 if f32 else torch.float64, device=dev)
+    normal = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev) if normals else None
+    stat = torch.empty((V, H, W), dtype=torch.uint8, device=dev) if status else None
+    volume.raycast(W, H, Ka, P, min_weight, step, z_near, z_far, depth.data_ptr(), f32, None if normal is None else normal.data_ptr(), None if stat is None else stat.data_ptr(),
+                   skip=skip, stream=_stream(volume.device))
+    out = (_result(depth, volume.as_tensor), None if normal is None else _result(normal, volume.as_tensor))
+    return out + (_result(stat, volume.as_tensor),) if status else out
+
+
+def depth_residuals(volume, depth, K, ext, **raycast_arguments):
+    """The model against measured depth maps, the check to run after ``mesh_views`` / ``integrate_depth_maps``: casts the views of
+    ``depth`` (V, H, W) and -> (residual (V, H, W) = model - depth where both are valid, NaN elsewhere; stats (V, 3) float64 = per view the
+    count of valid residuals, their median and the median absolute deviation from it: NaN for a view without one).  The keyword
+    arguments are those of ``raycast_views`` (the residual has its ``dtype``); the statistics are computed with torch on the device.
+    Tensors when the volume was integrated from tensors on the device, NumPy otherwise."""
+    torch = _torch()
+    if getattr(depth, "ndim", None) != 3:
+        raise ValueError(f"depth: expected (V, H, W), got shape {tuple(getattr(depth, 'shape', ()))}")
+    for key in ("normals", "status"):
+        if key in raycast_arguments:
+            raise ValueError(f"{key}: not an argument of depth_residuals")
+    V, H, W = (int(v) for v in depth.shape)
+    if _n_views(K) != V:
+        raise ValueError(f"K: expected ({V}, 4), one row per depth map, got shape {np.shape(K)}")
+    as_tensor = volume.as_tensor if isinstance(volume, TsdfVolume) else False
+    try:
+        if isinstance(volume, TsdfVolume):
+            volume.as_tensor = True
+        model, _ = raycast_views(volume, K, ext, W, H, normals=False, **raycast_arguments)
+    finally:
+        if isinstance(volume, TsdfVolume):
+            volume.as_tensor = as_tensor
+    D = _to_device(depth, model.dtype, volume.device)
+    ok = torch.isfinite(model) & torch.isfinite(D) & (D > 0)
+    res = torch.where(ok, model - D, torch.full_like(model, float("nan")))
+    stats = torch.full((V, 3), float("nan"), dtype=torch.float64, device=res.device)
+    for v in range(V):
+        r = res[v][ok[v]].to(torch.float64)
+        stats[v, 0] = float(r.numel())
+        if r.numel():
+            med = r.median()
+            stats[v, 1], stats[v, 2] = med, (r - med).abs().median()
+    return _result(res, as_tensor), _result(stats, as_tensor)
 
 
 def quads_to_triangles(quads):
