@@ -1296,7 +1296,7 @@ int pcs_sweep_last_kernel_ms(pcs_plane_sweeper *p, float *kernel_ms);
  * quad flags 3 nz of ny nx.  Its limits (32767 views; one workgroup scans the block counts, however many) admit every grid up to
  * 1024^3, so PCS_TSDF_MAX_DIM is the only grid limit; vertex numbers are int32 (1023^3 < 2^31).  The volume is dense: 6 (float32 sum) or
  * 10 bytes per node, and the extraction's workspace 8 more per node.
- * Not done here: per-view weights, colour or intensity per vertex, marching cubes, a sparse or hashed volume, mesh smoothing or
+ * Not done here: per-view weights, colour or intensity per vertex (row f19 below does it), marching cubes, a sparse or hashed volume, mesh smoothing or
  * simplification, distorted views (undistort first, pcs_imap_*).
  *   pcs_tsdf_create          a handle on `device` (no counterpart); it owns the view table, the volume and the extraction's workspace
  *   pcs_tsdf_destroy         frees the handle (no counterpart)
@@ -1386,7 +1386,7 @@ int pcs_tsdf_last_kernel_ms(pcs_tsdf_volume *p, float *integrate_ms, float *coun
  *                                    and mask; none of its outputs is touched) that writes to d_samples (n_views, height, width) uint32
  *                                    the number of samples each pixel's march and normal evaluated.  The cast itself counts nothing.
  *                                    PCS_ERR_STATE when no cast ran on the volume as it stands.
- * Not done here: colour or intensity per pixel, distorted render views, a hierarchy deeper than one brick level or a stride over whole
+ * Not done here: colour or intensity per pixel (row f19 below does it), distorted render views, a hierarchy deeper than one brick level or a stride over whole
  * bricks, a step that adapts to the distance value (it would tie a sample's position to the samples before it).
  */
 enum { PCS_TSDF_RAY_HIT = 0, PCS_TSDF_RAY_NO_NORMAL = 1, PCS_TSDF_RAY_NO_CROSSING = 2, PCS_TSDF_RAY_MISSED = 3, PCS_TSDF_RAYCAST_NO_SKIP = 1 };
@@ -1394,6 +1394,70 @@ int pcs_tsdf_raycast(pcs_tsdf_volume *p, int64_t n_views, int width, int height,
                      double z_far, void *d_depth, int depth_dtype, float *d_normal, uint8_t *d_status, int flags, void *stream);
 int pcs_tsdf_raycast_last_kernel_ms(pcs_tsdf_volume *p, float *mask_ms, float *cast_ms);
 int pcs_tsdf_raycast_count_samples(pcs_tsdf_volume *p, uint32_t *d_samples, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Colour of surface points from the images (row f19): a colour per point from the source views that see it (SURVEY 8 row f19;
+ * csrc/ba_tsdf_colour.hpp).  Since pcs_version() 129.
+ * Replaces: nothing the reference computes; it draws what it reconstructs as coloured pyvista meshes.  This is the stage that brings the
+ *           images the pipeline started from back onto the mesh of pcs_tsdf_extract_* and into the views of pcs_tsdf_raycast.  The rule
+ *           below is the library's own; tests/colour_reference.py states it in NumPy.
+ * The arithmetic is that of the two blocks above: FP64, plain IEEE operations in the order written, no contraction, sums of three
+ * products taken left to right, and a comparison with a NaN fails.
+ * Inputs.  Points X (N, 3), float32 or float64.  Optional unit normals n (N, 3) float32 in the world frame, pointing outward as the
+ * ray-cast stores them.  A table of source views: K = [fx, cx, fy, cy] and [R | t] world -> view, distortion-free, all of one width x
+ * height with both sides >= 2.  Source images (n_views, height, pitch BYTES), interleaved channels 1, 3 or 4, PCS_IMAP_U8 or
+ * PCS_IMAP_F32.  Optional visibility depth maps (n_views, height, width), float32 or float64: normally the model's own depth from
+ * pcs_tsdf_raycast into the source views; measured depth maps are allowed.
+ * Per point and view, the views in list order:
+ *   Y = R X + t, Y_a = ((R_a0 X_0 + R_a1 X_1) + R_a2 X_2) + t_a.  Rejected unless Y_2 > 0.
+ *   u = fx (Y_0 / Y_2) + cx, w = fy (Y_1 / Y_2) + cy.  Rejected unless 0 <= u <= width - 1 and 0 <= w <= height - 1: every bilinear tap
+ *   lies inside the image and no border colour enters a blend.
+ *   Visibility, if maps are given: d at the nearest pixel (floor(u + 0.5), floor(w + 0.5)).  Rejected unless d is finite, d > 0 and
+ *   Y_2 <= d + occlusion_tol (the sum first).  occlusion_tol is in world units.
+ *   Angle, if normals are given: e_a = C_a - X_a with C the centre of the ray-cast's table, C_a = -((R_0a t_0 + R_1a t_1) + R_2a t_2);
+ *   c = ((n_0 e_0 + n_1 e_1) + n_2 e_2) / sqrt((e_0^2 + e_1^2) + e_2^2).  Rejected unless c > cos_min; a NaN normal rejects every view.
+ *   Without normals c = 1.
+ *   Sample: cell x0 = min(floor(u), width - 2), fraction f = u - x0, and the same in y.  Each step of the blend has the form
+ *   (1 - f) A + f B, along x for the upper and the lower row and then along y, per channel, in FP64 from the stored values.
+ * Combination over the contributing views, in list order.  Wt = Wt + c from 0 in both modes.
+ *   PCS_COLOUR_BLEND  S_k = S_k + c I_k from 0; colour_k = S_k / Wt.
+ *   PCS_COLOUR_BEST   the sample of the view with the largest c; a tie goes to the lower list position.
+ * Outputs.  colour (N, channels) PCS_IMAP_U8 or PCS_IMAP_F32: the FP64 value rounded once, the uint8 half-to-even and saturated as in
+ * pcs_imap_remap (a NaN gives 0).  weight (N) float32 = Wt; count (N) uint16, the number of contributing views; best (N) int32, the list
+ * position of the largest c (the lower on a tie) or -1.  A point without a contributing view gets fill[k] (HOST doubles, NULL means 0,
+ * rounded like a colour), weight 0, count 0, best -1.  Any output pointer but colour may be NULL.
+ * Limits, checked on the host before the device is touched (PCS_ERR_ARG; pcs_last_error names the argument): views as for
+ * pcs_fuse_set_views with both sides >= 2; pitch a multiple of the element size and at least a row; occlusion_tol finite and >= 0 when
+ * maps are given; cos_min in [0, 1); fill not infinite; min_weight in [1, 65535].  The handle is looked at last.
+ *   pcs_tsdf_point_normals          the normal rule of the ray-cast at n arbitrary points (mesh vertices get normals): g = (X - o) / s,
+ *                                   the six samples T(g +- e_a) through the cast's own sample function, each in the box and VALID, else
+ *                                   the normal is three NaNs and the status 1 (0 otherwise).  A NaN point or one outside the box gives
+ *                                   NaN.  d_normals (n, 3) float32; d_status (n) uint8 or NULL.  Needs a grid; reads the volume only.
+ *   pcs_tsdf_colour_points          the rule on caller-supplied points.  K, P and fill HOST, copied; d_points, d_normals (or NULL),
+ *                                   d_images, d_visibility (or NULL) and every output DEVICE.  It needs no grid.  n = 0 does nothing.
+ *   pcs_tsdf_colour_views           the same rule with the pixels of n_render render views (K_render, P_render HOST; r_width x r_height)
+ *                                   as the points: pixel (x, y) with z-depth z = d_depth (float32 or float64) is C + z w by the
+ *                                   ray-cast's formulas, X_a = C_a + z w_a.  A depth that is not finite or not > 0 gives the fill.
+ *                                   d_normal (n_render, r_height, r_width, 3) float32 or NULL: the outputs of pcs_tsdf_raycast.
+ *                                   Outputs in image order (n_render, r_height, r_width, ...).
+ *   pcs_tsdf_colour_last_kernel_ms  device time of the last pcs_tsdf_point_normals and of the last colour kernel; either pointer may be
+ *                                   NULL.  PCS_ERR_STATE when the part asked for did not run.
+ * The colour calls leave the volume, the integration's view table, a preceding pcs_tsdf_extract_count and the last cast as they are.
+ * One launch each; the loop over the views runs inside the thread in list order, so two runs give identical bits.
+ * Not done here: texture atlases and UV maps, distorted source views (undistort first: pcs_imap_remap), exposure or white-balance
+ * compensation between views, colour stored in the volume during integration, seam levelling.
+ */
+enum { PCS_COLOUR_BLEND = 0, PCS_COLOUR_BEST = 1 };
+int pcs_tsdf_point_normals(pcs_tsdf_volume *p, int64_t n, const void *d_points, int point_dtype, int min_weight, float *d_normals, uint8_t *d_status, void *stream);
+int pcs_tsdf_colour_points(pcs_tsdf_volume *p, int64_t n, const void *d_points, int point_dtype, const float *d_normals, int64_t n_views, int width, int height,
+                           const double *K, const double *P, const void *d_images, int64_t pitch, int channels, int image_dtype, const void *d_visibility,
+                           int visibility_dtype, double occlusion_tol, double cos_min, int mode, const double *fill, void *d_colour, int colour_dtype, float *d_weight,
+                           uint16_t *d_count, int32_t *d_best, void *stream);
+int pcs_tsdf_colour_views(pcs_tsdf_volume *p, int64_t n_render, int r_width, int r_height, const double *K_render, const double *P_render, const void *d_depth,
+                          int depth_dtype, const float *d_normal, int64_t n_views, int width, int height, const double *K, const double *P, const void *d_images,
+                          int64_t pitch, int channels, int image_dtype, const void *d_visibility, int visibility_dtype, double occlusion_tol, double cos_min, int mode,
+                          const double *fill, void *d_colour, int colour_dtype, float *d_weight, uint16_t *d_count, int32_t *d_best, void *stream);
+int pcs_tsdf_colour_last_kernel_ms(pcs_tsdf_volume *p, float *normals_ms, float *colour_ms);
 
 /* ------------------------------------------------------------------------------------------------
  * The target pose of every image in a calibrated rig (csrc/ba_rigpose.hpp).  Since pcs_version() 110.

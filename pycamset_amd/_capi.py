@@ -64,6 +64,8 @@ TSDF_MAX_DIM, TSDF_MAX_WEIGHT = 1024, 65535
 # include/pcs_hip.h PCS_TSDF_RAY_* and PCS_TSDF_RAYCAST_NO_SKIP: per-pixel status of the ray-cast and its flag
 TSDF_RAY_HIT, TSDF_RAY_NO_NORMAL, TSDF_RAY_NO_CROSSING, TSDF_RAY_MISSED = 0, 1, 2, 3
 TSDF_RAYCAST_NO_SKIP = 1
+# include/pcs_hip.h PCS_COLOUR_*: how the contributing views of a point are combined
+COLOUR_MODE_IDS = {"blend": 0, "best": 1}
 RIGPOSE_RESIDUALS = 1                    # include/pcs_hip.h PCS_RIGPOSE_RESIDUALS
 # include/pcs_hip.h PCS_RIGPOSE_*: per-image status of the rig localiser (the meanings of PCS_PNP_*)
 RIGPOSE_NOT_ESTIMATED, RIGPOSE_CONVERGED, RIGPOSE_MAX_ITER, RIGPOSE_NO_DECREASE = 0, 1, 2, 3
@@ -249,6 +251,12 @@ SYMBOLS = {
     "pcs_tsdf_raycast": (c_int, [_P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double), c_int, c_double, c_double, c_double, _P, c_int, _P, _P, c_int, _P]),
     "pcs_tsdf_raycast_last_kernel_ms": (c_int, [_P, POINTER(c_float), POINTER(c_float)]),
     "pcs_tsdf_raycast_count_samples": (c_int, [_P, _P, _P]),
+    "pcs_tsdf_point_normals": (c_int, [_P, c_int64, _P, c_int, c_int, _P, _P, _P]),
+    "pcs_tsdf_colour_points": (c_int, [_P, c_int64, _P, c_int, _P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double), _P, c_int64, c_int, c_int, _P, c_int, c_double, c_double,
+                                       c_int, POINTER(c_double), _P, c_int, _P, _P, _P, _P]),
+    "pcs_tsdf_colour_views": (c_int, [_P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double), _P, c_int, _P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double), _P,
+                                      c_int64, c_int, c_int, _P, c_int, c_double, c_double, c_int, POINTER(c_double), _P, c_int, _P, _P, _P, _P]),
+    "pcs_tsdf_colour_last_kernel_ms": (c_int, [_P, POINTER(c_float), POINTER(c_float)]),
     "pcs_rigpose_create": (c_int, [POINTER(_P), c_int, c_int64, c_int64]),
     "pcs_rigpose_destroy": (c_int, [_P]),
     "pcs_rigpose_set_cameras": (c_int, [_P, POINTER(c_double)]),

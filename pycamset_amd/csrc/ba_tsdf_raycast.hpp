@@ -138,6 +138,24 @@ __device__ __forceinline__ bool tsdf_ray_normal_sample(const TsdfRaycastArgs &a,
     return tsdf_ray_sample_at<S>(a, g0, g1, g2, T);
 }
 
+// the normal at grid point g: central differences of T one node apart, taken in the order +x, -x, +y, -y, +z, -z; false (n untouched)
+// when one of the six samples fails or |G| is not > 0.  Shared with tsdf_point_normals_kernel (ba_tsdf_colour.hpp).
+template <class S>
+__device__ __forceinline__ bool tsdf_ray_normal(const TsdfRaycastArgs &a, double g0, double g1, double g2, double &n0, double &n1, double &n2, unsigned &evaluated) {
+#pragma clang fp contract(off)
+    double Ta, Tb, G0 = 0.0, G1 = 0.0, G2 = 0.0;
+    bool ok = tsdf_ray_normal_sample<S>(a, g0 + 1.0, g1, g2, Ta, evaluated) && tsdf_ray_normal_sample<S>(a, g0 - 1.0, g1, g2, Tb, evaluated);
+    if (ok) G0 = Ta - Tb;
+    ok = ok && tsdf_ray_normal_sample<S>(a, g0, g1 + 1.0, g2, Ta, evaluated) && tsdf_ray_normal_sample<S>(a, g0, g1 - 1.0, g2, Tb, evaluated);
+    if (ok) G1 = Ta - Tb;
+    ok = ok && tsdf_ray_normal_sample<S>(a, g0, g1, g2 + 1.0, Ta, evaluated) && tsdf_ray_normal_sample<S>(a, g0, g1, g2 - 1.0, Tb, evaluated);
+    if (ok) G2 = Ta - Tb;
+    const double len = sqrt((G0 * G0 + G1 * G1) + G2 * G2);
+    ok = ok && len > 0.0;   // a NaN fails
+    if (ok) n0 = G0 / len, n1 = G1 / len, n2 = G2 / len;
+    return ok;
+}
+
 // one axis of the clip: false when the ray runs along the axis outside the slab
 __device__ __forceinline__ bool tsdf_ray_clip(double gc, double gw, int n, double &z0, double &z1) {
 #pragma clang fp contract(off)
@@ -216,17 +234,7 @@ __global__ __launch_bounds__(TSDF_RAY_BLOCK *TSDF_RAY_BLOCK) void tsdf_raycast_k
         }
         if (status == TSDF_RAY_HIT && a.normal) {
             const double g0 = gc0 + depth * gw0, g1 = gc1 + depth * gw1, g2 = gc2 + depth * gw2;
-            double Ta, Tb, G0 = 0.0, G1 = 0.0, G2 = 0.0;
-            bool ok = tsdf_ray_normal_sample<S>(a, g0 + 1.0, g1, g2, Ta, evaluated) && tsdf_ray_normal_sample<S>(a, g0 - 1.0, g1, g2, Tb, evaluated);
-            if (ok) G0 = Ta - Tb;
-            ok = ok && tsdf_ray_normal_sample<S>(a, g0, g1 + 1.0, g2, Ta, evaluated) && tsdf_ray_normal_sample<S>(a, g0, g1 - 1.0, g2, Tb, evaluated);
-            if (ok) G1 = Ta - Tb;
-            ok = ok && tsdf_ray_normal_sample<S>(a, g0, g1, g2 + 1.0, Ta, evaluated) && tsdf_ray_normal_sample<S>(a, g0, g1, g2 - 1.0, Tb, evaluated);
-            if (ok) G2 = Ta - Tb;
-            const double len = sqrt((G0 * G0 + G1 * G1) + G2 * G2);
-            ok = ok && len > 0.0;   // a NaN fails
-            if (ok) n0 = G0 / len, n1 = G1 / len, n2 = G2 / len;
-            else status = TSDF_RAY_NO_NORMAL;
+            if (!tsdf_ray_normal<S>(a, g0, g1, g2, n0, n1, n2, evaluated)) status = TSDF_RAY_NO_NORMAL;
         }
     }
     const int64_t p = ((int64_t)v * a.H + y) * a.W + x;

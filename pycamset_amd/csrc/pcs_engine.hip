@@ -59,6 +59,7 @@
 #include "ba_sweep.hpp"
 #include "ba_tsdf.hpp"
 #include "ba_tsdf_raycast.hpp"
+#include "ba_tsdf_colour.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // host side

@@ -3,11 +3,12 @@
 // of the last integration and the extraction's workspace: the cell flags, the cell -> vertex map, the quad flags and the block counts
 // and offsets of the two compactions (stereo_count_kernel / stereo_scan_kernel, unchanged).  Depth maps, vertices and quads are the
 // caller's device buffers.  The ray-cast (kernels: ba_tsdf_raycast.hpp) adds the table of the render views and the brick mask; it reads
-// the volume only.  Fence and timers are those of pcs_handle.inc (DESIGN.md, "Batched handles").
+// the volume only.  The colour stage (kernels: ba_tsdf_colour.hpp) adds the table of the source views and of its own render views; it
+// reads the volume for the point normals only.  Fence and timers are those of pcs_handle.inc (DESIGN.md, "Batched handles").
 struct pcs_tsdf_volume {
     HandleCore core;
-    KernelTimer t_integrate, t_count, t_write, t_mask, t_cast;
-    DevBuf views, list, sum, weight, cflag, map, qflag, blk, coff, qoff, rviews, brick;
+    KernelTimer t_integrate, t_count, t_write, t_mask, t_cast, t_pnormal, t_colour;
+    DevBuf views, list, sum, weight, cflag, map, qflag, blk, coff, qoff, rviews, brick, cviews, crviews;
     int64_t n_views = 0, n_integrated = 0;   // n_integrated: views integrated since the volume was zeroed (no weight can exceed it)
     int width = 0, height = 0;
     TsdfGrid g{};
@@ -96,6 +97,8 @@ int pcs_tsdf_create(pcs_tsdf_volume **out, int device) {
     if (e == hipSuccess) e = p->t_write.create();
     if (e == hipSuccess) e = p->t_mask.create();
     if (e == hipSuccess) e = p->t_cast.create();
+    if (e == hipSuccess) e = p->t_pnormal.create();
+    if (e == hipSuccess) e = p->t_colour.create();
     if (e != hipSuccess) {
         const int rc = fail(PCS_ERR_HIP, "pcs_tsdf_create: %s", hipGetErrorString(e));
         pcs_tsdf_destroy(p);
@@ -107,8 +110,9 @@ int pcs_tsdf_create(pcs_tsdf_volume **out, int device) {
 
 int pcs_tsdf_destroy(pcs_tsdf_volume *p) {
     if (!p) return PCS_OK;
-    p->core.destroy({&p->views, &p->list, &p->sum, &p->weight, &p->cflag, &p->map, &p->qflag, &p->blk, &p->coff, &p->qoff, &p->rviews, &p->brick},
-                    {&p->t_integrate, &p->t_count, &p->t_write, &p->t_mask, &p->t_cast});
+    p->core.destroy({&p->views, &p->list, &p->sum, &p->weight, &p->cflag, &p->map, &p->qflag, &p->blk, &p->coff, &p->qoff, &p->rviews, &p->brick,
+                     &p->cviews, &p->crviews},
+                    {&p->t_integrate, &p->t_count, &p->t_write, &p->t_mask, &p->t_cast, &p->t_pnormal, &p->t_colour});
     delete p;
     return PCS_OK;
 }
@@ -400,6 +404,219 @@ int pcs_tsdf_last_kernel_ms(pcs_tsdf_volume *p, float *integrate_ms, float *coun
         if (const int rc = timer_ms(who, &p->t_count, count_ms, "no count has run yet")) return rc;
     if (write_ms)
         if (const int rc = timer_ms(who, &p->t_write, write_ms, "no write has run yet")) return rc;
+    return PCS_OK;
+}
+
+}  // extern "C"
+
+// ---- colour of surface points from the images (include/pcs_hip.h, row f19; kernels: ba_tsdf_colour.hpp) -----------------------------------------
+static_assert(TSDF_COLOUR_BLEND == PCS_COLOUR_BLEND && TSDF_COLOUR_BEST == PCS_COLOUR_BEST, "modes of pcs_hip.h");
+
+// What both colour entry points take of the source views, the images, the visibility maps, the rule's settings and the outputs.
+struct TsdfColourSource {
+    int64_t n_views;
+    int width, height;
+    const double *K, *P;
+    const void *d_images;
+    int64_t pitch;
+    int channels, image_dtype;
+    const void *d_visibility;
+    int visibility_dtype;
+    double occlusion_tol, cos_min;
+    int mode;
+    const double *fill;
+    void *d_colour;
+    int colour_dtype;
+    float *d_weight;
+    uint16_t *d_count;
+    int32_t *d_best;
+};
+
+// Every argument of the source side: nothing here touches the device.
+static int tsdf_check_colour_source(const char *who, const TsdfColourSource &c) {
+    if (const int rc = fuse_check_views(who, c.n_views, c.width, c.height, c.K, c.P)) return rc;
+    if (c.width < 2 || c.height < 2) return fail(PCS_ERR_ARG, "%s: width %d, height %d: a source image needs both sides >= 2", who, c.width, c.height);
+    if (c.channels != 1 && c.channels != 3 && c.channels != 4) return fail(PCS_ERR_ARG, "%s: channels %d (1, 3 or 4)", who, c.channels);
+    if (c.image_dtype != PCS_IMAP_U8 && c.image_dtype != PCS_IMAP_F32) return fail(PCS_ERR_ARG, "%s: image_dtype PCS_IMAP_U8 or PCS_IMAP_F32", who);
+    const int64_t esz = c.image_dtype == PCS_IMAP_U8 ? 1 : 4;
+    if (c.pitch < (int64_t)c.width * c.channels * esz || c.pitch % esz != 0 || c.pitch > ((int64_t)1 << 40))
+        return fail(PCS_ERR_ARG, "%s: pitch %lld must be a multiple of the element size, at least width * channels * element size = %lld", who, (long long)c.pitch,
+                    (long long)((int64_t)c.width * c.channels * esz));
+    if (!c.d_images) return fail(PCS_ERR_ARG, "%s: d_images must be given", who);
+    if ((uintptr_t)c.d_images % (uintptr_t)esz != 0) return fail(PCS_ERR_ARG, "%s: d_images is not aligned to its element size", who);
+    if (c.d_visibility) {
+        if (c.visibility_dtype != PCS_F64 && c.visibility_dtype != PCS_F32) return fail(PCS_ERR_ARG, "%s: visibility_dtype PCS_F64 or PCS_F32", who);
+        if (!std::isfinite(c.occlusion_tol) || !(c.occlusion_tol >= 0.0)) return fail(PCS_ERR_ARG, "%s: occlusion_tol must be finite and >= 0 (got %g)", who, c.occlusion_tol);
+    }
+    if (!(c.cos_min >= 0.0 && c.cos_min < 1.0)) return fail(PCS_ERR_ARG, "%s: cos_min %g outside [0, 1)", who, c.cos_min);
+    if (c.mode != PCS_COLOUR_BLEND && c.mode != PCS_COLOUR_BEST) return fail(PCS_ERR_ARG, "%s: mode PCS_COLOUR_BLEND or PCS_COLOUR_BEST", who);
+    for (int k = 0; c.fill && k < c.channels; ++k)
+        if (std::isinf(c.fill[k])) return fail(PCS_ERR_ARG, "%s: fill[%d] is infinite", who, k);
+    if (c.colour_dtype != PCS_IMAP_U8 && c.colour_dtype != PCS_IMAP_F32) return fail(PCS_ERR_ARG, "%s: colour_dtype PCS_IMAP_U8 or PCS_IMAP_F32", who);
+    if (!c.d_colour) return fail(PCS_ERR_ARG, "%s: d_colour must be given", who);
+    return PCS_OK;
+}
+
+// The table of the source views: per view the 16 doubles of pcs_fuse_set_views, then the centre C of the render rows, then one unused
+static std::vector<double> tsdf_colour_rows(int64_t n_views, const double *K, const double *P) {
+    const std::vector<double> fuse = fuse_view_rows(n_views, K, P), render = tsdf_render_rows(n_views, K, P);
+    std::vector<double> rows(TSDF_COLOUR_ROW * (size_t)n_views, 0.0);
+    for (int64_t v = 0; v < n_views; ++v) {
+        std::copy(fuse.begin() + 16 * v, fuse.begin() + 16 * v + 16, rows.begin() + TSDF_COLOUR_ROW * v);
+        std::copy(render.begin() + 16 * v + 13, render.begin() + 16 * v + 16, rows.begin() + TSDF_COLOUR_ROW * v + 16);
+    }
+    return rows;
+}
+
+static TsdfColourArgs tsdf_colour_args(const pcs_tsdf_volume *p, const TsdfColourSource &c) {
+    TsdfColourArgs a{};
+    a.views = p->cviews.as<const double>(), a.n_views = (int)c.n_views, a.W = c.width, a.H = c.height, a.images = c.d_images, a.pitch = c.pitch;
+    a.vis = c.d_visibility, a.vis_f32 = c.visibility_dtype == PCS_F32, a.tol = c.d_visibility ? c.occlusion_tol : 0.0, a.cos_min = c.cos_min, a.mode = c.mode;
+    for (int k = 0; k < 4; ++k) a.fill[k] = c.fill && k < c.channels ? c.fill[k] : 0.0;
+    a.colour = c.d_colour, a.colour_f32 = c.colour_dtype == PCS_IMAP_F32, a.weight = c.d_weight, a.count = c.d_count, a.best = c.d_best;
+    return a;
+}
+
+// One of the 2 x 2 x 3 x 2 x 2 instantiations of either colour kernel.  TP: the points' type, or the depth maps' for the render views.
+template <bool VIEWS, class TI, class TP, int C, bool VIS, bool NRM>
+static void tsdf_colour_launch5(dim3 grid, dim3 block, hipStream_t s, const TsdfColourArgs &a) {
+    if constexpr (VIEWS) hipLaunchKernelGGL((tsdf_colour_views_kernel<TI, TP, C, VIS, NRM>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((tsdf_colour_points_kernel<TI, TP, C, VIS, NRM>), grid, block, 0, s, a);
+}
+template <bool VIEWS, class TI, class TP, int C>
+static void tsdf_colour_launch3(bool vis, bool nrm, dim3 grid, dim3 block, hipStream_t s, const TsdfColourArgs &a) {
+    if (vis && nrm) tsdf_colour_launch5<VIEWS, TI, TP, C, true, true>(grid, block, s, a);
+    else if (vis) tsdf_colour_launch5<VIEWS, TI, TP, C, true, false>(grid, block, s, a);
+    else if (nrm) tsdf_colour_launch5<VIEWS, TI, TP, C, false, true>(grid, block, s, a);
+    else tsdf_colour_launch5<VIEWS, TI, TP, C, false, false>(grid, block, s, a);
+}
+template <bool VIEWS, class TI, class TP>
+static void tsdf_colour_launch2(int channels, bool vis, bool nrm, dim3 grid, dim3 block, hipStream_t s, const TsdfColourArgs &a) {
+    if (channels == 1) tsdf_colour_launch3<VIEWS, TI, TP, 1>(vis, nrm, grid, block, s, a);
+    else if (channels == 3) tsdf_colour_launch3<VIEWS, TI, TP, 3>(vis, nrm, grid, block, s, a);
+    else tsdf_colour_launch3<VIEWS, TI, TP, 4>(vis, nrm, grid, block, s, a);
+}
+template <bool VIEWS>
+static void tsdf_colour_launch(bool image_f32, bool point_f32, int channels, bool vis, bool nrm, dim3 grid, dim3 block, hipStream_t s, const TsdfColourArgs &a) {
+    if (image_f32 && point_f32) tsdf_colour_launch2<VIEWS, float, float>(channels, vis, nrm, grid, block, s, a);
+    else if (image_f32) tsdf_colour_launch2<VIEWS, float, double>(channels, vis, nrm, grid, block, s, a);
+    else if (point_f32) tsdf_colour_launch2<VIEWS, uint8_t, float>(channels, vis, nrm, grid, block, s, a);
+    else tsdf_colour_launch2<VIEWS, uint8_t, double>(channels, vis, nrm, grid, block, s, a);
+}
+
+static int tsdf_check_points(const char *who, int64_t n, const void *d_points, int point_dtype) {
+    if (n < 0 || n > (int64_t)INT32_MAX * TSDF_COLOUR_BLOCK) return fail(PCS_ERR_ARG, "%s: n %lld outside [0, %lld]", who, (long long)n, (long long)INT32_MAX * TSDF_COLOUR_BLOCK);
+    if (point_dtype != PCS_F64 && point_dtype != PCS_F32) return fail(PCS_ERR_ARG, "%s: point_dtype PCS_F64 or PCS_F32", who);
+    if (n > 0 && !d_points) return fail(PCS_ERR_ARG, "%s: d_points must be given", who);
+    return PCS_OK;
+}
+
+extern "C" {
+
+// The cast's normal rule at n arbitrary points (mesh vertices): reads the volume only.
+int pcs_tsdf_point_normals(pcs_tsdf_volume *p, int64_t n, const void *d_points, int point_dtype, int min_weight, float *d_normals, uint8_t *d_status, void *stream) {
+    const char *who = "pcs_tsdf_point_normals";
+    if (const int rc = tsdf_check_points(who, n, d_points, point_dtype)) return rc;
+    if (min_weight < 1 || min_weight > TSDF_MAX_WEIGHT) return fail(PCS_ERR_ARG, "%s: min_weight %d outside [1, %d]", who, min_weight, TSDF_MAX_WEIGHT);
+    if (n > 0 && !d_normals) return fail(PCS_ERR_ARG, "%s: d_normals must be given", who);
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (!p->have_grid) return fail(PCS_ERR_ARG, "%s: no grid: pcs_tsdf_set_grid comes first", who);
+    if (n == 0) return PCS_OK;
+    HIPCHK(hipSetDevice(p->core.device));
+    hipStream_t s = p->core.stream_or(stream);
+    HIPCHK(p->core.fence.before_run(s, false));
+    TsdfPointNormalArgs a{};
+    a.field.sum = p->sum.p, a.field.weight = p->weight.as<const uint16_t>(), a.field.g = p->g, a.field.min_weight = min_weight;
+    a.n = n, a.points = d_points, a.normals = d_normals, a.status = d_status;
+    const dim3 grid((unsigned)((n + TSDF_COLOUR_BLOCK - 1) / TSDF_COLOUR_BLOCK)), block(TSDF_COLOUR_BLOCK);
+    HIPCHK(hipEventRecord(p->t_pnormal.e0, s));
+    const bool p32 = point_dtype == PCS_F32;
+    if (p->f32 && p32) hipLaunchKernelGGL((tsdf_point_normals_kernel<float, float>), grid, block, 0, s, a);
+    else if (p->f32) hipLaunchKernelGGL((tsdf_point_normals_kernel<float, double>), grid, block, 0, s, a);
+    else if (p32) hipLaunchKernelGGL((tsdf_point_normals_kernel<double, float>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((tsdf_point_normals_kernel<double, double>), grid, block, 0, s, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->t_pnormal.e1, s));
+    p->t_pnormal.timed = true;
+    HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+// The colour of n caller-supplied points (the rule: include/pcs_hip.h).  K, P and fill are HOST arrays and are copied; the points, the
+// normals, the images, the visibility maps and every output are DEVICE buffers.  It needs no grid and leaves the volume, the
+// integration's view table, a preceding count and the last cast as they are.
+int pcs_tsdf_colour_points(pcs_tsdf_volume *p, int64_t n, const void *d_points, int point_dtype, const float *d_normals, int64_t n_views, int width, int height,
+                           const double *K, const double *P, const void *d_images, int64_t pitch, int channels, int image_dtype, const void *d_visibility,
+                           int visibility_dtype, double occlusion_tol, double cos_min, int mode, const double *fill, void *d_colour, int colour_dtype, float *d_weight,
+                           uint16_t *d_count, int32_t *d_best, void *stream) {
+    const char *who = "pcs_tsdf_colour_points";
+    const TsdfColourSource c{n_views, width, height, K, P, d_images, pitch, channels, image_dtype, d_visibility, visibility_dtype, occlusion_tol, cos_min, mode, fill,
+                             d_colour, colour_dtype, d_weight, d_count, d_best};
+    if (const int rc = tsdf_check_points(who, n, d_points, point_dtype)) return rc;
+    if (const int rc = tsdf_check_colour_source(who, c)) return rc;
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (n == 0) return PCS_OK;
+    const std::vector<double> rows = tsdf_colour_rows(n_views, K, P);
+    HIPCHK(p->core.quiesce());   // a queued colour run may still read the old table
+    const HostArray up[] = {{p->cviews, rows.data(), TSDF_COLOUR_ROW * n_views, sizeof(double)}};
+    if (const int rc = upload_host_arrays(p->core, up, 1)) return rc;
+    hipStream_t s = p->core.stream_or(stream);
+    HIPCHK(p->core.fence.before_run(s, false));
+    TsdfColourArgs a = tsdf_colour_args(p, c);
+    a.n = n, a.points = d_points, a.normals = d_normals;
+    const dim3 grid((unsigned)((n + TSDF_COLOUR_BLOCK - 1) / TSDF_COLOUR_BLOCK)), block(TSDF_COLOUR_BLOCK);
+    HIPCHK(hipEventRecord(p->t_colour.e0, s));
+    tsdf_colour_launch<false>(image_dtype == PCS_IMAP_F32, point_dtype == PCS_F32, channels, d_visibility != nullptr, d_normals != nullptr, grid, block, s, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->t_colour.e1, s));
+    p->t_colour.timed = true;
+    HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+// The same rule with the pixels of n_render render views as the points: pixel (x, y) at z-depth d_depth is C + z w by the cast's ray
+// formulas.  K_render, P_render, K, P and fill are HOST arrays and are copied.  Outputs in image order (n_render, r_height, r_width, ...).
+int pcs_tsdf_colour_views(pcs_tsdf_volume *p, int64_t n_render, int r_width, int r_height, const double *K_render, const double *P_render, const void *d_depth,
+                          int depth_dtype, const float *d_normal, int64_t n_views, int width, int height, const double *K, const double *P, const void *d_images,
+                          int64_t pitch, int channels, int image_dtype, const void *d_visibility, int visibility_dtype, double occlusion_tol, double cos_min, int mode,
+                          const double *fill, void *d_colour, int colour_dtype, float *d_weight, uint16_t *d_count, int32_t *d_best, void *stream) {
+    const char *who = "pcs_tsdf_colour_views";
+    const TsdfColourSource c{n_views, width, height, K, P, d_images, pitch, channels, image_dtype, d_visibility, visibility_dtype, occlusion_tol, cos_min, mode, fill,
+                             d_colour, colour_dtype, d_weight, d_count, d_best};
+    if (!K_render || !P_render) return fail(PCS_ERR_ARG, "%s: K_render (n_render, 4) and P_render (n_render, 12) must be given", who);
+    if (const int rc = fuse_check_views(who, n_render, r_width, r_height, K_render, P_render)) return rc;
+    if (n_render > 65535) return fail(PCS_ERR_ARG, "%s: n_render %lld above 65535", who, (long long)n_render);
+    if (depth_dtype != PCS_F64 && depth_dtype != PCS_F32) return fail(PCS_ERR_ARG, "%s: depth_dtype PCS_F64 or PCS_F32", who);
+    if (!d_depth) return fail(PCS_ERR_ARG, "%s: d_depth must be given", who);
+    if (const int rc = tsdf_check_colour_source(who, c)) return rc;
+    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    const std::vector<double> rows = tsdf_colour_rows(n_views, K, P), rrows = tsdf_render_rows(n_render, K_render, P_render);
+    HIPCHK(p->core.quiesce());
+    const HostArray up[] = {{p->cviews, rows.data(), TSDF_COLOUR_ROW * n_views, sizeof(double)}, {p->crviews, rrows.data(), 16 * n_render, sizeof(double)}};
+    if (const int rc = upload_host_arrays(p->core, up, 2)) return rc;
+    hipStream_t s = p->core.stream_or(stream);
+    HIPCHK(p->core.fence.before_run(s, false));
+    TsdfColourArgs a = tsdf_colour_args(p, c);
+    a.n = (int64_t)n_render * r_height * r_width, a.normals = d_normal, a.rviews = p->crviews.as<const double>(), a.depth = d_depth, a.RW = r_width, a.RH = r_height;
+    const dim3 grid((unsigned)((r_width + TSDF_RAY_BLOCK - 1) / TSDF_RAY_BLOCK), (unsigned)((r_height + TSDF_RAY_BLOCK - 1) / TSDF_RAY_BLOCK), (unsigned)n_render),
+        block(TSDF_RAY_BLOCK * TSDF_RAY_BLOCK);
+    HIPCHK(hipEventRecord(p->t_colour.e0, s));
+    tsdf_colour_launch<true>(image_dtype == PCS_IMAP_F32, depth_dtype == PCS_F32, channels, d_visibility != nullptr, d_normal != nullptr, grid, block, s, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->t_colour.e1, s));
+    p->t_colour.timed = true;
+    HIPCHK(p->core.fence.after_run(s));
+    return PCS_OK;
+}
+
+// Device time of the last pcs_tsdf_point_normals and of the last colour kernel (points or views); either pointer may be NULL.
+int pcs_tsdf_colour_last_kernel_ms(pcs_tsdf_volume *p, float *normals_ms, float *colour_ms) {
+    const char *who = "pcs_tsdf_colour_last_kernel_ms";
+    if (!p || (!normals_ms && !colour_ms)) return fail(PCS_ERR_ARG, "%s: bad arguments", who);
+    if (normals_ms)
+        if (const int rc = timer_ms(who, &p->t_pnormal, normals_ms, "no point normals have run yet")) return rc;
+    if (colour_ms)
+        if (const int rc = timer_ms(who, &p->t_colour, colour_ms, "no colour kernel has run yet")) return rc;
     return PCS_OK;
 }
 
