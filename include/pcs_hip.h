@@ -1253,6 +1253,82 @@ int pcs_sweep_run(pcs_plane_sweeper *p, const uint8_t *d_images, int64_t pitch, 
 int pcs_sweep_last_kernel_ms(pcs_plane_sweeper *p, float *kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * PatchMatch multi-view depth: a slanted plane per pixel, spread between pixels and refined at random (SURVEY 8 row f20;
+ * csrc/ba_patchmatch.hpp).  Since pcs_version() 130.
+ * Replaces: what the plane sweep above cannot give of the external program the reference exports its rig for (ACMMP is a PatchMatch
+ *           method: reconstruction/acmmp_utils.py, ReconParams, Camera.to_MVSnet_txt): unbiased depth on surfaces seen obliquely, depth
+ *           finer than a plane table, and a normal per pixel.  ACMMP is not reproduced: the rule below is the library's own, designed so
+ *           that the device can be held to equality.  tests/patchmatch_reference.py states it in NumPy.
+ * Inputs.  Views, images, intrinsics, extrinsics and neighbour lists are those of pcs_sweep_set_views / pcs_sweep_set_neighbours (at
+ * most PCS_PM_MAX_NEIGHBOURS = 16 per view).  A HOST table wrange (n_w, 2) float64, n_w = 1 or V, of inverse-depth bounds [w_lo, w_hi],
+ * 0 < w_lo < w_hi, both finite.  Census window cw x ch (the limits of pcs_stereo_sgm), rw = cw / 2, rh = ch / 2, and a window stride s
+ * in [1, 4]: the footprint is ((cw - 1) s + 1) x ((ch - 1) s + 1).  truncate tau in [1, cw ch - 1].  slope_max sigma (V doubles, > 0,
+ * finite, HOST): tan(largest slant) / min(fx, fy).  seed (uint64).
+ * State.  Per pixel of every view a plane (w, a, b) in float64 — w the inverse z-depth AT the pixel, a and b its change per pixel in x
+ * and y: the inverse depth of a plane is exactly affine in the pixel coordinates of a pinhole view — and an int32 cost.  STRICT pixels
+ * are those whose footprint lies inside the image: rows rh s .. H - 1 - rh s, columns rw s .. W - 1 - rw s; an empty rectangle is a valid
+ * call.  A non-strict pixel holds the plane (NaN, NaN, NaN) and cost -1.
+ * Admissible.  A plane is admissible at a pixel of view i iff w_lo <= w <= w_hi, |a| <= sigma_i w and |b| <= sigma_i w, in plain FP64 (the
+ * product first), a comparison with a NaN failing.
+ * Cost C of plane (w, a, b) at strict pixel p = (x, y) of view i:
+ *   1. for neighbour j the 12 numbers A, b of the sweep's step 1, formed by the same host code.
+ *   2. for window position (dx, dy), dx in -rw .. rw, dy in -rh .. rh, in FP64, plain IEEE operations in the order written, no
+ *      contraction: x' = x + s dx, y' = y + s dy (integers); omega = (w + a (s dx)) + b (s dy);
+ *      n_c = ((A_c0 x' + A_c1 y') + A_c2) + omega b_c for c = 0, 1, 2; u = n_0 / n_2, v = n_1 / n_2.
+ *   3. the sample is VALID iff omega > 0, n_2 > 0 and the sweep's step-2 range test passes on q_u = floor(16 u + 0.5),
+ *      q_v = floor(16 v + 0.5); g is the sweep's integer bilinear value in [0, 65280].
+ *   4. the descriptor has one bit per window position other than the centre, 1 iff g(dx, dy) < g(0, 0); it is valid iff every sample is.
+ *   5. the reference descriptor is the same census of I_i at the strided positions: I_i[y', x'] < I_i[y, x].
+ *   6. h_j = popcount of the xor of the two;  7. C_j = min(tau, h_j) when the descriptor is valid, tau outright when it is not;
+ *   8. C = sum over the list of C_j: an integer, so the order of a list does not change a bit.
+ * Random numbers: the generator of csrc/ba_consensus.hpp (mix = its splitmix64 finaliser, G = 0x9e3779b97f4a7c15), t the step counter:
+ *   k = mix(seed + G); k = mix(k ^ view); k = mix(k ^ (y W + x)); k = mix(k ^ t); r_d = double(mix(k + (d + 1) G) >> 11) 2^-53 in [0, 1).
+ *   A DRAW from (r_d, r_d+1, r_d+2) is w = w_lo + r_d (w_hi - w_lo), a = (sigma w)(2 r_d+1 - 1), b = (sigma w)(2 r_d+2 - 1).
+ * Initialise (t = 0; pcs_pm_init), every strict pixel: with a start depth map whose value d is valid (finite, > 0) the plane is
+ *   (clamp(1 / d, w_lo, w_hi), 0, 0); with start_planes = 1 the plane d_plane holds, where it is admissible; otherwise the draw from
+ *   (r_0, r_1, r_2).  cost = C of that plane (a start plane's cost is recomputed).
+ * Iterate (pcs_pm_iterate).  Iteration `it` (absolute, 0-based, at most 1000) runs colour c = 0, then c = 1; the colour of a pixel is
+ *   (x + y) & 1 and the half-iteration has t = 1 + 2 it + c.  Only strict pixels of colour c change, and they read only pixels of the
+ *   other colour, as those stood before the half-iteration.  Each tries these candidates in order; a candidate replaces the current
+ *   plane and cost iff it is admissible and its C is strictly less than the current cost:
+ *     propagation from the pixels at (ox, oy) = (-1, 0), (1, 0), (0, -1), (0, 1), (-5, 0), (5, 0), (0, -5), (0, 5), skipping a source that
+ *       is not strict: for its plane (w_q, a_q, b_q) the candidate is ((w_q - a_q ox) - b_q oy, a_q, b_q), the same plane read at p;
+ *     perturbation of the then-current plane (w, a, b), with rho = 2^-(2 + it) and delta = (sigma w) 2^-(1 + it):
+ *       A (w (1 + rho (2 r_0 - 1)), a, b);  B (w, a + delta (2 r_1 - 1), b + delta (2 r_2 - 1));
+ *       C (w (1 + rho (2 r_3 - 1)), a + delta (2 r_4 - 1), b + delta (2 r_5 - 1));  D the draw from (r_6, r_7, r_8),
+ *       each of B, C and D starting from whatever plane is current when its turn comes.
+ * Finish (pcs_pm_finish).  status (uint8), the first that applies: PCS_PM_NOT_STRICT; PCS_PM_NO_VIEW: cost >= tau (list length) (an empty
+ *   list gives it on every strict pixel).  depth = 1 / w, rounded once for a float32 output, NaN where status != 0.  normal, in the view's
+ *   camera frame, unit length, facing the camera: m = (a fx, b fy, (w + a (cx - x)) + b (cy - y)), normal = -m / sqrt((m_0^2 + m_1^2) +
+ *   m_2^2), of the depth's dtype, NaN where status != 0.
+ * No atomics.  A half-iteration depends only on the state before it: any tiling, a second run and any order of a neighbour list give
+ * identical bits, and iterations 0 .. n - 1 in one call equal any split of them over calls.
+ *   pcs_pm_create / pcs_pm_destroy / pcs_pm_set_views / pcs_pm_set_neighbours   as their pcs_sweep_* counterparts
+ *   pcs_pm_init            d_images (n_views, height, pitch BYTES); d_start_depth (n_views, height, width) of start_dtype or NULL;
+ *                          start_planes 0 or 1 (not with a start depth); d_plane (n_views, height, width, 3) float64 and d_cost
+ *                          (n_views, height, width) int32 are written (d_plane is read first when start_planes = 1)
+ *   pcs_pm_iterate         iterations first_iteration .. first_iteration + n_iterations - 1 on d_plane and d_cost in place
+ *   pcs_pm_finish          d_depth (n_views, height, width) of depth_dtype; optional (NULL: not written) d_normal (n_views, height,
+ *                          width, 3) of depth_dtype and d_status uint8.  It reads the tables of the last pcs_pm_init or pcs_pm_iterate.
+ *   pcs_pm_last_kernel_ms  device time of the last call's kernels
+ * Every argument is checked on the host before the device is touched (PCS_ERR_ARG; pcs_last_error names the argument); the handle is
+ * looked at last.  All buffers are DEVICE buffers of the caller unless marked HOST; a call is queued on `stream` (NULL = the handle's).
+ */
+typedef struct pcs_patchmatch pcs_patchmatch;
+enum { PCS_PM_NOT_STRICT = 1, PCS_PM_NO_VIEW = 2, PCS_PM_MAX_NEIGHBOURS = 16 };
+int pcs_pm_create(pcs_patchmatch **out, int device);
+int pcs_pm_destroy(pcs_patchmatch *p);
+int pcs_pm_set_views(pcs_patchmatch *p, int64_t n_views, int width, int height, const double *K, const double *P);
+int pcs_pm_set_neighbours(pcs_patchmatch *p, const int32_t *nbr_start, const int32_t *nbr, int64_t n);
+int pcs_pm_init(pcs_patchmatch *p, const uint8_t *d_images, int64_t pitch, const double *wrange, int64_t n_w, const double *slope_max, int census_w, int census_h, int stride,
+                int truncate, uint64_t seed, const void *d_start_depth, int start_dtype, int start_planes, double *d_plane, int32_t *d_cost, void *stream);
+int pcs_pm_iterate(pcs_patchmatch *p, int first_iteration, int n_iterations, const uint8_t *d_images, int64_t pitch, const double *wrange, int64_t n_w, const double *slope_max,
+                   int census_w, int census_h, int stride, int truncate, uint64_t seed, double *d_plane, int32_t *d_cost, void *stream);
+int pcs_pm_finish(pcs_patchmatch *p, int census_w, int census_h, int stride, int truncate, const double *d_plane, const int32_t *d_cost, void *d_depth, int depth_dtype,
+                  void *d_normal, uint8_t *d_status, void *stream);
+int pcs_pm_last_kernel_ms(pcs_patchmatch *p, float *kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * TSDF volume and surface extraction: from z-depth maps to a quad mesh (csrc/ba_tsdf.hpp).  Since pcs_version() 127.
  * Replaces: nothing the reference computes.  It draws everything as pyvista meshes, and leaves the step from views to a surface to the
  *           external multi-view program and to whatever mesher the user runs on that program's cloud.  The depth maps of pcs_sweep_run /

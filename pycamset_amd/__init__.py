@@ -6,7 +6,7 @@ first use and there is no CPU fallback.
 """
 from .detections import TargetDetection  # noqa: F401
 
-__all__ = ["TargetDetection", "Engine", "parameter_covariance", "ParameterCovariance", "handlers", "function_blocks", "compiled_helpers", "pose_seeding", "device_solver", "sharding", "synthetic", "imaging", "stereo", "fusion", "sweep", "volume", "raycast_views", "depth_residuals"]
+__all__ = ["TargetDetection", "Engine", "parameter_covariance", "ParameterCovariance", "handlers", "function_blocks", "compiled_helpers", "pose_seeding", "device_solver", "sharding", "synthetic", "imaging", "stereo", "fusion", "sweep", "patchmatch", "volume", "raycast_views", "depth_residuals", "refine_depth_maps"]
 __version__ = "0.1.0"
 
 
@@ -20,8 +20,11 @@ def __getattr__(name):
     if name in ("raycast_views", "depth_residuals"):
         from . import volume
         return getattr(volume, name)
+    if name == "refine_depth_maps":
+        from . import patchmatch
+        return patchmatch.refine_depth_maps
     if name in ("handlers", "function_blocks", "synthetic", "engine", "optimisation_handling", "sharding", "device_solver",
-                "compiled_helpers", "detections", "pose_seeding", "imaging", "stereo", "fusion", "sweep", "volume"):
+                "compiled_helpers", "detections", "pose_seeding", "imaging", "stereo", "fusion", "sweep", "patchmatch", "volume"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -59,6 +59,8 @@ STEREO_NOT_STRICT, STEREO_TEXTURE, STEREO_UNIQUENESS, STEREO_LEFT_RIGHT, STEREO_
 FUSE_INVALID_DEPTH, FUSE_FEW_VIEWS, FUSE_DUPLICATE, FUSE_MAX_NEIGHBOURS = 1, 2, 4, 32
 # include/pcs_hip.h PCS_SWEEP_*: status bits of the plane sweep and its limits
 SWEEP_NOT_STRICT, SWEEP_NO_VIEW, SWEEP_UNIQUENESS, SWEEP_MAX_NEIGHBOURS, SWEEP_MAX_PLANES = 1, 2, 4, 16, 1024
+# include/pcs_hip.h PCS_PM_*: status values of the PatchMatch depth and its limit
+PM_NOT_STRICT, PM_NO_VIEW, PM_MAX_NEIGHBOURS = 1, 2, 16
 # include/pcs_hip.h PCS_TSDF_*: the limits of the TSDF volume
 TSDF_MAX_DIM, TSDF_MAX_WEIGHT = 1024, 65535
 # include/pcs_hip.h PCS_TSDF_RAY_* and PCS_TSDF_RAYCAST_NO_SKIP: per-pixel status of the ray-cast and its flag
@@ -238,6 +240,14 @@ SYMBOLS = {
     "pcs_sweep_set_neighbours": (c_int, [_P, POINTER(c_int32), POINTER(c_int32), c_int64]),
     "pcs_sweep_run": (c_int, [_P, _P, c_int64, POINTER(c_double), c_int64, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P, _P]),
     "pcs_sweep_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
+    "pcs_pm_create": (c_int, [POINTER(_P), c_int]),
+    "pcs_pm_destroy": (c_int, [_P]),
+    "pcs_pm_set_views": (c_int, [_P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double)]),
+    "pcs_pm_set_neighbours": (c_int, [_P, POINTER(c_int32), POINTER(c_int32), c_int64]),
+    "pcs_pm_init": (c_int, [_P, _P, c_int64, POINTER(c_double), c_int64, POINTER(c_double), c_int, c_int, c_int, c_int, c_uint64, _P, c_int, c_int, _P, _P, _P]),
+    "pcs_pm_iterate": (c_int, [_P, c_int, c_int, _P, c_int64, POINTER(c_double), c_int64, POINTER(c_double), c_int, c_int, c_int, c_int, c_uint64, _P, _P, _P]),
+    "pcs_pm_finish": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, _P, _P, _P]),
+    "pcs_pm_last_kernel_ms": (c_int, [_P, POINTER(c_float)]),
     "pcs_tsdf_create": (c_int, [POINTER(_P), c_int]),
     "pcs_tsdf_destroy": (c_int, [_P]),
     "pcs_tsdf_set_views": (c_int, [_P, c_int64, c_int, c_int, POINTER(c_double), POINTER(c_double)]),

@@ -31,7 +31,7 @@ static int device_cu_count(int device) {
 }
 
 extern "C" {
-int pcs_version(void) { return 129; }
+int pcs_version(void) { return 130; }
 const char *pcs_last_error(void) { return g_err.c_str(); }
 
 int pcs_device_count(void) {

@@ -6,7 +6,7 @@
 // block-reduced normal equations, runs on the FP64 matrix cores (ba_normal.hpp).  See DESIGN.md.
 //
 // Kernels: ba_kernels.hpp (evaluation, compaction, legacy cost), ba_matfree.hpp (J products without J),
-// ba_normal.hpp (J^T J / J^T r), ba_triangulate.hpp, ba_pnp.hpp, ba_pnp_consensus.hpp, ba_intrinsics.hpp, ba_intr_consensus.hpp, ba_riggraph.hpp, ba_twoview.hpp, ba_fivepoint.hpp, ba_align.hpp, ba_imagemap.hpp, ba_stereo.hpp, ba_stereo_sgm.hpp, ba_fusion.hpp, ba_sweep.hpp; device maths: ba_device.hpp.  This file: the pcs_engine handle + its part of the C ABI; one translation unit with
+// ba_normal.hpp (J^T J / J^T r), ba_triangulate.hpp, ba_pnp.hpp, ba_pnp_consensus.hpp, ba_intrinsics.hpp, ba_intr_consensus.hpp, ba_riggraph.hpp, ba_twoview.hpp, ba_fivepoint.hpp, ba_align.hpp, ba_imagemap.hpp, ba_stereo.hpp, ba_stereo_sgm.hpp, ba_fusion.hpp, ba_sweep.hpp, ba_patchmatch.hpp; device maths: ba_device.hpp.  This file: the pcs_engine handle + its part of the C ABI; one translation unit with
 // pcs_common.inc (errors, device queries), pcs_handle.inc (what every handle shares), pcs_dettable.inc (the detection table of both engine kinds), pcs_triangulator.inc, pcs_pnp.inc, pcs_intrinsics.inc, pcs_rig.inc, pcs_solver.inc (handle-free solver + the LM trial) and pcs_genchain.inc, included in that order.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
@@ -57,6 +57,7 @@
 #include "ba_stereo_sgm.hpp"
 #include "ba_fusion.hpp"
 #include "ba_sweep.hpp"
+#include "ba_patchmatch.hpp"
 #include "ba_tsdf.hpp"
 #include "ba_tsdf_raycast.hpp"
 #include "ba_tsdf_colour.hpp"
@@ -77,6 +78,7 @@ using namespace pcs;
 #include "pcs_stereo.inc"
 #include "pcs_fusion.inc"
 #include "pcs_sweep.inc"
+#include "pcs_patchmatch.inc"
 #include "pcs_tsdf.inc"
 #include "pcs_rigpose.inc"
 #include "pcs_intrinsics.inc"

@@ -2,14 +2,22 @@
 // owns the views as given (host), the neighbour lists, the warp table — 12 doubles per entry of the lists, formed here in FP64 when the
 // lists are set — and the plane table of the last run.  Images and every output are the caller's device buffers; there is no workspace
 // that grows with the images: the cost volume lives in registers and LDS.  Fence and timer are those of pcs_handle.inc.
+// The views as given (host), the neighbour lists and the warp table: what pcs_sweep_set_views / pcs_sweep_set_neighbours keep, and
+// pcs_pm_set_views / pcs_pm_set_neighbours (pcs_patchmatch.inc) with them.
+struct RigViews {
+    DevBuf nbr_start, nbr, warp;      // warp: double (entries, 12)
+    std::vector<double> h_K, h_P;     // the views of set_views
+    int64_t n_views = 0, n_nbr_views = -1;
+    int width = 0, height = 0;
+    bool ready() const { return n_views != 0 && n_nbr_views == n_views; }
+};
+
 struct pcs_plane_sweeper {
     HandleCore core;
     KernelTimer t_kernel;
-    DevBuf nbr_start, nbr, warp, z;   // warp: double (entries, 12); z: double (n_z, D)
-    std::vector<double> h_K, h_P;     // the views of pcs_sweep_set_views
+    RigViews rig;
+    DevBuf z;                         // double (n_z, D)
     std::vector<double> h_z;          // what z holds
-    int64_t n_views = 0, n_nbr_views = -1;
-    int width = 0, height = 0;
 };
 
 static_assert(SWEEP_NOT_STRICT == PCS_SWEEP_NOT_STRICT && SWEEP_NO_VIEW == PCS_SWEEP_NO_VIEW && SWEEP_UNIQUENESS == PCS_SWEEP_UNIQUENESS, "status bits of pcs_hip.h");
@@ -36,6 +44,33 @@ static void sweep_warp(const double *Ki, const double *Pi, const double *Kj, con
     out[9] = Kj[0] * c[0] + Kj[1] * c[2];
     out[10] = Kj[2] * c[1] + Kj[3] * c[2];
     out[11] = c[2];
+}
+
+// The bodies of set_views and set_neighbours of both handles; `r` NULL: the handle was.
+static int rig_set_views(const char *who, RigViews *r, int64_t n_views, int width, int height, const double *K, const double *P) {
+    if (const int rc = fuse_check_views(who, n_views, width, height, K, P)) return rc;
+    if (!r) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    r->n_views = 0, r->n_nbr_views = -1;
+    r->h_K.assign(K, K + 4 * n_views), r->h_P.assign(P, P + 12 * n_views);
+    r->n_views = n_views, r->width = width, r->height = height;
+    return PCS_OK;
+}
+
+static int rig_set_neighbours(const char *who, const char *views_first, RigViews *r, const HandleCore *core, const int32_t *nbr_start, const int32_t *nbr, int64_t n) {
+    if (const int rc = fuse_check_neighbours(who, nbr_start, nbr, n, SWEEP_MAX_NBR)) return rc;
+    if (!r) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
+    if (r->n_views == 0) return fail(PCS_ERR_STATE, "%s: %s comes first", who, views_first);
+    if (n != r->n_views) return fail(PCS_ERR_ARG, "%s: n %lld differs from the %lld views of %s", who, (long long)n, (long long)r->n_views, views_first);
+    std::vector<double> warp(12 * (size_t)nbr_start[n]);
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t e = nbr_start[i]; e < nbr_start[i + 1]; ++e)
+            sweep_warp(&r->h_K[4 * i], &r->h_P[12 * i], &r->h_K[4 * (size_t)nbr[e]], &r->h_P[12 * (size_t)nbr[e]], &warp[12 * (size_t)e]);
+    HIPCHK(core->quiesce());   // a queued run may still read the old tables
+    r->n_nbr_views = -1;
+    const HostArray up[] = {{r->nbr_start, nbr_start, n + 1, sizeof(int32_t)}, {r->nbr, nbr, nbr_start[n], sizeof(int32_t)}, {r->warp, warp.data(), 12 * (int64_t)nbr_start[n], sizeof(double)}};
+    if (const int rc = upload_host_arrays(*core, up, 3)) return rc;
+    r->n_nbr_views = n;
+    return PCS_OK;
 }
 
 // Every argument of pcs_sweep_run but the handle: nothing here touches the device.
@@ -85,38 +120,18 @@ int pcs_sweep_create(pcs_plane_sweeper **out, int device) {
 
 int pcs_sweep_destroy(pcs_plane_sweeper *p) {
     if (!p) return PCS_OK;
-    p->core.destroy({&p->nbr_start, &p->nbr, &p->warp, &p->z}, {&p->t_kernel});
+    p->core.destroy({&p->rig.nbr_start, &p->rig.nbr, &p->rig.warp, &p->z}, {&p->t_kernel});
     delete p;
     return PCS_OK;
 }
 
 // K and P are HOST arrays and are copied.  New views drop the neighbour lists and with them the warp table.
 int pcs_sweep_set_views(pcs_plane_sweeper *p, int64_t n_views, int width, int height, const double *K, const double *P) {
-    const char *who = "pcs_sweep_set_views";
-    if (const int rc = fuse_check_views(who, n_views, width, height, K, P)) return rc;
-    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
-    p->n_views = 0, p->n_nbr_views = -1;
-    p->h_K.assign(K, K + 4 * n_views), p->h_P.assign(P, P + 12 * n_views);
-    p->n_views = n_views, p->width = width, p->height = height;
-    return PCS_OK;
+    return rig_set_views("pcs_sweep_set_views", p ? &p->rig : nullptr, n_views, width, height, K, P);
 }
 
 int pcs_sweep_set_neighbours(pcs_plane_sweeper *p, const int32_t *nbr_start, const int32_t *nbr, int64_t n) {
-    const char *who = "pcs_sweep_set_neighbours";
-    if (const int rc = fuse_check_neighbours(who, nbr_start, nbr, n, SWEEP_MAX_NBR)) return rc;
-    if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
-    if (p->n_views == 0) return fail(PCS_ERR_STATE, "%s: pcs_sweep_set_views comes first", who);
-    if (n != p->n_views) return fail(PCS_ERR_ARG, "%s: n %lld differs from the %lld views of pcs_sweep_set_views", who, (long long)n, (long long)p->n_views);
-    std::vector<double> warp(12 * (size_t)nbr_start[n]);
-    for (int64_t i = 0; i < n; ++i)
-        for (int32_t e = nbr_start[i]; e < nbr_start[i + 1]; ++e)
-            sweep_warp(&p->h_K[4 * i], &p->h_P[12 * i], &p->h_K[4 * (size_t)nbr[e]], &p->h_P[12 * (size_t)nbr[e]], &warp[12 * (size_t)e]);
-    HIPCHK(p->core.quiesce());   // a queued run may still read the old tables
-    p->n_nbr_views = -1;
-    const HostArray up[] = {{p->nbr_start, nbr_start, n + 1, sizeof(int32_t)}, {p->nbr, nbr, nbr_start[n], sizeof(int32_t)}, {p->warp, warp.data(), 12 * (int64_t)nbr_start[n], sizeof(double)}};
-    if (const int rc = upload_host_arrays(p->core, up, 3)) return rc;
-    p->n_nbr_views = n;
-    return PCS_OK;
+    return rig_set_neighbours("pcs_sweep_set_neighbours", "pcs_sweep_set_views", p ? &p->rig : nullptr, p ? &p->core : nullptr, nbr_start, nbr, n);
 }
 
 // z is a HOST table; it is uploaded when it differs from what the handle holds.
@@ -125,9 +140,9 @@ int pcs_sweep_run(pcs_plane_sweeper *p, const uint8_t *d_images, int64_t pitch, 
     const char *who = "pcs_sweep_run";
     if (const int rc = sweep_check_run(who, d_images, z, n_z, D, census_w, census_h, box_radius, truncate, uniqueness_ratio, d_depth, depth_dtype)) return rc;
     if (!p) return fail(PCS_ERR_ARG, "%s: NULL handle", who);
-    if (p->n_views == 0 || p->n_nbr_views != p->n_views) return fail(PCS_ERR_STATE, "%s: pcs_sweep_set_views and pcs_sweep_set_neighbours come first", who);
-    if (n_z != 1 && n_z != p->n_views) return fail(PCS_ERR_ARG, "%s: n_z %lld must be 1 or the %lld views", who, (long long)n_z, (long long)p->n_views);
-    if (pitch < p->width) return fail(PCS_ERR_ARG, "%s: pitch %lld is below the row size %d", who, (long long)pitch, p->width);
+    if (!p->rig.ready()) return fail(PCS_ERR_STATE, "%s: pcs_sweep_set_views and pcs_sweep_set_neighbours come first", who);
+    if (n_z != 1 && n_z != p->rig.n_views) return fail(PCS_ERR_ARG, "%s: n_z %lld must be 1 or the %lld views", who, (long long)n_z, (long long)p->rig.n_views);
+    if (pitch < p->rig.width) return fail(PCS_ERR_ARG, "%s: pitch %lld is below the row size %d", who, (long long)pitch, p->rig.width);
     int tw = stereo_env_int("PCS_SWEEP_TILE_COLUMNS", 8, 64);   // measurements, and the test of "any tiling gives the same bits"
     if (tw != 8 && tw != 16 && tw != 32 && tw != 64) tw = SWEEP_DEFAULT_TW;
     const int th = SWEEP_PPT * SWEEP_THREADS / tw;
@@ -146,12 +161,12 @@ int pcs_sweep_run(pcs_plane_sweeper *p, const uint8_t *d_images, int64_t pitch, 
         p->h_z = zt;
     }
     SweepArgs a{};
-    a.images = d_images, a.pitch = pitch, a.warp = p->warp.as<const double>(), a.nbr_start = p->nbr_start.as<const int32_t>(), a.nbr = p->nbr.as<const int32_t>();
-    a.z = p->z.as<const double>(), a.z_stride = n_z == 1 ? 0 : D, a.D = D, a.W = p->width, a.H = p->height;
+    a.images = d_images, a.pitch = pitch, a.warp = p->rig.warp.as<const double>(), a.nbr_start = p->rig.nbr_start.as<const int32_t>(), a.nbr = p->rig.nbr.as<const int32_t>();
+    a.z = p->z.as<const double>(), a.z_stride = n_z == 1 ? 0 : D, a.D = D, a.W = p->rig.width, a.H = p->rig.height;
     a.rw = census_w / 2, a.rh = census_h / 2, a.r = box_radius, a.tau = truncate, a.uniq = uniqueness_ratio;
     a.tw_log2 = tw == 8 ? 3 : tw == 16 ? 4 : tw == 32 ? 5 : 6;
     a.depth = d_depth, a.depth_f32 = depth_dtype == PCS_F32, a.level = d_level, a.cost = d_cost, a.status = d_status;
-    const dim3 grid((unsigned)((a.W + tw - 1) / tw), (unsigned)((a.H + th - 1) / th), (unsigned)p->n_views);
+    const dim3 grid((unsigned)((a.W + tw - 1) / tw), (unsigned)((a.H + th - 1) / th), (unsigned)p->rig.n_views);
     const size_t lds = (size_t)sweep_lds_bytes(tw, a.rw, a.rh, a.r);   // below 32 KiB at every admitted tile, window and box
     HIPCHK(hipEventRecord(p->t_kernel.e0, s));
     hipLaunchKernelGGL(sweep_kernel, grid, dim3(SWEEP_THREADS), lds, s, a);

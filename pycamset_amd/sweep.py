@@ -202,9 +202,12 @@ def sweep_depth_maps(images, K, ext, neighbours, planes, *, census=(5, 5), box=2
 
 def reconstruct_views(images, intr, ext, depth_range, steps=192, *, spacing="depth", neighbours=None, min_angle=3.0, max_angle=45.0, max_views=9, census=(5, 5), box=2,
                       truncate=None, uniqueness_ratio=15, interpolation: str = "bilinear", px_tol=1.0, rel_tol=0.01, min_views=2, unique=False, transform=None,
-                      dtype=np.float32, device=None):
+                      dtype=np.float32, device=None, refine_iterations=0):
     """From the images of a calibrated rig to one cloud: ``undistort_images`` -> ``view_neighbours`` -> ``sweep_depth_maps`` ->
-    ``fuse_depth_maps(values=, compact=True)``.  A thin composition: no kernel of its own.  ``images`` (C, H, W) uint8, one per camera;
+    ``fuse_depth_maps(values=, compact=True)``.  ``refine_iterations`` > 0: the sweep's depth maps pass through that many iterations of
+    ``patchmatch.refine_depth_maps`` in front of the fusion: its defaults, the search bounded by ``depth_range``, and ``max_slant`` =
+    90 - ``max_angle`` degrees (at most its default 70, at least 10) — a surface seen at slant s from one view is seen at up to s +
+    ``max_angle`` from a neighbour, and past 90 degrees there is nothing to match.  A thin composition: no kernel of its own.  ``images`` (C, H, W) uint8, one per camera;
     ``intr`` (C, 9); ``ext`` (C, 3, 4) world -> camera; ``depth_range`` = (depth_min, depth_max) and ``steps`` as ``ReconParams`` /
     ``to_MVSnet_txt`` hand them over.  ``neighbours`` defaults to ``view_neighbours(ext, min_angle, max_angle, max_views)``.  Every view
     keeps its own consistent pixels; ``unique=True`` leaves a surface element to the lowest view that sees it (``fuse_depth_maps``).
@@ -220,6 +223,11 @@ def reconstruct_views(images, intr, ext, depth_range, steps=192, *, spacing="dep
     nb = view_neighbours(E, min_angle, max_angle, min(int(max_views), SWEEP_MAX_NEIGHBOURS)) if neighbours is None else neighbours
     planes = depth_planes(depth_range, steps, spacing)
     depth = sweep_depth_maps(und, Kv, E, nb, planes, census=census, box=box, truncate=truncate, uniqueness_ratio=uniqueness_ratio, dtype=np.float64, device=dev)
+    if refine_iterations:
+        from .patchmatch import refine_depth_maps
+
+        depth = refine_depth_maps(und, Kv, E, nb, depth_range, depth, iterations=refine_iterations, max_slant=min(70.0, max(10.0, 90.0 - float(max_angle))), dtype=np.float64,
+                                  device=dev)
     clouds = fuse_depth_maps(depth, Kv, E, nb, px_tol=px_tol, rel_tol=rel_tol, min_views=min_views, unique=unique, transform=transform, values=und, compact=True, dtype=dtype,
                              device=dev)
     cat = _torch().cat if _is_tensor(clouds[0][0]) else np.concatenate
